@@ -16,6 +16,10 @@ Launched by ``python -m torch.distributed.run --nproc-per-node N ... bench.py --
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or directly as ``python bench.py
 --gpus N``: with WORLD_SIZE unset the parent starts the N ranks itself as fresh child processes
 BEFORE it touches any GPU, waits for them and relays rank 0's JSON line.  Prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, settle + warm up, time the K steps, write the last step's output if
+``--dump-outputs DIR`` is given, print the line.  ``--full`` adds every secondary measurement (roofline with live PMC traffic and the
+per-kernel pass, the other workloads under ``also``, the CPU oracle baseline and PSNR); the ``--no-*`` options trim a ``--full`` run.
 """
 from __future__ import annotations
 
@@ -129,6 +133,30 @@ def live_pmc_traffic(batch, timeout_s=180):
 
 def synthetic_frames(batch, shape, seed):
     return torch.from_numpy(np.random.default_rng(seed).integers(0, 256, (batch, shape[0], shape[1], 3), dtype=np.uint8))
+
+
+DUMP_WHOLE_MAX_ELEMS = 8 << 20     # up to 32 MB of float32: the whole output
+DUMP_SAMPLE_ELEMS = 4 << 20        # above that: 4 Mi values (16 MB) at fixed, seeded positions + their flat indices (32 MB of float64)
+
+
+def dump_outputs(out_dir, out):
+    """--dump-outputs: the frames the last timed step handed its caller (uint8 NHWC on the GPU), as float32 .npy files in out_dir (< 64 MB in
+    all).  upscaled_frames.npy is the whole output when it fits DUMP_WHOLE_MAX_ELEMS; otherwise upscaled_frames_sample.npy holds the values at
+    upscaled_frames_sample_index.npy (flat indices into the (N, H, W, 3) output, float64: exact; positions from a fixed seed, the same in every
+    run of the same arguments).  upscaled_frames_mean.npy (float64, N x 3) summarises every byte of the output, sampled or not."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    flat = out.reshape(-1)
+    if flat.numel() <= DUMP_WHOLE_MAX_ELEMS:
+        np.save(os.path.join(out_dir, "upscaled_frames.npy"), out.float().cpu().numpy())
+    else:
+        idx = np.unique(np.random.default_rng(20240).integers(0, flat.numel(), DUMP_SAMPLE_ELEMS, dtype=np.int64))
+        vals = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+        np.save(os.path.join(out_dir, "upscaled_frames_sample.npy"), vals)
+        np.save(os.path.join(out_dir, "upscaled_frames_sample_index.npy"), idx.astype(np.float64))
+    per_frame = out.reshape(out.shape[0], -1, out.shape[-1])
+    mean = per_frame.sum(dim=1, dtype=torch.float64) / per_frame.shape[1]
+    np.save(os.path.join(out_dir, "upscaled_frames_mean.npy"), mean.cpu().numpy())
 
 
 def cpu_baseline(workload, gpu_ctx, seconds_budget=14.0):
@@ -388,6 +416,10 @@ def main():
                     help="frames per step per GPU; 4 = the reference's stream-mode job size, small_batch_size = "
                          "min(4, fps) (src/sharkshark/pipeline.py:31,84), which is also what its README figure uses")
     ap.add_argument("--workload", default="rrdbnet", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements (roofline, also, cpu_baseline / PSNR); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last timed step's output frames (rank 0) to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-also", action="store_true", help="skip the short secondary-workload measurements")
@@ -436,9 +468,16 @@ def main():
         svc.upscale(frames, wait=False)
     torch.cuda.synchronize()
     # a step = one job through the service's frame-in/frame-out call; results are ordered on the job set's stream (wait=False, what the
-    # worker loop does) and the timed region ends with a device-wide synchronise
-    elapsed = run_timed(lambda: svc.upscale(frames, wait=False), args.steps, args.warmup, world, torch.cuda.synchronize,
-                        torch.device("cpu") if rehearse else device)
+    # worker loop does) and the timed region ends with a device-wide synchronise.  The step keeps its result: the last one is what
+    # --dump-outputs writes
+    last = {}
+
+    def step():
+        last["out"] = svc.upscale(frames, wait=False)
+    elapsed = run_timed(step, args.steps, args.warmup, world, torch.cuda.synchronize, torch.device("cpu") if rehearse else device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["out"])
+    del last
     total_frames = args.batch * args.steps * world
     fps = total_frames / elapsed
 
@@ -458,7 +497,7 @@ def main():
                    "fps_per_gpu": fps / world, "net_tflops_per_gpu": flops_per_frame * fps / world / 1e12},
     }
 
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         rl = conv_roofline(svc, frames, by_kernel=True)
         if rl is not None:
             traffic, traffic_src, result_traffic_by_kernel = None, None, None
@@ -528,7 +567,7 @@ def main():
                 result["roofline"] = {"bound": "mfma", "achieved": dom["achieved_tflops"], "peak": dom["peak_tflops"], "unit": "TFLOP/s",
                                       "frac": dom["frac"], "traffic": None, "kernel": "fsrcnn stage: " + name, "peak_is": dom["peak_is"],
                                       "stages": stages}
-    if rank == 0 and world == 1 and not args.no_also and args.workload == "rrdbnet":
+    if args.full and rank == 0 and world == 1 and not args.no_also and args.workload == "rrdbnet":
         # the other single-GPU BASELINE configs and the 1-frame (image-server / latency) job, measured the
         # same way (short, outside the headline timing); conv-based ones carry their own roofline fraction
         also = {}
@@ -625,7 +664,7 @@ def main():
         except Exception as e:  # never lose the headline line to a secondary measurement
             also["host_frames"] = {"error": f"{type(e).__name__}: {e}"}
         result["also"] = also
-    if rank == 0 and "roofline" in result and args.workload == "rrdbnet" and world == 1 and not args.no_by_kernel:
+    if args.full and rank == 0 and "roofline" in result and args.workload == "rrdbnet" and world == 1 and not args.no_by_kernel:
         # per kernel build, from a ONE-CHAIN run of the same job (SS4K_MODEL_ONE_CHAIN: with two launch chains in flight a launch's
         # duration includes the time it shares the chip with the other chain's launch - nobody should have to divide by 1.9).
         # Placed after every other measurement: before the library tested its lane stream (ss4k_stream_pair_check), a leg that ran AFTER
@@ -643,7 +682,7 @@ def main():
             torch.cuda.empty_cache()
         except Exception as e:  # never lose the headline line to a secondary measurement
             result["roofline"]["by_kernel"] = {"error": str(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb, psnr = cpu_baseline(args.workload, _capi.Context(local))
         result["cpu_baseline"] = cb
         result["psnr_db_vs_cpu_ref"] = psnr

@@ -56,7 +56,7 @@ def test_bench_two_ranks_rehearsed_on_one_gpu():
     over gloo.  Every line of the N > 1 path runs: the group, rank 0 generating the weights, the broadcast into rank 1's service worker,
     the barrier-bracketed timed region, the max over ranks, rank 0's one JSON line relayed by the parent."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], cwd=ROOT, env=_env(SS4K_BENCH_REHEARSE_ON_ONE_GPU="1"), capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], cwd=ROOT, env=_env(SS4K_BENCH_REHEARSE_ON_ONE_GPU="1"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                                     # stdout is the one JSON line

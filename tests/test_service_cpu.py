@@ -201,20 +201,6 @@ def test_on_queue_as_bound_method_of_the_pipeline_that_owns_two_services(method)
         pipe.stop()
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference"), reason="container-only: drives the reference's own caller modules")
-def test_reference_callers_drive_the_service_with_one_import_swapped():
-    """`tests/golden/drive_reference_callers.py`: the reference's real ``TwitchUpscalerPostStreamer`` (recorder callback -> OUR worker ->
-    its ``upscaler_on_queue`` bound method -> its streamer's queue) and its real image-server module (its handler thread, its
-    ``start_pipeline()`` constructor call, its ``pipeline_onqueue`` global) run against a CPU double of ``HipUpscalerService`` - with the
-    reference's own ``UpscalerQueueEntry`` / ``Profiler`` / ``RecoderEntry`` / ``TwitchStreamerEntry`` objects in the queues."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tests", "golden", "drive_reference_callers.py")], cwd=root, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "DRIVE OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
-
-
 class HeldResults(NearestDouble):
     """A double whose results are 'on the device' for a while: ready 30 ms after the job was taken, up to two of them may be held."""
 

@@ -9,7 +9,7 @@ want() { [ "$ONLY" = all ] || [[ ",$ONLY," == *",$1,"* ]]; }
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/$TAG; mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-also --no-by-kernel --no-live-traffic"
+B="python3 bench.py --full --no-cpu-baseline --no-also --no-by-kernel --no-live-traffic"
 if want 1; then
 # 1. headline: per-kernel stats + the bench line printed under the profiler + how many conv launches are in flight
 #    (frame lanes: two concurrent launch chains; the choice is measured by the library over its first calls)
@@ -85,7 +85,7 @@ if want 6; then
 DEV=$PWD/sharkshark-4k_amd/libss4k_hip_dev.so
 { for b in 4 2 1; do SS4K_LIB=$DEV python3 tools/env_ab.py "SS4K_D16=0;SS4K_D16=1" $b 3 2>&1 | grep -v "^HipUpscalerService"; done
   SS4K_LIB=$DEV SS4K_D16=1 SS4K_D16_STAMP=1 python3 tools/env_ab.py "SS4K_D16=1" 4 1 2>&1 | grep "d16 K1" | head -4
-  for d in 0 1; do SS4K_LIB=$DEV SS4K_D16=$d python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-also --no-live-traffic 2>/dev/null | python3 -c "
+  for d in 0 1; do SS4K_LIB=$DEV SS4K_D16=$d python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-also --no-live-traffic 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); bk=d['roofline']['by_kernel']
 print('SS4K_D16=$d: headline %.1f frames/s, conv frac %.3f; one chain, per kernel build:' % (d['value'], d['roofline']['frac']))

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 for r in 1 2 3; do
   for v in $VALS; do
     echo -n "round $r $VAR=$v: "
-    env $VAR=$v python3 bench.py --no-cpu-baseline --no-by-kernel --steps 40 --warmup 10 "$@" 2>/dev/null | python3 -c "
+    env $VAR=$v python3 bench.py --full --no-cpu-baseline --no-by-kernel --steps 40 --warmup 10 "$@" 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); a=d.get('also',{}); print(round(d['value'],2), round(d['roofline']['frac'],4), {k:round(v['fps'],1) for k,v in a.items() if 'fps' in v})"
   done
 done
