@@ -83,7 +83,9 @@ enum {
   /* --- what a deployment may want to choose ---------------------------------------------------------------------------------- */
   SS4K_MODEL_FS_EXACT = 1,      /* FSRCNN: exact-fp32 kernels for every stage instead of the fp16 hi/lo-split matrix-core
                                    stages (fp32-grade, ~1e-6 of the exact ones); also chosen automatically when the
-                                   checkpoint's range does not fit the split (a weight >= 6e4: Model::build, csrc/models.cpp) */
+                                   checkpoint's range does not fit the split: a value the matrix-core stages would receive
+                                   >= 6e4 in magnitude - weights and biases after their PReLU scaling by (1 + s) / 2, the
+                                   tail's weights and bias (Model::build, csrc/models.cpp) */
   SS4K_MODEL_ONE_CHAIN = 2,     /* a multi-frame job never runs as two concurrent launch chains (frame lanes) */
   SS4K_MODEL_TWO_CHAINS = 4,    /* ... always does (default: measured per shape over the first calls) */
   SS4K_MODEL_HR_F32 = 512,      /* fp16 SRVGG / fp16-mode FSRCNN on the service paths: keep the network's output tensor (x4 on 720p: 2880 x 5120 x 3

@@ -260,13 +260,12 @@ void Model::build(const float* w, size_t n) {
   ParamCursor pc{w, n};
   if (desc.kind == SS4K_FSRCNN) {
     // The fp16 hi/lo split (fsrcnn.hip split2) needs every operand inside the fp16 range: |x| < 65504 (below 2^-14 the hi part
-    // is an fp16 subnormal and the lo part makes up the difference, absolute error < 2^-24 |w|).  Weights are checked here - a
-    // checkpoint that does not fit runs the exact-fp32 kernels; activations of an image-range network are orders of magnitude
-    // inside (T91: < 120 for inputs in [0,1], tests/test_oracle_golden.py::test_fsrcnn_t91_activation_range), and
-    // SS4K_MODEL_FS_EXACT is the caller's switch for a network that is not.
-    float wmax = 0.f;
-    for (size_t i = 0; i < n; ++i) wmax = std::max(wmax, std::fabs(w[i]));
-    if (!(wmax < 6.0e4f)) fs_exact = true;
+    // is an fp16 subnormal and the lo part makes up the difference, absolute error < 2^-24 |w|).  The values the matrix-core
+    // kernels receive are checked below, after the PReLU scaling (which multiplies a producing weight or bias by up to (1 + s) / 2:
+    // x 5.05 on the T91 x4 checkpoint's s = 9.1) - a checkpoint that does not fit runs the exact-fp32 kernels; activations of an
+    // image-range network are orders of magnitude inside (T91: < 120 for inputs in [0,1],
+    // tests/test_oracle_golden.py::test_fsrcnn_t91_activation_range), and SS4K_MODEL_FS_EXACT is the caller's switch for a network
+    // that is not.
     // device blob layout: see FsrcnnWeights (glue.h)
     std::vector<float> blob;
     auto push = [&](const std::vector<float>& v) { size_t o = blob.size(); blob.insert(blob.end(), v.begin(), v.end()); while (blob.size() % 4) blob.push_back(0.f); return o; };
@@ -308,7 +307,8 @@ void Model::build(const float* w, size_t n) {
       for (const Act& A : acts)
         for (int c = 0; c < A.channels; ++c) if (!(blob[off[A.a] + c] > -0.875f)) fs_exact = true;
     if (!fs_exact) {   // (both matrix-core modes: fp16 and fp32-grade)
-      float* B = blob.data();
+      std::vector<float> scaled = blob;
+      float* B = scaled.data();
       for (const Act& A : acts)
         for (int c = 0; c < A.channels; ++c) {
           const float sl = B[off[A.a] + c], sa = 0.5f * (1.f + sl);
@@ -316,7 +316,11 @@ void Model::build(const float* w, size_t n) {
           B[off[A.b] + c] *= sa;
           B[off[A.a] + c] = (1.f - sl) / (1.f + sl);
         }
-      fsw.prelu_abs = true;
+      // the range check on what the kernels get: every scaled weight and bias, the slopes' c, the tail's weights and bias
+      bool fits = std::fabs(fsw.b_deconv) < 6.0e4f;
+      for (float v : scaled) fits = fits && std::fabs(v) < 6.0e4f;
+      if (fits) { blob.swap(scaled); fsw.prelu_abs = true; }
+      else fs_exact = true;   // the exact kernels take the unscaled layout
     }
     upload(fs_blob, blob.data(), blob.size() * 4);
     weight_bytes = blob.size() * 4;

@@ -100,3 +100,66 @@ def record_measured(name, **values):
             json.dump(data, f, indent=1, sort_keys=True)
     except OSError:
         pass
+
+
+def _f64(a):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return a.astype(np.float64)
+
+
+def error_budget(got, ref64, yard, *, u, tiles=(1,)):
+    """The two measures of ``assert_error_budget`` without a verdict: ``{"max": ..., "slice": ..., "worst_slice": ...}``.
+
+    ``max`` = max|got - ref64| / max(max|yard - ref64|, u max|ref64|); ``slice`` = the largest (rms(E_s) - u max|ref64|) / rms(N_s)
+    over the slices of at least 64 elements (frames, output channels, output rows, output columns, the row bands of 16 and 20 and
+    the column bands of 32 pixels of every tile grid in ``tiles`` - output pixels per layer pixel -, the one-pixel border ring)."""
+    g, r, y = _f64(got), _f64(ref64), _f64(yard)
+    assert g.shape == r.shape == y.shape, f"shapes {g.shape} {r.shape} {y.shape}"
+    g, r, y = (a.reshape((-1,) + a.shape[-3:]) for a in (g, r, y))   # (frames, channels, rows, columns)
+    E2, N2 = (g - r) ** 2, (y - r) ** 2
+    peak = float(np.abs(r).max())
+    floor = u * peak
+    out = {"max": float(np.sqrt(E2.max()) / max(np.sqrt(N2.max()), floor, 1e-300)), "slice": 0.0, "worst_slice": None}
+
+    def check(name, e_sum, n_sum, count):
+        for i in np.nonzero(count >= 64)[0]:
+            e, n = np.sqrt(e_sum[i] / count[i]), np.sqrt(n_sum[i] / count[i])
+            over = e - floor
+            ratio = 0.0 if over <= 0 else (over / n if n > 0 else float("inf"))
+            if ratio > out["slice"]:
+                out["slice"], out["worst_slice"] = float(ratio), f"{name} {i}"
+
+    f, c, h, w = g.shape
+    for name, axes, size in (("frame", (1, 2, 3), c * h * w), ("channel", (0, 2, 3), f * h * w),
+                             ("row", (0, 1, 3), f * c * w), ("column", (0, 1, 2), f * c * h)):
+        e, n = E2.sum(axis=axes), N2.sum(axis=axes)
+        check(name, e, n, np.full(e.shape, size))
+    er, nr, ec, nc = E2.sum(axis=(0, 1, 3)), N2.sum(axis=(0, 1, 3)), E2.sum(axis=(0, 1, 2)), N2.sum(axis=(0, 1, 2))
+    for s in tiles:
+        for name, e1, n1, band, per in (("row band 16", er, nr, 16 * s, f * c * w), ("row band 20", er, nr, 20 * s, f * c * w),
+                                        ("column band 32", ec, nc, 32 * s, f * c * h)):
+            idx = np.arange(e1.size) // band
+            check(f"{name} x{s}", np.bincount(idx, e1), np.bincount(idx, n1), np.bincount(idx) * per)
+    ring = np.zeros((h, w), bool)
+    ring[0, :] = ring[-1, :] = ring[:, 0] = ring[:, -1] = True
+    check("border ring", np.array([E2[..., ring].sum()]), np.array([N2[..., ring].sum()]), np.array([f * c * ring.sum()]))
+    return out
+
+
+def assert_error_budget(got, ref64, yard, *, k_max, k_slice, u, what, tiles=(1,)):
+    """Element-wise anchor of a result against a float64 reference.  ``E = |got - ref64|`` is held against the yardstick
+    ``N = |yard - ref64|`` - a correct implementation of the same precision (fp16 routes: ``oracle.precision.emu16``; fp32
+    routes: the fp32 oracle):
+
+    * ``got`` is finite everywhere;
+    * L-inf: ``max E <= k_max * max(max N, u * max|ref64|)``;
+    * locality: ``rms(E_s) <= k_slice * rms(N_s) + u * max|ref64|`` on every slice of ``error_budget`` (a wrong tile column,
+      a stale halo row, a dropped bias or a shifted border stays below the L-inf bar but not below this one).
+
+    Returns the worst ratios (``error_budget``) for ``record_measured``."""
+    g = _f64(got)
+    assert np.isfinite(g).all(), f"{what}: {int((~np.isfinite(g)).sum())} non-finite values"
+    m = error_budget(g, ref64, yard, u=u, tiles=tiles)
+    assert m["max"] <= k_max, f"{what}: max error {m['max']:.3g} x the yardstick's (bar {k_max})"
+    assert m["slice"] <= k_slice, f"{what}: rms error of {m['worst_slice']} {m['slice']:.3g} x the yardstick's (bar {k_slice})"
+    return m

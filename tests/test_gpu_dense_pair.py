@@ -20,16 +20,16 @@ pytestmark = pytest.mark.gpu
 NO_DENSE, DENSE, ONE, TWO = _capi.MODEL_NO_DENSE, 0, _capi.MODEL_ONE_CHAIN, _capi.MODEL_TWO_CHAINS   # DENSE: the default (fused pairs)
 
 
-PIN32 = _capi.MODEL_NO_W16   # this file tests conv_dense.hip (v_mfma_f32_32x32x16_f16: bit-identical to four launches of conv_mfma.hip); the default
-                             # fused route since round 4 is conv_d16.hip (16x16x32, another summation order): tests/test_gpu_d16.py
+PIN32 = _capi.MODEL_NO_W16   # this file tests conv_dense.hip (v_mfma_f32_32x32x16_f16: bit-identical to four launches of conv_mfma.hip); the fused
+                             # pairs are conv_dense.hip on every product route (conv_d16.hip, a 16x16x32 build, is dev-library only: tools/dev_tests/)
 
 
 def _model(ctx, flat, scale, nb, flags):
     return _capi.Model(ctx, _capi.make_desc(_capi.RRDBNET, _capi.F16, scale=scale, num_block=nb, flags=flags | PIN32), flat)
 
 
-# shapes: interior grid (h / r, w / r) with 1 .. many tiles of 16 x 30, ragged right / bottom edges, widths just below / at / above
-# a multiple of 30, heights that are not multiples of 16, one- to four-frame jobs (lanes on and off)
+# shapes: interior grid (h / r, w / r) with 1 .. many tiles of 16 rows x 32 columns, ragged right / bottom edges, widths around
+# multiples of 30 and 32, heights that are not multiples of 16, one- to four-frame jobs (lanes on and off)
 @pytest.mark.parametrize("scale,shape,lanes", [(2, (1, 3, 144, 208), ONE), (2, (2, 3, 92, 200), TWO), (2, (3, 3, 80, 72), ONE),
                                                (4, (1, 3, 37, 70), ONE), (1, (1, 3, 128, 256), ONE), (2, (4, 3, 64, 120), TWO),
                                                (2, (1, 3, 32, 60), ONE), (2, (1, 3, 34, 62), ONE), (2, (2, 3, 30, 58), TWO),

@@ -1,0 +1,255 @@
+"""GPU: every conv kernel route bounded element by element against a float64 reference (tests/helpers.py::assert_error_budget).
+
+One case per network, dtype and route pin, at shapes that put partial tiles on every edge: layer-resolution widths of 32k +- 1,
+heights off the 16 / 20-row grids, 1 x 1 and 1 x N tile grids, one to three frames (odd counts on two launch chains).
+
+* fp16 routes: ``E = |got - ref64|`` against ``N = |emu16 - ref64|`` (oracle/precision.py: float64 arithmetic with the fp16
+  path's roundings).  Roundings of the HIP path that the emulation does not model, absorbed by the budget (one extra rounding):
+  RRDBNet's up-sampling convs add two rows of weight fragments in fp16 before the MFMA by default (SS4K_MODEL_NO_UPS_PRESUM
+  pins the direct form); conv5 of an RDB takes its residual through the matrix core (the ``<RL>`` builds); FSRCNN's fp16 mode
+  evaluates its PReLU on packed fp16 and carries some biases in an fp16 K slot (the emulation rounds every scaled bias).
+* fp32 routes (exact-fp32 MFMA, FSRCNN's exact kernels and its fp32-grade hi/lo split): ``N = |fp32 oracle - ref64|``.
+  (The fp32 oracle's own error is 50-150 u * peak, so an fp16 rounding leaking into one layer measures 50-470 x it:
+  tests/test_error_budget_cpu.py::test_fp32_budget.)
+
+Each case declares the kernel builds it must reach and asserts that they were launched (the context's per-build profile);
+``test_every_product_build_is_bounded`` holds the union of the declarations to the product's list of conv builds.
+"""
+from collections import namedtuple
+
+import numpy as np
+import pytest
+import torch
+
+import sharkshark4k_amd  # noqa: F401
+from sharkshark4k_amd import _capi
+from sharkshark4k_amd import weights as W
+from sharkshark4k_amd.upscale import model as factory
+from oracle import nets as onets
+from oracle import precision as P
+from tests.helpers import assert_close, assert_error_budget, error_budget, record_measured
+from tests.test_oracle_golden import _t91
+
+pytestmark = pytest.mark.gpu
+
+# bars (ceilings: fp16 k_max 4 / k_slice 3, exact fp32 16, FSRCNN hi/lo split 64).  Measured on MI355X (record_measured, tests/helpers.py):
+# fp16 max 0.46-1.11 (slices under the u * peak floor), exact fp32 max <= 2.1 / slice <= 1.9, split max <= 4.4 / slice <= 6.6
+K16_MAX, K16_SLICE = 4.0, 3.0
+K32_MAX, K32_SLICE = 5.0, 5.0
+KSPLIT_MAX, KSPLIT_SLICE = 10.0, 14.0
+
+# the conv kernel builds of the product library (the launcher's family names up to " (")
+PRODUCT_BUILDS = {
+    "conv3x3_kernel<float,1>", "conv3x3_kernel<float,2>",
+    "conv3x3_kernel<__half,1,4>", "conv3x3_kernel<__half,1,5>", "conv3x3_kernel<__half,2,4>",
+    "wide::conv3x3_wide_kernel", "wide::conv3x3_wide_kernel<RL>", "wide::conv3x3_wide_kernel<UPS>",
+    "dense::conv3x3_dense2_kernel<4>", "dense::conv3x3_dense2_kernel<8>", "dense::conv3x3_dense2_kernel<0>",
+    "w16::conv3x3_w16_kernel", "w16::conv3x3_w16_kernel<RL>",
+    "w16n::conv3x3_w16n_kernel",
+    "pair::conv3x3_pair_kernel",
+}
+F32_1, F32_2 = "conv3x3_kernel<float,1>", "conv3x3_kernel<float,2>"
+H14, H15, H24 = "conv3x3_kernel<__half,1,4>", "conv3x3_kernel<__half,1,5>", "conv3x3_kernel<__half,2,4>"
+WIDE, WIDE_RL, WIDE_UPS = "wide::conv3x3_wide_kernel", "wide::conv3x3_wide_kernel<RL>", "wide::conv3x3_wide_kernel<UPS>"
+D4, D8, D0 = "dense::conv3x3_dense2_kernel<4>", "dense::conv3x3_dense2_kernel<8>", "dense::conv3x3_dense2_kernel<0>"
+W16, W16_RL, W16N, PAIR = "w16::conv3x3_w16_kernel", "w16::conv3x3_w16_kernel<RL>", "w16n::conv3x3_w16n_kernel", "pair::conv3x3_pair_kernel"
+
+ONE, TWO = _capi.MODEL_ONE_CHAIN, _capi.MODEL_TWO_CHAINS
+NO_W16, NO_DENSE, NO_WIDE, NO_PAIR = _capi.MODEL_NO_W16, _capi.MODEL_NO_DENSE, _capi.MODEL_NO_WIDE, _capi.MODEL_NO_PAIR
+T16, T20, NO_PRESUM = _capi.MODEL_TILE_ROWS_16, _capi.MODEL_TILE_ROWS_20, _capi.MODEL_NO_UPS_PRESUM
+
+# net: rrdbnet / srvgg / bsvd / bsvd_seq; arch: make_desc keywords (+ the table's); shape: the model's input
+Case = namedtuple("Case", "id net dtype flags arch shape must")
+
+
+def _rr(id, dtype, flags, scale, shape, must, nb=1, nf=64, g=32):
+    return Case(id, "rrdbnet", dtype, flags, dict(scale=scale, num_block=nb, num_feat=nf, num_grow_ch=g), shape, must)
+
+
+# RRDBNet input = layer resolution x (4, 2, 1) for scale (1, 2, 4)
+CASES = [
+    _rr("rrdbnet_f16_x2_default", "f16", 0, 2, (1, 3, 2 * 21, 2 * 65), {D4, D8, W16_RL, W16N}),
+    _rr("rrdbnet_f16_x1_default_2frames_two_chains", "f16", TWO, 1, (2, 3, 4 * 17, 4 * 31), {D4, D8, W16_RL}),
+    _rr("rrdbnet_f16_x4_default_3frames_two_chains", "f16", TWO, 4, (3, 3, 19, 33), {D4, D8, W16_RL}),
+    _rr("rrdbnet_f16_x4_1xN_grid", "f16", ONE, 4, (1, 3, 9, 97), {D4, D8}),
+    _rr("rrdbnet_f16_x2_1x1_grid", "f16", 0, 2, (1, 3, 2 * 7, 2 * 9), {D4, D8}),
+    _rr("rrdbnet_f16_x2_no_w16", "f16", NO_W16, 2, (1, 3, 2 * 13, 2 * 97), {WIDE, WIDE_RL, WIDE_UPS}),
+    _rr("rrdbnet_f16_x2_no_dense_2frames_one_chain", "f16", NO_DENSE | ONE, 2, (2, 3, 2 * 20, 2 * 33), {W16_RL}),
+    _rr("rrdbnet_f16_x2_no_wide_no_dense", "f16", NO_WIDE | NO_DENSE, 2, (1, 3, 2 * 9, 2 * 31), {H24}),
+    _rr("rrdbnet_f16_x2_tile_rows_16", "f16", T16 | NO_DENSE, 2, (1, 3, 2 * 35, 2 * 33), {H14}),
+    _rr("rrdbnet_f16_x2_tile_rows_20", "f16", T20 | NO_DENSE, 2, (1, 3, 2 * 35, 2 * 33), {H15}),
+    _rr("rrdbnet_f16_x4_no_ups_presum", "f16", NO_PRESUM, 4, (1, 3, 17, 31), {D4, D8}),
+    _rr("rrdbnet_f16_x2_2blocks", "f16", 0, 2, (1, 3, 2 * 15, 2 * 33), {D4, D8, W16_RL}, nb=2),
+    _rr("rrdbnet_f16_x2_feat96", "f16", 0, 2, (1, 3, 2 * 11, 2 * 33), {D0}, nf=96),
+    _rr("rrdbnet_f16_x2_grow64", "f16", 0, 2, (1, 3, 2 * 11, 2 * 31), set(), g=64),
+    Case("srvgg64_f16_x4_default", "srvgg", "f16", 0, dict(scale=4, num_feat=64, num_block=4), (1, 3, 23, 65), {W16}),
+    Case("srvgg64_f16_x2_no_w16_3frames_two_chains", "srvgg", "f16", NO_W16 | TWO, dict(scale=2, num_feat=64, num_block=4), (3, 3, 17, 31), {WIDE}),
+    Case("srvgg128_f16_x4_default", "srvgg", "f16", 0, dict(scale=4, num_feat=128, num_block=3), (1, 3, 13, 33), {W16}),
+    Case("srvgg128_f16_x2_no_w16", "srvgg", "f16", NO_W16, dict(scale=2, num_feat=128, num_block=3), (1, 3, 9, 63), {WIDE}),
+    Case("bsvd32_f16_f1_default", "bsvd", "f16", 0, dict(variant="bsvd-32"), (1, 4, 44, 124), {PAIR}),
+    Case("bsvd32_f16_f1_no_pair_2frames_two_chains", "bsvd", "f16", NO_PAIR | TWO, dict(variant="bsvd-32"), (2, 4, 36, 68), set()),
+    Case("bsvd32_f16_stream_3frames", "bsvd_seq", "f16", 0, dict(variant="bsvd-32"), (3, 4, 20, 68), {PAIR}),
+    Case("bsvd64_f16_f1_default", "bsvd", "f16", 0, dict(variant="bsvd-64"), (1, 4, 28, 60), set()),
+    Case("bsvd64_f16_stream_3frames_one_chain", "bsvd_seq", "f16", ONE, dict(variant="bsvd-64"), (3, 4, 20, 36), set()),
+    # fp32 routes: two ragged shapes per network
+    _rr("rrdbnet_f32_x2", "f32", 0, 2, (1, 3, 2 * 21, 2 * 33), {F32_1, F32_2}),
+    _rr("rrdbnet_f32_x4_2frames", "f32", 0, 4, (2, 3, 17, 31), {F32_1, F32_2}),
+    Case("srvgg64_f32_x4", "srvgg", "f32", 0, dict(scale=4, num_feat=64, num_block=4), (1, 3, 23, 65), {F32_2}),
+    Case("srvgg64_f32_x2_2frames", "srvgg", "f32", 0, dict(scale=2, num_feat=64, num_block=4), (2, 3, 17, 31), {F32_2}),
+    Case("bsvd32_f32_f1", "bsvd", "f32", 0, dict(variant="bsvd-32"), (1, 4, 44, 124), {F32_1}),
+    Case("bsvd32_f32_stream_3frames", "bsvd_seq", "f32", 0, dict(variant="bsvd-32"), (3, 4, 20, 68), {F32_1}),
+]
+
+
+def _srvgg_table(nf, nc, scale):
+    """Generated weights with PReLU slopes in [-0.5, 1.7] on alternate layers (both HIP epilogue forms: max(t, t s) needs s <= 1)."""
+    t = W.srvgg_table(seed=nf + scale, num_feat=nf, num_conv=nc, upscale=scale)
+    rng = np.random.default_rng(nf + scale)
+    for i, k in enumerate(k for k in list(t) if np.asarray(t[k]).ndim == 1 and k.endswith(".weight")):
+        lo, hi = (-0.5, 1.7) if i % 2 == 0 else (-0.5, 1.0)
+        t[k] = rng.uniform(lo, hi, t[k].shape).astype(np.float32)
+    return t
+
+
+def _build(ctx, c):
+    """(HIP model, oracle function, its extra arguments, weight table, input, tile scales: output pixels per layer pixel)."""
+    dt = _capi.F16 if c.dtype == "f16" else _capi.F32
+    x = torch.rand(*c.shape, generator=torch.Generator().manual_seed(len(c.id)))
+    a = c.arch
+    if c.net == "rrdbnet":
+        t = W.rrdbnet_table(a["scale"], **a)
+        desc = _capi.make_desc(_capi.RRDBNET, dt, flags=c.flags, **a)
+        m = _capi.Model(ctx, desc, W.flatten(t, W.rrdbnet_keys(a["num_block"])))
+        return m, onets.rrdbnet, (a["scale"], a["num_block"]), t, x, (4, 2, 1)
+    if c.net == "srvgg":
+        t = _srvgg_table(a["num_feat"], a["num_block"], a["scale"])
+        desc = _capi.make_desc(_capi.SRVGG, dt, flags=c.flags, **a)
+        m = _capi.Model(ctx, desc, W.flatten(t, W.srvgg_keys(a["num_block"])))
+        return m, onets.srvgg, (a["num_block"], a["scale"]), t, x, (a["scale"],)
+    stream = c.net == "bsvd_seq"
+    t = W.bsvd_table(seed=5, **factory.BSVD_VARIANTS[a["variant"]])
+    m = factory.build_denoise_model(ctx, weights=t, dtype=c.dtype, stream=stream, variant=a["variant"], flags=c.flags)
+    x = x[None] if stream else x[:, None]   # (N, F, C, H, W): one stream of F frames, or F = 1 per frame
+    return m, onets.bsvd_seq if stream else onets.bsvd_f1, (), t, x, (1, 2, 4)
+
+
+def _run_profiled(ctx, fn):
+    """fn() with the context's per-build profile on; returns (result, the conv builds launched)."""
+    ctx.prof_enable(True)
+    try:
+        ctx.prof_reset()
+        out = fn()
+        torch.cuda.synchronize()
+        fams = {name.split(" (")[0] for name, n, _, _ in ctx.prof_read_families() if n > 0}
+    finally:
+        ctx.prof_enable(False)
+    return out, fams
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
+def test_route_error_budget(ctx, case):
+    m, net, args, t, x, tiles = _build(ctx, case)
+    got, fams = _run_profiled(ctx, lambda: m(x.cuda()).cpu())
+    ref = P.ref64(net, x, t, *args)
+    if case.dtype == "f16":
+        yard, bars = P.emu16(net, x, t, *args), dict(k_max=K16_MAX, k_slice=K16_SLICE, u=P.U16)
+    else:
+        yard, bars = P.fp32_oracle(net, x, t, *args), dict(k_max=K32_MAX, k_slice=K32_SLICE, u=P.U32)
+    r = error_budget(got, ref, yard, u=bars["u"], tiles=tiles)
+    record_measured(f"error_budget_{case.id}", max_ratio=r["max"], slice_ratio=r["slice"], worst_slice=str(r["worst_slice"]),
+                    asserted=f"max <= {bars['k_max']}, slice <= {bars['k_slice']}", builds=sorted(fams))
+    assert_error_budget(got, ref, yard, what=case.id, tiles=tiles, **bars)
+    assert case.must <= fams, f"{case.id}: builds {sorted(case.must - fams)} not launched (launched: {sorted(fams)})"
+
+
+# ------------------------------------------------------------------------------ FSRCNN: f16 mode, fp32-grade split, exact
+FS_SIZES = [(1, 1, 5, 7), (2, 1, 33, 129), (1, 1, 150, 333)]
+
+
+def _fs_table(tag, factor):
+    return _t91(factor) if tag == "t91" else W.fsrcnn_table(seed=10 + factor)
+
+
+@pytest.mark.parametrize("size", FS_SIZES, ids=["5x7", "33x129", "150x333"])
+@pytest.mark.parametrize("tag", ["t91", "gen"])
+@pytest.mark.parametrize("factor", [2, 4])
+@pytest.mark.parametrize("mode", ["f16", "split", "exact"])
+def test_fsrcnn_error_budget(ctx, mode, factor, tag, size):
+    t = _fs_table(tag, factor)
+    x = torch.rand(*size, generator=torch.Generator().manual_seed(factor * 7 + size[2]))
+    flags = _capi.MODEL_FS_EXACT if mode == "exact" else 0
+    m = factory.build_model_fsrcnn(ctx, factor=factor, weights=t, dtype="f16" if mode == "f16" else "f32", flags=flags)
+    ctx.prof_enable(True)
+    try:
+        ctx.prof_reset()
+        got = m(x.cuda()).cpu()
+        torch.cuda.synchronize()
+        stages = [ctx.prof_read_kind(k)[0] for k in (1, 2, 3)]
+    finally:
+        ctx.prof_enable(False)
+    assert all(n >= 1 for n in stages), f"FSRCNN stages (head, mapping, tail) launched {stages} times"
+    if mode != "exact":
+        # the T91 checkpoints have PReLU slopes below -0.875 (x2 -0.91, x4 -1.11): both matrix-core modes send them to the exact
+        # kernels (Model::build); the generated tables run the mode itself
+        exact = factory.build_model_fsrcnn(ctx, factor=factor, weights=t, dtype="f16" if mode == "f16" else "f32",
+                                           flags=_capi.MODEL_FS_EXACT)(x.cuda()).cpu()
+        assert torch.equal(got, exact) == (tag == "t91"), f"{mode} x{factor} {tag}: route (exact kernels or not) changed"
+    ref = P.ref64(onets.fsrcnn, x, t, factor)
+    if mode == "f16":
+        yard, bars = P.emu16(onets.fsrcnn, x, t, factor), dict(k_max=K16_MAX, k_slice=K16_SLICE, u=P.U16)
+    else:
+        k = (KSPLIT_MAX, KSPLIT_SLICE) if mode == "split" else (K32_MAX, K32_SLICE)
+        yard, bars = P.fp32_oracle(onets.fsrcnn, x, t, factor), dict(k_max=k[0], k_slice=k[1], u=P.U32)
+    name = f"fsrcnn_{mode}_x{factor}_{tag}_{size[2]}x{size[3]}"
+    r = error_budget(got, ref, yard, u=bars["u"], tiles=(factor,))
+    record_measured(f"error_budget_{name}", max_ratio=r["max"], slice_ratio=r["slice"], worst_slice=str(r["worst_slice"]),
+                    asserted=f"max <= {bars['k_max']}, slice <= {bars['k_slice']}")
+    assert_error_budget(got, ref, yard, what=name, tiles=(factor,), **bars)
+
+
+# ------------------------------------------------------------------------------ FSRCNN range guard
+def _fs_range_table(big):
+    """Generated FSRCNN x4 table whose expand channels 0-3 have the T91 x4 checkpoint's PReLU slope 9.1 (scaling (1 + s) / 2 = 5.05)
+    and an expand.0 weight of magnitude ``big`` on input column j = 5; map.6's output channel 5 is scaled by 1e-4 so that the
+    activations stay O(1): only the weights can leave the fp16 range."""
+    t = {k: np.array(v, dtype=np.float32, copy=True) for k, v in W.fsrcnn_table(seed=31).items()}
+    ch, j = [0, 1, 2, 3], 5
+    t["expand.1.weight"][ch] = 9.1
+    t["expand.0.weight"][ch, j] = big * np.where(np.arange(len(ch)) % 2, -1.0, 1.0)[:, None, None]
+    t["map.6.weight"][j] *= 1e-4
+    t["map.6.bias"][j] *= 1e-4
+    return t
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f16"])
+def test_fsrcnn_range_guard_sees_scaled_weights(ctx, dtype):
+    """2e4 is below the 6e4 bound as given but 1.01e5 after the PReLU scaling - inf in fp16 and in the hi of the hi/lo split.
+    The model must take the exact kernels: finite, bit-identical to SS4K_MODEL_FS_EXACT, inside the fp32 tolerance."""
+    t = _fs_range_table(2.0e4)
+    x = torch.rand(2, 1, 33, 65, generator=torch.Generator().manual_seed(3))
+    got = factory.build_model_fsrcnn(ctx, factor=4, weights=t, dtype=dtype)(x.cuda()).cpu()
+    exact = factory.build_model_fsrcnn(ctx, factor=4, weights=t, dtype=dtype, flags=_capi.MODEL_FS_EXACT)(x.cuda()).cpu()
+    assert torch.isfinite(got).all(), f"{int((~torch.isfinite(got)).sum())} non-finite outputs"
+    assert torch.equal(got, exact), f"differs from FS_EXACT by up to {float((got - exact).abs().max()):.3g}"
+    with torch.no_grad():
+        assert_close(got, onets.fsrcnn(x, t, 4), what=f"range guard {dtype}")
+
+
+def test_fsrcnn_range_guard_does_not_over_trigger(ctx):
+    """Control: 1e4 scales to 5.05e4, inside the range - the fp32-grade split runs (not bit-identical to FS_EXACT) and meets its budget."""
+    t = _fs_range_table(1.0e4)
+    x = torch.rand(2, 1, 33, 65, generator=torch.Generator().manual_seed(3))
+    got = factory.build_model_fsrcnn(ctx, factor=4, weights=t, dtype="f32")(x.cuda()).cpu()
+    exact = factory.build_model_fsrcnn(ctx, factor=4, weights=t, dtype="f32", flags=_capi.MODEL_FS_EXACT)(x.cuda()).cpu()
+    assert not torch.equal(got, exact), "the split mode was not taken"
+    r = assert_error_budget(got, P.ref64(onets.fsrcnn, x, t, 4), P.fp32_oracle(onets.fsrcnn, x, t, 4), k_max=KSPLIT_MAX,
+                            k_slice=KSPLIT_SLICE, u=P.U32, what="range guard control", tiles=(4,))
+    record_measured("error_budget_fsrcnn_range_guard_control_split", max_ratio=r["max"], slice_ratio=r["slice"],
+                    asserted=f"max <= {KSPLIT_MAX}, slice <= {KSPLIT_SLICE}")
+
+
+def test_every_product_build_is_bounded():
+    """A conv build of the product library without a bounded case fails here (the list above is the launchers' family names)."""
+    declared = set().union(*(c.must for c in CASES))
+    assert PRODUCT_BUILDS <= declared, f"no bounded case reaches {sorted(PRODUCT_BUILDS - declared)}"
+    assert declared <= PRODUCT_BUILDS, f"declared builds outside the product list: {sorted(declared - PRODUCT_BUILDS)}"
