@@ -149,10 +149,8 @@ int ss4k_model_workspace_bytes(ss4k_model* m, int n, int h, int w, size_t* bytes
 int ss4k_model_forward(ss4k_model* m, const float* in_nchw_dev, float* out_nchw_dev, int n, int h,
                        int w, void* hip_stream);
 
-/* Asynchronous status of the model's earlier forwards.  No kernel of the product library has an asynchronous failure mode: always
- * SS4K_OK, at once.  (The dev library's cross-layer chain kernel - include/ss4k_dev.h, SS4K_DEV_MODEL_CHAIN - marks a sticky word when a
- * work unit gives up waiting for its neighbours; there this call returns SS4K_EHIP once per failure, after blocking until the model's
- * last chain launch has finished when wait != 0.) */
+/* Asynchronous status of the model's earlier forwards.  No kernel of either library has an asynchronous failure mode: always SS4K_OK, at
+ * once, whatever `wait` is (SS4K_EINVAL for a NULL model).  Kept for ABI 3: the one kernel that could fail this way was removed. */
 int ss4k_model_check(ss4k_model* m, int wait);
 
 /* ---- the service's frame-in/frame-out hot path ------------------------------------------- */

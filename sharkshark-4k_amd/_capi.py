@@ -44,8 +44,6 @@ class ModelDesc(C.Structure):
 MODEL_FS_EXACT, MODEL_ONE_CHAIN, MODEL_TWO_CHAINS, MODEL_TILE_ROWS_16, MODEL_TILE_ROWS_20 = 1, 2, 4, 16, 32
 MODEL_NO_PAIR, MODEL_HR_F32, MODEL_NO_DENSE, MODEL_NO_WIDE, MODEL_NO_UPS_PRESUM, MODEL_NO_W16 = 256, 512, 1024, 4096, 8192, 32768
 MODEL_FLAGS_ALL = 1 | 2 | 4 | 16 | 32 | 256 | 512 | 1024 | 4096 | 8192 | 32768
-# include/ss4k_dev.h: accepted by libss4k_hip_dev.so only (kernels of rounds 2-4 that are on no product route: tools/dev_tests/)
-DEV_MODEL_CHAIN, DEV_MODEL_CONV5_RS = 128, 16384
 
 
 class UpscaleCfg(C.Structure):
@@ -313,7 +311,7 @@ class Model:
             pass
 
     def check(self, wait: bool = True) -> None:
-        """Raise if an earlier forward of this model failed asynchronously (ss4k_model_check; only the chain kernel can)."""
+        """Raise if an earlier forward of this model failed asynchronously (ss4k_model_check; no kernel can any more: always passes)."""
         _check(lib().ss4k_model_check(self._h, 1 if wait else 0))
 
     def workspace_bytes(self, n, h, w) -> int:

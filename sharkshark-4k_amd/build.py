@@ -15,15 +15,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libss4k_hip.so")
 LIB_DEV = os.path.join(HERE, "libss4k_hip_dev.so")
 SOURCES = ["conv_mfma.hip", "conv_pair.hip", "conv_dense.hip", "conv_w16.hip", "conv_w16n.hip", "glue.hip", "fsrcnn.hip", "pack.cpp", "models.cpp", "api.cpp"]
-# libss4k_hip_dev.so alone: measured experiments (conv_s3, conv_d16) and the kernels of rounds 2-4 that no product route uses any more
-# (conv_rs: register-stationary weights; conv_chain: the RRDB body as one persistent launch) - tools/dev_tests/ keeps them honest
-DEV_SOURCES = ["conv_s3.hip", "conv_d16.hip", "conv_rs.hip", "conv_chain.hip"]
-# conv_rs.hip: the per-tile body is thousands of fully unrolled MFMAs (weights live in named registers); hipcc's
-# default cap on '#pragma unroll' size would leave the chunk loop rolled and the weights in scratch
 # fsrcnn.hip: no SLP vectorisation - left on, the tail's overlap-add (two adjacent output columns per lane) is packed into v_pk_add_f32,
 # which cannot take a DPP operand: 20 of its 35 wave shifts per row then become separate v_mov_b32_dpp, and packed fp32 adds are slower
 # than two plain ones beside MFMAs (MI355X_MICROARCH.md, cycle constants).  Without it every shift is folded into its add (v_add_f32_dpp)
-EXTRA_FLAGS = {"conv_rs.hip": ["-mllvm", "-pragma-unroll-threshold=4000000"], "fsrcnn.hip": ["-fno-slp-vectorize"]}
+EXTRA_FLAGS = {"fsrcnn.hip": ["-fno-slp-vectorize"]}
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-x", "hip", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable"]
 
@@ -51,8 +46,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
     flags = FLAGS + (["-DSS4K_DEV"] if dev else [])
     os.makedirs(objdir, exist_ok=True)
     jobs = []
-    sources = SOURCES + (DEV_SOURCES if dev else [])
-    for s in sources:
+    for s in SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(objdir, os.path.splitext(s)[0] + ".o")
         if force or _needs_build(obj, src):
@@ -71,7 +65,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         list(ex.map(run, jobs))
-    objs = [os.path.join(objdir, os.path.splitext(s)[0] + ".o") for s in sources]
+    objs = [os.path.join(objdir, os.path.splitext(s)[0] + ".o") for s in SOURCES]
     if jobs or not os.path.exists(lib):
         cmd = [hipcc, "-shared", "-fPIC", "--offload-arch=gfx950", *objs, "-o", lib]
         if verbose:

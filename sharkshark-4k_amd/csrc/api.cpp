@@ -393,7 +393,7 @@ int ss4k_model_forward(ss4k_model* m, const float* in, float* out, int n, int h,
 int ss4k_model_check(ss4k_model* m, int wait) {
   return guard([&] {
     SS4K_REQUIRE(m, "ss4k_model_check: NULL argument");
-    m->m.check_async_error(wait != 0);
+    (void)wait;   // no kernel has an asynchronous failure mode (include/ss4k.h)
   });
 }
 

@@ -187,15 +187,12 @@ struct ConvArgs {
                                         // plane are chosen on THIS - the same kernel for every launch chain of a job, whatever its n0
   float grid_share;                     // size the persistent grid for this share of the chip's workgroup slots (0 = all)
   int mb_override;                      // 0: tile height of the 32-cout layers by image height; 4 / 5: rows per wave forced (A/B)
-  int s3;                               // 32-cout layers without residuals on the three-stage kernel (conv_s3.hip)
-  int wide_rl;                          // ... and a residual that is the layer's own input may go through the matrix core there (conv5 of an RDB)
+  int wide_rl;                          // a residual that is the layer's own input may go through the matrix core on the 64-cout tile (conv5 of an RDB)
   int wide;                             // 64-cout-group layers with a plain epilogue on conv_dense.hip's single-layer build (conv3x3_wide_kernel)
   int no_band;                          // dev experiment: tiles dealt round-robin over the workgroups instead of one contiguous band per XCD
   int ups2;                             // input is the nearest-x2 upsampling of an (H/2, W/2) tensor
   int ups_presum;                       // ... and the wide kernel may add the weight fragments of the two taps that read the same input row
   const void* wpk;                      // packed weights [group][chunk][dx,ks][dy][nb][lane][E]
-  const void* wrs;                      // conv_rs.hip layout [group][cout group][chunk32][tap][cb][lane][8] or null
-  int rs_wide;                          // wrs is packed for the eight-wave variant of the shape
   const void* w16;                      // conv_w16.hip layout [group of 64][chunk pair][phase][dy][16-cout block][lane][8] or null
   const float* bias;                    // [cout_pad] virtual order
   const float* prelu;                   // [cout_pad] or null
@@ -217,43 +214,6 @@ struct ConvArgs {
 // bytes of the fp16 plane a launch's pixel offsets must reach: all frames of the job, not only this launch's (frame lanes: lane 1 starts at n0 = N / 2)
 inline double conv_plane_span_f16(const ConvArgs& a) { return (double)std::max(a.n0 + a.N, a.job_n) * a.H * a.W * 32.0; }
 enum { DBG_NO_STORE = 1, DBG_NO_MMA = 2, DBG_NO_TILE_DMA = 4, DBG_NO_W_DMA = 8, DBG_NO_EPILOGUE = 16, DBG_STAMP = 32 };  // | tile-shape id << 8 (ss4k_bench_conv)
-
-// ---- cross-layer execution of a chain of plain 32-cout-wide convs as ONE persistent launch (conv_chain.hip) -------------
-// A chain is a list of ITEMS; an item is one conv layer restricted to one 32-cout group (a 64-cout layer = two items), over all
-// tiles.  Work units (item, tile) are handed out in order from a queue; a unit may read what earlier layers wrote on its 3 x 3
-// tile neighbourhood as soon as those units have finished - per-tile counters replace the kernel boundary.
-struct ChainItem {
-  const char* in0; size_t in0_plane_bytes; int in0_plane0, nchunks0;
-  const char* in1; size_t in1_plane_bytes; int in1_plane0, nchunks1;
-  const char* wpk;                      // this group's packed weights (ConvArgs.wpk + group offset)
-  const float* bias;                    // this group's 32 bias values (virtual cout order)
-  int act; float slope, alpha, gamma;   // ACT_NONE / ACT_LRELU only
-  const char* res1; size_t r1_plane_bytes; int r1_plane0;
-  const char* res2; size_t r2_plane_bytes; int r2_plane0;
-  char* out; size_t out_plane_bytes; int out_plane0;   // out_plane0: first plane of this GROUP
-  int newest;                           // first K-chunk whose plane the previous layer wrote (0: all of them)
-  unsigned need_old, need_new;          // units that must have finished on every tile of the 3 x 3 neighbourhood before chunk 0 /
-                                        // before chunk `newest` is read (and before anything is written)
-  unsigned pub_need;                    // > 0: this unit's counter add waits until its OWN tile's counter has reached pub_need (the
-                                        // second cout group of a layer publishes after the first, so that "layer's first unit
-                                        // done" can be read off the counter)
-  int pad_[2];
-};
-struct ChainArgs {
-  const ChainItem* items; int nitems;
-  unsigned* ctl;                        // [0] queue head, [1] error word, [4 ...] per-tile counters of finished units; zeroed per launch
-  unsigned* err_sticky;                 // device pointer of the model's sticky error word (pinned, host-mapped): OR-ed into when a unit
-                                        // times out, never reset by a launch
-  const char* zero_page;
-  int N, n0, H, W, tiles_x, tiles_y;
-  int grid;                             // > 0: workgroups to launch (default: one per workgroup slot)
-  int abl;                              // dev library: timing-only ablation build (conv_chain.hip)
-  unsigned spin_limit;                  // dev library: polls before a unit gives up (0 = SPIN_LIMIT); fault injection for the error path
-};
-// every unit of the chain: fp16, plain epilogue, cout group of 32.  rows_per_wave 4 or 5 (16- / 20-row tiles).
-void launch_conv_chain(ss4k_ctx* ctx, const ChainArgs& a, int rows_per_wave, hipStream_t st);
-size_t conv_chain_ctl_bytes(int ntiles);
-int conv_chain_tiles(int N, int H, int W, int rows_per_wave, int* tiles_x, int* tiles_y);
 
 // launchers (conv_mfma.hip)
 void launch_conv3x3(ss4k_ctx* ctx, const ConvArgs& a, int dtype, hipStream_t st);
@@ -282,7 +242,6 @@ struct DenseArgs {
   const char* in1; size_t in1_plane_bytes; int in1_plane0, nchunks1;
   const char* w1; const float* bias1;                   // conv_k: packed fragments (pack.cpp, nb = 1), 32 biases
   const char* w2; const float* bias2;                   // conv_{k+1}: nchunks0 + nchunks1 + 2 K-chunks
-  const char* w16p;                                     // conv_d16.hip: both layers' fragments (pack.cpp, pack_dense_d16) or null
   float slope;                                          // LeakyReLU of both layers
   char* out1; size_t out1_plane_bytes; int out1_plane0; // x_k (two planes)
   char* out2; size_t out2_plane_bytes; int out2_plane0; // x_{k+1}
@@ -294,9 +253,6 @@ struct DenseArgs {
   unsigned long long* dbg_buf;                          // dev library, SS4K_DENSE_STAMP=1: per-wave phase cycle counters
 };
 bool conv3x3_dense2_eligible(int nchunks_a, int cout_pad_a, int nchunks_b, int cout_pad_b);
-// the same fused pair on v_mfma_f32_16x16x32_f16 (conv_d16.hip): needs DenseArgs.w16p
-bool conv3x3_d16_eligible(int nchunks_a, int cout_pad_a, int nchunks_b, int cout_pad_b);
-void launch_conv3x3_d16(ss4k_ctx* ctx, const DenseArgs& a, hipStream_t st);
 // conv_dense.hip: one layer, 64 couts per workgroup, plain epilogue (bit-identical to conv_mfma.hip's <__half,2,4,4> build)
 struct ConvArgs;
 bool conv3x3_wide_eligible(const ConvArgs& a, int dtype);
@@ -310,12 +266,6 @@ bool conv3x3_w16n_eligible(const ConvArgs& a, int dtype);
 void launch_conv3x3_w16n(ss4k_ctx* ctx, const ConvArgs& a, hipStream_t st);
 
 int conv_cw(int dtype);  // channels per plane / K-chunk: 16
-// three-stage-ring build of the 32-cout tile body (conv_s3.hip)
-bool conv3x3_s3_eligible(const ConvArgs& a, int dtype);
-void launch_conv3x3_s3(ss4k_ctx* ctx, const ConvArgs& a, hipStream_t st);
-// register-stationary-weights kernel (conv_rs.hip): fp16, plain epilogue, selected layer shapes
-bool rs_config(int nplanes, int cout_pad, bool wide, int* nch, int* rows, int* cb, int* cg);
-void launch_conv3x3_rs(ss4k_ctx* ctx, const ConvArgs& a, hipStream_t st);
 inline int conv_rec_bytes(int dtype) { return dtype == SS4K_F16 ? 32 : 64; }  // bytes of one pixel's record in a plane
 
 // weight packing (pack.cpp) --------------------------------------------------------------
@@ -325,7 +275,6 @@ struct PackSpec {
   std::vector<int> cin_map;        // [nchunks * CW] logical cin of every channel slot the conv reads, -1 = none
   int nchunks0, nchunks1;          // how the chunks split over the two input segments
   int ps2;                         // virtual cout order [sub][c'] for PixelShuffle(2)
-  int force_nb1 = 0;               // pack a 64-cout layer as two 32-cout groups (conv_chain.hip runs every layer on the 32-cout tile body)
 };
 struct PackedConv {
   std::vector<uint8_t> w;          // device-order bytes
@@ -333,13 +282,9 @@ struct PackedConv {
   int cout_pad, nb, groups;
 };
 PackedConv pack_conv3x3(const PackSpec& s, const float* w_oihw, const float* bias, const float* prelu);
-// conv_rs.hip weight order for a layer shape <nch, rows, cb> (fp16 only); same virtual cout order / bias as pack_conv3x3
-std::vector<uint8_t> pack_conv3x3_rs(const PackSpec& s, const float* w_oihw, int cout_pad, int nch, int cb, int cg);
 // conv_w16.hip weight order (fp16, 64-cout groups, an even number of K-chunks); same virtual cout order / bias as pack_conv3x3
 std::vector<uint8_t> pack_conv3x3_w16(const PackSpec& s, const float* w_oihw, int cout_pad);
 std::vector<uint8_t> pack_conv3x3_w16n(const PackSpec& s, const float* w_oihw);   // one 16-cout block (conv_w16n.hip)
-// conv_d16.hip weight order of a dense-block layer pair
-std::vector<uint8_t> pack_dense_d16(const PackSpec& sa, const float* wa, const PackSpec& sb, const float* wb);
 int virt_to_real_cout(const PackSpec& s, int v);
 
 }  // namespace ss4k

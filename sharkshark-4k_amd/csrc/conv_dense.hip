@@ -483,7 +483,7 @@ static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 // rounding of a weight sum, a different order of fp32 additions); SS4K_MODEL_NO_UPS_PRESUM selects the direct form.
 // RL: res1 is the layer's own input tensor and the first four K-chunks are its planes (conv5 of an RDB: out = conv * alpha + x, no
 // activation): x's centre pixels are in LDS as part of those chunks, so they are added to the accumulators there - one more MFMA per
-// output row and chunk with a (1 / alpha) * I fragment on the centre tap, as conv_rs.hip does - instead of being read from memory a
+// output row and chunk with a (1 / alpha) * I fragment on the centre tap - instead of being read from memory a
 // second time in the epilogue (measured on the layer in isolation: 225 -> 210 us per 4 frames, tools/conv5_routes.py).
 template <bool UPS, bool RL = false>
 __global__ __launch_bounds__(64 * NW, 2) void conv3x3_wide_kernel(const ConvArgs a) {

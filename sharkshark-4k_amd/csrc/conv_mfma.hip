@@ -724,13 +724,7 @@ void launch_conv3x3(ss4k_ctx* ctx, const ConvArgs& a0, int dtype, hipStream_t st
   ConvArgs a = a0;
   a.tiles_x = (a.W + TW - 1) / TW;
   a.zero_page = ctx->zero_page();
-#ifdef SS4K_DEV
-  const bool split64 = a.cout_pad == -64;   // dev experiment (models.cpp SS4K_SPLIT64): 64 couts as two 32-cout groups
-  if (split64) a.cout_pad = 64;
-#else
-  constexpr bool split64 = false;
-#endif
-  const int nb = (a.cout_pad <= 32 || split64) ? 1 : 2;
+  const int nb = a.cout_pad <= 32 ? 1 : 2;
   const int groups = (a.cout_pad + nb * 32 - 1) / (nb * 32);
   SS4K_REQUIRE(a.N > 0 && a.H > 0 && a.W > 0, "conv3x3: empty grid");
   SS4K_REQUIRE(a.act != ACT_LRELU || (a.slope >= 0.f && a.slope <= 1.f), "conv3x3: LeakyReLU slope must be in [0,1]");
@@ -738,12 +732,6 @@ void launch_conv3x3(ss4k_ctx* ctx, const ConvArgs& a0, int dtype, hipStream_t st
   SS4K_REQUIRE((double)a.N * a.H * a.W < 2147483648.0, "conv3x3: a plane holds at most 2^31 pixels");
   ProfScope prof(ctx, st, PROF_CONV);
   // fp16 tile shapes <couts/32, rows per wave, waves>; see DESIGN.md 4.3 and profiles/NOTES_r01_r03.md 4.1 for how they were chosen
-#ifdef SS4K_DEV
-  // dev library: fp16 layers of a supported shape with a plain epilogue on the register-stationary kernel (conv_rs.hip)
-  if (a.wrs && dtype == SS4K_F16 && !a.dbg && a.epi == EPI_NHWC && !a.bsvd_resid && a.act != ACT_RELU6) {
-    launch_conv3x3_rs(ctx, a, st);
-  } else
-#endif
   if (nb == 1 && conv3x3_w16n_eligible(a, dtype)) {
     launch_conv3x3_w16n(ctx, a, st);   // <= 4 output channels, NCHW fp32 hand-off: one 16-cout block on the 16x16x32 MFMA (conv_w16n.hip)
   } else if (a.wide && nb == 2 && conv3x3_w16_eligible(a, dtype)) {
@@ -799,9 +787,6 @@ void launch_conv3x3(ss4k_ctx* ctx, const ConvArgs& a0, int dtype, hipStream_t st
     const bool mb5 = dtype == SS4K_F16 && nb == 1 && ek == EK_PLAIN &&
                      (a.mb_override ? a.mb_override == 5 : (waste(20) < waste(16) - 1e-9 && tiles20 >= 2LL * ctx->num_cu));
 #ifdef SS4K_DEV
-    // experiment (SS4K_S3=1, dev library): three-stage ring of halo tiles, conv_s3.hip
-    if (a.s3 && conv3x3_s3_eligible(a, dtype)) launch_conv3x3_s3(ctx, a, st);
-    else
     // experiment (SS4K_MB=3, dev library): 12-row tiles at THREE workgroups per CU for the 32-cout layers
     if (a.mb_override == 3 && dtype == SS4K_F16 && nb == 1 && ek == EK_PLAIN) launch_t<__half, 1, 3, 4, 0, EK_PLAIN>(ctx, a, groups, st);
     else

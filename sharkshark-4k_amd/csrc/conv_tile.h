@@ -1,5 +1,5 @@
-// Building blocks shared by the 3x3 conv kernels of conv_mfma.hip (one launch per layer) and conv_chain.hip (the RRDB body as one
-// persistent launch): tile geometry, LDS-DMA, record loads / stores, the MFMA wrapper.  Device code, gfx950 only.
+// Building blocks of the 3x3 conv kernels of conv_mfma.hip: tile geometry, LDS-DMA, record loads / stores, the MFMA wrapper.
+// Device code, gfx950 only.
 #pragma once
 #include "common.h"
 

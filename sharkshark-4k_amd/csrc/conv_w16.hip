@@ -3,14 +3,14 @@
 //
 // Why.  The part runs these layers at its 1400 W cap (profiles/earlier/r04/r04_headline_power_clock.txt: 1.82 of 2.4 GHz through the whole timed
 // loop), and at equal cycles per FLOP the 16x16x32 shape costs less energy: 1.12-1.14 x the FLOP/s under the cap with operands
-// re-read from LDS at this loop's reuse ratios (tools/micro/mfma_shapes.hip).  conv_rs.hip has used the shape since round 2, paying for
+// re-read from LDS at this loop's reuse ratios (tools/micro/mfma_shapes.hip).  The register-stationary kernel of rounds 2-5 (removed) used the shape, paying for
 // its K = 32 with 64-byte-per-pixel halo stages (one tap x TWO planes per MFMA) and one workgroup per CU.  Here K = 32 is
 //   * two horizontally adjacent taps of ONE plane - (dx 0, dx 1) x 16 channels: the operand of k-group kg = lane >> 4 is the 16-byte
 //     half (kg & 1) of pixel column + (kg >> 1), so the planes stay 32-byte records in LDS and a halo tile stays 19 KB;
 //   * and, for the third tap column, dx 2 of TWO planes: k-groups 2, 3 read the same pixel of the other tile buffer.
 // A pair of K-chunks (planes 2q, 2q + 1; buffer 0 always holds the even plane, buffer 1 the odd one) is three PHASES:
 //   phase 0: plane 2q, taps (dx 0, dx 1)      phase 1: planes 2q and 2q + 1, tap dx 2      phase 2: plane 2q + 1, taps (dx 0, dx 1)
-// each 3 (dy) x 4 (16-cout blocks) weight fragments = 12 KB, 96 MFMAs per wave, no padded K anywhere (conv_rs.hip's intra-plane
+// each 3 (dy) x 4 (16-cout blocks) weight fragments = 12 KB, 96 MFMAs per wave, no padded K anywhere (the register-stationary kernel's intra-plane
 // pairing of nine taps would waste 1 in 10).  A wave owns 8 rows x 32 pixels x 32 couts (waves 0, 1: rows 0-7 / 8-15 of the group's first
 // two 16-cout blocks, waves 2, 3: of the other two): 128 accumulator registers, six weight fragments live (twelve - every wave all 64
 // couts on 4 rows - spilled 69 registers), an activation fragment (16 pixels x K 32) feeds 3 dy x 2 blocks = 6 MFMAs of 16 cycles, a
@@ -22,7 +22,7 @@
 // of a half-wave, i.e. sixteen consecutive pixels with halves (0 x 4, 1 x 8, 0 x 4) - distinct bank quads exactly when pixel c and
 // pixel c + 8 sit in the same half order.
 // Results: NOT bit-identical to the 32x32x16 kernels (an MFMA sums 32 products of two taps where the other sums 16 of one); within
-// fp32 accumulation noise of them (tests/test_gpu_w16.py) - the same relation conv_rs.hip's results have to conv_mfma.hip's.
+// fp32 accumulation noise of them (tests/test_gpu_w16.py).
 #include "common.h"
 #include <cmath>
 #include "conv_tile.h"
@@ -57,7 +57,7 @@ __device__ __forceinline__ f32x4 mma16(const uint4& w, const uint4& x, f32x4 acc
 //   STAMP (dev library, SS4K_W16_STAMP=1): per-wave cycle totals of the tile's parts (s_memtime), see launch_conv3x3_w16
 //   RL: res1 is the layer's own input tensor and its first four K-chunks are that tensor's planes (conv5 of an RDB: out = conv * alpha + x,
 //   no activation): x's centre pixels pass through LDS as the dx 1 half of phases 0 / 2 of the first two chunk pairs, so they are added
-//   there - one more MFMA per accumulator with a (1 / alpha) I fragment on tap (dy 1, dx 1), as conv_rs.hip and the wide kernel do -
+//   there - one more MFMA per accumulator with a (1 / alpha) I fragment on tap (dy 1, dx 1), as the wide kernel does -
 //   instead of being read from memory again in the epilogue.  Output plane P = 2 jw + (kg >> 1) is input plane P: wave pair jw adds during
 //   chunk pair q == jw, rows of row groups kg >> 1 == 0 in phase 0 (plane 2 jw), kg >> 1 == 1 in phase 2 (plane 2 jw + 1).
 template <bool STAMP = false, bool RL = false>
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3x3_w16_kernel(const ConvArgs 
     for (int e = 0; e < 2; ++e) wf[dy][e] = *reinterpret_cast<const uint4*>(smem + W_OFF + wsub + (dy * 4 + e) * 1024);
 
   while (true) {
-    f32x4 acc[MB][2][2];   // [output row][pixel half][block 2 jw + e]; written whole by its first MFMA of the tile (C = the bias, as conv_rs.hip does)
+    f32x4 acc[MB][2][2];   // [output row][pixel half][block 2 jw + e]; written whole by its first MFMA of the tile (C = the bias)
     f32x4 bias4[2];
     {
       const float4* bp = reinterpret_cast<const float4*>(smem + B_OFF + kg * 16 + jw * 128);

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(64 * NW, 3) void conv3x3_w16n_kernel(const ConvArgs
   };
   auto tile_src = [&](int k, int n, int y0, int x0) __attribute__((always_inline)) -> uint32_t {
     int ln = lane;
-    asm volatile("" : "+v"(ln));   // computed where it is used (conv_d16.hip)
+    asm volatile("" : "+v"(ln));   // computed where it is used
     const int s = k * 64 + ln;
     const int p = s >> 1, gq = s & 1;
     const int row = p / XW, x = p - row * XW;

@@ -2,9 +2,6 @@
 // the kernels in conv_mfma.hip / fsrcnn.hip.  Weights arrive as the reference's state_dict
 // flattened in key order (see sharkshark-4k_amd/weights.py) and are repacked once at creation.
 #include "models.h"
-#ifdef SS4K_DEV
-#include "chain_plan.h"
-#endif
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -103,12 +100,7 @@ static void upload(DevBuf& b, const void* src, size_t bytes) {
   SS4K_HIP(hipMemcpy(b.ptr, src, bytes, hipMemcpyHostToDevice));
 }
 
-#ifdef SS4K_DEV
-// bit of a layer shape in Model::rs_mask: 0-2 = 32 couts with 2/3/4 K-chunks (RDB conv1-3), 3 = conv4, 4 = 64->64, 5 = conv5
-static int rs_shape_bit(int nch, int cout_pad) { return cout_pad == 32 ? nch - 2 : (nch == 2 ? 4 : 5); }
-#endif
-
-int Model::add_conv(ParamCursor& pc, int cout, int cin_total, PackSpec s, bool has_prelu_after, bool allow_rs, bool chainable) {
+int Model::add_conv(ParamCursor& pc, int cout, int cin_total, PackSpec s, bool has_prelu_after) {
   s.dtype = desc.dtype; s.cout_real = cout; s.cin_total = cin_total;
   const float* w = pc.take((size_t)cout * cin_total * 9);
   const float* b = pc.take(cout);
@@ -118,24 +110,6 @@ int Model::add_conv(ParamCursor& pc, int cout, int cin_total, PackSpec s, bool h
   upload(L.w, p.w.data(), p.w.size());
   upload(L.bias, p.bias.data(), p.bias.size() * 4);
   if (a) upload(L.prelu, p.prelu.data(), p.prelu.size() * 4);
-#ifdef SS4K_DEV   // conv_rs.hip (register-stationary weights) and conv_chain.hip (cross-layer chain): dev library only since round 5
-  int nch, rows, cb, cg;
-  if (allow_rs && use_rs && desc.dtype == SS4K_F16 && rs_config(s.nchunks0 + s.nchunks1, p.cout_pad, rs_wide, &nch, &rows, &cb, &cg) &&
-      (rs_mask >> rs_shape_bit(nch, p.cout_pad)) & 1) {
-    const std::vector<uint8_t> wr = pack_conv3x3_rs(s, w, p.cout_pad, nch, cb, cg);
-    upload(L.wrs, wr.data(), wr.size());
-    weight_bytes += wr.size();
-    L.rs_wide = rs_wide;
-  }
-  if (chainable && chain_mode == 2 && desc.dtype == SS4K_F16 && p.nb == 2) {
-    PackSpec s1 = s; s1.force_nb1 = 1;
-    const PackedConv p1 = pack_conv3x3(s1, w, b, a);
-    upload(L.wch, p1.w.data(), p1.w.size());
-    weight_bytes += p1.w.size();
-  }
-#else
-  (void)allow_rs; (void)chainable;
-#endif
   if (use_w16 && use_wide && desc.dtype == SS4K_F16 && p.nb == 2 && p.cout_pad % 64 == 0 && (s.nchunks0 + s.nchunks1) % 2 == 0 && !s.ps2) {
     const std::vector<uint8_t> w6 = pack_conv3x3_w16(s, w, p.cout_pad);
     upload(L.w16, w6.data(), w6.size());
@@ -152,18 +126,6 @@ int Model::add_conv(ParamCursor& pc, int cout, int cin_total, PackSpec s, bool h
   L.cin_real = 0;
   for (int c : s.cin_map) L.cin_real += c >= 0;
   weight_bytes += p.w.size() + p.bias.size() * 4;
-#ifdef SS4K_DEV
-  // dev experiment (SS4K_D16=1): a dense-block pair (this layer = conv_{k+1} of the previous one) once more in conv_d16.hip's order
-  if (chainable && use_d16 && use_w16 && desc.dtype == SS4K_F16 && !layers.empty() && raw_w_prev && (int)layers.size() == raw_li_prev + 1 &&
-      conv3x3_d16_eligible(layers.back().nchunks0 + layers.back().nchunks1, layers.back().cout_pad, s.nchunks0 + s.nchunks1, p.cout_pad) &&
-      layers.back().nchunks0 == s.nchunks0 && !layers.back().w16p_is_second) {
-    const std::vector<uint8_t> wp = pack_dense_d16(raw_s_prev, raw_w_prev, s, w);
-    upload(layers.back().w16p, wp.data(), wp.size());
-    weight_bytes += wp.size();
-    L.w16p_is_second = true;
-  }
-  raw_w_prev = chainable ? w : nullptr; raw_s_prev = s; raw_li_prev = (int)layers.size();
-#endif
   layers.push_back(std::move(L));
   return (int)layers.size() - 1;
 }
@@ -212,14 +174,7 @@ void Model::build(const float* w, size_t n) {
   // can also be set from the environment of a deployed service: SS4K_LANES (0 = measured per shape, 1 = one
   // launch chain, 2 = two) and SS4K_FS_EXACT=1.  The measurement-only switches exist in the dev library alone.
   const int fl = desc.flags;
-#ifdef SS4K_DEV
-  SS4K_REQUIRE((fl & ~(SS4K_MODEL_FLAGS_ALL | SS4K_DEV_MODEL_FLAGS_ALL)) == 0, "desc.flags: unknown SS4K_MODEL_* / SS4K_DEV_MODEL_* bit");
-  SS4K_REQUIRE(!((fl & SS4K_DEV_MODEL_CHAIN) && (fl & SS4K_DEV_MODEL_CONV5_RS)), "desc.flags: the chain runs every layer on the 32-cout LDS-weights tile: CHAIN and CONV5_RS exclude each other");
-  if (fl & SS4K_DEV_MODEL_CHAIN) chain_mode = 2;
-  if (fl & SS4K_DEV_MODEL_CONV5_RS) { use_rs = true; conv5_mode = 1; }
-#else
   SS4K_REQUIRE((fl & ~SS4K_MODEL_FLAGS_ALL) == 0, "desc.flags: unknown SS4K_MODEL_* bit (bits 8, 64, 128, 2048 and 16384 were retired with ABI 3)");
-#endif
   SS4K_REQUIRE(!((fl & SS4K_MODEL_ONE_CHAIN) && (fl & SS4K_MODEL_TWO_CHAINS)), "desc.flags: ONE_CHAIN and TWO_CHAINS exclude each other");
   SS4K_REQUIRE(!((fl & SS4K_MODEL_TILE_ROWS_16) && (fl & SS4K_MODEL_TILE_ROWS_20)), "desc.flags: TILE_ROWS_16 and TILE_ROWS_20 exclude each other");
   if (fl & SS4K_MODEL_FS_EXACT) fs_exact = true;
@@ -239,18 +194,13 @@ void Model::build(const float* w, size_t n) {
 #ifdef SS4K_DEV
   if (const char* e = std::getenv("SS4K_NO_FLIP")) flip_walk = !(e[0] == '1');  // A/B switch for the tile-walk direction
   if (const char* e = std::getenv("SS4K_SUBBATCH")) sub_batch = std::atoi(e);   // A/B switch: frames per pass through the network
-  if (const char* e = std::getenv("SS4K_RS_MASK")) { rs_mask = std::atoi(e); use_rs = rs_mask != 0; }   // A/B switch: which layer shapes take conv_rs.hip
-  if (const char* e = std::getenv("SS4K_RS_W8")) rs_wide = e[0] == '1';          // A/B switch: eight-wave variants of the 32-cout shapes
   if (const char* e = std::getenv("SS4K_MB")) mb_override = std::atoi(e);
-  if (const char* e = std::getenv("SS4K_S3")) use_s3 = e[0] == '1';
   if (const char* e = std::getenv("SS4K_DENSE_MASK")) dense_mask = std::atoi(e);   // A/B switch: which layer pairs of an RDB run fused
   if (const char* e = std::getenv("SS4K_UPS_PRESUM")) ups_presum = e[0] == '1';   // A/B switch: pre-summed weights in the up-sampling convs
-  if (const char* e = std::getenv("SS4K_CONV5_MODE")) { conv5_mode = std::atoi(e); use_rs = use_rs || conv5_mode == 1; }   // A/B switch: 0 default, 1 always conv_rs.hip
   if (const char* e = std::getenv("SS4K_NO_RL")) no_rl = e[0] == '1';              // A/B switch: conv5's residual read from memory in the epilogue
   if (const char* e = std::getenv("SS4K_WIDE_RL")) wide_rl = e[0] == '1';          // A/B switch: conv5's residual through the matrix core on the wide kernel
   if (const char* e = std::getenv("SS4K_WIDE")) use_wide = e[0] == '1';            // A/B switch: 64-cout layers on conv3x3_wide_kernel
   if (const char* e = std::getenv("SS4K_W16")) use_w16 = e[0] == '1';              // A/B switch: ... on conv3x3_w16_kernel
-  if (const char* e = std::getenv("SS4K_D16")) use_d16 = e[0] == '1';              // A/B switch: fused pairs on conv3x3_d16_kernel
   if (const char* e = std::getenv("SS4K_DENSE_MODE")) dense_mode = std::atoi(e);   // A/B switch: 0 default policy, 1 never, 2 every job
   if (const char* e = std::getenv("SS4K_LANE_GRID")) lane_grid_share = (float)std::atof(e);   // A/B switch: grid of a lane's launch as a share of the chip's slots
   if (const char* e = std::getenv("SS4K_FAIL_AT_CONV")) fail_at_conv = std::atoi(e);   // fault injection: the k-th conv call of every
@@ -338,14 +288,14 @@ void Model::build(const float* w, size_t n) {
       for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 5; ++c) {
           const int co = c < 4 ? g : nf;
-          add_conv(pc, co, nf + c * g, c == 0 ? spec_plain(nf) : spec_concat(nf, c * g), false, /*allow_rs=*/true, /*chainable=*/true);
+          add_conv(pc, co, nf + c * g, c == 0 ? spec_plain(nf) : spec_concat(nf, c * g), false);
         }
-    for (int i = 0; i < 4; ++i) add_conv(pc, nf, nf, spec_plain(nf), false, /*allow_rs=*/true);
+    for (int i = 0; i < 4; ++i) add_conv(pc, nf, nf, spec_plain(nf), false);
     add_conv(pc, 3, nf, spec_plain(nf), false);
   } else if (desc.kind == SS4K_SRVGG) {
     const int nf = desc.num_feat;
     add_conv(pc, nf, 3, spec_plain(3), true);
-    for (int i = 0; i < desc.num_block; ++i) add_conv(pc, nf, nf, spec_plain(nf), true, /*allow_rs=*/true);
+    for (int i = 0; i < desc.num_block; ++i) add_conv(pc, nf, nf, spec_plain(nf), true);
     add_conv(pc, 3 * desc.scale * desc.scale, nf, spec_plain(nf), false);
   } else {  // BSVD
     for (int blk = 0; blk < 2; ++blk) {
@@ -363,57 +313,16 @@ void Model::build(const float* w, size_t n) {
 }
 
 // ------------------------------------------------------------------------------------------
-void Model::conv(int li, const Tens& in0, const Tens* in1, int N, int H, int W, const ConvOpts& o, hipStream_t st) {
-  if (plan_only) return;
-#ifdef SS4K_DEV
-  if (fail_at_conv > 0 && ++conv_calls == fail_at_conv) throw Error(SS4K_EINVAL, "injected failure (SS4K_FAIL_AT_CONV)");
-#endif
-  const ConvLayer& L = layers[li];
-  ConvArgs a{};
-  a.in0 = in0.p; a.in0_plane_bytes = in0.plane_bytes; a.in0_plane0 = in0.plane0; a.nchunks0 = L.nchunks0;
-  if (in1) { a.in1 = in1->p; a.in1_plane_bytes = in1->plane_bytes; a.in1_plane0 = in1->plane0; a.nchunks1 = L.nchunks1; }
-  SS4K_REQUIRE((in1 != nullptr) == (L.nchunks1 > 0), "internal: conv segment mismatch");
-  a.N = N; a.job_n = N; a.H = H; a.W = W; a.ups2 = o.ups2;
-  a.wpk = L.w.ptr; a.wrs = L.wrs.ptr; a.w16 = L.w16.ptr; a.rs_wide = L.rs_wide ? 1 : 0; a.bias = L.bias.as<float>(); a.prelu = L.has_prelu ? L.prelu.as<float>() : nullptr; a.prelu_le1 = L.prelu_le1 ? 1 : 0;
-  a.act = o.act; a.slope = o.slope; a.alpha = o.alpha; a.gamma = o.gamma;
-  if (o.res1) { a.res1 = o.res1->p; a.r1_plane_bytes = o.res1->plane_bytes; a.r1_plane0 = o.res1->plane0; }
-  if (o.res2) { a.res2 = o.res2->p; a.r2_plane_bytes = o.res2->plane_bytes; a.r2_plane0 = o.res2->plane0; }
-  a.bsvd_resid = o.bsvd_resid;
-  a.epi = o.epi; a.out = o.out.p; a.out_plane_bytes = o.out.plane_bytes; a.out_plane0 = o.out.plane0;
-  a.cout_real = L.cout_real; a.cout_pad = L.cout_pad;
-  a.dbg = dbg; a.dbg_buf = dbg_buf; a.mb_override = mb_override; a.s3 = use_s3 ? 1 : 0; a.wide = use_wide ? 1 : 0; a.ups_presum = ups_presum ? 1 : 0; a.wide_rl = wide_rl ? 1 : 0;
-#ifdef SS4K_DEV
-  static const bool no_band = std::getenv("SS4K_NO_BAND") && std::getenv("SS4K_NO_BAND")[0] == '1';
-  a.no_band = no_band ? 1 : 0;
-#endif
-  a.reverse = (flip_walk && (launch_parity ^= 1)) ? 1 : 0;
-  const double flops = 2.0 * 9.0 * L.cin_real * L.cout_real * (double)H * W * (o.epi == EPI_NHWC_SUB2 ? 0.25 : 1.0);
+template <typename Args, typename Launch>
+void Model::launch_lanes(Args& a, double flops_per_frame, int N, hipStream_t st, Launch launch) {
   if (ctx->prof && !section_open) {   // conv section of this forward: first conv launch ... end of the last one, on the caller's stream
     section = ctx->prof_get_events();
     SS4K_HIP(hipEventRecord(section.a, st));
     section_open = true;
   }
-#ifdef SS4K_DEV
-  if (chain_rec) {
-    a.flops = flops * N;
-    chain_record(a, L);
-    return;
-  }
-  // experiment: a 64-cout body layer as two 32-cout groups on the per-launch path (what the chain does to conv5)
-  static const bool split64 = std::getenv("SS4K_SPLIT64") && std::getenv("SS4K_SPLIT64")[0] == '1';
-  if (split64 && L.wch.ptr && a.cout_pad == 64 && a.epi == EPI_NHWC) { a.wpk = L.wch.ptr; a.wrs = nullptr; a.cout_pad = -64; }
-#endif
-  // conv5 of an RDB (residual = the conv's own input): on the 64-cout tile with the residual through the matrix core (conv_w16.hip; under
-  // SS4K_MODEL_NO_W16 conv_dense.hip's wide kernel), for EVERY job size - two workgroups per CU that co-reside with the fused dense-block
-  // launches of the other launch chain.  A frame's bits therefore never depend on the size of the job it arrived in.  (Rounds 2-4 also had a
-  // register-stationary kernel for this layer, conv_rs.hip: dev library only since round 5, SS4K_DEV_MODEL_CONV5_RS.)
-  if (use_wide && !no_rl && !(a.wrs && conv5_mode == 1) && a.res1 && a.act == ACT_NONE && a.nchunks0 == 4 && a.cout_pad == 64 && !a.ups2 &&
-      a.res1 + (size_t)a.r1_plane0 * a.r1_plane_bytes == a.in0 + (size_t)a.in0_plane0 * a.in0_plane_bytes) {
-    a.wrs = nullptr; a.wide_rl = 1;
-  }
   if (cur_lanes <= 1 || N != cur_n) {
-    a.flops = flops * N;
-    launch_conv3x3(ctx, a, desc.dtype, st);
+    a.n0 = 0; a.N = N; a.flops = flops_per_frame * N;
+    launch(a, st);
     return;
   }
   // frame lanes: lane l takes frames [N*l/2, N*(l+1)/2): lane 0 on the caller's stream, lane 1 on the context's lane stream
@@ -425,9 +334,44 @@ void Model::conv(int li, const Tens& in0, const Tens* in1, int N, int H, int W, 
   for (int l = 0; l < 2; ++l) {
     a.n0 = N * l / 2; a.N = N * (l + 1) / 2 - a.n0;
     a.grid_share = lane_grid_share;
-    a.flops = flops * a.N;
-    launch_conv3x3(ctx, a, desc.dtype, l == 0 ? st : ctx->lane_stream());
+    a.flops = flops_per_frame * a.N;
+    launch(a, l == 0 ? st : ctx->lane_stream());
   }
+}
+
+void Model::conv(int li,const Tens& in0, const Tens* in1, int N, int H, int W, const ConvOpts& o, hipStream_t st) {
+  if (plan_only) return;
+#ifdef SS4K_DEV
+  if (fail_at_conv > 0 && ++conv_calls == fail_at_conv) throw Error(SS4K_EINVAL, "injected failure (SS4K_FAIL_AT_CONV)");
+#endif
+  const ConvLayer& L = layers[li];
+  ConvArgs a{};
+  a.in0 = in0.p; a.in0_plane_bytes = in0.plane_bytes; a.in0_plane0 = in0.plane0; a.nchunks0 = L.nchunks0;
+  if (in1) { a.in1 = in1->p; a.in1_plane_bytes = in1->plane_bytes; a.in1_plane0 = in1->plane0; a.nchunks1 = L.nchunks1; }
+  SS4K_REQUIRE((in1 != nullptr) == (L.nchunks1 > 0), "internal: conv segment mismatch");
+  a.N = N; a.job_n = N; a.H = H; a.W = W; a.ups2 = o.ups2;
+  a.wpk = L.w.ptr; a.w16 = L.w16.ptr; a.bias = L.bias.as<float>(); a.prelu = L.has_prelu ? L.prelu.as<float>() : nullptr; a.prelu_le1 = L.prelu_le1 ? 1 : 0;
+  a.act = o.act; a.slope = o.slope; a.alpha = o.alpha; a.gamma = o.gamma;
+  if (o.res1) { a.res1 = o.res1->p; a.r1_plane_bytes = o.res1->plane_bytes; a.r1_plane0 = o.res1->plane0; }
+  if (o.res2) { a.res2 = o.res2->p; a.r2_plane_bytes = o.res2->plane_bytes; a.r2_plane0 = o.res2->plane0; }
+  a.bsvd_resid = o.bsvd_resid;
+  a.epi = o.epi; a.out = o.out.p; a.out_plane_bytes = o.out.plane_bytes; a.out_plane0 = o.out.plane0;
+  a.cout_real = L.cout_real; a.cout_pad = L.cout_pad;
+  a.dbg = dbg; a.dbg_buf = dbg_buf; a.mb_override = mb_override; a.wide = use_wide ? 1 : 0; a.ups_presum = ups_presum ? 1 : 0; a.wide_rl = wide_rl ? 1 : 0;
+#ifdef SS4K_DEV
+  static const bool no_band = std::getenv("SS4K_NO_BAND") && std::getenv("SS4K_NO_BAND")[0] == '1';
+  a.no_band = no_band ? 1 : 0;
+#endif
+  a.reverse = (flip_walk && (launch_parity ^= 1)) ? 1 : 0;
+  const double flops = 2.0 * 9.0 * L.cin_real * L.cout_real * (double)H * W * (o.epi == EPI_NHWC_SUB2 ? 0.25 : 1.0);
+  // conv5 of an RDB (residual = the conv's own input): on the 64-cout tile with the residual through the matrix core (conv_w16.hip; under
+  // SS4K_MODEL_NO_W16 conv_dense.hip's wide kernel), for EVERY job size - two workgroups per CU that co-reside with the fused dense-block
+  // launches of the other launch chain.  A frame's bits therefore never depend on the size of the job it arrived in.
+  if (use_wide && !no_rl && a.res1 && a.act == ACT_NONE && a.nchunks0 == 4 && a.cout_pad == 64 && !a.ups2 &&
+      a.res1 + (size_t)a.r1_plane0 * a.r1_plane_bytes == a.in0 + (size_t)a.in0_plane0 * a.in0_plane_bytes) {
+    a.wide_rl = 1;
+  }
+  launch_lanes(a, flops, N, st, [&](const ConvArgs& la, hipStream_t s) { launch_conv3x3(ctx, la, desc.dtype, s); });
 }
 
 // ---- fused layer pair (conv_pair.hip) ---------------------------------------------------------------------------------
@@ -453,27 +397,7 @@ bool Model::conv_pair(int li, const Tens& in0, int N, int H, int W, const ConvOp
   a.cout_real = B.cout_real;
   a.H = H; a.W = W;
   const double flops = 2.0 * 9.0 * ((double)A.cin_real * A.cout_real + (double)B.cin_real * B.cout_real) * (double)H * W;
-  if (ctx->prof && !section_open) {
-    section = ctx->prof_get_events();
-    SS4K_HIP(hipEventRecord(section.a, st));
-    section_open = true;
-  }
-  if (cur_lanes <= 1 || N != cur_n) {
-    a.n0 = 0; a.N = N; a.flops = flops * N;
-    launch_conv3x3_pair(ctx, a, st);
-    return true;
-  }
-  if (!forked) {
-    SS4K_HIP(hipEventRecord(ctx->lane_fork(), st));
-    SS4K_HIP(hipStreamWaitEvent(ctx->lane_stream(), ctx->lane_fork(), 0));
-    forked = true;
-  }
-  for (int l = 0; l < 2; ++l) {
-    a.n0 = N * l / 2; a.N = N * (l + 1) / 2 - a.n0;
-    a.grid_share = lane_grid_share;
-    a.flops = flops * a.N;
-    launch_conv3x3_pair(ctx, a, l == 0 ? st : ctx->lane_stream());
-  }
+  launch_lanes(a, flops, N, st, [&](const PairArgs& la, hipStream_t s) { launch_conv3x3_pair(ctx, la, s); });
   return true;
 }
 
@@ -484,7 +408,7 @@ bool Model::conv_dense(int li, const Tens& in0, const Tens* in1, int N, int H, i
   // default: fused.  Measured on the headline network (tools/env_ab.py SS4K_DENSE_MODE, one box, interleaved): 4-frame jobs + 2.4 %,
   // 2-frame jobs + 3.0 %, one-frame jobs + 11.5 % (nothing else covers their launch boundaries and partly filled rounds of tiles)
   const bool want = dense_mode != 1;
-  if (!want || !(dense_mask & pair_bit) || desc.dtype != SS4K_F16 || dbg || chain_rec || A.has_prelu || B.has_prelu || A.nchunks0 != B.nchunks0 ||
+  if (!want || !(dense_mask & pair_bit) || desc.dtype != SS4K_F16 || dbg || A.has_prelu || B.has_prelu || A.nchunks0 != B.nchunks0 ||
       !conv3x3_dense2_eligible(A.nchunks0 + A.nchunks1, A.cout_pad, B.nchunks0 + B.nchunks1, B.cout_pad) ||
       (double)N * H * W * rec() >= 4294967296.0)   // the fused kernel keeps 32-bit byte offsets inside a plane: bigger planes take four launches
     return false;
@@ -498,152 +422,14 @@ bool Model::conv_dense(int li, const Tens& in0, const Tens* in1, int N, int H, i
   if (in1) { a.in1 = in1->p; a.in1_plane_bytes = in1->plane_bytes; a.in1_plane0 = in1->plane0; a.nchunks1 = A.nchunks1; }
   a.w1 = A.w.as<char>(); a.bias1 = A.bias.as<float>();
   a.w2 = B.w.as<char>(); a.bias2 = B.bias.as<float>();
-  a.w16p = A.w16p.ptr ? A.w16p.as<char>() : nullptr;
   a.slope = slope;
   a.out1 = out1.p; a.out1_plane_bytes = out1.plane_bytes; a.out1_plane0 = out1.plane0;
   a.out2 = out2.p; a.out2_plane_bytes = out2.plane_bytes; a.out2_plane0 = out2.plane0;
   a.H = H; a.W = W;
   a.reverse = (flip_walk && (launch_parity ^= 1)) ? 1 : 0;
   const double flops = 2.0 * 9.0 * ((double)A.cin_real * A.cout_real + (double)B.cin_real * B.cout_real) * (double)H * W;
-  if (ctx->prof && !section_open) {
-    section = ctx->prof_get_events();
-    SS4K_HIP(hipEventRecord(section.a, st));
-    section_open = true;
-  }
-  if (cur_lanes <= 1 || N != cur_n) {
-    a.n0 = 0; a.N = N; a.flops = flops * N;
-#ifdef SS4K_DEV
-    if (a.w16p) { launch_conv3x3_d16(ctx, a, st); return true; }
-#endif
-    launch_conv3x3_dense2(ctx, a, st);
-    return true;
-  }
-  if (!forked) {
-    SS4K_HIP(hipEventRecord(ctx->lane_fork(), st));
-    SS4K_HIP(hipStreamWaitEvent(ctx->lane_stream(), ctx->lane_fork(), 0));
-    forked = true;
-  }
-  for (int l = 0; l < 2; ++l) {
-    a.n0 = N * l / 2; a.N = N * (l + 1) / 2 - a.n0;
-    a.grid_share = lane_grid_share;
-    a.flops = flops * a.N;
-#ifdef SS4K_DEV
-    if (a.w16p) { launch_conv3x3_d16(ctx, a, l == 0 ? st : ctx->lane_stream()); continue; }
-#endif
-    launch_conv3x3_dense2(ctx, a, l == 0 ? st : ctx->lane_stream());
-  }
+  launch_lanes(a, flops, N, st, [&](const DenseArgs& la, hipStream_t s) { launch_conv3x3_dense2(ctx, la, s); });
   return true;
-}
-
-#ifdef SS4K_DEV
-// ---- cross-layer chain (conv_chain.hip; dev library only) -----------------------------------------------------------------
-void Model::chain_record(const ConvArgs& a, const ConvLayer& L) {
-  SS4K_REQUIRE(desc.dtype == SS4K_F16 && a.epi == EPI_NHWC && !a.bsvd_resid && !a.ups2 && !a.prelu &&
-               (a.act == ACT_NONE || a.act == ACT_LRELU) && (a.cout_pad == 32 || a.cout_pad == 64),
-               "internal: layer cannot run in a conv chain");
-  SS4K_REQUIRE(a.cout_pad == 32 || L.wch.ptr, "internal: 64-cout chain layer without its two-group weights");
-  const int nch = a.nchunks0 + a.nchunks1, groups = a.cout_pad / 32;
-  SS4K_REQUIRE(nch >= 3, "internal: chain layer with fewer than three K-chunks");
-  const char* wbase = a.cout_pad == 32 ? reinterpret_cast<const char*>(a.wpk) : L.wch.as<char>();
-  ChainLayerRec rec{(int)chain_items.size(), groups, a.out + (size_t)a.out_plane0 * a.out_plane_bytes,
-                    a.out + (size_t)(a.out_plane0 + a.cout_pad / 16) * a.out_plane_bytes, a.flops};
-  // which K-chunks wait for what: chain_plan.h (pure host logic, unit-tested on the CPU)
-  const int kl = (int)chain_layers.size();
-  const unsigned cum_k = (unsigned)chain_items.size();                                  // units per tile of layers < k
-  const unsigned cum_km1 = kl >= 1 ? (unsigned)chain_layers[kl - 1].first_item : 0u;    // ... of layers < k - 1
-  std::vector<const char*> chunk_planes(nch);
-  for (int c = 0; c < nch; ++c)
-    chunk_planes[c] = c < a.nchunks0 ? a.in0 + (size_t)(a.in0_plane0 + c) * a.in0_plane_bytes
-                                     : a.in1 + (size_t)(a.in1_plane0 + c - a.nchunks0) * a.in1_plane_bytes;
-  ChainPrevLayer pvl{};
-  if (kl >= 1) pvl = ChainPrevLayer{chain_layers.back().out_lo, chain_layers.back().out_hi, chain_layers.back().nitems};
-  const ChainLayerPlan plan = chain_plan_layer(chunk_planes, kl >= 1 ? &pvl : nullptr, a.in0_plane_bytes, cum_k, cum_km1);
-  const int newest = plan.newest; const unsigned need_old = plan.need_old, need_new = plan.need_new;
-  for (int g = 0; g < groups; ++g) {
-    ChainItem it{};
-    it.in0 = a.in0; it.in0_plane_bytes = a.in0_plane_bytes; it.in0_plane0 = a.in0_plane0; it.nchunks0 = a.nchunks0;
-    it.in1 = a.in1; it.in1_plane_bytes = a.in1_plane_bytes; it.in1_plane0 = a.in1_plane0; it.nchunks1 = a.nchunks1;
-    it.wpk = wbase + (size_t)g * nch * 9 * 64 * 16;
-    it.bias = a.bias + 32 * g;
-    it.act = a.act; it.slope = a.slope; it.alpha = a.alpha; it.gamma = a.gamma;
-    it.res1 = a.res1; it.r1_plane_bytes = a.r1_plane_bytes; it.r1_plane0 = a.r1_plane0 + 2 * g;
-    it.res2 = a.res2; it.r2_plane_bytes = a.r2_plane_bytes; it.r2_plane0 = a.r2_plane0 + 2 * g;
-    it.out = a.out; it.out_plane_bytes = a.out_plane_bytes; it.out_plane0 = a.out_plane0 + 2 * g;
-    it.newest = newest; it.need_old = need_old; it.need_new = need_new;
-    it.pub_need = g > 0 ? cum_k + (unsigned)g : 0u;   // group g publishes after groups < g of this layer on the same tile
-    chain_items.push_back(it);
-  }
-  chain_layers.push_back(rec);
-}
-
-void Model::chain_run(int N, int H, int W, hipStream_t st) {
-  chain_rec = false;
-  if (chain_items.empty()) return;
-  if (!chain_err_host) {
-    // the sticky error word: pinned host memory mapped into the device's address space.  A unit that times out ORs into it
-    // (system scope); no launch resets it and no copy is involved, so an error can neither be lost nor raced - only
-    // check_async_error(), which reports it, clears it
-    SS4K_HIP(hipHostMalloc(reinterpret_cast<void**>(&chain_err_host), 64, hipHostMallocMapped | hipHostMallocCoherent));
-    __atomic_store_n(chain_err_host, 0u, __ATOMIC_RELAXED);
-    SS4K_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&chain_err_dev), chain_err_host, 0));
-    SS4K_HIP(hipEventCreateWithFlags(&chain_done, hipEventDisableTiming));
-  }
-  check_async_error(false);   // an EARLIER forward's chain gave up: reported here at the latest (ss4k_model_check reports it at once)
-  const size_t bytes = chain_items.size() * sizeof(ChainItem);
-  if (chain_uploaded.size() != chain_items.size() || std::memcmp(chain_uploaded.data(), chain_items.data(), bytes) != 0) {
-    // a new job shape (or re-allocated activations): rare, so the upload is allowed to wait - for the previous chain launch, which
-    // may still be reading the old table, and for the copy itself (the host vector is reused by the next shape change)
-    SS4K_HIP(hipStreamSynchronize(st));
-    chain_tab.ensure(bytes);
-    chain_uploaded = chain_items;
-    SS4K_HIP(hipMemcpy(chain_tab.ptr, chain_uploaded.data(), bytes, hipMemcpyHostToDevice));
-  }
-  const auto waste = [&](int th) { return (double)((H + th - 1) / th * th) / H; };
-  int mb = mb_override ? mb_override : (waste(20) < waste(16) - 1e-9 ? 5 : 4);
-#ifdef SS4K_DEV
-  if (const char* e = std::getenv("SS4K_CHAIN_MB")) mb = std::atoi(e);
-#endif
-  ChainArgs ca{};
-  ca.items = chain_tab.as<ChainItem>(); ca.nitems = (int)chain_items.size();
-  ca.N = N; ca.n0 = 0; ca.H = H; ca.W = W;
-  const int ntiles = conv_chain_tiles(N, H, W, mb, &ca.tiles_x, &ca.tiles_y);
-  chain_ctl.ensure(conv_chain_ctl_bytes(ntiles));
-  ca.ctl = chain_ctl.as<unsigned>();
-  ca.zero_page = ctx->zero_page();
-  ca.err_sticky = chain_err_dev;
-#ifdef SS4K_DEV
-  if (const char* e = std::getenv("SS4K_CHAIN_SPIN_LIMIT")) ca.spin_limit = (unsigned)std::atoi(e);   // fault injection: units give up early
-  if (const char* e = std::getenv("SS4K_CHAIN_GRID")) ca.grid = std::atoi(e);
-  if (const char* e = std::getenv("SS4K_CHAIN_ABL")) ca.abl = std::atoi(e);
-#endif
-  double flops = 0;
-  for (const auto& l : chain_layers) flops += l.flops;
-  ProfScope prof(ctx, st, PROF_CONV);
-  launch_conv_chain(ctx, ca, mb, st);
-  prof.done(flops);
-  SS4K_HIP(hipEventRecord(chain_done, st));   // ss4k_model_check(wait) waits for THIS launch before it reads the sticky word
-  chain_pending = true;
-#ifdef SS4K_DEV
-  if (ca.abl == 8) {   // statistics build: how often units started blocked, how long they polled
-    SS4K_HIP(hipStreamSynchronize(st));
-    std::vector<unsigned> h(4 + ntiles + 1);
-    SS4K_HIP(hipMemcpy(h.data(), ca.ctl, h.size() * 4, hipMemcpyDeviceToHost));
-    fprintf(stderr, "[chain] grid %d: %d items x %d tiles = %u units: %u blocking starts; workgroup-time spent polling: %.1f us at unit starts, %.1f us inside units (all workgroups together)\n",
-            ca.grid, ca.nitems, ntiles, (unsigned)ca.nitems * ntiles, h[2], h[3] / 100.0, h[4 + ntiles] / 100.0);
-  }
-#endif
-}
-
-#endif  // SS4K_DEV
-
-// Asynchronous failures of the chain kernel (a unit gave up waiting: a co-running kernel starved it for seconds, or a defect).
-// wait: block until the last chain launch has finished, so that THIS forward's status is known before its output is used.
-void Model::check_async_error(bool wait) {
-  if (!chain_err_host) return;
-  if (wait && chain_pending) { SS4K_HIP(hipEventSynchronize(chain_done)); chain_pending = false; }
-  if (__atomic_exchange_n(chain_err_host, 0u, __ATOMIC_ACQ_REL) != 0)
-    throw Error(SS4K_EHIP, "conv chain: a work unit timed out waiting for its neighbours; the output of the forward(s) since the "
-                           "last successful ss4k_model_check is invalid");
 }
 
 // Called at the top of a conv network's forward: one launch chain or two?  Both give bit-identical tensors.
@@ -873,7 +659,6 @@ void Model::abort_forward(hipStream_t st) noexcept {
   }
   if (section_open) { ctx->prof_pool.push_back(section); section_open = false; }
   tune_timed = nullptr; cur_lanes = 1;
-  chain_rec = false;
   out_stats_acc = nullptr; out_stats_done = false; out_half = false; in_u8 = false;
 }
 
@@ -939,18 +724,6 @@ void Model::forward_impl(const float* in, float* out, int n, int h, int w, hipSt
     int li = 0;
     { ConvOpts o; o.out = F; conv(li++, P, nullptr, n, H, W, o, st); }
     Tens cur = F;
-    // the body of an fp16 job as ONE persistent launch with per-tile hand-offs between the layers (conv_chain.hip): opt-in
-    // (SS4K_MODEL_CHAIN), never the default.  Measured in round 3 on one 720p frame (460 tiles per layer, 512 workgroup slots): the chain runs a single
-    // caller's 1-frame jobs 1-6 % faster than 345 launches (box by box), but two callers alternating on two streams are better
-    // off with launches (105-112 against 98 frames/s: their chains of launches fill each other's gaps, two chain kernels only
-    // compete for the slots) - and a model cannot know how many callers the GPU has; since round 4 the fused dense-block launches
-    // (conv_dense.hip) give the single caller more than the chain does.  DESIGN.md 4.5, profiles/NOTES_r01_r03.md 4.1d.
-#ifdef SS4K_DEV
-    const bool use_chain = !plan_only && f16 && !dbg && nf == 64 && g == 32 && chain_mode == 2;
-    if (use_chain) {
-      chain_rec = true; chain_items.clear(); chain_layers.clear();
-    }
-#endif
     for (int b = 0; b < desc.num_block; ++b) {
       const Tens a = cur;
       const Tens t1 = X[0], t2 = X[1];
@@ -973,17 +746,6 @@ void Model::forward_impl(const float* in, float* out, int n, int h, int w, hipSt
       }
       cur = dst;
     }
-#ifdef SS4K_DEV
-    if (use_chain) {
-      if (forked) {   // (a forced chain on an even batch: conv_first ran as two launch chains; the conv section stays open)
-        SS4K_HIP(hipEventRecord(ctx->lane_done(), ctx->lane_stream()));
-        SS4K_HIP(hipStreamWaitEvent(st, ctx->lane_done(), 0));
-        forked = false;
-      }
-      cur_lanes = 1;
-      chain_run(n, H, W, st);
-    }
-#endif
     { ConvOpts o; o.res1 = &F; o.out = X[0]; conv(li++, cur, nullptr, n, H, W, o, st); }  // feat + conv_body(body)
     Tens U1 = act(6, px * 4, nf), U2 = act(7, px * 16, nf), U3 = act(8, px * 16, nf);
     { ConvOpts o; o.ups2 = 1; o.act = ACT_LRELU; o.slope = 0.2f; o.out = U1; conv(li++, X[0], nullptr, n, 2 * H, 2 * W, o, st); }
@@ -1086,15 +848,13 @@ double bench_conv_layer(ss4k_ctx* ctx, int dtype, int cin0, int cin1, int cout, 
                         int iters, hipStream_t st) {
   ss4k_model_desc d{}; d.kind = SS4K_RRDBNET; d.dtype = dtype; d.scale = 2; d.num_feat = 64; d.num_block = 1; d.num_grow_ch = 32;
   Model m; m.ctx = ctx; m.desc = d;
-  m.use_rs = (flags & 4096) != 0;   // 4096: the register-stationary kernel (conv_rs.hip) where the shape is built
-  m.conv5_mode = m.use_rs ? 1 : 0;
-  m.rs_mask = 63; m.rs_wide = (flags & 8192) != 0;
+  SS4K_REQUIRE(!(flags & (4096 | 8192)), "ss4k_bench_conv: flags 4096 and 8192 selected the register-stationary kernel and were retired with it");
   const int cin = cin0 + cin1;
   std::vector<float> blob((size_t)cout * cin * 9 + cout);
   uint32_t s = 12345;
   for (auto& v : blob) { s = s * 1664525u + 1013904223u; v = ((s >> 8) & 0xffff) / 65536.0f * 0.02f - 0.01f; }
   ParamCursor pc{blob.data(), blob.size()};
-  const int li = m.add_conv(pc, cout, cin, cin1 ? m.spec_concat(cin0, cin1) : m.spec_plain(cin0), false, /*allow_rs=*/true);
+  const int li = m.add_conv(pc, cout, cin, cin1 ? m.spec_concat(cin0, cin1) : m.spec_plain(cin0), false);
   const size_t px = (size_t)n * h * w;
   Tens X = m.act(0, px, cin0), G = m.act(1, px, std::max(cin1, 32)), O = m.act(2, px, cout);
   {  // random operands: constant data lets the chip hold a higher clock than real frames do
@@ -1112,7 +872,7 @@ double bench_conv_layer(ss4k_ctx* ctx, int dtype, int cin0, int cin1, int cout, 
   }
   ConvOpts o; o.act = ACT_LRELU; o.slope = 0.2f; o.out = O;
   if ((flags & 2048) && cout <= cin0) { o.act = ACT_NONE; o.alpha = 0.2f; o.res1 = &X; }  // conv5 of an RDB: x5 * 0.2 + x
-  m.dbg = flags & ~(2048 | 4096 | 8192);
+  m.dbg = flags & ~2048;
   DevBuf dbgb; dbgb.ensure(1024 * 16 * 8); SS4K_HIP(hipMemsetAsync(dbgb.ptr, 0, 1024 * 16 * 8, st)); m.dbg_buf = dbgb.as<unsigned long long>();
   for (int i = 0; i < 3; ++i) m.conv(li, X, cin1 ? &G : nullptr, n, h, w, o, st);
   hipEvent_t e0, e1; SS4K_HIP(hipEventCreate(&e0)); SS4K_HIP(hipEventCreate(&e1));

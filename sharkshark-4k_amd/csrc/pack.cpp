@@ -53,7 +53,7 @@ PackedConv pack_conv3x3(const PackSpec& s, const float* w, const float* bias, co
   const int nchunks = s.nchunks0 + s.nchunks1;
   SS4K_REQUIRE((int)s.cin_map.size() == nchunks * CW, "pack_conv3x3: cin_map size");
   PackedConv p;
-  p.nb = (s.cout_real <= 32 || s.force_nb1) ? 1 : 2;
+  p.nb = s.cout_real <= 32 ? 1 : 2;
   const int gw = p.nb * 32;
   const int padw = s.cout_real <= 32 ? 32 : 64;   // the tensor's planes come in 32- / 64-cout blocks whatever the group width
   p.cout_pad = (s.cout_real + padw - 1) / padw * padw;
@@ -87,42 +87,6 @@ PackedConv pack_conv3x3(const PackSpec& s, const float* w, const float* bias, co
                 }
               }
   return p;
-}
-
-// conv_rs.hip: every wave holds its slice of the layer's weights in registers as v_mfma_f32_16x16x32_f16
-// A fragments.  Order [group][cout group cg][32-channel chunk c][tap dy*3+dx][cb][lane][8 fp16]:
-//   lane l: cout row m = l & 15 of block cb, k-group kq = l >> 4; element e: channel 8*kq + e of the chunk
-//   (= plane 2c + (kq >> 1), channel 8*(kq & 1) + e of that plane).  Row m of block cb of cout group cg is
-//   virtual cout  g*COUT_WG + cg*cb_count*16 + (cb_count == 2 ? 8*(m >> 2) + 4*cb + (m & 3) : m)  so that
-//   result lane (pixel, q) holds cb_count*4 CONSECUTIVE channels (16- or 8-byte stores).
-std::vector<uint8_t> pack_conv3x3_rs(const PackSpec& s, const float* w, int cout_pad, int nch, int cbn, int CG) {
-  SS4K_REQUIRE(s.dtype == SS4K_F16, "pack_conv3x3_rs: fp16 only");
-  const int nplanes = s.nchunks0 + s.nchunks1;
-  SS4K_REQUIRE((int)s.cin_map.size() == nplanes * 16 && nplanes <= 2 * nch, "pack_conv3x3_rs: cin_map size");
-  const int COUT_WG = CG * cbn * 16;
-  SS4K_REQUIRE(cout_pad % COUT_WG == 0, "pack_conv3x3_rs: cout_pad");
-  const int groups = cout_pad / COUT_WG;
-  std::vector<uint8_t> out((size_t)groups * CG * nch * 9 * cbn * 64 * 8 * 2, 0);
-  size_t idx = 0;
-  for (int g = 0; g < groups; ++g)
-    for (int cg = 0; cg < CG; ++cg)
-      for (int c = 0; c < nch; ++c)
-        for (int t = 0; t < 9; ++t)
-          for (int cb = 0; cb < cbn; ++cb)
-            for (int lane = 0; lane < 64; ++lane) {
-              const int m = lane & 15, kq = lane >> 4;
-              const int vl = cbn == 2 ? 8 * (m >> 2) + 4 * cb + (m & 3) : m;
-              const int co = virt_to_real_cout(s, g * COUT_WG + cg * cbn * 16 + vl);
-              for (int e = 0; e < 8; ++e, ++idx) {
-                const int plane = 2 * c + (kq >> 1), ch = 8 * (kq & 1) + e;
-                const int ci = plane < nplanes ? s.cin_map[(size_t)plane * 16 + ch] : -1;
-                float val = 0.f;
-                if (ci >= 0 && co >= 0) val = w[((size_t)co * s.cin_total + ci) * 9 + t];
-                const uint16_t h = f32_to_f16_bits(val);
-                std::memcpy(&out[idx * 2], &h, 2);
-              }
-            }
-  return out;
 }
 
 // conv_w16.hip: one 64-cout group of a layer as v_mfma_f32_16x16x32_f16 A fragments, [group][pair of K-chunks q][phase][dy][16-cout
@@ -185,43 +149,5 @@ std::vector<uint8_t> pack_conv3x3_w16n(const PackSpec& s, const float* w) {
         }
   return out;
 }
-
-#ifdef SS4K_DEV
-// conv_d16.hip: a dense-block layer pair (conv_k: K1 planes -> 32 couts; conv_{k+1}: the same K1 planes + x_k's two -> 32 couts) as
-// v_mfma_f32_16x16x32_f16 A fragments.  K1 / 2 chunk pairs of three 12 KB phases [dy][conv_k b0, conv_{k+1} b0, conv_k b1, conv_{k+1} b1][lane][8],
-// then conv_{k+1}'s x_k chunk pair as three 6 KB phases [dy][b0, b1][lane][8].  Phases and k-groups as pack_conv3x3_w16; row m of block b is
-// cout 16 b + m (result lane (pixel, row group rg) holds channels 4 rg .. 4 rg + 3 of plane b).
-std::vector<uint8_t> pack_dense_d16(const PackSpec& sa, const float* wa, const PackSpec& sb, const float* wb) {
-  SS4K_REQUIRE(sa.dtype == SS4K_F16 && sb.dtype == SS4K_F16, "pack_dense_d16: fp16 only");
-  const int k1 = sa.nchunks0 + sa.nchunks1, k2 = sb.nchunks0 + sb.nchunks1;
-  SS4K_REQUIRE(k1 % 2 == 0 && k2 == k1 + 2 && (int)sa.cin_map.size() == k1 * 16 && (int)sb.cin_map.size() == k2 * 16, "pack_dense_d16: shape");
-  std::vector<uint8_t> out((size_t)(k1 / 2) * 3 * 12288 + 3 * 6144, 0);
-  size_t idx = 0;
-  auto put = [&](const PackSpec& s, const float* w, int blk, int q, int ph, int dy, int lane) {
-    const int m = lane & 15, kq = lane >> 4;
-    const int co = virt_to_real_cout(s, 16 * blk + m);
-    const int plane = ph == 0 ? 2 * q : ph == 1 ? 2 * q + (kq >> 1) : 2 * q + 1;
-    const int dx = ph == 1 ? 2 : (kq >> 1);
-    for (int e = 0; e < 8; ++e, ++idx) {
-      const int ci = s.cin_map[(size_t)plane * 16 + 8 * (kq & 1) + e];
-      float val = 0.f;
-      if (ci >= 0 && co >= 0) val = w[((size_t)co * s.cin_total + ci) * 9 + dy * 3 + dx];
-      const uint16_t h = f32_to_f16_bits(val);
-      std::memcpy(&out[idx * 2], &h, 2);
-    }
-  };
-  for (int q = 0; q < k1 / 2; ++q)
-    for (int ph = 0; ph < 3; ++ph)
-      for (int dy = 0; dy < 3; ++dy)
-        for (int t = 0; t < 4; ++t)   // table entry t: layer t & 1 (0 = conv_k), block t >> 1
-          for (int lane = 0; lane < 64; ++lane) put((t & 1) ? sb : sa, (t & 1) ? wb : wa, t >> 1, q, ph, dy, lane);
-  for (int ph = 0; ph < 3; ++ph)
-    for (int dy = 0; dy < 3; ++dy)
-      for (int blk = 0; blk < 2; ++blk)
-        for (int lane = 0; lane < 64; ++lane) put(sb, wb, blk, k1 / 2, ph, dy, lane);
-  SS4K_REQUIRE(idx * 2 == out.size(), "pack_dense_d16: size");
-  return out;
-}
-#endif  // SS4K_DEV
 
 }  // namespace ss4k

@@ -21,7 +21,7 @@ NO_DENSE, DENSE, ONE, TWO = _capi.MODEL_NO_DENSE, 0, _capi.MODEL_ONE_CHAIN, _cap
 
 
 PIN32 = _capi.MODEL_NO_W16   # this file tests conv_dense.hip (v_mfma_f32_32x32x16_f16: bit-identical to four launches of conv_mfma.hip); the fused
-                             # pairs are conv_dense.hip on every product route (conv_d16.hip, a 16x16x32 build, is dev-library only: tools/dev_tests/)
+                             # pairs are conv_dense.hip on every product route (a 16x16x32 build of the pair was measured and removed: DESIGN.md 4.3)
 
 
 def _model(ctx, flat, scale, nb, flags):

@@ -1,7 +1,7 @@
 """Costing only (VERDICT r2 "next" 8b; nothing here ships): what would Winograd F(2x2, 3x3) do to the accuracy of the fp16 RRDBNet path?
 
 Emulates, in PyTorch on the CPU, the 23-block RRDBNet x2 with every 3x3 convolution computed
-  (a) directly, fp16 storage of activations and weights, fp32 accumulation   (what csrc/conv_mfma.hip / conv_rs.hip do), and
+  (a) directly, fp16 storage of activations and weights, fp32 accumulation   (what csrc/conv_mfma.hip does), and
   (b) as F(2x2, 3x3): U = G g G^T and V = B^T d B rounded to fp16 (the MFMA operands), the 16 element-wise products accumulated
       over the input channels in fp32, Y = A^T M A in fp32, one fp16 rounding of the stored activation,
 and reports the PSNR of both against the fp32 network on the same weights and input.  2.25x fewer multiplies per output; the

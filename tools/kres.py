@@ -8,7 +8,7 @@ from sharkshark4k_amd import build as B
 
 dev = "--dev" in sys.argv
 show_all = "--all" in sys.argv
-files = [a for a in sys.argv[1:] if not a.startswith("--")] or [s for s in B.SOURCES + (B.DEV_SOURCES if dev else []) if s.endswith(".hip")]
+files = [a for a in sys.argv[1:] if not a.startswith("--")] or [s for s in B.SOURCES if s.endswith(".hip")]
 keys = ["VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"]
 print(f"{'kernel':92s} {'vgpr':>4s} {'agpr':>4s} {'scratch':>7s} {'sspill':>6s} {'vspill':>6s} {'lds':>6s} {'occ':>3s}")
 for f in files:

@@ -1,6 +1,6 @@
 // Dev tool (round 2): does it matter which register file a 16x16x32 MFMA's operands live in?
 // One wave per SIMD (256 threads, 1 block per CU), registers only, 32 independent accumulators.
-//   variant 0: A, B in VGPRs, C/D in VGPRs      variant 1: A in AGPRs, B, C/D in VGPRs (conv_rs.hip)
+//   variant 0: A, B in VGPRs, C/D in VGPRs      variant 1: A in AGPRs, B, C/D in VGPRs (the removed register-stationary conv kernel)
 //   variant 2: A, B in VGPRs, C/D in AGPRs      variant 3: as 1 with a ds_read_b128 every 3rd MFMA (operand stream)
 // prints cycles per MFMA (s_memtime) - 16 = the matrix pipe's issue rate.
 // hipcc --offload-arch=gfx950 -O3 mfma_agpr.hip -o mfma_agpr

@@ -1,6 +1,6 @@
 """Dev tool: 1-frame (and n-frame) RRDBNet x2 720p jobs under model-description flags, interleaved rounds in one process.
 usage: python tools/n1_ab.py [frames=1] [rounds=3] [flags[:VAR=VAL[+VAR=VAL]],...]   (flags: integers, include/ss4k.h
-SS4K_MODEL_*; VAR=VAL: dev-library switches read per forward, e.g. 128:SS4K_CHAIN_ABL=1 with SS4K_LIB=.../libss4k_hip_dev.so)"""
+SS4K_MODEL_*; VAR=VAL: dev-library switches read when the model is built, e.g. 0:SS4K_DENSE_MASK=1 with SS4K_LIB=.../libss4k_hip_dev.so)"""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
@@ -11,10 +11,12 @@ nf = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 variants = sys.argv[3].split(",") if len(sys.argv) > 3 else ["0", str(0)]
 def setenv(v):
-    for k in [k for k in os.environ if k.startswith("SS4K_CHAIN_")]:
-        del os.environ[k]
+    for k in set_keys:
+        os.environ.pop(k, None)
+    set_keys.clear()
     for kv in v.split(":")[1].split("+") if ":" in v else []:
-        k, val = kv.split("="); os.environ[k] = val
+        k, val = kv.split("="); os.environ[k] = val; set_keys.add(k)
+set_keys = set()
 ctx = _capi.Context(0)
 flat = W.flatten(W.rrdbnet_table(0, scale=2), W.rrdbnet_keys(23))
 ups = {}
