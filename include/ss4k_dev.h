@@ -2,7 +2,7 @@
  * ss4k_dev.h - measurement-only entry points of libss4k_hip_dev.so (built with -DSS4K_DEV from the
  * same sources as libss4k_hip.so; a superset of include/ss4k.h).  Not part of the product library:
  * the instrumented / alternative-tile-shape instantiations of the conv kernel live only here.
- * Used by tools/stamp4.py, tools/traffic_ablate.py, tools/conv5_routes.py.
+ * Used by tools/stamp4.py, tools/traffic_ablate.py, tools/conv5_routes.py and tests/test_gpu_glue_budget.py.
  */
 #ifndef SS4K_DEV_H
 #define SS4K_DEV_H
@@ -24,6 +24,58 @@ extern "C" {
  * Bits 4096 and 8192 (the removed register-stationary kernel) are rejected with SS4K_EINVAL. */
 int ss4k_bench_conv(ss4k_ctx* ctx, int dtype, int cin0, int cin1, int cout, int n, int h, int w, int flags,
                     int iters, double* avg_us, void* hip_stream);
+
+/* ---- glue launchers (csrc/glue.hip) that the public ss4k_op_* calls do not reach, or reach with fixed arguments: what
+ * tests/test_gpu_glue_budget.py bounds against float64.  Conventions of the ss4k_op_* set: SS4K_OK or an error code with
+ * ss4k_last_error(), every pointer is device memory of the caller (except taps17 of ss4k_dev_gauss17_taps), asynchronous
+ * on hip_stream.  *_half != 0: that tensor holds __half, otherwise float.  Statistics accumulators `acc` hold
+ * 32 (slots) x planes x 2 doubles; st_hr / st_lr / stats hold {mean, std} per plane. */
+int ss4k_dev_op_area_normalized(ss4k_ctx* ctx, const void* in, int in_half, float* out, int planes, int h, int w, int oh,
+                                int ow, const float* st_hr, const float* st_lr, void* hip_stream);
+/* st_hr + st_lr (normalise), diff (dh x dw map, bilinear, subtracted) and out_u8 (uint8 NHWC result; NULL: clamped in place) may be NULL */
+int ss4k_dev_op_tail_fused(ss4k_ctx* ctx, void* hr, int hr_half, uint8_t* out_u8, const float* diff, int n, int c, int h,
+                           int w, int dh, int dw, const float* st_hr, const float* st_lr, void* hip_stream);
+int ss4k_dev_op_bicubic_u8(ss4k_ctx* ctx, const void* in, int in_half, uint8_t* out, int n, int c, int h, int w, int oh,
+                           int ow, void* hip_stream);
+int ss4k_dev_op_bicubic(ss4k_ctx* ctx, const float* in, float* out, int planes, int h, int w, int oh, int ow, int clamp01,
+                        void* hip_stream);
+int ss4k_dev_op_bilinear(ss4k_ctx* ctx, const float* in, float* out, int planes, int h, int w, int oh, int ow,
+                         int subtract_from_out, int clamp01, void* hip_stream);
+/* the 17 taps (host memory) an upscaler uploads for its colour-match blur */
+int ss4k_dev_gauss17_taps(float* taps17);
+int ss4k_dev_op_gauss17_reflect(ss4k_ctx* ctx, const float* in, float* tmp, float* out, const float* taps17_dev, int planes,
+                                int h, int w, void* hip_stream);
+/* k = 3 or 17, taps_dev: k x k; out = [clamp01] conv; with blend_src: out * blend_a + blend_b * blend_src */
+int ss4k_dev_op_depthwise_reflect(ss4k_ctx* ctx, const float* in, float* out, const float* taps_dev, int planes, int h,
+                                  int w, int k, int clamp01, const float* blend_src, float blend_a, float blend_b,
+                                  void* hip_stream);
+int ss4k_dev_op_normalize(ss4k_ctx* ctx, float* x, const float* st_hr, const float* st_lr, int planes, int hw, void* hip_stream);
+int ss4k_dev_op_sub(ss4k_ctx* ctx, const float* a, const float* b, float* out, size_t n, void* hip_stream);
+int ss4k_dev_op_clamp01(ss4k_ctx* ctx, float* x, size_t n, void* hip_stream);
+int ss4k_dev_op_plane_stats(ss4k_ctx* ctx, double* acc, const void* in, int in_half, float* stats, int planes, int hw,
+                            void* hip_stream);
+int ss4k_dev_op_plane_stats_u8nhwc(ss4k_ctx* ctx, double* acc, const uint8_t* in, float* stats, int n, int hw, void* hip_stream);
+/* the halves of the two above: partial sums into planes [plane0, plane0 + planes) of an accumulator of acc_planes planes (zeroed by
+ * the caller, or by an earlier ss4k_dev_op_plane_stats_finish2 with rezero), then one finishing launch */
+int ss4k_dev_op_plane_stats_partial(ss4k_ctx* ctx, double* acc, const void* in, int in_half, int planes, int hw,
+                                    int acc_planes, int plane0, void* hip_stream);
+int ss4k_dev_op_plane_stats_u8nhwc_partial(ss4k_ctx* ctx, double* acc, const uint8_t* in, int n, int hw, int acc_planes,
+                                           int plane0, void* hip_stream);
+int ss4k_dev_op_plane_stats_finish(ss4k_ctx* ctx, const double* acc, float* stats, int planes, int hw, void* hip_stream);
+int ss4k_dev_op_plane_stats_finish2(ss4k_ctx* ctx, double* acc, float* stats_a, float* stats_b, int planes, int hw_a,
+                                    int hw_b, int rezero, void* hip_stream);
+/* src: "planes" layout (16-channel records), cq * r * r channels; stats_acc (may be NULL): the output's plane sums ride along */
+int ss4k_dev_op_ps_nchw_addbase(ss4k_ctx* ctx, const void* src, int src_half, void* out, int out_half, const float* base,
+                                int n, int h, int w, int r, int cq, double* stats_acc, void* hip_stream);
+int ss4k_dev_op_pack_input(ss4k_ctx* ctx, const float* in, void* out, int out_half, int n, int c, int h, int w, int r,
+                           int nplanes, void* hip_stream);
+int ss4k_dev_op_temporal_shift(ss4k_ctx* ctx, const void* in, void* out, int nplanes, int frames, size_t frame_px,
+                               int slots_per_record, int ch_per_plane, int fold, void* hip_stream);
+
+/* Route report: every glue launcher counts the kernel route it chose under a static name ("glue::area_whole<NORM,8,half>", ...).
+ * _read returns the index-th route in name order (SS4K_EINVAL past the last), _reset clears the table.  Process-wide. */
+int ss4k_dev_glue_routes_reset(void);
+int ss4k_dev_glue_routes_read(int index, char* name, size_t name_capacity, int64_t* launches);
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,17 @@ SYMBOLS = [
     "ss4k_prof_enable", "ss4k_prof_reset", "ss4k_prof_read", "ss4k_prof_read_kind", "ss4k_prof_read_family", "ss4k_prof_read_section_ms",
     "ss4k_stream_pair_check", "ss4k_op_cv_area_shape", "ss4k_op_cv_area_resize_u8",
 ]
-DEV_SYMBOLS = ["ss4k_bench_conv"]  # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so)
+# include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
+DEV_SYMBOLS = [
+    "ss4k_bench_conv",
+    # the internal glue launchers and their route report (tests/test_gpu_glue_budget.py)
+    "ss4k_dev_op_area_normalized", "ss4k_dev_op_tail_fused", "ss4k_dev_op_bicubic_u8", "ss4k_dev_op_bicubic", "ss4k_dev_op_bilinear",
+    "ss4k_dev_gauss17_taps", "ss4k_dev_op_gauss17_reflect", "ss4k_dev_op_depthwise_reflect", "ss4k_dev_op_normalize", "ss4k_dev_op_sub",
+    "ss4k_dev_op_clamp01", "ss4k_dev_op_plane_stats", "ss4k_dev_op_plane_stats_u8nhwc", "ss4k_dev_op_plane_stats_partial",
+    "ss4k_dev_op_plane_stats_u8nhwc_partial", "ss4k_dev_op_plane_stats_finish", "ss4k_dev_op_plane_stats_finish2",
+    "ss4k_dev_op_ps_nchw_addbase", "ss4k_dev_op_pack_input", "ss4k_dev_op_temporal_shift",
+    "ss4k_dev_glue_routes_reset", "ss4k_dev_glue_routes_read",
+]
 
 
 class ModelDesc(C.Structure):
@@ -106,6 +116,30 @@ def load(path: str) -> C.CDLL:
     L.ss4k_op_f32nchw_to_u8nhwc.argtypes = [vp, vp, vp, i, i, i, i, vp]
     if hasattr(L, "ss4k_bench_conv"):  # dev library only
         L.ss4k_bench_conv.argtypes = [vp, i, i, i, i, i, i, i, i, i, C.POINTER(C.c_double), vp]
+    if hasattr(L, "ss4k_dev_glue_routes_read"):  # dev library only: the glue launchers (include/ss4k_dev.h)
+        f = C.c_float
+        L.ss4k_dev_op_area_normalized.argtypes = [vp, vp, i, vp, i, i, i, i, i, vp, vp, vp]
+        L.ss4k_dev_op_tail_fused.argtypes = [vp, vp, i, vp, vp, i, i, i, i, i, i, vp, vp, vp]
+        L.ss4k_dev_op_bicubic_u8.argtypes = [vp, vp, i, vp, i, i, i, i, i, i, vp]
+        L.ss4k_dev_op_bicubic.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp]
+        L.ss4k_dev_op_bilinear.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp]
+        L.ss4k_dev_gauss17_taps.argtypes = [vp]
+        L.ss4k_dev_op_gauss17_reflect.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp]
+        L.ss4k_dev_op_depthwise_reflect.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, f, f, vp]
+        L.ss4k_dev_op_normalize.argtypes = [vp, vp, vp, vp, i, i, vp]
+        L.ss4k_dev_op_sub.argtypes = [vp, vp, vp, vp, sz, vp]
+        L.ss4k_dev_op_clamp01.argtypes = [vp, vp, sz, vp]
+        L.ss4k_dev_op_plane_stats.argtypes = [vp, vp, vp, i, vp, i, i, vp]
+        L.ss4k_dev_op_plane_stats_u8nhwc.argtypes = [vp, vp, vp, vp, i, i, vp]
+        L.ss4k_dev_op_plane_stats_partial.argtypes = [vp, vp, vp, i, i, i, i, i, vp]
+        L.ss4k_dev_op_plane_stats_u8nhwc_partial.argtypes = [vp, vp, vp, i, i, i, i, vp]
+        L.ss4k_dev_op_plane_stats_finish.argtypes = [vp, vp, vp, i, i, vp]
+        L.ss4k_dev_op_plane_stats_finish2.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
+        L.ss4k_dev_op_ps_nchw_addbase.argtypes = [vp, vp, i, vp, i, vp, i, i, i, i, i, vp, vp]
+        L.ss4k_dev_op_pack_input.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp]
+        L.ss4k_dev_op_temporal_shift.argtypes = [vp, vp, vp, i, i, sz, i, i, i, vp]
+        L.ss4k_dev_glue_routes_reset.argtypes = []
+        L.ss4k_dev_glue_routes_read.argtypes = [i, C.c_char_p, sz, C.POINTER(C.c_int64)]
     L.ss4k_prof_enable.argtypes = [vp, i]
     L.ss4k_prof_reset.argtypes = [vp]
     L.ss4k_prof_read.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -118,6 +152,17 @@ def load(path: str) -> C.CDLL:
     L.ss4k_op_cv_area_shape.argtypes = [i, i, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.ss4k_op_cv_area_resize_u8.argtypes = [vp, vp, vp, sz, i, i, i, i, C.c_double, C.c_double, vp]
     return L
+
+
+def glue_routes(L: C.CDLL) -> dict:
+    """{route name: launches} of the dev library's glue launchers since the last ``L.ss4k_dev_glue_routes_reset()``."""
+    out, idx = {}, 0
+    while True:
+        name, n = C.create_string_buffer(256), C.c_int64()
+        if L.ss4k_dev_glue_routes_read(idx, name, 256, C.byref(n)) != 0:
+            return out
+        out[name.value.decode()] = n.value
+        idx += 1
 
 
 def _check(rc: int) -> None:

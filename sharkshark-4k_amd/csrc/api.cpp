@@ -583,6 +583,100 @@ int ss4k_bench_conv(ss4k_ctx* c, int dtype, int cin0, int cin1, int cout, int n,
     *avg_us = bench_conv_layer(c, dtype, cin0, cin1, cout, n, h, w, flags, iters, (hipStream_t)stream);
   });
 }
+
+// ---- the glue launchers the public ss4k_op_* set does not reach, or reaches with fixed arguments (include/ss4k_dev.h).  Thin: every
+// pointer is the caller's device memory, *_half selects the __half instantiation
+#define SS4K_DEV_OP(cond, ...) return guard([&] { SS4K_REQUIRE(cond, "NULL or out-of-range argument"); __VA_ARGS__; SS4K_HIP(hipGetLastError()); })
+int ss4k_dev_op_area_normalized(ss4k_ctx* c, const void* in, int in_half, float* out, int p, int h, int w, int oh, int ow, const float* st_hr,
+                                const float* st_lr, void* s) {
+  SS4K_DEV_OP(c && in && out && st_hr && st_lr,
+              if (in_half) op_area_normalized((const __half*)in, out, p, h, w, oh, ow, st_hr, st_lr, (hipStream_t)s);
+              else op_area_normalized((const float*)in, out, p, h, w, oh, ow, st_hr, st_lr, (hipStream_t)s));
+}
+int ss4k_dev_op_tail_fused(ss4k_ctx* c, void* hr, int hr_half, uint8_t* out_u8, const float* diff, int n, int ch, int h, int w, int dh, int dw,
+                           const float* st_hr, const float* st_lr, void* s) {
+  SS4K_DEV_OP(c && hr && (st_hr == nullptr) == (st_lr == nullptr),
+              if (hr_half) op_tail_fused((__half*)hr, out_u8, diff, n, ch, h, w, dh, dw, st_hr, st_lr, (hipStream_t)s);
+              else op_tail_fused((float*)hr, out_u8, diff, n, ch, h, w, dh, dw, st_hr, st_lr, (hipStream_t)s));
+}
+int ss4k_dev_op_bicubic_u8(ss4k_ctx* c, const void* in, int in_half, uint8_t* out, int n, int ch, int h, int w, int oh, int ow, void* s) {
+  SS4K_DEV_OP(c && in && out,
+              if (in_half) op_bicubic_u8((const __half*)in, out, n, ch, h, w, oh, ow, (hipStream_t)s);
+              else op_bicubic_u8((const float*)in, out, n, ch, h, w, oh, ow, (hipStream_t)s));
+}
+int ss4k_dev_op_bicubic(ss4k_ctx* c, const float* in, float* out, int p, int h, int w, int oh, int ow, int clamp01, void* s) {
+  SS4K_DEV_OP(c && in && out, op_bicubic(in, out, p, h, w, oh, ow, clamp01, (hipStream_t)s));
+}
+int ss4k_dev_op_bilinear(ss4k_ctx* c, const float* in, float* out, int p, int h, int w, int oh, int ow, int subtract_from_out, int clamp01, void* s) {
+  SS4K_DEV_OP(c && in && out, op_bilinear(in, out, p, h, w, oh, ow, subtract_from_out, clamp01, (hipStream_t)s));
+}
+int ss4k_dev_gauss17_taps(float* taps17) {
+  return guard([&] { SS4K_REQUIRE(taps17, "NULL argument"); const auto g = gaussian_taps_1d(17, 8.0f); std::memcpy(taps17, g.data(), 17 * 4); });
+}
+int ss4k_dev_op_gauss17_reflect(ss4k_ctx* c, const float* in, float* tmp, float* out, const float* taps17_dev, int p, int h, int w, void* s) {
+  SS4K_DEV_OP(c && in && tmp && out && taps17_dev, op_gauss17_reflect(in, tmp, out, taps17_dev, p, h, w, (hipStream_t)s));
+}
+int ss4k_dev_op_depthwise_reflect(ss4k_ctx* c, const float* in, float* out, const float* taps_dev, int p, int h, int w, int k, int clamp01,
+                                  const float* blend_src, float blend_a, float blend_b, void* s) {
+  SS4K_DEV_OP(c && in && out && taps_dev, op_depthwise_reflect(in, out, taps_dev, p, h, w, k, clamp01, blend_src, blend_a, blend_b, (hipStream_t)s));
+}
+int ss4k_dev_op_normalize(ss4k_ctx* c, float* x, const float* st_hr, const float* st_lr, int p, int hw, void* s) {
+  SS4K_DEV_OP(c && x && st_hr && st_lr, op_normalize(x, st_hr, st_lr, p, hw, (hipStream_t)s));
+}
+int ss4k_dev_op_sub(ss4k_ctx* c, const float* a, const float* b, float* out, size_t n, void* s) {
+  SS4K_DEV_OP(c && a && b && out, op_sub(a, b, out, n, (hipStream_t)s));
+}
+int ss4k_dev_op_clamp01(ss4k_ctx* c, float* x, size_t n, void* s) { SS4K_DEV_OP(c && x, op_clamp01(x, n, (hipStream_t)s)); }
+int ss4k_dev_op_plane_stats(ss4k_ctx* c, double* acc, const void* in, int in_half, float* stats, int p, int hw, void* s) {
+  SS4K_DEV_OP(c && acc && in && stats,
+              if (in_half) op_plane_stats(acc, (const __half*)in, stats, p, hw, (hipStream_t)s);
+              else op_plane_stats(acc, (const float*)in, stats, p, hw, (hipStream_t)s));
+}
+int ss4k_dev_op_plane_stats_u8nhwc(ss4k_ctx* c, double* acc, const uint8_t* in, float* stats, int n, int hw, void* s) {
+  SS4K_DEV_OP(c && acc && in && stats, op_plane_stats_u8nhwc(acc, in, stats, n, hw, (hipStream_t)s));
+}
+int ss4k_dev_op_plane_stats_partial(ss4k_ctx* c, double* acc, const void* in, int in_half, int p, int hw, int acc_planes, int plane0, void* s) {
+  SS4K_DEV_OP(c && acc && in && plane0 >= 0 && p > 0 && plane0 + p <= acc_planes,
+              if (in_half) op_plane_stats_partial(acc, (const __half*)in, p, hw, acc_planes, plane0, (hipStream_t)s);
+              else op_plane_stats_partial(acc, (const float*)in, p, hw, acc_planes, plane0, (hipStream_t)s));
+}
+int ss4k_dev_op_plane_stats_u8nhwc_partial(ss4k_ctx* c, double* acc, const uint8_t* in, int n, int hw, int acc_planes, int plane0, void* s) {
+  SS4K_DEV_OP(c && acc && in && plane0 >= 0 && n > 0 && plane0 + 3 * n <= acc_planes,
+              op_plane_stats_u8nhwc_partial(acc, in, n, hw, acc_planes, plane0, (hipStream_t)s));
+}
+int ss4k_dev_op_plane_stats_finish(ss4k_ctx* c, const double* acc, float* stats, int p, int hw, void* s) {
+  SS4K_DEV_OP(c && acc && stats, op_plane_stats_finish(acc, stats, p, hw, (hipStream_t)s));
+}
+int ss4k_dev_op_plane_stats_finish2(ss4k_ctx* c, double* acc, float* stats_a, float* stats_b, int p, int hw_a, int hw_b, int rezero, void* s) {
+  SS4K_DEV_OP(c && acc && stats_a && stats_b, op_plane_stats_finish2(acc, stats_a, stats_b, p, hw_a, hw_b, rezero != 0, (hipStream_t)s));
+}
+int ss4k_dev_op_ps_nchw_addbase(ss4k_ctx* c, const void* src, int src_half, void* out, int out_half, const float* base, int n, int h, int w, int r,
+                                int cq, double* stats_acc, void* s) {
+  SS4K_DEV_OP(c && src && out && base,
+              SS4K_REQUIRE(src_half || !out_half, "pixel shuffle tail: an fp16 output needs fp16 planes");
+              if (!src_half) op_ps_nchw_addbase((const float*)src, (float*)out, base, n, h, w, r, cq, stats_acc, (hipStream_t)s);
+              else if (!out_half) op_ps_nchw_addbase((const __half*)src, (float*)out, base, n, h, w, r, cq, stats_acc, (hipStream_t)s);
+              else op_ps_nchw_addbase((const __half*)src, (__half*)out, base, n, h, w, r, cq, stats_acc, (hipStream_t)s));
+}
+int ss4k_dev_op_pack_input(ss4k_ctx* c, const float* in, void* out, int out_half, int n, int ch, int h, int w, int r, int nplanes, void* s) {
+  SS4K_DEV_OP(c && in && out,
+              if (out_half) op_pack_input(in, (__half*)out, n, ch, h, w, r, nplanes, (hipStream_t)s);
+              else op_pack_input(in, (float*)out, n, ch, h, w, r, nplanes, (hipStream_t)s));
+}
+int ss4k_dev_op_temporal_shift(ss4k_ctx* c, const void* in, void* out, int nplanes, int frames, size_t frame_px, int slots_per_record,
+                               int ch_per_plane, int fold, void* s) {
+  SS4K_DEV_OP(c && in && out && slots_per_record > 0 && ch_per_plane >= slots_per_record, op_temporal_shift(in, out, nplanes, frames, frame_px, slots_per_record, ch_per_plane, fold, (hipStream_t)s));
+}
+#undef SS4K_DEV_OP
+int ss4k_dev_glue_routes_reset(void) { return guard([&] { glue_routes_reset(); }); }
+int ss4k_dev_glue_routes_read(int index, char* name, size_t name_capacity, int64_t* launches) {
+  return guard([&] {
+    SS4K_REQUIRE(index >= 0 && name && name_capacity > 0 && launches, "ss4k_dev_glue_routes_read: bad argument");
+    std::string nm;
+    SS4K_REQUIRE(glue_routes_read(index, &nm, launches), "ss4k_dev_glue_routes_read: index past the last route");
+    std::snprintf(name, name_capacity, "%s", nm.c_str());
+  });
+}
 #endif  // SS4K_DEV
 
 // ---- profiling hooks --------------------------------------------------------------------------

@@ -4,6 +4,18 @@
 
 namespace ss4k {
 
+// Route report (dev library only): every glue launcher names the kernel route it chose - "glue::<kernel><template arguments>", the
+// conv launchers' family naming - in a counter table of its own (NOT ss4k_ctx::prof_families: bench.py lists every family there), read
+// and reset through ss4k_dev_glue_routes_read / _reset (include/ss4k_dev.h).  The product build compiles the names away.
+#ifdef SS4K_DEV
+void glue_route_note(const char* name);
+void glue_routes_reset();
+bool glue_routes_read(int index, std::string* name, int64_t* count);   // the index-th route in name order; false past the last
+#define SS4K_GLUE_ROUTE(name) ::ss4k::glue_route_note(name)
+#else
+#define SS4K_GLUE_ROUTE(name) ((void)0)
+#endif
+
 void op_u8nhwc_to_f32nchw(const uint8_t* in, float* out, int n, int h, int w, int c, hipStream_t st);
 void op_area(const float* in, float* out, int planes, int h, int w, int oh, int ow, hipStream_t st);
 // acc: 2 * planes doubles of scratch owned by the caller (each upscaler owns its own, so two upscalers

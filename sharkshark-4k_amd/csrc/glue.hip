@@ -4,11 +4,34 @@
 // layout, so that each op can be parity-tested against its torch counterpart.
 #include "common.h"
 #include "glue.h"
+#ifdef SS4K_DEV
+#include <mutex>
+#endif
 
 namespace ss4k {
 
 // every launcher checks its launch: a bad grid surfaces here, not at the next synchronisation
 #define SS4K_LAUNCH_OK() SS4K_HIP(hipGetLastError())
+
+#ifdef SS4K_DEV
+// the dev library's route report (glue.h): launches per route name since the last reset
+static std::mutex g_route_mu;
+static std::map<std::string, int64_t> g_routes;
+void glue_route_note(const char* name) { std::lock_guard<std::mutex> lk(g_route_mu); g_routes[name] += 1; }
+void glue_routes_reset() { std::lock_guard<std::mutex> lk(g_route_mu); g_routes.clear(); }
+bool glue_routes_read(int index, std::string* name, int64_t* count) {
+  std::lock_guard<std::mutex> lk(g_route_mu);
+  if (index < 0 || (size_t)index >= g_routes.size()) return false;
+  auto it = g_routes.begin();
+  std::advance(it, index);
+  *name = it->first; *count = it->second;
+  return true;
+}
+#endif
+// element type of a template route's name
+template <typename T> struct RouteT;
+template <> struct RouteT<float> { static constexpr bool half = false; };
+template <> struct RouteT<__half> { static constexpr bool half = true; };
 
 static inline dim3 grid1d(size_t n, int block = 256) {
   size_t g = (n + block - 1) / block;
@@ -55,6 +78,7 @@ __global__ void k_u8nhwc_to_f32nchw(const uint8_t* __restrict__ in, float* __res
 }
 void op_u8nhwc_to_f32nchw(const uint8_t* in, float* out, int n, int h, int w, int c, hipStream_t st) {
   const size_t total = (size_t)n * h * w;
+  SS4K_GLUE_ROUTE("glue::u8nhwc_to_f32nchw");
   hipLaunchKernelGGL(k_u8nhwc_to_f32nchw, grid1d(total), dim3(256), 0, st, in, out, n, h, w, c); SS4K_LAUNCH_OK();
 }
 
@@ -112,19 +136,26 @@ static bool area_whole(const HT* in, float* out, int planes, int h, int w, int o
   if (h % oh || w % ow || (reinterpret_cast<uintptr_t>(in) & 15)) return false;
   const int ky = h / oh, kx = w / ow;
   const dim3 g((unsigned)std::min((ow + 255) / 256, 64), (unsigned)oh, (unsigned)planes);
-  if (kx == 4) hipLaunchKernelGGL((k_area_whole<NORM, 4, HT>), g, dim3(256), 0, st, in, out, planes, h, w, oh, ow, ky, st_hr, st_lr);
-  else if (kx == 8) hipLaunchKernelGGL((k_area_whole<NORM, 8, HT>), g, dim3(256), 0, st, in, out, planes, h, w, oh, ow, ky, st_hr, st_lr);
-  else return false;
+  constexpr bool HF = RouteT<HT>::half;
+  if (kx == 4) {
+    SS4K_GLUE_ROUTE(NORM ? (HF ? "glue::area_whole<NORM,4,half>" : "glue::area_whole<NORM,4,float>") : "glue::area_whole<4>");
+    hipLaunchKernelGGL((k_area_whole<NORM, 4, HT>), g, dim3(256), 0, st, in, out, planes, h, w, oh, ow, ky, st_hr, st_lr);
+  } else if (kx == 8) {
+    SS4K_GLUE_ROUTE(NORM ? (HF ? "glue::area_whole<NORM,8,half>" : "glue::area_whole<NORM,8,float>") : "glue::area_whole<8>");
+    hipLaunchKernelGGL((k_area_whole<NORM, 8, HT>), g, dim3(256), 0, st, in, out, planes, h, w, oh, ow, ky, st_hr, st_lr);
+  } else return false;
   return true;
 }
 static inline dim3 grid_rows(int ow, int oh, int planes) { return dim3((unsigned)std::min((ow + 255) / 256, 64), (unsigned)oh, (unsigned)planes); }
 void op_area(const float* in, float* out, int planes, int h, int w, int oh, int ow, hipStream_t st) {
   if (h == oh && w == ow) {
+    SS4K_GLUE_ROUTE("glue::area_identity");
     (void)hipMemcpyAsync(out, in, (size_t)planes * h * w * sizeof(float), hipMemcpyDeviceToDevice, st);
     return;
   }
   SS4K_REQUIRE(oh <= 65535 && planes <= 65535, "area: grid limits");
   if (area_whole<false>(in, out, planes, h, w, oh, ow, nullptr, nullptr, st)) { SS4K_LAUNCH_OK(); return; }
+  SS4K_GLUE_ROUTE("glue::area");
   hipLaunchKernelGGL(k_area<false>, grid_rows(ow, oh, planes), dim3(256), 0, st, in, out, planes, h, w, oh, ow, nullptr, nullptr); SS4K_LAUNCH_OK();
 }
 template <typename HT>
@@ -132,19 +163,23 @@ void op_area_normalized(const HT* in, float* out, int planes, int h, int w, int 
                         hipStream_t st) {
   SS4K_REQUIRE(oh <= 65535 && planes <= 65535, "area: grid limits");
   if (area_whole<true, HT>(in, out, planes, h, w, oh, ow, st_hr, st_lr, st)) { SS4K_LAUNCH_OK(); return; }
+  SS4K_GLUE_ROUTE(RouteT<HT>::half ? "glue::area<NORM,half>" : "glue::area<NORM,float>");
   hipLaunchKernelGGL((k_area<true, HT>), grid_rows(ow, oh, planes), dim3(256), 0, st, in, out, planes, h, w, oh, ow, st_hr, st_lr); SS4K_LAUNCH_OK();
 }
 template void op_area_normalized<float>(const float*, float*, int, int, int, int, int, const float*, const float*, hipStream_t);
 template void op_area_normalized<__half>(const __half*, float*, int, int, int, int, int, const float*, const float*, hipStream_t);
 
 // ------------------------------------------------------------------ per-plane mean / unbiased std
+// which loop a plane takes: ONE predicate for the kernels and for the dev library's route report (stats_route), so the two cannot drift apart
+__host__ __device__ __forceinline__ bool stats_plane_vec4(const void* plane, int hw) { return (hw & 3) == 0 && (reinterpret_cast<uintptr_t>(plane) & 15) == 0; }
+__host__ __device__ __forceinline__ bool stats_frame_vec12(const void* frame, int hw) { return (hw & 3) == 0 && (reinterpret_cast<uintptr_t>(frame) & 3) == 0; }
 template <typename HT = float>
 __global__ void k_stats_partial(const HT* __restrict__ in, double* __restrict__ acc, int hw, int acc_planes = 0, int plane0 = 0) {
   const int pl = blockIdx.y;
   if (acc_planes == 0) acc_planes = gridDim.y;
   const HT* src = in + (size_t)pl * hw;
   double s = 0.0, q = 0.0;
-  if ((hw & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+  if (stats_plane_vec4(src, hw)) {
     // four values per load, four independent fp64 chains (the sums are order-free: the partials meet in atomics anyway), FOUR loads in
     // flight per thread: with one (rounds 1-5) the pass ran at 4 TB/s - 84 % of its wave cycles waiting (profiles/r06_fsrcnn_f16_sq_counters.json)
     double s4[4] = {0, 0, 0, 0}, q4[4] = {0, 0, 0, 0};
@@ -199,7 +234,25 @@ __global__ void k_stats_final(const double* __restrict__ acc, float* __restrict_
   stats[2 * p + 1] = (float)sqrt(var);
 }
 void op_plane_stats_finish(const double* acc, float* stats, int planes, int hw, hipStream_t st) {
+  SS4K_GLUE_ROUTE("glue::stats_final");
   hipLaunchKernelGGL(k_stats_final, dim3((planes + 63) / 64), dim3(64), 0, st, acc, stats, planes, hw); SS4K_LAUNCH_OK();
+}
+// which loop of k_stats_partial the planes take, by the kernel's own predicate on every plane's address: vec4 = all of them the 16-byte
+// loop, scalar = none, mixed = some (fp16 planes of hw % 8 == 4 values alternate between 16- and 8-byte alignment)
+template <typename HT>
+static const char* stats_route(const HT* in, int planes, int hw) {
+  constexpr bool HF = RouteT<HT>::half;
+  int vec = 0;
+  for (int p = 0; p < planes; ++p) vec += stats_plane_vec4(in + (size_t)p * hw, hw) ? 1 : 0;
+  if (vec == planes) return HF ? "glue::stats_partial<vec4,half>" : "glue::stats_partial<vec4,float>";
+  // (fp32 planes of hw % 4 == 0 values lie a multiple of 16 bytes apart: all or none)
+  if (vec == 0 || !HF) return HF ? "glue::stats_partial<scalar,half>" : "glue::stats_partial<scalar,float>";
+  return "glue::stats_partial<mixed,half>";
+}
+static const char* stats_u8_route(const uint8_t* in, int n, int hw) {
+  int vec = 0;
+  for (int f = 0; f < n; ++f) vec += stats_frame_vec12(in + (size_t)f * hw * 3, hw) ? 1 : 0;
+  return vec == n ? "glue::stats_partial_u8<vec12>" : "glue::stats_partial_u8<scalar>";   // (frames of hw % 4 == 0 pixels lie 12 k bytes apart: all or none)
 }
 template <typename HT>
 void op_plane_stats(double* acc, const HT* in, float* stats, int planes, int hw, hipStream_t st) {
@@ -207,6 +260,7 @@ void op_plane_stats(double* acc, const HT* in, float* stats, int planes, int hw,
   SS4K_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 2 * planes * STATS_SLOTS, st));
   int gx = (hw + 256 * 16 - 1) / (256 * 16);
   gx = std::max(1, std::min(gx, 128));
+  SS4K_GLUE_ROUTE(stats_route(in, planes, hw));
   hipLaunchKernelGGL(k_stats_partial<HT>, dim3(gx, planes), dim3(256), 0, st, in, acc, hw); SS4K_LAUNCH_OK();
   op_plane_stats_finish(acc, stats, planes, hw, st);
 }
@@ -221,7 +275,7 @@ __global__ void k_stats_partial_u8(const uint8_t* __restrict__ in, double* __res
   __syncthreads();
   double s[3] = {0, 0, 0}, q[3] = {0, 0, 0};
   // four pixels = twelve bytes = three aligned words per step where the frame allows it
-  const bool vec = (hw & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0;
+  const bool vec = stats_frame_vec12(src, hw);
   if (vec) {
     const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src);
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)hw / 4; i += (size_t)gridDim.x * blockDim.x) {
@@ -259,18 +313,21 @@ void op_plane_stats_u8nhwc(double* acc, const uint8_t* in, float* stats, int n, 
   SS4K_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 2 * planes * STATS_SLOTS, st));
   int gx = (hw + 256 * 16 - 1) / (256 * 16);
   gx = std::max(1, std::min(gx, 128));
+  SS4K_GLUE_ROUTE(stats_u8_route(in, n, hw));
   hipLaunchKernelGGL(k_stats_partial_u8, dim3(gx, n), dim3(256), 0, st, in, acc, hw, planes); SS4K_LAUNCH_OK();
   op_plane_stats_finish(acc, stats, planes, hw, st);
 }
 void op_plane_stats_u8nhwc_partial(double* acc, const uint8_t* in, int n, int hw, int acc_planes, int plane0, hipStream_t st) {
   int gx = (hw + 256 * 16 - 1) / (256 * 16);
   gx = std::max(1, std::min(gx, 128));
+  SS4K_GLUE_ROUTE(stats_u8_route(in, n, hw));
   hipLaunchKernelGGL(k_stats_partial_u8, dim3(gx, n), dim3(256), 0, st, in, acc, hw, acc_planes, plane0); SS4K_LAUNCH_OK();
 }
 template <typename HT>
 void op_plane_stats_partial(double* acc, const HT* in, int planes, int hw, int acc_planes, int plane0, hipStream_t st) {
   int gx = (hw + 256 * 16 - 1) / (256 * 16);
   gx = std::max(1, std::min(gx, 128));
+  SS4K_GLUE_ROUTE(stats_route(in, planes, hw));
   hipLaunchKernelGGL(k_stats_partial<HT>, dim3(gx, planes), dim3(256), 0, st, in, acc, hw, acc_planes, plane0); SS4K_LAUNCH_OK();
 }
 template void op_plane_stats_partial<float>(double*, const float*, int, int, int, int, hipStream_t);
@@ -296,6 +353,7 @@ __global__ void k_stats_final2(double* __restrict__ acc, float* __restrict__ sa,
   o[1] = (float)sqrt(var);
 }
 void op_plane_stats_finish2(double* acc, float* stats_a, float* stats_b, int planes, int hw_a, int hw_b, bool rezero, hipStream_t st) {
+  SS4K_GLUE_ROUTE(rezero ? "glue::stats_final2<rezero>" : "glue::stats_final2");
   hipLaunchKernelGGL(k_stats_final2, dim3((2 * planes + 63) / 64), dim3(64), 0, st, acc, stats_a, stats_b, planes, hw_a, hw_b, rezero ? 1 : 0); SS4K_LAUNCH_OK();
 }
 template void op_plane_stats<float>(double*, const float*, float*, int, int, hipStream_t);
@@ -315,6 +373,7 @@ __global__ void k_normalize(float* __restrict__ x, const float* __restrict__ st_
 }
 void op_normalize(float* x, const float* st_hr, const float* st_lr, int planes, int hw, hipStream_t st) {
   int gx = std::max(1, std::min((hw + 255) / 256, 1024));
+  SS4K_GLUE_ROUTE("glue::normalize");
   hipLaunchKernelGGL(k_normalize, dim3(gx, planes), dim3(256), 0, st, x, st_hr, st_lr, planes, hw); SS4K_LAUNCH_OK();
 }
 
@@ -351,6 +410,7 @@ void op_depthwise_reflect(const float* in, float* out, const float* taps_dev, in
   SS4K_REQUIRE(k == 3 || k == 17, "depthwise: kernel size 3 or 17 (the service's sharpen / blur kernels)");
   // torch's reflect padding requires pad < size and raises otherwise (fsrcnn_upscaler.py:20-84 kernels)
   SS4K_REQUIRE(h > k / 2 && w > k / 2, "depthwise reflect: padding (k/2) must be smaller than the plane, as torch requires");
+  SS4K_GLUE_ROUTE(k == 3 ? "glue::depthwise_reflect<3>" : "glue::depthwise_reflect<17>");
   if (k == 3) {
     hipLaunchKernelGGL(k_depthwise_reflect<3>, grid_rows(w, h, planes), dim3(256), 0, st, in, out, taps_dev, planes, h, w,
                        clamp01, blend_src, blend_a, blend_b);
@@ -384,6 +444,7 @@ __global__ void k_gauss17(const float* __restrict__ in, float* __restrict__ out,
 void op_gauss17_reflect(const float* in, float* tmp, float* out, const float* g17_dev, int planes, int h, int w, hipStream_t st) {
   SS4K_REQUIRE(h <= 65535 && planes <= 65535, "gauss17: grid limits");
   SS4K_REQUIRE(h > 8 && w > 8, "gauss17 reflect: padding (8) must be smaller than the plane, as torch requires");
+  SS4K_GLUE_ROUTE("glue::gauss17");
   hipLaunchKernelGGL(k_gauss17<false>, grid_rows(w, h, planes), dim3(256), 0, st, in, tmp, g17_dev, planes, h, w);
   hipLaunchKernelGGL(k_gauss17<true>, grid_rows(w, h, planes), dim3(256), 0, st, tmp, out, g17_dev, planes, h, w);
   SS4K_LAUNCH_OK();
@@ -427,17 +488,28 @@ void op_bilinear(const float* in, float* out, int planes, int h, int w, int oh, 
                  int clamp01, hipStream_t st) {
   SS4K_REQUIRE(oh <= 65535 && planes <= 65535, "bilinear: grid limits");
   if (ow % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+    SS4K_GLUE_ROUTE("glue::bilinear<4>");
     hipLaunchKernelGGL(k_bilinear<4>, grid_rows(ow / 4, oh, planes), dim3(256), 0, st, in, out, planes, h, w, oh, ow,
                        subtract_from_out, clamp01);
   } else {
+    SS4K_GLUE_ROUTE("glue::bilinear<1>");
     hipLaunchKernelGGL(k_bilinear<1>, grid_rows(ow, oh, planes), dim3(256), 0, st, in, out, planes, h, w, oh, ow,
                        subtract_from_out, clamp01);
   }
   SS4K_LAUNCH_OK();
 }
 
-__device__ __forceinline__ float cc1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
-__device__ __forceinline__ float cc2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
+// Every rounding of the bicubic kernels is spelled out (fmaf, or a lone product): k_bicubic, k_bicubic_u8 and k_bicubic_u8_half promise each
+// other identical results, and with the contraction left to the compiler they did not keep it - the general kernel's row sums came out as
+// packed multiply + add pairs, the 2:1 kernel's as fused multiply-adds, and one byte in 1e5 differed
+// (tests/test_gpu_glue_budget.py::test_bicubic_u8_two_kernels_give_identical_bytes)
+__device__ __forceinline__ float cc1(float x, float A) { return fmaf(fmaf(A + 2.f, x, -(A + 3.f)) * x, x, 1.f); }
+__device__ __forceinline__ float cc2(float x, float A) { return fmaf(fmaf(fmaf(A, x, -5.f * A), x, 8.f * A), x, -4.f * A); }
+// source coordinate of output index o (align_corners=False), and sum_b c[b] * v[b] in index order
+__device__ __forceinline__ float cubic_src(float scale, int o) { return fmaf(scale, o + 0.5f, -0.5f); }
+__device__ __forceinline__ float cubic_dot(const float* c, float v0, float v1, float v2, float v3) {
+  return fmaf(c[3], v3, fmaf(c[2], v2, fmaf(c[1], v1, c[0] * v0)));
+}
 __device__ __forceinline__ void cubic_coeffs(float t, float* c) {
   const float A = -0.75f;
   c[0] = cc2(t + 1.f, A); c[1] = cc1(t, A); c[2] = cc1(1.f - t, A); c[3] = cc2(2.f - t, A);
@@ -448,7 +520,7 @@ __global__ void k_bicubic(const float* __restrict__ in, float* __restrict__ out,
   const float sy = (float)h / oh, sx = (float)w / ow;
   const float* src = in + (size_t)pl * h * w;
   float* dst = out + ((size_t)pl * oh + oy) * ow;
-  const float fy = sy * (oy + 0.5f) - 0.5f, fly = floorf(fy);
+  const float fy = cubic_src(sy, oy), fly = floorf(fy);
   const int iy = (int)fly;
   float cy[4];
   cubic_coeffs(fy - fly, cy);
@@ -456,7 +528,7 @@ __global__ void k_bicubic(const float* __restrict__ in, float* __restrict__ out,
 #pragma unroll
   for (int a = 0; a < 4; ++a) rows[a] = src + (size_t)min(max(iy - 1 + a, 0), h - 1) * w;
   for (int ox = blockIdx.x * blockDim.x + threadIdx.x; ox < ow; ox += gridDim.x * blockDim.x) {
-    const float fx = sx * (ox + 0.5f) - 0.5f, flx = floorf(fx);
+    const float fx = cubic_src(sx, ox), flx = floorf(fx);
     const int ix = (int)flx;
     float cx[4]; int xi[4];
     cubic_coeffs(fx - flx, cx);
@@ -464,18 +536,14 @@ __global__ void k_bicubic(const float* __restrict__ in, float* __restrict__ out,
     for (int b = 0; b < 4; ++b) xi[b] = min(max(ix - 1 + b, 0), w - 1);
     float acc = 0.f;
 #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      float row = 0.f;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) row += cx[b] * rows[a][xi[b]];
-      acc += cy[a] * row;
-    }
+    for (int a = 0; a < 4; ++a) acc = fmaf(cy[a], cubic_dot(cx, rows[a][xi[0]], rows[a][xi[1]], rows[a][xi[2]], rows[a][xi[3]]), acc);
     if (clamp01) acc = fminf(fmaxf(acc, 0.f), 1.f);
     dst[ox] = acc;
   }
 }
 void op_bicubic(const float* in, float* out, int planes, int h, int w, int oh, int ow, int clamp01, hipStream_t st) {
   SS4K_REQUIRE(oh <= 65535 && planes <= 65535, "bicubic: grid limits");
+  SS4K_GLUE_ROUTE("glue::bicubic");
   hipLaunchKernelGGL(k_bicubic, grid_rows(ow, oh, planes), dim3(256), 0, st, in, out, planes, h, w, oh, ow, clamp01); SS4K_LAUNCH_OK();
 }
 
@@ -576,8 +644,19 @@ void op_tail_fused(HT* hr, uint8_t* out_u8, const float* diff, int n, int c, int
   SS4K_REQUIRE(h <= 65535 && n <= 65535, "fused tail: grid limits");
   const dim3 g = grid_rows(w, h, n);
   const bool norm = st_hr != nullptr, df = diff != nullptr, u8 = out_u8 != nullptr;
+#ifdef SS4K_DEV
+  // glue::tail_fused[4]<NORM,DIFF,U8,float|half> with only the flags that are on, in that order
+  static const char* const names[2][2][8] = {
+#define SS4K_TAIL_NAMES(K_, T_) {"glue::" K_ "<" T_ ">", "glue::" K_ "<U8," T_ ">", "glue::" K_ "<DIFF," T_ ">", "glue::" K_ "<DIFF,U8," T_ ">", \
+                                 "glue::" K_ "<NORM," T_ ">", "glue::" K_ "<NORM,U8," T_ ">", "glue::" K_ "<NORM,DIFF," T_ ">", "glue::" K_ "<NORM,DIFF,U8," T_ ">"}
+      {SS4K_TAIL_NAMES("tail_fused", "float"), SS4K_TAIL_NAMES("tail_fused", "half")},
+      {SS4K_TAIL_NAMES("tail_fused4", "float"), SS4K_TAIL_NAMES("tail_fused4", "half")}};
+#undef SS4K_TAIL_NAMES
+  const int flag_ix = (norm ? 4 : 0) | (df ? 2 : 0) | (u8 ? 1 : 0);
+#endif
   if (c == 3 && (w & 3) == 0 && (reinterpret_cast<uintptr_t>(hr) & 15) == 0 && (reinterpret_cast<uintptr_t>(out_u8) & 3) == 0) {
     const dim3 g4 = grid_rows(w / 4, h, n);
+    SS4K_GLUE_ROUTE(names[1][RouteT<HT>::half][flag_ix]);
 #define SS4K_TAIL4(N_, D_, U_) hipLaunchKernelGGL((k_tail_fused4<N_, D_, U_, HT>), g4, dim3(256), 0, st, hr, out_u8, diff, n, h, w, dh, dw, st_hr, st_lr)
     if (norm && df && u8) SS4K_TAIL4(true, true, true); else if (norm && df) SS4K_TAIL4(true, true, false);
     else if (norm && u8) SS4K_TAIL4(true, false, true); else if (norm) SS4K_TAIL4(true, false, false);
@@ -587,6 +666,7 @@ void op_tail_fused(HT* hr, uint8_t* out_u8, const float* diff, int n, int c, int
     SS4K_LAUNCH_OK();
     return;
   }
+  SS4K_GLUE_ROUTE(names[0][RouteT<HT>::half][flag_ix]);
 #define SS4K_TAIL(N_, D_, U_) hipLaunchKernelGGL((k_tail_fused<N_, D_, U_, HT>), g, dim3(256), 0, st, hr, out_u8, diff, n, c, h, w, dh, dw, st_hr, st_lr)
   if (norm && df && u8) SS4K_TAIL(true, true, true); else if (norm && df) SS4K_TAIL(true, true, false);
   else if (norm && u8) SS4K_TAIL(true, false, true); else if (norm) SS4K_TAIL(true, false, false);
@@ -604,7 +684,7 @@ template <typename HT = float>
 __global__ void k_bicubic_u8(const HT* __restrict__ in, uint8_t* __restrict__ out, int n, int c, int h, int w, int oh, int ow) {
   const int oy = blockIdx.y, img = blockIdx.z;
   const float sy = (float)h / oh, sx = (float)w / ow;
-  const float fy = sy * (oy + 0.5f) - 0.5f, fly = floorf(fy);
+  const float fy = cubic_src(sy, oy), fly = floorf(fy);
   const int iy = (int)fly;
   float cy[4];
   cubic_coeffs(fy - fly, cy);
@@ -612,7 +692,7 @@ __global__ void k_bicubic_u8(const HT* __restrict__ in, uint8_t* __restrict__ ou
 #pragma unroll
   for (int a = 0; a < 4; ++a) yi[a] = min(max(iy - 1 + a, 0), h - 1);
   for (int ox = blockIdx.x * blockDim.x + threadIdx.x; ox < ow; ox += gridDim.x * blockDim.x) {
-    const float fx = sx * (ox + 0.5f) - 0.5f, flx = floorf(fx);
+    const float fx = cubic_src(sx, ox), flx = floorf(fx);
     const int ix = (int)flx;
     float cx[4]; int xi[4];
     cubic_coeffs(fx - flx, cx);
@@ -624,10 +704,7 @@ __global__ void k_bicubic_u8(const HT* __restrict__ in, uint8_t* __restrict__ ou
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
         const HT* rowp = src + (size_t)yi[a] * w;
-        float row = 0.f;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) row += cx[b] * hr_ld(rowp + xi[b]);
-        acc += cy[a] * row;
+        acc = fmaf(cy[a], cubic_dot(cx, hr_ld(rowp + xi[0]), hr_ld(rowp + xi[1]), hr_ld(rowp + xi[2]), hr_ld(rowp + xi[3])), acc);
       }
       acc = fminf(fmaxf(acc, 0.f), 1.f);
       out[(((size_t)img * oh + oy) * ow + ox) * c + k] = (uint8_t)(fminf(fmaxf(acc, 0.f), 1.f) * 255.f);
@@ -643,7 +720,7 @@ __global__ void k_bicubic_u8_half(const HT* __restrict__ in, uint8_t* __restrict
   constexpr int C = 3;
   const int oy = blockIdx.y, img = blockIdx.z;
   const float sy = (float)h / oh, sx = (float)w / ow;
-  const float fy = sy * (oy + 0.5f) - 0.5f, fly = floorf(fy);
+  const float fy = cubic_src(sy, oy), fly = floorf(fy);
   const int iy = (int)fly;
   float cy[4];
   cubic_coeffs(fy - fly, cy);
@@ -654,7 +731,7 @@ __global__ void k_bicubic_u8_half(const HT* __restrict__ in, uint8_t* __restrict
     float cx[4][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float fx = sx * (4 * t + j + 0.5f) - 0.5f;
+      const float fx = cubic_src(sx, 4 * t + j);
       cubic_coeffs(fx - floorf(fx), cx[j]);
     }
     const int xl = max(8 * t - 1, 0), xr = min(8 * t + 8, w - 1);
@@ -669,12 +746,7 @@ __global__ void k_bicubic_u8_half(const HT* __restrict__ in, uint8_t* __restrict
         const float4 m0 = hr_ld4<HT>(rowp + 8 * t), m1 = hr_ld4<HT>(rowp + 8 * t + 4);
         const float col[10] = {hr_ld(rowp + xl), m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, hr_ld(rowp + xr)};   // columns 8t-1 .. 8t+8
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float row = 0.f;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) row += cx[j][q] * col[2 * j + q];
-          acc[j] += cy[a] * row;
-        }
+        for (int j = 0; j < 4; ++j) acc[j] = fmaf(cy[a], cubic_dot(cx[j], col[2 * j], col[2 * j + 1], col[2 * j + 2], col[2 * j + 3]), acc[j]);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -695,9 +767,11 @@ template <typename HT>
 void op_bicubic_u8(const HT* in, uint8_t* out, int n, int c, int h, int w, int oh, int ow, hipStream_t st) {
   SS4K_REQUIRE(oh <= 65535 && n <= 65535, "bicubic: grid limits");
   if (c == 3 && h == 2 * oh && w == 2 * ow && (ow & 3) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0) {
+    SS4K_GLUE_ROUTE(RouteT<HT>::half ? "glue::bicubic_u8_half<half>" : "glue::bicubic_u8_half<float>");
     hipLaunchKernelGGL(k_bicubic_u8_half<HT>, grid_rows(ow / 4, oh, n), dim3(256), 0, st, in, out, n, h, w, oh, ow); SS4K_LAUNCH_OK();
     return;
   }
+  SS4K_GLUE_ROUTE(RouteT<HT>::half ? "glue::bicubic_u8<half>" : "glue::bicubic_u8<float>");
   hipLaunchKernelGGL(k_bicubic_u8<HT>, grid_rows(ow, oh, n), dim3(256), 0, st, in, out, n, c, h, w, oh, ow); SS4K_LAUNCH_OK();
 }
 template void op_bicubic_u8<float>(const float*, uint8_t*, int, int, int, int, int, int, hipStream_t);
@@ -709,13 +783,14 @@ __global__ void k_sub(const float* __restrict__ a, const float* __restrict__ b, 
     out[i] = a[i] - b[i];
 }
 void op_sub(const float* a, const float* b, float* out, size_t n, hipStream_t st) {
+  SS4K_GLUE_ROUTE("glue::sub");
   hipLaunchKernelGGL(k_sub, grid1d(n), dim3(256), 0, st, a, b, out, n); SS4K_LAUNCH_OK();
 }
 __global__ void k_clamp01(float* __restrict__ x, size_t n) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     x[i] = fminf(fmaxf(x[i], 0.f), 1.f);
 }
-void op_clamp01(float* x, size_t n, hipStream_t st) { hipLaunchKernelGGL(k_clamp01, grid1d(n), dim3(256), 0, st, x, n); SS4K_LAUNCH_OK(); }
+void op_clamp01(float* x, size_t n, hipStream_t st) { SS4K_GLUE_ROUTE("glue::clamp01"); hipLaunchKernelGGL(k_clamp01, grid1d(n), dim3(256), 0, st, x, n); SS4K_LAUNCH_OK(); }
 
 // cv2.resize(img, None, fx, fy, INTER_AREA) on uint8 NHWC frames, shrinking by a non-integer factor: the image server's pre / post scale
 // (image_pipeline.py:272-273, 347-348).  OpenCV's general area path (modules/imgproc/src/resize.cpp, computeResizeAreaTab +
@@ -778,6 +853,7 @@ __global__ void k_f32nchw_to_u8nhwc(const float* __restrict__ in, uint8_t* __res
   }
 }
 void op_f32nchw_to_u8nhwc(const float* in, uint8_t* out, int n, int c, int h, int w, hipStream_t st) {
+  SS4K_GLUE_ROUTE("glue::f32nchw_to_u8nhwc");
   hipLaunchKernelGGL(k_f32nchw_to_u8nhwc, grid1d((size_t)n * h * w), dim3(256), 0, st, in, out, n, c, h, w); SS4K_LAUNCH_OK();
 }
 
@@ -817,6 +893,11 @@ __global__ void k_pack_input(const float* __restrict__ in, T* __restrict__ out, 
 template <typename T>
 void op_pack_input(const float* in, T* out, int n, int c, int h, int w, int r, int nplanes, hipStream_t st) {
   const dim3 g = grid1d((size_t)n * (h / r) * (w / r));
+  constexpr bool HF = RouteT<T>::half;
+  if (r == 1 || r == 2 || r == 4)
+    SS4K_GLUE_ROUTE(r == 1 ? (HF ? "glue::pack_input<half,1>" : "glue::pack_input<float,1>")
+                    : r == 2 ? (HF ? "glue::pack_input<half,2>" : "glue::pack_input<float,2>")
+                             : (HF ? "glue::pack_input<half,4>" : "glue::pack_input<float,4>"));
   if (r == 1) { hipLaunchKernelGGL((k_pack_input<T, 1>), g, dim3(256), 0, st, in, out, n, c, h, w, nplanes); }
   else if (r == 2) { hipLaunchKernelGGL((k_pack_input<T, 2>), g, dim3(256), 0, st, in, out, n, c, h, w, nplanes); }
   else if (r == 4) { hipLaunchKernelGGL((k_pack_input<T, 4>), g, dim3(256), 0, st, in, out, n, c, h, w, nplanes); }
@@ -892,6 +973,16 @@ void op_ps_nchw_addbase(const T* src, HT* out, const float* base, int n, int h, 
   SS4K_REQUIRE(h <= 65535 && n <= 65535, "pixel shuffle tail: grid limits");
   SS4K_REQUIRE(!stats_acc || cq <= 4, "pixel shuffle tail: statistics for at most 4 colours");
   if (stats_acc) SS4K_HIP(hipMemsetAsync(stats_acc, 0, sizeof(double) * 2 * n * cq * STATS_SLOTS, st));
+#ifdef SS4K_DEV
+  if (r == 2 || r == 4) {
+    // glue::ps_nchw_addbase<T,R[,STATS],HT>
+    static const char* const names[3][2][2] = {
+        {{"glue::ps_nchw_addbase<float,2,float>", "glue::ps_nchw_addbase<float,2,STATS,float>"}, {"glue::ps_nchw_addbase<float,4,float>", "glue::ps_nchw_addbase<float,4,STATS,float>"}},
+        {{"glue::ps_nchw_addbase<half,2,float>", "glue::ps_nchw_addbase<half,2,STATS,float>"}, {"glue::ps_nchw_addbase<half,4,float>", "glue::ps_nchw_addbase<half,4,STATS,float>"}},
+        {{"glue::ps_nchw_addbase<half,2,half>", "glue::ps_nchw_addbase<half,2,STATS,half>"}, {"glue::ps_nchw_addbase<half,4,half>", "glue::ps_nchw_addbase<half,4,STATS,half>"}}};
+    SS4K_GLUE_ROUTE(names[RouteT<T>::half + RouteT<HT>::half][r == 4][stats_acc != nullptr]);
+  }
+#endif
   if (r == 4) {
     if (stats_acc) { hipLaunchKernelGGL((k_ps_nchw_addbase<T, 4, true, HT>), grid_rows(w, h, n), dim3(256), 0, st, src, out, base, n, h, w, cq, stats_acc); }
     else { hipLaunchKernelGGL((k_ps_nchw_addbase<T, 4, false, HT>), grid_rows(w, h, n), dim3(256), 0, st, src, out, base, n, h, w, cq, stats_acc); }
@@ -929,6 +1020,7 @@ void op_temporal_shift(const void* in, void* out, int nplanes, int frames, size_
                        int ch_per_plane, int fold, hipStream_t st) {
   if (fold % (ch_per_plane / slots_per_record) != 0)
     throw Error(SS4K_EINVAL, "temporal shift: fold must be a multiple of the 16-byte channel group");
+  SS4K_GLUE_ROUTE("glue::temporal_shift");
   hipLaunchKernelGGL(k_temporal_shift, grid1d((size_t)nplanes * frames * frame_px * slots_per_record), dim3(256), 0, st,
                      reinterpret_cast<const uint4*>(in), reinterpret_cast<uint4*>(out), nplanes, frames, frame_px,
                      slots_per_record, ch_per_plane, fold); SS4K_LAUNCH_OK();

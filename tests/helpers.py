@@ -107,12 +107,13 @@ def _f64(a):
     return a.astype(np.float64)
 
 
-def error_budget(got, ref64, yard, *, u, tiles=(1,)):
+def error_budget(got, ref64, yard, *, u, tiles=(1,), col_bands=()):
     """The two measures of ``assert_error_budget`` without a verdict: ``{"max": ..., "slice": ..., "worst_slice": ...}``.
 
     ``max`` = max|got - ref64| / max(max|yard - ref64|, u max|ref64|); ``slice`` = the largest (rms(E_s) - u max|ref64|) / rms(N_s)
     over the slices of at least 64 elements (frames, output channels, output rows, output columns, the row bands of 16 and 20 and
-    the column bands of 32 pixels of every tile grid in ``tiles`` - output pixels per layer pixel -, the one-pixel border ring)."""
+    the column bands of 32 pixels of every tile grid in ``tiles`` - output pixels per layer pixel -, the one-pixel border ring;
+    ``col_bands``: further column band widths, e.g. 4 for a kernel that writes four-pixel groups)."""
     g, r, y = _f64(got), _f64(ref64), _f64(yard)
     assert g.shape == r.shape == y.shape, f"shapes {g.shape} {r.shape} {y.shape}"
     g, r, y = (a.reshape((-1,) + a.shape[-3:]) for a in (g, r, y))   # (frames, channels, rows, columns)
@@ -140,13 +141,16 @@ def error_budget(got, ref64, yard, *, u, tiles=(1,)):
                                         ("column band 32", ec, nc, 32 * s, f * c * h)):
             idx = np.arange(e1.size) // band
             check(f"{name} x{s}", np.bincount(idx, e1), np.bincount(idx, n1), np.bincount(idx) * per)
+    for band in col_bands:
+        idx = np.arange(ec.size) // band
+        check(f"column band {band}", np.bincount(idx, ec), np.bincount(idx, nc), np.bincount(idx) * f * c * h)
     ring = np.zeros((h, w), bool)
     ring[0, :] = ring[-1, :] = ring[:, 0] = ring[:, -1] = True
     check("border ring", np.array([E2[..., ring].sum()]), np.array([N2[..., ring].sum()]), np.array([f * c * ring.sum()]))
     return out
 
 
-def assert_error_budget(got, ref64, yard, *, k_max, k_slice, u, what, tiles=(1,)):
+def assert_error_budget(got, ref64, yard, *, k_max, k_slice, u, what, tiles=(1,), col_bands=()):
     """Element-wise anchor of a result against a float64 reference.  ``E = |got - ref64|`` is held against the yardstick
     ``N = |yard - ref64|`` - a correct implementation of the same precision (fp16 routes: ``oracle.precision.emu16``; fp32
     routes: the fp32 oracle):
@@ -159,7 +163,57 @@ def assert_error_budget(got, ref64, yard, *, k_max, k_slice, u, what, tiles=(1,)
     Returns the worst ratios (``error_budget``) for ``record_measured``."""
     g = _f64(got)
     assert np.isfinite(g).all(), f"{what}: {int((~np.isfinite(g)).sum())} non-finite values"
-    m = error_budget(g, ref64, yard, u=u, tiles=tiles)
+    m = error_budget(g, ref64, yard, u=u, tiles=tiles, col_bands=col_bands)
     assert m["max"] <= k_max, f"{what}: max error {m['max']:.3g} x the yardstick's (bar {k_max})"
     assert m["slice"] <= k_slice, f"{what}: rms error of {m['worst_slice']} {m['slice']:.3g} x the yardstick's (bar {k_slice})"
     return m
+
+
+def u8_interval(v64, tau_lsb):
+    """The bytes a correct truncation of ``v64`` (unclamped float64 values) may give when the float it truncates is off by at most
+    ``tau_lsb`` / 255: ``[floor(255 clip(v - tau / 255)), floor(255 clip(v + tau / 255))]``; returns (lo, hi) as int arrays."""
+    v = _f64(v64)
+    t = tau_lsb / 255.0
+    lo = np.floor(255.0 * np.clip(v - t, 0.0, 1.0)).astype(np.int64)
+    hi = np.floor(255.0 * np.clip(v + t, 0.0, 1.0)).astype(np.int64)
+    return lo, hi
+
+
+def u8_ambiguity(v64, tau_lsb):
+    """Share of the bytes of an NHWC tensor whose interval (``u8_interval``) has two members: (overall, worst row of >= 64 bytes,
+    worst column of >= 64 bytes; 0.0 where no row / column is that long)."""
+    lo, hi = u8_interval(v64, tau_lsb)
+    amb = (hi > lo).reshape((-1,) + lo.shape[-3:])
+    n, h, w, c = amb.shape
+    row = float(amb.mean(axis=(2, 3)).max()) if w * c >= 64 else 0.0
+    col = float(amb.mean(axis=(1, 3)).max()) if h * c >= 64 else 0.0
+    return float(amb.mean()), row, col
+
+
+def assert_u8_within(got, v64, tau_lsb, what="", max_ambiguous=0.05, max_ambiguous_line=0.25):
+    """uint8 frames against the float64 value ``v64`` each byte truncates (NHWC, unclamped), with no allowance by count: every byte lies
+    in its ``u8_interval``.  ``tau_lsb`` = 255 * k_max * max(max|yardstick - v64|, u * max|v64|) of the case.  A case in which more than
+    5 % of the bytes (25 % of a row or column of >= 64 bytes) could take two values tests little and fails as badly chosen.
+    Returns the measured shares for ``record_measured``."""
+    got = got.detach().cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
+    v = _f64(v64)
+    assert got.dtype == np.uint8 and got.shape == v.shape, f"{what}: {got.shape} {got.dtype} vs {v.shape}"
+    assert np.isfinite(v).all(), f"{what}: the reference is not finite"
+    amb, row, col = u8_ambiguity(v, tau_lsb)
+    assert amb <= max_ambiguous and row <= max_ambiguous_line and col <= max_ambiguous_line, \
+        f"{what}: badly chosen case - {amb:.2%} of the bytes ambiguous (worst row {row:.2%}, column {col:.2%}) at tau = {tau_lsb:.3g} LSB"
+    lo, hi = u8_interval(v, tau_lsb)
+    g = got.astype(np.int64)
+    bad = (g < lo) | (g > hi)
+    if bad.any():
+        at = np.unravel_index(int(np.argmax(bad)), bad.shape)
+        raise AssertionError(f"{what}: {int(bad.sum())} / {bad.size} bytes outside their interval at tau = {tau_lsb:.3g} LSB; first at {at}: "
+                             f"got {got[at]}, 255 v = {255 * v[at]:.6f}, allowed [{lo[at]}, {hi[at]}]")
+    return {"ambiguous": amb, "ambiguous_row": row, "ambiguous_col": col, "tau_lsb": float(tau_lsb),
+            "off_floor": float((g != np.floor(255.0 * np.clip(v, 0, 1))).mean())}
+
+
+def u8_tau(yard_v, v64, k_max, u):
+    """tau in LSB of a uint8 case: 255 * k_max * max(max|yardstick - reference|, u * max|reference|) on the float values."""
+    y, v = _f64(yard_v), _f64(v64)
+    return 255.0 * k_max * max(float(np.abs(y - v).max()), u * float(np.abs(v).max()))

@@ -16,7 +16,8 @@ from sharkshark4k_amd.upscale import model as factory
 from oracle import nets as onets
 from oracle import service as osvc
 from tests.conftest import load_golden, manifest
-from tests.helpers import assert_close, assert_u8_close, psnr, record_measured, rrdb_small_table, smooth_u8, srvgg_full_table, srvgg_table_for
+from tests.helpers import (assert_close, assert_u8_close, assert_u8_within, psnr, record_measured, rrdb_small_table, smooth_u8, srvgg_full_table,
+                           srvgg_table_for, u8_tau)
 from tests.test_oracle_golden import _t91, oracle_service_from_manifest
 
 pytestmark = pytest.mark.gpu
@@ -813,3 +814,52 @@ def test_hip_service_fsrcnn_f16_in_process(ctx):
     frac = float((d != 0).float().mean())
     record_measured("svc_fsrcnn_f16_90x124", max_lsb=int(d.max()), frac_differing=frac)
     assert got.shape == want.shape and int(d.max()) <= 1 and frac < 0.06, (int(d.max()), frac)   # measured 3.8-4.4 %
+
+
+# ------------------------------------------------------------------------------ the service's bytes inside their float64 intervals
+def _noise_and_letterbox(seed, h, w):
+    """Two frames: white noise, and a smooth frame under black letterbox bands (a sixth of the height each)."""
+    f = np.stack([np.random.default_rng(seed).integers(0, 256, (h, w, 3), dtype=np.uint8), smooth_u8(seed, (1, h, w, 3))[0]])
+    f[1, :h // 6] = 0
+    f[1, h - h // 6:] = 0
+    return torch.from_numpy(f)
+
+
+@pytest.mark.parametrize("case", ["multi_srvgg_x4_color_bicubic_2to1", "single_fsrcnn_x2_u8_direct", "multi_srvgg_f16_half_hr"])
+def test_service_bytes_within_float64_interval(ctx, case):
+    """The black-box path under the byte criterion of tests/test_gpu_glue_budget.py (``assert_u8_within``: every byte inside the interval
+    its float64 value allows, no allowance by count): the product library's frames against a float64 run of the service pipeline
+    (oracle/glue_ref.py), tau from the float32 run of the same pipeline.  k_max is the bar the network inside is held to by its own
+    budget test (tests/test_gpu_error_budget.py): K32_MAX for the exact-fp32 SRVGG, KSPLIT_MAX for FSRCNN's fp32-grade split.
+    The fp16 case bounds the service's glue on the fp16 HR tensor: the network output is the HIP model's own (its fp16 arithmetic is
+    bounded by the conv budget tests, not here), rounded to fp16 where the kernel rounds it - after the statistics.  No output resize
+    there: with one the fused tail stores its clamped result in fp16 a second time, and a float64 value and the kernel's fp32 value
+    that straddle an fp16 rounding tie would then differ by a whole fp16 step (0.12 LSB) - not a defect, and not inside any tau."""
+    from oracle import glue_ref as G
+    from oracle import precision as P
+    from tests.test_gpu_error_budget import K32_MAX, KSPLIT_MAX
+    lr_shape = (72, 128) if "srvgg" in case else (90, 124)
+    frames = _noise_and_letterbox(len(case), *lr_shape)
+    if case == "single_fsrcnn_x2_u8_direct":
+        tab = W.fsrcnn_table(seed=3)
+        sr = factory.build_model_fsrcnn(ctx, factor=2, weights=tab)
+        up = _capi.Upscaler(ctx, sr, lr_shape, None, True, True, None, 1.0)
+        run = lambda dt, net: G.service_single(frames, lambda x: net(onets.fsrcnn, x, tab, 2), dt, lr_shape)
+        (_, v64), (_, v32), k_max = run(G.F64, P.ref64), run(G.F32, P.fp32_oracle), KSPLIT_MAX
+    elif case == "multi_srvgg_x4_color_bicubic_2to1":
+        tab = W.srvgg_table(5, num_feat=16, num_conv=2, upscale=4)
+        sr = _capi.Model(ctx, _capi.make_desc(_capi.SRVGG, _capi.F32, scale=4, num_feat=16, num_block=2), W.flatten(tab, W.srvgg_keys(2)))
+        up = _capi.Upscaler(ctx, sr, lr_shape, (144, 256), True, False, None, 1.0)
+        run = lambda dt, net: G.service_multi(frames, lambda x: net(onets.srvgg, x, tab, 2, 4), dt, lr_shape, (144, 256))
+        (_, v64), (_, v32), k_max = run(G.F64, P.ref64), run(G.F32, P.fp32_oracle), K32_MAX
+    else:
+        tab = W.dni_blend(W.srvgg_table(3, num_conv=4), W.srvgg_table(4, num_conv=4), 0.5)
+        sr = _capi.Model(ctx, _capi.make_desc(_capi.SRVGG, _capi.F16, scale=4, num_feat=64, num_block=4), W.flatten(tab, W.srvgg_keys(4)))
+        up = _capi.Upscaler(ctx, sr, lr_shape, None, True, False, None, 1.0)
+        hr = sr((frames.permute(0, 3, 1, 2) / 255.0).cuda()).cpu()    # what the PixelShuffle tail computes in fp32 before it stores
+        run = lambda dt: G.service_multi(frames, lambda x: hr.to(dt), dt, lr_shape, None, hr_round=G.round16)
+        (_, v64), (_, v32), k_max = run(G.F64), run(G.F32), K32_MAX
+    got = up(frames.cuda()).cpu()
+    tau = u8_tau(v32, v64, k_max, P.U32)
+    r = assert_u8_within(got, v64, tau, what=case)
+    record_measured(f"svc_u8_within_{case}", **r)
