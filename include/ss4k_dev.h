@@ -2,7 +2,8 @@
  * ss4k_dev.h - measurement-only entry points of libss4k_hip_dev.so (built with -DSS4K_DEV from the
  * same sources as libss4k_hip.so; a superset of include/ss4k.h).  Not part of the product library:
  * the instrumented / alternative-tile-shape instantiations of the conv kernel live only here.
- * Used by tools/stamp4.py, tools/traffic_ablate.py, tools/conv5_routes.py and tests/test_gpu_glue_budget.py.
+ * Used by tools/stamp4.py, tools/traffic_ablate.py, tools/conv5_routes.py, tests/test_gpu_glue_budget.py and
+ * tests/test_gpu_memory_hygiene.py (guard mode, through tests/drive_guarded.py).
  */
 #ifndef SS4K_DEV_H
 #define SS4K_DEV_H
@@ -76,6 +77,25 @@ int ss4k_dev_op_temporal_shift(ss4k_ctx* ctx, const void* in, void* out, int npl
  * _read returns the index-th route in name order (SS4K_EINVAL past the last), _reset clears the table.  Process-wide. */
 int ss4k_dev_glue_routes_reset(void);
 int ss4k_dev_glue_routes_read(int index, char* name, size_t name_capacity, int64_t* launches);
+
+/* ---- guard mode: red zones around, and 0xFF poison in, every device buffer the library allocates (csrc/common.h, DevBuf).
+ * Process-wide, off by default.  With it on, an allocation of `need` bytes is 64 KiB + need + 64 KiB, all 0xFF (NaN in fp16 / fp32 /
+ * fp64) when it is handed out, and the back red zone starts at the requested size, not at the 256-rounded one.  Nothing here makes a
+ * kernel touch memory outside an allocation of the library. */
+/* affects later allocations only; buffers that exist already stay as they are and are counted as "unguarded" */
+int ss4k_dev_guard_enable(int on);
+/* Synchronises the device, scans the red zones of every live guarded buffer and adds the damage recorded when buffers were freed or
+ * re-grown (the sticky list).  guarded / unguarded: live buffers of each kind; damaged: zones with at least one byte != 0xFF; text
+ * (may be NULL): the first damage - front or back, requested bytes, offsets of the first and last damaged byte relative to the payload. */
+int ss4k_dev_guard_check(int* guarded, int* unguarded, int* damaged, char* text, size_t text_capacity);
+/* Refills the payload of the TRANSIENT buffers of the objects given (each may be NULL) with 0xFF, after a synchronisation: a model's
+ * activations, an upscaler's intermediates and taps, a context's named scratch other than the zero page and the cv-area tables.
+ * buffers / bytes: what was filled; bytes_256: the same sizes, each rounded up to 256 (what the product library allocates for them). */
+int ss4k_dev_guard_poison(ss4k_ctx* ctx, ss4k_model* model, ss4k_upscaler* upscaler, int* buffers, size_t* bytes, size_t* bytes_256);
+/* Positive control without a fault: allocates a guarded buffer, writes one byte at payload - 1 and one at payload + need with hipMemset
+ * (both inside the allocation), requires the check to report exactly those two zones with those offsets, releases the buffer and clears
+ * the sticky list.  SS4K_EINVAL with a text if the guard does not see them (or if damage was already on record: run it first). */
+int ss4k_dev_guard_selftest(ss4k_ctx* ctx);
 
 #ifdef __cplusplus
 }

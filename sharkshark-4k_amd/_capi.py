@@ -40,6 +40,8 @@ DEV_SYMBOLS = [
     "ss4k_dev_op_plane_stats_u8nhwc_partial", "ss4k_dev_op_plane_stats_finish", "ss4k_dev_op_plane_stats_finish2",
     "ss4k_dev_op_ps_nchw_addbase", "ss4k_dev_op_pack_input", "ss4k_dev_op_temporal_shift",
     "ss4k_dev_glue_routes_reset", "ss4k_dev_glue_routes_read",
+    # guard mode: red zones and 0xFF poison for every device buffer of the library (tests/test_gpu_memory_hygiene.py)
+    "ss4k_dev_guard_enable", "ss4k_dev_guard_check", "ss4k_dev_guard_poison", "ss4k_dev_guard_selftest",
 ]
 
 
@@ -140,6 +142,11 @@ def load(path: str) -> C.CDLL:
         L.ss4k_dev_op_temporal_shift.argtypes = [vp, vp, vp, i, i, sz, i, i, i, vp]
         L.ss4k_dev_glue_routes_reset.argtypes = []
         L.ss4k_dev_glue_routes_read.argtypes = [i, C.c_char_p, sz, C.POINTER(C.c_int64)]
+    if hasattr(L, "ss4k_dev_guard_check"):  # dev library only: guard mode
+        L.ss4k_dev_guard_enable.argtypes = [i]
+        L.ss4k_dev_guard_check.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), C.c_char_p, sz]
+        L.ss4k_dev_guard_poison.argtypes = [vp, vp, vp, C.POINTER(i), C.POINTER(sz), C.POINTER(sz)]
+        L.ss4k_dev_guard_selftest.argtypes = [vp]
     L.ss4k_prof_enable.argtypes = [vp, i]
     L.ss4k_prof_reset.argtypes = [vp]
     L.ss4k_prof_read.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -163,6 +170,48 @@ def glue_routes(L: C.CDLL) -> dict:
             return out
         out[name.value.decode()] = n.value
         idx += 1
+
+
+def _guard_lib(L: Optional[C.CDLL]) -> C.CDLL:
+    L = L or lib()
+    if not hasattr(L, "ss4k_dev_guard_check"):
+        raise Ss4kError("guard mode lives in libss4k_hip_dev.so: run with SS4K_LIB=<package>/libss4k_hip_dev.so")
+    return L
+
+
+def _guard_rc(L: C.CDLL, rc: int) -> None:
+    if rc != 0:
+        raise Ss4kError(f"libss4k_hip_dev error {rc}: {L.ss4k_last_error().decode()}")
+
+
+def guard_enable(on: bool = True, L: Optional[C.CDLL] = None) -> None:
+    """Guard mode of the dev library (include/ss4k_dev.h): red zones and 0xFF poison for every LATER device allocation of the library."""
+    L = _guard_lib(L)
+    _guard_rc(L, L.ss4k_dev_guard_enable(int(on)))
+
+
+def guard_check(L: Optional[C.CDLL] = None) -> Tuple[int, int, int, str]:
+    """(guarded live buffers, unguarded live buffers, damaged red zones, text of the first damage); synchronises the device."""
+    L = _guard_lib(L)
+    g, u, d, text = C.c_int(), C.c_int(), C.c_int(), C.create_string_buffer(512)
+    _guard_rc(L, L.ss4k_dev_guard_check(C.byref(g), C.byref(u), C.byref(d), text, 512))
+    return g.value, u.value, d.value, text.value.decode()
+
+
+def guard_poison(ctx=None, model=None, upscaler=None, L: Optional[C.CDLL] = None) -> Tuple[int, int, int]:
+    """0xFF into the transient buffers of the objects given (handles or the wrappers of this module): (buffers, bytes, bytes rounded
+    up to 256 per buffer)."""
+    L = _guard_lib(L)
+    h = [getattr(o, "_h", o) for o in (ctx, model, upscaler)]
+    n, b, b256 = C.c_int(), C.c_size_t(), C.c_size_t()
+    _guard_rc(L, L.ss4k_dev_guard_poison(*h, C.byref(n), C.byref(b), C.byref(b256)))
+    return n.value, int(b.value), int(b256.value)
+
+
+def guard_selftest(ctx, L: Optional[C.CDLL] = None) -> None:
+    """The guard's positive control (one legal byte written into each red zone of a buffer of its own must be reported); raises if not."""
+    L = _guard_lib(L)
+    _guard_rc(L, L.ss4k_dev_guard_selftest(getattr(ctx, "_h", ctx)))
 
 
 def _check(rc: int) -> None:
@@ -369,7 +418,8 @@ class Model:
         _check(lib().ss4k_model_out_shape(self._h, n, h, w, C.byref(oc), C.byref(oh), C.byref(ow)))
         return oc.value, oh.value, ow.value
 
-    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+    def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``out``: a caller-owned float32 device tensor of the output's shape to write into (tests place it between red zones)."""
         squeeze_f = False
         seq_shape = None
         if x.ndim == 5:  # BSVD's (N, F, C, H, W)
@@ -384,7 +434,12 @@ class Model:
         x = x.to(device=self.ctx.device, dtype=torch.float32).contiguous()
         n, _, h, w = x.shape
         oc, oh, ow = self.out_shape(n, h, w)
-        out = torch.empty((n, oc, oh, ow), dtype=torch.float32, device=x.device)
+        if out is None:
+            out = torch.empty((n, oc, oh, ow), dtype=torch.float32, device=x.device)
+        else:
+            assert out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.is_contiguous() and \
+                out.numel() == n * oc * oh * ow, f"out: expected {n * oc * oh * ow} contiguous float32 elements on {x.device}"
+            out = out.view(n, oc, oh, ow)
         with torch.cuda.device(self.ctx.device):
             _check(lib().ss4k_model_forward(self._h, x.data_ptr(), out.data_ptr(), n, h, w, _stream()))
         if seq_shape is not None:

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <memory>
+#include <mutex>
 
 namespace ss4k {
 
@@ -414,6 +415,16 @@ int ss4k_upscaler_create(ss4k_ctx* ctx, const ss4k_upscale_cfg* cfg, ss4k_model*
     up(u->u.k_gauss17, gaussian_taps_1d(17, 8.0f));
     up(u->u.k_sharp, sharpen_taps(0.00002));
     up(u->u.k_sharp_hr, sharpen_taps(0.00007));
+#ifdef SS4K_DEV
+    // guard mode (ss4k_dev_guard_poison): every job rewrites what it reads from these.  NOT transient, so never poisoned: k_gauss17 and
+    // k_sharp* (uploaded once, above); st_acc2 (its "clean after the finishing launch" invariant is the contract: acc2_clean, single()).
+    // Elsewhere: a model's weights, bias, PReLU, w16 and fs_blob (uploaded once); the context's zero_page (zeros are its content) and
+    // cv-area tables (they hold offsets: poison there would turn a stale read into a wild address, not a NaN).
+    for (DevBuf* b : {&u->u.img, &u->u.lr, &u->u.lr4, &u->u.den, &u->u.hr, &u->u.hr2, &u->u.lb, &u->u.hb, &u->u.lbb, &u->u.hbb, &u->u.st_hr,
+                      &u->u.st_lr, &u->u.st_acc})
+      b->transient = true;
+    for (auto& t : u->u.tap) t.transient = true;
+#endif
     *out = u.release();
   });
 }
@@ -677,6 +688,145 @@ int ss4k_dev_glue_routes_read(int index, char* name, size_t name_capacity, int64
     std::snprintf(name, name_capacity, "%s", nm.c_str());
   });
 }
+}  // extern "C" (reopened below the guard mode)
+
+// ---- guard mode (include/ss4k_dev.h; DevBuf in common.h) -----------------------------------------
+namespace ss4k { namespace guardmode {
+namespace {
+struct Live { size_t need, total; };
+struct Damage { bool back, freed; size_t need; long long first, last; };   // offsets relative to the payload
+std::mutex g_mu;
+bool g_on = false;
+std::map<char*, Live> g_live;          // by base pointer
+std::set<void*> g_unguarded;
+std::vector<Damage> g_sticky;          // damage found when a buffer was freed or re-grown
+
+// bytes != 0xFF in [dev, dev + n): (first, last) index or (-1, -1)
+bool scan_bytes(const char* dev, size_t n, long long* first, long long* last) {
+  std::vector<unsigned char> h(n);
+  if (hipMemcpy(h.data(), dev, n, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); *first = 0; *last = (long long)n - 1; return true; }
+  *first = *last = -1;
+  for (size_t i = 0; i < n; ++i) if (h[i] != 0xFF) { if (*first < 0) *first = (long long)i; *last = (long long)i; }
+  return *first >= 0;
+}
+void scan(char* base, const Live& e, bool freed, std::vector<Damage>& out) {
+  long long a, b;
+  if (scan_bytes(base, RZ, &a, &b)) out.push_back({false, freed, e.need, a - (long long)RZ, b - (long long)RZ});
+  const size_t back = e.total - RZ - e.need;
+  if (scan_bytes(base + RZ + e.need, back, &a, &b)) out.push_back({true, freed, e.need, (long long)e.need + a, (long long)e.need + b});
+}
+std::string describe(const Damage& d) {
+  char t[256];
+  std::snprintf(t, sizeof(t), "%s red zone of a %zu-byte buffer%s: first damaged byte at payload offset %lld, last at %lld",
+                d.back ? "back" : "front", d.need, d.freed ? " (since freed)" : "", d.first, d.last);
+  return t;
+}
+}  // namespace
+
+bool on() { std::lock_guard<std::mutex> l(g_mu); return g_on; }
+void note_unguarded(void* p, bool live) {
+  std::lock_guard<std::mutex> l(g_mu);
+  if (live) g_unguarded.insert(p); else g_unguarded.erase(p);
+}
+void* alloc(size_t need) {
+  const size_t total = (RZ + need + RZ + 255) & ~size_t(255);
+  void* base = nullptr;
+  SS4K_HIP(hipMalloc(&base, total));
+  hipError_t e = hipMemset(base, 0xFF, total);
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // the fill is complete before any stream (the non-blocking lane stream too) can use the buffer
+  if (e != hipSuccess) { (void)hipFree(base); throw Error(SS4K_EHIP, std::string("guard fill: ") + hipGetErrorString(e)); }
+  std::lock_guard<std::mutex> l(g_mu);
+  g_live[static_cast<char*>(base)] = Live{need, total};
+  return static_cast<char*>(base) + RZ;
+}
+void free_guarded(void* payload) {
+  char* base = static_cast<char*>(payload) - RZ;
+  (void)hipDeviceSynchronize();
+  std::lock_guard<std::mutex> l(g_mu);
+  auto it = g_live.find(base);
+  if (it != g_live.end()) { scan(base, it->second, true, g_sticky); g_live.erase(it); }
+  (void)hipFree(base);
+}
+}  // namespace guardmode
+
+static void poison_one(DevBuf& b, int* n, size_t* bytes, size_t* bytes256) {
+  if (!b.ptr || !b.transient) return;
+  SS4K_HIP(hipMemset(b.ptr, 0xFF, b.bytes));
+  *n += 1; *bytes += b.bytes; *bytes256 += (b.bytes + 255) & ~size_t(255);
+}
+}  // namespace ss4k
+
+extern "C" {
+int ss4k_dev_guard_enable(int on_) {
+  std::lock_guard<std::mutex> l(ss4k::guardmode::g_mu);
+  ss4k::guardmode::g_on = on_ != 0;
+  return SS4K_OK;
+}
+int ss4k_dev_guard_check(int* guarded, int* unguarded, int* damaged, char* text, size_t text_capacity) {
+  return guard([&] {
+    using namespace ss4k::guardmode;
+    SS4K_REQUIRE(guarded && unguarded && damaged, "ss4k_dev_guard_check: NULL argument");
+    SS4K_HIP(hipDeviceSynchronize());
+    std::lock_guard<std::mutex> l(g_mu);
+    std::vector<Damage> found = g_sticky;
+    for (auto& kv : g_live) scan(kv.first, kv.second, false, found);
+    *guarded = (int)g_live.size(); *unguarded = (int)g_unguarded.size(); *damaged = (int)found.size();
+    if (text && text_capacity) std::snprintf(text, text_capacity, "%s", found.empty() ? "" : describe(found[0]).c_str());
+  });
+}
+int ss4k_dev_guard_poison(ss4k_ctx* c, ss4k_model* m, ss4k_upscaler* up, int* buffers, size_t* bytes, size_t* bytes_256) {
+  return guard([&] {
+    SS4K_REQUIRE(buffers && bytes && bytes_256, "ss4k_dev_guard_poison: NULL argument");
+    *buffers = 0; *bytes = 0; *bytes_256 = 0;
+    SS4K_HIP(hipDeviceSynchronize());
+    if (c) for (auto& kv : c->scratch) poison_one(kv.second, buffers, bytes, bytes_256);
+    if (m) for (auto& b : m->m.acts) poison_one(b, buffers, bytes, bytes_256);
+    if (up) {
+      Upscaler& u = up->u;
+      for (DevBuf* b : {&u.k_gauss17, &u.k_sharp, &u.k_sharp_hr, &u.img, &u.lr, &u.lr4, &u.den, &u.hr, &u.hr2, &u.lb, &u.hb, &u.lbb, &u.hbb,
+                        &u.st_hr, &u.st_lr, &u.st_acc, &u.st_acc2})
+        poison_one(*b, buffers, bytes, bytes_256);
+      for (auto& t : u.tap) poison_one(t, buffers, bytes, bytes_256);
+    }
+    SS4K_HIP(hipDeviceSynchronize());
+  });
+}
+int ss4k_dev_guard_selftest(ss4k_ctx* c) {
+  return guard([&] {
+    using namespace ss4k::guardmode;
+    SS4K_REQUIRE(c, "ss4k_dev_guard_selftest: NULL ctx");
+    SS4K_HIP(hipSetDevice(c->device));
+    int g0 = 0, u0 = 0, d0 = 0, g1 = 0, u1 = 0, d1 = 0;
+    char text[256];
+    SS4K_REQUIRE(ss4k_dev_guard_check(&g0, &u0, &d0, nullptr, 0) == SS4K_OK, "guard selftest: the check itself failed");
+    SS4K_REQUIRE(d0 == 0, "guard selftest: damage is already on record (run the selftest first)");
+    const size_t need = 1000;   // not a multiple of 256: the back zone must start at the requested size
+    bool was_on;
+    { std::lock_guard<std::mutex> l(g_mu); was_on = g_on; g_on = true; }
+    DevBuf b;
+    try { b.ensure(need); } catch (...) { std::lock_guard<std::mutex> l(g_mu); g_on = was_on; throw; }
+    { std::lock_guard<std::mutex> l(g_mu); g_on = was_on; }
+    SS4K_REQUIRE(b.guarded && b.bytes == need, "guard selftest: the buffer was not allocated in guard mode");
+    SS4K_HIP(hipMemset(b.as<char>() - 1, 0, 1));        // last byte of the front red zone
+    SS4K_HIP(hipMemset(b.as<char>() + need, 0, 1));     // first byte of the back red zone
+    const int rc = ss4k_dev_guard_check(&g1, &u1, &d1, text, sizeof(text));
+    std::vector<Damage> mine;
+    { std::lock_guard<std::mutex> l(g_mu); scan(b.as<char>() - RZ, g_live.at(b.as<char>() - RZ), false, mine); }
+    b.release();
+    size_t sticky;
+    { std::lock_guard<std::mutex> l(g_mu); sticky = g_sticky.size(); g_sticky.clear(); }
+    SS4K_REQUIRE(rc == SS4K_OK, "guard selftest: the check failed after the two writes");
+    SS4K_REQUIRE(g1 == g0 + 1 && u1 == u0 && d1 == 2, "guard selftest: the check did not report exactly the two damaged zones");
+    SS4K_REQUIRE(std::string(text).find("front") != std::string::npos && std::string(text).find("offset -1,") != std::string::npos,
+                 "guard selftest: the text does not name the front zone's byte at offset -1");
+    SS4K_REQUIRE(mine.size() == 2 && !mine[0].back && mine[0].first == -1 && mine[0].last == -1 && mine[1].back &&
+                     mine[1].first == (long long)need && mine[1].last == (long long)need && mine[0].need == need,
+                 "guard selftest: wrong zones or offsets");
+    SS4K_REQUIRE(sticky == 2, "guard selftest: the release did not keep the two damaged zones on record");
+  });
+}
+}  // extern "C"
+extern "C" {
 #endif  // SS4K_DEV
 
 // ---- profiling hooks --------------------------------------------------------------------------

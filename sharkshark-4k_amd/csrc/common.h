@@ -39,6 +39,7 @@ struct Error : std::runtime_error {
     if (!(cond)) throw ::ss4k::Error(SS4K_EINVAL, std::string(msg));   \
   } while (0)
 
+#ifndef SS4K_DEV
 // A device allocation owned by the object that holds it (a context's scratch, a model's layers and activations) and freed with it;
 // movable, never copied; grows on demand, never shrinks (no hipMalloc in steady state: shapes repeat frame after frame).
 struct DevBuf {
@@ -63,6 +64,54 @@ struct DevBuf {
   void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; bytes = 0; }
   template <typename T> T* as() const { return reinterpret_cast<T*>(ptr); }
 };
+#else
+// ---- dev library: the same DevBuf with a process-wide guard mode (ss4k_dev_guard_enable, include/ss4k_dev.h), off by default.
+// In guard mode an allocation is RZ + need + RZ bytes (rounded up as hipMalloc needs), filled with 0xFF - NaN in fp16 / fp32 / fp64 -
+// before ptr = base + RZ is handed out.  The back red zone starts at the REQUESTED need, not at the 256-rounded size, and `bytes` is
+// then `need`: a later, larger request inside what used to be slack re-allocates instead of sharing the red zone.  A registry keyed by
+// the base pointer (DevBuf is movable) holds every live guarded allocation; re-growth and release() scan the red zones first and keep
+// any damage in a sticky list, so the evidence survives the free.  Buffers allocated while guard mode was off count as "unguarded".
+namespace guardmode {
+constexpr size_t RZ = 64 * 1024;   // twice one 16 x 32-pixel fp32 tile of one plane (16 * 32 * 64 B), the largest unit a conv launch stores; a multiple of 256
+bool on();
+void* alloc(size_t need);            // registered and poisoned; returns the payload pointer
+void free_guarded(void* payload);    // synchronises, scans both red zones into the sticky list, frees
+void note_unguarded(void* p, bool live);
+}  // namespace guardmode
+struct DevBuf {
+  void* ptr = nullptr;
+  size_t bytes = 0;
+  bool guarded = false;
+  // the one fact a buffer carries for ss4k_dev_guard_poison: no later call is entitled to read what this call left in it
+  bool transient = false;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : ptr(o.ptr), bytes(o.bytes), guarded(o.guarded), transient(o.transient) { o.ptr = nullptr; o.bytes = 0; o.guarded = false; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { release(); ptr = o.ptr; bytes = o.bytes; guarded = o.guarded; transient = o.transient; o.ptr = nullptr; o.bytes = 0; o.guarded = false; }
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  void ensure(size_t need) {
+    if (need <= bytes) return;
+    release();
+    if (guardmode::on()) { ptr = guardmode::alloc(need); bytes = need; guarded = true; return; }
+    size_t want = (need + 255) & ~size_t(255);
+    SS4K_HIP(hipMalloc(&ptr, want));
+    bytes = want;
+    guardmode::note_unguarded(ptr, true);
+  }
+  void release() {
+    if (ptr) {
+      if (guarded) guardmode::free_guarded(ptr);
+      else { guardmode::note_unguarded(ptr, false); (void)hipFree(ptr); }
+    }
+    ptr = nullptr; bytes = 0; guarded = false;
+  }
+  template <typename T> T* as() const { return reinterpret_cast<T*>(ptr); }
+};
+#endif
 
 struct ProfEvent { hipEvent_t a, b; double flops; int kind; const char* family; };   // kind: PROF_* below; family: the launcher's static name for the kernel build it chose (or null)
 struct ProfFamily { int64_t launches = 0; double ms = 0, flops = 0; };
@@ -151,6 +200,9 @@ struct ss4k_ctx {
   ss4k::DevBuf& buf(const std::string& name, size_t bytes) {
     auto& b = scratch[name];
     b.ensure(bytes);
+#ifdef SS4K_DEV
+    b.transient = true;   // named scratch is rebuilt by every call that uses it (zero_page and the cv-area tables do not come through here)
+#endif
     return b;
   }
 };

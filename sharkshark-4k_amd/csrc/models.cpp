@@ -624,6 +624,9 @@ Tens Model::act(int idx, size_t pixels, int channels) {
     return Tens{nullptr, pixels * (size_t)rec(), 0};
   }
   acts[idx].ensure(need);
+#ifdef SS4K_DEV
+  acts[idx].transient = true;   // every forward rewrites what it reads from its activations
+#endif
   return Tens{acts[idx].as<char>(), pixels * (size_t)rec(), 0};
 }
 
@@ -697,6 +700,9 @@ void Model::forward_impl(const float* in, float* out, int n, int h, int w, hipSt
     if (acts.size() < 2) acts.resize(2);
     if (plan_only) { plan_bytes.assign(2, px * 12 * 4); return; }
     acts[0].ensure(px * 12 * 4); acts[1].ensure(px * 12 * 4);
+#ifdef SS4K_DEV
+    acts[0].transient = acts[1].transient = true;
+#endif
     const bool half_out = out_half; out_half = false;
     const bool u8_in = in_u8; in_u8 = false;
     fsrcnn_forward(ctx, fsw, desc.scale, in, out, n, h, w, acts[0].as<float>(), acts[1].as<float>(),

@@ -217,3 +217,48 @@ def u8_tau(yard_v, v64, k_max, u):
     """tau in LSB of a uint8 case: 255 * k_max * max(max|yardstick - reference|, u * max|reference|) on the float values."""
     y, v = _f64(yard_v), _f64(v64)
     return 255.0 * k_max * max(float(np.abs(y - v).max()), u * float(np.abs(v).max()))
+
+
+class ArenaGuard:
+    """Checker of one ``guarded()`` tensor: both pads still hold the fill and, for an input, the payload is bit-identical to what was
+    put in.  ``check()`` raises AssertionError naming the first damaged byte's offset relative to the payload."""
+
+    def __init__(self, arena, pad, nbytes, fill, snapshot=None):
+        self.arena, self.pad, self.nbytes, self.fill, self.snapshot = arena, pad, nbytes, fill, snapshot
+
+    def findings(self):
+        """[(what, first offset, last offset)] relative to the payload; empty when all is well."""
+        a = self.arena.detach().cpu().numpy()
+        out = []
+        for name, lo, hi in (("front pad", 0, self.pad), ("back pad", self.pad + self.nbytes, a.size)):
+            bad = np.flatnonzero(a[lo:hi] != self.fill)
+            if bad.size:
+                out.append((name, int(bad[0]) + lo - self.pad, int(bad[-1]) + lo - self.pad))
+        if self.snapshot is not None:
+            bad = np.flatnonzero(a[self.pad:self.pad + self.nbytes] != self.snapshot)
+            if bad.size:
+                out.append(("input payload", int(bad[0]), int(bad[-1])))
+        return out
+
+    def __call__(self, what=""):
+        f = self.findings()
+        assert not f, f"{what}: " + "; ".join(f"{n} changed at payload offset {a} (last: {b})" for n, a, b in f)
+
+    check = __call__
+
+
+def guarded(shape, dtype, fill=0xFF, pad=65536, device="cpu", data=None):
+    """A tensor of ``shape`` / ``dtype`` in the middle of one uint8 arena of ``pad + nbytes + pad`` bytes, all ``fill`` (0xFF reads as
+    NaN in fp16 / fp32 / fp64).  Returns (the typed view, its ArenaGuard).  With ``data`` the view is an INPUT: it receives ``data`` and
+    the checker also holds the payload to those bytes."""
+    shape = tuple(int(s) for s in shape)
+    item = torch.empty((), dtype=dtype).element_size()
+    nbytes = item * int(np.prod(shape, dtype=np.int64))
+    assert pad % 256 == 0, "the pad keeps the payload's alignment"
+    arena = torch.full((pad + nbytes + pad,), fill, dtype=torch.uint8, device=device)
+    view = arena[pad:pad + nbytes].view(dtype).view(shape)
+    snapshot = None
+    if data is not None:
+        view.copy_(data.to(dtype).reshape(shape))
+        snapshot = arena[pad:pad + nbytes].cpu().numpy().copy()
+    return view, ArenaGuard(arena, pad, nbytes, fill, snapshot)

@@ -13,6 +13,10 @@ Criteria (the bars are tests/test_gpu_error_budget.py's, imported):
 * uint8 outputs: ``assert_u8_within`` - every byte inside the interval its float64 value allows at tau = 255 * K32_MAX *
   max(max|yard - ref64|, u * peak); no allowance by count.
 * layout converters (pack_input, temporal_shift, u8 <-> f32): exact.
+
+Where the kernels read and write is checked with the values: every input, output, accumulator and statistics tensor of a runner sits in
+an arena of tests/helpers.py::guarded (``Dev.put`` / ``Dev.new``: 64 KiB of 0xFF on either side, outputs born 0xFF = NaN), and
+``Dev.routed`` ends by checking every arena of the call - pads intact, inputs bit-identical unless the op is in place by contract.
 """
 import ctypes as C
 import os
@@ -26,7 +30,7 @@ from sharkshark4k_amd import _capi, build as B
 from oracle import glue_ref as G
 from oracle import precision as P
 from tests import glue_cases as GC
-from tests.helpers import assert_error_budget, assert_u8_within, error_budget, record_measured, u8_tau
+from tests.helpers import assert_error_budget, assert_u8_within, error_budget, guarded, record_measured, u8_tau
 from tests.test_gpu_error_budget import K16_MAX, K16_SLICE, K32_MAX, K32_SLICE
 
 pytestmark = pytest.mark.gpu
@@ -81,12 +85,14 @@ class Dev:
         assert os.path.exists(B.LIB_DEV), "libss4k_hip_dev.so was not built (__graft_entry__.build())"
         assert torch.cuda.is_available(), "gpu-marked test started without a GPU"
         self.L = _capi.load(B.LIB_DEV)
+        self.arenas, self.kept = [], []
         self.h = C.c_void_p()
         assert self.L.ss4k_ctx_create(0, C.byref(self.h)) == 0, self.L.ss4k_last_error()
         taps = (C.c_float * 17)()
         self.ok(self.L.ss4k_dev_gauss17_taps(taps))
         self.g17_host = np.array(list(taps), dtype=np.float32)
-        self.g17 = torch.from_numpy(self.g17_host).cuda()
+        self.g17 = self.put(torch.from_numpy(self.g17_host))
+        self.kept, self.arenas = self.arenas, []      # lives as long as the context: checked by every routed() call
 
     def close(self):
         self.L.ss4k_ctx_destroy(self.h)
@@ -99,16 +105,41 @@ class Dev:
         a = [x.data_ptr() if isinstance(x, torch.Tensor) else x for x in args]
         self.ok(getattr(self.L, name)(self.h, *a, int(torch.cuda.current_stream().cuda_stream)))
 
+    def put(self, t, inplace=False):
+        """A CPU tensor on the device between two red zones.  An input: ``check_arenas`` holds its payload to these bytes, unless the
+        op writes it by contract (``inplace``)."""
+        v, chk = guarded(t.shape, t.dtype, device="cuda", data=t)
+        if inplace:
+            chk.snapshot = None
+        self.arenas.append(chk)
+        return v
+
+    def new(self, shape, dtype=torch.float32, fill=None):
+        """A device tensor between two red zones, born 0xFF (NaN in every float format), or holding the value ``fill``."""
+        v, chk = guarded(shape, dtype, device="cuda")
+        if fill is not None:
+            v.fill_(fill)
+        self.arenas.append(chk)
+        return v
+
+    def check_arenas(self, what=""):
+        """Every arena made since the last check (and the context's own): pads intact, inputs unchanged."""
+        torch.cuda.synchronize()
+        arenas, self.arenas = self.arenas, []
+        for i, chk in enumerate(arenas + self.kept):
+            chk(f"{what} arena {i} of {len(arenas)} ({chk.nbytes} bytes)")
+
     def routed(self, fn):
-        """fn() -> (its result, {route: launches})."""
+        """fn() -> (its result, {route: launches}); ends by checking every arena the call (and the test before it) made."""
         self.ok(self.L.ss4k_dev_glue_routes_reset())
         out = fn()
         torch.cuda.synchronize()
+        self.check_arenas("routed():")
         return out, _capi.glue_routes(self.L)
 
     def acc(self, planes):
         """Statistics accumulators holding garbage: the launchers that own the memset must do it."""
-        return torch.full((32 * planes * 2,), 7.25, dtype=F64, device="cuda")
+        return self.new((32 * planes * 2,), F64, fill=7.25)
 
 
 @pytest.fixture(scope="module")
@@ -127,21 +158,21 @@ def run_area(dev, c, d):
     x = d["x"]
     n, ch, h, w = x.shape
     oh, ow = c.a["size"]
-    out = torch.full((n, ch, oh, ow), float("nan"), device="cuda")
+    out = dev.new((n, ch, oh, ow))
     if c.a["norm"] is None:
-        xin = x.cuda()
+        xin = dev.put(x)
         dev.ok(dev.L.ss4k_op_area_resize(dev.h, xin.data_ptr(), out.data_ptr(), n * ch, h, w, oh, ow, 0))
     else:
-        xin = x.cuda().to(_dt(c.a["norm"]))
-        dev.call("ss4k_dev_op_area_normalized", xin, int(c.a["norm"]), out, n * ch, h, w, oh, ow, d["st_hr"].cuda(), d["st_lr"].cuda())
+        xin = dev.put(x.to(_dt(c.a["norm"])))
+        dev.call("ss4k_dev_op_area_normalized", xin, int(c.a["norm"]), out, n * ch, h, w, oh, ow, dev.put(d["st_hr"]), dev.put(d["st_lr"]))
     return out.cpu()
 
 
 def run_bilinear(dev, c, d):
     n, ch, h, w = d["x"].shape
     oh, ow = c.a["size"]
-    out = d["out0"].cuda().clone() if c.a["sub"] else torch.full((n, ch, oh, ow), float("nan"), device="cuda")
-    dev.call("ss4k_dev_op_bilinear", d["x"].cuda(), out, n * ch, h, w, oh, ow, int(c.a["sub"]), int(c.a["clamp"]))
+    out = dev.put(d["out0"], inplace=True) if c.a["sub"] else dev.new((n, ch, oh, ow))
+    dev.call("ss4k_dev_op_bilinear", dev.put(d["x"]), out, n * ch, h, w, oh, ow, int(c.a["sub"]), int(c.a["clamp"]))
     return out.cpu()
 
 
@@ -149,21 +180,21 @@ def run_bicubic(dev, c, d):
     n, ch, h, w = d["x"].shape
     oh, ow = c.a["size"]
     if c.op == "bicubic":
-        out = torch.full((n, ch, oh, ow), float("nan"), device="cuda")
-        dev.call("ss4k_dev_op_bicubic", d["x"].cuda(), out, n * ch, h, w, oh, ow, int(c.a["clamp"]))
+        out = dev.new((n, ch, oh, ow))
+        dev.call("ss4k_dev_op_bicubic", dev.put(d["x"]), out, n * ch, h, w, oh, ow, int(c.a["clamp"]))
         return out.cpu()
-    out = torch.full((n, oh, ow, ch), 77, dtype=torch.uint8, device="cuda")
-    dev.call("ss4k_dev_op_bicubic_u8", d["x"].cuda().to(_dt(c.a["half"])), int(c.a["half"]), out, n, ch, h, w, oh, ow)
+    out = dev.new((n, oh, ow, ch), torch.uint8, fill=77)
+    dev.call("ss4k_dev_op_bicubic_u8", dev.put(d["x"].to(_dt(c.a["half"]))), int(c.a["half"]), out, n, ch, h, w, oh, ow)
     return out.cpu()
 
 
 def run_tail(dev, c, d):
     a = c.a
     n, ch, h, w = a["shape"]
-    hr = d["x"].cuda().to(_dt(a["half"]))
-    out = torch.full((n, h, w, ch), 77, dtype=torch.uint8, device="cuda") if a["u8"] else None
-    dev.call("ss4k_dev_op_tail_fused", hr, int(a["half"]), out, d["diff"].cuda() if a["diff"] else None, n, ch, h, w, a["dmap"][0], a["dmap"][1],
-             d["st_hr"].cuda() if a["norm"] else None, d["st_lr"].cuda() if a["norm"] else None)
+    hr = dev.put(d["x"].to(_dt(a["half"])), inplace=not a["u8"])     # the float form clamps the HR tensor in place; the uint8 form only reads it
+    out = dev.new((n, h, w, ch), torch.uint8, fill=77) if a["u8"] else None
+    dev.call("ss4k_dev_op_tail_fused", hr, int(a["half"]), out, dev.put(d["diff"]) if a["diff"] else None, n, ch, h, w, a["dmap"][0], a["dmap"][1],
+             dev.put(d["st_hr"]) if a["norm"] else None, dev.put(d["st_lr"]) if a["norm"] else None)
     if a["u8"]:
         assert torch.equal(hr.cpu().float(), d["x"]), "the uint8 form must leave the HR tensor alone"
         return out.cpu()
@@ -172,16 +203,16 @@ def run_tail(dev, c, d):
 
 def run_blur(dev, c, d):
     n, ch, h, w = d["x"].shape
-    x = d["x"].cuda()
-    out = torch.full_like(x, float("nan"))
+    x = dev.put(d["x"])
+    out = dev.new(x.shape)
     if c.op == "gauss17":
-        diff, tmp = torch.empty_like(x), torch.empty_like(x)
-        dev.call("ss4k_dev_op_sub", x, d["y"].cuda(), diff, x.numel())
+        diff, tmp = dev.new(x.shape), dev.new(x.shape)
+        dev.call("ss4k_dev_op_sub", x, dev.put(d["y"]), diff, x.numel())
         dev.call("ss4k_dev_op_gauss17_reflect", diff, tmp, out, dev.g17, n * ch, h, w)
         return out.cpu()
-    taps = GC.depthwise_taps(c).cuda().contiguous()
+    taps = dev.put(GC.depthwise_taps(c).contiguous())
     dev.call("ss4k_dev_op_depthwise_reflect", x, out, taps, n * ch, h, w, c.a["k"], int(c.a["clamp"]),
-             d["src"].cuda() if c.a["blend"] else None, C.c_float(0.8), C.c_float(1 - 0.8))
+             dev.put(d["src"]) if c.a["blend"] else None, C.c_float(0.8), C.c_float(1 - 0.8))
     return out.cpu()
 
 
@@ -189,13 +220,13 @@ def run_ps(dev, c, d):
     a = c.a
     n, h, w = a["nhw"]
     r = a["r"]
-    src = torch.from_numpy(G.nchw_to_planes(d["y"].numpy())).cuda().to(_dt(a["t"] == "half")).contiguous()
-    out = torch.full((n, 3, h * r, w * r), float("nan"), dtype=_dt(a["ht"] == "half"), device="cuda")
+    src = dev.put(torch.from_numpy(G.nchw_to_planes(d["y"].numpy())).to(_dt(a["t"] == "half")).contiguous())
+    out = dev.new((n, 3, h * r, w * r), _dt(a["ht"] == "half"))
     acc = dev.acc(3 * n) if a["stats"] else None
-    dev.call("ss4k_dev_op_ps_nchw_addbase", src, int(a["t"] == "half"), out, int(a["ht"] == "half"), d["base"].cuda(), n, h, w, r, 3, acc)
+    dev.call("ss4k_dev_op_ps_nchw_addbase", src, int(a["t"] == "half"), out, int(a["ht"] == "half"), dev.put(d["base"]), n, h, w, r, 3, acc)
     st = None
     if a["stats"]:
-        st = torch.full((3 * n, 2), float("nan"), device="cuda")
+        st = dev.new((3 * n, 2))
         dev.call("ss4k_dev_op_plane_stats_finish", acc, st, 3 * n, h * r * w * r)
         st = st.cpu()
     return out.cpu().float(), st
@@ -204,11 +235,11 @@ def run_ps(dev, c, d):
 def run_stats(dev, c, d):
     a = c.a
     if c.op == "stats_u8":
-        st = torch.full((3 * a["n"], 2), float("nan"), device="cuda")
-        dev.call("ss4k_dev_op_plane_stats_u8nhwc", dev.acc(3 * a["n"]), d["frames"].cuda(), st, a["n"], a["hw"])
+        st = dev.new((3 * a["n"], 2))
+        dev.call("ss4k_dev_op_plane_stats_u8nhwc", dev.acc(3 * a["n"]), dev.put(d["frames"]), st, a["n"], a["hw"])
         return st.cpu()
-    st = torch.full((a["planes"], 2), float("nan"), device="cuda")
-    dev.call("ss4k_dev_op_plane_stats", dev.acc(a["planes"]), d["x"].cuda().to(_dt(a["half"])), int(a["half"]), st, a["planes"], a["hw"])
+    st = dev.new((a["planes"], 2))
+    dev.call("ss4k_dev_op_plane_stats", dev.acc(a["planes"]), dev.put(d["x"].to(_dt(a["half"]))), int(a["half"]), st, a["planes"], a["hw"])
     return st.cpu()
 
 
@@ -284,27 +315,27 @@ def test_normalize_clamp_sub_and_u8_converters(dev):
         for shape in ((2, 3, 23, 37), (1, 1, 1, 300000)):     # the second: more elements than the 1024 x 256 grid of k_normalize
             x = GC.plane(kind, shape, 11)
             st_hr, st_lr = GC.stats_pair(shape[0] * shape[1], 12)
-            xg = x.cuda()
-            _, routes = dev.routed(lambda: dev.call("ss4k_dev_op_normalize", xg, st_hr.cuda(), st_lr.cuda(), shape[0] * shape[1], shape[2] * shape[3]))
+            xg = dev.put(x, inplace=True)
+            _, routes = dev.routed(lambda: dev.call("ss4k_dev_op_normalize", xg, dev.put(st_hr), dev.put(st_lr), shape[0] * shape[1], shape[2] * shape[3]))
             assert routes == {"glue::normalize": 1}
             sh, sl = st_hr.reshape(shape[0], shape[1], 2), st_lr.reshape(shape[0], shape[1], 2)
             m = _budget(xg.cpu(), G.normalize(x, sh, sl, F64), G.normalize(x, sh, sl, torch.float32), f"normalize {shape} [{kind}]")
             record_measured(f"glue_budget_normalize_{shape[2]}x{shape[3]}_{kind}", routes=sorted(routes), **m)
         x, y = GC.plane(kind, (2, 3, 23, 37), 13), GC.plane(kind, (2, 3, 23, 37), 14)
-        out = torch.empty_like(x).cuda()
-        _, routes = dev.routed(lambda: dev.call("ss4k_dev_op_sub", x.cuda(), y.cuda(), out, x.numel()))
+        out = dev.new(x.shape)
+        _, routes = dev.routed(lambda: dev.call("ss4k_dev_op_sub", dev.put(x), dev.put(y), out, x.numel()))
         assert routes == {"glue::sub": 1} and torch.equal(out.cpu(), x - y)          # one fp32 subtraction: exact
-        xg = x.cuda()
+        xg = dev.put(x, inplace=True)
         _, routes = dev.routed(lambda: dev.call("ss4k_dev_op_clamp01", xg, x.numel()))
         assert routes == {"glue::clamp01": 1} and torch.equal(xg.cpu(), torch.clamp(x, 0, 1))
         assert float(xg.min()) == 0.0 and float(xg.max()) == 1.0, "the input must make both clamps act"
         # uint8 NHWC <-> fp32 NCHW through the public ops of the dev build
         u8 = torch.from_numpy(np.random.default_rng(3).integers(0, 256, (2, 20, 30, 3), dtype=np.uint8))
-        f = torch.empty((2, 3, 20, 30), device="cuda")
-        back = torch.empty((2, 20, 30, 3), dtype=torch.uint8, device="cuda")
+        f = dev.new((2, 3, 20, 30))
+        back = dev.new((2, 20, 30, 3), torch.uint8)
         v = GC.plane(kind, (2, 3, 20, 30), 15)
-        b2 = torch.empty((2, 20, 30, 3), dtype=torch.uint8, device="cuda")
-        u8g, vg = u8.cuda(), v.cuda()
+        b2 = dev.new((2, 20, 30, 3), torch.uint8)
+        u8g, vg = dev.put(u8), dev.put(v)
 
         def conv():
             dev.ok(dev.L.ss4k_op_u8nhwc_to_f32nchw(dev.h, u8g.data_ptr(), f.data_ptr(), 2, 20, 30, 3, 0))
@@ -327,8 +358,8 @@ def test_pack_input_exact(dev, ch, r, half):
     x = GC.plane("noise", (n, ch, h, w), 20 + r)
     creal = ch * r * r
     npl = (creal + 15) // 16
-    out = torch.full((npl, n, h // r, w // r, 16), float("nan"), dtype=_dt(half), device="cuda")
-    _, routes = dev.routed(lambda: dev.call("ss4k_dev_op_pack_input", x.cuda(), out, int(half), n, ch, h, w, r, npl))
+    out = dev.new((npl, n, h // r, w // r, 16), _dt(half))
+    _, routes = dev.routed(lambda: dev.call("ss4k_dev_op_pack_input", dev.put(x), out, int(half), n, ch, h, w, r, npl))
     name = f"glue::pack_input<{'half' if half else 'float'},{r}>"
     assert name in OTHER_DECLARED["pack_input"] and routes == {name: 1}
     want = torch.nn.functional.pixel_unshuffle(x, r) if r > 1 else x
@@ -346,8 +377,8 @@ def test_temporal_shift_exact(dev, half, frames):
     spr = 2 if half else 4
     x = torch.from_numpy(np.random.default_rng(frames).random((nplanes, frames, px, 16)).astype(np.float32) + 0.5)
     x = G.round16(x) if half else x
-    out = torch.full(x.shape, float("nan"), dtype=_dt(half), device="cuda")
-    _, routes = dev.routed(lambda: dev.call("ss4k_dev_op_temporal_shift", x.cuda().to(_dt(half)), out, nplanes, frames, px, spr, 16, fold))
+    out = dev.new(x.shape, _dt(half))
+    _, routes = dev.routed(lambda: dev.call("ss4k_dev_op_temporal_shift", dev.put(x.to(_dt(half))), out, nplanes, frames, px, spr, 16, fold))
     assert routes == {"glue::temporal_shift": 1}
     want = x.clone()
     want[0, :, :, :fold] = 0
@@ -365,14 +396,15 @@ def test_stats_constant_plane_has_zero_std_and_normalises_without_nan(dev):
     whatever the order.  0.3f in 16 values likewise (48-bit squares, 4 more bits).  After normalisation every element is mean_lr."""
     for val, hw in ((0.75, 12288), (0.75, 12290), (float(np.float32(0.3)), 16)):
         x = torch.full((1, 3, 1, hw), val)
-        st = torch.full((3, 2), float("nan"), device="cuda")
-        dev.call("ss4k_dev_op_plane_stats", dev.acc(3), x.cuda(), 0, st, 3, hw)
+        st = dev.new((3, 2))
+        dev.call("ss4k_dev_op_plane_stats", dev.acc(3), dev.put(x), 0, st, 3, hw)
         got = st.cpu()
         assert torch.equal(got[:, 0], torch.full((3,), val)) and torch.equal(got[:, 1], torch.zeros(3)), got
         st_lr = torch.tensor([[0.25, 0.5]] * 3)
-        xg = x.cuda()
-        dev.call("ss4k_dev_op_normalize", xg, st, st_lr.cuda(), 3, hw)
+        xg = dev.put(x, inplace=True)
+        dev.call("ss4k_dev_op_normalize", xg, st, dev.put(st_lr), 3, hw)
         assert torch.equal(xg.cpu(), torch.full_like(x, 0.25))
+        dev.check_arenas(f"constant plane {val} x {hw}:")
 
 
 def test_stats_small_variance_plane(dev):
@@ -380,8 +412,9 @@ def test_stats_small_variance_plane(dev):
     for hw in (4096, 4099, 524292):
         g = torch.Generator().manual_seed(hw)
         x = (0.5 + 1e-4 * torch.randn(1, 2, 1, hw, generator=g, dtype=F64)).float()
-        st = torch.full((2, 2), float("nan"), device="cuda")
-        dev.call("ss4k_dev_op_plane_stats", dev.acc(2), x.cuda(), 0, st, 2, hw)
+        st = dev.new((2, 2))
+        dev.call("ss4k_dev_op_plane_stats", dev.acc(2), dev.put(x), 0, st, 2, hw)
+        dev.check_arenas(f"small variance hw {hw}:")
         ref = G.plane_stats(x, F64).reshape(-1, 2)
         assert 0.9e-4 < float(ref[0, 1]) < 1.1e-4
         record_measured(f"glue_budget_stats_small_variance_hw{hw}", stats_rel_u=assert_stats(st.cpu(), ref, f"small variance hw {hw}"))
@@ -392,21 +425,24 @@ def test_stats_two_tensor_finish(dev, rezero):
     """The per-frame path's trio: uint8 frames into planes [0, P), the network output into [P, 2 P), one finishing launch - with
     hw_a != hw_b.  With rezero a second job runs on the same accumulators WITHOUT a memset; without it the sums must still be there."""
     n, P_ = 2, 6
-    acc = torch.zeros(32 * 2 * P_ * 2, dtype=F64, device="cuda")
+    acc = dev.new((32 * 2 * P_ * 2,), F64, fill=0.0)
+    acc_guard = dev.arenas.pop()        # lives across both jobs: checked after each, below
     seen = set()
     for job, (hw_a, hw_b, half) in enumerate((((4096, 4 * 4096, False)), ((4099, 4 * 4099 + 2, True)))):
         frames = torch.from_numpy(np.random.default_rng(job).integers(0, 256, (n, hw_a, 1, 3), dtype=np.uint8))
         hr = GC.plane("noise", (1, P_, 1, hw_b), 30 + job, 0.1, 1.1)
         hr = G.round16(hr) if half else hr
-        sa, sb = torch.full((P_, 2), float("nan"), device="cuda"), torch.full((P_, 2), float("nan"), device="cuda")
+        sa, sb = dev.new((P_, 2)), dev.new((P_, 2))
+        fg, hg = dev.put(frames), dev.put(hr.to(_dt(half)))
         if job and not rezero:
             acc.zero_()
 
         def trio():
-            dev.call("ss4k_dev_op_plane_stats_u8nhwc_partial", acc, frames.cuda(), n, hw_a, 2 * P_, 0)
-            dev.call("ss4k_dev_op_plane_stats_partial", acc, hr.cuda().to(_dt(half)), int(half), P_, hw_b, 2 * P_, P_)
+            dev.call("ss4k_dev_op_plane_stats_u8nhwc_partial", acc, fg, n, hw_a, 2 * P_, 0)
+            dev.call("ss4k_dev_op_plane_stats_partial", acc, hg, int(half), P_, hw_b, 2 * P_, P_)
             dev.call("ss4k_dev_op_plane_stats_finish2", acc, sa, sb, P_, hw_a, hw_b, int(rezero))
         _, routes = dev.routed(trio)
+        acc_guard(f"job {job} accumulators")
         seen |= set(routes)
         ref_a = G.plane_stats(frames.permute(0, 3, 1, 2).float() / 255.0, F64).reshape(-1, 2)
         ref_b = G.plane_stats(hr, F64).reshape(-1, 2)
@@ -426,9 +462,9 @@ def test_bicubic_u8_two_kernels_give_identical_bytes(dev, half):
     for kind in GC.KINDS:
         for (h, w) in ((8, 8), (12, 16), (20, 264), (34, 1032)):
             x = GC.plane(kind, (2, 3, h, w), h + w)
-            xg = x.cuda().to(_dt(half))
-            a = torch.empty((2, h // 2, w // 2, 3), dtype=torch.uint8, device="cuda")
-            b = torch.empty((6, h // 2, w // 2, 1), dtype=torch.uint8, device="cuda")
+            xg = dev.put(x.to(_dt(half)))
+            a = dev.new((2, h // 2, w // 2, 3), torch.uint8)
+            b = dev.new((6, h // 2, w // 2, 1), torch.uint8)
             _, routes = dev.routed(lambda: (dev.call("ss4k_dev_op_bicubic_u8", xg, int(half), a, 2, 3, h, w, h // 2, w // 2),
                                             dev.call("ss4k_dev_op_bicubic_u8", xg, int(half), b, 6, 1, h, w, h // 2, w // 2)))
             t = "half" if half else "float"
