@@ -78,6 +78,9 @@ typedef struct ss4k_model_desc {
                           pin a route without environment variables */
   int32_t reserved[3];
 } ss4k_model_desc;
+/* Every channel width of a description (num_feat, num_grow_ch, bsvd_chns, bsvd_mid_ch) is positive and at most SS4K_DESC_MAX_WIDTH,
+ * num_block at most SS4K_DESC_MAX_BLOCKS; anything else is refused with SS4K_EINVAL and a message that names the field. */
+enum { SS4K_DESC_MAX_WIDTH = 512, SS4K_DESC_MAX_BLOCKS = 64 };
 
 enum {
   /* --- what a deployment may want to choose ---------------------------------------------------------------------------------- */

@@ -76,5 +76,54 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
     return lib
 
 
+# ---- host check (tests/hostcheck, tests/test_hostcheck_cpu.py): the real models.cpp and pack.cpp, host side only, under ASan + UBSan,
+# linked against HIP stand-ins and launch auditors.  The program links no HIP runtime and no Python.  -DSS4K_DEV: DevBuf then allocates
+# through guardmode::alloc(need), which the stand-ins implement at the requested size (tests/hostcheck/standins.cpp).
+HOSTCHECK_DIR = os.path.join(HERE, "..", "tests", "hostcheck")
+HOSTCHECK = os.path.join(HOSTCHECK_DIR, "build", "hostcheck")
+HOSTCHECK_SOURCES = [os.path.join(CSRC, "models.cpp"), os.path.join(CSRC, "pack.cpp")] + \
+    [os.path.join(HOSTCHECK_DIR, f) for f in ("standins.cpp", "auditors.cpp", "main.cpp")]
+HOSTCHECK_FLAGS = ["-O2", "-g", "-std=c++17", "-x", "hip", "--offload-arch=gfx950", "--offload-host-only", "-DSS4K_DEV",
+                   "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-Wall",
+                   "-Wno-unused-function", "-Wno-unused-variable"]
+
+
+def build_hostcheck(force: bool = False, verbose: bool = False) -> str:
+    hipcc = _hipcc()
+    objdir = os.path.join(HOSTCHECK_DIR, "build")
+    os.makedirs(objdir, exist_ok=True)
+    jobs = []
+    for src in HOSTCHECK_SOURCES:
+        obj = os.path.join(objdir, os.path.splitext(os.path.basename(src))[0] + ".o")
+        newest = max([os.path.getmtime(os.path.join(HOSTCHECK_DIR, f)) for f in os.listdir(HOSTCHECK_DIR) if f.endswith((".h", ".cpp"))])
+        if force or _needs_build(obj, src) or os.path.getmtime(obj) < newest:
+            jobs.append((src, obj))
+
+    def run(job):
+        src, obj = job
+        cmd = [hipcc, *HOSTCHECK_FLAGS, "-c", src, "-o", obj]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
+
+    with ThreadPoolExecutor(max_workers=4) as ex:
+        list(ex.map(run, jobs))
+    objs = [os.path.join(objdir, os.path.splitext(os.path.basename(s))[0] + ".o") for s in HOSTCHECK_SOURCES]
+    if jobs or not os.path.exists(HOSTCHECK):
+        # -no-hip-rt: no libamdhip64 on the link line - the program cannot open a GPU wherever it runs
+        cmd = [hipcc, "-no-hip-rt", "-fsanitize=address,undefined", *objs, "-o", HOSTCHECK]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    return HOSTCHECK
+
+
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, dev="--dev" in sys.argv))
+    if "--hostcheck" in sys.argv:
+        print(build_hostcheck(force="--force" in sys.argv, verbose=True))
+    else:
+        print(build(force="--force" in sys.argv, dev="--dev" in sys.argv))

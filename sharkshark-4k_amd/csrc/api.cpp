@@ -1,5 +1,6 @@
 // C ABI (include/ss4k.h): context, models, the frame-in/frame-out upscaler and the granular ops.
 #include "models.h"
+#include "host_tables.h"
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -21,16 +22,6 @@ static int guard(F&& f) {
   catch (const std::exception& e) { set_error("%s", e.what()); return SS4K_EINVAL; }
 }
 
-// blur_ker (fsrcnn_upscaler.py:20-52) as its 1-D factor: the reference's normalised 2-D kernel
-// (1 / (2 pi var)) exp(-(dx^2 + dy^2) / (2 var)) / sum is g[y] * g[x] with g = e / sum(e)
-static std::vector<float> gaussian_taps_1d(int k, float sigma) {
-  std::vector<float> g(k);
-  const float mean = (k - 1) / 2.0f, var = sigma * sigma;
-  double sum = 0.0;
-  for (int i = 0; i < k; ++i) { const float d = i - mean; g[i] = expf(-(d * d) / (2 * var)); sum += g[i]; }
-  for (auto& v : g) v = (float)(v / sum);
-  return g;
-}
 static std::vector<float> sharpen_taps(double strength) {  // sharpen_ker, fsrcnn_upscaler.py:54-84
   std::vector<float> t(9);
   const float s = (float)strength, one_m = (float)(1.0 - strength);
@@ -507,22 +498,6 @@ void cv_check_factor(double f) {
   SS4K_REQUIRE(f > 0.0 && f < 1.0, "cv area resize: factors must shrink (0 < f < 1)");
   const double scale = 1.0 / f;
   SS4K_REQUIRE(std::fabs(scale - std::nearbyint(scale)) >= 2.220446049250313e-16, "cv area resize: 1 / f is an integer - OpenCV's fast path (other rounding) is not implemented");
-}
-struct CvEnt { int si; float a; };
-// computeResizeAreaTab: the entries of every output cell [d * scale, (d + 1) * scale), in order; ofs[d] = first entry of cell d
-void cv_area_tab(int ssize, int dsize, double scale, std::vector<CvEnt>& ent, std::vector<int>& ofs) {
-  ent.clear(); ofs.assign(dsize + 1, 0);
-  for (int d = 0; d < dsize; ++d) {
-    ofs[d] = (int)ent.size();
-    const double fs1 = d * scale, fs2 = fs1 + scale, cell = std::min(scale, ssize - fs1);
-    int s1 = (int)std::ceil(fs1), s2 = (int)std::floor(fs2);
-    s2 = std::min(s2, ssize - 1);
-    s1 = std::min(s1, s2);
-    if (s1 - fs1 > 1e-3) ent.push_back({s1 - 1, (float)((s1 - fs1) / cell)});
-    for (int sx = s1; sx < s2; ++sx) ent.push_back({sx, float(1.0 / cell)});
-    if (fs2 - s2 > 1e-3) ent.push_back({s2, (float)(std::min(std::min(fs2 - s2, 1.), cell) / cell)});
-  }
-  ofs[dsize] = (int)ent.size();
 }
 }  // namespace
 int ss4k_op_cv_area_shape(int h, int w, double fx, double fy, int* oh, int* ow) {

@@ -284,7 +284,10 @@ struct PairArgs {
   float grid_share;
   double flops;
 };
-bool conv3x3_pair_eligible(int planes_a, int cout_pad_a, int nchunks_b, int cout_pad_b);
+// (the three routing predicates of the model executor are inline here: host code that links no kernel routes exactly as the product does)
+inline bool conv3x3_pair_eligible(int planes_a, int cout_pad_a, int nchunks_b, int cout_pad_b) {
+  return (planes_a == 1 || planes_a == 2) && cout_pad_a == 32 && nchunks_b == 2 && cout_pad_b == 32;
+}
 void launch_conv3x3_pair(ss4k_ctx* ctx, const PairArgs& a, hipStream_t st);
 
 // conv_dense.hip: conv_k and conv_{k+1} of a dense block (32 couts each, LeakyReLU, fp16) as one launch; conv_{k+1} reads conv_k's
@@ -304,7 +307,9 @@ struct DenseArgs {
   double flops;
   unsigned long long* dbg_buf;                          // dev library, SS4K_DENSE_STAMP=1: per-wave phase cycle counters
 };
-bool conv3x3_dense2_eligible(int nchunks_a, int cout_pad_a, int nchunks_b, int cout_pad_b);
+inline bool conv3x3_dense2_eligible(int nchunks_a, int cout_pad_a, int nchunks_b, int cout_pad_b) {
+  return cout_pad_a == 32 && cout_pad_b == 32 && nchunks_b == nchunks_a + 2 && nchunks_a >= 2 && nchunks_a % 2 == 0;
+}
 // conv_dense.hip: one layer, 64 couts per workgroup, plain epilogue (bit-identical to conv_mfma.hip's <__half,2,4,4> build)
 struct ConvArgs;
 bool conv3x3_wide_eligible(const ConvArgs& a, int dtype);
@@ -317,7 +322,10 @@ void launch_conv3x3_w16(ss4k_ctx* ctx, const ConvArgs& a, hipStream_t st);
 bool conv3x3_w16n_eligible(const ConvArgs& a, int dtype);
 void launch_conv3x3_w16n(ss4k_ctx* ctx, const ConvArgs& a, hipStream_t st);
 
-int conv_cw(int dtype);  // channels per plane / K-chunk: 16
+inline int conv_cw(int) { return 16; }  // channels per plane / K-chunk (conv_tile.h: CW)
+// channels a conv of `cout` output channels stores: one 32-cout block up to 32, whole 64-cout groups beyond (96 are written as 128).  The one
+// statement of the rule: pack_conv3x3 pads its blob to it, Model::act sizes a tensor by it, the kernels store all of it.
+inline int cout_pad_of(int cout) { return cout <= 32 ? 32 : (cout + 63) / 64 * 64; }
 inline int conv_rec_bytes(int dtype) { return dtype == SS4K_F16 ? 32 : 64; }  // bytes of one pixel's record in a plane
 
 // weight packing (pack.cpp) --------------------------------------------------------------

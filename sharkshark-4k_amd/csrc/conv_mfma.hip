@@ -40,7 +40,7 @@
 
 namespace ss4k {
 
-int conv_cw(int) { return CW; }
+static_assert(CW == 16, "conv_cw (common.h) states the plane width");
 
 // EK = epilogue kind the build is specialised for (a runtime switch between them costs registers - the all-in-one
 // build of round 1 spilled 52-68 bytes - and the kinds differ in the MFMA loop as well):

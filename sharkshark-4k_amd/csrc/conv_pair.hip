@@ -346,10 +346,6 @@ static void launch_t(ss4k_ctx* ctx, const PairArgs& a0, hipStream_t st) {
 
 }  // namespace pair
 
-bool conv3x3_pair_eligible(int planes_a, int cout_pad_a, int nchunks_b, int cout_pad_b) {
-  return (planes_a == 1 || planes_a == 2) && cout_pad_a == 32 && nchunks_b == 2 && cout_pad_b == 32;
-}
-
 void launch_conv3x3_pair(ss4k_ctx* ctx, const PairArgs& a, hipStream_t st) {
   using namespace pair;
   SS4K_REQUIRE(a.N > 0 && a.H > 0 && a.W > 0 && (a.planes_a == 1 || a.planes_a == 2), "conv3x3_pair: shape");

@@ -30,7 +30,11 @@ static std::vector<std::pair<int, int>> bsvd_denblock_shapes(const int* chns, in
           {c2, c2}, {c2, c2}, {c1 * 4, c2}, {c1, c1}, {c1, c1}, {c0 * 4, c1}, {c0, c0}, {out_ch, c0}};
 }
 
+static void validate_desc(const ss4k_model_desc& d);
+
+// 0 for a description validate_desc refuses (include/ss4k.h): the sums below are only in range for validated widths
 size_t model_param_count(const ss4k_model_desc& d) {
+  try { validate_desc(d); } catch (const Error&) { return 0; }
   switch (d.kind) {
     case SS4K_FSRCNN:
       return 56 * 25 + 56 + 56 + 12 * 56 + 12 + 12 + 4 * (12 * 12 * 9 + 12 + 12) + 56 * 12 + 56 + 56 + 56 * 81 + 1;
@@ -68,7 +72,13 @@ size_t model_param_count(const ss4k_model_desc& d) {
   return 0;
 }
 
+// Every width is bounded by MAX_WIDTH (512: twice the widest network the service builds, BSVD-64's 256) and every depth by MAX_BLOCKS
+// (64: RealESRGAN has 23 blocks, SRVGG 32 convs) - include/ss4k.h.  Plane counts (at most 5 * 512 / 16) and channel products (4 * 512)
+// then stay far inside int, a layer has at most 2560 * 512 * 9 weights and model_param_count at most 3 * 5 * 64 layers of them, below
+// 2^34 - inside size_t.  Both bounds are points of the host check's walk (tests/hostcheck).  The message names the offending field.
 static void validate_desc(const ss4k_model_desc& d) {
+  constexpr int MAX_WIDTH = SS4K_DESC_MAX_WIDTH, MAX_BLOCKS = SS4K_DESC_MAX_BLOCKS;
+  auto width = [&](int v, int mult) { return v > 0 && v <= MAX_WIDTH && v % mult == 0; };
   SS4K_REQUIRE(d.dtype == SS4K_F32 || d.dtype == SS4K_F16, "desc.dtype must be SS4K_F32 or SS4K_F16");
   SS4K_REQUIRE(d.bsvd_stream == 0 || (d.bsvd_stream == 1 && d.kind == SS4K_BSVD), "desc.bsvd_stream is 0 or 1 and only applies to BSVD");
   switch (d.kind) {
@@ -77,17 +87,21 @@ static void validate_desc(const ss4k_model_desc& d) {
       break;
     case SS4K_RRDBNET:
       SS4K_REQUIRE(d.scale == 1 || d.scale == 2 || d.scale == 4, "RRDBNet scale must be 1, 2 or 4");
-      SS4K_REQUIRE(d.num_feat > 0 && d.num_feat % 32 == 0 && d.num_grow_ch > 0 && d.num_grow_ch % 32 == 0 && d.num_block > 0,
-                   "RRDBNet: num_feat and num_grow_ch must be multiples of 32");
+      SS4K_REQUIRE(width(d.num_feat, 32), "RRDBNet: num_feat must be a multiple of 32 in 32..512");
+      SS4K_REQUIRE(width(d.num_grow_ch, 32), "RRDBNet: num_grow_ch must be a multiple of 32 in 32..512");
+      SS4K_REQUIRE(d.num_block > 0 && d.num_block <= MAX_BLOCKS, "RRDBNet: num_block must be in 1..64");
       break;
     case SS4K_SRVGG:
       SS4K_REQUIRE(d.scale == 2 || d.scale == 4, "SRVGG upscale must be 2 or 4 (PixelShuffle tail)");
-      SS4K_REQUIRE(d.num_feat > 0 && d.num_feat % 16 == 0 && d.num_block >= 0, "SRVGG: num_feat must be a multiple of 16");
+      SS4K_REQUIRE(width(d.num_feat, 16), "SRVGG: num_feat must be a multiple of 16 in 16..512");
+      SS4K_REQUIRE(d.num_block >= 0 && d.num_block <= MAX_BLOCKS, "SRVGG: num_block must be in 0..64");
       break;
     case SS4K_BSVD:
-      SS4K_REQUIRE(d.bsvd_chns[0] % 32 == 0 && d.bsvd_chns[1] % 64 == 0 && d.bsvd_chns[2] % 64 == 0 && d.bsvd_mid_ch % 32 == 0 &&
-                       d.bsvd_interm_ch > 0 && d.bsvd_interm_ch <= 256,
-                   "BSVD: unsupported channel configuration");
+      SS4K_REQUIRE(width(d.bsvd_chns[0], 32), "BSVD: bsvd_chns[0] must be a multiple of 32 in 32..512");
+      SS4K_REQUIRE(width(d.bsvd_chns[1], 64), "BSVD: bsvd_chns[1] must be a multiple of 64 in 64..512");
+      SS4K_REQUIRE(width(d.bsvd_chns[2], 64), "BSVD: bsvd_chns[2] must be a multiple of 64 in 64..512");
+      SS4K_REQUIRE(width(d.bsvd_mid_ch, 32), "BSVD: bsvd_mid_ch must be a multiple of 32 in 32..512");
+      SS4K_REQUIRE(d.bsvd_interm_ch > 0 && d.bsvd_interm_ch <= 256, "BSVD: bsvd_interm_ch must be in 1..256");
       break;
     default:
       throw Error(SS4K_EINVAL, "unknown model kind");
@@ -611,11 +625,12 @@ size_t Model::workspace_bytes(int n, int h, int w) {
 // activation buffer idx holding `channels` channels (rounded up to whole 32-cout groups of planes,
 // which is what a producing conv writes) for `pixels` pixels
 Tens Model::act(int idx, size_t pixels, int channels) {
+  // what a producing conv writes (cout_pad_of, common.h: a 96-channel tensor is written as 128 - sized to 96 its last two planes
+  // would land past the buffer)
+  return act_planes(idx, pixels, planes_for(cout_pad_of(channels)));
+}
+Tens Model::act_planes(int idx, size_t pixels, int planes) {
   if ((int)acts.size() <= idx) acts.resize(idx + 1);
-  // what a producing conv writes: one 32-cout block up to 32 channels, whole 64-cout groups beyond (pack_conv3x3's cout_pad - a
-  // 96-channel tensor is written as 128: sized to 96 its last two planes would land past the buffer)
-  const int ch32 = channels <= 32 ? 32 : (channels + 63) / 64 * 64;
-  const int planes = planes_for(ch32);
   SS4K_REQUIRE(pixels < 2147483648ull, "an activation plane holds at most 2^31 pixels");
   const size_t need = (size_t)planes * pixels * rec();
   if (plan_only) {
@@ -725,7 +740,9 @@ void Model::forward_impl(const float* in, float* out, int n, int h, int w, hipSt
     const int cin0 = 3 * r * r;
     Tens P = act(0, px, cin0);
     Tens F = act(1, px, nf), X[3] = {act(2, px, nf), act(3, px, nf), act(4, px, nf)};
-    Tens G = act(5, px, 4 * g);
+    // the growth tensor: conv4 stores at channel 3 g, and a conv stores cout_pad_of(g) channels, not g (96 are written as 128) - 4 g
+    // channels would leave conv4's padding planes past the buffer.  g = 32 and g = 64 have cout_pad_of(g) == g: the size of before.
+    Tens G = act_planes(5, px, planes_for(3 * g + cout_pad_of(g)));
     pack_in(in, P, planes_for(cin0), n, 3, h, w, r, st);
     int li = 0;
     { ConvOpts o; o.out = F; conv(li++, P, nullptr, n, H, W, o, st); }

@@ -127,6 +127,7 @@ struct Model {
   // dense-block layers li and li + 1 (both LeakyReLU `slope`, outputs out1 / out2) as one fused launch; false if the pair does not fit
   bool conv_dense(int li, const Tens& in0, const Tens* in1, int N, int H, int W, float slope, const Tens& out1, const Tens& out2, hipStream_t st);
   Tens act(int idx, size_t pixels, int channels);
+  Tens act_planes(int idx, size_t pixels, int planes);   // ... holding exactly `planes` planes
   void pack_in(const float* in, const Tens& dst, int nplanes, int n, int c, int h, int w, int r, hipStream_t st);
 
  private:

@@ -101,6 +101,54 @@ CASES = [
 ]
 
 
+# ---- the width lattice: channel configurations between the ones above that validate_desc accepts (the host check, tests/hostcheck, walks
+# all of them for buffer ranges and packing; these sample them for the arithmetic).  num_block = 1 throughout; layer-resolution shapes
+# with partial tiles on both edges, small enough that two planes fit the guard mode's 64 KiB red zone (11 x 33 px x 32 B x 2 = 23 KB).
+# cout_pad != cout_real at 96 / 160 / 48 / 80 / 112 (a 96-channel tensor is written as 128), odd K-chunk counts at 48 / 80 / 112 (no w16 blob),
+# dense pairs only where the growth is 32, conv_pair only where both layers of the pair are one 32-cout block.
+# Measured on MI355X (profiles/lattice_parity_measured.json): fp16 max 0.32-1.34, exact fp32 max 1.49-2.16 / slice <= 2.69.
+def _sv(nf, dtype="f16", flags=0, scale=4, nb=1, must=frozenset(), shape=(1, 3, 13, 33)):
+    tag = f"srvgg{nf}_{dtype}_x{scale}_nb{nb}" + ("_no_w16" if flags & NO_W16 else "")
+    return Case("lattice_" + tag, "srvgg", dtype, flags, dict(scale=scale, num_feat=nf, num_block=nb), shape, set(must))
+
+
+def _bs(id, net, dtype, chns, mid, interm, shape, must=frozenset(), flags=ONE):
+    return Case("lattice_" + id, net, dtype, flags, dict(chns=chns, mid_ch=mid, interm_ch=interm), shape, set(must))
+
+
+L2 = (1, 3, 2 * 11, 2 * 33)
+CASES += [
+    _rr("lattice_rrdbnet_f16_x2_nf32_g32", "f16", 0, 2, L2, {D0}, nf=32, g=32),
+    _rr("lattice_rrdbnet_f16_x2_nf128_g32", "f16", 0, 2, L2, {D0}, nf=128, g=32),
+    _rr("lattice_rrdbnet_f16_x2_nf64_g96", "f16", 0, 2, L2, set(), nf=64, g=96),
+    _rr("lattice_rrdbnet_f16_x2_nf32_g96", "f16", 0, 2, L2, set(), nf=32, g=96),
+    _rr("lattice_rrdbnet_f16_x2_nf96_g64", "f16", 0, 2, L2, set(), nf=96, g=64),
+    _rr("lattice_rrdbnet_f16_x2_nf160_g160", "f16", 0, 2, L2, set(), nf=160, g=160),
+    _rr("lattice_rrdbnet_f16_x2_nf64_g96_no_dense_no_w16", "f16", NO_DENSE | NO_W16, 2, L2, set(), nf=64, g=96),
+    _rr("lattice_rrdbnet_f16_x2_nf64_g96_3frames_two_chains", "f16", TWO, 2, (3, 3, 2 * 9, 2 * 31), set(), nf=64, g=96),
+    _rr("lattice_rrdbnet_f16_x4_nf96_g96", "f16", 0, 4, (1, 3, 13, 31), set(), nf=96, g=96),
+    _rr("lattice_rrdbnet_f32_x2_nf96_g96", "f32", 0, 2, L2, set(), nf=96, g=96),
+    _sv(16), _sv(48), _sv(80), _sv(96, must={W16}), _sv(112), _sv(96, flags=NO_W16),
+    _sv(64, nb=0), _sv(48, dtype="f32", scale=2, nb=0),
+    # conv_pair (inc: 4 -> interm -> chns[0], outc: chns[0] -> chns[0] -> out) needs 32-cout blocks and two K-chunks into its second layer:
+    # interm 16 is ONE K-chunk, so inc falls back to two launches while outc still fuses; interm 32 fuses both; chns[0] >= 64 fuses neither
+    _bs("bsvd_f16_f1_32_64_64_mid32_interm16", "bsvd", "f16", (32, 64, 64), 32, 16, (1, 4, 28, 60), {PAIR}),
+    _bs("bsvd_f16_f1_32_64_128_mid32_interm32", "bsvd", "f16", (32, 64, 128), 32, 32, (1, 4, 28, 60), {PAIR}),
+    _bs("bsvd_f16_f1_64_64_128_mid64_interm48", "bsvd", "f16", (64, 64, 128), 64, 48, (1, 4, 28, 60)),
+    _bs("bsvd_f16_f1_96_128_192_mid96_interm33", "bsvd", "f16", (96, 128, 192), 96, 33, (1, 4, 28, 60)),
+    _bs("bsvd_f16_stream_3frames_32_64_64_mid32_interm30", "bsvd_seq", "f16", (32, 64, 64), 32, 30, (3, 4, 20, 36)),
+    _bs("bsvd_f32_f1_96_128_192_mid96_interm33", "bsvd", "f32", (96, 128, 192), 96, 33, (1, 4, 28, 60), flags=0),
+]
+# launches of the fused pair kernel per forward (one frame, one chain: one launch per pair; two denoising blocks): where the widths
+# were chosen for the pair's eligibility the COUNT is asserted, not only the build's presence - outc fuses whatever interm_ch is
+PAIR_LAUNCHES = {
+    "lattice_bsvd_f16_f1_32_64_64_mid32_interm16": 2,      # inc falls back (one K-chunk into its second layer), outc fuses
+    "lattice_bsvd_f16_f1_32_64_128_mid32_interm32": 4,     # inc and outc fuse
+    "lattice_bsvd_f16_f1_64_64_128_mid64_interm48": 0,
+    "lattice_bsvd_f16_f1_96_128_192_mid96_interm33": 0,
+}
+
+
 def _srvgg_table(nf, nc, scale):
     """Generated weights with PReLU slopes in [-0.5, 1.7] on alternate layers (both HIP epilogue forms: max(t, t s) needs s <= 1)."""
     t = W.srvgg_table(seed=nf + scale, num_feat=nf, num_conv=nc, upscale=scale)
@@ -127,20 +175,26 @@ def _build(ctx, c):
         m = _capi.Model(ctx, desc, W.flatten(t, W.srvgg_keys(a["num_block"])))
         return m, onets.srvgg, (a["num_block"], a["scale"]), t, x, (a["scale"],)
     stream = c.net == "bsvd_seq"
-    t = W.bsvd_table(seed=5, **factory.BSVD_VARIANTS[a["variant"]])
-    m = factory.build_denoise_model(ctx, weights=t, dtype=c.dtype, stream=stream, variant=a["variant"], flags=c.flags)
+    if "variant" in a:
+        t = W.bsvd_table(seed=5, **factory.BSVD_VARIANTS[a["variant"]])
+        m = factory.build_denoise_model(ctx, weights=t, dtype=c.dtype, stream=stream, variant=a["variant"], flags=c.flags)
+    else:   # the widths directly: chns, mid_ch, interm_ch
+        t = W.bsvd_table(seed=5, **a)
+        desc = _capi.make_desc(_capi.BSVD, dt, scale=1, bsvd_stream=stream, bsvd_chns=a["chns"], bsvd_mid_ch=a["mid_ch"],
+                               bsvd_interm_ch=a["interm_ch"], flags=c.flags)
+        m = _capi.Model(ctx, desc, W.flatten(t, W.bsvd_keys(**a)))
     x = x[None] if stream else x[:, None]   # (N, F, C, H, W): one stream of F frames, or F = 1 per frame
     return m, onets.bsvd_seq if stream else onets.bsvd_f1, (), t, x, (1, 2, 4)
 
 
 def _run_profiled(ctx, fn):
-    """fn() with the context's per-build profile on; returns (result, the conv builds launched)."""
+    """fn() with the context's per-build profile on; returns (result, {conv build launched: launches})."""
     ctx.prof_enable(True)
     try:
         ctx.prof_reset()
         out = fn()
         torch.cuda.synchronize()
-        fams = {name.split(" (")[0] for name, n, _, _ in ctx.prof_read_families() if n > 0}
+        fams = {name.split(" (")[0]: n for name, n, _, _ in ctx.prof_read_families() if n > 0}
     finally:
         ctx.prof_enable(False)
     return out, fams
@@ -159,7 +213,9 @@ def test_route_error_budget(ctx, case):
     record_measured(f"error_budget_{case.id}", max_ratio=r["max"], slice_ratio=r["slice"], worst_slice=str(r["worst_slice"]),
                     asserted=f"max <= {bars['k_max']}, slice <= {bars['k_slice']}", builds=sorted(fams))
     assert_error_budget(got, ref, yard, what=case.id, tiles=tiles, **bars)
-    assert case.must <= fams, f"{case.id}: builds {sorted(case.must - fams)} not launched (launched: {sorted(fams)})"
+    assert case.must <= set(fams), f"{case.id}: builds {sorted(case.must - set(fams))} not launched (launched: {sorted(fams)})"
+    if case.id in PAIR_LAUNCHES:
+        assert fams.get(PAIR, 0) == PAIR_LAUNCHES[case.id], f"{case.id}: {fams.get(PAIR, 0)} fused-pair launches, {PAIR_LAUNCHES[case.id]} expected"
 
 
 # ------------------------------------------------------------------------------ FSRCNN: f16 mode, fp32-grade split, exact

@@ -4,6 +4,7 @@ fp32 path: rtol 1e-3 / atol 1e-4 (BASELINE.json north_star).  uint8 frames: at m
 (truncation of floats that agree to 1e-4 can flip the integer).  fp16 path: PSNR.
 """
 import os
+import re
 
 import numpy as np
 import pytest
@@ -283,6 +284,29 @@ def test_service_rejects_bad_input(ctx):
     with pytest.raises(_capi.Ss4kError):  # RRDBNet x2 needs even sizes (pixel_unshuffle raises in the reference too)
         factory.build_model_esrgan(ctx, "RealESRGAN_x2plus", weights=rrdb_small_table(seed=7, scale=2, num_block=1),
                                    dtype="f32", scale=2, num_block=1)(torch.rand(1, 3, 15, 16).cuda())
+
+
+@pytest.mark.parametrize("kind,kw,field", [
+    ("BSVD", dict(bsvd_chns=(0, 64, 128)), "bsvd_chns[0]"),
+    ("BSVD", dict(bsvd_chns=(-32, 64, 128)), "bsvd_chns[0]"),
+    ("BSVD", dict(bsvd_chns=(32, 0, 128)), "bsvd_chns[1]"),
+    ("BSVD", dict(bsvd_chns=(32, 64, -64)), "bsvd_chns[2]"),
+    ("BSVD", dict(bsvd_chns=(32, 64, 1 << 29)), "bsvd_chns[2]"),      # c * 4 would overflow int
+    ("BSVD", dict(bsvd_mid_ch=0), "bsvd_mid_ch"),
+    ("RRDBNET", dict(num_feat=2048, num_block=1), "num_feat"),
+    ("RRDBNET", dict(num_grow_ch=2147483616, num_block=1), "num_grow_ch"),
+    ("RRDBNET", dict(num_block=1 << 20), "num_block"),
+    ("SRVGG", dict(scale=4, num_feat=1040, num_block=1), "num_feat"),
+    ("SRVGG", dict(scale=4, num_feat=64, num_block=2000), "num_block"),
+], ids=lambda v: v if isinstance(v, str) else None)
+def test_model_descriptions_outside_the_bounds_are_refused(ctx, kind, kw, field):
+    """The product boundary from the Python binding: a description outside validate_desc's bounds (csrc/models.cpp; widths positive and at most
+    SS4K_DESC_MAX_WIDTH, depths at most SS4K_DESC_MAX_BLOCKS) comes back as Ss4kError naming the field, before any size is computed
+    from it; ss4k_model_param_count answers 0."""
+    desc = _capi.make_desc(getattr(_capi, kind), _capi.F16, **kw)
+    assert _capi.param_count(desc) == 0
+    with pytest.raises(_capi.Ss4kError, match=re.escape(field)):
+        _capi.Model(ctx, desc, np.zeros(64, np.float32))
 
 
 # ------------------------------------------------------------------------------ ragged shapes

@@ -1,0 +1,132 @@
+"""CPU: the host check - the product's models.cpp and pack.cpp, host side only, under ASan + UBSan (tests/hostcheck, DESIGN.md "Host check").
+
+The program links HIP stand-ins backed by host memory and launch auditors in place of the kernels - no HIP runtime, no Python, so it
+cannot open a GPU - and runs as a plain child process (nothing is preloaded).  It walks the lattice of model descriptions: every
+accepted one is built from a generated weight blob and run through ``workspace_bytes`` and a real forward at 8 shapes (1 and 3 frames at
+layer resolution 1 x 1, 1 x 33, 7 x 9, 17 x 33), every byte range a kernel would touch asserted inside one live allocation; the packed
+weight blobs are shown to be a bijection onto the layer's live weights; every invalid description must be refused with SS4K_EINVAL.
+
+The lattice as walked (thinned: the full cross product of the issue's axes packs 100 G parameters, 40 minutes under the sanitizers;
+every axis keeps both ends):
+
+* RRDBNet: num_feat 32, 64, 96, 128, 160, 256 x num_grow_ch 32, 64, 96, 160, num_block 1.  Flags 0 at scale 1, 2, 4 in both dtypes with the
+  bijection check; NO_DENSE, NO_W16, NO_WIDE, NO_W16|NO_DENSE, TWO_CHAINS in fp16 at scale 2 (the flags choose between fp16 kernels and
+  change no packed weight and no buffer size).
+* SRVGG: num_feat 16..256 step 16 x num_block 0, 1, 3.  Flags 0 at scale 2, 4 in both dtypes with the bijection check; NO_W16, NO_WIDE,
+  TWO_CHAINS in fp16 at scale 4.
+* BSVD: the 16 corners of (chns[0], chns[1], chns[2], mid_ch) in {32, 96} x {64, 192} x {64, 192} x {32, 96}, the centre
+  (64, 128, 128, 64) and the interior points the GPU cases run, (32, 64, 128, 32), (64, 64, 128, 64), (96, 128, 192, 96); interm_ch 1, 16,
+  30, 32, 33, 48, 64, 256 at stream 0 in fp16; at interm_ch 1, 30, 33, 256 also stream 1, fp32, NO_PAIR and NO_PAIR|TWO_CHAINS on a stream.
+* FSRCNN: scale 2, 4 x both dtypes x flags 0, FS_EXACT, TWO_CHAINS.
+* The bounds validate_desc sets (widths at most 512, num_block at most 64): RRDBNet 512 x 512 and 32 x 32 with 64 blocks, SRVGG 512 and
+  16 with 64 convs, BSVD (512, 512, 512, mid 512, interm 256) with and without a stream - both dtypes, no bijection check.  Nothing
+  the library accepts lies outside the walked box.
+
+Every description a GPU test runs (tests/test_gpu_error_budget.py) is a point of this walk.
+
+1184 descriptions accepted, 104 refused, 9472 shapes audited (323 k launches), 13 904 layers through the bijection check.  Measured on 8
+CPUs: 8 shards side by side, 68 s wall and 8.3 CPU-minutes (7.6 G parameters packed at 65 ns each; the slowest shard 68 s, the fastest
+59 s).  The walk has ONE deadline (DEADLINE), not one per shard.
+"""
+import os
+import re
+import subprocess
+import time
+
+import pytest
+
+import sharkshark4k_amd  # noqa: F401
+from sharkshark4k_amd import build as B
+
+SHARDS = 8        # side by side; a command on a GPU machine may use 16 CPUs
+DEADLINE = 600    # seconds for the whole walk (measured: 68 s on 8 CPUs, 8.3 CPU-minutes - a machine with one free core still fits)
+ACCEPTED, REFUSED, SHAPES = 1184, 104, 9472
+
+
+@pytest.fixture(scope="module")
+def prog():
+    return B.build_hostcheck()
+
+
+def _env():
+    """The caller's environment without what would change the program's own behaviour: sanitizer options and the library's switches."""
+    return {k: v for k, v in os.environ.items() if k not in ("ASAN_OPTIONS", "UBSAN_OPTIONS") and not k.startswith("SS4K_")}
+
+
+def _run(prog, *args, timeout=120):
+    return subprocess.run([prog, *args], capture_output=True, text=True, timeout=timeout, env=_env())
+
+
+def test_program_links_no_gpu_runtime(prog):
+    r = subprocess.run(["ldd", prog], capture_output=True, text=True)
+    assert r.returncode == 0
+    bad = [ln for ln in r.stdout.splitlines() if re.search(r"amdhip|hsa-runtime|libpython|libtorch", ln)]
+    assert not bad, bad
+
+
+def test_lattice_walk_is_clean(prog):
+    procs = [subprocess.Popen([prog, "--shard", str(i), str(SHARDS)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=_env()) for i in range(SHARDS)]
+    total = dict(accepted=0, refused=0, shapes=0, launches=0, bijection_layers=0, violations=0, findings=0)
+    deadline = time.monotonic() + DEADLINE   # one limit for the whole walk, not one per shard
+    try:
+        for i, p in enumerate(procs):
+            out, err = p.communicate(timeout=max(1.0, deadline - time.monotonic()))
+            lines = out.splitlines()
+            bad = [ln for ln in lines if ln.startswith(("VIOLATION", "FINDING"))]
+            assert not bad, f"shard {i}: {len(bad)} reports, first:\n" + "\n".join(bad[:10])
+            assert err == "", f"shard {i}: output on the sanitizers' stream:\n{err[-3000:]}"
+            assert p.returncode == 0, f"shard {i}: exit status {p.returncode}\n{out[-2000:]}"
+            done = [ln for ln in lines if ln.startswith("HOSTCHECK ")]
+            assert len(done) == 1, out[-2000:]
+            for k, v in re.findall(r"(\w+)=(\d+)", done[0]):
+                total[k] += int(v)
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+    assert (total["accepted"], total["refused"], total["shapes"]) == (ACCEPTED, REFUSED, SHAPES), total
+    assert total["violations"] == 0 and total["findings"] == 0, total
+    assert total["launches"] > 300000 and total["bijection_layers"] > 13000, total
+
+
+# One RRDBNet forward (num_feat 64, num_grow_ch 32, x4, NO_DENSE, one frame of 7 x 9): launch 0 packs the input, launch 1 is conv_first,
+# RDB r runs conv1..conv5 as launches 2 + 5 r .. 6 + 5 r.  The growth tensor (buffer 5) holds 8 planes; its last one is written by conv4
+# (planes 6, 7) and read by conv5 (planes 0..7) of each of the three RDBs.  conv_first's output (buffer 1, 4 planes) is written by
+# launch 1, read by RDB 1 (conv1..conv5: launches 2..6; conv5 also takes it as its residual), by conv5 of RDB 3 (launch 16: the RRDB's
+# own skip, res2) and by conv_body (launch 17) as its residual.
+@pytest.mark.parametrize("buffer,launches", [(5, [5, 6, 10, 11, 15, 16]), (1, [1, 2, 3, 4, 5, 6, 16, 17])], ids=["growth", "conv_first"])
+def test_control_short_buffer_is_reported(prog, buffer, launches):
+    r = _run(prog, "--control-shrink", str(buffer))
+    assert r.returncode == 0 and r.stderr == "", r.stdout[-2000:] + r.stderr[-2000:]
+    seen = sorted({int(m) for m in re.findall(r"^VIOLATION .*\| launch (\d+) ", r.stdout, re.M)})
+    assert seen == launches, f"the auditor reported launches {seen}, the last plane of buffer {buffer} is touched by {launches}\n{r.stdout[-1500:]}"
+    assert re.search(r"^CONTROL shrink buffer %d violations=[1-9]" % buffer, r.stdout, re.M)
+
+
+def test_control_short_blob_is_refused(prog):
+    r = _run(prog, "--control-short-blob")
+    assert r.returncode == 0 and r.stderr == "", r.stdout + r.stderr
+    assert "CONTROL short blob: SS4K_EINVAL (-22)" in r.stdout, r.stdout
+
+
+# Which route a width takes, from the executor itself (--trace prints one line per launch): the eligibility the GPU cases of
+# tests/test_gpu_error_budget.py were chosen for, checked here without a GPU.  Arguments: kind dtype scale num_feat num_block num_grow_ch
+# chns[0..2] mid_ch interm_ch stream flags | frames H W (layer resolution).  Flags 2 = ONE_CHAIN.
+@pytest.mark.parametrize("desc,shape,kind,count", [
+    ("4 1 1 0 0 0 32 64 64 32 16 0 2", "1 7 15", "pair", 2),      # interm_ch 16 is one K-chunk: inc falls back, outc still fuses (two blocks)
+    ("4 1 1 0 0 0 32 64 128 32 32 0 2", "1 7 15", "pair", 4),     # inc and outc fuse
+    ("4 1 1 0 0 0 64 64 128 64 48 0 2", "1 7 15", "pair", 0),     # chns[0] = 64 is a 64-cout block: no pair
+    ("4 1 1 0 0 0 96 128 192 96 33 0 2", "1 7 15", "pair", 0),
+    ("2 1 2 32 1 32 0 0 0 0 0 0 0", "1 11 33", "dense2", 6),      # growth 32: (conv1, conv2) and (conv3, conv4) of three RDBs fuse
+    ("2 1 2 128 1 32 0 0 0 0 0 0 0", "1 11 33", "dense2", 6),
+    ("2 1 2 64 1 96 0 0 0 0 0 0 0", "1 11 33", "dense2", 0),      # growth 96 is written as 128 channels: not the 32-cout pair
+    ("3 1 4 96 1 0 0 0 0 0 0 0 0", "1 13 33", "w16", 2),          # 6 K-chunks, cout_pad 128: body and tail layers carry a w16 blob
+    ("3 1 4 48 1 0 0 0 0 0 0 0 0", "1 13 33", "w16", 0),          # 3 K-chunks: odd, no w16 blob
+])
+def test_routes_of_the_gpu_lattice_cases(prog, desc, shape, kind, count):
+    r = _run(prog, "--trace", *desc.split(), *shape.split())
+    assert r.returncode == 0 and r.stderr == "", r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("LAUNCH ")]
+    assert lines, r.stdout
+    got = sum((" w16" in ln) if kind == "w16" else (f" {kind} " in ln) for ln in lines)
+    assert got == count, f"{got} {kind} launches, {count} expected:\n" + "\n".join(lines)
