@@ -60,8 +60,17 @@ __device__ __forceinline__ f32x4 mma16(const uint4& w, const uint4& x, f32x4 acc
 //   there - one more MFMA per accumulator with a (1 / alpha) I fragment on tap (dy 1, dx 1), as the wide kernel does -
 //   instead of being read from memory again in the epilogue.  Output plane P = 2 jw + (kg >> 1) is input plane P: wave pair jw adds during
 //   chunk pair q == jw, rows of row groups kg >> 1 == 0 in phase 0 (plane 2 jw), kg >> 1 == 1 in phase 2 (plane 2 jw + 1).
+//   GEN (dev library, SS4K_EPI_GENERIC=1): the epilogue as it was before its forms were specialised (every activation's arithmetic
+//   evaluated, absent residuals added as zeros, a store's address rebuilt per row) - the A/B and bit-identity reference of the forms below
+#ifdef SS4K_DEV
+template <bool STAMP = false, bool RL = false, bool GEN = false>
+#else
 template <bool STAMP = false, bool RL = false>
+#endif
 __global__ __launch_bounds__(64 * NW, 2) void conv3x3_w16_kernel(const ConvArgs a) {
+#ifndef SS4K_DEV
+  constexpr bool GEN = false;
+#endif
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const uint32_t lds0 = (uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -144,6 +153,12 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3x3_w16_kernel(const ConvArgs 
     }
   };
   auto slot_inc = [](int s) { return s == NWS - 1 ? 0 : s + 1; };
+  // the lane number, computed where it is asked for (the opaque zero keeps the compiler from computing it once and holding it)
+  auto lane_now = [] {
+    unsigned z = 0;
+    asm volatile("" : "+v"(z));
+    return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
+  };
 
   float* epi_lds = reinterpret_cast<float*>(smem + B_OFF);   // [64 bias, accumulator order (block, row group, i)][64 slope, virtual cout order]
   if (tid < 64) {
@@ -182,10 +197,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3x3_w16_kernel(const ConvArgs 
     f32x4 acc[MB][2][2];   // [output row][pixel half][block 2 jw + e]; written whole by its first MFMA of the tile (C = the bias)
     f32x4 bias4[2];
     {
-      const float4* bp = reinterpret_cast<const float4*>(smem + B_OFF + kg * 16 + jw * 128);
-      int o = 0;
-      asm volatile("" : "+v"(o));   // re-read per tile: held across tiles the eight values are registers of the MFMA loops
-      const float4 b0 = bp[o], b1 = bp[o + 4];
+      // re-read per tile, at an address rebuilt from the lane number: held across tiles the eight values, or the address, are registers of the MFMA loops
+      const float4* bp = reinterpret_cast<const float4*>(smem + B_OFF + (lane_now() >> 4) * 16 + jw * 128);
+      const float4 b0 = bp[0], b1 = bp[4];
       bias4[0] = f32x4{b0.x, b0.y, b0.z, b0.w}; bias4[1] = f32x4{b1.x, b1.y, b1.z, b1.w};
     }
     const int cur_n = n, cur_y0 = y0, cur_x0 = x0;
@@ -289,35 +303,44 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3x3_w16_kernel(const ConvArgs 
     // group's four output planes in its two blocks (first four | last four): one 16-byte store per row and pixel half
     {
       const float alpha = a.alpha, gamma = a.gamma;
-      int kge = kg;
-      asm volatile("" : "+v"(kge));
-      float slope_v[8];
-      {
+      // the lane's row group and pixel from the lane number as computed HERE: whatever of the epilogue is derived ahead of the MFMA
+      // loops is a register held through them (kg alone, held that way, was the RL build's one spilled register)
+      const int le = lane_now();
+      const int kge = le >> 4, n16e = le & 15;
+      // the slopes of this lane's eight channels: read only by the forms that multiply by them
+      auto load_slopes = [&](float* s) {
         const float4* sp = reinterpret_cast<const float4*>(epi_lds + 64 + 32 * jw + 8 * kge);
         const float4 s0 = sp[0], s1 = sp[1];
-        slope_v[0] = s0.x; slope_v[1] = s0.y; slope_v[2] = s0.z; slope_v[3] = s0.w;
-        slope_v[4] = s1.x; slope_v[5] = s1.y; slope_v[6] = s1.z; slope_v[7] = s1.w;
-      }
+        s[0] = s0.x; s[1] = s0.y; s[2] = s0.z; s[3] = s0.w;
+        s[4] = s1.x; s[5] = s1.y; s[6] = s1.z; s[7] = s1.w;
+      };
       const int opl = grp * 4 + 2 * jw + (kge >> 1);
       const size_t sub = (size_t)(kge & 1) * 16;
       const char* r1p = (a.res1 && !RL) ? a.res1 + (size_t)(a.r1_plane0 + opl) * a.r1_plane_bytes + sub : nullptr;
       const char* r2p = a.res2 ? a.res2 + (size_t)(a.r2_plane0 + opl) * a.r2_plane_bytes + sub : nullptr;
       char* outp = a.out + (size_t)(a.out_plane0 + opl) * a.out_plane_bytes + sub;
-      const bool resid = r1p || r2p;
-      // one copy of the store loop per epilogue form (a single loop with the forms selected per value compiled to eleven vector
-      // instructions per value: every form evaluated, the result picked with v_cndmask)
-      //   0: t >= 0 ? t : t * slope (PReLU per channel)   1: max(t, t * slope) (LeakyReLU, slope in [0, 1]; none: slope 1)   2: ReLU6
+      // Addresses: (plane + x * REC) per lane + a wave-uniform row offset that stays on the scalar unit - three vector instructions per
+      // store instead of five.  ONE 64-bit address per tile advanced by the row stride would be two less again, but held through the
+      // epilogue it sent an address register of the DMA issue (MFMA loops) to scratch in the RL build (profiles/NOTES_r07.md).
+      const int ey0 = cur_y0 + rgp * MB, ex = cur_x0 + n16e;
+      auto row_off = [&](int y) { return ((size_t)cur_n * a.H + y) * a.W * REC; };   // wave-uniform: scalar instructions
+      // One copy of the store loop per epilogue form and per set of residuals (a single loop with the forms selected per value
+      // compiled to eleven vector instructions per value: every form evaluated, the result picked with v_cndmask).  Activation forms:
+      //   0: t >= 0 ? t : t * slope (PReLU per channel)   1: max(t, t * slope) (LeakyReLU / PReLU with slopes in [0, 1])   2: ReLU6
+      //   3: none - no slope read, no multiply by a slope of 1, no maximum (x * 1.0f, max(t, t) and t >= 0 ? t : t are t itself for every
+      //      non-NaN t, -0 included: the same bytes as forms 0 and 1 gave with a slope of 1)
       auto stores = [&](auto FORM, auto ALPHA1) {
         constexpr int form = decltype(FORM)::value;
         constexpr bool alpha1 = decltype(ALPHA1)::value;   // alpha == 1: no multiply (x * 1.0f is x)
+        float slope_v[8];
+        if constexpr (form < 2) load_slopes(slope_v);
+        const bool okx[2] = {ex < a.W, ex + 16 < a.W};
 #pragma unroll
         for (int r = 0; r < MB; ++r) {
-          const int y = cur_y0 + rgp * MB + r;
+          const bool oky = ey0 + r < a.H;
+          const size_t srow = row_off(ey0 + r);
 #pragma unroll
           for (int hn = 0; hn < 2; ++hn) {
-            const int x = cur_x0 + 16 * hn + n16;
-            const bool ok = y < a.H && x < a.W;
-            const size_t rec = (((size_t)cur_n * a.H + y) * a.W + x) * REC;
             float v[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -327,56 +350,65 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3x3_w16_kernel(const ConvArgs 
               else if constexpr (form == 1) {
                 const float st = t * slope_v[i];
                 asm("v_max_f32 %0, %1, %2" : "=v"(u) : "v"(t), "v"(st));   // = fmaxf(t, st) for every non-NaN input, one instruction
-              } else u = __builtin_amdgcn_fmed3f(t, 0.f, 6.f);
+              } else if constexpr (form == 2) u = __builtin_amdgcn_fmed3f(t, 0.f, 6.f);
+              else u = t;
               v[i] = alpha1 ? u : u * alpha;
             }
-            if (ok) store8<__half>(outp + rec, v);
+            if (oky && okx[hn]) store8<__half>(outp + (size_t)(ex + 16 * hn) * REC + srow, v);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
       };
-      // Residual epilogues (any activation, then * alpha + res1, * gamma + res2; absent residuals add nothing).  The residual records of
-      // FOUR rows (two with both residuals) are requested together, unconditionally (coordinates clamped into the image: a load under a branch makes hipcc wait with
+      // Residual epilogues (the activation, then * alpha + res1, * gamma + res2).  The residual records of FOUR rows (two with both
+      // residuals) are requested together, unconditionally (coordinates clamped into the image: a load under a branch makes hipcc wait with
       // vmcnt(0) right behind it - sixteen exposed round trips per tile, + 12 % on conv5 of every third RDB), then the four rows are stored.
-      auto stores_res = [&](auto R1T, auto R2T) {
+      // An absent residual has no registers and no conversions; its step stays an fma with a +0 addend (what adding its zeros compiled
+      // to, and the price of a multiply): t * alpha + 0 turns a -0 product into +0, and the sign of a zero result of the next step can
+      // depend on that.  Forms 0 and 1 as above (the residual epilogue evaluated the select for every activation: form 1 is its value
+      // whenever the slopes are in [0, 1]); 2: ReLU6 as (t >= 0 ? t : t * 0) then min(., 6) - the -0 of a negative t kept; 3: none.
+      auto stores_res = [&](auto R1T, auto R2T, auto FORM) {
         constexpr bool R1 = decltype(R1T)::value, R2 = decltype(R2T)::value;
+        constexpr int form = decltype(FORM)::value;
         constexpr int RB = (R1 && R2) ? 2 : 4;   // rows per request: 8 registers per row and residual next to 128 accumulators
+        float slope_v[8];
+        if constexpr (form < 2) load_slopes(slope_v);
+        const bool okx[2] = {ex < a.W, ex + 16 < a.W};
 #pragma unroll
         for (int r0 = 0; r0 < MB; r0 += RB) {
-          uint4 q1[RB][2], q2[RB][2];
+          uint4 q1[R1 ? RB : 1][2], q2[R2 ? RB : 1][2];
 #pragma unroll
-          for (int rr = 0; rr < RB; ++rr)
+          for (int rr = 0; rr < RB; ++rr) {
+            const size_t srowc = row_off(min(ey0 + r0 + rr, a.H - 1));
 #pragma unroll
             for (int hn = 0; hn < 2; ++hn) {
-              const int yc = min(cur_y0 + rgp * MB + r0 + rr, a.H - 1), xc = min(cur_x0 + 16 * hn + n16, a.W - 1);
-              const size_t recc = (((size_t)cur_n * a.H + yc) * a.W + xc) * REC;
-              if constexpr (R1) q1[rr][hn] = *reinterpret_cast<const uint4*>(r1p + recc);
-              if constexpr (R2) q2[rr][hn] = *reinterpret_cast<const uint4*>(r2p + recc);
+              const size_t xrec = (size_t)min(ex + 16 * hn, a.W - 1) * REC;
+              if constexpr (R1) q1[rr][hn] = *reinterpret_cast<const uint4*>(r1p + xrec + srowc);
+              if constexpr (R2) q2[rr][hn] = *reinterpret_cast<const uint4*>(r2p + xrec + srowc);
             }
+          }
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int rr = 0; rr < RB; ++rr) {
-            const int r = r0 + rr, y = cur_y0 + rgp * MB + r;
+            const int r = r0 + rr;
+            const bool oky = ey0 + r < a.H;
+            const size_t srow = row_off(ey0 + r);
 #pragma unroll
             for (int hn = 0; hn < 2; ++hn) {
-              const int x = cur_x0 + 16 * hn + n16;
-              const bool ok = y < a.H && x < a.W;
-              const size_t rec = (((size_t)cur_n * a.H + y) * a.W + x) * REC;
-              float r1[8], r2[8], v[8];
-#pragma unroll
-              for (int i = 0; i < 8; ++i) { r1[i] = 0.f; r2[i] = 0.f; }
+              float r1[R1 ? 8 : 1], r2[R2 ? 8 : 1], v[8];
               if constexpr (R1) load8<__half>(reinterpret_cast<const char*>(&q1[rr][hn]), r1);
               if constexpr (R2) load8<__half>(reinterpret_cast<const char*>(&q2[rr][hn]), r2);
 #pragma unroll
               for (int i = 0; i < 8; ++i) {
                 float t = i < 4 ? acc[r][hn][0][i] : acc[r][hn][1][i - 4];
-                const float neg = t * slope_v[i];
-                t = t >= 0.f ? t : neg;
-                if (a.act == ACT_RELU6) t = fminf(t, 6.f);
-                t = t * alpha + r1[i];
-                v[i] = t * gamma + r2[i];   // (conv_dense.hip's wide kernel, the same expressions)
+                if constexpr (form == 0) { const float neg = t * slope_v[i]; t = t >= 0.f ? t : neg; }
+                else if constexpr (form == 1) {
+                  const float st = t * slope_v[i];
+                  asm("v_max_f32 %0, %1, %2" : "=v"(t) : "v"(t), "v"(st));
+                } else if constexpr (form == 2) { const float neg = t * 0.f; t = fminf(t >= 0.f ? t : neg, 6.f); }
+                if constexpr (R1) t = t * alpha + r1[i]; else t = t * alpha + 0.f;
+                if constexpr (R2) v[i] = t * gamma + r2[i]; else v[i] = t * gamma + 0.f;
               }
-              if (ok) store8<__half>(outp + rec, v);
+              if (oky && okx[hn]) store8<__half>(outp + (size_t)(ex + 16 * hn) * REC + srow, v);
             }
           }
           __builtin_amdgcn_sched_barrier(0);
@@ -385,12 +417,115 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3x3_w16_kernel(const ConvArgs 
       // PReLU with every slope of the layer <= 1 (host-checked, ConvArgs.prelu_le1): t >= 0 ? t : t s  ==  max(t, t s), one instruction less per value
       const bool max_form = a.act != ACT_PRELU || a.prelu_le1;
       const bool a1 = alpha == 1.f;
-      if (r1p && r2p) stores_res(std::true_type{}, std::true_type{});
-      else if (r1p) stores_res(std::true_type{}, std::false_type{});
-      else if (r2p) stores_res(std::false_type{}, std::true_type{});
-      else if (a.act == ACT_RELU6) stores(std::integral_constant<int, 2>{}, std::false_type{});
-      else if (max_form) { if (a1) stores(std::integral_constant<int, 1>{}, std::true_type{}); else stores(std::integral_constant<int, 1>{}, std::false_type{}); }
-      else { if (a1) stores(std::integral_constant<int, 0>{}, std::true_type{}); else stores(std::integral_constant<int, 0>{}, std::false_type{}); }
+#ifdef SS4K_DEV
+      if constexpr (GEN) {   // the generic epilogues, as they were
+        float slope_v[8];
+        load_slopes(slope_v);
+        auto stores_gen = [&](auto FORM, auto ALPHA1) {
+          constexpr int form = decltype(FORM)::value;
+          constexpr bool alpha1 = decltype(ALPHA1)::value;
+#pragma unroll
+          for (int r = 0; r < MB; ++r) {
+            const int y = cur_y0 + rgp * MB + r;
+#pragma unroll
+            for (int hn = 0; hn < 2; ++hn) {
+              const int x = cur_x0 + 16 * hn + n16;
+              const bool ok = y < a.H && x < a.W;
+              const size_t rec = (((size_t)cur_n * a.H + y) * a.W + x) * REC;
+              float v[8];
+#pragma unroll
+              for (int i = 0; i < 8; ++i) {
+                const float t = i < 4 ? acc[r][hn][0][i] : acc[r][hn][1][i - 4];
+                float u;
+                if constexpr (form == 0) { const float neg = t * slope_v[i]; u = t >= 0.f ? t : neg; }
+                else if constexpr (form == 1) {
+                  const float st = t * slope_v[i];
+                  asm("v_max_f32 %0, %1, %2" : "=v"(u) : "v"(t), "v"(st));   // = fmaxf(t, st) for every non-NaN input, one instruction
+                } else u = __builtin_amdgcn_fmed3f(t, 0.f, 6.f);
+                v[i] = alpha1 ? u : u * alpha;
+              }
+              if (ok) store8<__half>(outp + rec, v);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        };
+        // Residual epilogues (any activation, then * alpha + res1, * gamma + res2; absent residuals add nothing).  The residual records of
+        // FOUR rows (two with both residuals) are requested together, unconditionally (coordinates clamped into the image: a load under a branch makes hipcc wait with
+        // vmcnt(0) right behind it - sixteen exposed round trips per tile, + 12 % on conv5 of every third RDB), then the four rows are stored.
+        auto stores_res_gen = [&](auto R1T, auto R2T) {
+          constexpr bool R1 = decltype(R1T)::value, R2 = decltype(R2T)::value;
+          constexpr int RB = (R1 && R2) ? 2 : 4;   // rows per request: 8 registers per row and residual next to 128 accumulators
+#pragma unroll
+          for (int r0 = 0; r0 < MB; r0 += RB) {
+            uint4 q1[RB][2], q2[RB][2];
+#pragma unroll
+            for (int rr = 0; rr < RB; ++rr)
+#pragma unroll
+              for (int hn = 0; hn < 2; ++hn) {
+                const int yc = min(cur_y0 + rgp * MB + r0 + rr, a.H - 1), xc = min(cur_x0 + 16 * hn + n16, a.W - 1);
+                const size_t recc = (((size_t)cur_n * a.H + yc) * a.W + xc) * REC;
+                if constexpr (R1) q1[rr][hn] = *reinterpret_cast<const uint4*>(r1p + recc);
+                if constexpr (R2) q2[rr][hn] = *reinterpret_cast<const uint4*>(r2p + recc);
+              }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int rr = 0; rr < RB; ++rr) {
+              const int r = r0 + rr, y = cur_y0 + rgp * MB + r;
+#pragma unroll
+              for (int hn = 0; hn < 2; ++hn) {
+                const int x = cur_x0 + 16 * hn + n16;
+                const bool ok = y < a.H && x < a.W;
+                const size_t rec = (((size_t)cur_n * a.H + y) * a.W + x) * REC;
+                float r1[8], r2[8], v[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) { r1[i] = 0.f; r2[i] = 0.f; }
+                if constexpr (R1) load8<__half>(reinterpret_cast<const char*>(&q1[rr][hn]), r1);
+                if constexpr (R2) load8<__half>(reinterpret_cast<const char*>(&q2[rr][hn]), r2);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                  float t = i < 4 ? acc[r][hn][0][i] : acc[r][hn][1][i - 4];
+                  const float neg = t * slope_v[i];
+                  t = t >= 0.f ? t : neg;
+                  if (a.act == ACT_RELU6) t = fminf(t, 6.f);
+                  t = t * alpha + r1[i];
+                  v[i] = t * gamma + r2[i];   // (conv_dense.hip's wide kernel, the same expressions)
+                }
+                if (ok) store8<__half>(outp + rec, v);
+              }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        };
+        if (r1p && r2p) stores_res_gen(std::true_type{}, std::true_type{});
+        else if (r1p) stores_res_gen(std::true_type{}, std::false_type{});
+        else if (r2p) stores_res_gen(std::false_type{}, std::true_type{});
+        else if (a.act == ACT_RELU6) stores_gen(std::integral_constant<int, 2>{}, std::false_type{});
+        else if (max_form) { if (a1) stores_gen(std::integral_constant<int, 1>{}, std::true_type{}); else stores_gen(std::integral_constant<int, 1>{}, std::false_type{}); }
+        else { if (a1) stores_gen(std::integral_constant<int, 0>{}, std::true_type{}); else stores_gen(std::integral_constant<int, 0>{}, std::false_type{}); }
+      }
+#endif
+      if constexpr (!GEN) {
+        using T = std::true_type; using F = std::false_type;
+        auto plain = [&](auto FORM) { if (a1) stores(FORM, T{}); else stores(FORM, F{}); };
+        auto res = [&](auto FORM) {
+          if (r1p && r2p) stores_res(T{}, T{}, FORM);
+          else if (r1p) stores_res(T{}, F{}, FORM);
+          else stores_res(F{}, T{}, FORM);
+        };
+        std::integral_constant<int, 0> f_select; std::integral_constant<int, 1> f_max; std::integral_constant<int, 2> f_relu6; std::integral_constant<int, 3> f_none;
+        if constexpr (RL) {   // (launch condition: no activation; res1 went through the matrix core)
+          if (r2p) stores_res(F{}, T{}, f_none); else plain(f_none);
+        } else {
+          const bool resid = r1p || r2p;
+          // the residual epilogue's select equals the maximum when the slopes are in [0, 1]
+          const bool max_res = a.act == ACT_LRELU ? (a.slope >= 0.f && a.slope <= 1.f) : a.prelu_le1;
+          if (a.act == ACT_NONE) { if (resid) res(f_none); else plain(f_none); }
+          else if (a.act == ACT_RELU6) { if (resid) res(f_relu6); else stores(f_relu6, F{}); }
+          else if (resid) { if (max_res) res(f_max); else res(f_select); }
+          else if (max_form) plain(f_max);
+          else plain(f_select);
+        }
+      }
     }
     stamp(5);
     if (next_tile < 0) break;
@@ -429,16 +564,21 @@ void launch_conv3x3_w16(ss4k_ctx* ctx, const ConvArgs& a0, hipStream_t st) {
                   a.res1 + (size_t)a.r1_plane0 * a.r1_plane_bytes == a.in0 + (size_t)a.in0_plane0 * a.in0_plane_bytes &&
                   a.r1_plane_bytes == a.in0_plane_bytes;
 #ifdef SS4K_DEV
+  // SS4K_EPI_GENERIC=1: the builds with the generic epilogue (the GEN builds of the kernel), for A/B runs and the bit-identity tests
+  static const bool epi_generic = std::getenv("SS4K_EPI_GENERIC") && std::getenv("SS4K_EPI_GENERIC")[0] == '1';
   static const bool stamp_mode = std::getenv("SS4K_W16_STAMP") && std::getenv("SS4K_W16_STAMP")[0] == '1';
   if (stamp_mode) {   // cycle counters of every wave of the first 1024 workgroups of cout group 0
     static unsigned long long* dbuf = nullptr;
     if (!dbuf) SS4K_HIP(hipMalloc(reinterpret_cast<void**>(&dbuf), 1024 * 4 * 8 * 8));
     SS4K_HIP(hipMemsetAsync(dbuf, 0, 1024 * 4 * 8 * 8, st));
     a.dbg_buf = dbuf;
-    const void* fs = rl ? reinterpret_cast<const void*>(&conv3x3_w16_kernel<true, true>) : reinterpret_cast<const void*>(&conv3x3_w16_kernel<true, false>);
-    if (ctx->lds_attr_set.insert(fs).second) SS4K_HIP(hipFuncSetAttribute(fs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-    if (rl) hipLaunchKernelGGL((conv3x3_w16_kernel<true, true>), dim3(gx, groups), dim3(64 * NW), LDS_BYTES, st, a);
-    else hipLaunchKernelGGL((conv3x3_w16_kernel<true, false>), dim3(gx, groups), dim3(64 * NW), LDS_BYTES, st, a);
+    auto gos = [&](auto kern) {
+      const void* fs = reinterpret_cast<const void*>(kern);
+      if (ctx->lds_attr_set.insert(fs).second) SS4K_HIP(hipFuncSetAttribute(fs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
+      hipLaunchKernelGGL(kern, dim3(gx, groups), dim3(64 * NW), LDS_BYTES, st, a);
+    };
+    if (rl) gos(&conv3x3_w16_kernel<true, true>);   // (the stamped builds carry the specialised epilogue only)
+    else gos(&conv3x3_w16_kernel<true, false>);
     SS4K_HIP(hipStreamSynchronize(st));
     std::vector<unsigned long long> hb(1024 * 4 * 8);
     SS4K_HIP(hipMemcpy(hb.data(), dbuf, hb.size() * 8, hipMemcpyDeviceToHost));
@@ -460,13 +600,23 @@ void launch_conv3x3_w16(ss4k_ctx* ctx, const ConvArgs& a0, hipStream_t st) {
     return;
   }
 #endif
-  const void* fn = rl ? reinterpret_cast<const void*>(&conv3x3_w16_kernel<false, true>) : reinterpret_cast<const void*>(&conv3x3_w16_kernel<false, false>);
-  if (ctx->lds_attr_set.insert(fn).second)
-    SS4K_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
+  auto go = [&](auto kern) {
+    const void* fn = reinterpret_cast<const void*>(kern);
+    if (ctx->lds_attr_set.insert(fn).second)
+      SS4K_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
+    hipLaunchKernelGGL(kern, dim3(gx, groups), dim3(64 * NW), LDS_BYTES, st, a);
+  };
   ctx->prof_family = rl ? "w16::conv3x3_w16_kernel<RL> (64-cout tile, 16x16x32 MFMA, residual through the matrix core: conv5 of an RDB)"
                         : "w16::conv3x3_w16_kernel (64-cout tile, 16x16x32 MFMA)";
-  if (rl) hipLaunchKernelGGL((conv3x3_w16_kernel<false, true>), dim3(gx, groups), dim3(64 * NW), LDS_BYTES, st, a);
-  else hipLaunchKernelGGL((conv3x3_w16_kernel<false, false>), dim3(gx, groups), dim3(64 * NW), LDS_BYTES, st, a);
+#ifdef SS4K_DEV
+  if (epi_generic) {
+    if (rl) go(&conv3x3_w16_kernel<false, true, true>); else go(&conv3x3_w16_kernel<false, false, true>);
+    SS4K_HIP(hipGetLastError());
+    return;
+  }
+#endif
+  if (rl) go(&conv3x3_w16_kernel<false, true>);
+  else go(&conv3x3_w16_kernel<false, false>);
   SS4K_HIP(hipGetLastError());
 }
 
