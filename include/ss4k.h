@@ -231,6 +231,63 @@ int ss4k_op_cv_area_shape(int h, int w, double fx, double fy, int* out_h, int* o
 int ss4k_op_cv_area_resize_u8(ss4k_ctx* ctx, const uint8_t* in_nhwc_dev, uint8_t* out_nhwc_dev, size_t out_capacity_bytes, int n, int h, int w,
                               int channels, double fx, double fy, void* hip_stream);
 
+/* ---- the frame-recurrent upscaler: EGVSR's FRNet x4 (model/egvsr/egvsr.py:146-212), the network behind EgvsrUpscalerService
+ * (egvsr_upscaler.py:145-212).  An object of its own, not a model kind: a step takes three tensors and frame t needs frame t - 1's output,
+ * so there are no frame lanes and no job sets.  FRNet(in_nc=3, out_nc=3, nf=num_feat, nb=num_block, degradation='BD', scale=4)
+ * (egvsr_upscaler.py:26): FNet (egvsr.py:12-78), 4 x BicubicUpsample(4) of the flow (utils/net_utils.py:112-165), backward_warp of the previous
+ * output (net_utils.py:50-93), space-to-depth (egvsr.py:203-208), SRNet (egvsr.py:99-143).  SS4K_F16: fp16 activations with fp32 accumulation;
+ * the flow, hr_prev and hr_curr stay fp32 in both dtypes. */
+typedef struct ss4k_frvsr ss4k_frvsr;
+typedef struct ss4k_frvsr_upscaler ss4k_frvsr_upscaler;
+typedef struct ss4k_frvsr_desc {
+  int32_t dtype;       /* ss4k_dtype */
+  int32_t num_feat;    /* nf: SRNet's tail is PixelShuffle(4) + Conv2d(4, 3) (egvsr.py:122-127), which fixes nf = 64; anything else is refused */
+  int32_t num_block;   /* nb: residual blocks, 0..SS4K_DESC_MAX_BLOCKS (the service: 10) */
+  int32_t flags;       /* must be 0 */
+  int32_t reserved[4];
+} ss4k_frvsr_desc;
+/* fp32 scalars of FRNet's state_dict, flattened in state_dict order like every other model's blob: it INCLUDES the entries forward() never
+ * uses (upsample_func.kernels, srnet.conv_up.*, srnet.upsample_func.kernels: skipped).  2 587 505 at 64 / 10.  Host only; 0 for a bad desc. */
+size_t ss4k_frvsr_param_count(const ss4k_frvsr_desc* desc);
+/* Replaces build_egvsr_model's FRNet(...) + load_state_dict (egvsr_upscaler.py:25-29) */
+int ss4k_frvsr_create(ss4k_ctx* ctx, const ss4k_frvsr_desc* desc, const float* host_weights, size_t n_floats, ss4k_frvsr** out);
+void ss4k_frvsr_destroy(ss4k_frvsr* m);
+/* Replaces `self.model(lr_curr, self.lr_prev, self.hr_prev)` (egvsr_upscaler.py:204) = FRNet.forward (egvsr.py:180-212): lr_curr, lr_prev
+ * (n, 3, h, w), hr_prev (n, 3, 4 h, 4 w) -> hr_out (n, 3, 4 h, 4 w), contiguous fp32 NCHW on the device; the n items are independent streams.
+ * Stateless.  h, w >= 8 (the reference's reflect pad fails below that): SS4K_EINVAL otherwise. */
+int ss4k_frvsr_step(ss4k_frvsr* m, const float* lr_curr_dev, const float* lr_prev_dev, const float* hr_prev_dev, float* hr_out_dev, int n, int h,
+                    int w, void* hip_stream);
+/* Device bytes of workspace the object holds after a step of n x h x w (nothing is allocated or launched) */
+int ss4k_frvsr_workspace_bytes(ss4k_frvsr* m, int n, int h, int w, size_t* bytes);
+/* Per-stage time of the steps since the last enable(1), from events on the caller's stream (tools/frvsr_time.py): stage 0 = FNet convs, 1 = SRNet
+ * convs, 2 = pool and x2, 3 = flow finish (tanh, pad), 4 = flow x4 + warp + space-to-depth, 5 = tail, 6 = the rest (input packing, service glue).
+ * ss4k_frvsr_prof_read synchronises with the recorded events. */
+int ss4k_frvsr_prof_enable(ss4k_frvsr* m, int enable);
+int ss4k_frvsr_prof_read(ss4k_frvsr* m, int stage, double* total_ms);
+
+/* The service path.  Replaces EgvsrUpscalerService.proc_init / upscale (egvsr_upscaler.py:159-212): lr_shape = (lr_h, lr_w), output_shape =
+ * (out_h, out_w), 0, 0 = None.  The n frames of ss4k_frvsr_upscale_frames are CONSECUTIVE FRAMES OF ONE STREAM, processed in order (:182-186); the
+ * state (lr_prev, hr_prev) is carried across calls, so a stream must stay on one object.  Per frame (:192-212): / 255, area to lr_shape, step, the state
+ * keeps the unclamped output, clamp to [0, 1], F.interpolate(mode='area') to the output shape if set, * 255 truncated to uint8 HWC. */
+int ss4k_frvsr_upscaler_create(ss4k_ctx* ctx, ss4k_frvsr* m, int lr_h, int lr_w, int out_h, int out_w, ss4k_frvsr_upscaler** out);
+void ss4k_frvsr_upscaler_destroy(ss4k_frvsr_upscaler* up);
+/* the next frame sees zero lr_prev / hr_prev (egvsr_upscaler.py:197-202) */
+int ss4k_frvsr_upscaler_reset(ss4k_frvsr_upscaler* up);
+int ss4k_frvsr_upscaler_out_shape(const ss4k_frvsr_upscaler* up, int* out_h, int* out_w);
+int ss4k_frvsr_upscale_frames(ss4k_frvsr_upscaler* up, const uint8_t* in_nhwc_dev, int n, int h, int w, uint8_t* out_nhwc_dev,
+                              size_t out_capacity_bytes, void* hip_stream);
+/* Parity taps of the LAST frame of the last call, fp32 NCHW: 0 = lr_curr, 1 = lr flow (padded, (1, 2, h, w)), 2 = the warped and space-to-depth
+ * tensor (1, 48, h, w), 3 = hr_curr (unclamped).  As ss4k_upscaler_enable_taps / _read_tap. */
+int ss4k_frvsr_upscaler_enable_taps(ss4k_frvsr_upscaler* up, int enable);
+int ss4k_frvsr_upscaler_read_tap(ss4k_frvsr_upscaler* up, int which, float* out_dev, size_t capacity_floats, int dims[4], void* hip_stream);
+
+/* backward_warp(x, flow) (utils/net_utils.py:50-93): grid_sample(bilinear, padding_mode='border', align_corners=True) at linspace(-1, 1) +
+ * flow / ((size - 1) / 2).  x (n, c, h, w), flow (n, 2, h, w) (channel 0 = x displacement in pixels), out (n, c, h, w); h, w >= 2 */
+int ss4k_op_backward_warp(ss4k_ctx* ctx, const float* x_dev, const float* flow_dev, float* out_dev, int n, int c, int h, int w, void* hip_stream);
+/* BicubicUpsample(4)(input) (utils/net_utils.py:112-165): replicate pad (1, 2, 1, 2), four 4-tap phase kernels of the cubic with a = -0.75, height
+ * pass then width pass - NOT F.interpolate's bicubic.  (planes, h, w) -> (planes, 4 h, 4 w) */
+int ss4k_op_bicubic_upsample4(ss4k_ctx* ctx, const float* in_dev, float* out_dev, int planes, int h, int w, void* hip_stream);
+
 /* ---- measurement hooks (bench.py: live per-kernel timing with HIP events on the launch stream) */
 /* When enabled, every launch of the dominant conv kernel is bracketed with hipEvents on the
  * stream it is launched on; ss4k_prof_read returns (#launches, total ms, algorithmic FLOPs). */

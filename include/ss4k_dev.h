@@ -92,6 +92,9 @@ int ss4k_dev_guard_check(int* guarded, int* unguarded, int* damaged, char* text,
  * activations, an upscaler's intermediates and taps, a context's named scratch other than the zero page and the cv-area tables.
  * buffers / bytes: what was filled; bytes_256: the same sizes, each rounded up to 256 (what the product library allocates for them). */
 int ss4k_dev_guard_poison(ss4k_ctx* ctx, ss4k_model* model, ss4k_upscaler* upscaler, int* buffers, size_t* bytes, size_t* bytes_256);
+/* ... the same for the frame-recurrent upscaler (include/ss4k.h, ss4k_frvsr_*; each may be NULL): the executor's activations, flow buffers
+ * and tap, the service path's staging buffers.  The recurrent state (lr_prev / hr_prev) is NOT transient: the next frame is entitled to it. */
+int ss4k_dev_guard_poison_frvsr(ss4k_frvsr* m, ss4k_frvsr_upscaler* up, int* buffers, size_t* bytes, size_t* bytes_256);
 /* Positive control without a fault: allocates a guarded buffer, writes one byte at payload - 1 and one at payload + need with hipMemset
  * (both inside the allocation), requires the check to report exactly those two zones with those offsets, releases the buffer and clears
  * the sticky list.  SS4K_EINVAL with a text if the guard does not see them (or if damage was already on record: run it first). */

@@ -29,6 +29,10 @@ SYMBOLS = [
     "ss4k_op_bilinear_resize", "ss4k_op_depthwise_reflect", "ss4k_op_plane_stats", "ss4k_op_f32nchw_to_u8nhwc",
     "ss4k_prof_enable", "ss4k_prof_reset", "ss4k_prof_read", "ss4k_prof_read_kind", "ss4k_prof_read_family", "ss4k_prof_read_section_ms",
     "ss4k_stream_pair_check", "ss4k_op_cv_area_shape", "ss4k_op_cv_area_resize_u8",
+    "ss4k_frvsr_param_count", "ss4k_frvsr_create", "ss4k_frvsr_destroy", "ss4k_frvsr_step", "ss4k_frvsr_workspace_bytes",
+    "ss4k_frvsr_prof_enable", "ss4k_frvsr_prof_read", "ss4k_frvsr_upscaler_create", "ss4k_frvsr_upscaler_destroy",
+    "ss4k_frvsr_upscaler_reset", "ss4k_frvsr_upscaler_out_shape", "ss4k_frvsr_upscale_frames", "ss4k_frvsr_upscaler_enable_taps",
+    "ss4k_frvsr_upscaler_read_tap", "ss4k_op_backward_warp", "ss4k_op_bicubic_upsample4",
 ]
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
@@ -41,7 +45,7 @@ DEV_SYMBOLS = [
     "ss4k_dev_op_ps_nchw_addbase", "ss4k_dev_op_pack_input", "ss4k_dev_op_temporal_shift",
     "ss4k_dev_glue_routes_reset", "ss4k_dev_glue_routes_read",
     # guard mode: red zones and 0xFF poison for every device buffer of the library (tests/test_gpu_memory_hygiene.py)
-    "ss4k_dev_guard_enable", "ss4k_dev_guard_check", "ss4k_dev_guard_poison", "ss4k_dev_guard_selftest",
+    "ss4k_dev_guard_enable", "ss4k_dev_guard_check", "ss4k_dev_guard_poison", "ss4k_dev_guard_selftest", "ss4k_dev_guard_poison_frvsr",
 ]
 
 
@@ -63,6 +67,11 @@ class UpscaleCfg(C.Structure):
                 ("lr_hr_resize", C.c_int32), ("single_mode", C.c_int32), ("sr_is_realesrgan", C.c_int32),
                 ("denoising", C.c_int32), ("reserved0", C.c_int32), ("denoise_rate", C.c_double),
                 ("reserved", C.c_int32 * 6)]
+
+
+class FrvsrDesc(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("num_feat", C.c_int32), ("num_block", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
 
 
 class Ss4kError(RuntimeError):
@@ -147,6 +156,8 @@ def load(path: str) -> C.CDLL:
         L.ss4k_dev_guard_check.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), C.c_char_p, sz]
         L.ss4k_dev_guard_poison.argtypes = [vp, vp, vp, C.POINTER(i), C.POINTER(sz), C.POINTER(sz)]
         L.ss4k_dev_guard_selftest.argtypes = [vp]
+        if hasattr(L, "ss4k_dev_guard_poison_frvsr"):
+            L.ss4k_dev_guard_poison_frvsr.argtypes = [vp, vp, C.POINTER(i), C.POINTER(sz), C.POINTER(sz)]
     L.ss4k_prof_enable.argtypes = [vp, i]
     L.ss4k_prof_reset.argtypes = [vp]
     L.ss4k_prof_read.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -158,6 +169,23 @@ def load(path: str) -> C.CDLL:
     L.ss4k_stream_pair_check.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
     L.ss4k_op_cv_area_shape.argtypes = [i, i, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.ss4k_op_cv_area_resize_u8.argtypes = [vp, vp, vp, sz, i, i, i, i, C.c_double, C.c_double, vp]
+    if hasattr(L, "ss4k_frvsr_create"):   # (absent from older builds, which tools/lib_ab.py loads for A/B timing)
+        L.ss4k_frvsr_param_count.argtypes = [C.POINTER(FrvsrDesc)]; L.ss4k_frvsr_param_count.restype = sz
+        L.ss4k_frvsr_create.argtypes = [vp, C.POINTER(FrvsrDesc), vp, sz, C.POINTER(vp)]
+        L.ss4k_frvsr_destroy.argtypes = [vp]; L.ss4k_frvsr_destroy.restype = None
+        L.ss4k_frvsr_step.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp]
+        L.ss4k_frvsr_workspace_bytes.argtypes = [vp, i, i, i, C.POINTER(C.c_size_t)]
+        L.ss4k_frvsr_prof_enable.argtypes = [vp, i]
+        L.ss4k_frvsr_prof_read.argtypes = [vp, i, C.POINTER(C.c_double)]
+        L.ss4k_frvsr_upscaler_create.argtypes = [vp, vp, i, i, i, i, C.POINTER(vp)]
+        L.ss4k_frvsr_upscaler_destroy.argtypes = [vp]; L.ss4k_frvsr_upscaler_destroy.restype = None
+        L.ss4k_frvsr_upscaler_reset.argtypes = [vp]
+        L.ss4k_frvsr_upscaler_out_shape.argtypes = [vp, C.POINTER(i), C.POINTER(i)]
+        L.ss4k_frvsr_upscale_frames.argtypes = [vp, vp, i, i, i, vp, sz, vp]
+        L.ss4k_frvsr_upscaler_enable_taps.argtypes = [vp, i]
+        L.ss4k_frvsr_upscaler_read_tap.argtypes = [vp, i, vp, sz, C.POINTER(i * 4), vp]
+        L.ss4k_op_backward_warp.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
+        L.ss4k_op_bicubic_upsample4.argtypes = [vp, vp, vp, i, i, i, vp]
     return L
 
 
@@ -205,6 +233,15 @@ def guard_poison(ctx=None, model=None, upscaler=None, L: Optional[C.CDLL] = None
     h = [getattr(o, "_h", o) for o in (ctx, model, upscaler)]
     n, b, b256 = C.c_int(), C.c_size_t(), C.c_size_t()
     _guard_rc(L, L.ss4k_dev_guard_poison(*h, C.byref(n), C.byref(b), C.byref(b256)))
+    return n.value, int(b.value), int(b256.value)
+
+
+def guard_poison_frvsr(model=None, upscaler=None, L: Optional[C.CDLL] = None) -> Tuple[int, int, int]:
+    """``guard_poison`` for a ``Frvsr`` and / or a ``FrvsrUpscaler``; the recurrent state is left alone."""
+    L = _guard_lib(L)
+    h = [getattr(o, "_h", o) for o in (model, upscaler)]
+    n, b, b256 = C.c_int(), C.c_size_t(), C.c_size_t()
+    _guard_rc(L, L.ss4k_dev_guard_poison_frvsr(*h, C.byref(n), C.byref(b), C.byref(b256)))
     return n.value, int(b.value), int(b256.value)
 
 
@@ -355,6 +392,23 @@ class Context:
         n, c, h, w = x.shape
         out = torch.empty((n, c, 2), dtype=torch.float32, device=x.device)
         _check(lib().ss4k_op_plane_stats(self._h, x.data_ptr(), out.data_ptr(), n * c, h * w, _stream()))
+        return out
+
+    def backward_warp(self, x, flow):
+        """``backward_warp(x, flow)`` (utils/net_utils.py:50-93): x (n, c, h, w), flow (n, 2, h, w)."""
+        self._f32(x); self._f32(flow)
+        n, c, h, w = x.shape
+        assert tuple(flow.shape) == (n, 2, h, w)
+        out = torch.empty_like(x)
+        _check(lib().ss4k_op_backward_warp(self._h, x.data_ptr(), flow.data_ptr(), out.data_ptr(), n, c, h, w, _stream()))
+        return out
+
+    def bicubic_upsample4(self, x):
+        """``BicubicUpsample(4)(x)`` (utils/net_utils.py:112-165)."""
+        self._f32(x)
+        n, c, h, w = x.shape
+        out = torch.empty((n, c, 4 * h, 4 * w), dtype=torch.float32, device=x.device)
+        _check(lib().ss4k_op_bicubic_upsample4(self._h, x.data_ptr(), out.data_ptr(), n * c, h, w, _stream()))
         return out
 
     def f32nchw_to_u8nhwc(self, x):
@@ -513,4 +567,124 @@ class Upscaler:
             out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
         with torch.cuda.device(self.ctx.device):
             _check(lib().ss4k_upscale_frames(self._h, frames.data_ptr(), n, h, w, out.data_ptr(), out.numel(), _stream()))
+        return out
+
+
+FRV_STAGES = ("fnet_conv", "srnet_conv", "pool_up", "flow_finish", "warp", "tail", "glue")
+
+
+def make_frvsr_desc(dtype: int = F32, num_feat: int = 64, num_block: int = 10, flags: int = 0) -> FrvsrDesc:
+    d = FrvsrDesc()
+    d.dtype, d.num_feat, d.num_block, d.flags = dtype, num_feat, num_block, int(flags)
+    return d
+
+
+def frvsr_param_count(desc: FrvsrDesc) -> int:
+    return int(lib().ss4k_frvsr_param_count(C.byref(desc)))
+
+
+class Frvsr:
+    """ss4k_frvsr: EGVSR's FRNet x4 resident on one GPU; callable like the reference's ``self.model(lr_curr, lr_prev, hr_prev)``
+    (egvsr_upscaler.py:204)."""
+
+    def __init__(self, ctx: Context, desc: FrvsrDesc, flat_weights: np.ndarray):
+        self.ctx, self.desc = ctx, desc
+        w = np.ascontiguousarray(flat_weights, dtype=np.float32)
+        h = C.c_void_p()
+        with torch.cuda.device(ctx.device):
+            _check(lib().ss4k_frvsr_create(ctx._h, C.byref(desc), w.ctypes.data_as(C.c_void_p), w.size, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().ss4k_frvsr_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def workspace_bytes(self, n, h, w) -> int:
+        b = C.c_size_t()
+        _check(lib().ss4k_frvsr_workspace_bytes(self._h, n, h, w, C.byref(b)))
+        return int(b.value)
+
+    def prof_enable(self, on: bool = True):
+        _check(lib().ss4k_frvsr_prof_enable(self._h, int(on)))
+
+    def prof_read(self) -> dict:
+        """{stage: total ms since prof_enable(True)}; waits for the recorded events."""
+        out = {}
+        for k, name in enumerate(FRV_STAGES):
+            ms = C.c_double()
+            _check(lib().ss4k_frvsr_prof_read(self._h, k, C.byref(ms)))
+            out[name] = ms.value
+        return out
+
+    def __call__(self, lr_curr: torch.Tensor, lr_prev: torch.Tensor, hr_prev: torch.Tensor) -> torch.Tensor:
+        dev = self.ctx.device
+        lr_curr, lr_prev, hr_prev = (t.to(device=dev, dtype=torch.float32).contiguous() for t in (lr_curr, lr_prev, hr_prev))
+        n, c, h, w = lr_curr.shape
+        assert c == 3 and tuple(lr_prev.shape) == (n, 3, h, w) and tuple(hr_prev.shape) == (n, 3, 4 * h, 4 * w), "FRNet.forward shapes"
+        out = torch.empty((n, 3, 4 * h, 4 * w), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _check(lib().ss4k_frvsr_step(self._h, lr_curr.data_ptr(), lr_prev.data_ptr(), hr_prev.data_ptr(), out.data_ptr(), n, h, w, _stream()))
+        return out
+
+    forward = __call__
+
+    def eval(self):
+        return self
+
+
+class FrvsrUpscaler:
+    """ss4k_frvsr_upscaler: EgvsrUpscalerService.upscale (egvsr_upscaler.py:172-212), uint8 NHWC frames of ONE stream in order -> uint8 NHWC."""
+
+    def __init__(self, ctx: Context, model: Frvsr, lr_shape, output_shape=None):
+        self.ctx, self.model = ctx, model
+        oh, ow = (0, 0) if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
+        h = C.c_void_p()
+        _check(lib().ss4k_frvsr_upscaler_create(ctx._h, model._h, int(lr_shape[0]), int(lr_shape[1]), oh, ow, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().ss4k_frvsr_upscaler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        _check(lib().ss4k_frvsr_upscaler_reset(self._h))
+
+    def out_shape(self):
+        oh, ow = C.c_int(), C.c_int()
+        _check(lib().ss4k_frvsr_upscaler_out_shape(self._h, C.byref(oh), C.byref(ow)))
+        return oh.value, ow.value
+
+    def enable_taps(self, on=True):
+        _check(lib().ss4k_frvsr_upscaler_enable_taps(self._h, int(on)))
+
+    def read_tap(self, which: int) -> torch.Tensor:
+        dims = (C.c_int * 4)()
+        _check(lib().ss4k_frvsr_upscaler_read_tap(self._h, which, None, 0, C.byref(dims), _stream()))
+        out = torch.empty(tuple(dims), dtype=torch.float32, device=self.ctx.device)
+        _check(lib().ss4k_frvsr_upscaler_read_tap(self._h, which, out.data_ptr(), out.numel(), C.byref(dims), _stream()))
+        return out
+
+    def __call__(self, frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.ndim == 4 and frames.shape[-1] == 3
+        frames = frames.contiguous()
+        n, h, w, _ = frames.shape
+        oh, ow = self.out_shape()
+        if out is None:
+            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_frvsr_upscale_frames(self._h, frames.data_ptr(), n, h, w, out.data_ptr(), out.numel(), _stream()))
         return out

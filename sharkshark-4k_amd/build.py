@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libss4k_hip.so")
 LIB_DEV = os.path.join(HERE, "libss4k_hip_dev.so")
-SOURCES = ["conv_mfma.hip", "conv_pair.hip", "conv_dense.hip", "conv_w16.hip", "conv_w16n.hip", "glue.hip", "fsrcnn.hip", "pack.cpp", "models.cpp", "api.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_pair.hip", "conv_dense.hip", "conv_w16.hip", "conv_w16n.hip", "glue.hip", "fsrcnn.hip", "frvsr.hip", "pack.cpp", "models.cpp", "frvsr.cpp", "api.cpp"]
 # fsrcnn.hip: no SLP vectorisation - left on, the tail's overlap-add (two adjacent output columns per lane) is packed into v_pk_add_f32,
 # which cannot take a DPP operand: 20 of its 35 wave shifts per row then become separate v_mov_b32_dpp, and packed fp32 adds are slower
 # than two plain ones beside MFMAs (MI355X_MICROARCH.md, cycle constants).  Without it every shift is folded into its add (v_add_f32_dpp)
@@ -48,7 +48,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
     jobs = []
     for s in SOURCES:
         src = os.path.join(CSRC, s)
-        obj = os.path.join(objdir, os.path.splitext(s)[0] + ".o")
+        obj = os.path.join(objdir, s + ".o")   # (frvsr.hip and frvsr.cpp share a stem)
         if force or _needs_build(obj, src):
             jobs.append((src, obj))
 
@@ -65,7 +65,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         list(ex.map(run, jobs))
-    objs = [os.path.join(objdir, os.path.splitext(s)[0] + ".o") for s in SOURCES]
+    objs = [os.path.join(objdir, s + ".o") for s in SOURCES]
     if jobs or not os.path.exists(lib):
         cmd = [hipcc, "-shared", "-fPIC", "--offload-arch=gfx950", *objs, "-o", lib]
         if verbose:

@@ -10,6 +10,7 @@
   ``convblock.0`` and turns ``convblock.3.{c1,c2}.net.`` into ``memconv.{c1,c2}.op.conv.``
   (``:276-279,167-169``); ``UpBlock`` turns ``convblock.0.{c1,c2}.net.`` into ``memconv...`` and
   ``convblock.1`` into ``convblock.0`` (``:304-306``).
+* EGVSR: the file is a bare ``state_dict`` of ``FRNet`` (``EGVSR_iter420000.pth``, ``egvsr_upscaler.py:25-27``).
 """
 from __future__ import annotations
 
@@ -78,3 +79,10 @@ def bsvd_from_checkpoint(ckpt: Mapping, **kw):
             if prefix in k:
                 out[f"{blk}." + _bsvd_block_remap(k.replace(prefix, ""))] = v
     return _ordered(out, W.bsvd_keys(**kw), "BSVD")
+
+
+def egvsr_from_checkpoint(ckpt: Mapping, nb: int = 10):
+    """``torch.load('EGVSR_iter420000.pth')`` is FRNet's bare state_dict (``egvsr_upscaler.py:25-27``); the entries ``forward`` never
+    reads (``srnet.conv_up.*``, the two ``upsample_func.kernels`` buffers) stay in the table: the blob is the whole state_dict."""
+    sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
+    return _ordered(sd, W.frnet_keys(nb), "FRNet")

@@ -1,5 +1,6 @@
 // C ABI (include/ss4k.h): context, models, the frame-in/frame-out upscaler and the granular ops.
 #include "models.h"
+#include "frvsr.h"
 #include "host_tables.h"
 #include <chrono>
 #include <cmath>
@@ -561,6 +562,105 @@ int ss4k_op_f32nchw_to_u8nhwc(ss4k_ctx* c, const float* in, uint8_t* out, int n,
   return guard([&] { SS4K_REQUIRE(c && in && out, "NULL argument"); op_f32nchw_to_u8nhwc(in, out, n, ch, h, w, (hipStream_t)s); SS4K_HIP(hipGetLastError()); });
 }
 
+// ---- the frame-recurrent upscaler (frvsr.cpp) ----------------------------------------------------
+size_t ss4k_frvsr_param_count(const ss4k_frvsr_desc* d) { return d ? frvsr_param_count(*d) : 0; }
+int ss4k_frvsr_create(ss4k_ctx* ctx, const ss4k_frvsr_desc* d, const float* w, size_t n, ss4k_frvsr** out) {
+  return guard([&] {
+    SS4K_REQUIRE(ctx && d && w && out, "ss4k_frvsr_create: NULL argument");
+    SS4K_HIP(hipSetDevice(ctx->device));
+    auto m = std::make_unique<ss4k_frvsr>();
+    m->f.ctx = ctx; m->f.desc = *d;
+    m->f.build(w, n);
+#ifdef SS4K_DEV
+    for (DevBuf* b : {&m->f.flow_raw, &m->f.flow, &m->f.tap_s2d}) b->transient = true;   // guard mode: every step rewrites what it reads from these
+#endif
+    *out = m.release();
+  });
+}
+void ss4k_frvsr_destroy(ss4k_frvsr* m) { delete m; }
+int ss4k_frvsr_step(ss4k_frvsr* m, const float* lr_curr, const float* lr_prev, const float* hr_prev, float* hr_out, int n, int h, int w, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(m && lr_curr && lr_prev && hr_prev && hr_out, "ss4k_frvsr_step: NULL argument");
+    m->f.step(lr_curr, lr_prev, hr_prev, hr_out, n, h, w, (hipStream_t)stream);
+  });
+}
+int ss4k_frvsr_workspace_bytes(ss4k_frvsr* m, int n, int h, int w, size_t* bytes) {
+  return guard([&] {
+    SS4K_REQUIRE(m && bytes, "ss4k_frvsr_workspace_bytes: NULL argument");
+    *bytes = m->f.workspace_bytes(n, h, w);
+  });
+}
+int ss4k_frvsr_prof_enable(ss4k_frvsr* m, int en) {
+  return guard([&] {
+    SS4K_REQUIRE(m, "ss4k_frvsr_prof_enable: NULL argument");
+    m->f.prof_collect();
+    if (en) for (double& v : m->f.stage_ms) v = 0;
+    m->f.prof = en != 0;
+  });
+}
+int ss4k_frvsr_prof_read(ss4k_frvsr* m, int stage, double* ms) {
+  return guard([&] {
+    SS4K_REQUIRE(m && ms && stage >= 0 && stage < FRV_STAGES, "ss4k_frvsr_prof_read: bad argument");
+    m->f.prof_collect();
+    *ms = m->f.stage_ms[stage];
+  });
+}
+int ss4k_frvsr_upscaler_create(ss4k_ctx* ctx, ss4k_frvsr* m, int lr_h, int lr_w, int out_h, int out_w, ss4k_frvsr_upscaler** out) {
+  return guard([&] {
+    SS4K_REQUIRE(ctx && m && out, "ss4k_frvsr_upscaler_create: NULL argument");
+    SS4K_REQUIRE(lr_h >= 8 && lr_w >= 8, "lr_shape must be at least 8 x 8");
+    SS4K_REQUIRE((out_h == 0 && out_w == 0) || (out_h > 0 && out_w > 0), "output_shape is (0, 0) or positive");
+    SS4K_REQUIRE((double)lr_h * lr_w * 16.0 < 2147483648.0, "lr_shape: the output frame must hold fewer than 2^31 pixels");
+    auto u = std::make_unique<ss4k_frvsr_upscaler>();
+    u->u.ctx = ctx; u->u.m = &m->f; u->u.lr_h = lr_h; u->u.lr_w = lr_w; u->u.out_h = out_h; u->u.out_w = out_w;
+#ifdef SS4K_DEV
+    for (DevBuf* b : {&u->u.img, &u->u.hrc, &u->u.outf}) b->transient = true;   // (lr[] and hr[] carry the recurrent state across calls)
+#endif
+    *out = u.release();
+  });
+}
+void ss4k_frvsr_upscaler_destroy(ss4k_frvsr_upscaler* up) { delete up; }
+int ss4k_frvsr_upscaler_reset(ss4k_frvsr_upscaler* up) { if (!up) return SS4K_EINVAL; up->u.have_state = false; return SS4K_OK; }
+int ss4k_frvsr_upscaler_out_shape(const ss4k_frvsr_upscaler* up, int* oh, int* ow) {
+  return guard([&] { SS4K_REQUIRE(up && oh && ow, "NULL argument"); up->u.out_shape(oh, ow); });
+}
+int ss4k_frvsr_upscale_frames(ss4k_frvsr_upscaler* up, const uint8_t* in, int n, int h, int w, uint8_t* out, size_t cap, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(up && in && out, "ss4k_frvsr_upscale_frames: NULL argument");
+    SS4K_REQUIRE(n > 0 && h > 0 && w > 0, "ss4k_frvsr_upscale_frames: empty batch");
+    int oh, ow; up->u.out_shape(&oh, &ow);
+    SS4K_REQUIRE(cap >= (size_t)oh * ow * 3 * n, "ss4k_frvsr_upscale_frames: output buffer too small");
+    up->u.frames(in, n, h, w, out, (hipStream_t)stream);
+  });
+}
+int ss4k_frvsr_upscaler_enable_taps(ss4k_frvsr_upscaler* up, int en) {
+  if (!up) return SS4K_EINVAL;
+  up->u.taps_on = en != 0;
+  if (!en) std::memset(up->u.tap_dims, 0, sizeof(up->u.tap_dims));
+  return SS4K_OK;
+}
+int ss4k_frvsr_upscaler_read_tap(ss4k_frvsr_upscaler* up, int which, float* out, size_t cap, int dims[4], void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(up && which >= 0 && which < 4 && dims, "bad tap request");
+    FrvsrUpscaler& u = up->u;
+    const int* d = u.tap_dims[which];
+    for (int i = 0; i < 4; ++i) dims[i] = d[i];
+    const size_t nflt = (size_t)d[0] * d[1] * d[2] * d[3];
+    SS4K_REQUIRE(nflt > 0, "tap not recorded (enable taps before ss4k_frvsr_upscale_frames)");
+    if (out) {
+      SS4K_REQUIRE(cap >= nflt, "tap buffer too small");
+      const void* src = which == 0 ? u.lr[u.cur].ptr : which == 1 ? u.m->flow.ptr : which == 2 ? u.m->tap_s2d.ptr : u.hr[u.cur].ptr;
+      SS4K_HIP(hipMemcpyAsync(out, src, nflt * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
+  });
+}
+int ss4k_op_backward_warp(ss4k_ctx* c, const float* x, const float* flow, float* out, int n, int ch, int h, int w, void* s) {
+  return guard([&] { SS4K_REQUIRE(c && x && flow && out, "NULL argument"); op_backward_warp(x, flow, out, n, ch, h, w, (hipStream_t)s); });
+}
+int ss4k_op_bicubic_upsample4(ss4k_ctx* c, const float* in, float* out, int p, int h, int w, void* s) {
+  return guard([&] { SS4K_REQUIRE(c && in && out, "NULL argument"); op_bicubic_upsample4(in, out, p, h, w, (hipStream_t)s); });
+}
+
 #ifdef SS4K_DEV
 int ss4k_bench_conv(ss4k_ctx* c, int dtype, int cin0, int cin1, int cout, int n, int h, int w, int flags, int iters,
                     double* avg_us, void* stream) {
@@ -763,6 +863,19 @@ int ss4k_dev_guard_poison(ss4k_ctx* c, ss4k_model* m, ss4k_upscaler* up, int* bu
         poison_one(*b, buffers, bytes, bytes_256);
       for (auto& t : u.tap) poison_one(t, buffers, bytes, bytes_256);
     }
+    SS4K_HIP(hipDeviceSynchronize());
+  });
+}
+int ss4k_dev_guard_poison_frvsr(ss4k_frvsr* m, ss4k_frvsr_upscaler* up, int* buffers, size_t* bytes, size_t* bytes_256) {
+  return guard([&] {
+    SS4K_REQUIRE(buffers && bytes && bytes_256, "ss4k_dev_guard_poison_frvsr: NULL argument");
+    *buffers = 0; *bytes = 0; *bytes_256 = 0;
+    SS4K_HIP(hipDeviceSynchronize());
+    if (m) {
+      for (auto& b : m->f.net.acts) poison_one(b, buffers, bytes, bytes_256);
+      for (DevBuf* b : {&m->f.flow_raw, &m->f.flow, &m->f.tap_s2d}) poison_one(*b, buffers, bytes, bytes_256);
+    }
+    if (up) for (DevBuf* b : {&up->u.img, &up->u.hrc, &up->u.outf}) poison_one(*b, buffers, bytes, bytes_256);
     SS4K_HIP(hipDeviceSynchronize());
   });
 }

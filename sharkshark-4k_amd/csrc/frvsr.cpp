@@ -1,0 +1,256 @@
+// Executor of the frame-recurrent upscaler (EGVSR's FRNet x4, reference src/upscale/model/egvsr/egvsr.py:146-212) and the service path
+// around it (src/upscale/egvsr_upscaler.py:172-212).  Every convolution is 3x3 / stride 1 / pad 1 and runs through Model::conv on the conv
+// kernels the other networks use; the rest of the network is the glue of frvsr.hip.  Weights arrive as FRNet's state_dict flattened in key order
+// (sharkshark-4k_amd/weights.py: frnet_keys).
+#include "frvsr.h"
+
+namespace ss4k {
+
+// FNet's convolutions (cout, cin) in state_dict order (egvsr.py:19-61); every one but the last is followed by LeakyReLU(0.2)
+static const int FNET_CONVS[14][2] = {{32, 6}, {32, 32}, {64, 32}, {64, 64}, {128, 64}, {128, 128}, {256, 128}, {256, 256},
+                                      {128, 256}, {128, 128}, {64, 128}, {64, 64}, {32, 64}, {2, 32}};
+
+static void validate_frvsr_desc(const ss4k_frvsr_desc& d) {
+  SS4K_REQUIRE(d.dtype == SS4K_F32 || d.dtype == SS4K_F16, "frvsr desc.dtype must be SS4K_F32 or SS4K_F16");
+  SS4K_REQUIRE(d.num_feat > 0 && d.num_feat <= SS4K_DESC_MAX_WIDTH && d.num_feat % 16 == 0, "frvsr: num_feat must be a multiple of 16 in 16..512");
+  SS4K_REQUIRE(d.num_feat == 64, "frvsr: SRNet's tail is PixelShuffle(4) + Conv2d(4, 3) (egvsr.py:122-127): num_feat must be 64");
+  SS4K_REQUIRE(d.num_block >= 0 && d.num_block <= SS4K_DESC_MAX_BLOCKS, "frvsr: num_block must be in 0..64");
+  SS4K_REQUIRE(d.flags == 0, "frvsr desc.flags must be 0");
+  for (int r : d.reserved) SS4K_REQUIRE(r == 0, "frvsr desc.reserved must be 0");
+}
+
+size_t frvsr_param_count(const ss4k_frvsr_desc& d) {
+  try { validate_frvsr_desc(d); } catch (const Error&) { return 0; }
+  const size_t nf = (size_t)d.num_feat;
+  size_t n = 16;                                                    // upsample_func.kernels
+  for (auto& c : FNET_CONVS) n += (size_t)c[0] * c[1] * 9 + c[0];
+  n += nf * 51 * 9 + nf;                                            // srnet.conv_in.0
+  n += (size_t)d.num_block * 2 * (nf * nf * 9 + nf);                // srnet.resblocks.*.conv.{0,2}
+  n += 2 * (nf * nf * 9 + nf);                                      // srnet.conv_up.{0,2}: in the state_dict, unused by forward
+  n += 3 * 4 * 9 + 3;                                               // srnet.conv_out
+  n += 16;                                                          // srnet.upsample_func.kernels
+  return n;
+}
+
+void Frvsr::build(const float* w, size_t n) {
+  validate_frvsr_desc(desc);
+  SS4K_REQUIRE(n == frvsr_param_count(desc), "weight blob size does not match the frvsr description");
+  net.ctx = ctx;
+  net.desc = ss4k_model_desc{}; net.desc.kind = SS4K_SRVGG; net.desc.dtype = desc.dtype; net.desc.scale = 4; net.desc.num_feat = desc.num_feat;
+  const int nf = desc.num_feat;
+  ParamCursor pc{w, n};
+  (void)pc.take(16);
+  fnet0 = 0;
+  for (int i = 0; i < 14; ++i)   // torch.cat([x1, x2], 1) (egvsr.py:67): two input segments of one plane each
+    net.add_conv(pc, FNET_CONVS[i][0], FNET_CONVS[i][1], i == 0 ? net.spec_concat(3, 3) : net.spec_plain(FNET_CONVS[i][1]), false);
+  srnet0 = (int)net.layers.size();
+  net.add_conv(pc, nf, 51, net.spec_concat(3, 48), false);   // torch.cat([lr_curr, hr_prev_tran], 1) (egvsr.py:137)
+  for (int i = 0; i < 2 * desc.num_block; ++i) net.add_conv(pc, nf, nf, net.spec_plain(nf), false);
+  (void)pc.take(2 * ((size_t)nf * nf * 9 + nf));
+  const float* tw = pc.take(108);
+  std::vector<float> wb(tw, tw + 108);
+  const float* b = pc.take(3);
+  wb.insert(wb.end(), b, b + 3);
+  tail_wb.ensure(wb.size() * 4);
+  SS4K_HIP(hipMemcpy(tail_wb.ptr, wb.data(), wb.size() * 4, hipMemcpyHostToDevice));
+  (void)pc.take(16);
+  SS4K_REQUIRE(pc.pos == n, "internal: weight cursor did not consume the blob");
+}
+
+Frvsr::~Frvsr() {
+  for (auto& s : spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
+}
+
+void Frvsr::prof_collect() {
+  for (auto& s : spans) {
+    float ms = 0.f;
+    if (hipEventSynchronize(s.b) == hipSuccess && hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) stage_ms[s.stage] += ms;
+    else (void)hipGetLastError();
+    (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b);
+  }
+  spans.clear();
+}
+
+size_t Frvsr::workspace_bytes(int n, int h, int w) {
+  net.plan_only = true; net.plan_bytes.clear();
+  try { step(nullptr, nullptr, nullptr, nullptr, n, h, w, nullptr); } catch (...) { net.plan_only = false; throw; }
+  net.plan_only = false;
+  size_t total = 0;
+  for (size_t b : net.plan_bytes) total += (b + 255) & ~size_t(255);
+  const size_t flow_b = (size_t)n * 2 * h * w * 4;
+  return total + 2 * ((flow_b + 255) & ~size_t(255));   // flow_raw (sized like flow: at most as large), flow
+}
+
+void Frvsr::step(const float* lr_curr, const float* lr_prev, const float* hr_prev, float* hr_out, int n, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(n > 0, "frvsr step: empty batch");
+  SS4K_REQUIRE(h >= 8 && w >= 8, "frvsr step: h and w must be at least 8 (the flow is computed at (h // 8 * 8, w // 8 * 8) and reflect-padded, egvsr.py:191-194)");
+  SS4K_REQUIRE((double)n * 16.0 * h * w < 2147483648.0, "frvsr step: the output of a call holds at most 2^31 pixels per plane");
+  const bool plan = net.plan_only, f16 = desc.dtype == SS4K_F16;
+  const int h1 = h / 2, w1 = w / 2, h2 = h1 / 2, w2 = w1 / 2, h3 = h2 / 2, w3 = w2 / 2, h8 = 8 * h3, w8 = 8 * w3;
+  const size_t px = (size_t)n * h * w, px1 = (size_t)n * h1 * w1, px2 = (size_t)n * h2 * w2, px3 = (size_t)n * h3 * w3;
+  auto stage = [&](int s, auto&& body) {
+    if (!prof || plan) { body(); return; }
+    Span sp{nullptr, nullptr, s};
+    SS4K_HIP(hipEventCreate(&sp.a));
+    if (hipEventCreate(&sp.b) != hipSuccess) { (void)hipEventDestroy(sp.a); throw Error(SS4K_EHIP, "hipEventCreate failed"); }
+    spans.push_back(sp);
+    SS4K_HIP(hipEventRecord(sp.a, st));
+    body();
+    SS4K_HIP(hipEventRecord(sp.b, st));
+  };
+  auto lrelu = [](const Tens& out, float slope) { ConvOpts o; o.act = ACT_LRELU; o.slope = slope; o.out = out; return o; };
+  auto pool = [&](const Tens& in, const Tens& out, int channels, int H, int W) {
+    if (plan) return;
+    if (f16) op_maxpool2_planes<__half>(reinterpret_cast<const __half*>(in.p), reinterpret_cast<__half*>(out.p), channels / 16, n, H, W, st);
+    else op_maxpool2_planes<float>(reinterpret_cast<const float*>(in.p), reinterpret_cast<float*>(out.p), channels / 16, n, H, W, st);
+  };
+  auto up2 = [&](const Tens& in, const Tens& out, int channels, int H, int W) {
+    if (plan) return;
+    if (f16) op_bilinear2_planes<__half>(reinterpret_cast<const __half*>(in.p), reinterpret_cast<__half*>(out.p), channels / 16, n, H, W, st);
+    else op_bilinear2_planes<float>(reinterpret_cast<const float*>(in.p), reinterpret_cast<float*>(out.p), channels / 16, n, H, W, st);
+  };
+  int slot = 0;
+  auto act = [&](size_t pixels, int channels) { return net.act(slot++, pixels, channels); };
+
+  // ---- inputs: lr_curr and lr_prev as one 16-channel plane each (channels 0..2 live)
+  Tens A = net.act_planes(slot++, px, 1), B = net.act_planes(slot++, px, 1);
+  stage(FRV_GLUE, [&] {
+    net.pack_in(lr_curr, A, 1, n, 3, h, w, 1, st);
+    net.pack_in(lr_prev, B, 1, n, 3, h, w, 1, st);
+  });
+
+  // ---- FNet (egvsr.py:63-78)
+  int li = fnet0;
+  Tens e1a = act(px, 32), e1b = act(px, 32), p1 = act(px1, 32);
+  Tens e2a = act(px1, 64), e2b = act(px1, 64), p2 = act(px2, 64);
+  Tens e3a = act(px2, 128), e3b = act(px2, 128), p3 = act(px3, 128);
+  Tens d1a = act(px3, 256), d1b = act(px3, 256), u1 = act(px3 * 4, 256);
+  Tens d2a = act(px3 * 4, 128), d2b = act(px3 * 4, 128), u2 = act(px3 * 16, 128);
+  Tens d3a = act(px3 * 16, 64), d3b = act(px3 * 16, 64), u3 = act(px3 * 64, 64);
+  Tens f0 = act(px3 * 64, 32);
+  const size_t flow_raw_b = (size_t)n * 2 * h8 * w8 * 4, flow_b = (size_t)n * 2 * h * w * 4;
+  if (!plan) { flow_raw.ensure(flow_raw_b); flow.ensure(flow_b); }
+  auto two = [&](const Tens& in0, const Tens* in1, const Tens& mid, const Tens& out, int H, int W) {
+    stage(FRV_FNET_CONV, [&] {
+      net.conv(li++, in0, in1, n, H, W, lrelu(mid, 0.2f), st);
+      net.conv(li++, mid, nullptr, n, H, W, lrelu(out, 0.2f), st);
+    });
+  };
+  two(A, &B, e1a, e1b, h, w);
+  stage(FRV_POOL_UP, [&] { pool(e1b, p1, 32, h, w); });
+  two(p1, nullptr, e2a, e2b, h1, w1);
+  stage(FRV_POOL_UP, [&] { pool(e2b, p2, 64, h1, w1); });
+  two(p2, nullptr, e3a, e3b, h2, w2);
+  stage(FRV_POOL_UP, [&] { pool(e3b, p3, 128, h2, w2); });
+  two(p3, nullptr, d1a, d1b, h3, w3);
+  stage(FRV_POOL_UP, [&] { up2(d1b, u1, 256, h3, w3); });
+  two(u1, nullptr, d2a, d2b, 2 * h3, 2 * w3);
+  stage(FRV_POOL_UP, [&] { up2(d2b, u2, 128, 2 * h3, 2 * w3); });
+  two(u2, nullptr, d3a, d3b, 4 * h3, 4 * w3);
+  stage(FRV_POOL_UP, [&] { up2(d3b, u3, 64, 4 * h3, 4 * w3); });
+  stage(FRV_FNET_CONV, [&] {
+    net.conv(li++, u3, nullptr, n, h8, w8, lrelu(f0, 0.2f), st);
+    ConvOpts o; o.epi = EPI_NCHW_F32; o.out = Tens{flow_raw.as<char>(), 0, 0};   // the raw flow leaves the network as fp32 NCHW (n, 2, h8, w8)
+    net.conv(li++, f0, nullptr, n, h8, w8, o, st);
+  });
+  // tanh * 24 (egvsr.py:76), reflect pad to (h, w) (:191-194)
+  stage(FRV_FLOW, [&] { if (!plan) op_flow_finish(flow_raw.as<float>(), flow.as<float>(), n, h8, w8, h, w, st); });
+
+  // ---- hr_flow = 4 * BicubicUpsample(4)(lr_flow), backward_warp(hr_prev, hr_flow), space-to-depth (egvsr.py:196-208): one launch, three planes
+  Tens Wp = net.act_planes(slot++, px, 3);
+  stage(FRV_WARP, [&] {
+    if (plan) return;
+    if (f16) op_warp_s2d_planes<__half>(flow.as<float>(), hr_prev, reinterpret_cast<__half*>(Wp.p), n, h, w, st);
+    else op_warp_s2d_planes<float>(flow.as<float>(), hr_prev, reinterpret_cast<float*>(Wp.p), n, h, w, st);
+  });
+  if (keep_taps && !plan) {
+    tap_s2d.ensure(px * 48 * 4);
+    if (f16) op_planes_to_nchw<__half>(reinterpret_cast<const __half*>(Wp.p), tap_s2d.as<float>(), n, 48, h, w, st);
+    else op_planes_to_nchw<float>(reinterpret_cast<const float*>(Wp.p), tap_s2d.as<float>(), n, 48, h, w, st);
+  }
+
+  // ---- SRNet (egvsr.py:132-143): ReLU is LeakyReLU with slope 0; a residual block's skip is res1 with alpha = 1
+  const int nf = desc.num_feat;
+  li = srnet0;
+  Tens x0 = act(px, nf), t = act(px, nf), x1 = act(px, nf);
+  Tens cur = x0, nxt = x1;
+  stage(FRV_SRNET_CONV, [&] {
+    net.conv(li++, A, &Wp, n, h, w, lrelu(x0, 0.f), st);
+    for (int b = 0; b < desc.num_block; ++b) {
+      net.conv(li++, cur, nullptr, n, h, w, lrelu(t, 0.f), st);
+      ConvOpts o; o.res1 = &cur; o.out = nxt;
+      net.conv(li++, t, nullptr, n, h, w, o, st);
+      std::swap(cur, nxt);
+    }
+    net.lanes_join(st, true);   // (closes the context's conv profiling section if one is open; a step never forks)
+  });
+  // PixelShuffle(4), ReLU, conv_out (egvsr.py:139-140)
+  stage(FRV_TAIL, [&] {
+    if (plan) return;
+    if (f16) op_ps4_conv_tail<__half>(reinterpret_cast<const __half*>(cur.p), tail_wb.as<float>(), hr_out, n, h, w, st);
+    else op_ps4_conv_tail<float>(reinterpret_cast<const float*>(cur.p), tail_wb.as<float>(), hr_out, n, h, w, st);
+  });
+}
+
+// ------------------------------------------------------------------------------------------ the service path
+void FrvsrUpscaler::out_shape(int* oh, int* ow) const {
+  *oh = out_h > 0 ? out_h : 4 * lr_h; *ow = out_w > 0 ? out_w : 4 * lr_w;
+}
+
+void FrvsrUpscaler::frames(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st) {
+  const int H = 4 * lr_h, W = 4 * lr_w;
+  int oh, ow; out_shape(&oh, &ow);
+  const size_t lr_b = (size_t)3 * lr_h * lr_w * 4, hr_b = (size_t)3 * H * W * 4;
+  for (int k = 0; k < 2; ++k) { lr[k].ensure(lr_b); hr[k].ensure(hr_b); }
+  if (!have_state) {   // self.lr_prev = zeros_like(lr_curr), self.hr_prev = zeros (egvsr_upscaler.py:197-202)
+    SS4K_HIP(hipMemsetAsync(lr[cur].ptr, 0, lr_b, st));
+    SS4K_HIP(hipMemsetAsync(hr[cur].ptr, 0, hr_b, st));
+    have_state = true;
+  }
+  const bool resize_in = h != lr_h || w != lr_w, resize_out = oh != H || ow != W;
+  m->keep_taps = taps_on;
+  auto glue = [&](auto&& body) {
+    if (!m->prof) { body(); return; }
+    Frvsr::Span sp{nullptr, nullptr, FRV_GLUE};
+    SS4K_HIP(hipEventCreate(&sp.a));
+    if (hipEventCreate(&sp.b) != hipSuccess) { (void)hipEventDestroy(sp.a); throw Error(SS4K_EHIP, "hipEventCreate failed"); }
+    m->spans.push_back(sp);
+    SS4K_HIP(hipEventRecord(sp.a, st));
+    body();
+    SS4K_HIP(hipEventRecord(sp.b, st));
+  };
+  for (int i = 0; i < n; ++i) {
+    float* lr_curr = lr[cur ^ 1].as<float>();
+    float* hr_curr = hr[cur ^ 1].as<float>();
+    glue([&] {
+      const uint8_t* frame = in + (size_t)i * h * w * 3;
+      if (resize_in) {   // img / 255.0, F.interpolate(img, size=self.lr_shape, mode='area') (egvsr_upscaler.py:195-196)
+        img.ensure((size_t)3 * h * w * 4);
+        op_u8nhwc_to_f32nchw(frame, img.as<float>(), 1, h, w, 3, st);
+        op_area(img.as<float>(), lr_curr, 3, h, w, lr_h, lr_w, st);
+      } else {
+        op_u8nhwc_to_f32nchw(frame, lr_curr, 1, h, w, 3, st);
+      }
+    });
+    m->step(lr_curr, lr[cur].as<float>(), hr[cur].as<float>(), hr_curr, 1, lr_h, lr_w, st);   // (:204)
+    cur ^= 1;   // the state takes the UNCLAMPED output (:206-207)
+    glue([&] {
+      uint8_t* dst = out + (size_t)i * oh * ow * 3;
+      if (resize_out) {   // clamp(hr_curr, 0, 1), F.interpolate(size=self.output_shape, mode='area') (:209-211)
+        hrc.ensure(hr_b); outf.ensure((size_t)3 * oh * ow * 4);
+        op_clamp01_to(hr_curr, hrc.as<float>(), (size_t)3 * H * W, st);
+        op_area(hrc.as<float>(), outf.as<float>(), 3, H, W, oh, ow, st);
+        op_f32nchw_to_u8nhwc(outf.as<float>(), dst, 1, 3, oh, ow, st);
+      } else {
+        op_f32nchw_to_u8nhwc(hr_curr, dst, 1, 3, H, W, st);   // (clamps, * 255, truncates: :209,212)
+      }
+    });
+  }
+  m->keep_taps = false;
+  if (taps_on) {
+    const int d[4][4] = {{1, 3, lr_h, lr_w}, {1, 2, lr_h, lr_w}, {1, 48, lr_h, lr_w}, {1, 3, H, W}};
+    std::memcpy(tap_dims, d, sizeof(d));
+  }
+}
+
+}  // namespace ss4k

@@ -1,0 +1,74 @@
+// EGVSR's frame-recurrent upscaler (FRNet x4, reference src/upscale/model/egvsr/egvsr.py:146-212): the executor behind ss4k_frvsr and
+// the service path behind ss4k_frvsr_upscaler (include/ss4k.h), and the launchers of the glue kernels they need (frvsr.hip).
+#pragma once
+#include "models.h"
+
+namespace ss4k {
+
+// ---- kernels (frvsr.hip).  "planes" tensors are the conv kernels' layout: [plane][pixel][16 channels of T] -----------------------------
+// nn.MaxPool2d(2, 2) (egvsr.py:24,31,38): (n, h, w) -> (n, h / 2, w / 2), odd sizes floored
+template <typename T> void op_maxpool2_planes(const T* in, T* out, int nplanes, int n, int h, int w, hipStream_t st);
+// F.interpolate(scale_factor=2, mode='bilinear', align_corners=False) (egvsr.py:70-75): (n, h, w) -> (n, 2 h, 2 w)
+template <typename T> void op_bilinear2_planes(const T* in, T* out, int nplanes, int n, int h, int w, hipStream_t st);
+// tanh(raw) * 24 (egvsr.py:76) and F.pad(..., (0, pad_w, 0, pad_h), 'reflect') (:191-194): (n, 2, h8, w8) -> (n, 2, h, w), fp32
+void op_flow_finish(const float* raw, float* flow, int n, int h8, int w8, int h, int w, hipStream_t st);
+// BicubicUpsample(4) (utils/net_utils.py:112-165): (planes, h, w) -> (planes, 4 h, 4 w), fp32
+void op_bicubic_upsample4(const float* in, float* out, int planes, int h, int w, hipStream_t st);
+// backward_warp (utils/net_utils.py:50-93): x (n, c, h, w), flow (n, 2, h, w) -> (n, c, h, w), fp32
+void op_backward_warp(const float* x, const float* flow, float* out, int n, int c, int h, int w, hipStream_t st);
+// 4 * BicubicUpsample(4)(lr_flow), backward_warp(hr_prev, .) and the space-to-depth of egvsr.py:196-208 as one launch: lr_flow (n, 2, h, w),
+// hr_prev (n, 3, 4 h, 4 w), both fp32 -> three planes of T (channel (sy * 4 + sx) * 3 + c)
+template <typename T> void op_warp_s2d_planes(const float* lr_flow, const float* hr_prev, T* out, int n, int h, int w, hipStream_t st);
+// PixelShuffle(4), ReLU, Conv2d(4, 3, 3, 1, 1) (egvsr.py:122-127,139-140): four planes of T (64 channels) at (n, h, w) -> fp32 NCHW
+// (n, 3, 4 h, 4 w); wb: 108 weights (OIHW) + 3 biases on the device
+template <typename T> void op_ps4_conv_tail(const T* in, const float* wb, float* out, int n, int h, int w, hipStream_t st);
+// planes of T -> fp32 NCHW (n, channels, h, w) (the parity taps)
+template <typename T> void op_planes_to_nchw(const T* in, float* out, int n, int channels, int h, int w, hipStream_t st);
+// clamp(x, 0, 1) into another tensor (egvsr_upscaler.py:209: the recurrent state keeps the unclamped one)
+void op_clamp01_to(const float* in, float* out, size_t n, hipStream_t st);
+
+size_t frvsr_param_count(const ss4k_frvsr_desc& d);   // 0 for a description that is refused
+
+// stages of a step, for the per-stage event timing (ss4k_frvsr_prof_read)
+enum { FRV_FNET_CONV = 0, FRV_SRNET_CONV = 1, FRV_POOL_UP = 2, FRV_FLOW = 3, FRV_WARP = 4, FRV_TAIL = 5, FRV_GLUE = 6, FRV_STAGES = 7 };
+
+struct Frvsr {
+  ss4k_ctx* ctx = nullptr;
+  ss4k_frvsr_desc desc{};
+  Model net;                 // container of the conv layers and the activation workspaces (Model::conv / Model::act)
+  DevBuf tail_wb;            // srnet.conv_out: 108 weights + 3 biases, fp32
+  DevBuf flow_raw, flow;     // fp32 in both dtypes
+  int fnet0 = 0, srnet0 = 0; // first layer of each network in net.layers
+  bool keep_taps = false;    // step() leaves copies for the service's parity taps
+  DevBuf tap_s2d;            // fp32 NCHW (n, 48, h, w)
+  // per-stage timing with events on the caller's stream (off by default)
+  bool prof = false;
+  struct Span { hipEvent_t a, b; int stage; };
+  std::vector<Span> spans;
+  double stage_ms[FRV_STAGES] = {};
+  void prof_collect();
+  ~Frvsr();
+
+  void build(const float* w, size_t n);
+  // FRNet.forward (egvsr.py:180-212)
+  void step(const float* lr_curr, const float* lr_prev, const float* hr_prev, float* hr_out, int n, int h, int w, hipStream_t st);
+  size_t workspace_bytes(int n, int h, int w);
+};
+
+struct FrvsrUpscaler {
+  ss4k_ctx* ctx = nullptr;
+  Frvsr* m = nullptr;
+  int lr_h = 0, lr_w = 0, out_h = 0, out_w = 0;
+  bool have_state = false;
+  int cur = 0;               // which of lr[2] / hr[2] holds the previous frame
+  DevBuf img, lr[2], hr[2], hrc, outf;
+  bool taps_on = false;      // read_tap copies from the live buffers: lr[cur], m->flow, m->tap_s2d, hr[cur]
+  int tap_dims[4][4] = {};
+  void out_shape(int* oh, int* ow) const;
+  void frames(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st);
+};
+
+}  // namespace ss4k
+
+struct ss4k_frvsr { ss4k::Frvsr f; };
+struct ss4k_frvsr_upscaler { ss4k::FrvsrUpscaler u; };

@@ -1,0 +1,332 @@
+// Glue kernels of the frame-recurrent upscaler (EGVSR's FRNet x4, reference src/upscale/model/egvsr/egvsr.py): everything of
+// FRNet.forward that is not a 3x3 convolution.  The convolutions run on the conv kernels through Model::conv (frvsr.cpp).
+// "planes" tensors: [plane][pixel (n, y, x)][16 channels of T], T = __half (32-byte records) or float (64-byte records).
+// The flow, hr_prev and hr_curr are fp32 in both dtypes.
+//
+// The bicubic x4 and the warp exist twice - as granular ops (ss4k_op_bicubic_upsample4, ss4k_op_backward_warp) and inside the fused
+// warp + space-to-depth kernel - and both go through the SAME device functions below, written with explicit __fmaf_rn / __fmul_rn /
+// __fadd_rn so that the compiler contracts nothing differently in the two places: the fused kernel's tensor is bit-identical to the chain
+// of the granular ops (tests/test_gpu_frvsr.py).
+#include "frvsr.h"
+
+namespace ss4k {
+
+#define SS4K_LAUNCH_OK() SS4K_HIP(hipGetLastError())
+
+static inline dim3 grid_for(size_t n, int block = 256) {
+  size_t g = (n + block - 1) / block;
+  if (g > 256 * 8 * 4) g = 256 * 8 * 4;   // grid-stride beyond a few waves per CU
+  return dim3((unsigned)std::max<size_t>(g, 1));
+}
+
+// one 16-byte slot of a record as E values of T
+template <typename T> struct Slot {
+  static constexpr int E = 16 / sizeof(T);
+  union { uint4 u; T v[E]; };
+  __device__ __forceinline__ Slot() : u(make_uint4(0, 0, 0, 0)) {}
+};
+
+// ------------------------------------------------------------------ MaxPool2d(2, 2) on planes
+template <typename T>
+__global__ void k_maxpool2_planes(const uint4* __restrict__ in, uint4* __restrict__ out, int nplanes, int n, int h, int w) {
+  constexpr int RV = sizeof(T);   // 16-byte slots per record: 16 channels * sizeof(T) / 16
+  const int oh = h / 2, ow = w / 2;
+  const size_t ipx = (size_t)n * h * w, opx = (size_t)n * oh * ow, total = (size_t)nplanes * opx * RV;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int slot = (int)(i % RV);
+    const size_t q = i / RV, pix = q % opx, plane = q / opx;
+    const int ox = (int)(pix % ow), oy = (int)((pix / ow) % oh);
+    const size_t img = pix / ((size_t)ow * oh);
+    const size_t base = plane * ipx + (img * h + 2 * (size_t)oy) * w + 2 * (size_t)ox;
+    Slot<T> a, b, c, d, r;
+    a.u = in[base * RV + slot]; b.u = in[(base + 1) * RV + slot];
+    c.u = in[(base + w) * RV + slot]; d.u = in[(base + w + 1) * RV + slot];
+#pragma unroll
+    for (int e = 0; e < Slot<T>::E; ++e)
+      r.v[e] = (T)fmaxf(fmaxf((float)a.v[e], (float)b.v[e]), fmaxf((float)c.v[e], (float)d.v[e]));
+    out[i] = r.u;   // i == ((plane * opx + pix) * RV + slot)
+  }
+}
+template <typename T>
+void op_maxpool2_planes(const T* in, T* out, int nplanes, int n, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(nplanes > 0 && n > 0 && h >= 2 && w >= 2, "maxpool2: needs at least 2 x 2 pixels");
+  const size_t total = (size_t)nplanes * n * (h / 2) * (w / 2) * sizeof(T);
+  SS4K_GLUE_ROUTE(sizeof(T) == 2 ? "frvsr::maxpool2_planes<half>" : "frvsr::maxpool2_planes<float>");
+  hipLaunchKernelGGL((k_maxpool2_planes<T>), grid_for(total), dim3(256), 0, st, reinterpret_cast<const uint4*>(in), reinterpret_cast<uint4*>(out),
+                     nplanes, n, h, w);
+  SS4K_LAUNCH_OK();
+}
+template void op_maxpool2_planes<float>(const float*, float*, int, int, int, int, hipStream_t);
+template void op_maxpool2_planes<__half>(const __half*, __half*, int, int, int, int, hipStream_t);
+
+// ------------------------------------------------------------------ bilinear x2 (align_corners=False) on planes
+// source index of ATen's upsample_bilinear2d for scale_factor = 2: src = max(0.5 (dst + 0.5) - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, size - 1)
+__device__ __forceinline__ void bil2_src(int dst, int size, int& i0, int& i1, float& l0, float& l1) {
+  const float s = fmaxf(0.5f * ((float)dst + 0.5f) - 0.5f, 0.f);
+  i0 = min((int)s, size - 1); i1 = min(i0 + 1, size - 1);
+  l1 = s - (float)i0; l0 = 1.f - l1;
+}
+template <typename T>
+__global__ void k_bilinear2_planes(const uint4* __restrict__ in, uint4* __restrict__ out, int nplanes, int n, int h, int w) {
+  constexpr int RV = sizeof(T);
+  const int oh = 2 * h, ow = 2 * w;
+  const size_t ipx = (size_t)n * h * w, opx = (size_t)n * oh * ow, total = (size_t)nplanes * opx * RV;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int slot = (int)(i % RV);
+    const size_t q = i / RV, pix = q % opx, plane = q / opx;
+    const int ox = (int)(pix % ow), oy = (int)((pix / ow) % oh);
+    const size_t img = pix / ((size_t)ow * oh);
+    int y0, y1, x0, x1; float wy0, wy1, wx0, wx1;
+    bil2_src(oy, h, y0, y1, wy0, wy1); bil2_src(ox, w, x0, x1, wx0, wx1);
+    const size_t r0 = plane * ipx + (img * h + y0) * w, r1 = plane * ipx + (img * h + y1) * w;
+    Slot<T> a, b, c, d, r;
+    a.u = in[(r0 + x0) * RV + slot]; b.u = in[(r0 + x1) * RV + slot];
+    c.u = in[(r1 + x0) * RV + slot]; d.u = in[(r1 + x1) * RV + slot];
+#pragma unroll
+    for (int e = 0; e < Slot<T>::E; ++e)
+      r.v[e] = (T)(wy0 * (wx0 * (float)a.v[e] + wx1 * (float)b.v[e]) + wy1 * (wx0 * (float)c.v[e] + wx1 * (float)d.v[e]));
+    out[i] = r.u;
+  }
+}
+template <typename T>
+void op_bilinear2_planes(const T* in, T* out, int nplanes, int n, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(nplanes > 0 && n > 0 && h > 0 && w > 0, "bilinear x2: empty tensor");
+  const size_t total = (size_t)nplanes * n * (2 * h) * (2 * w) * sizeof(T);
+  SS4K_GLUE_ROUTE(sizeof(T) == 2 ? "frvsr::bilinear2_planes<half>" : "frvsr::bilinear2_planes<float>");
+  hipLaunchKernelGGL((k_bilinear2_planes<T>), grid_for(total), dim3(256), 0, st, reinterpret_cast<const uint4*>(in), reinterpret_cast<uint4*>(out),
+                     nplanes, n, h, w);
+  SS4K_LAUNCH_OK();
+}
+template void op_bilinear2_planes<float>(const float*, float*, int, int, int, int, hipStream_t);
+template void op_bilinear2_planes<__half>(const __half*, __half*, int, int, int, int, hipStream_t);
+
+// ------------------------------------------------------------------ tanh * 24, reflect pad on the right and at the bottom
+__global__ void k_flow_finish(const float* __restrict__ raw, float* __restrict__ flow, int n, int h8, int w8, int h, int w) {
+  const size_t total = (size_t)n * 2 * h * w;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % w), y = (int)((i / w) % h);
+    const size_t pl = i / ((size_t)w * h);
+    const int sx = x < w8 ? x : 2 * (w8 - 1) - x, sy = y < h8 ? y : 2 * (h8 - 1) - y;   // pad <= 7 <= size - 1: inside
+    flow[i] = tanhf(raw[(pl * h8 + sy) * w8 + sx]) * 24.f;
+  }
+}
+void op_flow_finish(const float* raw, float* flow, int n, int h8, int w8, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(n > 0 && h8 >= 8 && w8 >= 8 && h >= h8 && w >= w8 && h - h8 < 8 && w - w8 < 8, "flow pad: sizes");
+  SS4K_GLUE_ROUTE("frvsr::flow_finish");
+  hipLaunchKernelGGL(k_flow_finish, grid_for((size_t)n * 2 * h * w), dim3(256), 0, st, raw, flow, n, h8, w8, h, w);
+  SS4K_LAUNCH_OK();
+}
+
+// ------------------------------------------------------------------ BicubicUpsample(4) and backward_warp: shared arithmetic
+// kernels[d] = cubic . (1, s, s^2, s^3), s = d / 4, a = -0.75 (net_utils.py:126-140): tap i of phase d weighs input clamp(base - 1 + i)
+struct Bic4 { float k[4][4]; };
+static Bic4 bic4_taps() {
+  Bic4 t;
+  const float a = -0.75f;
+  const float cubic[4][4] = {{0, a, -2 * a, a}, {1, 0, -(a + 3), a + 2}, {0, -a, (2 * a + 3), -(a + 2)}, {0, 0, a, -a}};
+  for (int d = 0; d < 4; ++d) {
+    const float s = 1.0f * d / 4, p[4] = {1.f, s, s * s, s * s * s};
+    for (int i = 0; i < 4; ++i) {
+      float acc = 0.f;
+      for (int j = 0; j < 4; ++j) acc += cubic[i][j] * p[j];
+      t.k[d][i] = acc;
+    }
+  }
+  return t;
+}
+__device__ __forceinline__ float bic4_dot(const float k[4], float a, float b, float c, float d) {
+  return __fmaf_rn(k[3], d, __fmaf_rn(k[2], c, __fmaf_rn(k[1], b, __fmul_rn(k[0], a))));
+}
+// 4 x 4 neighbourhood of (y, x) with replicate padding (1, 2, 1, 2): rows clamp(y - 1 .. y + 2), columns clamp(x - 1 .. x + 2)
+__device__ __forceinline__ void bic4_load(const float* __restrict__ pl, int y, int x, int h, int w, float f[4][4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int yy = min(max(y - 1 + i, 0), h - 1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f[i][j] = pl[(size_t)yy * w + min(max(x - 1 + j, 0), w - 1)];
+  }
+}
+// output (4 y + sy, 4 x + sx): the height pass first, then the width pass (net_utils.py:153-163)
+__device__ __forceinline__ float bic4_at(const Bic4& t, const float f[4][4], int sy, int sx) {
+  float col[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) col[j] = bic4_dot(t.k[sy], f[0][j], f[1][j], f[2][j], f[3][j]);
+  return bic4_dot(t.k[sx], col[0], col[1], col[2], col[3]);
+}
+// sampling position of backward_warp in pixels, in the reference's order of operations: torch.linspace(-1, 1, size)[i] (ATen's
+// symmetric form) + flow / ((size - 1) / 2) (net_utils.py:62-72), then grid_sample's un-normalisation for align_corners=True,
+// ((g + 1) / 2) * (size - 1), and its border clip.  fminf / fmaxf drop a NaN flow: the position is always inside [0, size - 1]
+__device__ __forceinline__ float warp_pos(int i, int size, float flow) {
+  const float step = 2.f / (float)(size - 1);
+  const float lin = i < size / 2 ? __fmaf_rn(step, (float)i, -1.f) : __fmaf_rn(-step, (float)(size - i - 1), 1.f);   // (ATen's linspace fuses the multiply-add)
+  const float g = __fadd_rn(lin, __fdiv_rn(flow, (float)(((double)size - 1.0) / 2.0)));
+  const float p = __fmul_rn(__fdiv_rn(__fadd_rn(g, 1.f), 2.f), (float)(size - 1));
+  return fminf((float)(size - 1), fmaxf(p, 0.f));
+}
+struct WarpTaps { int x0, x1, y0, y1; float nw, ne, sw, se; };
+__device__ __forceinline__ WarpTaps warp_taps(int X, int Y, int W, int H, float fx, float fy) {
+  const float px = warp_pos(X, W, fx), py = warp_pos(Y, H, fy);
+  const float x0 = floorf(px), y0 = floorf(py);
+  const float ex = __fadd_rn(__fadd_rn(x0, 1.f), -px), ey = __fadd_rn(__fadd_rn(y0, 1.f), -py);   // ix_se - ix, iy_se - iy
+  const float dx = __fadd_rn(px, -x0), dy = __fadd_rn(py, -y0);
+  WarpTaps t;
+  t.x0 = (int)x0; t.y0 = (int)y0; t.x1 = min(t.x0 + 1, W - 1); t.y1 = min(t.y0 + 1, H - 1);   // (a tap past the border has weight 0)
+  t.nw = __fmul_rn(ex, ey); t.ne = __fmul_rn(dx, ey); t.sw = __fmul_rn(ex, dy); t.se = __fmul_rn(dx, dy);
+  return t;
+}
+__device__ __forceinline__ float warp_sample(const float* __restrict__ pl, int W, const WarpTaps& t) {
+  const float a = pl[(size_t)t.y0 * W + t.x0], b = pl[(size_t)t.y0 * W + t.x1], c = pl[(size_t)t.y1 * W + t.x0], d = pl[(size_t)t.y1 * W + t.x1];
+  return __fmaf_rn(d, t.se, __fmaf_rn(c, t.sw, __fmaf_rn(b, t.ne, __fmul_rn(a, t.nw))));
+}
+
+__global__ void k_bicubic_upsample4(const float* __restrict__ in, float* __restrict__ out, int planes, int h, int w, Bic4 taps) {
+  const int OW = 4 * w, OH = 4 * h;
+  const size_t total = (size_t)planes * OH * OW;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int X = (int)(i % OW), Y = (int)((i / OW) % OH);
+    const size_t pl = i / ((size_t)OW * OH);
+    float f[4][4];
+    bic4_load(in + pl * h * w, Y >> 2, X >> 2, h, w, f);
+    out[i] = bic4_at(taps, f, Y & 3, X & 3);
+  }
+}
+void op_bicubic_upsample4(const float* in, float* out, int planes, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(planes > 0 && h > 0 && w > 0 && h <= (1 << 28) && w <= (1 << 28), "bicubic x4: sizes");
+  SS4K_GLUE_ROUTE("frvsr::bicubic_upsample4");
+  hipLaunchKernelGGL(k_bicubic_upsample4, grid_for((size_t)planes * 16 * h * w), dim3(256), 0, st, in, out, planes, h, w, bic4_taps());
+  SS4K_LAUNCH_OK();
+}
+
+__global__ void k_backward_warp(const float* __restrict__ x, const float* __restrict__ flow, float* __restrict__ out, int n, int c, int h, int w) {
+  const size_t hw = (size_t)h * w, total = (size_t)n * hw;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int X = (int)(i % w), Y = (int)((i / w) % h);
+    const size_t img = i / hw, p = i - img * hw;
+    const WarpTaps t = warp_taps(X, Y, w, h, flow[(img * 2) * hw + p], flow[(img * 2 + 1) * hw + p]);
+    for (int k = 0; k < c; ++k) out[(img * c + k) * hw + p] = warp_sample(x + (img * c + k) * hw, w, t);
+  }
+}
+void op_backward_warp(const float* x, const float* flow, float* out, int n, int c, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(n > 0 && c > 0 && h >= 2 && w >= 2, "backward_warp: needs at least 2 x 2 pixels");
+  SS4K_GLUE_ROUTE("frvsr::backward_warp");
+  hipLaunchKernelGGL(k_backward_warp, grid_for((size_t)n * h * w), dim3(256), 0, st, x, flow, out, n, c, h, w);
+  SS4K_LAUNCH_OK();
+}
+
+// ------------------------------------------------------------------ flow x4 + warp + space-to-depth -> three planes
+// One thread per LR pixel: its 4 x 4 flow neighbourhood serves all 16 sub-pixels (the four phases of each pass read the same inputs), and
+// the 48 channels (sy * 4 + sx) * 3 + c it produces are exactly the three records it stores, with 16-byte stores.
+template <typename T>
+__global__ __launch_bounds__(256) void k_warp_s2d_planes(const float* __restrict__ lr_flow, const float* __restrict__ hr_prev, uint4* __restrict__ out, int n, int h,
+                                                         int w, Bic4 taps) {
+  constexpr int RV = sizeof(T);
+  const int H = 4 * h, W = 4 * w;
+  const size_t hw = (size_t)h * w, HW = (size_t)H * W, npix = (size_t)n * hw;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % w), y = (int)((i / w) % h);
+    const size_t img = i / hw;
+    union { T v[48]; uint4 u[3 * RV]; } rec;
+    float fu[4][4], fv[4][4];
+    bic4_load(lr_flow + (img * 2) * hw, y, x, h, w, fu);
+    bic4_load(lr_flow + (img * 2 + 1) * hw, y, x, h, w, fv);
+    const float* src = hr_prev + img * 3 * HW;
+#pragma unroll
+    for (int sy = 0; sy < 4; ++sy)
+#pragma unroll
+      for (int sx = 0; sx < 4; ++sx) {
+        const float u = __fmul_rn(4.f, bic4_at(taps, fu, sy, sx)), v = __fmul_rn(4.f, bic4_at(taps, fv, sy, sx));
+        const WarpTaps t = warp_taps(4 * x + sx, 4 * y + sy, W, H, u, v);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rec.v[(sy * 4 + sx) * 3 + c] = (T)warp_sample(src + c * HW, W, t);
+      }
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int q = 0; q < RV; ++q) out[((size_t)p * npix + i) * RV + q] = rec.u[p * RV + q];
+  }
+}
+template <typename T>
+void op_warp_s2d_planes(const float* lr_flow, const float* hr_prev, T* out, int n, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull, "warp: sizes");
+  SS4K_GLUE_ROUTE(sizeof(T) == 2 ? "frvsr::warp_s2d_planes<half>" : "frvsr::warp_s2d_planes<float>");
+  hipLaunchKernelGGL((k_warp_s2d_planes<T>), grid_for((size_t)n * h * w), dim3(256), 0, st, lr_flow, hr_prev, reinterpret_cast<uint4*>(out), n, h, w, bic4_taps());
+  SS4K_LAUNCH_OK();
+}
+template void op_warp_s2d_planes<float>(const float*, const float*, float*, int, int, int, hipStream_t);
+template void op_warp_s2d_planes<__half>(const float*, const float*, __half*, int, int, int, hipStream_t);
+
+// ------------------------------------------------------------------ PixelShuffle(4) + ReLU + Conv2d(4, 3, 3, 1, 1) -> fp32 NCHW
+// One thread per HR pixel.  Shuffled channel c of HR pixel (Y, X) is LR channel c * 16 + (Y % 4) * 4 + X % 4 of pixel (Y / 4, X / 4): element
+// (Y % 4) * 4 + X % 4 of plane c's record.  3 x 3 x 4 rectified values, 108 MACs in fp32, weights and biases in LDS; zero padding at the HR border.
+template <typename T>
+__global__ __launch_bounds__(256) void k_ps4_conv_tail(const T* __restrict__ in, const float* __restrict__ wb, float* __restrict__ out, int n, int h, int w) {
+  __shared__ float s_w[112];
+  if (threadIdx.x < 111) s_w[threadIdx.x] = wb[threadIdx.x];
+  __syncthreads();
+  const int H = 4 * h, W = 4 * w;
+  const size_t HW = (size_t)H * W, total = (size_t)n * HW, npix = (size_t)n * h * w;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int X = (int)(i % W), Y = (int)((i / W) % H);
+    const size_t img = i / HW;
+    float acc[3] = {s_w[108], s_w[109], s_w[110]};
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const int yy = Y + ky - 1;
+      if (yy < 0 || yy >= H) continue;
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int xx = X + kx - 1;
+        if (xx < 0 || xx >= W) continue;
+        const size_t pix = (img * h + (yy >> 2)) * w + (xx >> 2);
+        const int sub = (yy & 3) * 4 + (xx & 3);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float v = fmaxf((float)in[((size_t)c * npix + pix) * 16 + sub], 0.f);
+#pragma unroll
+          for (int o = 0; o < 3; ++o) acc[o] = fmaf(s_w[((o * 4 + c) * 3 + ky) * 3 + kx], v, acc[o]);
+        }
+      }
+    }
+    const size_t p = i - img * HW;
+#pragma unroll
+    for (int o = 0; o < 3; ++o) out[(img * 3 + o) * HW + p] = acc[o];
+  }
+}
+template <typename T>
+void op_ps4_conv_tail(const T* in, const float* wb, float* out, int n, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "tail: sizes");
+  SS4K_GLUE_ROUTE(sizeof(T) == 2 ? "frvsr::ps4_conv_tail<half>" : "frvsr::ps4_conv_tail<float>");
+  hipLaunchKernelGGL((k_ps4_conv_tail<T>), grid_for((size_t)n * 16 * h * w), dim3(256), 0, st, in, wb, out, n, h, w);
+  SS4K_LAUNCH_OK();
+}
+template void op_ps4_conv_tail<float>(const float*, const float*, float*, int, int, int, hipStream_t);
+template void op_ps4_conv_tail<__half>(const __half*, const float*, float*, int, int, int, hipStream_t);
+
+// ------------------------------------------------------------------ planes -> fp32 NCHW (parity taps), clamp into another tensor
+template <typename T>
+__global__ void k_planes_to_nchw(const T* __restrict__ in, float* __restrict__ out, int n, int channels, int h, int w) {
+  const size_t hw = (size_t)h * w, npix = (size_t)n * hw, total = npix * channels;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t p = i % hw, k = (i / hw) % channels, img = i / (hw * channels);
+    out[i] = (float)in[((k / 16) * npix + img * hw + p) * 16 + (k % 16)];
+  }
+}
+template <typename T>
+void op_planes_to_nchw(const T* in, float* out, int n, int channels, int h, int w, hipStream_t st) {
+  SS4K_GLUE_ROUTE(sizeof(T) == 2 ? "frvsr::planes_to_nchw<half>" : "frvsr::planes_to_nchw<float>");
+  hipLaunchKernelGGL((k_planes_to_nchw<T>), grid_for((size_t)n * channels * h * w), dim3(256), 0, st, in, out, n, channels, h, w);
+  SS4K_LAUNCH_OK();
+}
+template void op_planes_to_nchw<float>(const float*, float*, int, int, int, int, hipStream_t);
+template void op_planes_to_nchw<__half>(const __half*, float*, int, int, int, int, hipStream_t);
+
+__global__ void k_clamp01_to(const float* __restrict__ in, float* __restrict__ out, size_t n) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = fminf(fmaxf(in[i], 0.f), 1.f);
+}
+void op_clamp01_to(const float* in, float* out, size_t n, hipStream_t st) {
+  SS4K_GLUE_ROUTE("frvsr::clamp01_to");
+  hipLaunchKernelGGL(k_clamp01_to, grid_for(n), dim3(256), 0, st, in, out, n);
+  SS4K_LAUNCH_OK();
+}
+
+}  // namespace ss4k

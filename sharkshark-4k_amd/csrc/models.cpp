@@ -15,13 +15,7 @@ static int pad16(int c) { return (c + 15) / 16 * 16; }
 // ------------------------------------------------------------------------------------------
 // parameter bookkeeping (must mirror weights.py: *_keys order)
 // ------------------------------------------------------------------------------------------
-struct ParamCursor {
-  const float* base; size_t n, pos = 0;
-  const float* take(size_t k) {
-    SS4K_REQUIRE(pos + k <= n, "weight blob shorter than the model's state_dict");
-    const float* p = base + pos; pos += k; return p;
-  }
-};
+// (ParamCursor: models.h)
 
 static std::vector<std::pair<int, int>> bsvd_denblock_shapes(const int* chns, int in_ch, int out_ch, int interm) {
   const int c0 = chns[0], c1 = chns[1], c2 = chns[2];

@@ -27,7 +27,14 @@ struct ConvOpts {
   Tens out{nullptr, 0, 0};
 };
 
-struct ParamCursor;
+// walks a state_dict blob in key order (models.cpp, frvsr.cpp)
+struct ParamCursor {
+  const float* base; size_t n, pos = 0;
+  const float* take(size_t k) {
+    SS4K_REQUIRE(pos + k <= n, "weight blob shorter than the model's state_dict");
+    const float* p = base + pos; pos += k; return p;
+  }
+};
 size_t model_param_count(const ss4k_model_desc& d);
 
 struct Model {

@@ -4,6 +4,7 @@ Reference seams replaced (each returns a callable ``model(x: NCHW float) -> NCHW
   * ``build_model_fsrcnn``  <- ``src/upscale/model/fsrcnn/factory.py:5-71``
   * ``build_model_esrgan``  <- ``src/upscale/model/realesrgan/factory.py:108-234``
   * ``build_denoise_model`` <- ``src/upscale/model/bsvd/factory.py:21-83``
+  * ``build_model_egvsr``   <- ``src/upscale/egvsr_upscaler.py:12-29`` (``model(lr_curr, lr_prev, hr_prev)``)
 The reference downloads / loads ``.pth`` checkpoints (``fsrcnn/factory.py:8-13``,
 ``realesrgan/factory.py:140-170``, ``bsvd/factory.py:31-36``).  Here every factory takes ``weights``:
 
@@ -196,3 +197,26 @@ def build_denoise_model(ctx: _capi.Context, weights: WeightSpec = None, dtype="f
     ``fsrcnn_upscaler.py:277``).  ``stream=True``: ``BSVD.forward`` on ``(N,F,4,H,W)`` clips, all N*F
     frames run through the bidirectional buffers as one stream (``bsvd/model.py:515-580``)."""
     return _capi.Model(ctx, denoise_desc(dtype, stream, variant, flags), denoise_flat(weights, seed, variant, checkpoint_dir))
+
+
+# ---- EGVSR's FRNet (egvsr_upscaler.py:12-29: FRNet(in_nc=3, out_nc=3, nf=64, nb=10, degradation='BD', scale=4) + EGVSR_iter420000.pth)
+EGVSR_CHECKPOINT = "EGVSR_iter420000.pth"
+
+
+def egvsr_desc(dtype="f16", nb: int = 10):
+    return _capi.make_frvsr_desc(_dtype(dtype), 64, nb)
+
+
+def egvsr_flat(weights: WeightSpec = None, seed: int = 0, checkpoint_dir: Optional[str] = None, nb: int = 10) -> np.ndarray:
+    if isinstance(weights, str) and weights == SYNTHETIC:
+        table = W.frnet_table(seed, nb=nb)
+    else:
+        kind, obj = _load_checkpoint(weights, "EGVSR", EGVSR_CHECKPOINT, checkpoint_dir)
+        table = CK.egvsr_from_checkpoint(obj, nb) if kind == "ckpt" else obj
+    return W.flatten(table, W.frnet_keys(nb))
+
+
+def build_model_egvsr(ctx: _capi.Context, weights: WeightSpec = None, seed: int = 0, checkpoint_dir: Optional[str] = None,
+                      dtype="f16", nb: int = 10):
+    """The callable behind ``self.model(lr_curr, self.lr_prev, self.hr_prev)`` (egvsr_upscaler.py:204)."""
+    return _capi.Frvsr(ctx, egvsr_desc(dtype, nb), egvsr_flat(weights, seed, checkpoint_dir, nb))

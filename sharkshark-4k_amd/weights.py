@@ -186,6 +186,58 @@ def bsvd_table(seed: int = 0, **kw) -> Table:
 
 
 # --------------------------------------------------------------------------------------
+# FRNet as built by the EGVSR service (reference: src/upscale/model/egvsr/egvsr.py:146-162, egvsr_upscaler.py:26)
+# --------------------------------------------------------------------------------------
+_FNET_CONVS = [("encoder1.0", 32, 6), ("encoder1.2", 32, 32), ("encoder2.0", 64, 32), ("encoder2.2", 64, 64),
+               ("encoder3.0", 128, 64), ("encoder3.2", 128, 128), ("decoder1.0", 256, 128), ("decoder1.2", 256, 256),
+               ("decoder2.0", 128, 256), ("decoder2.2", 128, 128), ("decoder3.0", 64, 128), ("decoder3.2", 64, 64),
+               ("flow.0", 32, 64), ("flow.2", 2, 32)]
+
+
+def frnet_keys(nb: int = 10) -> List[str]:
+    """FRNet(degradation='BD').state_dict() order: the two ``upsample_func.kernels`` buffers and ``srnet.conv_up.*`` are in the
+    state_dict although ``forward`` never reads them (egvsr.py:116-120,141)."""
+    keys = ["upsample_func.kernels"]
+    for name, _, _ in _FNET_CONVS:
+        keys += [f"fnet.{name}.weight", f"fnet.{name}.bias"]
+    keys += ["srnet.conv_in.0.weight", "srnet.conv_in.0.bias"]
+    for b in range(nb):
+        for c in (0, 2):
+            keys += [f"srnet.resblocks.{b}.conv.{c}.weight", f"srnet.resblocks.{b}.conv.{c}.bias"]
+    for c in (0, 2):
+        keys += [f"srnet.conv_up.{c}.weight", f"srnet.conv_up.{c}.bias"]
+    keys += ["srnet.conv_out.weight", "srnet.conv_out.bias", "srnet.upsample_func.kernels"]
+    return keys
+
+
+def bicubic_upsample_kernels(scale: int = 4, a: float = -0.75) -> np.ndarray:
+    """The ``kernels`` buffer of BicubicUpsample (utils/net_utils.py:129-144): cubic . (1, s, s^2, s^3) for s = d / scale."""
+    cubic = np.array([[0, a, -2 * a, a], [1, 0, -(a + 3), a + 2], [0, -a, (2 * a + 3), -(a + 2)], [0, 0, a, -a]], dtype=np.float32)
+    return np.stack([cubic @ np.array([1, s, s ** 2, s ** 3], dtype=np.float32) for s in [1.0 * d / scale for d in range(scale)]]).astype(np.float32)
+
+
+def frnet_table(seed: int = 0, nf: int = 64, nb: int = 10, flow_gain: float = 1.0) -> Table:
+    """``flow_gain`` scales ``fnet.flow.2.weight`` (tests want flows of several pixels: tests/golden/egvsr/MANIFEST.json records what
+    each fixture's flow measures)."""
+    t: Table = OrderedDict()
+    t["upsample_func.kernels"] = bicubic_upsample_kernels()
+    for name, cout, cin in _FNET_CONVS:
+        _conv(t, seed, f"fnet.{name}", cout, cin, 3)
+    # the flow is tanh(conv) * 24 (egvsr.py:76): at kaiming scale the output conv saturates it; damped so that gain 1 leaves flows of a pixel
+    # or two on smooth frames and gain 16 several pixels, unsaturated
+    t["fnet.flow.2.weight"] = (t["fnet.flow.2.weight"] * np.float32(0.05) * np.float32(flow_gain)).astype(np.float32)
+    _conv(t, seed, "srnet.conv_in.0", nf, 51, 3)
+    for b in range(nb):
+        _conv(t, seed, f"srnet.resblocks.{b}.conv.0", nf, nf, 3)
+        _conv(t, seed, f"srnet.resblocks.{b}.conv.2", nf, nf, 3, gain=0.3)
+    for c in (0, 2):   # ConvTranspose2d weights (C_in, C_out, kH, kW): unused by forward
+        _conv(t, seed, f"srnet.conv_up.{c}", nf, nf, 3)
+    _conv(t, seed, "srnet.conv_out", 3, nf // 16, 3)
+    t["srnet.upsample_func.kernels"] = bicubic_upsample_kernels()
+    return OrderedDict((k, t[k]) for k in frnet_keys(nb))
+
+
+# --------------------------------------------------------------------------------------
 # flat blob <-> table
 # --------------------------------------------------------------------------------------
 def flatten(table: Table, keys: Iterable[str]) -> np.ndarray:

@@ -1,0 +1,131 @@
+"""Oracle of the frame-recurrent upscaler: functional PyTorch-CPU restatement of EGVSR's FRNet and of the service around it.
+TEST INFRASTRUCTURE ONLY.  Paths are relative to the reference repository's ``src/upscale``.
+
+``w`` is a mapping ``state_dict key -> ndarray`` in the reference's key names (``sharkshark-4k_amd/weights.py: frnet_table``).  Held
+bit-exact against the reference's own modules on every fixture of ``tests/golden/egvsr`` (``tests/test_egvsr_oracle_cpu.py``), so that GPU
+tests may use shapes that have no fixture.
+"""
+from __future__ import annotations
+
+from typing import Mapping, Optional
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+
+def _t(v) -> torch.Tensor:
+    return v.detach().float() if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v), dtype=np.float32))
+
+
+def _conv(x, w, name):
+    return F.conv2d(x, _t(w[name + ".weight"]), _t(w[name + ".bias"]), stride=1, padding=1)
+
+
+def fnet(x1, x2, w: Mapping) -> torch.Tensor:
+    """FNet.forward (model/egvsr/egvsr.py:63-78); layers :19-61."""
+    def pair(x, name):
+        return F.leaky_relu(_conv(F.leaky_relu(_conv(x, w, f"fnet.{name}.0"), 0.2), w, f"fnet.{name}.2"), 0.2)
+    out = F.max_pool2d(pair(torch.cat([x1, x2], dim=1), "encoder1"), 2, 2)
+    out = F.max_pool2d(pair(out, "encoder2"), 2, 2)
+    out = F.max_pool2d(pair(out, "encoder3"), 2, 2)
+    for name in ("decoder1", "decoder2", "decoder3"):
+        out = F.interpolate(pair(out, name), scale_factor=2.0, mode="bilinear", align_corners=False)
+    out = _conv(F.leaky_relu(_conv(out, w, "fnet.flow.0"), 0.2), w, "fnet.flow.2")
+    return torch.tanh(out) * 24
+
+
+def bicubic_upsample4(x, kernels=None) -> torch.Tensor:
+    """BicubicUpsample(4).forward (model/egvsr/utils/net_utils.py:146-165); the ``kernels`` buffer :129-144."""
+    s = 4
+    if kernels is None:
+        a = -0.75
+        cubic = torch.FloatTensor([[0, a, -2 * a, a], [1, 0, -(a + 3), a + 2], [0, -a, (2 * a + 3), -(a + 2)], [0, 0, a, -a]])
+        kernels = torch.stack([torch.matmul(cubic, torch.FloatTensor([1, t, t ** 2, t ** 3])) for t in [1.0 * d / s for d in range(s)]])
+    kernels = _t(kernels)
+    n, c, h, w = x.size()
+    x = F.pad(x, (1, 2, 1, 2), mode="replicate")
+    kernel_h = kernels.repeat(c, 1).view(-1, 1, s, 1)
+    out = F.conv2d(x, kernel_h, stride=1, padding=0, groups=c)
+    out = out.reshape(n, c, s, -1, w + 3).permute(0, 1, 3, 2, 4).reshape(n, c, -1, w + 3)
+    kernel_w = kernels.repeat(c, 1).view(-1, 1, 1, s)
+    out = F.conv2d(out, kernel_w, stride=1, padding=0, groups=c)
+    return out.reshape(n, c, s, h * s, -1).permute(0, 1, 3, 4, 2).reshape(n, c, h * s, -1)
+
+
+def backward_warp(x, flow) -> torch.Tensor:
+    """backward_warp (model/egvsr/utils/net_utils.py:50-93)."""
+    n, c, h, w = x.size()
+    iu = torch.linspace(-1.0, 1.0, w).view(1, 1, 1, w).expand(n, -1, h, -1)
+    iv = torch.linspace(-1.0, 1.0, h).view(1, 1, h, 1).expand(n, -1, -1, w)
+    grid = torch.cat([iu, iv], 1)
+    flow = torch.cat([flow[:, 0:1, ...] / ((w - 1.0) / 2.0), flow[:, 1:2, ...] / ((h - 1.0) / 2.0)], dim=1)
+    grid = (grid + flow).permute(0, 2, 3, 1)
+    return F.grid_sample(x, grid, mode="bilinear", padding_mode="border", align_corners=True)
+
+
+def space_to_depth4(x) -> torch.Tensor:
+    """egvsr.py:203-208: channel (sy * 4 + sx) * c + k."""
+    n, c, in_h, in_w = x.size()
+    out_h, out_w = in_h // 4, in_w // 4
+    return x.reshape(n, c, out_h, 4, out_w, 4).permute(0, 3, 5, 1, 2, 4).reshape(n, 16 * c, out_h, out_w)
+
+
+def srnet(lr_curr, hr_prev_tran, w: Mapping, nb: int) -> torch.Tensor:
+    """SRNet.forward (egvsr.py:132-143); layers :108-127, ResidualBlock :88-96."""
+    out = F.relu(_conv(torch.cat([lr_curr, hr_prev_tran], dim=1), w, "srnet.conv_in.0"))
+    for b in range(nb):
+        out = _conv(F.relu(_conv(out, w, f"srnet.resblocks.{b}.conv.0")), w, f"srnet.resblocks.{b}.conv.2") + out
+    out = F.relu(F.pixel_shuffle(out, 4))
+    return _conv(out, w, "srnet.conv_out")
+
+
+def frnet_step(lr_curr, lr_prev, hr_prev, w: Mapping, nb: int, taps: Optional[dict] = None) -> torch.Tensor:
+    """FRNet.forward (egvsr.py:180-212) with degradation='BD', scale=4.  ``taps``: receives lr_flow (padded) and the warped,
+    space-to-depth tensor."""
+    with torch.no_grad():
+        lr_flow = fnet(lr_curr, lr_prev, w)
+        pad_h = lr_curr.size(2) - lr_curr.size(2) // 8 * 8
+        pad_w = lr_curr.size(3) - lr_curr.size(3) // 8 * 8
+        lr_flow_pad = F.pad(lr_flow, (0, pad_w, 0, pad_h), "reflect")
+        hr_flow = 4 * bicubic_upsample4(lr_flow_pad, w.get("upsample_func.kernels"))
+        s2d = space_to_depth4(backward_warp(hr_prev, hr_flow))
+        if taps is not None:
+            taps["lr_flow"], taps["s2d"] = lr_flow_pad, s2d
+        return srnet(lr_curr, s2d, w, nb)
+
+
+class OracleEgvsrUpscaler:
+    """EgvsrUpscalerService.upscale / upscale_single (egvsr_upscaler.py:172-212) on the CPU."""
+
+    def __init__(self, w: Mapping, nb: int, lr_shape, output_shape=None):
+        self.w, self.nb, self.lr_shape, self.output_shape = w, nb, tuple(lr_shape), output_shape
+        self.hr_shape = tuple(4 * i for i in self.lr_shape)
+        self.lr_prev = self.hr_prev = None
+        self.taps: dict = {}
+
+    def reset(self):
+        self.lr_prev = self.hr_prev = None
+
+    def upscale_single(self, img: torch.Tensor) -> torch.Tensor:
+        with torch.no_grad():
+            img = img.permute(2, 0, 1).unsqueeze(0)
+            img = img / 255.0
+            lr_curr = F.interpolate(img, size=self.lr_shape, mode="area")
+            if self.lr_prev is None:
+                self.lr_prev = torch.zeros_like(lr_curr)
+            if self.hr_prev is None:
+                self.hr_prev = torch.zeros((1, 3, self.hr_shape[0], self.hr_shape[1]), dtype=lr_curr.dtype)
+            hr_curr = frnet_step(lr_curr, self.lr_prev, self.hr_prev, self.w, self.nb, self.taps)
+            self.taps["lr_curr"], self.taps["hr_curr"] = lr_curr, hr_curr
+            self.hr_prev = hr_curr
+            self.lr_prev = lr_curr
+            _hr_curr = torch.clamp(hr_curr, 0, 1)
+            if self.output_shape is not None:
+                _hr_curr = F.interpolate(_hr_curr, size=self.output_shape, mode="area")
+            return (_hr_curr * 255)[0].permute(1, 2, 0).to(torch.uint8)
+
+    def upscale(self, frames: torch.Tensor) -> torch.Tensor:
+        if frames.ndim == 3:
+            return self.upscale_single(frames)
+        return torch.stack([self.upscale_single(frames[i]) for i in range(frames.shape[0])], dim=0)
