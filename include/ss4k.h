@@ -268,16 +268,34 @@ int ss4k_frvsr_prof_read(ss4k_frvsr* m, int stage, double* total_ms);
 /* The service path.  Replaces EgvsrUpscalerService.proc_init / upscale (egvsr_upscaler.py:159-212): lr_shape = (lr_h, lr_w), output_shape =
  * (out_h, out_w), 0, 0 = None.  The n frames of ss4k_frvsr_upscale_frames are CONSECUTIVE FRAMES OF ONE STREAM, processed in order (:182-186); the
  * state (lr_prev, hr_prev) is carried across calls, so a stream must stay on one object.  Per frame (:192-212): / 255, area to lr_shape, step, the state
- * keeps the unclamped output, clamp to [0, 1], F.interpolate(mode='area') to the output shape if set, * 255 truncated to uint8 HWC. */
+ * keeps the unclamped output, clamp to [0, 1], F.interpolate(mode='area') to the output shape if set, * 255 truncated to uint8 HWC.
+ *
+ * One object serves up to SS4K_FRVSR_MAX_STREAMS streams.  It has max_streams SLOTS, each with the recurrent state of one stream (allocated
+ * on the slot's first frame: 2 x (lr + hr) fp32, 376 MB at lr 720 x 1280); which stream sits in which slot is the caller's business.
+ * ss4k_frvsr_upscale_streams runs one ROUND: one frame for each of n_streams DISTINCT slots, as ONE step of n_streams items - every conv, pool,
+ * x2, flow, warp and tail launch covers the whole round, and the streams' HR state is read and written where it lives (never gathered into a
+ * batch).  in: (n_streams, h, w, 3) uint8; out: (n_streams, out_h, out_w, 3) uint8, item i belonging to slots[i].  Each stream's frames are bit for
+ * bit what an object of its own would have produced.  SS4K_EINVAL - and no slot's state changed - for a slot outside 0..max_streams-1, a slot
+ * named twice, n_streams outside 1..max_streams, a too small output buffer, or a round of 2^31 or more output pixels per plane
+ * (n_streams x 16 lr_h lr_w).  ss4k_frvsr_upscaler_create is max_streams = 1; ss4k_frvsr_upscale_frames on any object is the stream of slot 0. */
+#define SS4K_FRVSR_MAX_STREAMS 64
 int ss4k_frvsr_upscaler_create(ss4k_ctx* ctx, ss4k_frvsr* m, int lr_h, int lr_w, int out_h, int out_w, ss4k_frvsr_upscaler** out);
+int ss4k_frvsr_upscaler_create_streams(ss4k_ctx* ctx, ss4k_frvsr* m, int lr_h, int lr_w, int out_h, int out_w, int max_streams,
+                                       ss4k_frvsr_upscaler** out);
 void ss4k_frvsr_upscaler_destroy(ss4k_frvsr_upscaler* up);
-/* the next frame sees zero lr_prev / hr_prev (egvsr_upscaler.py:197-202) */
+/* the next frame of EVERY slot sees zero lr_prev / hr_prev (egvsr_upscaler.py:197-202); _reset_stream: of that slot only */
 int ss4k_frvsr_upscaler_reset(ss4k_frvsr_upscaler* up);
+int ss4k_frvsr_upscaler_reset_stream(ss4k_frvsr_upscaler* up, int slot);
 int ss4k_frvsr_upscaler_out_shape(const ss4k_frvsr_upscaler* up, int* out_h, int* out_w);
+/* device bytes of recurrent state the object holds now (slots that never saw a frame hold none; a reset frees nothing) */
+int ss4k_frvsr_upscaler_state_bytes(const ss4k_frvsr_upscaler* up, size_t* bytes);
 int ss4k_frvsr_upscale_frames(ss4k_frvsr_upscaler* up, const uint8_t* in_nhwc_dev, int n, int h, int w, uint8_t* out_nhwc_dev,
                               size_t out_capacity_bytes, void* hip_stream);
-/* Parity taps of the LAST frame of the last call, fp32 NCHW: 0 = lr_curr, 1 = lr flow (padded, (1, 2, h, w)), 2 = the warped and space-to-depth
- * tensor (1, 48, h, w), 3 = hr_curr (unclamped).  As ss4k_upscaler_enable_taps / _read_tap. */
+int ss4k_frvsr_upscale_streams(ss4k_frvsr_upscaler* up, const int32_t* slots, int n_streams, const uint8_t* in_nhwc_dev, int h, int w,
+                               uint8_t* out_nhwc_dev, size_t out_capacity_bytes, void* hip_stream);
+/* Parity taps of the LAST frame of the last call - after ss4k_frvsr_upscale_streams: of the LAST ITEM of the last round -, fp32 NCHW: 0 = lr_curr,
+ * 1 = lr flow (padded, (1, 2, h, w)), 2 = the warped and space-to-depth tensor (1, 48, h, w), 3 = hr_curr (unclamped).  As
+ * ss4k_upscaler_enable_taps / _read_tap. */
 int ss4k_frvsr_upscaler_enable_taps(ss4k_frvsr_upscaler* up, int enable);
 int ss4k_frvsr_upscaler_read_tap(ss4k_frvsr_upscaler* up, int which, float* out_dev, size_t capacity_floats, int dims[4], void* hip_stream);
 

@@ -33,6 +33,7 @@ SYMBOLS = [
     "ss4k_frvsr_prof_enable", "ss4k_frvsr_prof_read", "ss4k_frvsr_upscaler_create", "ss4k_frvsr_upscaler_destroy",
     "ss4k_frvsr_upscaler_reset", "ss4k_frvsr_upscaler_out_shape", "ss4k_frvsr_upscale_frames", "ss4k_frvsr_upscaler_enable_taps",
     "ss4k_frvsr_upscaler_read_tap", "ss4k_op_backward_warp", "ss4k_op_bicubic_upsample4",
+    "ss4k_frvsr_upscaler_create_streams", "ss4k_frvsr_upscale_streams", "ss4k_frvsr_upscaler_reset_stream", "ss4k_frvsr_upscaler_state_bytes",
 ]
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
@@ -186,6 +187,11 @@ def load(path: str) -> C.CDLL:
         L.ss4k_frvsr_upscaler_read_tap.argtypes = [vp, i, vp, sz, C.POINTER(i * 4), vp]
         L.ss4k_op_backward_warp.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
         L.ss4k_op_bicubic_upsample4.argtypes = [vp, vp, vp, i, i, i, vp]
+    if hasattr(L, "ss4k_frvsr_upscale_streams"):   # (absent from builds before the stream slots)
+        L.ss4k_frvsr_upscaler_create_streams.argtypes = [vp, vp, i, i, i, i, i, C.POINTER(vp)]
+        L.ss4k_frvsr_upscale_streams.argtypes = [vp, C.POINTER(C.c_int32), i, vp, i, i, vp, sz, vp]
+        L.ss4k_frvsr_upscaler_reset_stream.argtypes = [vp, i]
+        L.ss4k_frvsr_upscaler_state_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     return L
 
 
@@ -570,6 +576,7 @@ class Upscaler:
         return out
 
 
+FRVSR_MAX_STREAMS = 64   # SS4K_FRVSR_MAX_STREAMS (include/ss4k.h)
 FRV_STAGES = ("fnet_conv", "srnet_conv", "pool_up", "flow_finish", "warp", "tail", "glue")
 
 
@@ -640,13 +647,17 @@ class Frvsr:
 
 
 class FrvsrUpscaler:
-    """ss4k_frvsr_upscaler: EgvsrUpscalerService.upscale (egvsr_upscaler.py:172-212), uint8 NHWC frames of ONE stream in order -> uint8 NHWC."""
+    """ss4k_frvsr_upscaler: EgvsrUpscalerService.upscale (egvsr_upscaler.py:172-212), uint8 NHWC frames of ONE stream in order -> uint8 NHWC;
+    with ``max_streams`` > 1 also rounds of one frame per stream slot (``upscale_streams``).  Calling the object drives slot 0."""
 
-    def __init__(self, ctx: Context, model: Frvsr, lr_shape, output_shape=None):
-        self.ctx, self.model = ctx, model
+    def __init__(self, ctx: Context, model: Frvsr, lr_shape, output_shape=None, max_streams: int = 1):
+        self.ctx, self.model, self.max_streams = ctx, model, int(max_streams)
         oh, ow = (0, 0) if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
         h = C.c_void_p()
-        _check(lib().ss4k_frvsr_upscaler_create(ctx._h, model._h, int(lr_shape[0]), int(lr_shape[1]), oh, ow, C.byref(h)))
+        if self.max_streams == 1:   # (the entry point every build of the library has: tools/lib_ab.py loads older ones)
+            _check(lib().ss4k_frvsr_upscaler_create(ctx._h, model._h, int(lr_shape[0]), int(lr_shape[1]), oh, ow, C.byref(h)))
+        else:
+            _check(lib().ss4k_frvsr_upscaler_create_streams(ctx._h, model._h, int(lr_shape[0]), int(lr_shape[1]), oh, ow, self.max_streams, C.byref(h)))
         self._h = h
 
     def close(self):
@@ -660,8 +671,18 @@ class FrvsrUpscaler:
         except Exception:
             pass
 
-    def reset(self):
-        _check(lib().ss4k_frvsr_upscaler_reset(self._h))
+    def reset(self, slot: Optional[int] = None):
+        """Forget the state of every slot, or of ``slot`` only."""
+        if slot is None:
+            _check(lib().ss4k_frvsr_upscaler_reset(self._h))
+        else:
+            _check(lib().ss4k_frvsr_upscaler_reset_stream(self._h, int(slot)))
+
+    def state_bytes(self) -> int:
+        """Device bytes of recurrent state held now (slots that never saw a frame hold none)."""
+        b = C.c_size_t()
+        _check(lib().ss4k_frvsr_upscaler_state_bytes(self._h, C.byref(b)))
+        return int(b.value)
 
     def out_shape(self):
         oh, ow = C.c_int(), C.c_int()
@@ -687,4 +708,20 @@ class FrvsrUpscaler:
             out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
         with torch.cuda.device(self.ctx.device):
             _check(lib().ss4k_frvsr_upscale_frames(self._h, frames.data_ptr(), n, h, w, out.data_ptr(), out.numel(), _stream()))
+        return out
+
+    def upscale_streams(self, frames: torch.Tensor, slots: Sequence[int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One round: ``frames[i]`` is the next frame of the stream in slot ``slots[i]`` (distinct slots); returns ``(len(slots), oh, ow, 3)``
+        in the same order.  The round runs as one batched step (ss4k_frvsr_upscale_streams)."""
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.ndim == 4 and frames.shape[-1] == 3
+        frames = frames.contiguous()
+        n, h, w, _ = frames.shape
+        slots = [int(s) for s in slots]
+        assert len(slots) == n, "one slot per frame"
+        oh, ow = self.out_shape()
+        if out is None:
+            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
+        ids = (C.c_int32 * max(n, 1))(*slots)
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_frvsr_upscale_streams(self._h, ids, n, frames.data_ptr(), h, w, out.data_ptr(), out.numel(), _stream()))
         return out

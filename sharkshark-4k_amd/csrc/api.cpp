@@ -605,22 +605,41 @@ int ss4k_frvsr_prof_read(ss4k_frvsr* m, int stage, double* ms) {
     *ms = m->f.stage_ms[stage];
   });
 }
-int ss4k_frvsr_upscaler_create(ss4k_ctx* ctx, ss4k_frvsr* m, int lr_h, int lr_w, int out_h, int out_w, ss4k_frvsr_upscaler** out) {
+int ss4k_frvsr_upscaler_create_streams(ss4k_ctx* ctx, ss4k_frvsr* m, int lr_h, int lr_w, int out_h, int out_w, int max_streams, ss4k_frvsr_upscaler** out) {
   return guard([&] {
-    SS4K_REQUIRE(ctx && m && out, "ss4k_frvsr_upscaler_create: NULL argument");
+    SS4K_REQUIRE(ctx && m && out, "ss4k_frvsr_upscaler_create[_streams]: NULL argument");
     SS4K_REQUIRE(lr_h >= 8 && lr_w >= 8, "lr_shape must be at least 8 x 8");
     SS4K_REQUIRE((out_h == 0 && out_w == 0) || (out_h > 0 && out_w > 0), "output_shape is (0, 0) or positive");
     SS4K_REQUIRE((double)lr_h * lr_w * 16.0 < 2147483648.0, "lr_shape: the output frame must hold fewer than 2^31 pixels");
+    SS4K_REQUIRE(max_streams >= 1 && max_streams <= SS4K_FRVSR_MAX_STREAMS, "max_streams must be in 1..64 (SS4K_FRVSR_MAX_STREAMS)");
     auto u = std::make_unique<ss4k_frvsr_upscaler>();
     u->u.ctx = ctx; u->u.m = &m->f; u->u.lr_h = lr_h; u->u.lr_w = lr_w; u->u.out_h = out_h; u->u.out_w = out_w;
+    u->u.slots.resize((size_t)max_streams);
 #ifdef SS4K_DEV
-    for (DevBuf* b : {&u->u.img, &u->u.hrc, &u->u.outf}) b->transient = true;   // (lr[] and hr[] carry the recurrent state across calls)
+    for (DevBuf* b : {&u->u.img, &u->u.hrc, &u->u.outf}) b->transient = true;   // (the slots' lr[] and hr[] carry the recurrent state across calls)
 #endif
     *out = u.release();
   });
 }
+int ss4k_frvsr_upscaler_create(ss4k_ctx* ctx, ss4k_frvsr* m, int lr_h, int lr_w, int out_h, int out_w, ss4k_frvsr_upscaler** out) {
+  return ss4k_frvsr_upscaler_create_streams(ctx, m, lr_h, lr_w, out_h, out_w, 1, out);
+}
 void ss4k_frvsr_upscaler_destroy(ss4k_frvsr_upscaler* up) { delete up; }
-int ss4k_frvsr_upscaler_reset(ss4k_frvsr_upscaler* up) { if (!up) return SS4K_EINVAL; up->u.have_state = false; return SS4K_OK; }
+int ss4k_frvsr_upscaler_reset(ss4k_frvsr_upscaler* up) {
+  if (!up) return SS4K_EINVAL;
+  for (auto& s : up->u.slots) s.have_state = false;
+  return SS4K_OK;
+}
+int ss4k_frvsr_upscaler_reset_stream(ss4k_frvsr_upscaler* up, int slot) {
+  return guard([&] {
+    SS4K_REQUIRE(up, "ss4k_frvsr_upscaler_reset_stream: NULL argument");
+    SS4K_REQUIRE(slot >= 0 && slot < (int)up->u.slots.size(), "ss4k_frvsr_upscaler_reset_stream: slot outside 0..max_streams-1");
+    up->u.slots[(size_t)slot].have_state = false;
+  });
+}
+int ss4k_frvsr_upscaler_state_bytes(const ss4k_frvsr_upscaler* up, size_t* bytes) {
+  return guard([&] { SS4K_REQUIRE(up && bytes, "ss4k_frvsr_upscaler_state_bytes: NULL argument"); *bytes = up->u.state_bytes(); });
+}
 int ss4k_frvsr_upscaler_out_shape(const ss4k_frvsr_upscaler* up, int* oh, int* ow) {
   return guard([&] { SS4K_REQUIRE(up && oh && ow, "NULL argument"); up->u.out_shape(oh, ow); });
 }
@@ -631,6 +650,18 @@ int ss4k_frvsr_upscale_frames(ss4k_frvsr_upscaler* up, const uint8_t* in, int n,
     int oh, ow; up->u.out_shape(&oh, &ow);
     SS4K_REQUIRE(cap >= (size_t)oh * ow * 3 * n, "ss4k_frvsr_upscale_frames: output buffer too small");
     up->u.frames(in, n, h, w, out, (hipStream_t)stream);
+  });
+}
+int ss4k_frvsr_upscale_streams(ss4k_frvsr_upscaler* up, const int32_t* slots, int n_streams, const uint8_t* in, int h, int w, uint8_t* out, size_t cap,
+                               void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(up, "ss4k_frvsr_upscale_streams: NULL argument");
+    SS4K_REQUIRE(n_streams >= 1 && n_streams <= (int)up->u.slots.size(), "ss4k_frvsr_upscale_streams: n_streams must be in 1..max_streams");
+    SS4K_REQUIRE(slots && in && out, "ss4k_frvsr_upscale_streams: NULL argument");
+    SS4K_REQUIRE(h > 0 && w > 0, "ss4k_frvsr_upscale_streams: empty frames");
+    int oh, ow; up->u.out_shape(&oh, &ow);
+    SS4K_REQUIRE(cap >= (size_t)oh * ow * 3 * n_streams, "ss4k_frvsr_upscale_streams: output buffer too small");
+    up->u.round(in, slots, n_streams, h, w, out, (hipStream_t)stream);
   });
 }
 int ss4k_frvsr_upscaler_enable_taps(ss4k_frvsr_upscaler* up, int en) {
@@ -649,7 +680,9 @@ int ss4k_frvsr_upscaler_read_tap(ss4k_frvsr_upscaler* up, int which, float* out,
     SS4K_REQUIRE(nflt > 0, "tap not recorded (enable taps before ss4k_frvsr_upscale_frames)");
     if (out) {
       SS4K_REQUIRE(cap >= nflt, "tap buffer too small");
-      const void* src = which == 0 ? u.lr[u.cur].ptr : which == 1 ? u.m->flow.ptr : which == 2 ? u.m->tap_s2d.ptr : u.hr[u.cur].ptr;
+      const FrvsrUpscaler::Slot& sl = u.slots[(size_t)u.tap_slot];   // the last item of the last round: its slot's state, its part of the round's batches
+      const void* src = which == 0 ? sl.lr[sl.cur].ptr : which == 1 ? (const void*)(u.m->flow.as<float>() + u.tap_item * nflt)
+                      : which == 2 ? (const void*)(u.m->tap_s2d.as<float>() + u.tap_item * nflt) : sl.hr[sl.cur].ptr;
       SS4K_HIP(hipMemcpyAsync(out, src, nflt * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
   });

@@ -82,6 +82,17 @@ size_t Frvsr::workspace_bytes(int n, int h, int w) {
 }
 
 void Frvsr::step(const float* lr_curr, const float* lr_prev, const float* hr_prev, float* hr_out, int n, int h, int w, hipStream_t st) {
+  run(lr_curr, lr_prev, hr_prev, hr_out, nullptr, n, h, w, st);
+}
+
+void Frvsr::step_items(const Items& items, int n, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS, "frvsr step: 1..64 items that live in buffers of their own");
+  SS4K_REQUIRE(items.lr_curr && items.lr_prev && items.hr_prev && items.hr_out, "frvsr step: NULL item table");
+  run(nullptr, nullptr, nullptr, nullptr, &items, n, h, w, st);
+}
+
+// `items` null: the four contiguous batches; else the per-item pointers (the contiguous arguments are unused)
+void Frvsr::run(const float* lr_curr, const float* lr_prev, const float* hr_prev, float* hr_out, const Items* items, int n, int h, int w, hipStream_t st) {
   SS4K_REQUIRE(n > 0, "frvsr step: empty batch");
   SS4K_REQUIRE(h >= 8 && w >= 8, "frvsr step: h and w must be at least 8 (the flow is computed at (h // 8 * 8, w // 8 * 8) and reflect-padded, egvsr.py:191-194)");
   SS4K_REQUIRE((double)n * 16.0 * h * w < 2147483648.0, "frvsr step: the output of a call holds at most 2^31 pixels per plane");
@@ -115,8 +126,16 @@ void Frvsr::step(const float* lr_curr, const float* lr_prev, const float* hr_pre
   // ---- inputs: lr_curr and lr_prev as one 16-channel plane each (channels 0..2 live)
   Tens A = net.act_planes(slot++, px, 1), B = net.act_planes(slot++, px, 1);
   stage(FRV_GLUE, [&] {
-    net.pack_in(lr_curr, A, 1, n, 3, h, w, 1, st);
-    net.pack_in(lr_prev, B, 1, n, 3, h, w, 1, st);
+    if (!items) {
+      net.pack_in(lr_curr, A, 1, n, 3, h, w, 1, st);
+      net.pack_in(lr_prev, B, 1, n, 3, h, w, 1, st);
+    } else if (!plan) {   // item i's pixels are one contiguous run of the single plane
+      const size_t item_b = (size_t)h * w * conv_rec_bytes(desc.dtype);
+      for (int i = 0; i < n; ++i) {
+        net.pack_in(items->lr_curr[i], Tens{A.p + i * item_b, A.plane_bytes, 0}, 1, 1, 3, h, w, 1, st);
+        net.pack_in(items->lr_prev[i], Tens{B.p + i * item_b, B.plane_bytes, 0}, 1, 1, 3, h, w, 1, st);
+      }
+    }
   });
 
   // ---- FNet (egvsr.py:63-78)
@@ -160,7 +179,10 @@ void Frvsr::step(const float* lr_curr, const float* lr_prev, const float* hr_pre
   Tens Wp = net.act_planes(slot++, px, 3);
   stage(FRV_WARP, [&] {
     if (plan) return;
-    if (f16) op_warp_s2d_planes<__half>(flow.as<float>(), hr_prev, reinterpret_cast<__half*>(Wp.p), n, h, w, st);
+    if (items) {
+      if (f16) op_warp_s2d_planes_items<__half>(flow.as<float>(), *items->hr_prev, reinterpret_cast<__half*>(Wp.p), n, h, w, st);
+      else op_warp_s2d_planes_items<float>(flow.as<float>(), *items->hr_prev, reinterpret_cast<float*>(Wp.p), n, h, w, st);
+    } else if (f16) op_warp_s2d_planes<__half>(flow.as<float>(), hr_prev, reinterpret_cast<__half*>(Wp.p), n, h, w, st);
     else op_warp_s2d_planes<float>(flow.as<float>(), hr_prev, reinterpret_cast<float*>(Wp.p), n, h, w, st);
   });
   if (keep_taps && !plan) {
@@ -187,7 +209,10 @@ void Frvsr::step(const float* lr_curr, const float* lr_prev, const float* hr_pre
   // PixelShuffle(4), ReLU, conv_out (egvsr.py:139-140)
   stage(FRV_TAIL, [&] {
     if (plan) return;
-    if (f16) op_ps4_conv_tail<__half>(reinterpret_cast<const __half*>(cur.p), tail_wb.as<float>(), hr_out, n, h, w, st);
+    if (items) {
+      if (f16) op_ps4_conv_tail_items<__half>(reinterpret_cast<const __half*>(cur.p), tail_wb.as<float>(), *items->hr_out, n, h, w, st);
+      else op_ps4_conv_tail_items<float>(reinterpret_cast<const float*>(cur.p), tail_wb.as<float>(), *items->hr_out, n, h, w, st);
+    } else if (f16) op_ps4_conv_tail<__half>(reinterpret_cast<const __half*>(cur.p), tail_wb.as<float>(), hr_out, n, h, w, st);
     else op_ps4_conv_tail<float>(reinterpret_cast<const float*>(cur.p), tail_wb.as<float>(), hr_out, n, h, w, st);
   });
 }
@@ -197,18 +222,27 @@ void FrvsrUpscaler::out_shape(int* oh, int* ow) const {
   *oh = out_h > 0 ? out_h : 4 * lr_h; *ow = out_w > 0 ? out_w : 4 * lr_w;
 }
 
-void FrvsrUpscaler::frames(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st) {
+size_t FrvsrUpscaler::state_bytes() const {
+  size_t b = 0;
+  for (const Slot& s : slots) b += s.lr[0].bytes + s.lr[1].bytes + s.hr[0].bytes + s.hr[1].bytes;
+  return b;
+}
+
+void FrvsrUpscaler::round(const uint8_t* in, const int32_t* slot_ids, int S, int h, int w, uint8_t* out, hipStream_t st) {
+  // every refusal comes before the first change of any slot
+  SS4K_REQUIRE(S >= 1 && S <= (int)slots.size(), "frvsr round: n_streams must be in 1..max_streams");
+  SS4K_REQUIRE(h > 0 && w > 0, "frvsr round: empty frames");
+  bool seen[SS4K_FRVSR_MAX_STREAMS] = {};
+  for (int i = 0; i < S; ++i) {
+    SS4K_REQUIRE(slot_ids[i] >= 0 && slot_ids[i] < (int)slots.size(), "frvsr round: slot outside 0..max_streams-1");
+    SS4K_REQUIRE(!seen[slot_ids[i]], "frvsr round: a slot is named twice (a round holds ONE frame per stream)");
+    seen[slot_ids[i]] = true;
+  }
+  SS4K_REQUIRE((double)S * 16.0 * lr_h * lr_w < 2147483648.0, "frvsr round: the output of a round holds at most 2^31 pixels per plane");
   const int H = 4 * lr_h, W = 4 * lr_w;
   int oh, ow; out_shape(&oh, &ow);
   const size_t lr_b = (size_t)3 * lr_h * lr_w * 4, hr_b = (size_t)3 * H * W * 4;
-  for (int k = 0; k < 2; ++k) { lr[k].ensure(lr_b); hr[k].ensure(hr_b); }
-  if (!have_state) {   // self.lr_prev = zeros_like(lr_curr), self.hr_prev = zeros (egvsr_upscaler.py:197-202)
-    SS4K_HIP(hipMemsetAsync(lr[cur].ptr, 0, lr_b, st));
-    SS4K_HIP(hipMemsetAsync(hr[cur].ptr, 0, hr_b, st));
-    have_state = true;
-  }
   const bool resize_in = h != lr_h || w != lr_w, resize_out = oh != H || ow != W;
-  m->keep_taps = taps_on;
   auto glue = [&](auto&& body) {
     if (!m->prof) { body(); return; }
     Frvsr::Span sp{nullptr, nullptr, FRV_GLUE};
@@ -219,38 +253,62 @@ void FrvsrUpscaler::frames(const uint8_t* in, int n, int h, int w, uint8_t* out,
     body();
     SS4K_HIP(hipEventRecord(sp.b, st));
   };
-  for (int i = 0; i < n; ++i) {
-    float* lr_curr = lr[cur ^ 1].as<float>();
-    float* hr_curr = hr[cur ^ 1].as<float>();
-    glue([&] {
+  const float* lr_curr[SS4K_FRVSR_MAX_STREAMS]; const float* lr_prev[SS4K_FRVSR_MAX_STREAMS];
+  FrvsrPtrs hr_prev{}, hr_curr{};
+  for (int i = 0; i < S; ++i) {
+    Slot& s = slots[slot_ids[i]];
+    for (int k = 0; k < 2; ++k) { s.lr[k].ensure(lr_b); s.hr[k].ensure(hr_b); }
+    if (!s.have_state) {   // self.lr_prev = zeros_like(lr_curr), self.hr_prev = zeros (egvsr_upscaler.py:197-202)
+      SS4K_HIP(hipMemsetAsync(s.lr[s.cur].ptr, 0, lr_b, st));
+      SS4K_HIP(hipMemsetAsync(s.hr[s.cur].ptr, 0, hr_b, st));
+      s.have_state = true;
+    }
+    lr_prev[i] = s.lr[s.cur].as<float>(); lr_curr[i] = s.lr[s.cur ^ 1].as<float>();
+    hr_prev.p[i] = s.hr[s.cur].as<float>(); hr_curr.p[i] = s.hr[s.cur ^ 1].as<float>();
+  }
+  m->keep_taps = taps_on;
+  glue([&] {
+    for (int i = 0; i < S; ++i) {
       const uint8_t* frame = in + (size_t)i * h * w * 3;
+      float* dst = const_cast<float*>(lr_curr[i]);
       if (resize_in) {   // img / 255.0, F.interpolate(img, size=self.lr_shape, mode='area') (egvsr_upscaler.py:195-196)
         img.ensure((size_t)3 * h * w * 4);
         op_u8nhwc_to_f32nchw(frame, img.as<float>(), 1, h, w, 3, st);
-        op_area(img.as<float>(), lr_curr, 3, h, w, lr_h, lr_w, st);
+        op_area(img.as<float>(), dst, 3, h, w, lr_h, lr_w, st);
       } else {
-        op_u8nhwc_to_f32nchw(frame, lr_curr, 1, h, w, 3, st);
+        op_u8nhwc_to_f32nchw(frame, dst, 1, h, w, 3, st);
       }
-    });
-    m->step(lr_curr, lr[cur].as<float>(), hr[cur].as<float>(), hr_curr, 1, lr_h, lr_w, st);   // (:204)
-    cur ^= 1;   // the state takes the UNCLAMPED output (:206-207)
-    glue([&] {
+    }
+  });
+  // (:204) one stream: the contiguous launchers, as before there were slots; several: the same step with every item's state where it lives
+  if (S == 1) m->step(lr_curr[0], lr_prev[0], hr_prev.p[0], hr_curr.p[0], 1, lr_h, lr_w, st);
+  else m->step_items(Frvsr::Items{lr_curr, lr_prev, &hr_prev, &hr_curr}, S, lr_h, lr_w, st);
+  for (int i = 0; i < S; ++i) slots[slot_ids[i]].cur ^= 1;   // the state takes the UNCLAMPED output (:206-207)
+  glue([&] {
+    for (int i = 0; i < S; ++i) {
       uint8_t* dst = out + (size_t)i * oh * ow * 3;
       if (resize_out) {   // clamp(hr_curr, 0, 1), F.interpolate(size=self.output_shape, mode='area') (:209-211)
         hrc.ensure(hr_b); outf.ensure((size_t)3 * oh * ow * 4);
-        op_clamp01_to(hr_curr, hrc.as<float>(), (size_t)3 * H * W, st);
+        op_clamp01_to(hr_curr.p[i], hrc.as<float>(), (size_t)3 * H * W, st);
         op_area(hrc.as<float>(), outf.as<float>(), 3, H, W, oh, ow, st);
         op_f32nchw_to_u8nhwc(outf.as<float>(), dst, 1, 3, oh, ow, st);
       } else {
-        op_f32nchw_to_u8nhwc(hr_curr, dst, 1, 3, H, W, st);   // (clamps, * 255, truncates: :209,212)
+        op_f32nchw_to_u8nhwc(hr_curr.p[i], dst, 1, 3, H, W, st);   // (clamps, * 255, truncates: :209,212)
       }
-    });
-  }
+    }
+  });
   m->keep_taps = false;
   if (taps_on) {
     const int d[4][4] = {{1, 3, lr_h, lr_w}, {1, 2, lr_h, lr_w}, {1, 48, lr_h, lr_w}, {1, 3, H, W}};
     std::memcpy(tap_dims, d, sizeof(d));
+    tap_slot = slot_ids[S - 1]; tap_item = S - 1;
   }
+}
+
+void FrvsrUpscaler::frames(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st) {
+  int oh, ow; out_shape(&oh, &ow);
+  const int32_t slot0 = 0;
+  for (int i = 0; i < n; ++i) round(in + (size_t)i * h * w * 3, &slot0, 1, h, w, out + (size_t)i * oh * ow * 3, st);
 }
 
 }  // namespace ss4k

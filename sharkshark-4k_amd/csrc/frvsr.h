@@ -5,6 +5,11 @@
 
 namespace ss4k {
 
+// Base pointers of the items of a batched launch whose tensors are NOT one contiguous batch: stream i's hr_prev / hr_curr, (3, 4 h, 4 w) fp32,
+// each in its own allocation.  Passed BY VALUE in the kernel arguments (512 B): no device table, no upload, no synchronisation, and the
+// buffers stay separate DevBufs (a red zone around each in the dev library's guard mode).  Entries past the launch's n are not read.
+struct FrvsrPtrs { float* p[SS4K_FRVSR_MAX_STREAMS]; };
+
 // ---- kernels (frvsr.hip).  "planes" tensors are the conv kernels' layout: [plane][pixel][16 channels of T] -----------------------------
 // nn.MaxPool2d(2, 2) (egvsr.py:24,31,38): (n, h, w) -> (n, h / 2, w / 2), odd sizes floored
 template <typename T> void op_maxpool2_planes(const T* in, T* out, int nplanes, int n, int h, int w, hipStream_t st);
@@ -19,9 +24,13 @@ void op_backward_warp(const float* x, const float* flow, float* out, int n, int 
 // 4 * BicubicUpsample(4)(lr_flow), backward_warp(hr_prev, .) and the space-to-depth of egvsr.py:196-208 as one launch: lr_flow (n, 2, h, w),
 // hr_prev (n, 3, 4 h, 4 w), both fp32 -> three planes of T (channel (sy * 4 + sx) * 3 + c)
 template <typename T> void op_warp_s2d_planes(const float* lr_flow, const float* hr_prev, T* out, int n, int h, int w, hipStream_t st);
+// ... item i reading hr_prev.p[i] instead of hr_prev + i * 3 * 16 h w: the same device functions in the same order, bit-identical; n <= 64
+template <typename T> void op_warp_s2d_planes_items(const float* lr_flow, const FrvsrPtrs& hr_prev, T* out, int n, int h, int w, hipStream_t st);
 // PixelShuffle(4), ReLU, Conv2d(4, 3, 3, 1, 1) (egvsr.py:122-127,139-140): four planes of T (64 channels) at (n, h, w) -> fp32 NCHW
 // (n, 3, 4 h, 4 w); wb: 108 weights (OIHW) + 3 biases on the device
 template <typename T> void op_ps4_conv_tail(const T* in, const float* wb, float* out, int n, int h, int w, hipStream_t st);
+// ... item i written to out.p[i] (3, 4 h, 4 w): bit-identical; n <= 64
+template <typename T> void op_ps4_conv_tail_items(const T* in, const float* wb, const FrvsrPtrs& out, int n, int h, int w, hipStream_t st);
 // planes of T -> fp32 NCHW (n, channels, h, w) (the parity taps)
 template <typename T> void op_planes_to_nchw(const T* in, float* out, int n, int channels, int h, int w, hipStream_t st);
 // clamp(x, 0, 1) into another tensor (egvsr_upscaler.py:209: the recurrent state keeps the unclamped one)
@@ -52,20 +61,36 @@ struct Frvsr {
   void build(const float* w, size_t n);
   // FRNet.forward (egvsr.py:180-212)
   void step(const float* lr_curr, const float* lr_prev, const float* hr_prev, float* hr_out, int n, int h, int w, hipStream_t st);
+  // the same step over n <= SS4K_FRVSR_MAX_STREAMS items that each live in buffers of their own (the service's streams): item i reads lr_curr[i],
+  // lr_prev[i] (3, h, w) and hr_prev.p[i], writes hr_out.p[i].  Every conv, pool, x2, flow, warp and tail launch covers all n items; only the
+  // input packing runs per item.  Bit-identical, item by item, to step() on a contiguous batch.
+  struct Items { const float* const* lr_curr; const float* const* lr_prev; const FrvsrPtrs* hr_prev; const FrvsrPtrs* hr_out; };
+  void step_items(const Items& items, int n, int h, int w, hipStream_t st);
   size_t workspace_bytes(int n, int h, int w);
+ private:
+  void run(const float* lr_curr, const float* lr_prev, const float* hr_prev, float* hr_out, const Items* items, int n, int h, int w, hipStream_t st);
 };
 
 struct FrvsrUpscaler {
   ss4k_ctx* ctx = nullptr;
   Frvsr* m = nullptr;
   int lr_h = 0, lr_w = 0, out_h = 0, out_w = 0;
-  bool have_state = false;
-  int cur = 0;               // which of lr[2] / hr[2] holds the previous frame
-  DevBuf img, lr[2], hr[2], hrc, outf;
-  bool taps_on = false;      // read_tap copies from the live buffers: lr[cur], m->flow, m->tap_s2d, hr[cur]
+  // one slot per stream: its own recurrent state, allocated on the slot's first frame
+  struct Slot {
+    bool have_state = false;
+    int cur = 0;             // which of lr[2] / hr[2] holds the previous frame
+    DevBuf lr[2], hr[2];
+  };
+  std::vector<Slot> slots;   // max_streams of them (ss4k_frvsr_upscaler_create_streams); slot 0 is the stream of frames()
+  DevBuf img, hrc, outf;     // resize scratch, reused item after item (stream order)
+  bool taps_on = false;      // read_tap copies from the live buffers of the LAST item of the last round: its slot's lr[cur] / hr[cur], m->flow, m->tap_s2d
   int tap_dims[4][4] = {};
+  int tap_slot = 0, tap_item = 0;
   void out_shape(int* oh, int* ow) const;
-  void frames(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st);
+  // one frame for each of S distinct slots, as one n = S step: in (S, h, w, 3) -> out (S, oh, ow, 3), in the order of `slot_ids`
+  void round(const uint8_t* in, const int32_t* slot_ids, int S, int h, int w, uint8_t* out, hipStream_t st);
+  void frames(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st);   // n consecutive frames of slot 0
+  size_t state_bytes() const;
 };
 
 }  // namespace ss4k

@@ -216,33 +216,49 @@ void op_backward_warp(const float* x, const float* flow, float* out, int n, int 
 // ------------------------------------------------------------------ flow x4 + warp + space-to-depth -> three planes
 // One thread per LR pixel: its 4 x 4 flow neighbourhood serves all 16 sub-pixels (the four phases of each pass read the same inputs), and
 // the 48 channels (sy * 4 + sx) * 3 + c it produces are exactly the three records it stores, with 16-byte stores.
+// pixel i of item img: `src` is that item's hr_prev (3, 4 h, 4 w)
+template <typename T>
+__device__ __forceinline__ void warp_s2d_pixel(const float* __restrict__ lr_flow, const float* __restrict__ src, uint4* __restrict__ out, size_t i, size_t img,
+                                               size_t npix, int h, int w, const Bic4& taps) {
+  constexpr int RV = sizeof(T);
+  const int H = 4 * h, W = 4 * w;
+  const size_t hw = (size_t)h * w, HW = (size_t)H * W;
+  const int x = (int)(i % w), y = (int)((i / w) % h);
+  union { T v[48]; uint4 u[3 * RV]; } rec;
+  float fu[4][4], fv[4][4];
+  bic4_load(lr_flow + (img * 2) * hw, y, x, h, w, fu);
+  bic4_load(lr_flow + (img * 2 + 1) * hw, y, x, h, w, fv);
+#pragma unroll
+  for (int sy = 0; sy < 4; ++sy)
+#pragma unroll
+    for (int sx = 0; sx < 4; ++sx) {
+      const float u = __fmul_rn(4.f, bic4_at(taps, fu, sy, sx)), v = __fmul_rn(4.f, bic4_at(taps, fv, sy, sx));
+      const WarpTaps t = warp_taps(4 * x + sx, 4 * y + sy, W, H, u, v);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) rec.v[(sy * 4 + sx) * 3 + c] = (T)warp_sample(src + c * HW, W, t);
+    }
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int q = 0; q < RV; ++q) out[((size_t)p * npix + i) * RV + q] = rec.u[p * RV + q];
+}
 template <typename T>
 __global__ __launch_bounds__(256) void k_warp_s2d_planes(const float* __restrict__ lr_flow, const float* __restrict__ hr_prev, uint4* __restrict__ out, int n, int h,
                                                          int w, Bic4 taps) {
-  constexpr int RV = sizeof(T);
-  const int H = 4 * h, W = 4 * w;
-  const size_t hw = (size_t)h * w, HW = (size_t)H * W, npix = (size_t)n * hw;
+  const size_t hw = (size_t)h * w, npix = (size_t)n * hw;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
-    const int x = (int)(i % w), y = (int)((i / w) % h);
     const size_t img = i / hw;
-    union { T v[48]; uint4 u[3 * RV]; } rec;
-    float fu[4][4], fv[4][4];
-    bic4_load(lr_flow + (img * 2) * hw, y, x, h, w, fu);
-    bic4_load(lr_flow + (img * 2 + 1) * hw, y, x, h, w, fv);
-    const float* src = hr_prev + img * 3 * HW;
-#pragma unroll
-    for (int sy = 0; sy < 4; ++sy)
-#pragma unroll
-      for (int sx = 0; sx < 4; ++sx) {
-        const float u = __fmul_rn(4.f, bic4_at(taps, fu, sy, sx)), v = __fmul_rn(4.f, bic4_at(taps, fv, sy, sx));
-        const WarpTaps t = warp_taps(4 * x + sx, 4 * y + sy, W, H, u, v);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) rec.v[(sy * 4 + sx) * 3 + c] = (T)warp_sample(src + c * HW, W, t);
-      }
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int q = 0; q < RV; ++q) out[((size_t)p * npix + i) * RV + q] = rec.u[p * RV + q];
+    warp_s2d_pixel<T>(lr_flow, hr_prev + img * 3 * (16 * hw), out, i, img, npix, h, w, taps);
+  }
+}
+// ... with every item's hr_prev where its stream keeps it: the base pointers arrive by value in the kernel arguments (FrvsrPtrs, frvsr.h)
+template <typename T>
+__global__ __launch_bounds__(256) void k_warp_s2d_planes_items(const float* __restrict__ lr_flow, FrvsrPtrs hr_prev, uint4* __restrict__ out, int n, int h, int w,
+                                                               Bic4 taps) {
+  const size_t hw = (size_t)h * w, npix = (size_t)n * hw;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t img = i / hw;
+    warp_s2d_pixel<T>(lr_flow, hr_prev.p[img], out, i, img, npix, h, w, taps);
   }
 }
 template <typename T>
@@ -254,10 +270,45 @@ void op_warp_s2d_planes(const float* lr_flow, const float* hr_prev, T* out, int 
 }
 template void op_warp_s2d_planes<float>(const float*, const float*, float*, int, int, int, hipStream_t);
 template void op_warp_s2d_planes<__half>(const float*, const float*, __half*, int, int, int, hipStream_t);
+template <typename T>
+void op_warp_s2d_planes_items(const float* lr_flow, const FrvsrPtrs& hr_prev, T* out, int n, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull, "warp (items): sizes");
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(hr_prev.p[i], "warp (items): NULL item");
+  SS4K_GLUE_ROUTE(sizeof(T) == 2 ? "frvsr::warp_s2d_planes_items<half>" : "frvsr::warp_s2d_planes_items<float>");
+  hipLaunchKernelGGL((k_warp_s2d_planes_items<T>), grid_for((size_t)n * h * w), dim3(256), 0, st, lr_flow, hr_prev, reinterpret_cast<uint4*>(out), n, h, w,
+                     bic4_taps());
+  SS4K_LAUNCH_OK();
+}
+template void op_warp_s2d_planes_items<float>(const float*, const FrvsrPtrs&, float*, int, int, int, hipStream_t);
+template void op_warp_s2d_planes_items<__half>(const float*, const FrvsrPtrs&, __half*, int, int, int, hipStream_t);
 
 // ------------------------------------------------------------------ PixelShuffle(4) + ReLU + Conv2d(4, 3, 3, 1, 1) -> fp32 NCHW
 // One thread per HR pixel.  Shuffled channel c of HR pixel (Y, X) is LR channel c * 16 + (Y % 4) * 4 + X % 4 of pixel (Y / 4, X / 4): element
 // (Y % 4) * 4 + X % 4 of plane c's record.  3 x 3 x 4 rectified values, 108 MACs in fp32, weights and biases in LDS; zero padding at the HR border.
+// HR pixel (Y, X) of item img: the three output values, bias first, taps in (ky, kx, c) order
+template <typename T>
+__device__ __forceinline__ void ps4_tail_pixel(const T* __restrict__ in, const float* s_w, size_t img, size_t npix, int X, int Y, int h, int w, float acc[3]) {
+  const int H = 4 * h, W = 4 * w;
+  acc[0] = s_w[108]; acc[1] = s_w[109]; acc[2] = s_w[110];
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky) {
+    const int yy = Y + ky - 1;
+    if (yy < 0 || yy >= H) continue;
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const int xx = X + kx - 1;
+      if (xx < 0 || xx >= W) continue;
+      const size_t pix = (img * h + (yy >> 2)) * w + (xx >> 2);
+      const int sub = (yy & 3) * 4 + (xx & 3);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float v = fmaxf((float)in[((size_t)c * npix + pix) * 16 + sub], 0.f);
+#pragma unroll
+        for (int o = 0; o < 3; ++o) acc[o] = fmaf(s_w[((o * 4 + c) * 3 + ky) * 3 + kx], v, acc[o]);
+      }
+    }
+  }
+}
 template <typename T>
 __global__ __launch_bounds__(256) void k_ps4_conv_tail(const T* __restrict__ in, const float* __restrict__ wb, float* __restrict__ out, int n, int h, int w) {
   __shared__ float s_w[112];
@@ -268,28 +319,29 @@ __global__ __launch_bounds__(256) void k_ps4_conv_tail(const T* __restrict__ in,
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int X = (int)(i % W), Y = (int)((i / W) % H);
     const size_t img = i / HW;
-    float acc[3] = {s_w[108], s_w[109], s_w[110]};
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-      const int yy = Y + ky - 1;
-      if (yy < 0 || yy >= H) continue;
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) {
-        const int xx = X + kx - 1;
-        if (xx < 0 || xx >= W) continue;
-        const size_t pix = (img * h + (yy >> 2)) * w + (xx >> 2);
-        const int sub = (yy & 3) * 4 + (xx & 3);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float v = fmaxf((float)in[((size_t)c * npix + pix) * 16 + sub], 0.f);
-#pragma unroll
-          for (int o = 0; o < 3; ++o) acc[o] = fmaf(s_w[((o * 4 + c) * 3 + ky) * 3 + kx], v, acc[o]);
-        }
-      }
-    }
+    float acc[3];
+    ps4_tail_pixel<T>(in, s_w, img, npix, X, Y, h, w, acc);
     const size_t p = i - img * HW;
 #pragma unroll
     for (int o = 0; o < 3; ++o) out[(img * 3 + o) * HW + p] = acc[o];
+  }
+}
+// ... writing every item's (3, 4 h, 4 w) where its stream keeps it (FrvsrPtrs by value, as k_warp_s2d_planes_items)
+template <typename T>
+__global__ __launch_bounds__(256) void k_ps4_conv_tail_items(const T* __restrict__ in, const float* __restrict__ wb, FrvsrPtrs out, int n, int h, int w) {
+  __shared__ float s_w[112];
+  if (threadIdx.x < 111) s_w[threadIdx.x] = wb[threadIdx.x];
+  __syncthreads();
+  const int H = 4 * h, W = 4 * w;
+  const size_t HW = (size_t)H * W, total = (size_t)n * HW, npix = (size_t)n * h * w;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int X = (int)(i % W), Y = (int)((i / W) % H);
+    const size_t img = i / HW;
+    float acc[3];
+    ps4_tail_pixel<T>(in, s_w, img, npix, X, Y, h, w, acc);
+    float* dst = out.p[img] + (i - img * HW);
+#pragma unroll
+    for (int o = 0; o < 3; ++o) dst[o * HW] = acc[o];
   }
 }
 template <typename T>
@@ -301,6 +353,16 @@ void op_ps4_conv_tail(const T* in, const float* wb, float* out, int n, int h, in
 }
 template void op_ps4_conv_tail<float>(const float*, const float*, float*, int, int, int, hipStream_t);
 template void op_ps4_conv_tail<__half>(const __half*, const float*, float*, int, int, int, hipStream_t);
+template <typename T>
+void op_ps4_conv_tail_items(const T* in, const float* wb, const FrvsrPtrs& out, int n, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "tail (items): sizes");
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(out.p[i], "tail (items): NULL item");
+  SS4K_GLUE_ROUTE(sizeof(T) == 2 ? "frvsr::ps4_conv_tail_items<half>" : "frvsr::ps4_conv_tail_items<float>");
+  hipLaunchKernelGGL((k_ps4_conv_tail_items<T>), grid_for((size_t)n * 16 * h * w), dim3(256), 0, st, in, wb, out, n, h, w);
+  SS4K_LAUNCH_OK();
+}
+template void op_ps4_conv_tail_items<float>(const float*, const float*, const FrvsrPtrs&, int, int, int, hipStream_t);
+template void op_ps4_conv_tail_items<__half>(const __half*, const float*, const FrvsrPtrs&, int, int, int, hipStream_t);
 
 // ------------------------------------------------------------------ planes -> fp32 NCHW (parity taps), clamp into another tensor
 template <typename T>

@@ -7,19 +7,25 @@ uint8 HWC frame or a uint8 NHWC batch of CONSECUTIVE frames of one stream in, ui
 frame to frame and from job to job (``:197-207``).  All arithmetic runs in libss4k_hip.so (``ss4k_frvsr_upscale_frames``, include/ss4k.h).
 
 The state lives in the worker, so a stream must stay on ONE worker: this service is not something ``node.UpscalerNode`` can shard
-(INTEGRATION.md).  Weights as for the other services: ``weights=None`` looks ``EGVSR_iter420000.pth`` (``egvsr_upscaler.py:25``) up in
+(INTEGRATION.md).  One worker can hold SEVERAL streams, though: ``max_streams=S`` gives it S stream slots, ``upscale(frames, streams=ids)``
+names the stream of every frame of a job, and the frames of different streams go through the network together, one batched step per round
+(``ss4k_frvsr_upscale_streams``).  ``StreamQueueEntry`` is the job record that carries the ids; with the default ``max_streams=1`` and jobs
+without ids the service is what it was.  Weights as for the other services: ``weights=None`` looks ``EGVSR_iter420000.pth`` (``egvsr_upscaler.py:25``) up in
 ``checkpoint_dir`` / ``$SS4K_CHECKPOINT_DIR`` and raises ``FileNotFoundError`` when it is missing; a path, the dict ``torch.load`` returns
 (a bare state_dict) or a state-dict table are taken as they are; ``'synthetic'`` is the tests' explicit opt-in.  The worker process,
 fork / spawn choice, caller-owned entry and profiler types come from ``BaseUpscalerService``.
 """
 from __future__ import annotations
 
+import dataclasses
 import sys
-from typing import Optional
+import time
+from typing import Hashable, List, Optional, Sequence
 
 import torch
 
-from .upscaler_base import BaseUpscalerService, UpscalerQueueEntry  # noqa: F401
+from .upscaler_base import BaseUpscalerService, UpscalerQueueEntry, answer
+from ..util.profiler import Profiler
 
 LR_SHAPES = [(540, 960), (630, 1120), (720, 1280)]   # egvsr_upscaler.py:147-151
 
@@ -29,9 +35,55 @@ def log(*args, **kwargs):
     print(f"HipEgvsrUpscalerService: {' '.join(str(a) for a in args)}", **kwargs)
 
 
+@dataclasses.dataclass
+class StreamQueueEntry(UpscalerQueueEntry):
+    """The job record of a multi-stream worker: the six fields plus ``streams`` (the stream id of every frame of ``frames``, or None: all of
+    them are the next frames of the unnamed stream) and ``end_streams`` (ids whose slots are freed after the job)."""
+    streams: Optional[Sequence[Hashable]] = None
+    end_streams: Sequence[Hashable] = ()
+
+
+class StreamSlots:
+    """Which stream id sits in which of ``max_streams`` slots.  An id seen for the first time takes the lowest free slot; ``end`` frees it.
+    Nothing is ever evicted: a stream that lost its slot would go on from another stream's state - a silently wrong picture."""
+
+    def __init__(self, max_streams: int):
+        self.max_streams = int(max_streams)
+        self.slot_of = {}
+
+    def slot(self, stream_id):
+        """``(slot, is_new)``; ``is_new``: the id just took the slot, whose state the caller resets."""
+        if stream_id in self.slot_of:
+            return self.slot_of[stream_id], False
+        used = set(self.slot_of.values())
+        free = [k for k in range(self.max_streams) if k not in used]
+        if not free:
+            raise RuntimeError(f"no free stream slot for {stream_id!r}: all {self.max_streams} are held by {list(self.slot_of)!r} "
+                               "(end a stream with end_streams, or raise max_streams)")
+        self.slot_of[stream_id] = free[0]
+        return free[0], True
+
+    def end(self, stream_id) -> Optional[int]:
+        """Frees the id's slot and returns it; None for an id that holds none."""
+        return self.slot_of.pop(stream_id, None)
+
+
+def plan_rounds(streams: Sequence[Hashable]) -> List[List[int]]:
+    """``streams[i]`` is the stream of frame i of a job, a stream's frames in their order.  Round r holds the index of the r-th frame of every
+    stream that has one: ``['a', 'b', 'a', 'c', 'b', 'a'] -> [[0, 1, 3], [2, 4], [5]]``."""
+    rounds, seen = [], {}
+    for i, sid in enumerate(streams):
+        r = seen.get(sid, 0)
+        seen[sid] = r + 1
+        if r == len(rounds):
+            rounds.append([])
+        rounds[r].append(i)
+    return rounds
+
+
 class HipEgvsrUpscalerService(BaseUpscalerService):
     def __init__(self, lr_level=1, device=0, on_queue=None, *, weights=None, checkpoint_dir: Optional[str] = None, dtype="f16", nb=10,
-                 lr_shape=None, seed=0):
+                 lr_shape=None, seed=0, max_streams=1):
         self.lr_shape = tuple(lr_shape) if lr_shape is not None else LR_SHAPES[lr_level]
         self.scale = 4
         self.hr_shape = tuple([i * self.scale for i in self.lr_shape])
@@ -42,6 +94,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self.dtype = dtype
         self.nb = int(nb)
         self.seed = seed
+        self.max_streams = int(max_streams)
         super().__init__()
 
     def out_hw(self):
@@ -60,6 +113,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self.model = factory.build_model_egvsr(self.ctx, self.weights, self.seed, self.checkpoint_dir, self.dtype, self.nb)
         self._up = None
         self._up_key = None
+        self._slots = StreamSlots(self.max_streams)
         log("model loaded")
 
     def proc_cleanup(self):
@@ -74,7 +128,8 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         if self._up is None or self._up_key != key:   # (the pipelines overwrite lr_shape / output_shape after construction)
             if self._up is not None:
                 self._up.close()
-            self._up, self._up_key = _capi.FrvsrUpscaler(self.ctx, self.model, key[0], key[1]), key
+            self._up, self._up_key = _capi.FrvsrUpscaler(self.ctx, self.model, key[0], key[1], self.max_streams), key
+            self._slots = StreamSlots(self.max_streams)   # (a new shape: every stream starts over)
         return self._up
 
     def reset(self):
@@ -82,16 +137,81 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         if getattr(self, "_up", None) is not None:
             self._up.reset()
 
-    def upscale(self, frames: torch.Tensor):
+    def upscale(self, frames: torch.Tensor, streams: Optional[Sequence[Hashable]] = None, end_streams: Sequence[Hashable] = ()):
+        """``streams=None``: ``frames`` are the next frames of the unnamed stream (id ``None``), as before there were slots.  Else
+        ``streams[i]`` is the stream of ``frames[i]`` (one id for a 3-D frame): the job runs as ``plan_rounds(streams)``, one batched step per
+        round, and the result is in input order.  ``end_streams`` are released after the job."""
         assert isinstance(frames, torch.Tensor)
         frames = frames.to(self.torch_device, non_blocking=True)
         if frames.dtype != torch.uint8:   # (the reference's own demo pushes float frames holding byte values, egvsr_upscaler.py:226-230)
             frames = frames.to(torch.uint8)
-        if frames.ndim == 3:
-            assert frames.shape[-1] == 3
-            return self._upscaler()(frames.unsqueeze(0))[0]
-        elif frames.ndim == 4:
-            assert frames.shape[-1] == 3
-            return self._upscaler()(frames)
-        else:
+        if frames.ndim not in (3, 4):
             raise Exception(frames.shape)
+        assert frames.shape[-1] == 3
+        single = frames.ndim == 3
+        if single:
+            frames = frames.unsqueeze(0)
+        up = self._upscaler()
+        try:
+            if streams is None:
+                streams = [None] * frames.shape[0]
+            if all(sid is None for sid in streams) and self._unnamed_slot(up) == 0:
+                out = up(frames)   # the unnamed stream in slot 0 - always, unless named streams came first: ss4k_frvsr_upscale_frames
+            else:
+                out = self._upscale_streams(up, frames, list(streams))
+        finally:
+            for sid in end_streams:
+                self._slots.end(sid)
+        return out[0] if single else out
+
+    def _unnamed_slot(self, up):
+        slot, new = self._slots.slot(None)
+        if new:
+            up.reset(slot)
+        return slot
+
+    def _upscale_streams(self, up, frames, streams):
+        assert len(streams) == frames.shape[0], "one stream id per frame"
+        slots, taken = [], []
+        try:
+            for sid in streams:   # (ids first: a job that does not fit raises before any of its frames ran, and takes no slot)
+                slot, new = self._slots.slot(sid)
+                if new:
+                    taken.append(sid)
+                    up.reset(slot)
+                slots.append(slot)
+        except RuntimeError:
+            for sid in taken:
+                self._slots.end(sid)
+            raise
+        out = torch.empty((frames.shape[0],) + tuple(up.out_shape()) + (3,), dtype=torch.uint8, device=frames.device)
+        for idx in plan_rounds(streams):
+            if len(idx) == 1:
+                up.upscale_streams(frames[idx[0]:idx[0] + 1], [slots[idx[0]]], out=out[idx[0]:idx[0] + 1])
+            else:   # gather the round's input frames (bytes of LR frames; the 4K state stays where it is), scatter its output
+                ix = torch.tensor(idx, device=frames.device)
+                out.index_copy_(0, ix, up.upscale_streams(frames.index_select(0, ix), [slots[i] for i in idx]))
+        return out
+
+    def proc_job_recieved(self, job):  # (sic) the reference's spelling
+        # as BaseUpscalerService.proc_job_recieved, plus the two optional attributes of a multi-stream job; a record without them is a job of
+        # the unnamed stream and is answered by the base class's answer() exactly as before
+        streams, end_streams = getattr(job, "streams", None), tuple(getattr(job, "end_streams", None) or ())
+        prof = job.profiler if getattr(job, "profiler", None) is not None else Profiler()
+        self.profiler = prof
+        arrived = time.time()
+        prof.end("recoder.output")
+        prof.start("upscaler.upscale")
+        try:
+            upscaled = self.upscale(job.frames, streams, end_streams) if streams is not None or end_streams else self.upscale(job.frames)
+        finally:
+            prof.end("upscaler.upscale")
+        elapsed = time.time() - arrived
+        prof.start("upscaler.output")
+        if hasattr(job, "streams") or hasattr(job, "end_streams"):
+            try:   # the caller's own type, when it takes the eight fields
+                return type(job)(frames=upscaled, audio_segment=getattr(job, "audio_segment", None), step=getattr(job, "step", 0), elapsed=elapsed,
+                                 last_modified=time.time(), profiler=prof, streams=streams, end_streams=end_streams)
+            except TypeError:
+                pass
+        return answer(job, upscaled, elapsed, prof)

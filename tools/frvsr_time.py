@@ -7,7 +7,13 @@ a second pass with ``ss4k_frvsr_prof_enable`` (an event pair around every stage:
 event overhead).  The reference publishes 25 / 35 / 45 ms per frame for the same network under TensorRT on hardware it does not name
 (``src/upscale/egvsr_test.py:9-11``); 24 frames/s is 41.7 ms.
 
-usage: python tools/frvsr_time.py [--frames 64] [--nb 10] [--out frvsr_time.json]"""
+``--streams S``: S streams in lockstep on ONE upscaler with S stream slots (``ss4k_frvsr_upscale_streams``): every round is one frame of
+each stream - stream k is the same scene ``5 k`` frames ahead - and one batched step.  Same timing method; ms per frame = window /
+(rounds x S), the per-stage figures likewise per frame.  ``--streams 1`` is the single-stream call exactly as before (it also runs on a
+library built before the slots existed: ``SS4K_LIB=<older build>`` for an A/B).  ``--lr`` / ``--output-shapes`` restrict the table.
+
+usage: python tools/frvsr_time.py [--frames 64] [--nb 10] [--streams 1] [--lr 540x960,720x1280] [--output-shapes 1440x2560,none]
+                                  [--out frvsr_time.json]"""
 import argparse
 import json
 import os
@@ -44,43 +50,64 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--nb", type=int, default=10)
+    ap.add_argument("--streams", type=int, default=1, help="streams stepped in lockstep, one batched step per round")
+    ap.add_argument("--lr", default=",".join(f"{h}x{w}" for h, w in REFERENCE_MS), help="lr shapes, HxW[,HxW...]")
+    ap.add_argument("--output-shapes", default="1440x2560,none", help="output shapes, HxW or none[,...]")
     ap.add_argument("--out", default="frvsr_time.json")
     a = ap.parse_args()
     assert a.frames >= 64, "the steady state is read from a stream of at least 64 distinct frames"
+    S = a.streams
+    lrs = [tuple(int(v) for v in t.split("x")) for t in a.lr.split(",")]
+    out_shapes = [None if t == "none" else tuple(int(v) for v in t.split("x")) for t in a.output_shapes.split(",")]
     import sharkshark4k_amd  # noqa: F401
     from sharkshark4k_amd import _capi, weights as W
     assert torch.cuda.is_available(), "needs the GPU: no timing without one"
     ctx = _capi.Context(0)
     model = _capi.Frvsr(ctx, _capi.make_frvsr_desc(_capi.F16, 64, a.nb), W.flatten(W.frnet_table(0, nb=a.nb), W.frnet_keys(a.nb)))
     rows = []
-    for lr in REFERENCE_MS:
+    for lr in lrs:
         frames = stream_frames(a.frames, lr[0], lr[1], ctx.device)
-        for out_shape in ((1440, 2560), None):
-            up = _capi.FrvsrUpscaler(ctx, model, lr, out_shape)
+        if S > 1:   # (frames, S, h, w, 3): round i holds frame i of every stream
+            frames = torch.stack([torch.roll(frames, shifts=-5 * k, dims=0) for k in range(S)], dim=1)
+        for out_shape in out_shapes:
+            up = _capi.FrvsrUpscaler(ctx, model, lr, out_shape, S)
             oh, ow = up.out_shape()
-            out = torch.empty((a.frames // 2, oh, ow, 3), dtype=torch.uint8, device=ctx.device)
             half = a.frames // 2
-            up(frames[:half], out)                      # warm-up: the first half of the stream (allocations, code objects, clocks)
+            out = torch.empty((half, oh, ow, 3) if S == 1 else (half, S, oh, ow, 3), dtype=torch.uint8, device=ctx.device)
+            slots = list(range(S))
+
+            def run(first, count):
+                """`count` consecutive frames of every stream from frame `first` on, into out[:count]"""
+                if S == 1:
+                    up(frames[first:first + count], out[:count])
+                else:
+                    for i in range(count):
+                        up.upscale_streams(frames[first + i], slots, out=out[i])
+
+            run(0, half)                                # warm-up: the first half of the streams (allocations, code objects, clocks)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            up(frames[half:2 * half], out)              # the steady state: the second half
+            run(half, half)                             # the steady state: the second half
             torch.cuda.synchronize()
-            ms = 1000.0 * (time.perf_counter() - t0) / half
+            ms = 1000.0 * (time.perf_counter() - t0) / (half * S)
             # per stage, in a pass of its own
             up.reset()
-            up(frames[:8], out[:8])
+            run(0, 8)
             model.prof_enable(True)
-            up(frames[8:8 + 16], out[:16])
-            stages = {k: v / 16 for k, v in model.prof_read().items()}
+            run(8, 16)
+            stages = {k: v / (16 * S) for k, v in model.prof_read().items()}
             model.prof_enable(False)
             ff, fs = conv_flops(lr[0], lr[1], a.nb)
-            row = dict(lr_shape=list(lr), output_shape=None if out_shape is None else list(out_shape), nb=a.nb, frames_timed=half,
-                       ms_per_frame=ms, frames_per_s=1000.0 / ms, reference_ms_tensorrt_unknown_hw=REFERENCE_MS[lr], realtime_24fps_ms=1000.0 / 24,
+            row = dict(lr_shape=list(lr), output_shape=None if out_shape is None else list(out_shape), nb=a.nb, streams=S, frames_timed=half * S,
+                       library=os.path.basename(os.path.dirname(_capi.LIB_PATH)) + "/" + os.path.basename(_capi.LIB_PATH),
+                       state_bytes=up.state_bytes() if hasattr(_capi.lib(), "ss4k_frvsr_upscaler_state_bytes") else None,
+                       ms_per_frame=ms, frames_per_s=1000.0 / ms, reference_ms_tensorrt_unknown_hw=REFERENCE_MS.get(lr), realtime_24fps_ms=1000.0 / 24,
                        stage_ms_per_frame=stages, stage_sum_ms=sum(stages.values()), fnet_conv_tflops=ff / stages["fnet_conv"] / 1e9,
                        srnet_conv_tflops=fs / stages["srnet_conv"] / 1e9, conv_tflop_per_step=(ff + fs) / 1e12,
-                       workspace_mb=model.workspace_bytes(1, lr[0], lr[1]) / 2 ** 20)
+                       workspace_mb=model.workspace_bytes(S, lr[0], lr[1]) / 2 ** 20)
             rows.append(row)
-            print(f"lr {lr[0]}x{lr[1]} -> {oh}x{ow}: {ms:.2f} ms/frame, {1000.0 / ms:.1f} frames/s (reference {REFERENCE_MS[lr]:.0f} ms, TensorRT, hardware unstated); "
+            print(f"lr {lr[0]}x{lr[1]} -> {oh}x{ow}, {S} stream{'s' if S > 1 else ''}: {ms:.2f} ms/frame, {1000.0 / ms:.1f} frames/s "
+                  f"(reference {REFERENCE_MS.get(lr, float('nan')):.0f} ms, TensorRT, hardware unstated); "
                   + ", ".join(f"{k} {v:.2f}" for k, v in stages.items()) + f" ms; FNet convs {row['fnet_conv_tflops']:.0f} TFLOP/s, SRNet convs {row['srnet_conv_tflops']:.0f} TFLOP/s",
                   flush=True)
             up.close()
