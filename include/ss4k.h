@@ -293,6 +293,15 @@ int ss4k_frvsr_upscale_frames(ss4k_frvsr_upscaler* up, const uint8_t* in_nhwc_de
                               size_t out_capacity_bytes, void* hip_stream);
 int ss4k_frvsr_upscale_streams(ss4k_frvsr_upscaler* up, const int32_t* slots, int n_streams, const uint8_t* in_nhwc_dev, int h, int w,
                                uint8_t* out_nhwc_dev, size_t out_capacity_bytes, void* hip_stream);
+/* One round like ss4k_frvsr_upscale_streams with the frames SCATTERED: item i's input frame is in_frames_dev[i] (h, w, 3) uint8 and its result goes to
+ * out_frames_dev[i] (out_h, out_w, 3) uint8 - host arrays of n_streams DEVICE pointers, the frames anywhere in device memory (rows of a ring's staging
+ * tensor, allocations of their own), at any byte alignment.  The tables travel by value in the kernel arguments: no device table, no upload, no
+ * synchronisation.  A round's glue is three launches whatever n_streams is (frames in, pack, frames out) and writes no fp32 intermediate.  Every
+ * output byte and every slot's state is bit for bit what ss4k_frvsr_upscale_streams gives for the same frames and slots, and the two may be mixed on
+ * one object.  Refuses what that call refuses, and NULL tables or entries, with SS4K_EINVAL before any slot changes; out_frame_capacity_bytes is the
+ * size of EACH output frame. */
+int ss4k_frvsr_upscale_streams_at(ss4k_frvsr_upscaler* up, const int32_t* slots, int n_streams, const uint8_t* const* in_frames_dev, int h, int w,
+                                  uint8_t* const* out_frames_dev, size_t out_frame_capacity_bytes, void* hip_stream);
 /* Parity taps of the LAST frame of the last call - after ss4k_frvsr_upscale_streams: of the LAST ITEM of the last round -, fp32 NCHW: 0 = lr_curr,
  * 1 = lr flow (padded, (1, 2, h, w)), 2 = the warped and space-to-depth tensor (1, 48, h, w), 3 = hr_curr (unclamped).  As
  * ss4k_upscaler_enable_taps / _read_tap. */

@@ -34,6 +34,7 @@ SYMBOLS = [
     "ss4k_frvsr_upscaler_reset", "ss4k_frvsr_upscaler_out_shape", "ss4k_frvsr_upscale_frames", "ss4k_frvsr_upscaler_enable_taps",
     "ss4k_frvsr_upscaler_read_tap", "ss4k_op_backward_warp", "ss4k_op_bicubic_upsample4",
     "ss4k_frvsr_upscaler_create_streams", "ss4k_frvsr_upscale_streams", "ss4k_frvsr_upscaler_reset_stream", "ss4k_frvsr_upscaler_state_bytes",
+    "ss4k_frvsr_upscale_streams_at",
 ]
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
@@ -192,6 +193,8 @@ def load(path: str) -> C.CDLL:
         L.ss4k_frvsr_upscale_streams.argtypes = [vp, C.POINTER(C.c_int32), i, vp, i, i, vp, sz, vp]
         L.ss4k_frvsr_upscaler_reset_stream.argtypes = [vp, i]
         L.ss4k_frvsr_upscaler_state_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
+    if hasattr(L, "ss4k_frvsr_upscale_streams_at"):   # (absent from builds before the scattered rounds)
+        L.ss4k_frvsr_upscale_streams_at.argtypes = [vp, C.POINTER(C.c_int32), i, C.POINTER(vp), i, i, C.POINTER(vp), sz, vp]
     return L
 
 
@@ -725,3 +728,28 @@ class FrvsrUpscaler:
         with torch.cuda.device(self.ctx.device):
             _check(lib().ss4k_frvsr_upscale_streams(self._h, ids, n, frames.data_ptr(), h, w, out.data_ptr(), out.numel(), _stream()))
         return out
+
+    @staticmethod
+    def has_streams_at() -> bool:
+        """Whether the loaded library has the scattered round (an older build loaded through SS4K_LIB has not)."""
+        return hasattr(lib(), "ss4k_frvsr_upscale_streams_at")
+
+    def upscale_streams_at(self, frames: Sequence[torch.Tensor], slots: Sequence[int], outs: Sequence[torch.Tensor]) -> None:
+        """One round like ``upscale_streams`` with the frames scattered: ``frames[i]`` is a contiguous ``(h, w, 3)`` uint8 device tensor - a
+        row of a larger tensor will do - with the next frame of the stream in slot ``slots[i]``, and its result is written into ``outs[i]``,
+        a contiguous ``(oh, ow, 3)`` one.  Nothing is gathered or scattered: the kernels read and write the frames where they lie
+        (ss4k_frvsr_upscale_streams_at), bit for bit what ``upscale_streams`` gives."""
+        n = len(frames)
+        slots = [int(s) for s in slots]
+        assert n >= 1 and len(slots) == n and len(outs) == n, "one slot and one output frame per frame"
+        h, w = int(frames[0].shape[0]), int(frames[0].shape[1])
+        oh, ow = self.out_shape()
+        for f, o in zip(frames, outs):
+            assert f.is_cuda and f.dtype == torch.uint8 and tuple(f.shape) == (h, w, 3) and f.is_contiguous(), "frames: contiguous (h, w, 3) uint8"
+            assert o.is_cuda and o.dtype == torch.uint8 and tuple(o.shape) == (oh, ow, 3) and o.is_contiguous(), "outs: contiguous (oh, ow, 3) uint8"
+            assert f.device == o.device == frames[0].device
+        ids = (C.c_int32 * n)(*slots)
+        fin = (C.c_void_p * n)(*[f.data_ptr() for f in frames])
+        fout = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_frvsr_upscale_streams_at(self._h, ids, n, fin, h, w, fout, oh * ow * 3, _stream()))

@@ -664,6 +664,18 @@ int ss4k_frvsr_upscale_streams(ss4k_frvsr_upscaler* up, const int32_t* slots, in
     up->u.round(in, slots, n_streams, h, w, out, (hipStream_t)stream);
   });
 }
+int ss4k_frvsr_upscale_streams_at(ss4k_frvsr_upscaler* up, const int32_t* slots, int n_streams, const uint8_t* const* in, int h, int w, uint8_t* const* out,
+                                  size_t frame_cap, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(up, "ss4k_frvsr_upscale_streams_at: NULL argument");
+    SS4K_REQUIRE(n_streams >= 1 && n_streams <= (int)up->u.slots.size(), "ss4k_frvsr_upscale_streams_at: n_streams must be in 1..max_streams");
+    SS4K_REQUIRE(slots && in && out, "ss4k_frvsr_upscale_streams_at: NULL argument");
+    SS4K_REQUIRE(h > 0 && w > 0, "ss4k_frvsr_upscale_streams_at: empty frames");
+    int oh, ow; up->u.out_shape(&oh, &ow);
+    SS4K_REQUIRE(frame_cap >= (size_t)oh * ow * 3, "ss4k_frvsr_upscale_streams_at: output frames too small");
+    up->u.round_at(in, slots, n_streams, h, w, out, (hipStream_t)stream);
+  });
+}
 int ss4k_frvsr_upscaler_enable_taps(ss4k_frvsr_upscaler* up, int en) {
   if (!up) return SS4K_EINVAL;
   up->u.taps_on = en != 0;

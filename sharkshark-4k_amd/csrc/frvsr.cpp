@@ -129,7 +129,14 @@ void Frvsr::run(const float* lr_curr, const float* lr_prev, const float* hr_prev
     if (!items) {
       net.pack_in(lr_curr, A, 1, n, 3, h, w, 1, st);
       net.pack_in(lr_prev, B, 1, n, 3, h, w, 1, st);
-    } else if (!plan) {   // item i's pixels are one contiguous run of the single plane
+    } else if (plan) {
+      return;
+    } else if (items->pack_batched) {
+      FrvsrPtrs c{}, p{};
+      for (int i = 0; i < n; ++i) { c.p[i] = const_cast<float*>(items->lr_curr[i]); p.p[i] = const_cast<float*>(items->lr_prev[i]); }
+      if (f16) op_pack_lr_items<__half>(c, p, reinterpret_cast<__half*>(A.p), reinterpret_cast<__half*>(B.p), n, h, w, st);
+      else op_pack_lr_items<float>(c, p, reinterpret_cast<float*>(A.p), reinterpret_cast<float*>(B.p), n, h, w, st);
+    } else {   // item i's pixels are one contiguous run of the single plane
       const size_t item_b = (size_t)h * w * conv_rec_bytes(desc.dtype);
       for (int i = 0; i < n; ++i) {
         net.pack_in(items->lr_curr[i], Tens{A.p + i * item_b, A.plane_bytes, 0}, 1, 1, 3, h, w, 1, st);
@@ -228,8 +235,7 @@ size_t FrvsrUpscaler::state_bytes() const {
   return b;
 }
 
-void FrvsrUpscaler::round(const uint8_t* in, const int32_t* slot_ids, int S, int h, int w, uint8_t* out, hipStream_t st) {
-  // every refusal comes before the first change of any slot
+void FrvsrUpscaler::check_round(const int32_t* slot_ids, int S, int h, int w) const {
   SS4K_REQUIRE(S >= 1 && S <= (int)slots.size(), "frvsr round: n_streams must be in 1..max_streams");
   SS4K_REQUIRE(h > 0 && w > 0, "frvsr round: empty frames");
   bool seen[SS4K_FRVSR_MAX_STREAMS] = {};
@@ -239,22 +245,24 @@ void FrvsrUpscaler::round(const uint8_t* in, const int32_t* slot_ids, int S, int
     seen[slot_ids[i]] = true;
   }
   SS4K_REQUIRE((double)S * 16.0 * lr_h * lr_w < 2147483648.0, "frvsr round: the output of a round holds at most 2^31 pixels per plane");
-  const int H = 4 * lr_h, W = 4 * lr_w;
-  int oh, ow; out_shape(&oh, &ow);
-  const size_t lr_b = (size_t)3 * lr_h * lr_w * 4, hr_b = (size_t)3 * H * W * 4;
-  const bool resize_in = h != lr_h || w != lr_w, resize_out = oh != H || ow != W;
-  auto glue = [&](auto&& body) {
-    if (!m->prof) { body(); return; }
-    Frvsr::Span sp{nullptr, nullptr, FRV_GLUE};
-    SS4K_HIP(hipEventCreate(&sp.a));
-    if (hipEventCreate(&sp.b) != hipSuccess) { (void)hipEventDestroy(sp.a); throw Error(SS4K_EHIP, "hipEventCreate failed"); }
-    m->spans.push_back(sp);
-    SS4K_HIP(hipEventRecord(sp.a, st));
-    body();
-    SS4K_HIP(hipEventRecord(sp.b, st));
-  };
-  const float* lr_curr[SS4K_FRVSR_MAX_STREAMS]; const float* lr_prev[SS4K_FRVSR_MAX_STREAMS];
-  FrvsrPtrs hr_prev{}, hr_curr{};
+}
+
+// a span of the service glue in the per-stage timing (stage 6), on the caller's stream
+template <typename F>
+void FrvsrUpscaler::glue_span(hipStream_t st, F&& body) {
+  if (!m->prof) { body(); return; }
+  Frvsr::Span sp{nullptr, nullptr, FRV_GLUE};
+  SS4K_HIP(hipEventCreate(&sp.a));
+  if (hipEventCreate(&sp.b) != hipSuccess) { (void)hipEventDestroy(sp.a); throw Error(SS4K_EHIP, "hipEventCreate failed"); }
+  m->spans.push_back(sp);
+  SS4K_HIP(hipEventRecord(sp.a, st));
+  body();
+  SS4K_HIP(hipEventRecord(sp.b, st));
+}
+
+// the first change of any slot in a round: every item's state buffers exist, a stream's first frame sees zeros, and the round's tables point at them
+void FrvsrUpscaler::open_slots(const int32_t* slot_ids, int S, hipStream_t st, RoundPtrs& r) {
+  const size_t lr_b = (size_t)3 * lr_h * lr_w * 4, hr_b = (size_t)3 * 16 * lr_h * lr_w * 4;
   for (int i = 0; i < S; ++i) {
     Slot& s = slots[slot_ids[i]];
     for (int k = 0; k < 2; ++k) { s.lr[k].ensure(lr_b); s.hr[k].ensure(hr_b); }
@@ -263,14 +271,35 @@ void FrvsrUpscaler::round(const uint8_t* in, const int32_t* slot_ids, int S, int
       SS4K_HIP(hipMemsetAsync(s.hr[s.cur].ptr, 0, hr_b, st));
       s.have_state = true;
     }
-    lr_prev[i] = s.lr[s.cur].as<float>(); lr_curr[i] = s.lr[s.cur ^ 1].as<float>();
-    hr_prev.p[i] = s.hr[s.cur].as<float>(); hr_curr.p[i] = s.hr[s.cur ^ 1].as<float>();
+    r.lr_prev[i] = s.lr[s.cur].as<float>(); r.lr_curr[i] = r.lr_dst.p[i] = s.lr[s.cur ^ 1].as<float>();
+    r.hr_prev.p[i] = s.hr[s.cur].as<float>(); r.hr_curr.p[i] = s.hr[s.cur ^ 1].as<float>();
   }
   m->keep_taps = taps_on;
-  glue([&] {
+}
+
+// after the step: the state takes the UNCLAMPED output (:206-207); the taps describe the round's last item
+void FrvsrUpscaler::close_slots(const int32_t* slot_ids, int S) {
+  for (int i = 0; i < S; ++i) slots[slot_ids[i]].cur ^= 1;
+  m->keep_taps = false;
+  if (taps_on) {
+    const int d[4][4] = {{1, 3, lr_h, lr_w}, {1, 2, lr_h, lr_w}, {1, 48, lr_h, lr_w}, {1, 3, 4 * lr_h, 4 * lr_w}};
+    std::memcpy(tap_dims, d, sizeof(d));
+    tap_slot = slot_ids[S - 1]; tap_item = S - 1;
+  }
+}
+
+void FrvsrUpscaler::round(const uint8_t* in, const int32_t* slot_ids, int S, int h, int w, uint8_t* out, hipStream_t st) {
+  check_round(slot_ids, S, h, w);   // every refusal comes before the first change of any slot
+  const int H = 4 * lr_h, W = 4 * lr_w;
+  int oh, ow; out_shape(&oh, &ow);
+  const size_t hr_b = (size_t)3 * H * W * 4;
+  const bool resize_in = h != lr_h || w != lr_w, resize_out = oh != H || ow != W;
+  RoundPtrs r{};
+  open_slots(slot_ids, S, st, r);
+  glue_span(st, [&] {
     for (int i = 0; i < S; ++i) {
       const uint8_t* frame = in + (size_t)i * h * w * 3;
-      float* dst = const_cast<float*>(lr_curr[i]);
+      float* dst = r.lr_dst.p[i];
       if (resize_in) {   // img / 255.0, F.interpolate(img, size=self.lr_shape, mode='area') (egvsr_upscaler.py:195-196)
         img.ensure((size_t)3 * h * w * 4);
         op_u8nhwc_to_f32nchw(frame, img.as<float>(), 1, h, w, 3, st);
@@ -281,28 +310,43 @@ void FrvsrUpscaler::round(const uint8_t* in, const int32_t* slot_ids, int S, int
     }
   });
   // (:204) one stream: the contiguous launchers, as before there were slots; several: the same step with every item's state where it lives
-  if (S == 1) m->step(lr_curr[0], lr_prev[0], hr_prev.p[0], hr_curr.p[0], 1, lr_h, lr_w, st);
-  else m->step_items(Frvsr::Items{lr_curr, lr_prev, &hr_prev, &hr_curr}, S, lr_h, lr_w, st);
-  for (int i = 0; i < S; ++i) slots[slot_ids[i]].cur ^= 1;   // the state takes the UNCLAMPED output (:206-207)
-  glue([&] {
+  if (S == 1) m->step(r.lr_curr[0], r.lr_prev[0], r.hr_prev.p[0], r.hr_curr.p[0], 1, lr_h, lr_w, st);
+  else m->step_items(Frvsr::Items{r.lr_curr, r.lr_prev, &r.hr_prev, &r.hr_curr}, S, lr_h, lr_w, st);
+  close_slots(slot_ids, S);
+  glue_span(st, [&] {
     for (int i = 0; i < S; ++i) {
       uint8_t* dst = out + (size_t)i * oh * ow * 3;
       if (resize_out) {   // clamp(hr_curr, 0, 1), F.interpolate(size=self.output_shape, mode='area') (:209-211)
         hrc.ensure(hr_b); outf.ensure((size_t)3 * oh * ow * 4);
-        op_clamp01_to(hr_curr.p[i], hrc.as<float>(), (size_t)3 * H * W, st);
+        op_clamp01_to(r.hr_curr.p[i], hrc.as<float>(), (size_t)3 * H * W, st);
         op_area(hrc.as<float>(), outf.as<float>(), 3, H, W, oh, ow, st);
         op_f32nchw_to_u8nhwc(outf.as<float>(), dst, 1, 3, oh, ow, st);
       } else {
-        op_f32nchw_to_u8nhwc(hr_curr.p[i], dst, 1, 3, H, W, st);   // (clamps, * 255, truncates: :209,212)
+        op_f32nchw_to_u8nhwc(r.hr_curr.p[i], dst, 1, 3, H, W, st);   // (clamps, * 255, truncates: :209,212)
       }
     }
   });
-  m->keep_taps = false;
-  if (taps_on) {
-    const int d[4][4] = {{1, 3, lr_h, lr_w}, {1, 2, lr_h, lr_w}, {1, 48, lr_h, lr_w}, {1, 3, H, W}};
-    std::memcpy(tap_dims, d, sizeof(d));
-    tap_slot = slot_ids[S - 1]; tap_item = S - 1;
+}
+
+void FrvsrUpscaler::round_at(const uint8_t* const* in, const int32_t* slot_ids, int S, int h, int w, uint8_t* const* out, hipStream_t st) {
+  check_round(slot_ids, S, h, w);
+  const int H = 4 * lr_h, W = 4 * lr_w;
+  int oh, ow; out_shape(&oh, &ow);
+  // what the two frame kernels' launchers would refuse is refused here, before the first change of any slot
+  SS4K_REQUIRE((double)h * lr_h < 2147483648.0 && (double)w * lr_w < 2147483648.0 && (double)H * oh < 2147483648.0 && (double)W * ow < 2147483648.0,
+               "frvsr round: frame sizes whose area window bounds overflow");
+  FrvsrFramesIn fin{}; FrvsrFramesOut fout{};
+  for (int i = 0; i < S; ++i) {
+    SS4K_REQUIRE(in[i] && out[i], "frvsr round: NULL frame pointer");
+    fin.p[i] = in[i]; fout.p[i] = out[i];
   }
+  RoundPtrs r{};
+  open_slots(slot_ids, S, st, r);
+  glue_span(st, [&] { op_frames_in_items(fin, r.lr_dst, S, h, w, lr_h, lr_w, st); });
+  // always the item launchers, S = 1 included: they are bit-identical to the contiguous ones, and the packing is one launch for the round
+  m->step_items(Frvsr::Items{r.lr_curr, r.lr_prev, &r.hr_prev, &r.hr_curr, true}, S, lr_h, lr_w, st);
+  close_slots(slot_ids, S);
+  glue_span(st, [&] { op_frames_out_items(r.hr_curr, fout, S, H, W, oh, ow, st); });
 }
 
 void FrvsrUpscaler::frames(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st) {

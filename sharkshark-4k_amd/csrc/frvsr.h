@@ -9,6 +9,9 @@ namespace ss4k {
 // each in its own allocation.  Passed BY VALUE in the kernel arguments (512 B): no device table, no upload, no synchronisation, and the
 // buffers stay separate DevBufs (a red zone around each in the dev library's guard mode).  Entries past the launch's n are not read.
 struct FrvsrPtrs { float* p[SS4K_FRVSR_MAX_STREAMS]; };
+// ... and of a scattered round's frames (ss4k_frvsr_upscale_streams_at): item i's input and output frame, uint8 HWC, any byte alignment
+struct FrvsrFramesIn { const uint8_t* p[SS4K_FRVSR_MAX_STREAMS]; };
+struct FrvsrFramesOut { uint8_t* p[SS4K_FRVSR_MAX_STREAMS]; };
 
 // ---- kernels (frvsr.hip).  "planes" tensors are the conv kernels' layout: [plane][pixel][16 channels of T] -----------------------------
 // nn.MaxPool2d(2, 2) (egvsr.py:24,31,38): (n, h, w) -> (n, h / 2, w / 2), odd sizes floored
@@ -35,6 +38,16 @@ template <typename T> void op_ps4_conv_tail_items(const T* in, const float* wb, 
 template <typename T> void op_planes_to_nchw(const T* in, float* out, int n, int channels, int h, int w, hipStream_t st);
 // clamp(x, 0, 1) into another tensor (egvsr_upscaler.py:209: the recurrent state keeps the unclamped one)
 void op_clamp01_to(const float* in, float* out, size_t n, hipStream_t st);
+
+// ---- the glue of a scattered round: ONE launch each for all n items, bit-identical to the per-item chains of FrvsrUpscaler::round ---------
+// item i: uint8 HWC (h, w, 3) at in.p[i] -> / 255 -> area to (lh, lw) when the sizes differ -> fp32 (3, lh, lw) at lr_curr.p[i]
+// (op_u8nhwc_to_f32nchw [+ op_area] of glue.hip, every window route of it)
+void op_frames_in_items(const FrvsrFramesIn& in, const FrvsrPtrs& lr_curr, int n, int h, int w, int lh, int lw, hipStream_t st);
+// item i's lr_curr.p[i] / lr_prev.p[i] (3, h, w) fp32 -> item i's run of the single planes a / b (op_pack_input<T> with r = 1, c = 3, one plane)
+template <typename T> void op_pack_lr_items(const FrvsrPtrs& lr_curr, const FrvsrPtrs& lr_prev, T* a, T* b, int n, int h, int w, hipStream_t st);
+// item i: hr.p[i] (3, H, W) fp32, left untouched -> clamp to [0, 1] -> area to (oh, ow) when the sizes differ -> clamp, * 255 truncated ->
+// uint8 HWC (oh, ow, 3) at out.p[i] (op_clamp01_to + op_area + op_f32nchw_to_u8nhwc, or the last alone); no fp32 intermediate in memory
+void op_frames_out_items(const FrvsrPtrs& hr, const FrvsrFramesOut& out, int n, int H, int W, int oh, int ow, hipStream_t st);
 
 size_t frvsr_param_count(const ss4k_frvsr_desc& d);   // 0 for a description that is refused
 
@@ -64,7 +77,8 @@ struct Frvsr {
   // the same step over n <= SS4K_FRVSR_MAX_STREAMS items that each live in buffers of their own (the service's streams): item i reads lr_curr[i],
   // lr_prev[i] (3, h, w) and hr_prev.p[i], writes hr_out.p[i].  Every conv, pool, x2, flow, warp and tail launch covers all n items; only the
   // input packing runs per item.  Bit-identical, item by item, to step() on a contiguous batch.
-  struct Items { const float* const* lr_curr; const float* const* lr_prev; const FrvsrPtrs* hr_prev; const FrvsrPtrs* hr_out; };
+  // pack_batched: the items' lr_curr / lr_prev are packed by ONE launch (op_pack_lr_items) instead of two per item
+  struct Items { const float* const* lr_curr; const float* const* lr_prev; const FrvsrPtrs* hr_prev; const FrvsrPtrs* hr_out; bool pack_batched = false; };
   void step_items(const Items& items, int n, int h, int w, hipStream_t st);
   size_t workspace_bytes(int n, int h, int w);
  private:
@@ -89,8 +103,17 @@ struct FrvsrUpscaler {
   void out_shape(int* oh, int* ow) const;
   // one frame for each of S distinct slots, as one n = S step: in (S, h, w, 3) -> out (S, oh, ow, 3), in the order of `slot_ids`
   void round(const uint8_t* in, const int32_t* slot_ids, int S, int h, int w, uint8_t* out, hipStream_t st);
+  // the same round with item i's frame at in[i] and its result at out[i] (host arrays of device pointers): three glue launches whatever S is
+  void round_at(const uint8_t* const* in, const int32_t* slot_ids, int S, int h, int w, uint8_t* const* out, hipStream_t st);
   void frames(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st);   // n consecutive frames of slot 0
   size_t state_bytes() const;
+ private:
+  // a round's per-item pointers into the slots' state: lr_curr (= lr_dst, as a table), lr_prev, hr_prev, hr_curr
+  struct RoundPtrs { const float* lr_curr[SS4K_FRVSR_MAX_STREAMS]; const float* lr_prev[SS4K_FRVSR_MAX_STREAMS]; FrvsrPtrs lr_dst, hr_prev, hr_curr; };
+  void check_round(const int32_t* slot_ids, int S, int h, int w) const;   // every refusal of a round, before any slot changes
+  void open_slots(const int32_t* slot_ids, int S, hipStream_t st, RoundPtrs& r);
+  void close_slots(const int32_t* slot_ids, int S);
+  template <typename F> void glue_span(hipStream_t st, F&& body);
 };
 
 }  // namespace ss4k

@@ -391,4 +391,146 @@ void op_clamp01_to(const float* in, float* out, size_t n, hipStream_t st) {
   SS4K_LAUNCH_OK();
 }
 
+// ------------------------------------------------------------------ the glue of a scattered round (FrvsrUpscaler::round_at)
+// Three launches for the whole round, each item's frame read and written where it lies (pointer tables by value, as FrvsrPtrs).  They restate
+// the arithmetic of the per-item chains of FrvsrUpscaler::round - k_u8nhwc_to_f32nchw, k_area / k_area_whole<4|8> / the identity copy, k_clamp01_to,
+// k_f32nchw_to_u8nhwc, k_pack_input<T, 1> (glue.hip) - expression for expression: the bytes and the state are bit-identical
+// (tests/test_gpu_frvsr_scattered.py).  Every area route sums its window rows outer, columns inner from 0.f and divides by the row count, then by
+// the column count; a whole-number window of the float bounds below is the window k_area_whole takes, so one loop stands for all of them.
+// window bounds of adaptive average pooling: glue.hip's a_start / a_end, the float formula
+__device__ __forceinline__ int area_lo(int i, int in, int out) { return (int)floorf((float)(i * in) / out); }
+__device__ __forceinline__ int area_hi(int i, int in, int out) { return (int)ceilf((float)((i + 1) * in) / out); }
+
+__global__ __launch_bounds__(256) void k_frames_in_items(FrvsrFramesIn in, FrvsrPtrs lr_curr, int n, int h, int w, int lh, int lw) {
+  const size_t lhw = (size_t)lh * lw, total = (size_t)n * lhw;
+  const bool resize = h != lh || w != lw;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t img = i / lhw, p = i - img * lhw;
+    const uint8_t* __restrict__ src = in.p[img];
+    float* __restrict__ dst = lr_curr.p[img] + p;
+    if (!resize) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) dst[k * lhw] = (float)src[p * 3 + k] / 255.0f;
+      continue;
+    }
+    const int oy = (int)(p / lw), ox = (int)(p - (size_t)oy * lw);
+    const int y0 = area_lo(oy, h, lh), y1 = area_hi(oy, h, lh), x0 = area_lo(ox, w, lw), x1 = area_hi(ox, w, lw);
+    float sum[3] = {0.f, 0.f, 0.f};
+    for (int y = y0; y < y1; ++y) {
+      const uint8_t* row = src + ((size_t)y * w + x0) * 3;
+      for (int x = 0; x < x1 - x0; ++x) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sum[k] += (float)row[3 * x + k] / 255.0f;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dst[k * lhw] = sum[k] / (float)(y1 - y0) / (float)(x1 - x0);
+  }
+}
+void op_frames_in_items(const FrvsrFramesIn& in, const FrvsrPtrs& lr_curr, int n, int h, int w, int lh, int lw, hipStream_t st) {
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && lh > 0 && lw > 0, "frames in (items): sizes");
+  SS4K_REQUIRE((double)h * lh < 2147483648.0 && (double)w * lw < 2147483648.0, "frames in (items): a window bound would overflow");
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(in.p[i] && lr_curr.p[i], "frames in (items): NULL item");
+  SS4K_GLUE_ROUTE(h != lh || w != lw ? "frvsr::frames_in_items<area>" : "frvsr::frames_in_items");
+  hipLaunchKernelGGL(k_frames_in_items, grid_for((size_t)n * lh * lw), dim3(256), 0, st, in, lr_curr, n, h, w, lh, lw);
+  SS4K_LAUNCH_OK();
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_pack_lr_items(FrvsrPtrs lr_curr, FrvsrPtrs lr_prev, uint4* __restrict__ a, uint4* __restrict__ b, int n, int h, int w) {
+  constexpr int RV = sizeof(T);   // 16-byte slots per 16-channel record
+  const size_t hw = (size_t)h * w, total = (size_t)n * hw;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t img = i / hw, p = i - img * hw;
+    const float* __restrict__ c = lr_curr.p[img] + p;
+    const float* __restrict__ q = lr_prev.p[img] + p;
+    union { T v[16]; uint4 u[RV]; } ra, rb;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { ra.v[k] = (T)(k < 3 ? c[k * hw] : 0.f); rb.v[k] = (T)(k < 3 ? q[k * hw] : 0.f); }
+#pragma unroll
+    for (int s = 0; s < RV; ++s) { a[i * RV + s] = ra.u[s]; b[i * RV + s] = rb.u[s]; }
+  }
+}
+template <typename T>
+void op_pack_lr_items(const FrvsrPtrs& lr_curr, const FrvsrPtrs& lr_prev, T* a, T* b, int n, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && a && b, "pack (items): sizes");
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(lr_curr.p[i] && lr_prev.p[i], "pack (items): NULL item");
+  SS4K_GLUE_ROUTE(sizeof(T) == 2 ? "frvsr::pack_lr_items<half>" : "frvsr::pack_lr_items<float>");
+  hipLaunchKernelGGL((k_pack_lr_items<T>), grid_for((size_t)n * h * w), dim3(256), 0, st, lr_curr, lr_prev, reinterpret_cast<uint4*>(a), reinterpret_cast<uint4*>(b),
+                     n, h, w);
+  SS4K_LAUNCH_OK();
+}
+template void op_pack_lr_items<float>(const FrvsrPtrs&, const FrvsrPtrs&, float*, float*, int, int, int, hipStream_t);
+template void op_pack_lr_items<__half>(const FrvsrPtrs&, const FrvsrPtrs&, __half*, __half*, int, int, int, hipStream_t);
+
+// One thread per FOUR consecutive output pixels of a frame taken as a flat run of oh * ow pixels (a group may straddle two rows): twelve bytes,
+// three 4-byte stores where the frame starts on a 4-byte boundary (k_tail_fused4's packing), twelve 1-byte stores otherwise and in the
+// frame's last, partial group.  RESIZE: each pixel is the mean of its window of CLAMPED values (k_clamp01_to, then k_area).
+__device__ __forceinline__ uint32_t u8_of(float v) { return (uint32_t)(uint8_t)(fminf(fmaxf(v, 0.f), 1.f) * 255.f); }
+template <bool RESIZE>
+__global__ __launch_bounds__(256) void k_frames_out_items(FrvsrPtrs hr, FrvsrFramesOut out, int n, int H, int W, int oh, int ow) {
+  const size_t HW = (size_t)H * W, opx = (size_t)oh * ow, groups = (opx + 3) / 4, total = (size_t)n * groups;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t img = i / groups, p0 = (i - img * groups) * 4;
+    const float* __restrict__ src = hr.p[img];
+    uint8_t* __restrict__ dst = out.p[img] + p0 * 3;
+    const int cnt = (int)(opx - p0 < 4 ? opx - p0 : 4);
+    uint32_t b[4][3] = {};
+    if constexpr (!RESIZE) {
+      if (cnt == 4 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {   // (HW = 16 lr_h lr_w: the planes lie a multiple of 16 bytes apart)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const float4 v = *reinterpret_cast<const float4*>(src + k * HW + p0);
+          b[0][k] = u8_of(v.x); b[1][k] = u8_of(v.y); b[2][k] = u8_of(v.z); b[3][k] = u8_of(v.w);
+        }
+      } else {
+        for (int j = 0; j < cnt; ++j)
+#pragma unroll
+          for (int k = 0; k < 3; ++k) b[j][k] = u8_of(src[k * HW + p0 + j]);
+      }
+    } else {
+      for (int j = 0; j < cnt; ++j) {
+        const size_t p = p0 + j;
+        const int oy = (int)(p / ow), ox = (int)(p - (size_t)oy * ow);
+        const int y0 = area_lo(oy, H, oh), y1 = area_hi(oy, H, oh), x0 = area_lo(ox, W, ow), x1 = area_hi(ox, W, ow);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const float* pl = src + k * HW;
+          float sum = 0.f;
+          for (int y = y0; y < y1; ++y)
+            for (int x = x0; x < x1; ++x) sum += fminf(fmaxf(pl[(size_t)y * W + x], 0.f), 1.f);
+          b[j][k] = u8_of(sum / (float)(y1 - y0) / (float)(x1 - x0));
+        }
+      }
+    }
+    if (cnt == 4 && (reinterpret_cast<uintptr_t>(dst) & 3) == 0) {
+      uint32_t wds[3] = {0u, 0u, 0u};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { const int byte = 3 * j + k; wds[byte >> 2] |= b[j][k] << (8 * (byte & 3)); }
+      uint32_t* o = reinterpret_cast<uint32_t*>(dst);
+      o[0] = wds[0]; o[1] = wds[1]; o[2] = wds[2];
+    } else {
+      for (int j = 0; j < cnt; ++j)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dst[3 * j + k] = (uint8_t)b[j][k];
+    }
+  }
+}
+void op_frames_out_items(const FrvsrPtrs& hr, const FrvsrFramesOut& out, int n, int H, int W, int oh, int ow, hipStream_t st) {
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && H > 0 && W > 0 && oh > 0 && ow > 0, "frames out (items): sizes");
+  SS4K_REQUIRE((double)H * oh < 2147483648.0 && (double)W * ow < 2147483648.0, "frames out (items): a window bound would overflow");
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(hr.p[i] && out.p[i], "frames out (items): NULL item");
+  const dim3 g = grid_for((size_t)n * (((size_t)oh * ow + 3) / 4));
+  if (H != oh || W != ow) {
+    SS4K_GLUE_ROUTE("frvsr::frames_out_items<area>");
+    hipLaunchKernelGGL(k_frames_out_items<true>, g, dim3(256), 0, st, hr, out, n, H, W, oh, ow);
+  } else {
+    SS4K_GLUE_ROUTE("frvsr::frames_out_items");
+    hipLaunchKernelGGL(k_frames_out_items<false>, g, dim3(256), 0, st, hr, out, n, H, W, oh, ow);
+  }
+  SS4K_LAUNCH_OK();
+}
+
 }  // namespace ss4k

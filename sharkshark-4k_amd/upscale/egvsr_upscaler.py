@@ -6,11 +6,22 @@ Same constructor arguments (``lr_level``, ``device``, ``on_queue``), attributes 
 uint8 HWC frame or a uint8 NHWC batch of CONSECUTIVE frames of one stream in, uint8 frames out; ``lr_prev`` / ``hr_prev`` are carried from
 frame to frame and from job to job (``:197-207``).  All arithmetic runs in libss4k_hip.so (``ss4k_frvsr_upscale_frames``, include/ss4k.h).
 
-The state lives in the worker, so a stream must stay on ONE worker: this service is not something ``node.UpscalerNode`` can shard
-(INTEGRATION.md).  One worker can hold SEVERAL streams, though: ``max_streams=S`` gives it S stream slots, ``upscale(frames, streams=ids)``
-names the stream of every frame of a job, and the frames of different streams go through the network together, one batched step per round
-(``ss4k_frvsr_upscale_streams``).  ``StreamQueueEntry`` is the job record that carries the ids; with the default ``max_streams=1`` and jobs
-without ids the service is what it was.  Weights as for the other services: ``weights=None`` looks ``EGVSR_iter420000.pth`` (``egvsr_upscaler.py:25``) up in
+The state lives in the worker, so a stream must stay on ONE worker: ``node.UpscalerNode`` (job ``step`` -> worker ``step % G``) cannot shard
+this service; ``egvsr_node.EgvsrNode`` can - it routes by stream id and keeps a stream where it opened.  One worker holds
+SEVERAL streams: ``max_streams=S`` gives it S stream slots, ``upscale(frames, streams=ids)`` names the stream of every frame of a job, and
+the frames of different streams go through the network together, one batched step per round.  A round reads every frame where it lies
+and writes every result where it goes (``ss4k_frvsr_upscale_streams_at``: three glue launches per round whatever its size, no gather, no
+scatter, no fp32 intermediate); a library from before that entry point takes the contiguous rounds (``ss4k_frvsr_upscale_streams``).
+``StreamQueueEntry`` is the job record that carries the ids; with the default ``max_streams=1`` and jobs without ids the service is what it
+was.
+
+Host frames (``host_rings``, set by ``egvsr_node.EgvsrNode`` or by the caller before ``start()``; ``hostring.py``): a job whose ``frames`` is a
+``HostFrames`` descriptor names a slot of this worker's pinned input ring.  The worker copies it to a staging tensor on a copy stream of its
+own, runs the job, copies the result into the named slot of the output ring on a second copy stream and answers with
+``HostFrames(result=True)``; one more job is enqueued before that result is waited for, so the copies run under the neighbour's kernels.  A
+``StreamQueueEntry`` with ``frames=None`` and ``end_streams`` only frees those slots: no GPU work, answered with ``frames=None``.
+
+Weights as for the other services: ``weights=None`` looks ``EGVSR_iter420000.pth`` (``egvsr_upscaler.py:25``) up in
 ``checkpoint_dir`` / ``$SS4K_CHECKPOINT_DIR`` and raises ``FileNotFoundError`` when it is missing; a path, the dict ``torch.load`` returns
 (a bare state_dict) or a state-dict table are taken as they are; ``'synthetic'`` is the tests' explicit opt-in.  The worker process,
 fork / spawn choice, caller-owned entry and profiler types come from ``BaseUpscalerService``.
@@ -24,6 +35,7 @@ from typing import Hashable, List, Optional, Sequence
 
 import torch
 
+from ..hostring import HostFrames
 from .upscaler_base import BaseUpscalerService, UpscalerQueueEntry, answer
 from ..util.profiler import Profiler
 
@@ -82,6 +94,11 @@ def plan_rounds(streams: Sequence[Hashable]) -> List[List[int]]:
 
 
 class HipEgvsrUpscalerService(BaseUpscalerService):
+    #: (frames-in ring, frames-out ring) of ``hostring.make_rings``, set before ``start()``: the worker then takes ``HostFrames`` jobs
+    host_rings = None
+    #: staging tensors per input shape: one more than the jobs that can be in flight (the job running, the one held back, the next one's copy)
+    HOST_STAGE_DEPTH = 3
+
     def __init__(self, lr_level=1, device=0, on_queue=None, *, weights=None, checkpoint_dir: Optional[str] = None, dtype="f16", nb=10,
                  lr_shape=None, seed=0, max_streams=1):
         self.lr_shape = tuple(lr_shape) if lr_shape is not None else LR_SHAPES[lr_level]
@@ -114,7 +131,70 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self._up = None
         self._up_key = None
         self._slots = StreamSlots(self.max_streams)
+        self._init_host_io()
         log("model loaded")
+
+    # host frames: HipUpscalerService._init_host_io / _staging / _host_job restated for this service (no job sets here: a job's launches are
+    # all on the current stream, so its end is one event recorded there)
+    def _init_host_io(self):
+        self._host_jobs = 0
+        self._landing = {}     # id(answer's HostFrames) -> (the HostFrames, event after which the result slot holds the frames)
+        self._lag_now = 0
+        if self.host_rings is None:
+            return
+        for ring in self.host_rings:
+            try:
+                ring.pin()
+            except RuntimeError as e:   # (copies to and from pageable memory still work - staged by the runtime, no longer asynchronous)
+                log(f"WARNING: {e}: host frames go through UNPINNED memory")
+        self._s_in, self._s_out = torch.cuda.Stream(self.torch_device), torch.cuda.Stream(self.torch_device)
+        self._stage = {}    # input shape -> [[device tensor, event after which it may be overwritten], ...], used round robin
+        self._stage_at = {}
+        log(f"host frame rings pinned: {self.host_rings[0].slots} slots, {self.host_rings[0].slot_bytes >> 10} KB in / {self.host_rings[1].slot_bytes >> 10} KB out each")
+
+    def _staging(self, shape):
+        bufs = self._stage.setdefault(shape, [])
+        if len(bufs) < self.HOST_STAGE_DEPTH:
+            bufs.append([torch.empty(shape, dtype=torch.uint8, device=self.torch_device), None])
+            return bufs[-1]
+        i = self._stage_at.get(shape, 0)
+        self._stage_at[shape] = (i + 1) % self.HOST_STAGE_DEPTH
+        return bufs[i]
+
+    def _host_job(self, hf: HostFrames, streams, end_streams):
+        """H2D on the copy stream -> upscale -> D2H on the other copy stream; returns (result shape, event after which the result slot holds
+        the frames)."""
+        src = self.host_rings[0].view(hf.slot, hf.shape)
+        with torch.cuda.device(self.torch_device):
+            cur = torch.cuda.current_stream(self.torch_device)
+            stage = self._staging(tuple(hf.shape))
+            with torch.cuda.stream(self._s_in):
+                if stage[1] is not None:
+                    self._s_in.wait_event(stage[1])
+                stage[0].copy_(src, non_blocking=True)
+                copied = self._s_in.record_event()
+            cur.wait_event(copied)
+            out = self.upscale(stage[0], streams, end_streams) if streams is not None or end_streams else self.upscale(stage[0])
+            done = cur.record_event()
+            stage[1] = done
+            with torch.cuda.stream(self._s_out):
+                self._s_out.wait_event(done)
+                self.host_rings[1].view(hf.out_slot, tuple(out.shape)).copy_(out, non_blocking=True)
+                landed = self._s_out.record_event()
+            out.record_stream(self._s_out)
+        return tuple(out.shape), landed
+
+    def proc_deliver_lag(self) -> int:
+        return getattr(self, "_lag_now", 0)
+
+    def proc_result_ready(self, entry) -> bool:
+        rec = getattr(self, "_landing", {}).get(id(getattr(entry, "frames", None)))
+        return rec is None or rec[1].query()
+
+    def proc_before_deliver(self, entry):
+        rec = getattr(self, "_landing", {}).pop(id(getattr(entry, "frames", None)), None)
+        if rec is not None:
+            rec[1].synchronize()   # the consumer reads the ring slot from another process: the bytes must have landed
 
     def proc_cleanup(self):
         for name in ("_up", "model", "ctx"):
@@ -185,7 +265,12 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
                 self._slots.end(sid)
             raise
         out = torch.empty((frames.shape[0],) + tuple(up.out_shape()) + (3,), dtype=torch.uint8, device=frames.device)
-        for idx in plan_rounds(streams):
+        if up.has_streams_at():   # every round reads frames[i] and writes out[i] where they lie: no gather, no scatter
+            frames = frames.contiguous()
+            for idx in plan_rounds(streams):
+                up.upscale_streams_at([frames[i] for i in idx], [slots[i] for i in idx], [out[i] for i in idx])
+            return out
+        for idx in plan_rounds(streams):   # a library from before the scattered rounds (an A/B through SS4K_LIB)
             if len(idx) == 1:
                 up.upscale_streams(frames[idx[0]:idx[0] + 1], [slots[idx[0]]], out=out[idx[0]:idx[0] + 1])
             else:   # gather the round's input frames (bytes of LR frames; the 4K state stays where it is), scatter its output
@@ -203,7 +288,20 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         prof.end("recoder.output")
         prof.start("upscaler.upscale")
         try:
-            upscaled = self.upscale(job.frames, streams, end_streams) if streams is not None or end_streams else self.upscale(job.frames)
+            if job.frames is None and end_streams:   # nothing to upscale: the ids give their slots back, the GPU is not touched
+                for sid in end_streams:
+                    self._slots.end(sid)
+                upscaled = None
+            elif isinstance(job.frames, HostFrames):
+                if self.host_rings is None:
+                    raise RuntimeError("a HostFrames job reached a worker that was started without host rings")
+                shape, landed = self._host_job(job.frames, streams, end_streams)
+                self._host_jobs += 1
+                upscaled = HostFrames(slot=job.frames.slot, out_slot=job.frames.out_slot, shape=shape, result=True)
+                self._landing[id(upscaled)] = (upscaled, landed)
+                self._lag_now = 1   # one more job is enqueued before this result is waited for: the copies hide under it
+            else:
+                upscaled = self.upscale(job.frames, streams, end_streams) if streams is not None or end_streams else self.upscale(job.frames)
         finally:
             prof.end("upscaler.upscale")
         elapsed = time.time() - arrived

@@ -12,8 +12,12 @@ each stream - stream k is the same scene ``5 k`` frames ahead - and one batched 
 (rounds x S), the per-stage figures likewise per frame.  ``--streams 1`` is the single-stream call exactly as before (it also runs on a
 library built before the slots existed: ``SS4K_LIB=<older build>`` for an A/B).  ``--lr`` / ``--output-shapes`` restrict the table.
 
-usage: python tools/frvsr_time.py [--frames 64] [--nb 10] [--streams 1] [--lr 540x960,720x1280] [--output-shapes 1440x2560,none]
-                                  [--out frvsr_time.json]"""
+``--scattered``: the same rounds through ``ss4k_frvsr_upscale_streams_at`` (``--streams 1`` included: rounds of one item), every input frame
+and every result an ALLOCATION OF ITS OWN - the shape of frames that arrive in ring slots and leave into ring slots.  A round's glue is
+then three launches whatever S is, and the glue column of the stage split is where it shows.
+
+usage: python tools/frvsr_time.py [--frames 64] [--nb 10] [--streams 1] [--scattered] [--lr 540x960,720x1280]
+                                  [--output-shapes 1440x2560,none] [--out frvsr_time.json]"""
 import argparse
 import json
 import os
@@ -51,6 +55,7 @@ def main():
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--nb", type=int, default=10)
     ap.add_argument("--streams", type=int, default=1, help="streams stepped in lockstep, one batched step per round")
+    ap.add_argument("--scattered", action="store_true", help="rounds through ss4k_frvsr_upscale_streams_at, frames and results as separate allocations")
     ap.add_argument("--lr", default=",".join(f"{h}x{w}" for h, w in REFERENCE_MS), help="lr shapes, HxW[,HxW...]")
     ap.add_argument("--output-shapes", default="1440x2560,none", help="output shapes, HxW or none[,...]")
     ap.add_argument("--out", default="frvsr_time.json")
@@ -69,6 +74,9 @@ def main():
         frames = stream_frames(a.frames, lr[0], lr[1], ctx.device)
         if S > 1:   # (frames, S, h, w, 3): round i holds frame i of every stream
             frames = torch.stack([torch.roll(frames, shifts=-5 * k, dims=0) for k in range(S)], dim=1)
+        if a.scattered:   # [round][item]: every frame in an allocation of its own
+            assert _capi.FrvsrUpscaler.has_streams_at(), "--scattered needs a library with ss4k_frvsr_upscale_streams_at"
+            apart = [[(frames[i] if S == 1 else frames[i, k]).clone() for k in range(S)] for i in range(a.frames)]
         for out_shape in out_shapes:
             up = _capi.FrvsrUpscaler(ctx, model, lr, out_shape, S)
             oh, ow = up.out_shape()
@@ -76,9 +84,16 @@ def main():
             out = torch.empty((half, oh, ow, 3) if S == 1 else (half, S, oh, ow, 3), dtype=torch.uint8, device=ctx.device)
             slots = list(range(S))
 
+            if a.scattered:
+                del out
+                out = [[torch.empty((oh, ow, 3), dtype=torch.uint8, device=ctx.device) for _ in range(S)] for _ in range(half)]
+
             def run(first, count):
                 """`count` consecutive frames of every stream from frame `first` on, into out[:count]"""
-                if S == 1:
+                if a.scattered:
+                    for i in range(count):
+                        up.upscale_streams_at(apart[first + i], slots, out[i])
+                elif S == 1:
                     up(frames[first:first + count], out[:count])
                 else:
                     for i in range(count):
@@ -98,7 +113,7 @@ def main():
             stages = {k: v / (16 * S) for k, v in model.prof_read().items()}
             model.prof_enable(False)
             ff, fs = conv_flops(lr[0], lr[1], a.nb)
-            row = dict(lr_shape=list(lr), output_shape=None if out_shape is None else list(out_shape), nb=a.nb, streams=S, frames_timed=half * S,
+            row = dict(lr_shape=list(lr), output_shape=None if out_shape is None else list(out_shape), nb=a.nb, streams=S, scattered=bool(a.scattered), frames_timed=half * S,
                        library=os.path.basename(os.path.dirname(_capi.LIB_PATH)) + "/" + os.path.basename(_capi.LIB_PATH),
                        state_bytes=up.state_bytes() if hasattr(_capi.lib(), "ss4k_frvsr_upscaler_state_bytes") else None,
                        ms_per_frame=ms, frames_per_s=1000.0 / ms, reference_ms_tensorrt_unknown_hw=REFERENCE_MS.get(lr), realtime_24fps_ms=1000.0 / 24,
@@ -106,7 +121,7 @@ def main():
                        srnet_conv_tflops=fs / stages["srnet_conv"] / 1e9, conv_tflop_per_step=(ff + fs) / 1e12,
                        workspace_mb=model.workspace_bytes(S, lr[0], lr[1]) / 2 ** 20)
             rows.append(row)
-            print(f"lr {lr[0]}x{lr[1]} -> {oh}x{ow}, {S} stream{'s' if S > 1 else ''}: {ms:.2f} ms/frame, {1000.0 / ms:.1f} frames/s "
+            print(f"lr {lr[0]}x{lr[1]} -> {oh}x{ow}, {S} stream{'s' if S > 1 else ''}{' scattered' if a.scattered else ''}: {ms:.2f} ms/frame, {1000.0 / ms:.1f} frames/s "
                   f"(reference {REFERENCE_MS.get(lr, float('nan')):.0f} ms, TensorRT, hardware unstated); "
                   + ", ".join(f"{k} {v:.2f}" for k, v in stages.items()) + f" ms; FNet convs {row['fnet_conv_tflops']:.0f} TFLOP/s, SRNet convs {row['srnet_conv_tflops']:.0f} TFLOP/s",
                   flush=True)
