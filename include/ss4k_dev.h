@@ -2,8 +2,9 @@
  * ss4k_dev.h - measurement-only entry points of libss4k_hip_dev.so (built with -DSS4K_DEV from the
  * same sources as libss4k_hip.so; a superset of include/ss4k.h).  Not part of the product library:
  * the instrumented / alternative-tile-shape instantiations of the conv kernel live only here.
- * Used by tools/stamp4.py, tools/traffic_ablate.py, tools/conv5_routes.py, tests/test_gpu_glue_budget.py and
- * tests/test_gpu_memory_hygiene.py (guard mode, through tests/drive_guarded.py).
+ * Used by tools/stamp4.py, tools/traffic_ablate.py, tools/conv5_routes.py, tests/test_gpu_glue_budget.py,
+ * tests/test_gpu_frvsr_glue_budget.py (the ss4k_dev_op_frvsr_* launchers) and tests/test_gpu_memory_hygiene.py (guard mode,
+ * through tests/drive_guarded.py).
  */
 #ifndef SS4K_DEV_H
 #define SS4K_DEV_H
@@ -72,6 +73,35 @@ int ss4k_dev_op_pack_input(ss4k_ctx* ctx, const float* in, void* out, int out_ha
                            int nplanes, void* hip_stream);
 int ss4k_dev_op_temporal_shift(ss4k_ctx* ctx, const void* in, void* out, int nplanes, int frames, size_t frame_px,
                                int slots_per_record, int ch_per_plane, int fold, void* hip_stream);
+
+/* ---- launchers of the frame-recurrent upscaler's glue (csrc/frvsr.hip, csrc/frvsr.h) that the public API reaches only inside a whole
+ * step or round: what tests/test_gpu_frvsr_glue_budget.py bounds against float64.  Same conventions as above; their routes are reported
+ * as "frvsr::...", and so are those of ss4k_op_bicubic_upsample4 / ss4k_op_backward_warp (include/ss4k.h) when called through this library.
+ * "planes": [plane][pixel (n, y, x)][16 channels] of float, or of __half where `half` != 0.  The _items forms take HOST arrays of n
+ * (1..64) device pointers, one per item, and pass them to the kernel by value. */
+int ss4k_dev_op_frvsr_maxpool2_planes(ss4k_ctx* ctx, const void* in, void* out, int half, int nplanes, int n, int h, int w, void* hip_stream);
+int ss4k_dev_op_frvsr_bilinear2_planes(ss4k_ctx* ctx, const void* in, void* out, int half, int nplanes, int n, int h, int w, void* hip_stream);
+/* raw (n, 2, h8, w8) -> tanh * 24, reflect-padded on the right and at the bottom to (n, 2, h, w); h - h8, w - w8 in 0..7 */
+int ss4k_dev_op_frvsr_flow_finish(ss4k_ctx* ctx, const float* raw, float* flow, int n, int h8, int w8, int h, int w, void* hip_stream);
+/* lr_flow (n, 2, h, w), hr_prev (n, 3, 4 h, 4 w) [items: hr_prev[i] (3, 4 h, 4 w)] -> three planes at (n, h, w) */
+int ss4k_dev_op_frvsr_warp_s2d_planes(ss4k_ctx* ctx, const float* lr_flow, const float* hr_prev, void* out, int half, int n, int h, int w,
+                                      void* hip_stream);
+int ss4k_dev_op_frvsr_warp_s2d_planes_items(ss4k_ctx* ctx, const float* lr_flow, const float* const* hr_prev, void* out, int half, int n,
+                                            int h, int w, void* hip_stream);
+/* four planes at (n, h, w), wb: 108 weights (OIHW) + 3 biases -> (n, 3, 4 h, 4 w) [items: out[i] (3, 4 h, 4 w)] */
+int ss4k_dev_op_frvsr_ps4_conv_tail(ss4k_ctx* ctx, const void* in, int half, const float* wb, float* out, int n, int h, int w, void* hip_stream);
+int ss4k_dev_op_frvsr_ps4_conv_tail_items(ss4k_ctx* ctx, const void* in, int half, const float* wb, float* const* out, int n, int h, int w,
+                                          void* hip_stream);
+int ss4k_dev_op_frvsr_planes_to_nchw(ss4k_ctx* ctx, const void* in, int half, float* out, int n, int channels, int h, int w, void* hip_stream);
+int ss4k_dev_op_frvsr_clamp01_to(ss4k_ctx* ctx, const float* in, float* out, size_t n, void* hip_stream);
+/* the three launches of a scattered round: in[i] uint8 (h, w, 3) -> lr_curr[i] (3, lh, lw); lr_curr[i] / lr_prev[i] (3, h, w) -> item i's
+ * run of the single planes a / b; hr[i] (3, H, W) -> out[i] uint8 (oh, ow, 3), any byte alignment */
+int ss4k_dev_op_frvsr_frames_in_items(ss4k_ctx* ctx, const uint8_t* const* in, float* const* lr_curr, int n, int h, int w, int lh, int lw,
+                                      void* hip_stream);
+int ss4k_dev_op_frvsr_pack_lr_items(ss4k_ctx* ctx, const float* const* lr_curr, const float* const* lr_prev, void* a, void* b, int half, int n,
+                                    int h, int w, void* hip_stream);
+int ss4k_dev_op_frvsr_frames_out_items(ss4k_ctx* ctx, const float* const* hr, uint8_t* const* out, int n, int H, int W, int oh, int ow,
+                                       void* hip_stream);
 
 /* Route report: every glue launcher counts the kernel route it chose under a static name ("glue::area_whole<NORM,8,half>", ...).
  * _read returns the index-th route in name order (SS4K_EINVAL past the last), _reset clears the table.  Process-wide. */

@@ -46,6 +46,11 @@ DEV_SYMBOLS = [
     "ss4k_dev_op_plane_stats_u8nhwc_partial", "ss4k_dev_op_plane_stats_finish", "ss4k_dev_op_plane_stats_finish2",
     "ss4k_dev_op_ps_nchw_addbase", "ss4k_dev_op_pack_input", "ss4k_dev_op_temporal_shift",
     "ss4k_dev_glue_routes_reset", "ss4k_dev_glue_routes_read",
+    # the launchers of csrc/frvsr.hip (tests/test_gpu_frvsr_glue_budget.py)
+    "ss4k_dev_op_frvsr_maxpool2_planes", "ss4k_dev_op_frvsr_bilinear2_planes", "ss4k_dev_op_frvsr_flow_finish",
+    "ss4k_dev_op_frvsr_warp_s2d_planes", "ss4k_dev_op_frvsr_warp_s2d_planes_items", "ss4k_dev_op_frvsr_ps4_conv_tail",
+    "ss4k_dev_op_frvsr_ps4_conv_tail_items", "ss4k_dev_op_frvsr_planes_to_nchw", "ss4k_dev_op_frvsr_clamp01_to",
+    "ss4k_dev_op_frvsr_frames_in_items", "ss4k_dev_op_frvsr_pack_lr_items", "ss4k_dev_op_frvsr_frames_out_items",
     # guard mode: red zones and 0xFF poison for every device buffer of the library (tests/test_gpu_memory_hygiene.py)
     "ss4k_dev_guard_enable", "ss4k_dev_guard_check", "ss4k_dev_guard_poison", "ss4k_dev_guard_selftest", "ss4k_dev_guard_poison_frvsr",
 ]
@@ -152,6 +157,19 @@ def load(path: str) -> C.CDLL:
         L.ss4k_dev_op_pack_input.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp]
         L.ss4k_dev_op_temporal_shift.argtypes = [vp, vp, vp, i, i, sz, i, i, i, vp]
         L.ss4k_dev_glue_routes_reset.argtypes = []
+        # csrc/frvsr.hip; the _items forms take host arrays of device pointers ((C.c_void_p * n)(...))
+        L.ss4k_dev_op_frvsr_maxpool2_planes.argtypes = [vp, vp, vp, i, i, i, i, i, vp]
+        L.ss4k_dev_op_frvsr_bilinear2_planes.argtypes = [vp, vp, vp, i, i, i, i, i, vp]
+        L.ss4k_dev_op_frvsr_flow_finish.argtypes = [vp, vp, vp, i, i, i, i, i, vp]
+        L.ss4k_dev_op_frvsr_warp_s2d_planes.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
+        L.ss4k_dev_op_frvsr_warp_s2d_planes_items.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
+        L.ss4k_dev_op_frvsr_ps4_conv_tail.argtypes = [vp, vp, i, vp, vp, i, i, i, vp]
+        L.ss4k_dev_op_frvsr_ps4_conv_tail_items.argtypes = [vp, vp, i, vp, vp, i, i, i, vp]
+        L.ss4k_dev_op_frvsr_planes_to_nchw.argtypes = [vp, vp, i, vp, i, i, i, i, vp]
+        L.ss4k_dev_op_frvsr_clamp01_to.argtypes = [vp, vp, vp, sz, vp]
+        L.ss4k_dev_op_frvsr_frames_in_items.argtypes = [vp, vp, vp, i, i, i, i, i, vp]
+        L.ss4k_dev_op_frvsr_pack_lr_items.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
+        L.ss4k_dev_op_frvsr_frames_out_items.argtypes = [vp, vp, vp, i, i, i, i, i, vp]
         L.ss4k_dev_glue_routes_read.argtypes = [i, C.c_char_p, sz, C.POINTER(C.c_int64)]
     if hasattr(L, "ss4k_dev_guard_check"):  # dev library only: guard mode
         L.ss4k_dev_guard_enable.argtypes = [i]

@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 
 namespace ss4k {
 
@@ -798,6 +799,76 @@ int ss4k_dev_op_temporal_shift(ss4k_ctx* c, const void* in, void* out, int nplan
                                int ch_per_plane, int fold, void* s) {
   SS4K_DEV_OP(c && in && out && slots_per_record > 0 && ch_per_plane >= slots_per_record, op_temporal_shift(in, out, nplanes, frames, frame_px, slots_per_record, ch_per_plane, fold, (hipStream_t)s));
 }
+// ---- the launchers of csrc/frvsr.hip that the public API reaches only through a whole step or round (tests/test_gpu_frvsr_glue_budget.py).
+// The _items forms take HOST arrays of n device pointers and fill the by-value tables the kernels receive
+#define SS4K_DEV_ITEMS(n) ((n) > 0 && (n) <= SS4K_FRVSR_MAX_STREAMS)
+extern "C++" {
+template <typename Tab, typename P> static Tab dev_items(P* const* host, int n) {
+  Tab t{};
+  for (int i = 0; i < n; ++i) t.p[i] = const_cast<std::remove_reference_t<decltype(t.p[0])>>(host[i]);
+  return t;
+}
+}
+int ss4k_dev_op_frvsr_maxpool2_planes(ss4k_ctx* c, const void* in, void* out, int half, int nplanes, int n, int h, int w, void* s) {
+  SS4K_DEV_OP(c && in && out,
+              if (half) op_maxpool2_planes((const __half*)in, (__half*)out, nplanes, n, h, w, (hipStream_t)s);
+              else op_maxpool2_planes((const float*)in, (float*)out, nplanes, n, h, w, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsr_bilinear2_planes(ss4k_ctx* c, const void* in, void* out, int half, int nplanes, int n, int h, int w, void* s) {
+  SS4K_DEV_OP(c && in && out,
+              if (half) op_bilinear2_planes((const __half*)in, (__half*)out, nplanes, n, h, w, (hipStream_t)s);
+              else op_bilinear2_planes((const float*)in, (float*)out, nplanes, n, h, w, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsr_flow_finish(ss4k_ctx* c, const float* raw, float* flow, int n, int h8, int w8, int h, int w, void* s) {
+  SS4K_DEV_OP(c && raw && flow, op_flow_finish(raw, flow, n, h8, w8, h, w, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsr_warp_s2d_planes(ss4k_ctx* c, const float* lr_flow, const float* hr_prev, void* out, int half, int n, int h, int w, void* s) {
+  SS4K_DEV_OP(c && lr_flow && hr_prev && out,
+              if (half) op_warp_s2d_planes(lr_flow, hr_prev, (__half*)out, n, h, w, (hipStream_t)s);
+              else op_warp_s2d_planes(lr_flow, hr_prev, (float*)out, n, h, w, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsr_warp_s2d_planes_items(ss4k_ctx* c, const float* lr_flow, const float* const* hr_prev, void* out, int half, int n, int h, int w,
+                                            void* s) {
+  SS4K_DEV_OP(c && lr_flow && hr_prev && out && SS4K_DEV_ITEMS(n),
+              const FrvsrPtrs t = dev_items<FrvsrPtrs>(hr_prev, n);
+              if (half) op_warp_s2d_planes_items(lr_flow, t, (__half*)out, n, h, w, (hipStream_t)s);
+              else op_warp_s2d_planes_items(lr_flow, t, (float*)out, n, h, w, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsr_ps4_conv_tail(ss4k_ctx* c, const void* in, int half, const float* wb, float* out, int n, int h, int w, void* s) {
+  SS4K_DEV_OP(c && in && wb && out,
+              if (half) op_ps4_conv_tail((const __half*)in, wb, out, n, h, w, (hipStream_t)s);
+              else op_ps4_conv_tail((const float*)in, wb, out, n, h, w, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsr_ps4_conv_tail_items(ss4k_ctx* c, const void* in, int half, const float* wb, float* const* out, int n, int h, int w, void* s) {
+  SS4K_DEV_OP(c && in && wb && out && SS4K_DEV_ITEMS(n),
+              const FrvsrPtrs t = dev_items<FrvsrPtrs>(out, n);
+              if (half) op_ps4_conv_tail_items((const __half*)in, wb, t, n, h, w, (hipStream_t)s);
+              else op_ps4_conv_tail_items((const float*)in, wb, t, n, h, w, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsr_planes_to_nchw(ss4k_ctx* c, const void* in, int half, float* out, int n, int channels, int h, int w, void* s) {
+  SS4K_DEV_OP(c && in && out && n > 0 && channels > 0 && h > 0 && w > 0,
+              if (half) op_planes_to_nchw((const __half*)in, out, n, channels, h, w, (hipStream_t)s);
+              else op_planes_to_nchw((const float*)in, out, n, channels, h, w, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsr_clamp01_to(ss4k_ctx* c, const float* in, float* out, size_t n, void* s) {
+  SS4K_DEV_OP(c && in && out && n > 0, op_clamp01_to(in, out, n, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsr_frames_in_items(ss4k_ctx* c, const uint8_t* const* in, float* const* lr_curr, int n, int h, int w, int lh, int lw, void* s) {
+  SS4K_DEV_OP(c && in && lr_curr && SS4K_DEV_ITEMS(n),
+              op_frames_in_items(dev_items<FrvsrFramesIn>(in, n), dev_items<FrvsrPtrs>(lr_curr, n), n, h, w, lh, lw, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsr_pack_lr_items(ss4k_ctx* c, const float* const* lr_curr, const float* const* lr_prev, void* a, void* b, int half, int n, int h, int w,
+                                    void* s) {
+  SS4K_DEV_OP(c && lr_curr && lr_prev && a && b && SS4K_DEV_ITEMS(n),
+              const FrvsrPtrs tc = dev_items<FrvsrPtrs>(lr_curr, n); const FrvsrPtrs tp = dev_items<FrvsrPtrs>(lr_prev, n);
+              if (half) op_pack_lr_items(tc, tp, (__half*)a, (__half*)b, n, h, w, (hipStream_t)s);
+              else op_pack_lr_items(tc, tp, (float*)a, (float*)b, n, h, w, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsr_frames_out_items(ss4k_ctx* c, const float* const* hr, uint8_t* const* out, int n, int H, int W, int oh, int ow, void* s) {
+  SS4K_DEV_OP(c && hr && out && SS4K_DEV_ITEMS(n),
+              op_frames_out_items(dev_items<FrvsrPtrs>(hr, n), dev_items<FrvsrFramesOut>(out, n), n, H, W, oh, ow, (hipStream_t)s));
+}
+#undef SS4K_DEV_ITEMS
 #undef SS4K_DEV_OP
 int ss4k_dev_glue_routes_reset(void) { return guard([&] { glue_routes_reset(); }); }
 int ss4k_dev_glue_routes_read(int index, char* name, size_t name_capacity, int64_t* launches) {

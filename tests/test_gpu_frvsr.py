@@ -79,6 +79,38 @@ def test_f32_service_frames_within_one_lsb_and_taps(ctx, name):
     up.close()
 
 
+def test_f32_service_frames_beyond_the_grid_within_one_lsb_and_taps(ctx):
+    """LR 368 x 360 -> HR 1472 x 1440 = 2,119,680 pixels: more than the 8192 x 256 threads a launch of csrc/frvsr.hip is capped at, so the
+    tail, the warp and the frame converters take the second pass of their grid-stride loops inside a whole round.  fp32, no residual blocks,
+    two frames that translate by (2, 4) pixels; the bars of test_f32_service_frames_within_one_lsb_and_taps.
+
+    The weights keep the generator's own flow gain of 1 (flows up to 2.4 LR px = 9.7 HR px).  The generated SRNet's picture is steep - up to
+    0.49 per HR pixel - so the warped tensor moves by 4 x 0.49 = 2 per LR pixel of flow and its atol of 1e-4 leaves 5e-5 LR px for the flow.
+    At a gain of 8 (flows of 15.7 LR px) the float32 oracle's own flow is 2.3e-5 LR px from a float64 chain of the same functions, half of
+    that bar before the kernels add theirs, and the MI355X missed it on 16 of 6.4 M elements (worst 1.77e-4) with every frame byte within
+    1 LSB; at a gain of 1 the oracle's flow is 3.6e-6 px from float64.  (The float32 position chain itself costs W 2^-23 px x 0.49 =
+    9e-5 against float64 at this width, oracle and kernel alike: it is the same chain, operation for operation.)"""
+    meta = dict(seed=41, nb=0, flow_gain=1.0)
+    lr = (368, 360)
+    base = smooth_u8(6, (1, lr[0] + 2, lr[1] + 4, 3))[0]
+    frames = torch.from_numpy(np.stack([base[2 * k:2 * k + lr[0], 4 * k:4 * k + lr[1]] for k in range(2)]))
+    assert 16 * lr[0] * lr[1] > 8192 * 256
+    up = _capi.FrvsrUpscaler(ctx, frvsr(ctx, meta), lr, None)
+    up.enable_taps(True)
+    got = up(frames.cuda()).cpu().numpy()
+    osvc = EO.OracleEgvsrUpscaler(table_for(meta), meta["nb"], lr, None)
+    want = osvc.upscale(frames).numpy()
+    d = np.abs(got.astype(np.int32) - want.astype(np.int32))
+    print(f"LR {lr}: max {d.max()} LSB, {(d > 0).mean():.4%} of the bytes differ; flow up to {float(osvc.taps['lr_flow'].abs().max()):.2f} LR px")
+    record_measured("frvsr_f32_service_368x360", worst_lsb=int(d.max()), differing_share=float((d > 0).mean()),
+                    flow_max_lr_px=float(osvc.taps["lr_flow"].abs().max()))
+    assert got.shape == want.shape == (2, 4 * lr[0], 4 * lr[1], 3) and d.max() <= 1
+    assert float(osvc.taps["lr_flow"].abs().max()) > 0.25, "the second frame must really be warped"
+    for which, key in enumerate(("lr_curr", "lr_flow", "s2d", "hr_curr")):
+        assert_close(up.read_tap(which), osvc.taps[key], what=f"LR {lr} tap {which} ({key})")
+    up.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------- the warp
 def test_granular_warp_ops_match_the_known_answers(ctx):
     _, a = load_case("kat_bicubic4_warp")

@@ -259,8 +259,9 @@ def assert_stats(got, ref64, what):
     return worst / P.U32
 
 
-def _budget(got, ref64, yard, what, half_out=False, col_bands=(4,), k_max=None):
-    """k_max: the case's own L-inf bar where tests/glue_cases.py gives one (with its reason); the shared bars otherwise."""
+def _budget(got, ref64, yard, what, half_out=False, col_bands=(4,), k_max=None, tiles=(1,)):
+    """k_max: the case's own L-inf bar where tests/glue_cases.py gives one (with its reason); the shared bars otherwise.
+    tiles: output pixels per layer pixel of the row / column band slices (tests/frvsr_glue_cases.py: 4 for tensors at HR)."""
     if half_out:
         yard, bars = G.round16(yard), dict(k_max=K16_MAX, k_slice=K16_SLICE, u=P.U16)
     else:
@@ -268,7 +269,7 @@ def _budget(got, ref64, yard, what, half_out=False, col_bands=(4,), k_max=None):
     if k_max is not None:
         assert not half_out and K32_MAX < k_max < 16
         bars["k_max"] = k_max
-    r = assert_error_budget(got, ref64, yard, what=what, tiles=(1,), col_bands=col_bands, **bars)
+    r = assert_error_budget(got, ref64, yard, what=what, tiles=tiles, col_bands=col_bands, **bars)
     return dict(max_ratio=r["max"], slice_ratio=r["slice"], worst_slice=str(r["worst_slice"]), asserted=f"max <= {bars['k_max']}, slice <= {bars['k_slice']}")
 
 
