@@ -3,7 +3,7 @@
  * same sources as libss4k_hip.so; a superset of include/ss4k.h).  Not part of the product library:
  * the instrumented / alternative-tile-shape instantiations of the conv kernel live only here.
  * Used by tools/stamp4.py, tools/traffic_ablate.py, tools/conv5_routes.py, tests/test_gpu_glue_budget.py,
- * tests/test_gpu_frvsr_glue_budget.py (the ss4k_dev_op_frvsr_* launchers) and tests/test_gpu_memory_hygiene.py (guard mode,
+ * tests/test_gpu_frvsr_glue_budget.py (the ss4k_dev_op_frvsr_* launchers), tests/test_gpu_frvsr_budget.py (ss4k_dev_frvsr_step_taps) and tests/test_gpu_memory_hygiene.py (guard mode,
  * through tests/drive_guarded.py).
  */
 #ifndef SS4K_DEV_H
@@ -102,6 +102,13 @@ int ss4k_dev_op_frvsr_pack_lr_items(ss4k_ctx* ctx, const float* const* lr_curr, 
                                     int h, int w, void* hip_stream);
 int ss4k_dev_op_frvsr_frames_out_items(ss4k_ctx* ctx, const float* const* hr, uint8_t* const* out, int n, int H, int W, int oh, int ow,
                                        void* hip_stream);
+
+/* ss4k_frvsr_step (include/ss4k.h) on a contiguous batch of n items, with the two tensors between FNet, the warp and SRNet copied out for
+ * EVERY item: flow_out (n, 2, h, w) = the padded LR flow, s2d_out (n, 48, h, w) = the warped, space-to-depth hr_prev as SRNet's first conv read
+ * it (an fp16 model: exactly the fp16 values), both fp32 device memory of the caller.  The public taps describe only the last item of a round.
+ * What tests/test_gpu_frvsr_budget.py bounds FNet's and SRNet's convolutions with, each against float64 on its own. */
+int ss4k_dev_frvsr_step_taps(ss4k_frvsr* m, const float* lr_curr, const float* lr_prev, const float* hr_prev, float* hr_out, float* flow_out,
+                             float* s2d_out, int n, int h, int w, void* hip_stream);
 
 /* Route report: every glue launcher counts the kernel route it chose under a static name ("glue::area_whole<NORM,8,half>", ...).
  * _read returns the index-th route in name order (SS4K_EINVAL past the last), _reset clears the table.  Process-wide. */

@@ -32,6 +32,10 @@ U32 = 2.0 ** -24   # ... of fp32
 _FS_PRELU = {"feature_extraction.0": "feature_extraction.1", "shrink.0": "shrink.1", "expand.0": "expand.1",
              **{f"map.{2 * i}": f"map.{2 * i + 1}" for i in range(4)}}
 
+# conv kernels the fp16 path keeps in fp32: the frame-recurrent upscaler's tail (PixelShuffle, ReLU, conv_out: csrc/frvsr.hip) reads its 108
+# weights as given and writes fp32
+_FP32_WEIGHTS = {"srnet.conv_out.weight"}
+
 
 def round16(a) -> np.ndarray:
     """float64 array of the fp16 values nearest ``a`` (round to nearest even; beyond the range: inf)."""
@@ -61,7 +65,7 @@ def table16(table: Mapping, net: Callable) -> dict:
         out["deconv.weight"] = round16(t["deconv.weight"])
         return out
     for k, v in t.items():
-        if k.endswith(".weight") and v.ndim == 4:
+        if k.endswith(".weight") and v.ndim == 4 and k not in _FP32_WEIGHTS:
             out[k] = round16(v)
     return out
 

@@ -51,6 +51,8 @@ DEV_SYMBOLS = [
     "ss4k_dev_op_frvsr_warp_s2d_planes", "ss4k_dev_op_frvsr_warp_s2d_planes_items", "ss4k_dev_op_frvsr_ps4_conv_tail",
     "ss4k_dev_op_frvsr_ps4_conv_tail_items", "ss4k_dev_op_frvsr_planes_to_nchw", "ss4k_dev_op_frvsr_clamp01_to",
     "ss4k_dev_op_frvsr_frames_in_items", "ss4k_dev_op_frvsr_pack_lr_items", "ss4k_dev_op_frvsr_frames_out_items",
+    # a whole step with every item's flow and warped space-to-depth tensor copied out (tests/test_gpu_frvsr_budget.py)
+    "ss4k_dev_frvsr_step_taps",
     # guard mode: red zones and 0xFF poison for every device buffer of the library (tests/test_gpu_memory_hygiene.py)
     "ss4k_dev_guard_enable", "ss4k_dev_guard_check", "ss4k_dev_guard_poison", "ss4k_dev_guard_selftest", "ss4k_dev_guard_poison_frvsr",
 ]
@@ -171,6 +173,8 @@ def load(path: str) -> C.CDLL:
         L.ss4k_dev_op_frvsr_pack_lr_items.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
         L.ss4k_dev_op_frvsr_frames_out_items.argtypes = [vp, vp, vp, i, i, i, i, i, vp]
         L.ss4k_dev_glue_routes_read.argtypes = [i, C.c_char_p, sz, C.POINTER(C.c_int64)]
+    if hasattr(L, "ss4k_dev_frvsr_step_taps"):  # dev library only
+        L.ss4k_dev_frvsr_step_taps.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
     if hasattr(L, "ss4k_dev_guard_check"):  # dev library only: guard mode
         L.ss4k_dev_guard_enable.argtypes = [i]
         L.ss4k_dev_guard_check.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), C.c_char_p, sz]

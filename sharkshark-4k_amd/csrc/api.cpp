@@ -870,6 +870,22 @@ int ss4k_dev_op_frvsr_frames_out_items(ss4k_ctx* c, const float* const* hr, uint
 }
 #undef SS4K_DEV_ITEMS
 #undef SS4K_DEV_OP
+// Frvsr::step on a contiguous batch with keep_taps set, and EVERY item's padded flow and warped space-to-depth tensor copied out next to hr_out
+// (the public taps describe only the last item of a round): what tests/test_gpu_frvsr_budget.py holds FNet and SRNet to, each on its own
+int ss4k_dev_frvsr_step_taps(ss4k_frvsr* m, const float* lr_curr, const float* lr_prev, const float* hr_prev, float* hr_out, float* flow_out,
+                             float* s2d_out, int n, int h, int w, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(m && lr_curr && lr_prev && hr_prev && hr_out && flow_out && s2d_out, "ss4k_dev_frvsr_step_taps: NULL argument");
+    Frvsr& f = m->f;
+    const bool was = f.keep_taps;
+    f.keep_taps = true;
+    try { f.step(lr_curr, lr_prev, hr_prev, hr_out, n, h, w, (hipStream_t)stream); } catch (...) { f.keep_taps = was; throw; }
+    f.keep_taps = was;
+    const size_t px = (size_t)n * h * w;
+    SS4K_HIP(hipMemcpyAsync(flow_out, f.flow.ptr, px * 2 * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    SS4K_HIP(hipMemcpyAsync(s2d_out, f.tap_s2d.ptr, px * 48 * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  });
+}
 int ss4k_dev_glue_routes_reset(void) { return guard([&] { glue_routes_reset(); }); }
 int ss4k_dev_glue_routes_read(int index, char* name, size_t name_capacity, int64_t* launches) {
   return guard([&] {

@@ -218,8 +218,105 @@ def test_route_error_budget(ctx, case):
         assert fams.get(PAIR, 0) == PAIR_LAUNCHES[case.id], f"{case.id}: {fams.get(PAIR, 0)} fused-pair launches, {PAIR_LAUNCHES[case.id]} expected"
 
 
+# ------------------------------------------------------------------------------ several tiles per workgroup
+# Every conv kernel is a persistent loop: a workgroup takes tile t, then t + gridDim (or the next of its band), prefetching the next tile's halo
+# and wrapping the weight ring onto it while it finishes the current one.  The cases above give every workgroup ONE tile (25 at the most);
+# in these the named launches have more tiles than workgroups, which is the product's steady state (a 720p frame: 920 tiles for 512 slots).
+# The second pass of the walk, the next-tile prefetch, the banded walk with uneven bands and - consecutive launches alternate it - the
+# reverse walk are then held per element.
+#
+# A job is N frames that alternate two pictures, P0 P1 P0 P1 ...: the references are computed for P0 and P1 only; frames 0 and 1 meet
+# the budget and every later frame is bit-identical to frame 0 or 1 (a frame's bits never depend on the job it arrives in).  Neighbours
+# differ, so a tile taken from the frame before shows.  Heights are off both row grids and widths are 32k + 11 (k + 12 for BSVD, whose
+# sizes are multiples of 4): the last band and the last tile of each walk are ragged.
+#
+# walk: build -> (its launch's resolution as a multiple of the layer resolution, cout groups).  The geometry comes from the launchers'
+# own rule (_walk_geometry) and the device's CU count; ``ntiles > grid`` is asserted for every one of them, so that on another part the
+# case fails loudly rather than passing on a single walk.  N as written is for 256 CUs; _walk_frames raises it by the same rule elsewhere.
+# Measured on MI355X (profiles/frvsr_conv_and_walk_parity_measured.json): fp16 max 0.43-1.05, slices under the u * peak floor; fp32 max 3.44 / slice 0.15.
+WalkCase = namedtuple("WalkCase", "case layer walk")
+_SV64 = dict(scale=2, num_feat=64, num_block=1)
+WALK_CASES = [
+    WalkCase(Case("walk_srvgg64_f16_x2", "srvgg", "f16", ONE, _SV64, (8, 3, 130, 267), {W16}), (130, 267), {W16: (1, 1)}),
+    WalkCase(Case("walk_srvgg64_f32_x2", "srvgg", "f32", ONE, _SV64, (8, 3, 130, 267), {F32_2}), (130, 267), {F32_2: (1, 1)}),
+    WalkCase(Case("walk_srvgg128_f16_x2", "srvgg", "f16", ONE, dict(scale=2, num_feat=128, num_block=1), (4, 3, 130, 267), {W16}),
+             (130, 267), {W16: (1, 2)}),
+    WalkCase(_rr("walk_rrdbnet_f16_x2", "f16", ONE, 2, (8, 3, 260, 534), {D4, D8, W16_RL, W16, W16N}),
+             (130, 267), {D4: (1, 1), D8: (1, 1), W16_RL: (1, 1), W16: (1, 1), W16N: (4, 1)}),
+    WalkCase(_rr("walk_rrdbnet_f16_x2_no_w16", "f16", ONE | NO_W16, 2, (8, 3, 260, 534), {WIDE, WIDE_RL, WIDE_UPS}),
+             (130, 267), {WIDE: (1, 1), WIDE_RL: (1, 1), WIDE_UPS: (2, 1)}),
+    WalkCase(Case("walk_bsvd32_f16_f1", "bsvd", "f16", ONE, dict(variant="bsvd-32"), (18, 4, 132, 268), {PAIR}), (132, 268), {PAIR: (1, 1)}),
+]
+
+
+def _walk_geometry(build, n, h, w, num_cu, groups=1):
+    """(tiles, workgroups along x) of one launch, by the launchers' own rule.  The tile kernels (conv_mfma.hip launch_t, conv_w16.hip,
+    conv_w16n.hip, conv_dense.hip): tiles of 16 (``<__half,1,5>``: 20) rows x 32 columns, grid = min(ntiles, num_cu * workgroups per CU /
+    cout groups) with 2 workgroups per CU (the exact-fp32 builds: 1, conv_tile.h wgs_per_cu; w16n: 3, no groups).  The fused pair
+    (conv_pair.hip) marches bands of rows down strips of 62 columns: bands = min(ceil(h / 16), slots / (n strips)) with at most 3 num_cu
+    slots (fewer slots only lengthen the walk), so its 16-row steps outnumber its workgroups as soon as a band is longer than 16 rows."""
+    if build == PAIR:
+        strips, rows16 = -(-w // 62), -(-h // 16)
+        bands = max(1, min(rows16, 3 * num_cu // (n * strips)))
+        return n * strips * rows16, n * strips * bands
+    ntiles = n * -(-h // (20 if build == H15 else 16)) * -(-w // 32)
+    per_cu = 1 if build in (F32_1, F32_2) else 3 if build == W16N else 2
+    return ntiles, min(ntiles, max(1, num_cu * per_cu // (1 if build == W16N else groups)))
+
+
+def _walk_frames(n, fits, limit=64):
+    """The smallest even job of at least ``n`` frames for which ``fits(n)`` holds (every named launch has more tiles than workgroups)."""
+    while n < limit and not fits(n):
+        n += 2
+    return n
+
+
+_walk_refs = {}
+
+
+def _walk_reference(c, kind, net, x2, t, args):
+    """ref64 / emu16 / fp32 oracle of the two pictures, shared by the cases that run the same network on the same input."""
+    key = (c.net, repr(sorted(c.arch.items())), tuple(x2.shape), float(x2.double().sum()), kind)
+    if key not in _walk_refs:
+        _walk_refs[key] = {"ref64": P.ref64, "emu16": P.emu16, "fp32": P.fp32_oracle}[kind](net, x2, t, *args)
+    return _walk_refs[key]
+
+
+@pytest.mark.parametrize("wc", WALK_CASES, ids=[w.case.id for w in WALK_CASES])
+def test_multi_tile_walk_error_budget(ctx, wc):
+    num_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    (lh, lw), c = wc.layer, wc.case
+    geometry = lambda n: {b: _walk_geometry(b, n, s * lh, s * lw, num_cu, g) for b, (s, g) in wc.walk.items()}
+    n = _walk_frames(c.shape[0], lambda n: all(t > g for t, g in geometry(n).values()))
+    for b, (ntiles, grid) in geometry(n).items():
+        print(f"{c.id}: {b}: {ntiles} tiles on {grid} workgroups ({n} frames, {num_cu} CUs)")
+        assert ntiles > grid, f"{c.id}: {b} has {ntiles} tiles for {grid} workgroups on {num_cu} CUs: no workgroup walks a second tile"
+    assert set(wc.walk) == c.must
+    c = c._replace(shape=(2,) + tuple(c.shape[1:]))
+    m, net, args, t, x2, tiles = _build(ctx, c)
+    # the two pictures: seeded by the shape, not by the case, so that the cases of one network and shape share their references
+    x2 = torch.rand(*x2.shape, generator=torch.Generator().manual_seed(sum(c.shape)))
+    x = x2.repeat((n // 2,) + (1,) * (x2.dim() - 1))              # P0 P1 P0 P1 ...
+    got, fams = _run_profiled(ctx, lambda: m(x.cuda()))
+    for k in range(2, n):
+        assert torch.equal(got[k], got[k % 2]), f"{c.id}: frame {k} differs from frame {k % 2}, the same picture"
+    got = got[:2].cpu()
+    ref = _walk_reference(c, "ref64", net, x2, t, args)
+    if c.dtype == "f16":
+        yard, bars = _walk_reference(c, "emu16", net, x2, t, args), dict(k_max=K16_MAX, k_slice=K16_SLICE, u=P.U16)
+    else:
+        yard, bars = _walk_reference(c, "fp32", net, x2, t, args), dict(k_max=K32_MAX, k_slice=K32_SLICE, u=P.U32)
+    r = error_budget(got, ref, yard, u=bars["u"], tiles=tiles)
+    print(c.id, r)
+    record_measured(f"error_budget_{c.id}", max_ratio=r["max"], slice_ratio=r["slice"], worst_slice=str(r["worst_slice"]), frames=n,
+                    asserted=f"max <= {bars['k_max']}, slice <= {bars['k_slice']}", builds=sorted(fams),
+                    tiles_over_workgroups={b: f"{a} / {g}" for b, (a, g) in geometry(n).items()})
+    assert_error_budget(got, ref, yard, what=c.id, tiles=tiles, **bars)
+    assert c.must <= set(fams), f"{c.id}: builds {sorted(c.must - set(fams))} not launched (launched: {sorted(fams)})"
+
+
 # ------------------------------------------------------------------------------ FSRCNN: f16 mode, fp32-grade split, exact
-FS_SIZES = [(1, 1, 5, 7), (2, 1, 33, 129), (1, 1, 150, 333)]
+FS_SIZES =[(1, 1, 5, 7), (2, 1, 33, 129), (1, 1, 150, 333)]
 
 
 def _fs_table(tag, factor):

@@ -5,7 +5,9 @@ The two kernels sum the same products in a different order (an MFMA adds 32 prod
 their results are NOT bit-identical; they must agree to within fp32 accumulation noise ahead of the fp16 rounding of each layer's
 output - far inside the fp16 path's own distance to the oracle - through every epilogue form the networks use (PReLU per channel,
 LeakyReLU, ReLU6, none, alpha, one and two residuals written in place, several cout groups, concat inputs), on ragged sizes
-(partly filled tiles on every edge), one to many tiles per workgroup, one and two launch chains."""
+(partly filled tiles on every edge), one to 110 tiles per launch, one and two launch chains.  (110 tiles are ONE tile per workgroup
+on a part of 256 CUs, whose grid holds 512: the launches in which a workgroup walks several tiles are those of
+tests/test_gpu_error_budget.py::test_multi_tile_walk_error_budget, per element against float64.)"""
 import pytest
 import torch
 
