@@ -1,4 +1,4 @@
-// Pure host-side table builders of the C ABI (api.cpp): no HIP call, no state.  They live in a header so that a host-only
+// Pure host-side table builders of the C ABI (api.cpp, upscaler.cpp): no HIP call, no state.  They live in a header so that a host-only
 // program (tests/hostcheck) can run them under the sanitizers exactly as the library does.
 #pragma once
 #include <algorithm>

@@ -671,17 +671,15 @@ void Model::abort_forward(hipStream_t st) noexcept {
   }
   if (section_open) { ctx->prof_pool.push_back(section); section_open = false; }
   tune_timed = nullptr; cur_lanes = 1;
-  out_stats_acc = nullptr; out_stats_done = false; out_half = false; in_u8 = false;
 }
 
-void Model::forward(const float* in, float* out, int n, int h, int w, hipStream_t st) {
-  try { forward_impl(in, out, n, h, w, st); }
+bool Model::forward(const float* in, float* out, int n, int h, int w, hipStream_t st, const ForwardOpts& o) {
+  try { return forward_impl(in, out, n, h, w, st, o); }
   catch (...) { if (!plan_only) abort_forward(st); throw; }
 }
 
-void Model::forward_impl(const float* in, float* out, int n, int h, int w, hipStream_t st) {
+bool Model::forward_impl(const float* in, float* out, int n, int h, int w, hipStream_t st, const ForwardOpts& fo) {
   SS4K_REQUIRE(n > 0 && h > 0 && w > 0, "forward: empty input");
-  out_stats_done = false;
   const bool f16 = desc.dtype == SS4K_F16;
   if (desc.kind != SS4K_FSRCNN) {
     // the conv kernel indexes the pixels of a plane with 32 bits: split batches whose largest internal
@@ -695,28 +693,26 @@ void Model::forward_impl(const float* in, float* out, int n, int h, int w, hipSt
     int max_n = std::max(1, (int)(2147483647.0 / plane1));
     if (sub_batch > 0) max_n = std::min(max_n, sub_batch);
     if (n > max_n) {
-      out_stats_acc = nullptr;   // per-plane accumulation is not offered across a split batch: the caller makes its own pass
-      SS4K_REQUIRE(!out_half, "forward: an fp16 output tensor is not offered across a split batch");
+      // per-plane accumulation is not offered across a split batch (the parts run without options): the caller makes its own pass
+      SS4K_REQUIRE(!fo.half_out, "forward: an fp16 output tensor is not offered across a split batch");
       for (int i = 0; i < n; i += max_n) {
         const int nn = std::min(max_n, n - i);
         forward(in + (size_t)i * in_channels() * h * w, out + (size_t)i * oc * oh * ow, nn, h, w, st);
       }
-      return;
+      return false;
     }
   }
   if (desc.kind == SS4K_FSRCNN) {
     const size_t px = (size_t)n * h * w;
     if (acts.size() < 2) acts.resize(2);
-    if (plan_only) { plan_bytes.assign(2, px * 12 * 4); return; }
+    if (plan_only) { plan_bytes.assign(2, px * 12 * 4); return false; }
     acts[0].ensure(px * 12 * 4); acts[1].ensure(px * 12 * 4);
 #ifdef SS4K_DEV
     acts[0].transient = acts[1].transient = true;
 #endif
-    const bool half_out = out_half; out_half = false;
-    const bool u8_in = in_u8; in_u8 = false;
     fsrcnn_forward(ctx, fsw, desc.scale, in, out, n, h, w, acts[0].as<float>(), acts[1].as<float>(),
-                   fs_exact ? FS_MODE_EXACT : f16 ? FS_MODE_HALF : FS_MODE_SPLIT, st, half_out, u8_in);
-    return;
+                   fs_exact ? FS_MODE_EXACT : f16 ? FS_MODE_HALF : FS_MODE_SPLIT, st, fo.half_out, fo.u8_in);
+    return false;
   }
   lanes_begin(n, h, w, st);
 #ifdef SS4K_DEV
@@ -770,7 +766,7 @@ void Model::forward_impl(const float* in, float* out, int n, int h, int w, hipSt
     { ConvOpts o; o.act = ACT_LRELU; o.slope = 0.2f; o.out = U3; conv(li++, U2, nullptr, n, 4 * H, 4 * W, o, st); }
     { ConvOpts o; o.epi = EPI_NCHW_F32; o.out = nchw_out(); conv(li++, U3, nullptr, n, 4 * H, 4 * W, o, st); }
     lanes_join(st, true);
-    return;
+    return false;
   }
   if (desc.kind == SS4K_SRVGG) {
     const int nf = desc.num_feat;
@@ -787,15 +783,12 @@ void Model::forward_impl(const float* in, float* out, int n, int h, int w, hipSt
     Tens Z = act(3, px, layers[li].cout_pad);
     { ConvOpts o; o.out = Z; conv(li++, cur, nullptr, n, h, w, o, st); }
     lanes_join(st, true);
-    if (plan_only) return;
-    // the service may ask for the output's plane statistics to be accumulated while it is written
-    double* sacc = out_stats_acc; out_stats_acc = nullptr; out_stats_done = sacc != nullptr;
-    const bool half_out = out_half; out_half = false;
-    SS4K_REQUIRE(!half_out || f16, "internal: fp16 output tensor requested from an fp32 network");
-    if (half_out) op_ps_nchw_addbase<__half, __half>(reinterpret_cast<const __half*>(Z.p), reinterpret_cast<__half*>(out), in, n, h, w, desc.scale, 3, sacc, st);
-    else if (f16) op_ps_nchw_addbase<__half>(reinterpret_cast<const __half*>(Z.p), out, in, n, h, w, desc.scale, 3, sacc, st);
-    else op_ps_nchw_addbase<float>(reinterpret_cast<const float*>(Z.p), out, in, n, h, w, desc.scale, 3, sacc, st);
-    return;
+    if (plan_only) return false;
+    SS4K_REQUIRE(!fo.half_out || f16, "internal: fp16 output tensor requested from an fp32 network");
+    if (fo.half_out) op_ps_nchw_addbase<__half, __half>(reinterpret_cast<const __half*>(Z.p), reinterpret_cast<__half*>(out), in, n, h, w, desc.scale, 3, fo.stats_acc, st);
+    else if (f16) op_ps_nchw_addbase<__half>(reinterpret_cast<const __half*>(Z.p), out, in, n, h, w, desc.scale, 3, fo.stats_acc, st);
+    else op_ps_nchw_addbase<float>(reinterpret_cast<const float*>(Z.p), out, in, n, h, w, desc.scale, 3, fo.stats_acc, st);
+    return fo.stats_acc != nullptr;   // the statistics rode along
   }
   // ---- BSVD, one frame per call -----------------------------------------------------------
   SS4K_REQUIRE(h % 4 == 0 && w % 4 == 0, "BSVD: frame size must be divisible by 4");
@@ -856,6 +849,7 @@ void Model::forward_impl(const float* in, float* out, int n, int h, int w, hipSt
       } }
   }
   lanes_join(st, true);
+  return false;
 }
 
 

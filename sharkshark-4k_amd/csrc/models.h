@@ -37,6 +37,18 @@ struct ParamCursor {
 };
 size_t model_param_count(const ss4k_model_desc& d);
 
+// What the service asks of ONE forward.  Each is honoured only by the network kinds named; the others ignore it.
+struct ForwardOpts {
+  // SRVGG: accumulate sum / sum of squares per output plane into this buffer while the output is written (forward() then returns true).
+  // Not offered across a split batch: its parts run without options, forward() returns false and the caller makes its own pass
+  double* stats_acc = nullptr;
+  // SRVGG and FSRCNN where can_half_out() says so: write the NCHW output tensor as fp16 instead of fp32 (an fp16 SRVGG's PixelShuffle tail converts
+  // anyway; an fp16-mode FSRCNN's tail stores from registers); the caller sized `out` accordingly.  Refused across a split batch
+  bool half_out = false;
+  // FSRCNN where can_u8_in() says so: `in` is the service's uint8 NHWC frame tensor (n = 3 x frames colour planes), not fp32 planes
+  bool u8_in = false;
+};
+
 struct Model {
   ss4k_ctx* ctx = nullptr;
   ss4k_model_desc desc{};
@@ -52,19 +64,9 @@ struct Model {
   bool plan_only = false;
   std::vector<size_t> plan_bytes;
   size_t workspace_bytes(int n, int h, int w);
-  // one-shot request of the caller (the service): accumulate sum / sum of squares per output plane into this buffer
-  // while the output is written (networks whose tail can do it set out_stats_done; the batch must not be split)
-  double* out_stats_acc = nullptr;
-  bool out_stats_done = false;
-  // one-shot request of the caller (like out_stats_acc): write the NCHW output tensor as fp16 instead of fp32.  Only honoured where
-  // can_half_out() says so (an fp16 SRVGG: its PixelShuffle tail converts anyway; an fp16-mode FSRCNN: its tail stores from registers); the caller sized `out` accordingly
-  bool out_half = false;
   bool hr_f32 = false;         // SS4K_MODEL_HR_F32
-  // one-shot request of the caller: `in` of the next forward is the service's uint8 NHWC frame tensor (n = 3 x frames colour planes), not fp32
-  // planes.  Only where can_u8_in() says so (an FSRCNN on the matrix-core head: it converts while it loads)
-  bool in_u8 = false;
-  // (both matrix-core modes: the fp32-grade head sits at 256 registers and the byte loader costs it four spilled registers, + 4 % on that
-  //  stage - the job still gains 2 % from the passes it no longer makes: profiles/NOTES_r06.md)
+  // where ForwardOpts::u8_in / half_out are honoured (u8_in, both matrix-core modes: the fp32-grade head sits at 256 registers and the byte
+  // loader costs it four spilled registers, + 4 % on that stage - the job still gains 2 % from the passes it no longer makes: profiles/NOTES_r06.md)
   bool can_u8_in() const { return desc.kind == SS4K_FSRCNN && !fs_exact; }
   bool can_half_out() const {
     return (desc.kind == SS4K_SRVGG || (desc.kind == SS4K_FSRCNN && !fs_exact)) && desc.dtype == SS4K_F16 && !plan_only && !hr_f32;
@@ -106,9 +108,9 @@ struct Model {
   void build(const float* w, size_t n);
   // forward() = forward_impl() inside a guard: if anything throws after the second launch chain was forked, the caller's
   // stream is made to wait for the lane stream (the next call must not race lane-1 kernels still reading the activation
-  // buffers), and the one-shot requests (out_stats_acc, the open profiling section, the timed tuning call) are dropped
-  void forward(const float* in, float* out, int n, int h, int w, hipStream_t st);
-  void forward_impl(const float* in, float* out, int n, int h, int w, hipStream_t st);
+  // buffers), and the open profiling section and the timed tuning call are dropped.  Returns whether o.stats_acc was filled along the way
+  bool forward(const float* in, float* out, int n, int h, int w, hipStream_t st, const ForwardOpts& o = {});
+  bool forward_impl(const float* in, float* out, int n, int h, int w, hipStream_t st, const ForwardOpts& o);
   void abort_forward(hipStream_t st) noexcept;
   void out_shape(int n, int h, int w, int* oc, int* oh, int* ow) const;
   int in_channels() const;

@@ -148,7 +148,7 @@ class HipUpscalerService(BaseUpscalerService):
         return int(kw["scale"] if kind == "rrdbnet" else kw["upscale"])
 
     def out_hw(self, h: int, w: int):
-        """(H, W) of the frames ``upscale`` returns for ``h x w`` input frames - the rule of ``ss4k_upscaler_out_shape`` (csrc/api.cpp
+        """(H, W) of the frames ``upscale`` returns for ``h x w`` input frames - the rule of ``ss4k_upscaler_out_shape`` (csrc/upscaler.cpp
         ``Upscaler::out_shape``; reference: fsrcnn_upscaler.py:174-176,223-233,236-241,316-326), evaluated on the host so that a launcher
         without a HIP context can size result buffers."""
         lh, lw = h, w

@@ -8,11 +8,13 @@ transient buffers are poisoned, then the case's own job runs; a fresh model runs
 a plane, meets NaN; a store past a buffer lands in a red zone; an element never stored keeps its 0xFF.
 
 Output: ``CASE <id> <sha256 of the output>`` per case (the parent compares them with the product library's), ``FAIL <id> <what>`` per
-finding, ``DONE <family> cases=.. guarded=.. poisoned=.. damaged=.. unguarded=..`` at the end.  Exit status 0 only without findings; a
+finding, ``ROUTES <config> <job> <json>`` per service job (the glue launchers' launch counts of that job alone: the parent holds them to a
+written-out table), ``DONE <family> cases=.. guarded=.. poisoned=.. damaged=.. unguarded=..`` at the end.  Exit status 0 only without findings; a
 HIP error is printed and ends the process at once (status 2): nothing more is started on the GPU after it.
 
 The job definitions (weights, inputs, shapes) are functions of this module, which the parent imports too: both sides run the same jobs."""
 import hashlib
+import json
 import os
 import sys
 
@@ -111,25 +113,42 @@ def _bsvd(ctx):
     return factory.build_denoise_model(ctx, weights=W.bsvd_table(seed=5, **factory.BSVD_VARIANTS["bsvd-32"]), dtype="f16", variant="bsvd-32")
 
 
-#: id -> (SR model, denoiser or None, lr_shape, output_shape, single_mode, input frame size)
+def _fs16(ctx):
+    return _fs(ctx, 2, "f16")
+
+
+#: id -> (SR model, denoiser or None, lr_shape, output_shape, single_mode, input frame size, parity taps on)
 SERVICE = {
     # the three configurations of tests/test_gpu_parity.py::test_service_bytes_within_float64_interval
-    "multi_srvgg_x4_color_bicubic_2to1": (_srvgg32, None, (72, 128), (144, 256), False, (72, 128)),
-    "single_fsrcnn_x2_u8_direct": (_fs, None, (90, 124), None, True, (90, 124)),
-    "multi_srvgg_f16_half_hr": (_srvgg16, None, (72, 128), None, False, (72, 128)),
-    "single_fsrcnn_x2_bsvd_denoise_resize": (_fs, _bsvd, (72, 128), (100, 180), True, (72, 128)),
-    "multi_srvgg_area_pre_resize": (_srvgg32, None, (72, 128), None, False, (108, 192)),
+    "multi_srvgg_x4_color_bicubic_2to1": (_srvgg32, None, (72, 128), (144, 256), False, (72, 128), False),
+    "single_fsrcnn_x2_u8_direct": (_fs, None, (90, 124), None, True, (90, 124), False),
+    "multi_srvgg_f16_half_hr": (_srvgg16, None, (72, 128), None, False, (72, 128), False),
+    "single_fsrcnn_x2_bsvd_denoise_resize": (_fs, _bsvd, (72, 128), (100, 180), True, (72, 128), False),
+    "multi_srvgg_area_pre_resize": (_srvgg32, None, (72, 128), None, False, (108, 192), False),
+    # the remaining branches of Upscaler::multi / single (csrc/upscaler.cpp).  Colour needs an HR tensor above 72 x 72 (HR / 8 > 8): x4 of
+    # 12 x 16 stays below it; BSVD needs LR sizes divisible by 4
+    "multi_srvgg_taps_color_bicubic": (_srvgg32, None, (72, 128), (144, 256), False, (72, 128), True),   # unfused, bilinear subtract, hr2
+    "multi_srvgg_taps_no_color": (_srvgg32, None, (12, 16), None, False, (12, 16), True),
+    "multi_srvgg_fused_no_color": (_srvgg32, None, (12, 16), None, False, (12, 16), False),
+    "multi_srvgg_f16_half_hr_bicubic": (_srvgg16, None, (24, 32), (60, 90), False, (24, 32), False),     # op_bicubic_u8<half>
+    "single_fsrcnn_f16_area_in": (_fs16, None, (45, 62), None, True, (90, 124), False),                  # half HR tensor, not u8-direct
+    "single_fsrcnn_f32_area_in_bicubic": (_fs, None, (45, 62), (100, 150), True, (90, 124), False),
+    "single_fsrcnn_bsvd_taps_bicubic": (_fs, _bsvd, (40, 64), (100, 150), True, (40, 64), True),          # unfused, both sharpen passes
+    "single_srvgg_f16": (_srvgg16, None, (24, 32), None, True, (24, 32), False),
+    "single_fsrcnn_f16_u8_direct_bicubic": (_fs16, None, (45, 62), (100, 150), True, (45, 62), False),
 }
 #: the uint8-input form of FSRCNN's matrix-core modes at the FSRCNN family's sizes (colour frames: three planes each)
-FS_U8 = {f"fsrcnn_u8_direct_{dt}_x{f}_{h}x{w}": ((lambda ctx, f=f, dt=dt: _fs(ctx, f, dt, 10 + f)), None, (h, w), None, True, (h, w))
+FS_U8 = {f"fsrcnn_u8_direct_{dt}_x{f}_{h}x{w}": ((lambda ctx, f=f, dt=dt: _fs(ctx, f, dt, 10 + f)), None, (h, w), None, True, (h, w), False)
          for dt in ("f16", "f32") for f in FS_FACTORS for (h, w) in ((5, 7), (33, 129))}
 SERVICE_JOBS = (3, 1, 2)   # frames per job, in this order on one upscaler
 
 
 def service_build(ctx, cfg):
-    mk_sr, mk_dn, lr_shape, out_shape, single, _ = cfg
+    mk_sr, mk_dn, lr_shape, out_shape, single, _, taps = cfg
     sr, dn = mk_sr(ctx), (mk_dn(ctx) if mk_dn else None)
-    return sr, dn, _capi.Upscaler(ctx, sr, lr_shape, out_shape, True, single, dn, 1.0)
+    up = _capi.Upscaler(ctx, sr, lr_shape, out_shape, True, single, dn, 1.0)
+    up.enable_taps(taps)
+    return sr, dn, up
 
 
 def service_job_frames(name, cfg, job, n):
@@ -323,26 +342,32 @@ def run_conv():
 
 def service_sequence(ctx, F, name, cfg):
     """3-frame job, poison, 1-frame job, poison, 2-frame job on ONE upscaler; every job twice - the arena around the input frames 0xFF,
-    then 0x00 (uint8 inputs cannot turn into NaN: an over-read shows as a dependence on the fill) - and against a new upscaler."""
+    then 0x00 (uint8 inputs cannot turn into NaN: an over-read shows as a dependence on the fill) - and against a new upscaler.  Each run's
+    glue launches are counted on their own; the job's ROUTES line is what both runs launched."""
+    L = _capi.lib()
     sr, dn, up = service_build(ctx, cfg)
     fresh = service_plain(ctx, name, cfg)
     for job, n in enumerate(SERVICE_JOBS):
         cid = f"{name}_job{job}_{n}frames"
         frames = service_job_frames(name, cfg, job, n)
-        outs = []
+        outs, routes = [], []
         for fill in (0xFF, 0x00):
             fin, cin = guarded(frames.shape, torch.uint8, fill=fill, device="cuda", data=frames)
             oh, ow = up.out_shape(*frames.shape[:3])
             out, cout = guarded((n, oh, ow, 3), torch.uint8, device="cuda")
             up.reset()
+            L.ss4k_dev_glue_routes_reset()
             up(fin, out=out)
             torch.cuda.synchronize()
+            routes.append(_capi.glue_routes(L))
             F.arenas(cid, f"input arena {fill:#04x}", cin, cout)
             F.guards(cid, f"input arena {fill:#04x}")
             outs.append(out.cpu())
         F.expect(torch.equal(outs[0], outs[1]), cid, f"{int((outs[0] != outs[1]).sum())} output bytes depend on the fill of the arena around the input")
         F.expect(sha(outs[0]) == fresh[job], cid, "differs from a new upscaler's result for the same frames")
+        F.expect(routes[0] == routes[1], cid, f"the two runs of the job launched different glue routes: {routes}")
         F.case(cid, sha(outs[0]))
+        print(f"ROUTES {name} {job} {json.dumps(routes[0], sort_keys=True)}", flush=True)
         nb = by = 0
         for args in ((ctx, sr, up), (None, dn, None)):
             if args[1] is not None:

@@ -16,6 +16,7 @@ launched.  The conv family also holds ss4k_model_workspace_bytes to the sum of a
 
 Glue launchers on caller tensors run guarded in tests/test_gpu_glue_budget.py itself (``Dev.put`` / ``Dev.new``); the glue family here
 covers the ops that allocate scratch inside the context."""
+import json
 import os
 import re
 import subprocess
@@ -46,6 +47,7 @@ def _child(family, timeout):
     assert r.returncode == 0 and len(done) == 1, r.stdout[-2000:] + r.stderr[-3000:]
     stats = {k: int(v) for k, v in re.findall(r"(\w+)=(\d+)", done[0])}
     cases = dict(ln.split()[1:3] for ln in lines if ln.startswith("CASE "))
+    stats["routes"] = {tuple(ln.split(" ", 3)[1:3]): json.loads(ln.split(" ", 3)[3]) for ln in lines if ln.startswith("ROUTES ")}
     assert stats["cases"] == len(cases) and stats["damaged"] == 0 and stats["unguarded"] == 0 and stats["fails"] == 0, done[0]
     assert stats["poisoned"] > 0 and stats["guarded"] > 0, done[0]
     record_measured(f"memory_hygiene_{family}", cases=stats["cases"], guarded_buffers=stats["guarded"], poisoned_bytes=stats["poisoned"],
@@ -84,14 +86,72 @@ def test_fsrcnn_guarded(ctx):
     _same(cases, product, "FSRCNN")
 
 
+#: {configuration: {glue route: launches}} of ONE job of tests/drive_guarded.py::SERVICE, whatever its frame count - every path of
+#: Upscaler::multi / single (csrc/upscaler.cpp) as a launch histogram.  Written out from the run of the commit BEFORE the upscaler moved
+#: into csrc/upscaler.cpp: a change of that file that is meant to launch what it launched must leave every line as it is.
+SERVICE_ROUTES = {
+    "multi_srvgg_x4_color_bicubic_2to1": {
+        "glue::area": 1, "glue::area_whole<NORM,8,float>": 1, "glue::bicubic_u8_half<float>": 1, "glue::gauss17": 1, "glue::pack_input<float,1>": 1,
+        "glue::ps_nchw_addbase<float,4,STATS,float>": 1, "glue::stats_final": 2, "glue::stats_partial<vec4,float>": 1, "glue::sub": 1,
+        "glue::tail_fused4<NORM,DIFF,float>": 1, "glue::u8nhwc_to_f32nchw": 1},
+    "single_fsrcnn_x2_u8_direct": {
+        "glue::stats_final2<rezero>": 1, "glue::stats_partial<vec4,float>": 1, "glue::stats_partial_u8<vec12>": 1,
+        "glue::tail_fused4<NORM,U8,float>": 1},
+    "multi_srvgg_f16_half_hr": {
+        "glue::area": 1, "glue::area_whole<NORM,8,half>": 1, "glue::gauss17": 1, "glue::pack_input<half,1>": 1,
+        "glue::ps_nchw_addbase<half,4,STATS,half>": 1, "glue::stats_final": 2, "glue::stats_partial<vec4,float>": 1, "glue::sub": 1,
+        "glue::tail_fused4<NORM,DIFF,U8,half>": 1, "glue::u8nhwc_to_f32nchw": 1},
+    "single_fsrcnn_x2_bsvd_denoise_resize": {
+        "glue::bicubic_u8<float>": 1, "glue::depthwise_reflect<3>": 2, "glue::pack_input<half,1>": 1, "glue::stats_final": 2,
+        "glue::stats_partial<vec4,float>": 2, "glue::tail_fused4<NORM,float>": 1, "glue::u8nhwc_to_f32nchw": 1},
+    "multi_srvgg_area_pre_resize": {
+        "glue::area": 2, "glue::area_whole<NORM,8,float>": 1, "glue::gauss17": 1, "glue::pack_input<float,1>": 1,
+        "glue::ps_nchw_addbase<float,4,STATS,float>": 1, "glue::stats_final": 2, "glue::stats_partial<vec4,float>": 1, "glue::sub": 1,
+        "glue::tail_fused4<NORM,DIFF,U8,float>": 1, "glue::u8nhwc_to_f32nchw": 1},
+    "multi_srvgg_taps_color_bicubic": {
+        "glue::area": 1, "glue::area_whole<8>": 1, "glue::bicubic": 1, "glue::bilinear<4>": 1, "glue::clamp01": 1, "glue::f32nchw_to_u8nhwc": 1,
+        "glue::gauss17": 1, "glue::normalize": 1, "glue::pack_input<float,1>": 1, "glue::ps_nchw_addbase<float,4,float>": 1, "glue::stats_final": 2,
+        "glue::stats_partial<vec4,float>": 2, "glue::sub": 1, "glue::u8nhwc_to_f32nchw": 1},
+    "multi_srvgg_taps_no_color": {
+        "glue::clamp01": 1, "glue::f32nchw_to_u8nhwc": 1, "glue::normalize": 1, "glue::pack_input<float,1>": 1,
+        "glue::ps_nchw_addbase<float,4,float>": 1, "glue::stats_final": 2, "glue::stats_partial<vec4,float>": 2, "glue::u8nhwc_to_f32nchw": 1},
+    "multi_srvgg_fused_no_color": {
+        "glue::pack_input<float,1>": 1, "glue::ps_nchw_addbase<float,4,STATS,float>": 1, "glue::stats_final": 2,
+        "glue::stats_partial<vec4,float>": 1, "glue::tail_fused4<NORM,U8,float>": 1, "glue::u8nhwc_to_f32nchw": 1},
+    "multi_srvgg_f16_half_hr_bicubic": {
+        "glue::area": 1, "glue::area_whole<NORM,8,half>": 1, "glue::bicubic_u8<half>": 1, "glue::gauss17": 1, "glue::pack_input<half,1>": 1,
+        "glue::ps_nchw_addbase<half,4,STATS,half>": 1, "glue::stats_final": 2, "glue::stats_partial<vec4,float>": 1, "glue::sub": 1,
+        "glue::tail_fused4<NORM,DIFF,half>": 1, "glue::u8nhwc_to_f32nchw": 1},
+    "single_fsrcnn_f16_area_in": {
+        "glue::area": 1, "glue::stats_final": 2, "glue::stats_partial<scalar,float>": 1, "glue::stats_partial<vec4,half>": 1,
+        "glue::tail_fused4<NORM,U8,half>": 1, "glue::u8nhwc_to_f32nchw": 1},
+    "single_fsrcnn_f32_area_in_bicubic": {
+        "glue::area": 1, "glue::bicubic_u8<float>": 1, "glue::stats_final": 2, "glue::stats_partial<scalar,float>": 1,
+        "glue::stats_partial<vec4,float>": 1, "glue::tail_fused4<NORM,float>": 1, "glue::u8nhwc_to_f32nchw": 1},
+    "single_fsrcnn_bsvd_taps_bicubic": {
+        "glue::bicubic": 1, "glue::clamp01": 1, "glue::depthwise_reflect<3>": 2, "glue::f32nchw_to_u8nhwc": 1, "glue::normalize": 1,
+        "glue::pack_input<half,1>": 1, "glue::stats_final": 2, "glue::stats_partial<vec4,float>": 2, "glue::u8nhwc_to_f32nchw": 1},
+    "single_srvgg_f16": {
+        "glue::pack_input<half,1>": 1, "glue::ps_nchw_addbase<half,4,half>": 1, "glue::stats_final": 2, "glue::stats_partial<vec4,float>": 1,
+        "glue::stats_partial<vec4,half>": 1, "glue::tail_fused4<NORM,U8,half>": 1, "glue::u8nhwc_to_f32nchw": 1},
+    "single_fsrcnn_f16_u8_direct_bicubic": {
+        "glue::bicubic_u8<half>": 1, "glue::stats_final2<rezero>": 1, "glue::stats_partial<vec4,half>": 1, "glue::stats_partial_u8<scalar>": 1,
+        "glue::tail_fused4<NORM,half>": 1},
+}
+
+
 def test_service_guarded(ctx):
-    cases, _ = _child("service", 600)
+    cases, stats = _child("service", 600)
     product = {}
     for name, cfg in DG.SERVICE.items():
         for job, (n, digest) in enumerate(zip(DG.SERVICE_JOBS, DG.service_plain(ctx, name, cfg))):
             product[f"{name}_job{job}_{n}frames"] = digest
-    assert len(product) == 5 * 3
+    assert len(product) == 14 * 3
     _same(cases, product, "service")
+    assert set(SERVICE_ROUTES) == set(DG.SERVICE)
+    assert set(stats["routes"]) == {(name, str(job)) for name in DG.SERVICE for job in range(len(DG.SERVICE_JOBS))}
+    for (name, job), launched in stats["routes"].items():
+        assert launched == SERVICE_ROUTES[name], f"{name}, job {job}: launched {launched}, the table has {SERVICE_ROUTES[name]}"
 
 
 def test_glue_context_scratch_guarded(ctx):

@@ -712,7 +712,7 @@ def test_fsrcnn_f16_mode_vs_oracle(ctx, factor, tag, shape):
 @pytest.mark.parametrize("dtype", ["f32", "f16"])
 def test_fsrcnn_service_accumulators_clean_themselves_across_jobs(ctx, dtype):
     """The uint8-direct FSRCNN job (no area resize, no denoiser) keeps ONE set of fp64 accumulators for both statistics, and its finishing
-    launch zeroes what it has read instead of the next job paying a memset (api.cpp: st_acc2).  Jobs of 4, 1, 3, 2, 4 frames through one
+    launch zeroes what it has read instead of the next job paying a memset (upscaler.cpp: st_acc2).  Jobs of 4, 1, 3, 2, 4 frames through one
     upscaler - different plane counts, hence different accumulator layouts over the same buffer - against a NEW upscaler per job: every
     byte.  Then the same job CAPTURED into a graph on a side stream (a captured job always carries the memset: it runs later, in whatever
     state eager jobs in between leave) and replayed around eager jobs."""
