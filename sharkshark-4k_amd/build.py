@@ -5,6 +5,7 @@
 conv kernel that the measurement tools use.  The product library carries none of that."""
 from __future__ import annotations
 
+import hashlib
 import os
 import subprocess
 import sys
@@ -76,13 +77,26 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
     return lib
 
 
-# ---- host check (tests/hostcheck, tests/test_hostcheck_cpu.py): the real models.cpp and pack.cpp, host side only, under ASan + UBSan,
+# ---- host check (tests/hostcheck, tests/test_hostcheck_cpu.py): the product's real host code, host side only, under ASan + UBSan,
 # linked against HIP stand-ins and launch auditors.  The program links no HIP runtime and no Python.  -DSS4K_DEV: DevBuf then allocates
 # through guardmode::alloc(need), which the stand-ins implement at the requested size (tests/hostcheck/standins.cpp).
+# Which product files it links is the program's own business - a product file can only be linked where auditors.cpp stands in for every
+# launcher it calls - so the program's directory names them (tests/hostcheck/PRODUCT_SOURCES, one file of csrc/ per line); a program
+# without that list is the one that audits models.cpp and pack.cpp alone.
 HOSTCHECK_DIR = os.path.join(HERE, "..", "tests", "hostcheck")
 HOSTCHECK = os.path.join(HOSTCHECK_DIR, "build", "hostcheck")
-HOSTCHECK_SOURCES = [os.path.join(CSRC, "models.cpp"), os.path.join(CSRC, "pack.cpp")] + \
-    [os.path.join(HOSTCHECK_DIR, f) for f in ("standins.cpp", "auditors.cpp", "main.cpp")]
+
+
+def _hostcheck_product_sources() -> list:
+    names = ["models.cpp", "pack.cpp"]
+    listing = os.path.join(HOSTCHECK_DIR, "PRODUCT_SOURCES")
+    if os.path.exists(listing):
+        with open(listing) as f:
+            names = [ln.strip() for ln in f if ln.strip() and not ln.startswith("#")]
+    return [os.path.join(CSRC, n) for n in names]
+
+
+HOSTCHECK_SOURCES = _hostcheck_product_sources() + [os.path.join(HOSTCHECK_DIR, f) for f in ("standins.cpp", "auditors.cpp", "main.cpp")]
 HOSTCHECK_FLAGS = ["-O2", "-g", "-std=c++17", "-x", "hip", "--offload-arch=gfx950", "--offload-host-only", "-DSS4K_DEV",
                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-Wall",
                    "-Wno-unused-function", "-Wno-unused-variable"]
@@ -93,10 +107,16 @@ def build_hostcheck(force: bool = False, verbose: bool = False) -> str:
     objdir = os.path.join(HOSTCHECK_DIR, "build")
     os.makedirs(objdir, exist_ok=True)
     jobs = []
+    # an object also remembers the text it was compiled from (the source and the program's headers): a tree whose files were exchanged for
+    # other versions, whatever their time stamps, does not keep objects of the versions before
+    headers = b"".join(open(os.path.join(HOSTCHECK_DIR, f), "rb").read() for f in sorted(os.listdir(HOSTCHECK_DIR)) if f.endswith(".h"))
+    digest = {}
     for src in HOSTCHECK_SOURCES:
         obj = os.path.join(objdir, os.path.splitext(os.path.basename(src))[0] + ".o")
         newest = max([os.path.getmtime(os.path.join(HOSTCHECK_DIR, f)) for f in os.listdir(HOSTCHECK_DIR) if f.endswith((".h", ".cpp"))])
-        if force or _needs_build(obj, src) or os.path.getmtime(obj) < newest:
+        digest[obj] = hashlib.sha256(open(src, "rb").read() + headers).hexdigest()
+        known = open(obj + ".sha").read() if os.path.exists(obj + ".sha") else ""
+        if force or _needs_build(obj, src) or os.path.getmtime(obj) < newest or known != digest[obj]:
             jobs.append((src, obj))
 
     def run(job):
@@ -107,11 +127,15 @@ def build_hostcheck(force: bool = False, verbose: bool = False) -> str:
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
+        with open(obj + ".sha", "w") as f:
+            f.write(digest[obj])
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         list(ex.map(run, jobs))
     objs = [os.path.join(objdir, os.path.splitext(os.path.basename(s))[0] + ".o") for s in HOSTCHECK_SOURCES]
-    if jobs or not os.path.exists(HOSTCHECK):
+    linked = os.path.join(objdir, "linked.txt")   # the objects the program on disk was linked from: another list is another program
+    same = os.path.exists(linked) and open(linked).read().split("\n") == objs
+    if jobs or not same or not os.path.exists(HOSTCHECK):
         # -no-hip-rt: no libamdhip64 on the link line - the program cannot open a GPU wherever it runs
         cmd = [hipcc, "-no-hip-rt", "-fsanitize=address,undefined", *objs, "-o", HOSTCHECK]
         if verbose:
@@ -119,6 +143,8 @@ def build_hostcheck(force: bool = False, verbose: bool = False) -> str:
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+        with open(linked, "w") as f:
+            f.write("\n".join(objs))
     return HOSTCHECK
 
 

@@ -235,7 +235,7 @@ size_t FrvsrUpscaler::state_bytes() const {
   return b;
 }
 
-void FrvsrUpscaler::check_round(const int32_t* slot_ids, int S, int h, int w) const {
+void FrvsrUpscaler::check_round(const int32_t* slot_ids, int S, int h, int w, bool area_chain) const {
   SS4K_REQUIRE(S >= 1 && S <= (int)slots.size(), "frvsr round: n_streams must be in 1..max_streams");
   SS4K_REQUIRE(h > 0 && w > 0, "frvsr round: empty frames");
   bool seen[SS4K_FRVSR_MAX_STREAMS] = {};
@@ -245,6 +245,11 @@ void FrvsrUpscaler::check_round(const int32_t* slot_ids, int S, int h, int w) co
     seen[slot_ids[i]] = true;
   }
   SS4K_REQUIRE((double)S * 16.0 * lr_h * lr_w < 2147483648.0, "frvsr round: the output of a round holds at most 2^31 pixels per plane");
+  if (area_chain) {   // round()'s per-item chains resize with op_area, whose grid holds one block row per output row (glue.hip: "area: grid limits")
+    int oh, ow; out_shape(&oh, &ow);
+    SS4K_REQUIRE((h == lr_h && w == lr_w) || lr_h <= 65535, "frvsr round: frames are resized to an lr_shape of at most 65535 rows");
+    SS4K_REQUIRE((oh == 4 * lr_h && ow == 4 * lr_w) || oh <= 65535, "frvsr round: the output is resized to at most 65535 rows");
+  }
 }
 
 // a span of the service glue in the per-stage timing (stage 6), on the caller's stream
@@ -289,7 +294,7 @@ void FrvsrUpscaler::close_slots(const int32_t* slot_ids, int S) {
 }
 
 void FrvsrUpscaler::round(const uint8_t* in, const int32_t* slot_ids, int S, int h, int w, uint8_t* out, hipStream_t st) {
-  check_round(slot_ids, S, h, w);   // every refusal comes before the first change of any slot
+  check_round(slot_ids, S, h, w, true);   // every refusal comes before the first change of any slot
   const int H = 4 * lr_h, W = 4 * lr_w;
   int oh, ow; out_shape(&oh, &ow);
   const size_t hr_b = (size_t)3 * H * W * 4;
@@ -329,7 +334,7 @@ void FrvsrUpscaler::round(const uint8_t* in, const int32_t* slot_ids, int S, int
 }
 
 void FrvsrUpscaler::round_at(const uint8_t* const* in, const int32_t* slot_ids, int S, int h, int w, uint8_t* const* out, hipStream_t st) {
-  check_round(slot_ids, S, h, w);
+  check_round(slot_ids, S, h, w, false);
   const int H = 4 * lr_h, W = 4 * lr_w;
   int oh, ow; out_shape(&oh, &ow);
   // what the two frame kernels' launchers would refuse is refused here, before the first change of any slot

@@ -110,7 +110,8 @@ struct FrvsrUpscaler {
  private:
   // a round's per-item pointers into the slots' state: lr_curr (= lr_dst, as a table), lr_prev, hr_prev, hr_curr
   struct RoundPtrs { const float* lr_curr[SS4K_FRVSR_MAX_STREAMS]; const float* lr_prev[SS4K_FRVSR_MAX_STREAMS]; FrvsrPtrs lr_dst, hr_prev, hr_curr; };
-  void check_round(const int32_t* slot_ids, int S, int h, int w) const;   // every refusal of a round, before any slot changes
+  // every refusal of a round, before any slot changes; area_chain: the round resizes with op_area (round), not inside the frame kernels (round_at)
+  void check_round(const int32_t* slot_ids, int S, int h, int w, bool area_chain) const;
   void open_slots(const int32_t* slot_ids, int S, hipStream_t st, RoundPtrs& r);
   void close_slots(const int32_t* slot_ids, int S);
   template <typename F> void glue_span(hipStream_t st, F&& body);

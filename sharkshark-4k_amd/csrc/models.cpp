@@ -678,8 +678,18 @@ bool Model::forward(const float* in, float* out, int n, int h, int w, hipStream_
   catch (...) { if (!plan_only) abort_forward(st); throw; }
 }
 
-bool Model::forward_impl(const float* in, float* out, int n, int h, int w, hipStream_t st, const ForwardOpts& fo) {
+// the input sizes a forward refuses, in one place: a caller that has work of its own to do first (Upscaler) asks before it starts
+void Model::check_input(int n, int h, int w) const {
   SS4K_REQUIRE(n > 0 && h > 0 && w > 0, "forward: empty input");
+  if (desc.kind == SS4K_RRDBNET) {
+    const int r = desc.scale == 2 ? 2 : desc.scale == 1 ? 4 : 1;
+    SS4K_REQUIRE(h % r == 0 && w % r == 0, "RRDBNet: input size must be divisible by the pixel-unshuffle factor");
+  }
+  if (desc.kind == SS4K_BSVD) SS4K_REQUIRE(h % 4 == 0 && w % 4 == 0, "BSVD: frame size must be divisible by 4");
+}
+
+bool Model::forward_impl(const float* in, float* out, int n, int h, int w, hipStream_t st, const ForwardOpts& fo) {
+  check_input(n, h, w);
   const bool f16 = desc.dtype == SS4K_F16;
   if (desc.kind != SS4K_FSRCNN) {
     // the conv kernel indexes the pixels of a plane with 32 bits: split batches whose largest internal
@@ -723,8 +733,7 @@ bool Model::forward_impl(const float* in, float* out, int n, int h, int w, hipSt
   auto nchw_out = [&]() { return Tens{reinterpret_cast<char*>(out), 0, 0}; };
   if (desc.kind == SS4K_RRDBNET) {
     const int nf = desc.num_feat, g = desc.num_grow_ch;
-    const int r = desc.scale == 2 ? 2 : desc.scale == 1 ? 4 : 1;
-    SS4K_REQUIRE(h % r == 0 && w % r == 0, "RRDBNet: input size must be divisible by the pixel-unshuffle factor");
+    const int r = desc.scale == 2 ? 2 : desc.scale == 1 ? 4 : 1;   // (h, w divisible by it: check_input)
     const int H = h / r, W = w / r;
     const size_t px = (size_t)n * H * W;
     const int cin0 = 3 * r * r;
@@ -791,7 +800,6 @@ bool Model::forward_impl(const float* in, float* out, int n, int h, int w, hipSt
     return fo.stats_acc != nullptr;   // the statistics rode along
   }
   // ---- BSVD, one frame per call -----------------------------------------------------------
-  SS4K_REQUIRE(h % 4 == 0 && w % 4 == 0, "BSVD: frame size must be divisible by 4");
   const int c0 = desc.bsvd_chns[0], c1 = desc.bsvd_chns[1], c2 = desc.bsvd_chns[2], mid = desc.bsvd_mid_ch;
   const size_t px = (size_t)n * h * w, px2 = px / 4, px4 = px / 16;
   const int h2 = h / 2, w2 = w / 2, h4 = h / 4, w4 = w / 4;

@@ -112,6 +112,7 @@ struct Model {
   bool forward(const float* in, float* out, int n, int h, int w, hipStream_t st, const ForwardOpts& o = {});
   bool forward_impl(const float* in, float* out, int n, int h, int w, hipStream_t st, const ForwardOpts& o);
   void abort_forward(hipStream_t st) noexcept;
+  void check_input(int n, int h, int w) const;   // SS4K_EINVAL for an input size forward() refuses (it asks first, too)
   void out_shape(int n, int h, int w, int* oc, int* oh, int* ow) const;
   int in_channels() const;
   bool no_rl = false;      // dev library (SS4K_NO_RL=1): conv5's residual read from memory in the epilogue instead of through the matrix core

@@ -130,19 +130,22 @@ void Upscaler::finish_unfused(float* hrp, int n, int H, int W, uint8_t* out, hip
 void Upscaler::multi(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st) {
   const int P = 3 * n;
   int lh, lw; lr_size(h, w, &lh, &lw);
-  const float* lrp = planes_in(in, n, h, w, lh, lw, st);
   int oc, H, W; sr->out_shape(n, lh, lw, &oc, &H, &W);
+  const int mh = H / 8, mw = W / 8;
+  const bool color = mh > 8 && H > 64 && W > 64;  // local colour match, :201-218
+  // ---- every refusal of a job that its sizes decide comes before the job's first launch and allocation
+  sr->check_input(n, lh, lw);
+  SS4K_REQUIRE(P <= STATS_MAX_PLANES, "too many frames in one job");
+  // the reference's guard looks at the height only; for HR widths of 65..71 its 17-tap reflect pad (8)
+  // reaches the 8-pixel-wide map and torch raises - so does this build
+  SS4K_REQUIRE(!color || mw > 8, "local colour match: HR width / 8 must exceed the 17-tap blur's reflect padding (torch raises here too)");
+  const float* lrp = planes_in(in, n, h, w, lh, lw, st);
   // fp16 HR tensor where the network's tail can write one (an fp16 SRVGG): the fused path below makes four passes over it (x4 on
   // 720p: 2880 x 5120 x 3 per frame), half the bytes each.  The fp32 parity path (taps) and fp32 models keep fp32.
   const bool hr16 = !taps_on && sr->can_half_out();
   hr.ensure((size_t)P * H * W * (hr16 ? 2 : 4));
   float* hrp = hr.as<float>();
   ensure_stats(P);
-  const int mh = H / 8, mw = W / 8;
-  const bool color = mh > 8 && H > 64 && W > 64;  // local colour match, :201-218
-  // the reference's guard looks at the height only; for HR widths of 65..71 its 17-tap reflect pad (8)
-  // reaches the 8-pixel-wide map and torch raises - so does this build
-  SS4K_REQUIRE(!color || mw > 8, "local colour match: HR width / 8 must exceed the 17-tap blur's reflect padding (torch raises here too)");
   const double tm0 = now_ms();
   // statistics of hr ride along with its producer where it can
   const bool hr_rode_along = sr->forward(lrp, hrp, n, lh, lw, st, ForwardOpts{taps_on ? nullptr : st_acc.as<double>(), hr16});
@@ -182,11 +185,16 @@ void Upscaler::single(const uint8_t* in, int n, int h, int w, uint8_t* out, hipS
   const int lh = cfg.lr_h, lw = cfg.lr_w, P = 3 * n;
   const size_t plane = (size_t)lh * lw;
   int oc, H, W; sr->out_shape(1, lh, lw, &oc, &H, &W);
+  // ---- every refusal of a job that its sizes decide comes before the job's first launch and allocation (and before first_frame changes)
+  sr->check_input(cfg.sr_is_realesrgan ? n : P, lh, lw);
+  if (cfg.denoising) dn->check_input(n, lh, lw);
+  SS4K_REQUIRE(P <= STATS_MAX_PLANES, "too many frames in one job");
   // FSRCNN on frames that need neither the area resize nor the denoiser reads the uint8 frames ITSELF (fsrcnn.hip, U8IN: the same
   // (float)byte / 255.0f) and the low-resolution statistics come straight from the bytes: the fp32 colour planes are never written
   // (round 6: one launch and 44 MB + 44 MB of traffic per four 720p frames less).  The parity path (taps) keeps the planes.
   const bool u8_direct = !taps_on && !cfg.denoising && !cfg.sr_is_realesrgan && h == lh && w == lw && sr->can_u8_in();
   if (u8_direct) {
+    SS4K_REQUIRE(2 * P <= STATS_MAX_PLANES, "too many frames in one job");   // (the frames' and the output's planes share one set of accumulators)
     const bool hr16 = sr->can_half_out();
     hr.ensure((size_t)P * H * W * 4 * 2);
     st_hr.ensure(P * 8); st_lr.ensure(P * 8);
@@ -194,7 +202,6 @@ void Upscaler::single(const uint8_t* in, int n, int h, int w, uint8_t* out, hipS
     // that also zeroes what it has read: the accumulators (their own buffer, sized once for the largest job) are memset only when they
     // are new or when a job died between its first partial sum and its finishing launch (three launches of ~ 5 us less than two
     // op_plane_stats calls, in a 0.65 ms job)
-    SS4K_REQUIRE(2 * P <= STATS_MAX_PLANES, "too many frames in one job");
     const size_t acc2_bytes = sizeof(double) * 2 * STATS_MAX_PLANES * STATS_SLOTS;
     if (st_acc2.bytes < acc2_bytes) { st_acc2.ensure(acc2_bytes); acc2_clean = false; }
     // (a job that is being CAPTURED into a graph by the caller runs later, any number of times, in whatever state an eager job in

@@ -7,29 +7,46 @@
 
 namespace hc {
 
-static std::map<const char*, size_t> g_reg;
+struct Entry {
+  size_t bytes = 0, lead = 0;        // lead: bytes of the host block in front of the registered range (reg_alloc_at)
+  bool tracked = false;             // allocated while g_log was set: `cov` holds the byte intervals written since
+  std::map<size_t, size_t> cov;     // start -> end, disjoint, merged on insert
+};
+static std::map<const char*, Entry> g_reg;
 Where g_where;
-long g_violations = 0, g_launches = 0;
-bool g_trace = false;
+long g_violations = 0, g_launches = 0, g_allocs = 0, g_memsets = 0;
+bool g_trace = false, g_log = false;
+std::vector<Launch> g_launch_log;
+std::vector<Memset> g_memset_log;
 
-void* reg_alloc(size_t bytes) {
-  char* p = static_cast<char*>(std::malloc(bytes ? bytes : 1));
+void* reg_alloc_at(size_t lead, size_t bytes) {
+  char* p = static_cast<char*>(std::malloc(lead + (bytes ? bytes : 1)));
   if (!p) throw std::bad_alloc();
-  std::memset(p, 0xFF, bytes);
-  g_reg[p] = bytes;
-  return p;
+  std::memset(p, 0xFF, lead + bytes);
+  Entry& e = g_reg[p + lead];
+  e = Entry{}; e.bytes = bytes; e.lead = lead; e.tracked = g_log;
+  ++g_allocs;
+  return p + lead;
 }
+void* reg_alloc(size_t bytes) { return reg_alloc_at(0, bytes); }
 void reg_free(void* p) {
   if (!p) return;
   auto it = g_reg.find(static_cast<const char*>(p));
   if (it == g_reg.end()) { std::fprintf(stdout, "VIOLATION free of an unknown pointer %p\n", p); ++g_violations; return; }
+  const size_t lead = it->second.lead;
   g_reg.erase(it);
-  std::free(p);
+  std::free(static_cast<char*>(p) - lead);
 }
 size_t reg_live() { return g_reg.size(); }
 void reg_shrink(const void* base, size_t bytes) {
   auto it = g_reg.find(static_cast<const char*>(base));
-  if (it != g_reg.end() && it->second >= bytes) it->second -= bytes;
+  if (it != g_reg.end() && it->second.bytes >= bytes) it->second.bytes -= bytes;
+}
+static std::map<const char*, Entry>::iterator owner(const char* q) {
+  auto it = g_reg.upper_bound(q);
+  if (it == g_reg.begin()) return g_reg.end();
+  --it;
+  return (size_t)(q - it->first) <= it->second.bytes ? it : g_reg.end();
 }
 bool reg_inside(const void* p, size_t bytes, size_t* off, size_t* alloc_bytes) {
   if (off) *off = 0;
@@ -41,8 +58,34 @@ bool reg_inside(const void* p, size_t bytes, size_t* off, size_t* alloc_bytes) {
   --it;
   const size_t o = (size_t)(q - it->first);
   if (off) *off = o;
-  if (alloc_bytes) *alloc_bytes = it->second;
-  return o <= it->second && bytes <= it->second - o;
+  if (alloc_bytes) *alloc_bytes = it->second.bytes;
+  return o <= it->second.bytes && bytes <= it->second.bytes - o;
+}
+void log_clear() { g_launch_log.clear(); g_memset_log.clear(); }
+void cov_write(const void* p, size_t bytes) {
+  if (!bytes) return;
+  auto e = owner(static_cast<const char*>(p));
+  if (e == g_reg.end() || !e->second.tracked) return;
+  auto& cov = e->second.cov;
+  size_t a = (size_t)(static_cast<const char*>(p) - e->first), b = a + bytes;
+  auto it = cov.lower_bound(a);
+  if (it != cov.begin()) {
+    auto pv = std::prev(it);
+    if (pv->second >= a) { a = pv->first; b = std::max(b, pv->second); it = cov.erase(pv); }
+  }
+  while (it != cov.end() && it->first <= b) { b = std::max(b, it->second); it = cov.erase(it); }
+  cov[a] = b;
+}
+bool cov_covered(const void* p, size_t bytes) {
+  if (!bytes) return true;
+  auto e = owner(static_cast<const char*>(p));
+  if (e == g_reg.end() || !e->second.tracked) return true;   // (outside every allocation: reported by the range check)
+  const auto& cov = e->second.cov;
+  const size_t a = (size_t)(static_cast<const char*>(p) - e->first);
+  auto it = cov.upper_bound(a);
+  if (it == cov.begin()) return false;
+  --it;
+  return it->second >= a + bytes;
 }
 
 }  // namespace hc
@@ -66,12 +109,13 @@ static hipError_t copy_checked(void* dst, const void* src, size_t bytes, hipMemc
   size_t off, ab;
   // the device side of an upload or a read-back lies inside one live allocation (the host side is the sanitizer's business)
   const void* dev = kind == hipMemcpyDeviceToHost ? src : dst;
-  if (!hc::reg_inside(dev, bytes, &off, &ab)) {
+  if (!hc::reg_inside(dev, bytes, &off, &ab) || (kind == hipMemcpyDeviceToDevice && !hc::reg_inside(src, bytes, &off, &ab))) {
     std::fprintf(stdout, "VIOLATION %s | hipMemcpy of %zu bytes at offset %zu of an allocation of %zu bytes\n", hc::g_where.desc.c_str(), bytes, off, ab);
     ++hc::g_violations;
     return hipSuccess;
   }
   std::memcpy(dst, src, bytes);
+  if (hc::g_log && kind != hipMemcpyDeviceToHost) hc::cov_write(dst, bytes);
   return hipSuccess;
 }
 hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) { return copy_checked(dst, src, bytes, kind); }
@@ -84,10 +128,16 @@ static hipError_t set_checked(void* p, int v, size_t bytes) {
     return hipSuccess;
   }
   std::memset(p, v, bytes);
+  // which buffers a round zeroed: (pointer, bytes, index of the launch the memset precedes)
+  ++hc::g_memsets;
+  if (hc::g_log) { hc::g_memset_log.push_back({static_cast<const char*>(p), bytes, hc::g_where.launch}); hc::cov_write(p, bytes); }
   return hipSuccess;
 }
 hipError_t hipMemset(void* p, int v, size_t bytes) { return set_checked(p, v, bytes); }
 hipError_t hipMemsetAsync(void* p, int v, size_t bytes, hipStream_t) { return set_checked(p, v, bytes); }
+hipError_t hipMemsetD32Async(hipDeviceptr_t p, int v, size_t count, hipStream_t) {   // (a 32-bit pattern: the content is not looked at, the range is)
+  return set_checked(p, v & 0xff, count * 4);
+}
 hipError_t hipEventCreate(hipEvent_t* e) { *e = reinterpret_cast<hipEvent_t>(&g_event_tag); return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = reinterpret_cast<hipEvent_t>(&g_event_tag); return hipSuccess; }
 hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }

@@ -1,4 +1,4 @@
-"""CPU: the host check - the product's models.cpp and pack.cpp, host side only, under ASan + UBSan (tests/hostcheck, DESIGN.md "Host check").
+"""CPU: the host check - the product's models.cpp, pack.cpp and frvsr.cpp, host side only, under ASan + UBSan (tests/hostcheck, DESIGN.md "Host check").
 
 The program links HIP stand-ins backed by host memory and launch auditors in place of the kernels - no HIP runtime, no Python, so it
 cannot open a GPU - and runs as a plain child process (nothing is preloaded).  It walks the lattice of model descriptions: every
@@ -24,9 +24,31 @@ every axis keeps both ends):
 
 Every description a GPU test runs (tests/test_gpu_error_budget.py) is a point of this walk.
 
-1184 descriptions accepted, 104 refused, 9472 shapes audited (323 k launches), 13 904 layers through the bijection check.  Measured on 8
-CPUs: 8 shards side by side, 68 s wall and 8.3 CPU-minutes (7.6 G parameters packed at 65 ns each; the slowest shard 68 s, the fastest
-59 s).  The walk has ONE deadline (DEADLINE), not one per shard.
+1184 descriptions accepted, 104 refused, 9472 shapes audited (323 k launches), 13 904 layers through the bijection check.
+
+The frame-recurrent upscaler (frvsr.cpp: ``Frvsr``, ``FrvsrUpscaler``), with every launch recorded (what it read, what it wrote) so that the
+walk can also ask that no launch reads bytes nothing wrote since their buffer was allocated, that no launch writes what it reads, and which
+buffers a round zeroed:
+
+* FRNet descriptions: num_feat 64 x num_block 0, 1, 2, 10, 64 x both dtypes accepted (one step each), 16 refused; the bijection check over
+  every layer at num_block 2 - the two concatenated-input layers, the 2-cout flow layer and the 256 x 256 layers among them.
+* ``step`` / ``step_items``: every (h, w) in 8..40 x 8..40 at n = 1, both dtypes, the three input-packing routes, taps on and off; h, w in
+  {8, 9, 15, 16, 17, 23, 31, 33} at n = 2, 3, 64 (taps on).  The routes launch the same sequence apart from the packing, the activation
+  requests equal ``workspace_bytes``, the raw flow is exactly (n, 2, h // 8 * 8, w // 8 * 8); 12 refused steps per dtype make no launch and
+  no allocation.
+* ``FrvsrUpscaler`` rounds: 10 geometries x max_streams 1, 4, 64 x both dtypes x ``round`` / ``round_at`` on a ragged schedule with resets; a
+  slot's previous frame is the buffer its last round wrote (or one this round zeroed), no slot buffer is written twice, ``state_bytes`` and
+  the untouched slots are as expected; every refused round leaves the slots, the launch and memset counts and the live allocations as they
+  were.
+
+The frame upscaler (upscaler.cpp: ``Upscaler::multi`` / ``single``): the 14 configurations of tests/drive_guarded.py and the cross product of
+single_mode x SR model x denoising x lr_hr_resize x output_shape x taps x frame size x lr_shape, four jobs per configuration; the same launch
+checks, ``st_acc2`` zero-filled whenever ``acc2_clean`` is set, and every job refused or accepted as its sizes say, a refusal before the job's
+first launch and allocation.
+
+14 230 steps, 720 rounds, 724 refused rounds, 2903 upscaler jobs, 989 refused jobs.  Measured on 8 CPUs: 8 shards side by side, 62 s wall (52 s
+before the frame-recurrent and frame upscaler parts; 7.6 G parameters packed at 65 ns each; the slowest shard 62 s, the fastest 55 s).  The walk
+has ONE deadline (DEADLINE), not one per shard.
 """
 import os
 import re
@@ -39,8 +61,9 @@ import sharkshark4k_amd  # noqa: F401
 from sharkshark4k_amd import build as B
 
 SHARDS = 8        # side by side; a command on a GPU machine may use 16 CPUs
-DEADLINE = 600    # seconds for the whole walk (measured: 68 s on 8 CPUs, 8.3 CPU-minutes - a machine with one free core still fits)
+DEADLINE = 600    # seconds for the whole walk (measured: 62 s on 8 CPUs, 7.8 CPU-minutes - a machine with one free core still fits)
 ACCEPTED, REFUSED, SHAPES = 1184, 104, 9472
+FR_ACCEPTED, FR_REFUSED, STEPS, REFUSED_STEPS, ROUNDS, REFUSED_ROUNDS, JOBS, REFUSED_JOBS = 10, 16, 14230, 24, 720, 724, 2903, 989
 
 
 @pytest.fixture(scope="module")
@@ -66,7 +89,8 @@ def test_program_links_no_gpu_runtime(prog):
 
 def test_lattice_walk_is_clean(prog):
     procs = [subprocess.Popen([prog, "--shard", str(i), str(SHARDS)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=_env()) for i in range(SHARDS)]
-    total = dict(accepted=0, refused=0, shapes=0, launches=0, bijection_layers=0, violations=0, findings=0)
+    total = dict(accepted=0, refused=0, shapes=0, launches=0, bijection_layers=0, frvsr_accepted=0, frvsr_refused=0, steps=0, refused_steps=0, rounds=0, refused_rounds=0, jobs=0, refused_jobs=0,
+                 violations=0, findings=0)
     deadline = time.monotonic() + DEADLINE   # one limit for the whole walk, not one per shard
     try:
         for i, p in enumerate(procs):
@@ -86,7 +110,9 @@ def test_lattice_walk_is_clean(prog):
                 p.kill()
     assert (total["accepted"], total["refused"], total["shapes"]) == (ACCEPTED, REFUSED, SHAPES), total
     assert total["violations"] == 0 and total["findings"] == 0, total
-    assert total["launches"] > 300000 and total["bijection_layers"] > 13000, total
+    assert total["launches"] > 800000 and total["bijection_layers"] == 13904 + 38, total
+    got = tuple(total[k] for k in ("frvsr_accepted", "frvsr_refused", "steps", "refused_steps", "rounds", "refused_rounds", "jobs", "refused_jobs"))
+    assert got == (FR_ACCEPTED, FR_REFUSED, STEPS, REFUSED_STEPS, ROUNDS, REFUSED_ROUNDS, JOBS, REFUSED_JOBS), total
 
 
 # One RRDBNet forward (num_feat 64, num_grow_ch 32, x4, NO_DENSE, one frame of 7 x 9): launch 0 packs the input, launch 1 is conv_first,
@@ -130,3 +156,54 @@ def test_routes_of_the_gpu_lattice_cases(prog, desc, shape, kind, count):
     assert lines, r.stdout
     got = sum((" w16" in ln) if kind == "w16" else (f" {kind} " in ln) for ln in lines)
     assert got == count, f"{got} {kind} launches, {count} expected:\n" + "\n".join(lines)
+
+
+# ---- the frame-recurrent upscaler
+FNET = ["conv3x3:0", "conv3x3:1", "maxpool2_planes", "conv3x3:2", "conv3x3:3", "maxpool2_planes", "conv3x3:4", "conv3x3:5", "maxpool2_planes", "conv3x3:6", "conv3x3:7",
+        "bilinear2_planes", "conv3x3:8", "conv3x3:9", "bilinear2_planes", "conv3x3:10", "conv3x3:11", "bilinear2_planes", "conv3x3:12", "conv3x3:13", "flow_finish"]
+SRNET = ["planes_to_nchw", "conv3x3:14", "conv3x3:15", "conv3x3:16"]   # the parity tap, conv_in, one residual block
+
+
+def _launches(text):
+    """[(launch index, kind with the layer of a conv)] per section of a trace: a section starts at a ROUTE or ROUND line"""
+    sections, cur = {}, None
+    for ln in text.splitlines():
+        if ln.startswith(("ROUTE ", "ROUND ")):
+            cur = sections.setdefault(ln.split(" ", 1)[1], [])
+        m = re.match(r"LAUNCH (\d+) (\S+) layer (-?\d+)", ln)
+        if m and cur is not None:
+            cur.append((int(m.group(1)), m.group(2) + (":" + m.group(3) if m.group(3) != "-1" else "")))
+    return sections
+
+
+def test_frvsr_step_launch_sequence_of_the_three_routes(prog):
+    """One fp16 step, num_block 1, two items of 9 x 15, taps on: the routes differ in how the inputs are packed and in the item launchers."""
+    r = _run(prog, "--trace-frvsr", "1", "1", "2", "9", "15")
+    assert r.returncode == 0 and r.stderr == "", r.stdout[-2000:] + r.stderr[-2000:]
+    got = {k: [kind for _, kind in v] for k, v in _launches(r.stdout).items()}
+    assert got == {
+        "contiguous": ["pack_input"] * 2 + FNET + ["warp_s2d_planes"] + SRNET + ["ps4_conv_tail"],
+        "items": ["pack_input"] * 4 + FNET + ["warp_s2d_planes(items)"] + SRNET + ["ps4_conv_tail(items)"],
+        "items, pack_batched": ["pack_lr(items)"] + FNET + ["warp_s2d_planes(items)"] + SRNET + ["ps4_conv_tail(items)"],
+    }, got
+
+
+# Each control of the round walk must be reported at exactly the launches that touch the object named, which the test finds in the trace by
+# kind: round 0 opens slots 2 and 0; the fault is injected after it.
+#   hr-short   the HR frame slot 2 wrote in round 0, registered 4 bytes short: round 1 warps it, round 2 writes it again (tail) and converts it (output glue)
+#   out-short  the output frame of item 1 of round 1, one byte short: that round's output glue
+#   cur        slot 2's `cur` flipped back after round 0 (a hook of the program, not of the product): round 1 packs and warps the wrong previous frames
+@pytest.mark.parametrize("control,touching", [
+    ("hr-short", [("1", "warp_s2d_planes(items)"), ("2", "ps4_conv_tail(items)"), ("2", "frames_out(items)")]),
+    ("out-short", [("1", "frames_out(items)")]),
+    ("cur", [("1", "pack_lr(items)"), ("1", "warp_s2d_planes(items)")]),
+])
+def test_control_of_the_round_walk_is_reported_where_it_touches(prog, control, touching):
+    r = _run(prog, "--control-frvsr", control)
+    assert r.returncode == 0 and r.stderr == "", r.stdout[-2000:] + r.stderr[-2000:]
+    sections = _launches(r.stdout)
+    expected = sorted(i for rnd, kind in touching for i, k in sections[rnd] if k == kind)
+    assert len(expected) == len(touching)
+    seen = sorted(int(m) for m in re.findall(r"^VIOLATION .*\| launch (\d+) ", r.stdout, re.M))
+    assert seen == expected, f"reported at launches {seen}, the object is touched by {expected}\n" + "\n".join(ln for ln in r.stdout.splitlines() if ln.startswith("VIOLATION"))
+    assert re.search(r"^CONTROL frvsr %s violations=%d findings=0$" % (control, len(expected)), r.stdout, re.M), r.stdout[-500:]
