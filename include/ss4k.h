@@ -252,6 +252,23 @@ size_t ss4k_frvsr_param_count(const ss4k_frvsr_desc* desc);
 /* Replaces build_egvsr_model's FRNet(...) + load_state_dict (egvsr_upscaler.py:25-29) */
 int ss4k_frvsr_create(ss4k_ctx* ctx, const ss4k_frvsr_desc* desc, const float* host_weights, size_t n_floats, ss4k_frvsr** out);
 void ss4k_frvsr_destroy(ss4k_frvsr* m);
+/* The generator the same description builds.  SS4K_FRVSR_EGVSR: the above.  SS4K_FRVSR_TECOGAN: TecoGAN's FRNet, which EGVSR's was cut down from
+ * (model/egvsr/models/networks/tecogan_nets.py:101-202; the service's nb is 16): identical up to the last residual block, then
+ * ConvTranspose2d(64, 64, 3, 2, 1, output_padding=1) + ReLU twice, Conv2d(64, 3, 3, 1, 1) at (4 h, 4 w), + BicubicUpsample(4)(lr_curr)
+ * (degradation 'BD').  Its blob is that class's whole state_dict in key order: the same 46 tensors, srnet.conv_out being (3, 64, 3, 3) -
+ * 3 032 261 scalars at 64 / 16.  num_feat must be 64 here too.  route_flags pin the route of the transposed layers:
+ * SS4K_FRVSR_CONVT_EMBEDDED - each embedded in a pad-1 3x3 convolution 64 -> 256 + PixelShuffle(2) on the conv kernels the other layers use -
+ * or SS4K_FRVSR_CONVT_PHASE - the kernel of their own that computes them phase by phase with a quarter of the matrix work
+ * (csrc/conv_up2.hip).  0 = the faster of the two as measured: today the embedded route.  Both pins at once are refused.
+ * A wrong generator or unknown route flags: SS4K_EINVAL, and a count of 0.  ss4k_frvsr_create / ss4k_frvsr_param_count are generator 0.
+ * Every other ss4k_frvsr_* entry point works on either generator.  A TecoGAN step walks its tail in groups of items such that no (4 h, 4 w)
+ * plane reaches 2^32 bytes; ss4k_frvsr_workspace_bytes counts one group's tensors, and no result depends on the grouping. */
+enum { SS4K_FRVSR_EGVSR = 0, SS4K_FRVSR_TECOGAN = 1 };
+enum { SS4K_FRVSR_CONVT_EMBEDDED = 1, SS4K_FRVSR_CONVT_PHASE = 4 };
+size_t ss4k_frvsr_param_count_as(const ss4k_frvsr_desc* desc, int generator);
+int ss4k_frvsr_create_as(ss4k_ctx* ctx, const ss4k_frvsr_desc* desc, int generator, int route_flags, const float* host_weights, size_t n_floats,
+                         ss4k_frvsr** out);
+int ss4k_frvsr_generator(const ss4k_frvsr* m);
 /* Replaces `self.model(lr_curr, self.lr_prev, self.hr_prev)` (egvsr_upscaler.py:204) = FRNet.forward (egvsr.py:180-212): lr_curr, lr_prev
  * (n, 3, h, w), hr_prev (n, 3, 4 h, 4 w) -> hr_out (n, 3, 4 h, 4 w), contiguous fp32 NCHW on the device; the n items are independent streams.
  * Stateless.  h, w >= 8 (the reference's reflect pad fails below that): SS4K_EINVAL otherwise. */
@@ -260,7 +277,8 @@ int ss4k_frvsr_step(ss4k_frvsr* m, const float* lr_curr_dev, const float* lr_pre
 /* Device bytes of workspace the object holds after a step of n x h x w (nothing is allocated or launched) */
 int ss4k_frvsr_workspace_bytes(ss4k_frvsr* m, int n, int h, int w, size_t* bytes);
 /* Per-stage time of the steps since the last enable(1), from events on the caller's stream (tools/frvsr_time.py): stage 0 = FNet convs, 1 = SRNet
- * convs, 2 = pool and x2, 3 = flow finish (tanh, pad), 4 = flow x4 + warp + space-to-depth, 5 = tail, 6 = the rest (input packing, service glue).
+ * convs, 2 = pool and x2, 3 = flow finish (tanh, pad), 4 = flow x4 + warp + space-to-depth, 5 = tail, 6 = the rest (input packing, service glue);
+ * a TecoGAN generator's tail: 7 = the two transposed convolutions, 8 = conv_out, 9 = the bicubic skip (5 stays 0).
  * ss4k_frvsr_prof_read synchronises with the recorded events. */
 int ss4k_frvsr_prof_enable(ss4k_frvsr* m, int enable);
 int ss4k_frvsr_prof_read(ss4k_frvsr* m, int stage, double* total_ms);

@@ -110,6 +110,20 @@ int ss4k_dev_op_frvsr_frames_out_items(ss4k_ctx* ctx, const float* const* hr, ui
 int ss4k_dev_frvsr_step_taps(ss4k_frvsr* m, const float* lr_curr, const float* lr_prev, const float* hr_prev, float* hr_out, float* flow_out,
                              float* s2d_out, int n, int h, int w, void* hip_stream);
 
+/* The tail of a TecoGAN generator (ss4k_frvsr_create_as, SS4K_FRVSR_TECOGAN) alone: body_nchw (n, 64, h, w) fp32 stands for the last residual
+ * block's output and is packed into the model's dtype; lr_curr (n, 3, h, w).  Next to hr_out (n, 3, 4 h, 4 w) it returns both transposed
+ * layers' outputs after ReLU as fp32 NCHW: up1_out (n, 64, 2 h, 2 w), up2_out (n, 64, 4 h, 4 w) (an fp16 model: exactly its fp16 values).
+ * group_items: items per group of the tail's walk (0 = the default: as many as keep every HR plane below 2^32 bytes).  max_workgroups: a cap on
+ * the grid of the phase kernel (0 = none); the embedded route has no grid of its own and ignores it.  SS4K_EINVAL on an EGVSR object. */
+int ss4k_dev_frvsr_tail_taps(ss4k_frvsr* m, const float* body_nchw, const float* lr_curr, float* up1_out, float* up2_out, float* hr_out, int n, int h,
+                             int w, int max_workgroups, int group_items, void* hip_stream);
+/* Host only: one transposed layer's state_dict entries (Wt (nf, nf, 3, 3), then nf biases) as the pad-1 3x3 convolution + PixelShuffle(2) the
+ * library runs: W_eq (4 nf, nf, 3, 3) OIHW, then 4 nf biases (csrc/frvsr_teco.cpp states the map) */
+int ss4k_dev_frvsr_embed_convt(const float* wt_and_bias, int nf, float* out, size_t capacity_floats);
+/* Host only: Wt (64, 64, 3, 3) in the fragment order of the phase kernel (csrc/conv_up2.hip states the map), in `dtype`: 36 864 values of
+ * fp16 (73 728 bytes) or fp32 (147 456 bytes) */
+int ss4k_dev_frvsr_pack_convt(const float* wt, int dtype, void* out, size_t capacity_bytes);
+
 /* Route report: every glue launcher counts the kernel route it chose under a static name ("glue::area_whole<NORM,8,half>", ...).
  * _read returns the index-th route in name order (SS4K_EINVAL past the last), _reset clears the table.  Process-wide. */
 int ss4k_dev_glue_routes_reset(void);

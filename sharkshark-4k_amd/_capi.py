@@ -35,6 +35,7 @@ SYMBOLS = [
     "ss4k_frvsr_upscaler_read_tap", "ss4k_op_backward_warp", "ss4k_op_bicubic_upsample4",
     "ss4k_frvsr_upscaler_create_streams", "ss4k_frvsr_upscale_streams", "ss4k_frvsr_upscaler_reset_stream", "ss4k_frvsr_upscaler_state_bytes",
     "ss4k_frvsr_upscale_streams_at",
+    "ss4k_frvsr_param_count_as", "ss4k_frvsr_create_as", "ss4k_frvsr_generator",
 ]
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
@@ -53,6 +54,8 @@ DEV_SYMBOLS = [
     "ss4k_dev_op_frvsr_frames_in_items", "ss4k_dev_op_frvsr_pack_lr_items", "ss4k_dev_op_frvsr_frames_out_items",
     # a whole step with every item's flow and warped space-to-depth tensor copied out (tests/test_gpu_frvsr_budget.py)
     "ss4k_dev_frvsr_step_taps",
+    # the tail of a TecoGAN generator alone, and the host-side embedding of its transposed layers (tests/test_gpu_tecogan_tail.py)
+    "ss4k_dev_frvsr_tail_taps", "ss4k_dev_frvsr_embed_convt", "ss4k_dev_frvsr_pack_convt",
     # guard mode: red zones and 0xFF poison for every device buffer of the library (tests/test_gpu_memory_hygiene.py)
     "ss4k_dev_guard_enable", "ss4k_dev_guard_check", "ss4k_dev_guard_poison", "ss4k_dev_guard_selftest", "ss4k_dev_guard_poison_frvsr",
 ]
@@ -217,6 +220,14 @@ def load(path: str) -> C.CDLL:
         L.ss4k_frvsr_upscaler_state_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     if hasattr(L, "ss4k_frvsr_upscale_streams_at"):   # (absent from builds before the scattered rounds)
         L.ss4k_frvsr_upscale_streams_at.argtypes = [vp, C.POINTER(C.c_int32), i, C.POINTER(vp), i, i, C.POINTER(vp), sz, vp]
+    if hasattr(L, "ss4k_frvsr_create_as"):   # (absent from builds before the second generator)
+        L.ss4k_frvsr_param_count_as.argtypes = [C.POINTER(FrvsrDesc), i]; L.ss4k_frvsr_param_count_as.restype = sz
+        L.ss4k_frvsr_create_as.argtypes = [vp, C.POINTER(FrvsrDesc), i, i, vp, sz, C.POINTER(vp)]
+        L.ss4k_frvsr_generator.argtypes = [vp]
+    if hasattr(L, "ss4k_dev_frvsr_tail_taps"):
+        L.ss4k_dev_frvsr_tail_taps.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
+        L.ss4k_dev_frvsr_embed_convt.argtypes = [vp, i, vp, sz]
+        L.ss4k_dev_frvsr_pack_convt.argtypes = [vp, i, vp, sz]
     return L
 
 
@@ -603,6 +614,9 @@ class Upscaler:
 
 FRVSR_MAX_STREAMS = 64   # SS4K_FRVSR_MAX_STREAMS (include/ss4k.h)
 FRV_STAGES = ("fnet_conv", "srnet_conv", "pool_up", "flow_finish", "warp", "tail", "glue")
+FRV_STAGES_TECOGAN = FRV_STAGES + ("convt", "conv_out", "skip")   # stages 7..9: a TecoGAN generator's tail ("tail" stays 0 there)
+FRVSR_EGVSR, FRVSR_TECOGAN = 0, 1   # SS4K_FRVSR_EGVSR / SS4K_FRVSR_TECOGAN
+FRVSR_CONVT_EMBEDDED, FRVSR_CONVT_PHASE = 1, 4   # route_flags: SS4K_FRVSR_CONVT_* (0: the library's choice, today the embedded route)
 
 
 def make_frvsr_desc(dtype: int = F32, num_feat: int = 64, num_block: int = 10, flags: int = 0) -> FrvsrDesc:
@@ -611,20 +625,26 @@ def make_frvsr_desc(dtype: int = F32, num_feat: int = 64, num_block: int = 10, f
     return d
 
 
-def frvsr_param_count(desc: FrvsrDesc) -> int:
-    return int(lib().ss4k_frvsr_param_count(C.byref(desc)))
+def frvsr_param_count(desc: FrvsrDesc, generator: int = FRVSR_EGVSR) -> int:
+    if generator == FRVSR_EGVSR:
+        return int(lib().ss4k_frvsr_param_count(C.byref(desc)))
+    return int(lib().ss4k_frvsr_param_count_as(C.byref(desc), int(generator)))
 
 
 class Frvsr:
-    """ss4k_frvsr: EGVSR's FRNet x4 resident on one GPU; callable like the reference's ``self.model(lr_curr, lr_prev, hr_prev)``
-    (egvsr_upscaler.py:204)."""
+    """ss4k_frvsr: EGVSR's FRNet x4 (``generator=0``) or TecoGAN's (``generator=1``, tecogan_nets.py:101-202) resident on one GPU; callable like
+    the reference's ``self.model(lr_curr, lr_prev, hr_prev)`` (egvsr_upscaler.py:204)."""
 
-    def __init__(self, ctx: Context, desc: FrvsrDesc, flat_weights: np.ndarray):
-        self.ctx, self.desc = ctx, desc
+    def __init__(self, ctx: Context, desc: FrvsrDesc, flat_weights: np.ndarray, generator: int = FRVSR_EGVSR, route_flags: int = 0):
+        self.ctx, self.desc, self.generator = ctx, desc, int(generator)
         w = np.ascontiguousarray(flat_weights, dtype=np.float32)
         h = C.c_void_p()
         with torch.cuda.device(ctx.device):
-            _check(lib().ss4k_frvsr_create(ctx._h, C.byref(desc), w.ctypes.data_as(C.c_void_p), w.size, C.byref(h)))
+            if self.generator == FRVSR_EGVSR and not route_flags:
+                _check(lib().ss4k_frvsr_create(ctx._h, C.byref(desc), w.ctypes.data_as(C.c_void_p), w.size, C.byref(h)))
+            else:
+                _check(lib().ss4k_frvsr_create_as(ctx._h, C.byref(desc), self.generator, int(route_flags), w.ctypes.data_as(C.c_void_p), w.size,
+                                                  C.byref(h)))
         self._h = h
 
     def close(self):
@@ -649,7 +669,7 @@ class Frvsr:
     def prof_read(self) -> dict:
         """{stage: total ms since prof_enable(True)}; waits for the recorded events."""
         out = {}
-        for k, name in enumerate(FRV_STAGES):
+        for k, name in enumerate(FRV_STAGES_TECOGAN if self.generator == FRVSR_TECOGAN else FRV_STAGES):
             ms = C.c_double()
             _check(lib().ss4k_frvsr_prof_read(self._h, k, C.byref(ms)))
             out[name] = ms.value

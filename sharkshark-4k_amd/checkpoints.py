@@ -86,3 +86,10 @@ def egvsr_from_checkpoint(ckpt: Mapping, nb: int = 10):
     reads (``srnet.conv_up.*``, the two ``upsample_func.kernels`` buffers) stay in the table: the blob is the whole state_dict."""
     sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
     return _ordered(sd, W.frnet_keys(nb), "FRNet")
+
+
+def tecogan_from_checkpoint(ckpt: Mapping, nb: int = W.TECOGAN_NB):
+    """A TecoGAN generator checkpoint is ``FRNet``'s bare state_dict too (tecogan_nets.py:101-202, ``define_generator``'s ``name: frnet``); the
+    blob is the whole state_dict in key order."""
+    sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
+    return _ordered(sd, W.tecogan_keys(nb), "TecoGAN FRNet")

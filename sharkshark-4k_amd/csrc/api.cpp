@@ -241,12 +241,21 @@ int ss4k_op_f32nchw_to_u8nhwc(ss4k_ctx* c, const float* in, uint8_t* out, int n,
 
 // ---- the frame-recurrent upscaler (frvsr.cpp) ----------------------------------------------------
 size_t ss4k_frvsr_param_count(const ss4k_frvsr_desc* d) { return d ? frvsr_param_count(*d) : 0; }
+size_t ss4k_frvsr_param_count_as(const ss4k_frvsr_desc* d, int generator) { return d ? frvsr_param_count(*d, generator) : 0; }
 int ss4k_frvsr_create(ss4k_ctx* ctx, const ss4k_frvsr_desc* d, const float* w, size_t n, ss4k_frvsr** out) {
+  return ss4k_frvsr_create_as(ctx, d, SS4K_FRVSR_EGVSR, 0, w, n, out);
+}
+int ss4k_frvsr_generator(const ss4k_frvsr* m) { return m ? m->f.generator : -1; }
+int ss4k_frvsr_create_as(ss4k_ctx* ctx, const ss4k_frvsr_desc* d, int generator, int route_flags, const float* w, size_t n, ss4k_frvsr** out) {
   return guard([&] {
     SS4K_REQUIRE(ctx && d && w && out, "ss4k_frvsr_create: NULL argument");
+    SS4K_REQUIRE(generator == SS4K_FRVSR_EGVSR || generator == SS4K_FRVSR_TECOGAN, "ss4k_frvsr_create_as: generator must be SS4K_FRVSR_EGVSR or SS4K_FRVSR_TECOGAN");
+    SS4K_REQUIRE((route_flags & ~(SS4K_FRVSR_CONVT_EMBEDDED | SS4K_FRVSR_CONVT_PHASE)) == 0, "ss4k_frvsr_create_as: unknown route flags");
+    SS4K_REQUIRE(generator == SS4K_FRVSR_TECOGAN || route_flags == 0, "ss4k_frvsr_create_as: the route flags belong to the TecoGAN generator");
     SS4K_HIP(hipSetDevice(ctx->device));
     auto m = std::make_unique<ss4k_frvsr>();
-    m->f.ctx = ctx; m->f.desc = *d;
+    m->f.ctx = ctx; m->f.desc = *d; m->f.generator = generator;
+    if (generator == SS4K_FRVSR_TECOGAN) m->f.tail = make_tecogan_tail(route_flags);
     m->f.build(w, n);
 #ifdef SS4K_DEV
     for (DevBuf* b : {&m->f.flow_raw, &m->f.flow, &m->f.tap_s2d}) b->transient = true;   // guard mode: every step rewrites what it reads from these

@@ -235,6 +235,33 @@ int ss4k_dev_frvsr_step_taps(ss4k_frvsr* m, const float* lr_curr, const float* l
     SS4K_HIP(hipMemcpyAsync(s2d_out, f.tap_s2d.ptr, px * 48 * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   });
 }
+// TecoGAN's tail alone (frvsr_teco.cpp) on a chosen body tensor, both transposed layers' outputs copied out (tests/test_gpu_tecogan_tail.py)
+int ss4k_dev_frvsr_tail_taps(ss4k_frvsr* m, const float* body_nchw, const float* lr_curr, float* up1_out, float* up2_out, float* hr_out, int n, int h,
+                             int w, int max_workgroups, int group_items, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(m && body_nchw && lr_curr && up1_out && up2_out && hr_out, "ss4k_dev_frvsr_tail_taps: NULL argument");
+    TecoTailDev o; o.max_workgroups = max_workgroups; o.group_items = group_items;
+    tecogan_tail_taps(m->f, body_nchw, lr_curr, up1_out, up2_out, hr_out, n, h, w, o, (hipStream_t)stream);
+  });
+}
+// host only: W_eq + biases of embed_convt for one transposed layer (nf * nf * 9 + nf floats in, 4 nf * nf * 9 + 4 nf out)
+int ss4k_dev_frvsr_embed_convt(const float* wt_and_bias, int nf, float* out, size_t capacity_floats) {
+  return guard([&] {
+    SS4K_REQUIRE(wt_and_bias && out && nf > 0 && nf <= SS4K_DESC_MAX_WIDTH, "ss4k_dev_frvsr_embed_convt: bad argument");
+    const std::vector<float> eq = embed_convt(wt_and_bias, nf);
+    SS4K_REQUIRE(capacity_floats >= eq.size(), "ss4k_dev_frvsr_embed_convt: output too small");
+    std::copy(eq.begin(), eq.end(), out);
+  });
+}
+// host only: pack_convt3x3s2's blob for one transposed layer's Wt (64, 64, 3, 3) in dtype SS4K_F32 | SS4K_F16 (73 728 | 147 456 bytes)
+int ss4k_dev_frvsr_pack_convt(const float* wt, int dtype, void* out, size_t capacity_bytes) {
+  return guard([&] {
+    SS4K_REQUIRE(wt && out && (dtype == SS4K_F32 || dtype == SS4K_F16), "ss4k_dev_frvsr_pack_convt: bad argument");
+    const std::vector<uint8_t> pk = pack_convt3x3s2(wt, dtype);
+    SS4K_REQUIRE(capacity_bytes >= pk.size(), "ss4k_dev_frvsr_pack_convt: output too small");
+    std::copy(pk.begin(), pk.end(), static_cast<uint8_t*>(out));
+  });
+}
 int ss4k_dev_glue_routes_reset(void) { return guard([&] { glue_routes_reset(); }); }
 int ss4k_dev_glue_routes_read(int index, char* name, size_t name_capacity, int64_t* launches) {
   return guard([&] {

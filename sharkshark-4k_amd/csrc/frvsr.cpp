@@ -19,22 +19,25 @@ static void validate_frvsr_desc(const ss4k_frvsr_desc& d) {
   for (int r : d.reserved) SS4K_REQUIRE(r == 0, "frvsr desc.reserved must be 0");
 }
 
-size_t frvsr_param_count(const ss4k_frvsr_desc& d) {
+size_t frvsr_param_count(const ss4k_frvsr_desc& d, int generator) {
   try { validate_frvsr_desc(d); } catch (const Error&) { return 0; }
+  if (generator != SS4K_FRVSR_EGVSR && generator != SS4K_FRVSR_TECOGAN) return 0;
   const size_t nf = (size_t)d.num_feat;
   size_t n = 16;                                                    // upsample_func.kernels
   for (auto& c : FNET_CONVS) n += (size_t)c[0] * c[1] * 9 + c[0];
   n += nf * 51 * 9 + nf;                                            // srnet.conv_in.0
   n += (size_t)d.num_block * 2 * (nf * nf * 9 + nf);                // srnet.resblocks.*.conv.{0,2}
-  n += 2 * (nf * nf * 9 + nf);                                      // srnet.conv_up.{0,2}: in the state_dict, unused by forward
-  n += 3 * 4 * 9 + 3;                                               // srnet.conv_out
+  n += 2 * (nf * nf * 9 + nf);                                      // srnet.conv_up.{0,2}: in the state_dict; EGVSR's forward does not use them
+  n += generator == SS4K_FRVSR_TECOGAN ? 3 * nf * 9 + 3 : 3 * 4 * 9 + 3;   // srnet.conv_out: Conv2d(nf, 3) at (4 h, 4 w) (tecogan_nets.py:128) | Conv2d(4, 3)
   n += 16;                                                          // srnet.upsample_func.kernels
   return n;
 }
 
 void Frvsr::build(const float* w, size_t n) {
   validate_frvsr_desc(desc);
-  SS4K_REQUIRE(n == frvsr_param_count(desc), "weight blob size does not match the frvsr description");
+  SS4K_REQUIRE(generator == SS4K_FRVSR_EGVSR || generator == SS4K_FRVSR_TECOGAN, "frvsr: generator must be SS4K_FRVSR_EGVSR or SS4K_FRVSR_TECOGAN");
+  SS4K_REQUIRE((generator == SS4K_FRVSR_EGVSR) == (tail == nullptr), "internal: a generator other than EGVSR brings its tail (ss4k_frvsr_create_as)");
+  SS4K_REQUIRE(n == frvsr_param_count(desc, generator), "weight blob size does not match the frvsr description");
   net.ctx = ctx;
   net.desc = ss4k_model_desc{}; net.desc.kind = SS4K_SRVGG; net.desc.dtype = desc.dtype; net.desc.scale = 4; net.desc.num_feat = desc.num_feat;
   const int nf = desc.num_feat;
@@ -46,13 +49,19 @@ void Frvsr::build(const float* w, size_t n) {
   srnet0 = (int)net.layers.size();
   net.add_conv(pc, nf, 51, net.spec_concat(3, 48), false);   // torch.cat([lr_curr, hr_prev_tran], 1) (egvsr.py:137)
   for (int i = 0; i < 2 * desc.num_block; ++i) net.add_conv(pc, nf, nf, net.spec_plain(nf), false);
-  (void)pc.take(2 * ((size_t)nf * nf * 9 + nf));
-  const float* tw = pc.take(108);
-  std::vector<float> wb(tw, tw + 108);
-  const float* b = pc.take(3);
-  wb.insert(wb.end(), b, b + 3);
-  tail_wb.ensure(wb.size() * 4);
-  SS4K_HIP(hipMemcpy(tail_wb.ptr, wb.data(), wb.size() * 4, hipMemcpyHostToDevice));
+  if (tail) {
+    const float* up0 = pc.take((size_t)nf * nf * 9 + nf);
+    const float* up2 = pc.take((size_t)nf * nf * 9 + nf);
+    tail->build(*this, up0, up2, pc.take((size_t)3 * nf * 9 + 3));
+  } else {
+    (void)pc.take(2 * ((size_t)nf * nf * 9 + nf));
+    const float* tw = pc.take(108);
+    std::vector<float> wb(tw, tw + 108);
+    const float* b = pc.take(3);
+    wb.insert(wb.end(), b, b + 3);
+    tail_wb.ensure(wb.size() * 4);
+    SS4K_HIP(hipMemcpy(tail_wb.ptr, wb.data(), wb.size() * 4, hipMemcpyHostToDevice));
+  }
   (void)pc.take(16);
   SS4K_REQUIRE(pc.pos == n, "internal: weight cursor did not consume the blob");
 }
@@ -99,16 +108,7 @@ void Frvsr::run(const float* lr_curr, const float* lr_prev, const float* hr_prev
   const bool plan = net.plan_only, f16 = desc.dtype == SS4K_F16;
   const int h1 = h / 2, w1 = w / 2, h2 = h1 / 2, w2 = w1 / 2, h3 = h2 / 2, w3 = w2 / 2, h8 = 8 * h3, w8 = 8 * w3;
   const size_t px = (size_t)n * h * w, px1 = (size_t)n * h1 * w1, px2 = (size_t)n * h2 * w2, px3 = (size_t)n * h3 * w3;
-  auto stage = [&](int s, auto&& body) {
-    if (!prof || plan) { body(); return; }
-    Span sp{nullptr, nullptr, s};
-    SS4K_HIP(hipEventCreate(&sp.a));
-    if (hipEventCreate(&sp.b) != hipSuccess) { (void)hipEventDestroy(sp.a); throw Error(SS4K_EHIP, "hipEventCreate failed"); }
-    spans.push_back(sp);
-    SS4K_HIP(hipEventRecord(sp.a, st));
-    body();
-    SS4K_HIP(hipEventRecord(sp.b, st));
-  };
+  auto stage = [&](int s, auto&& body) { timed(s, st, body); };
   auto lrelu = [](const Tens& out, float slope) { ConvOpts o; o.act = ACT_LRELU; o.slope = slope; o.out = out; return o; };
   auto pool = [&](const Tens& in, const Tens& out, int channels, int H, int W) {
     if (plan) return;
@@ -213,6 +213,10 @@ void Frvsr::run(const float* lr_curr, const float* lr_prev, const float* hr_prev
     }
     net.lanes_join(st, true);   // (closes the context's conv profiling section if one is open; a step never forks)
   });
+  if (tail) {   // another generator's tail, with stages of its own
+    tail->run(*this, FrvsrTail::Call{cur, slot, lr_curr, hr_out, items ? items->lr_curr : nullptr, items ? items->hr_out : nullptr, n, h, w}, st);
+    return;
+  }
   // PixelShuffle(4), ReLU, conv_out (egvsr.py:139-140)
   stage(FRV_TAIL, [&] {
     if (plan) return;

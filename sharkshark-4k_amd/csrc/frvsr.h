@@ -2,6 +2,7 @@
 // the service path behind ss4k_frvsr_upscaler (include/ss4k.h), and the launchers of the glue kernels they need (frvsr.hip).
 #pragma once
 #include "models.h"
+#include <memory>
 
 namespace ss4k {
 
@@ -34,6 +35,11 @@ template <typename T> void op_warp_s2d_planes_items(const float* lr_flow, const 
 template <typename T> void op_ps4_conv_tail(const T* in, const float* wb, float* out, int n, int h, int w, hipStream_t st);
 // ... item i written to out.p[i] (3, 4 h, 4 w): bit-identical; n <= 64
 template <typename T> void op_ps4_conv_tail_items(const T* in, const float* wb, const FrvsrPtrs& out, int n, int h, int w, hipStream_t st);
+// conv + BicubicUpsample(4)(lr) (TecoGAN's SRNet, degradation 'BD': tecogan_nets.py:146-148): conv (n, 3, 4 h, 4 w) and lr (n, 3, h, w) fp32 ->
+// out (n, 3, 4 h, 4 w) fp32; the skip goes through op_bicubic_upsample4's device functions, so it is that op bit for bit
+void op_bicubic4_add(const float* conv, const float* lr, float* out, int n, int h, int w, hipStream_t st);
+// ... item i reading lr.p[i] (3, h, w) and writing out.p[i] (3, 4 h, 4 w); conv stays one contiguous batch: bit-identical; n <= 64
+void op_bicubic4_add_items(const float* conv, const FrvsrPtrs& lr, const FrvsrPtrs& out, int n, int h, int w, hipStream_t st);
 // planes of T -> fp32 NCHW (n, channels, h, w) (the parity taps)
 template <typename T> void op_planes_to_nchw(const T* in, float* out, int n, int channels, int h, int w, hipStream_t st);
 // clamp(x, 0, 1) into another tensor (egvsr_upscaler.py:209: the recurrent state keeps the unclamped one)
@@ -49,14 +55,57 @@ template <typename T> void op_pack_lr_items(const FrvsrPtrs& lr_curr, const Frvs
 // uint8 HWC (oh, ow, 3) at out.p[i] (op_clamp01_to + op_area + op_f32nchw_to_u8nhwc, or the last alone); no fp32 intermediate in memory
 void op_frames_out_items(const FrvsrPtrs& hr, const FrvsrFramesOut& out, int n, int H, int W, int oh, int ow, hipStream_t st);
 
-size_t frvsr_param_count(const ss4k_frvsr_desc& d);   // 0 for a description that is refused
+// 0 for a description or a generator that is refused.  generator: SS4K_FRVSR_EGVSR | SS4K_FRVSR_TECOGAN (include/ss4k.h)
+size_t frvsr_param_count(const ss4k_frvsr_desc& d, int generator = SS4K_FRVSR_EGVSR);
 
 // stages of a step, for the per-stage event timing (ss4k_frvsr_prof_read)
-enum { FRV_FNET_CONV = 0, FRV_SRNET_CONV = 1, FRV_POOL_UP = 2, FRV_FLOW = 3, FRV_WARP = 4, FRV_TAIL = 5, FRV_GLUE = 6, FRV_STAGES = 7 };
+// (7..9 are TecoGAN's tail: its two transposed convolutions, conv_out, the bicubic skip; FRV_TAIL is EGVSR's tail alone)
+enum { FRV_FNET_CONV = 0, FRV_SRNET_CONV = 1, FRV_POOL_UP = 2, FRV_FLOW = 3, FRV_WARP = 4, FRV_TAIL = 5, FRV_GLUE = 6, FRV_CONVT = 7, FRV_CONV_OUT = 8,
+       FRV_SKIP = 9, FRV_STAGES = 10 };
+
+struct Frvsr;
+// What follows SRNet's last residual block when it is not EGVSR's tail (which Frvsr::run holds itself).  A tail lives in a file of its own
+// together with the launchers it calls (frvsr_teco.cpp), and ss4k_frvsr_create_as installs it: frvsr.cpp names no launcher but its own.
+struct FrvsrTail {
+  virtual ~FrvsrTail() = default;
+  // srnet.conv_up.{0,2} as the state_dict holds them ((C_in, C_out, 3, 3) + bias each) and srnet.conv_out (OIHW + bias): adds its layers to f.net
+  virtual void build(Frvsr& f, const float* up0, const float* up2, const float* out_w) = 0;
+  // body: the last residual block's output, nf channels at (n, h, w).  lr_curr / hr_out: the contiguous batches, or (items != null) the
+  // per-item tables.  slot: the first free activation slot of f.net.  Plans (f.net.plan_only) like every other part of a step
+  struct Call { Tens body; int slot; const float* lr_curr; float* hr_out; const float* const* items_lr; const FrvsrPtrs* items_out; int n, h, w; };
+  virtual void run(Frvsr& f, const Call& c, hipStream_t st) = 0;
+};
+
+// ---- conv_up2.hip: ConvTranspose2d(64, 64, 3, 2, 1, output_padding=1) + bias + ReLU on planes, (N, H, W) -> (N, 2 H, 2 W), by output phase
+constexpr int CONVT_TH = 8, CONVT_TW = 32;   // input pixels per workgroup tile
+struct ConvtArgs {
+  const char* in; size_t in_plane_bytes;     // four planes (64 channels) at (N, H, W)
+  char* out; size_t out_plane_bytes;         // four planes at (N, 2 H, 2 W)
+  const char* w;                             // pack_convt3x3s2's blob
+  const float* bias;                         // 64
+  int N, H, W, tiles_x, tiles_y;             // (the launcher fills the tile counts)
+};
+// Wt (64, 64, 3, 3) (C_in, C_out, kH, kW) -> the kernel's fragment order in the model's dtype (the head of conv_up2.hip states the map); host only
+std::vector<uint8_t> pack_convt3x3s2(const float* wt, int dtype);
+// max_workgroups > 0 caps the persistent grid (dev: a walk of more tiles than workgroups at small shapes)
+void launch_convt3x3s2(ss4k_ctx* ctx, const ConvtArgs& a, int dtype, int max_workgroups, hipStream_t st);
+
+// TecoGAN's tail (frvsr_teco.cpp).  route_flags: SS4K_FRVSR_CONVT_* (include/ss4k.h); unknown bits are refused
+std::unique_ptr<FrvsrTail> make_tecogan_tail(int route_flags);
+// W_eq (4 nf, nf, 3, 3) OIHW + 4 nf biases: the transposed layer (Wt (nf, nf, 3, 3) + nf biases) as a pad-1 3x3 convolution + PixelShuffle(2)
+std::vector<float> embed_convt(const float* wt_and_bias, int nf);
+// dev library: the tail alone on a chosen body tensor (n, nf, h, w) fp32 NCHW, with both transposed layers' outputs copied out as fp32 NCHW
+// (up1 (n, nf, 2 h, 2 w), up2 (n, nf, 4 h, 4 w)).  group_items: items per group of the tail's walk (0 = default); max_workgroups: a cap
+// on the phase kernel's grid (launch_convt3x3s2; the embedded route has no grid of its own: accepted and unused)
+struct TecoTailDev { float* up1 = nullptr; float* up2 = nullptr; int group_items = 0, max_workgroups = 0; };
+void tecogan_tail_taps(Frvsr& f, const float* body_nchw, const float* lr_curr, float* up1, float* up2, float* hr_out, int n, int h, int w,
+                       const TecoTailDev& opts, hipStream_t st);
 
 struct Frvsr {
   ss4k_ctx* ctx = nullptr;
   ss4k_frvsr_desc desc{};
+  int generator = SS4K_FRVSR_EGVSR;
+  std::unique_ptr<FrvsrTail> tail;   // null: EGVSR's built-in tail
   Model net;                 // container of the conv layers and the activation workspaces (Model::conv / Model::act)
   DevBuf tail_wb;            // srnet.conv_out: 108 weights + 3 biases, fp32
   DevBuf flow_raw, flow;     // fp32 in both dtypes
@@ -69,6 +118,17 @@ struct Frvsr {
   std::vector<Span> spans;
   double stage_ms[FRV_STAGES] = {};
   void prof_collect();
+  // body() as one span of stage `s` on `st` (nothing is recorded while the timing is off or the step only plans)
+  template <typename F> void timed(int s, hipStream_t st, F&& body) {
+    if (!prof || net.plan_only) { body(); return; }
+    Span sp{nullptr, nullptr, s};
+    SS4K_HIP(hipEventCreate(&sp.a));
+    if (hipEventCreate(&sp.b) != hipSuccess) { (void)hipEventDestroy(sp.a); throw Error(SS4K_EHIP, "hipEventCreate failed"); }
+    spans.push_back(sp);
+    SS4K_HIP(hipEventRecord(sp.a, st));
+    body();
+    SS4K_HIP(hipEventRecord(sp.b, st));
+  }
   ~Frvsr();
 
   void build(const float* w, size_t n);

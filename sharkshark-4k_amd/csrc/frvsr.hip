@@ -364,6 +364,47 @@ void op_ps4_conv_tail_items(const T* in, const float* wb, const FrvsrPtrs& out, 
 template void op_ps4_conv_tail_items<float>(const float*, const float*, const FrvsrPtrs&, int, int, int, hipStream_t);
 template void op_ps4_conv_tail_items<__half>(const __half*, const float*, const FrvsrPtrs&, int, int, int, hipStream_t);
 
+// ------------------------------------------------------------------ conv_out + BicubicUpsample(4)(lr_curr) -> fp32 NCHW (TecoGAN's tail)
+// One thread per HR value.  The skip is bic4_load / bic4_at, as k_bicubic_upsample4 calls them: that op's value bit for bit, then ONE rounded add
+__device__ __forceinline__ float bic4_add_value(const Bic4& t, const float* __restrict__ lr_plane, float conv, int X, int Y, int h, int w) {
+  float f[4][4];
+  bic4_load(lr_plane, Y >> 2, X >> 2, h, w, f);
+  return __fadd_rn(conv, bic4_at(t, f, Y & 3, X & 3));
+}
+__global__ __launch_bounds__(256) void k_bicubic4_add(const float* __restrict__ conv, const float* __restrict__ lr, float* __restrict__ out, int planes, int h,
+                                                      int w, Bic4 taps) {
+  const int OW = 4 * w, OH = 4 * h;
+  const size_t total = (size_t)planes * OH * OW;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int X = (int)(i % OW), Y = (int)((i / OW) % OH);
+    const size_t pl = i / ((size_t)OW * OH);
+    out[i] = bic4_add_value(taps, lr + pl * h * w, conv[i], X, Y, h, w);
+  }
+}
+// ... item (pl / 3) reading lr.p[item] and writing out.p[item] (FrvsrPtrs by value, as k_ps4_conv_tail_items); conv stays one batch
+__global__ __launch_bounds__(256) void k_bicubic4_add_items(const float* __restrict__ conv, FrvsrPtrs lr, FrvsrPtrs out, int planes, int h, int w, Bic4 taps) {
+  const int OW = 4 * w, OH = 4 * h;
+  const size_t HW = (size_t)OW * OH, total = (size_t)planes * HW;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int X = (int)(i % OW), Y = (int)((i / OW) % OH);
+    const size_t pl = i / HW, item = pl / 3, c = pl - item * 3;
+    out.p[item][c * HW + (i - pl * HW)] = bic4_add_value(taps, lr.p[item] + c * h * w, conv[i], X, Y, h, w);
+  }
+}
+void op_bicubic4_add(const float* conv, const float* lr, float* out, int n, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "bicubic4_add: sizes");
+  SS4K_GLUE_ROUTE("frvsr_teco::bicubic4_add");   // (the tail of the second generator: bounded by tests/test_gpu_tecogan*.py)
+  hipLaunchKernelGGL(k_bicubic4_add, grid_for((size_t)n * 3 * 16 * h * w), dim3(256), 0, st, conv, lr, out, 3 * n, h, w, bic4_taps());
+  SS4K_LAUNCH_OK();
+}
+void op_bicubic4_add_items(const float* conv, const FrvsrPtrs& lr, const FrvsrPtrs& out, int n, int h, int w, hipStream_t st) {
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "bicubic4_add (items): sizes");
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(lr.p[i] && out.p[i], "bicubic4_add (items): NULL item");
+  SS4K_GLUE_ROUTE("frvsr_teco::bicubic4_add_items");
+  hipLaunchKernelGGL(k_bicubic4_add_items, grid_for((size_t)n * 3 * 16 * h * w), dim3(256), 0, st, conv, lr, out, 3 * n, h, w, bic4_taps());
+  SS4K_LAUNCH_OK();
+}
+
 // ------------------------------------------------------------------ planes -> fp32 NCHW (parity taps), clamp into another tensor
 template <typename T>
 __global__ void k_planes_to_nchw(const T* __restrict__ in, float* __restrict__ out, int n, int channels, int h, int w) {

@@ -21,6 +21,8 @@ own, runs the job, copies the result into the named slot of the output ring on a
 ``HostFrames(result=True)``; one more job is enqueued before that result is waited for, so the copies run under the neighbour's kernels.  A
 ``StreamQueueEntry`` with ``frames=None`` and ``end_streams`` only frees those slots: no GPU work, answered with ``frames=None``.
 
+``generator='tecogan'`` runs TecoGAN's FRNet instead (``nb`` then defaults to 16; its checkpoint is that class's bare state_dict).
+
 Weights as for the other services: ``weights=None`` looks ``EGVSR_iter420000.pth`` (``egvsr_upscaler.py:25``) up in
 ``checkpoint_dir`` / ``$SS4K_CHECKPOINT_DIR`` and raises ``FileNotFoundError`` when it is missing; a path, the dict ``torch.load`` returns
 (a bare state_dict) or a state-dict table are taken as they are; ``'synthetic'`` is the tests' explicit opt-in.  The worker process,
@@ -99,8 +101,8 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
     #: staging tensors per input shape: one more than the jobs that can be in flight (the job running, the one held back, the next one's copy)
     HOST_STAGE_DEPTH = 3
 
-    def __init__(self, lr_level=1, device=0, on_queue=None, *, weights=None, checkpoint_dir: Optional[str] = None, dtype="f16", nb=10,
-                 lr_shape=None, seed=0, max_streams=1):
+    def __init__(self, lr_level=1, device=0, on_queue=None, *, weights=None, checkpoint_dir: Optional[str] = None, dtype="f16", nb=None,
+                 lr_shape=None, seed=0, max_streams=1, generator="egvsr"):
         self.lr_shape = tuple(lr_shape) if lr_shape is not None else LR_SHAPES[lr_level]
         self.scale = 4
         self.hr_shape = tuple([i * self.scale for i in self.lr_shape])
@@ -109,7 +111,8 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self.weights = weights
         self.checkpoint_dir = checkpoint_dir
         self.dtype = dtype
-        self.nb = int(nb)
+        self.generator = generator   # 'egvsr' (the reference service's FRNet) | 'tecogan' (the FRNet it was cut down from, tecogan_nets.py:101-202)
+        self.nb = int(nb) if nb is not None else (16 if generator in ("tecogan", 1) else 10)
         self.seed = seed
         self.max_streams = int(max_streams)
         super().__init__()
@@ -127,7 +130,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
             log("WARNING: weights='synthetic' - the network runs on generated weights, output frames are noise")
         self.ctx = _capi.Context(self.device)
         self.torch_device = self.ctx.device
-        self.model = factory.build_model_egvsr(self.ctx, self.weights, self.seed, self.checkpoint_dir, self.dtype, self.nb)
+        self.model = factory.build_model_frvsr(self.ctx, self.weights, self.seed, self.checkpoint_dir, self.dtype, self.nb, self.generator)
         self._up = None
         self._up_key = None
         self._slots = StreamSlots(self.max_streams)

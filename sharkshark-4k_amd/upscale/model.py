@@ -220,3 +220,39 @@ def build_model_egvsr(ctx: _capi.Context, weights: WeightSpec = None, seed: int 
                       dtype="f16", nb: int = 10):
     """The callable behind ``self.model(lr_curr, self.lr_prev, self.hr_prev)`` (egvsr_upscaler.py:204)."""
     return _capi.Frvsr(ctx, egvsr_desc(dtype, nb), egvsr_flat(weights, seed, checkpoint_dir, nb))
+
+
+# ---- the frame-recurrent generators: EGVSR's FRNet and the one it was cut down from, TecoGAN's (tecogan_nets.py:101-202, nb = 16)
+TECOGAN_CHECKPOINT = "TecoGAN_BD_iter500000.pth"
+FRVSR_GENERATORS = {"egvsr": _capi.FRVSR_EGVSR, "tecogan": _capi.FRVSR_TECOGAN}
+
+
+def frvsr_generator(generator) -> int:
+    """'egvsr' | 'tecogan' | 0 | 1 -> SS4K_FRVSR_*"""
+    if isinstance(generator, str):
+        if generator not in FRVSR_GENERATORS:
+            raise ValueError(f"generator must be one of {sorted(FRVSR_GENERATORS)}, not {generator!r}")
+        return FRVSR_GENERATORS[generator]
+    if int(generator) not in FRVSR_GENERATORS.values():
+        raise ValueError(f"generator must be 0 (egvsr) or 1 (tecogan), not {generator!r}")
+    return int(generator)
+
+
+def tecogan_flat(weights: WeightSpec = None, seed: int = 0, checkpoint_dir: Optional[str] = None, nb: int = W.TECOGAN_NB) -> np.ndarray:
+    if isinstance(weights, str) and weights == SYNTHETIC:
+        table = W.tecogan_table(seed, nb=nb)
+    else:
+        kind, obj = _load_checkpoint(weights, "TecoGAN", TECOGAN_CHECKPOINT, checkpoint_dir)
+        table = CK.tecogan_from_checkpoint(obj, nb) if kind == "ckpt" else obj
+    return W.flatten(table, W.tecogan_keys(nb))
+
+
+def build_model_frvsr(ctx: _capi.Context, weights: WeightSpec = None, seed: int = 0, checkpoint_dir: Optional[str] = None,
+                      dtype="f16", nb: Optional[int] = None, generator="egvsr", route_flags: int = 0):
+    """``build_model_egvsr`` for either generator; ``nb`` defaults to the generator's own (10 | 16)."""
+    g = frvsr_generator(generator)
+    if g == _capi.FRVSR_EGVSR:
+        nb = 10 if nb is None else nb
+        return _capi.Frvsr(ctx, egvsr_desc(dtype, nb), egvsr_flat(weights, seed, checkpoint_dir, nb), g, route_flags)
+    nb = W.TECOGAN_NB if nb is None else nb
+    return _capi.Frvsr(ctx, egvsr_desc(dtype, nb), tecogan_flat(weights, seed, checkpoint_dir, nb), g, route_flags)

@@ -185,6 +185,25 @@ def bsvd_table(seed: int = 0, **kw) -> Table:
     return t
 
 
+TECOGAN_NB = 16   # tecogan_nets.py:153 (FRNet's default nb; EGVSR's service builds its cut-down FRNet with 10)
+
+
+def tecogan_keys(nb: int = TECOGAN_NB) -> List[str]:
+    """TecoGAN's FRNet(degradation='BD').state_dict() order (tecogan_nets.py:101-202): key for key EGVSR's - the two differ in what ``forward`` does
+    with ``srnet.conv_up.*`` and in the shape of ``srnet.conv_out.weight`` ((3, nf, 3, 3) here)."""
+    return frnet_keys(nb)
+
+
+def tecogan_table(seed: int = 0, nf: int = 64, nb: int = TECOGAN_NB, flow_gain: float = 1.0) -> Table:
+    """``frnet_table`` with the tail TecoGAN's forward runs: every output pixel of ConvTranspose2d(3, 2, 1, output_padding=1) sums 1, 2 or 4
+    of the nine taps (9 / 4 on average), so the transposed layers' weights are kaiming scale times 2 and activations keep their magnitude."""
+    t: Table = OrderedDict(frnet_table(seed, nf, nb, flow_gain))
+    for c in (0, 2):   # ConvTranspose2d weights are (C_in, C_out, kH, kW)
+        _conv(t, seed, f"srnet.conv_up.{c}", nf, nf, 3, gain=2.0)
+    _conv(t, seed, "srnet.conv_out", 3, nf, 3)
+    return OrderedDict((k, t[k]) for k in tecogan_keys(nb))
+
+
 # --------------------------------------------------------------------------------------
 # FRNet as built by the EGVSR service (reference: src/upscale/model/egvsr/egvsr.py:146-162, egvsr_upscaler.py:26)
 # --------------------------------------------------------------------------------------

@@ -16,8 +16,14 @@ library built before the slots existed: ``SS4K_LIB=<older build>`` for an A/B). 
 and every result an ALLOCATION OF ITS OWN - the shape of frames that arrive in ring slots and leave into ring slots.  A round's glue is
 then three launches whatever S is, and the glue column of the stage split is where it shows.
 
+``--generator tecogan``: TecoGAN's FRNet (``ss4k_frvsr_create_as``; ``--nb`` then defaults to 16) instead of EGVSR's.  Its tail has stages of
+its own - ``convt`` (the two transposed convolutions), ``conv_out``, ``skip`` - and the row carries the transposed layers' TFLOP/s on their
+useful FLOPs (2 x 9 x 64 x 64 per input pixel, at (h, w) and at (2 h, 2 w)).  ``--embedded`` pins them to the route that embeds each in a
+pad-1 3x3 convolution 64 -> 256 on the conv kernels (``SS4K_FRVSR_CONVT_EMBEDDED``), ``--phase`` to the kernel of their own
+(``SS4K_FRVSR_CONVT_PHASE``); neither: the library's choice.
+
 usage: python tools/frvsr_time.py [--frames 64] [--nb 10] [--streams 1] [--scattered] [--lr 540x960,720x1280]
-                                  [--output-shapes 1440x2560,none] [--out frvsr_time.json]"""
+                                  [--output-shapes 1440x2560,none] [--generator egvsr|tecogan] [--embedded | --phase] [--out frvsr_time.json]"""
 import argparse
 import json
 import os
@@ -42,6 +48,11 @@ def conv_flops(h, w, nb, nf=64):
     return f, s
 
 
+def tecogan_tail_flops(h, w, nf=64):
+    """(the two transposed layers on their useful FLOPs - nine nf x nf taps per INPUT pixel -, conv_out) of one step"""
+    return 18.0 * nf * nf * (h * w + 4 * h * w), 18.0 * nf * 3 * 16 * h * w
+
+
 def stream_frames(n, h, w, device):
     """n distinct uint8 frames: a smooth scene that moves 2 px right and 1 px down per frame (wrapping)."""
     g = torch.Generator(device="cpu").manual_seed(1)
@@ -53,7 +64,10 @@ def stream_frames(n, h, w, device):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
-    ap.add_argument("--nb", type=int, default=10)
+    ap.add_argument("--nb", type=int, default=None, help="residual blocks (default: 10, tecogan 16)")
+    ap.add_argument("--generator", default="egvsr", choices=["egvsr", "tecogan"])
+    ap.add_argument("--embedded", action="store_true", help="tecogan: the transposed layers on the embedded route (SS4K_FRVSR_CONVT_EMBEDDED)")
+    ap.add_argument("--phase", action="store_true", help="tecogan: the transposed layers on the phase kernel (SS4K_FRVSR_CONVT_PHASE)")
     ap.add_argument("--streams", type=int, default=1, help="streams stepped in lockstep, one batched step per round")
     ap.add_argument("--scattered", action="store_true", help="rounds through ss4k_frvsr_upscale_streams_at, frames and results as separate allocations")
     ap.add_argument("--lr", default=",".join(f"{h}x{w}" for h, w in REFERENCE_MS), help="lr shapes, HxW[,HxW...]")
@@ -62,13 +76,22 @@ def main():
     a = ap.parse_args()
     assert a.frames >= 64, "the steady state is read from a stream of at least 64 distinct frames"
     S = a.streams
+    teco = a.generator == "tecogan"
+    assert teco or not (a.embedded or a.phase), "--embedded and --phase are routes of the tecogan generator"
+    assert not (a.embedded and a.phase), "one route"
+    route = "embedded" if a.embedded else "phase" if a.phase else "default"
+    a.nb = a.nb if a.nb is not None else (16 if teco else 10)
     lrs = [tuple(int(v) for v in t.split("x")) for t in a.lr.split(",")]
     out_shapes = [None if t == "none" else tuple(int(v) for v in t.split("x")) for t in a.output_shapes.split(",")]
     import sharkshark4k_amd  # noqa: F401
     from sharkshark4k_amd import _capi, weights as W
     assert torch.cuda.is_available(), "needs the GPU: no timing without one"
     ctx = _capi.Context(0)
-    model = _capi.Frvsr(ctx, _capi.make_frvsr_desc(_capi.F16, 64, a.nb), W.flatten(W.frnet_table(0, nb=a.nb), W.frnet_keys(a.nb)))
+    if teco:
+        model = _capi.Frvsr(ctx, _capi.make_frvsr_desc(_capi.F16, 64, a.nb), W.flatten(W.tecogan_table(0, nb=a.nb), W.tecogan_keys(a.nb)),
+                            _capi.FRVSR_TECOGAN, _capi.FRVSR_CONVT_EMBEDDED if a.embedded else _capi.FRVSR_CONVT_PHASE if a.phase else 0)
+    else:
+        model = _capi.Frvsr(ctx, _capi.make_frvsr_desc(_capi.F16, 64, a.nb), W.flatten(W.frnet_table(0, nb=a.nb), W.frnet_keys(a.nb)))
     rows = []
     for lr in lrs:
         frames = stream_frames(a.frames, lr[0], lr[1], ctx.device)
@@ -120,10 +143,15 @@ def main():
                        stage_ms_per_frame=stages, stage_sum_ms=sum(stages.values()), fnet_conv_tflops=ff / stages["fnet_conv"] / 1e9,
                        srnet_conv_tflops=fs / stages["srnet_conv"] / 1e9, conv_tflop_per_step=(ff + fs) / 1e12,
                        workspace_mb=model.workspace_bytes(S, lr[0], lr[1]) / 2 ** 20)
+            if teco:
+                ft, fo = tecogan_tail_flops(lr[0], lr[1])
+                row.update(generator="tecogan", convt_route=route, convt_tflops_useful=ft / stages["convt"] / 1e9,
+                           conv_out_tflops=fo / stages["conv_out"] / 1e9, convt_gflop_per_step=ft / 1e9)
             rows.append(row)
             print(f"lr {lr[0]}x{lr[1]} -> {oh}x{ow}, {S} stream{'s' if S > 1 else ''}{' scattered' if a.scattered else ''}: {ms:.2f} ms/frame, {1000.0 / ms:.1f} frames/s "
                   f"(reference {REFERENCE_MS.get(lr, float('nan')):.0f} ms, TensorRT, hardware unstated); "
-                  + ", ".join(f"{k} {v:.2f}" for k, v in stages.items()) + f" ms; FNet convs {row['fnet_conv_tflops']:.0f} TFLOP/s, SRNet convs {row['srnet_conv_tflops']:.0f} TFLOP/s",
+                  + ", ".join(f"{k} {v:.2f}" for k, v in stages.items()) + f" ms; FNet convs {row['fnet_conv_tflops']:.0f} TFLOP/s, SRNet convs {row['srnet_conv_tflops']:.0f} TFLOP/s"
+                  + (f", transposed layers ({row['convt_route']}) {row['convt_tflops_useful']:.0f} TFLOP/s useful" if teco else ""),
                   flush=True)
             up.close()
             del out
