@@ -30,6 +30,9 @@ Semantics (``StreamRouter`` is the table, testable without processes):
   count in ``report()['lost']`` and their steps are handed out without them.  A later submit that names a lost id opens it anew on a
   living worker FROM ZERO STATE (``report()['reopened']``).  Nothing is rescued or run again - old frames on fresh state would be a
   wrong picture - and no replacement worker is started.
+
+The workers' life cycle (device list, rings and ready events before the start, the ready wait, ``alive`` / ``stop`` / ``close``) is
+``worker_pool.WorkerPool``'s, shared with ``node.UpscalerNode``.
 """
 from __future__ import annotations
 
@@ -40,9 +43,9 @@ from typing import Any, Dict, Hashable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from . import hostring
 from .hostring import HostFrames, SlotPool
 from .upscale.egvsr_upscaler import HipEgvsrUpscalerService, StreamQueueEntry
+from .worker_pool import WorkerPool
 
 
 class StreamRouter:
@@ -114,15 +117,10 @@ class NodeResult:
     profiler: Any = None
 
 
-class EgvsrNode:
+class EgvsrNode(WorkerPool):
     def __init__(self, devices: Union[int, Sequence[int], None] = None, max_streams: int = 1, job_frames: int = 4, host_frames=True,
                  host_slots: int = 6, output_shape="unset", service_cls=HipEgvsrUpscalerService, push_timeout: float = 10.0, **service_kwargs):
-        if devices is None:
-            import torch
-            devices = torch.cuda.device_count()   # (counting devices does not initialise the GPU in this process)
-        self.devices: List[int] = list(range(devices)) if isinstance(devices, int) else [int(d) for d in devices]
-        if not self.devices:
-            raise ValueError("EgvsrNode needs at least one device")
+        super().__init__(devices)
         if not host_frames:
             raise ValueError("EgvsrNode takes host frames: host_frames is True (frames of the service's lr_shape) or (H, W)")
         self.max_streams, self.job_frames, self.host_slots = int(max_streams), int(job_frames), int(host_slots)
@@ -139,66 +137,10 @@ class EgvsrNode:
         self.next_emit = 0
         self.host_jobs = [0] * G
         self.lost = 0
-        self.started = False
 
     def _make_service(self, k: int):
-        import torch.multiprocessing as mp
         svc = self.service_cls(device=self.devices[k], max_streams=self.max_streams, **self.service_kwargs)
-        if self.output_shape != "unset":
-            svc.output_shape = self.output_shape
-        h, w = svc.lr_shape if self.host_frames is True else self.host_frames
-        oh, ow = svc.out_hw()
-        svc.host_rings = hostring.make_rings(self.host_slots, self.job_frames * h * w * 3, self.job_frames * oh * ow * 3)
-        svc.mp_start_method = "spawn"   # the launcher may have touched the GPU; workers are fresh interpreters
-        svc.ready_event = mp.get_context("spawn").Event()
-        return svc
-
-    # ------------------------------------------------------------------------------------------ life cycle
-    def start(self, timeout: float = 600.0) -> "EgvsrNode":
-        for svc in self.services:
-            svc.start()
-        self.started = True
-        deadline = time.monotonic() + timeout
-        waiting = list(self.services)
-        while waiting:
-            for svc in list(waiting):
-                if svc.ready_event.wait(0.05):
-                    waiting.remove(svc)
-                elif not svc.proc.is_alive():
-                    raise RuntimeError(f"EgvsrNode: the worker on device {svc.device} died during start-up (exit code {svc.proc.exitcode})")
-            if waiting and time.monotonic() > deadline:
-                raise TimeoutError(f"EgvsrNode: {len(waiting)} worker(s) not ready after {timeout:.0f} s")
-        return self
-
-    def alive(self) -> List[bool]:
-        return [svc.proc.is_alive() for svc in self.services]
-
-    def stop(self) -> List[Optional[int]]:
-        codes = []
-        for svc in self.services:
-            if svc.proc.is_alive():
-                try:
-                    svc.stop()
-                except Exception:  # noqa: BLE001 - a worker that dies between the check and the command is already stopped
-                    pass
-                if svc.proc.is_alive():
-                    svc.proc.kill()   # it did not take the exit command: end exactly the child this node started
-                    svc.proc.join(timeout=15)
-            codes.append(svc.proc.exitcode)
-        return codes
-
-    def close(self) -> None:
-        """Give the host rings back (after ``stop()``; views handed out by ``poll()`` die with them)."""
-        for svc in self.services:
-            for ring in getattr(svc, "host_rings", None) or ():
-                ring.close()
-
-    def __enter__(self):
-        return self.start() if not self.started else self
-
-    def __exit__(self, *exc):
-        self.stop()
-        return False
+        return self._prepare(svc, svc.lr_shape if self.host_frames is True else self.host_frames, svc.out_hw)
 
     # ------------------------------------------------------------------------------------------ in
     def submit(self, frames, streams: Sequence[Hashable], end_streams: Sequence[Hashable] = (), audio_segment=None, profiler=None) -> int:

@@ -30,16 +30,19 @@ What it does, in order:
   the group of the start-up is gone by then.  ``auto_replace=True`` does that by itself, without blocking the stream: ``poll()`` starts
   the replacement when it sees a dead worker and swaps it in once it reports ready (the reference's image server restarts its pipeline on a
   dead worker, ``image_pipeline.py:66-73,295-301``; its deployment script loops ``while true``).
+
+The workers' life cycle (device list, rings and ready events before the start, the ready wait, ``alive`` / ``stop`` / ``close``) is
+``worker_pool.WorkerPool``'s, shared with ``egvsr_node.EgvsrNode``; this class adds the process group, replacement and the dispatcher.
 """
 from __future__ import annotations
 
 import socket
-import time
 from typing import List, Optional, Sequence, Union
 
-from . import hostring, sharding
+from . import sharding
 from .stream import StreamDispatcher
 from .upscale.hip_upscaler import HipUpscalerService
+from .worker_pool import WorkerPool
 
 
 def _free_port() -> int:
@@ -48,16 +51,11 @@ def _free_port() -> int:
         return s.getsockname()[1]
 
 
-class UpscalerNode:
+class UpscalerNode(WorkerPool):
     def __init__(self, devices: Union[int, Sequence[int], None] = None, service_cls=HipUpscalerService, backend: Optional[str] = None,
                  fps: int = 24, frame_skips: bool = True, on_result=None, lost_after_s: float = 5.0, force_group: bool = False,
                  output_shape="unset", host_frames=True, host_slots: int = 6, auto_replace: bool = False, **service_kwargs):
-        if devices is None:
-            import torch
-            devices = torch.cuda.device_count()   # (counting devices does not initialise the GPU in this process)
-        self.devices: List[int] = list(range(devices)) if isinstance(devices, int) else [int(d) for d in devices]
-        if not self.devices:
-            raise ValueError("UpscalerNode needs at least one device")
+        super().__init__(devices)
         if backend is None and len(set(self.devices)) < len(self.devices):
             backend = "gloo"   # RCCL refuses two ranks on one GPU: workers that share a device exchange the weights through host memory
         self.service_cls, self.service_kwargs, self.backend, self.force_group = service_cls, dict(service_kwargs), backend, force_group
@@ -68,49 +66,18 @@ class UpscalerNode:
         self.port = _free_port()
         self.services = [self._make_service(k, len(self.devices)) for k in range(len(self.devices))]
         self.dispatcher = StreamDispatcher(self.services, fps=fps, frame_skips=frame_skips, on_result=on_result, lost_after_s=lost_after_s)
-        self.started = False
         self.auto_replace = bool(auto_replace)
         self._replacing = {}      # slot -> replacement service that has been started and is not ready yet
         self.replaced_total = 0
 
     def _make_service(self, k: int, world: int):
-        import torch.multiprocessing as mp
         group = sharding.GroupSpec(rank=k if world > 1 else 0, world=world, master_port=self.port, backend=self.backend,
                                    force=self.force_group and world == 1)
         svc = self.service_cls(device=self.devices[k], group=group, **self.service_kwargs)
-        if self.output_shape != "unset":
-            svc.output_shape = self.output_shape
-        if self.host_frames:
-            h, w = svc.lr_shape if self.host_frames is True else self.host_frames
-            oh, ow = svc.out_hw(h, w)
-            svc.host_rings = hostring.make_rings(self.host_slots, self.job_frames * h * w * 3, self.job_frames * oh * ow * 3)
-        svc.mp_start_method = "spawn"   # the launcher may have touched the GPU (warm-up, device queries); workers are fresh interpreters
-        svc.ready_event = mp.get_context("spawn").Event()
-        return svc
-
-    # ------------------------------------------------------------------------------------------
-    def start(self, timeout: float = 600.0) -> "UpscalerNode":
-        for svc in self.services:
-            svc.start()
-        self.started = True
-        self._wait_ready(self.services, timeout)
-        return self
-
-    @staticmethod
-    def _wait_ready(services, timeout: float) -> None:
-        deadline = time.monotonic() + timeout
-        waiting = list(services)
-        while waiting:
-            for svc in list(waiting):
-                if svc.ready_event.wait(0.05):
-                    waiting.remove(svc)
-                elif not svc.proc.is_alive():
-                    raise RuntimeError(f"UpscalerNode: the worker on device {svc.device} died during start-up (exit code {svc.proc.exitcode})")
-            if waiting and time.monotonic() > deadline:
-                raise TimeoutError(f"UpscalerNode: {len(waiting)} worker(s) not ready after {timeout:.0f} s")
-
-    def alive(self) -> List[bool]:
-        return [svc.proc.is_alive() for svc in self.services]
+        if not self.host_frames:
+            return self._prepare(svc)
+        hw = svc.lr_shape if self.host_frames is True else self.host_frames
+        return self._prepare(svc, hw, lambda: svc.out_hw(*hw))
 
     def replace_dead(self, timeout: float = 600.0) -> List[int]:
         """Start a fresh child in the slot of every dead worker; returns the slots replaced.  The replacement is a world-of-one worker
@@ -129,11 +96,6 @@ class UpscalerNode:
             self.dispatcher.services[k] = svc
             self._close_rings(old)
         return slots
-
-    @staticmethod
-    def _close_rings(svc) -> None:
-        for ring in getattr(svc, "host_rings", None) or ():
-            ring.close()
 
     # ------------------------------------------------------------------------------------------ the stream caller's interface
     def submit_batch(self, frames, audio_segment=None, profiler=None):
@@ -177,35 +139,10 @@ class UpscalerNode:
         return r
 
     def stop(self) -> List[Optional[int]]:
-        codes = []
         for new in list(self._replacing.values()):   # (replacements that were still loading)
             if new.proc.is_alive():
                 new.proc.kill()
                 new.proc.join(timeout=15)
             self._close_rings(new)
         self._replacing.clear()
-        for svc in self.services:
-            if svc.proc.is_alive():
-                try:
-                    svc.stop()
-                except Exception:  # noqa: BLE001 - a worker that dies between the check and the command is already stopped
-                    pass
-                if svc.proc.is_alive():
-                    # it did not take the exit command (e.g. still inside a collective whose peer died during start-up): end exactly
-                    # this child - the process object this node started
-                    svc.proc.kill()
-                    svc.proc.join(timeout=15)
-            codes.append(svc.proc.exitcode)
-        return codes
-
-    def close(self) -> None:
-        """Give the host rings back (after ``stop()``; views handed out by ``poll()`` die with them)."""
-        for svc in self.services:
-            self._close_rings(svc)
-
-    def __enter__(self):
-        return self.start() if not self.started else self
-
-    def __exit__(self, *exc):
-        self.stop()
-        return False
+        return super().stop()

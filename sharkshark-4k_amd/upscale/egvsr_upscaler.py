@@ -18,7 +18,7 @@ was.
 Host frames (``host_rings``, set by ``egvsr_node.EgvsrNode`` or by the caller before ``start()``; ``hostring.py``): a job whose ``frames`` is a
 ``HostFrames`` descriptor names a slot of this worker's pinned input ring.  The worker copies it to a staging tensor on a copy stream of its
 own, runs the job, copies the result into the named slot of the output ring on a second copy stream and answers with
-``HostFrames(result=True)``; one more job is enqueued before that result is waited for, so the copies run under the neighbour's kernels.  A
+``HostFrames(result=True)``; one more job is enqueued before that result is waited for, so the copies run under the neighbour's kernels (``host_io.py``: ``HostFrameIO`` and ``HeldResults``, shared with ``HipUpscalerService``).  A
 ``StreamQueueEntry`` with ``frames=None`` and ``end_streams`` only frees those slots: no GPU work, answered with ``frames=None``.
 
 ``generator='tecogan'`` runs TecoGAN's FRNet instead (``nb`` then defaults to 16; its checkpoint is that class's bare state_dict).
@@ -38,8 +38,8 @@ from typing import Hashable, List, Optional, Sequence
 import torch
 
 from ..hostring import HostFrames
+from .host_io import HOST, HeldResults, HostFrameIO
 from .upscaler_base import BaseUpscalerService, UpscalerQueueEntry, answer
-from ..util.profiler import Profiler
 
 LR_SHAPES = [(540, 960), (630, 1120), (720, 1280)]   # egvsr_upscaler.py:147-151
 
@@ -137,67 +137,21 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self._init_host_io()
         log("model loaded")
 
-    # host frames: HipUpscalerService._init_host_io / _staging / _host_job restated for this service (no job sets here: a job's launches are
-    # all on the current stream, so its end is one event recorded there)
     def _init_host_io(self):
         self._host_jobs = 0
-        self._landing = {}     # id(answer's HostFrames) -> (the HostFrames, event after which the result slot holds the frames)
-        self._lag_now = 0
-        if self.host_rings is None:
-            return
-        for ring in self.host_rings:
-            try:
-                ring.pin()
-            except RuntimeError as e:   # (copies to and from pageable memory still work - staged by the runtime, no longer asynchronous)
-                log(f"WARNING: {e}: host frames go through UNPINNED memory")
-        self._s_in, self._s_out = torch.cuda.Stream(self.torch_device), torch.cuda.Stream(self.torch_device)
-        self._stage = {}    # input shape -> [[device tensor, event after which it may be overwritten], ...], used round robin
-        self._stage_at = {}
-        log(f"host frame rings pinned: {self.host_rings[0].slots} slots, {self.host_rings[0].slot_bytes >> 10} KB in / {self.host_rings[1].slot_bytes >> 10} KB out each")
-
-    def _staging(self, shape):
-        bufs = self._stage.setdefault(shape, [])
-        if len(bufs) < self.HOST_STAGE_DEPTH:
-            bufs.append([torch.empty(shape, dtype=torch.uint8, device=self.torch_device), None])
-            return bufs[-1]
-        i = self._stage_at.get(shape, 0)
-        self._stage_at[shape] = (i + 1) % self.HOST_STAGE_DEPTH
-        return bufs[i]
-
-    def _host_job(self, hf: HostFrames, streams, end_streams):
-        """H2D on the copy stream -> upscale -> D2H on the other copy stream; returns (result shape, event after which the result slot holds
-        the frames)."""
-        src = self.host_rings[0].view(hf.slot, hf.shape)
-        with torch.cuda.device(self.torch_device):
-            cur = torch.cuda.current_stream(self.torch_device)
-            stage = self._staging(tuple(hf.shape))
-            with torch.cuda.stream(self._s_in):
-                if stage[1] is not None:
-                    self._s_in.wait_event(stage[1])
-                stage[0].copy_(src, non_blocking=True)
-                copied = self._s_in.record_event()
-            cur.wait_event(copied)
-            out = self.upscale(stage[0], streams, end_streams) if streams is not None or end_streams else self.upscale(stage[0])
-            done = cur.record_event()
-            stage[1] = done
-            with torch.cuda.stream(self._s_out):
-                self._s_out.wait_event(done)
-                self.host_rings[1].view(hf.out_slot, tuple(out.shape)).copy_(out, non_blocking=True)
-                landed = self._s_out.record_event()
-            out.record_stream(self._s_out)
-        return tuple(out.shape), landed
+        self._held = HeldResults()
+        self._lag_now = 0   # 1 from the first host job on: one more job is enqueued before a result is waited for, the copies hide under it
+        # (no job sets here: a job's launches are all on the current stream, so its end is the event HostFrameIO records there)
+        self._io = HostFrameIO(self.host_rings, self.torch_device, self.HOST_STAGE_DEPTH, log)
 
     def proc_deliver_lag(self) -> int:
-        return getattr(self, "_lag_now", 0)
+        return self._lag_now
 
     def proc_result_ready(self, entry) -> bool:
-        rec = getattr(self, "_landing", {}).get(id(getattr(entry, "frames", None)))
-        return rec is None or rec[1].query()
+        return self._held.ready(entry)
 
     def proc_before_deliver(self, entry):
-        rec = getattr(self, "_landing", {}).pop(id(getattr(entry, "frames", None)), None)
-        if rec is not None:
-            rec[1].synchronize()   # the consumer reads the ring slot from another process: the bytes must have landed
+        self._held.release(entry)   # (the consumer reads the ring slot from another process: the bytes must have landed)
 
     def proc_cleanup(self):
         for name in ("_up", "model", "ctx"):
@@ -285,30 +239,29 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         # as BaseUpscalerService.proc_job_recieved, plus the two optional attributes of a multi-stream job; a record without them is a job of
         # the unnamed stream and is answered by the base class's answer() exactly as before
         streams, end_streams = getattr(job, "streams", None), tuple(getattr(job, "end_streams", None) or ())
-        prof = job.profiler if getattr(job, "profiler", None) is not None else Profiler()
-        self.profiler = prof
-        arrived = time.time()
-        prof.end("recoder.output")
-        prof.start("upscaler.upscale")
-        try:
-            if job.frames is None and end_streams:   # nothing to upscale: the ids give their slots back, the GPU is not touched
+
+        def upscale(frames):
+            return self.upscale(frames, streams, end_streams) if streams is not None or end_streams else self.upscale(frames)
+
+        def run():
+            hf = job.frames
+            if hf is None and end_streams:   # nothing to upscale: the ids give their slots back, the GPU is not touched
                 for sid in end_streams:
                     self._slots.end(sid)
-                upscaled = None
-            elif isinstance(job.frames, HostFrames):
-                if self.host_rings is None:
-                    raise RuntimeError("a HostFrames job reached a worker that was started without host rings")
-                shape, landed = self._host_job(job.frames, streams, end_streams)
-                self._host_jobs += 1
-                upscaled = HostFrames(slot=job.frames.slot, out_slot=job.frames.out_slot, shape=shape, result=True)
-                self._landing[id(upscaled)] = (upscaled, landed)
-                self._lag_now = 1   # one more job is enqueued before this result is waited for: the copies hide under it
-            else:
-                upscaled = self.upscale(job.frames, streams, end_streams) if streams is not None or end_streams else self.upscale(job.frames)
-        finally:
-            prof.end("upscaler.upscale")
-        elapsed = time.time() - arrived
-        prof.start("upscaler.output")
+                return None
+            if not isinstance(hf, HostFrames):
+                return upscale(hf)
+            if self.host_rings is None:
+                raise RuntimeError("a HostFrames job reached a worker that was started without host rings")
+            shape, landed = self._io.run(hf, upscale)
+            self._host_jobs += 1
+            answered = HostFrames(slot=hf.slot, out_slot=hf.out_slot, shape=shape, result=True)
+            if landed is not None:
+                self._held.hold(answered, landed, HOST)
+                self._lag_now = 1
+            return answered
+
+        upscaled, elapsed, prof = self._run_job(job, run)
         if hasattr(job, "streams") or hasattr(job, "end_streams"):
             try:   # the caller's own type, when it takes the eight fields
                 return type(job)(frames=upscaled, audio_segment=getattr(job, "audio_segment", None), step=getattr(job, "step", 0), elapsed=elapsed,

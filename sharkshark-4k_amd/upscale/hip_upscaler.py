@@ -40,7 +40,8 @@ Host frames (``host_rings``, set by ``node.UpscalerNode``; ``hostring.py``): a j
 of this worker's pinned input ring; the worker copies it to the device on its own copy stream, runs the job, copies the result into the
 named slot of the pinned output ring on a second copy stream and answers with a descriptor.  One more job is enqueued before a result is
 waited for (two jobs in flight), so both copies run under the neighbouring jobs' kernels (``pipeline.py:84-93`` / ``streamer.py:92-98`` are the
-reference's host <-> device hops).  A device tensor that lives on ANOTHER GPU is copied over once, counted in ``'upscaler.input.peer_copies'``.
+reference's host <-> device hops).  The copies, their ordering and the held results are ``host_io.py``'s (``HostFrameIO``, ``HeldResults``), shared with
+the EGVSR service; this service adds its staging depth, the job sets' end events and its lag policy.  A device tensor that lives on ANOTHER GPU is copied over once, counted in ``'upscaler.input.peer_copies'``.
 """
 from __future__ import annotations
 
@@ -54,6 +55,7 @@ import torch
 from .. import sharding
 from ..hostring import HostFrames
 from ..util.profiler import Profiler
+from .host_io import DEVICE, HOST, HeldResults, HostFrameIO
 from .upscaler_base import BaseUpscalerService, UpscalerQueueEntry, answer, record_span  # noqa: F401
 
 LR_LEVELS = [(360, 640), (540, 960), (630, 1120), (720, 1280), (900, 1600), (1080, 1920)]
@@ -250,7 +252,6 @@ class HipUpscalerService(BaseUpscalerService):
         # job sets: [0] is what every job ran on before; [1] (second context / model / stream) is built on the first one-frame job
         self._sets = [{"ctx": self.ctx, "model": self.model, "denoise": self.denoise_model, "up": None, "key": None, "stream": None}]
         self._alt = 0
-        self._pending = {}
         self._inflight = collections.deque()   # (end-of-job event, input frames) of jobs on a job set's stream: see _retire
         self._streams_checked = False
         self._small = {}
@@ -262,93 +263,47 @@ class HipUpscalerService(BaseUpscalerService):
         # stream waits for before it starts, and a consumer callback may block on it - but it leaves as soon as its end event has fired
         # (proc_result_ready).  A job that does not alternate (multi-frame: frame lanes on set 0) sets the lag to 0 and flushes (proc_deliver_lag).
         self.deliver_lag = self.overlap_sets - 1 if self._overlap_active() else 0
-        self._lag_now = 0
+
+    #: the most results held back right now (``proc_deliver_lag``): set by ``upscale()`` from the path the NEWEST job took, raised to 1 by a host job
+    _lag_now = 0
+    #: (the empty registry of a double whose ``proc_init`` skips ``_init_host_io``: nothing is ever held there)
+    _held = HeldResults()
 
     def _init_host_io(self):
         self._peer_copies = 0
         self._host_jobs = 0
-        if not hasattr(self, "_pending"):
-            self._pending = {}
-        if self.host_rings is None:
-            return
-        self._host_on_gpu = self.torch_device.type == "cuda"   # (a CPU double of the worker - tests - reads and writes the rings directly)
-        if not self._host_on_gpu:
-            return
-        for ring in self.host_rings:
-            try:
-                ring.pin()
-            except RuntimeError as e:   # (copies to and from pageable memory still work - staged by the runtime, no longer asynchronous)
-                log(f"WARNING: {e}: host frames go through UNPINNED memory")
-        self._s_in, self._s_out = torch.cuda.Stream(self.torch_device), torch.cuda.Stream(self.torch_device)
-        self._stage = {}    # input shape -> [[device tensor, event after which it may be overwritten], ...], used round robin
-        self._stage_at = {}
-        log(f"host frame rings pinned: {self.host_rings[0].slots} slots, {self.host_rings[0].slot_bytes >> 10} KB in / {self.host_rings[1].slot_bytes >> 10} KB out each")
-
-    def _staging(self, shape):
-        """A device tensor for one job's input frames.  More of them than jobs can be in flight, each guarded by the end event of the job
-        that last read it (the copy stream waits for it before it overwrites the tensor)."""
-        bufs = self._stage.setdefault(shape, [])
-        depth = self.overlap_sets + 2
-        if len(bufs) < depth:
-            bufs.append([torch.empty(shape, dtype=torch.uint8, device=self.torch_device), None])
-            return bufs[-1]
-        i = self._stage_at.get(shape, 0)
-        self._stage_at[shape] = (i + 1) % depth
-        return bufs[i]
+        self._lag_now = 0
+        self._held = HeldResults()
+        # more staging tensors than jobs can be in flight; on a CPU double of the worker (tests) the rings are read and written directly
+        self._io = HostFrameIO(self.host_rings, self.torch_device, self.overlap_sets + 2, log)
 
     def _host_job(self, hf: HostFrames):
-        """H2D on the copy stream -> upscale -> D2H on the other copy stream; returns (result shape, event after which the result slot holds
-        the frames - None when it already does)."""
-        src = self.host_rings[0].view(hf.slot, hf.shape)
-        if not self._host_on_gpu:
-            out = self.upscale(src)
-            self.host_rings[1].view(hf.out_slot, tuple(out.shape)).copy_(out)
-            return tuple(out.shape), None
-        cur = torch.cuda.current_stream(self.torch_device)
-        stage = self._staging(tuple(hf.shape))
-        with torch.cuda.stream(self._s_in):
-            if stage[1] is not None:
-                self._s_in.wait_event(stage[1])
-            stage[0].copy_(src, non_blocking=True)
-            copied = self._s_in.record_event()
-        cur.wait_event(copied)
-        out = self.upscale(stage[0])
-        rec = self._pending.pop(id(out), None)           # (job-set path: the result is ordered on its set's stream, not on the current one)
-        done = rec[1] if rec is not None else cur.record_event()
-        stage[1] = done
-        with torch.cuda.stream(self._s_out):
-            self._s_out.wait_event(done)
-            self.host_rings[1].view(hf.out_slot, tuple(out.shape)).copy_(out, non_blocking=True)
-            landed = self._s_out.record_event()
-        out.record_stream(self._s_out)
-        return tuple(out.shape), landed
+        """``HostFrameIO.run`` around ``upscale``; the end of a job that ran on a job set's stream is that set's event, held under its result."""
+        return self._io.run(hf, self.upscale, self._held.pop_event)
 
     def proc_job_recieved(self, job):
-        if not isinstance(getattr(job, "frames", None), HostFrames):
+        hf = getattr(job, "frames", None)
+        if not isinstance(hf, HostFrames):
             entry = super().proc_job_recieved(job)
             return self._to_host_result(entry) if self.host_results and getattr(self, "_in_worker", False) else entry
-        # the same spans as BaseUpscalerService.proc_job_recieved, around the host job
-        import time
-        hf = job.frames
         if self.host_rings is None:
             raise RuntimeError("a HostFrames job reached a worker that was started without host rings")
-        prof = job.profiler if getattr(job, "profiler", None) is not None else Profiler()
-        self.profiler = prof
-        arrived = time.time()
-        prof.end("recoder.output")
-        prof.start("upscaler.upscale")
-        try:
+
+        def host_job():
             shape, landed = self._host_job(hf)
-        finally:
-            prof.end("upscaler.upscale")
-        self._host_jobs += 1
-        answer_frames = HostFrames(slot=hf.slot, out_slot=hf.out_slot, shape=shape, result=True)
-        if landed is not None:
-            self._lag_now = max(getattr(self, "_lag_now", 0), 1)   # one more job is enqueued before this result is waited for: the copies hide under it
-            self._pending[id(answer_frames)] = (answer_frames, landed, "host")
+            self._host_jobs += 1
+            frames = HostFrames(slot=hf.slot, out_slot=hf.out_slot, shape=shape, result=True)
+            if landed is not None:
+                self._hold_host(frames, landed)
+            return frames
+
+        frames, elapsed, prof = self._run_job(job, host_job)
         prof.set("upscaler.input.peer_copies", self._peer_copies)
-        prof.start("upscaler.output")
-        return answer(job, answer_frames, time.time() - arrived, prof)
+        return answer(job, frames, elapsed, prof)
+
+    def _hold_host(self, frames, landed) -> None:
+        self._held.hold(frames, landed, HOST)
+        self._lag_now = max(self._lag_now, 1)   # one more job is enqueued before this result is waited for: the copies hide under it
 
     def start(self) -> None:
         if self.host_results and self.result_ring is None:   # (here, in the caller's process: the ring must exist before the worker does)
@@ -372,8 +327,6 @@ class HipUpscalerService(BaseUpscalerService):
                 self._warned_big = True
                 log(f"host_results: a result of {tuple(out.shape)} does not fit a {ring.slot_bytes}-byte slot (host_result_bytes) - it stays on the device")
             return entry
-        if not hasattr(self, "_s_out"):
-            self._s_out = torch.cuda.Stream(self.torch_device)
         if not getattr(self, "_result_ring_pinned", False):
             self._result_ring_pinned = True
             try:
@@ -382,18 +335,13 @@ class HipUpscalerService(BaseUpscalerService):
                 log(f"WARNING: {e}: host results go through UNPINNED memory")
         slot = self._result_slot = (getattr(self, "_result_slot", -1) + 1) % ring.slots
         dst = ring.view(slot, tuple(out.shape))
-        rec = self._pending.pop(id(out), None)
-        cur = torch.cuda.current_stream(self.torch_device)
-        done = rec[1] if rec is not None else cur.record_event()
-        with torch.cuda.stream(self._s_out):
-            self._s_out.wait_event(done)
-            dst.copy_(out, non_blocking=True)
-            landed = self._s_out.record_event()
-        out.record_stream(self._s_out)
+        done = self._held.pop_event(out)   # (job-set path: the result is ordered on its set's stream, not on the current one)
+        if done is None:
+            done = torch.cuda.current_stream(self.torch_device).record_event()
+        landed = self._io.copy_out(out, dst, done)
         # on_queue runs in this process: it gets the tensor; the result queue gets the 100-byte handle that unpickles as the same view
         entry.frames = dst if self.on_queue is not None else RingView(ring, slot, out.shape)
-        self._pending[id(entry.frames)] = (entry.frames, landed, "host")
-        self._lag_now = max(getattr(self, "_lag_now", 0), 1)
+        self._hold_host(entry.frames, landed)
         return entry
 
     def _overlap_active(self) -> bool:
@@ -522,22 +470,15 @@ class HipUpscalerService(BaseUpscalerService):
 
     def proc_before_deliver(self, entry):
         self._retire()
-        # a result computed on a job set's own stream: the current stream - on which the result tensor is handed to the consumer
-        # (on_queue, or the IPC event torch records when the tensor is pickled into the result queue) - waits for it here
-        pending = getattr(self, "_pending", None)
-        rec = pending.pop(id(entry.frames), None) if pending and getattr(entry, "frames", None) is not None else None
-        if rec is not None and len(rec) > 2:
-            rec[1].synchronize()     # a host result: the consumer reads host memory (a ring slot, possibly from another process) - the bytes must have landed
-        elif rec is not None:
-            torch.cuda.current_stream(self.torch_device).wait_event(rec[1])
+        # a result computed on a job set's own stream: the current stream - on which the result tensor is handed to the consumer (on_queue, or
+        # the IPC event torch records when the tensor is pickled into the result queue) - waits for it here; a host result has landed after this
+        self._held.release(entry)
 
     def proc_deliver_lag(self) -> int:
-        return getattr(self, "_lag_now", 0)   # set by upscale() from the path the NEWEST job took
+        return self._lag_now
 
     def proc_result_ready(self, entry) -> bool:
-        pending = getattr(self, "_pending", None)
-        rec = pending.get(id(entry.frames)) if pending and getattr(entry, "frames", None) is not None else None
-        return rec is None or rec[1].query()
+        return self._held.ready(entry)
 
     def proc_cleanup(self):
         pass
@@ -594,7 +535,7 @@ class HipUpscalerService(BaseUpscalerService):
         self._inflight.append((done, frames))
         out.record_stream(cur)
         if getattr(self, "_in_worker", False):
-            self._pending[id(out)] = (out, done)   # proc_before_deliver makes the current stream wait, one job later
+            self._held.hold(out, done, DEVICE)   # proc_before_deliver makes the current stream wait, one job later
         elif wait:
             cur.wait_event(done)
         return out

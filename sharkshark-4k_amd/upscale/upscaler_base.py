@@ -73,18 +73,23 @@ class BaseUpscalerService(BaseService):
     def upscale(self, frames: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError("an upscaler service implements upscale(uint8 NHWC) -> uint8 NHWC")
 
-    def proc_job_recieved(self, job):  # (sic) the reference's spelling
-        # only what the reference's own objects offer is used on `job` and its profiler (upscaler_base.py:17-24, util/profiler.py:3-26:
-        # the six fields; set / start / end / data): the callers build both from THEIR modules (pipeline.py:95-100, image_pipeline.py:280-287)
+    def _run_job(self, job, fn):
+        """The spans of one job around ``fn()`` (its device work); returns ``(what fn returned, seconds since the job arrived, profiler)`` -
+        ``answer``'s last three arguments.  Only what the reference's own objects offer is used on ``job`` and its profiler
+        (upscaler_base.py:17-24, util/profiler.py:3-26: the six fields; set / start / end / data): the callers build both from THEIR
+        modules (pipeline.py:95-100, image_pipeline.py:280-287)."""
         prof = job.profiler if getattr(job, "profiler", None) is not None else Profiler()
         self.profiler = prof  # upscale() implementations add their own spans to the job's profiler
         arrived = time.time()
         prof.end("recoder.output")
         prof.start("upscaler.upscale")
         try:
-            upscaled = self.upscale(job.frames)
+            result = fn()
         finally:
             prof.end("upscaler.upscale")
         elapsed = time.time() - arrived
         prof.start("upscaler.output")
-        return answer(job, upscaled, elapsed, prof)
+        return result, elapsed, prof
+
+    def proc_job_recieved(self, job):  # (sic) the reference's spelling
+        return answer(job, *self._run_job(job, lambda: self.upscale(job.frames)))

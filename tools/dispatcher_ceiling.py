@@ -39,7 +39,6 @@ class NoopWorker(HipUpscalerService):
 
     def _init_job_sets(self):
         self.deliver_lag = 0
-        self._pending = {}
 
     def _host_job(self, hf):
         oh, ow = self.out_hw(hf.shape[1], hf.shape[2])
