@@ -234,7 +234,7 @@ int ss4k_op_cv_area_resize_u8(ss4k_ctx* ctx, const uint8_t* in_nhwc_dev, uint8_t
 /* ---- the frame-recurrent upscaler: EGVSR's FRNet x4 (model/egvsr/egvsr.py:146-212), the network behind EgvsrUpscalerService
  * (egvsr_upscaler.py:145-212).  An object of its own, not a model kind: a step takes three tensors and frame t needs frame t - 1's output,
  * so there are no frame lanes and no job sets.  FRNet(in_nc=3, out_nc=3, nf=num_feat, nb=num_block, degradation='BD', scale=4)
- * (egvsr_upscaler.py:26): FNet (egvsr.py:12-78), 4 x BicubicUpsample(4) of the flow (utils/net_utils.py:112-165), backward_warp of the previous
+ * (egvsr_upscaler.py:26; degradation 'BI': ss4k_frvsr_create_ex below): FNet (egvsr.py:12-78), 4 x BicubicUpsample(4) of the flow (utils/net_utils.py:112-165), backward_warp of the previous
  * output (net_utils.py:50-93), space-to-depth (egvsr.py:203-208), SRNet (egvsr.py:99-143).  SS4K_F16: fp16 activations with fp32 accumulation;
  * the flow, hr_prev and hr_curr stay fp32 in both dtypes. */
 typedef struct ss4k_frvsr ss4k_frvsr;
@@ -269,6 +269,20 @@ size_t ss4k_frvsr_param_count_as(const ss4k_frvsr_desc* desc, int generator);
 int ss4k_frvsr_create_as(ss4k_ctx* ctx, const ss4k_frvsr_desc* desc, int generator, int route_flags, const float* host_weights, size_t n_floats,
                          ss4k_frvsr** out);
 int ss4k_frvsr_generator(const ss4k_frvsr* m);
+/* The degradation the generator was trained for: FRNet's `degradation` argument, which picks the up-sampling function (utils/net_utils.py:96-108).
+ * SS4K_FRVSR_BD: BicubicUpsample(4) - everything above.  SS4K_FRVSR_BI: F.interpolate(scale_factor=4, mode='bilinear', align_corners=False),
+ * the reference classes' own default.  The function up-samples the LR flow before the warp (both generators) and is TecoGAN's skip
+ * conv_out + upsample_func(lr_curr); both run on kernels of their own (csrc/frvsr_bi.hip).  With 'BI' the function is no module, so the
+ * state_dict holds neither upsample_func.kernels nor srnet.upsample_func.kernels: the blob is still the whole state_dict in key order, 44
+ * tensors and 32 scalars fewer, and a blob of the other degradation is refused by its size.  An unknown degradation: SS4K_EINVAL, and a count
+ * of 0.  Degradation SS4K_FRVSR_BD is ss4k_frvsr_param_count_as / ss4k_frvsr_create_as, bit for bit; either degradation goes with either
+ * generator and either route of the transposed layers, and every other ss4k_frvsr_* entry point works on the object unchanged (stage 4 stays
+ * the flow x4 + warp, stage 9 the skip). */
+enum { SS4K_FRVSR_BD = 0, SS4K_FRVSR_BI = 1 };
+size_t ss4k_frvsr_param_count_ex(const ss4k_frvsr_desc* desc, int generator, int degradation);
+int ss4k_frvsr_create_ex(ss4k_ctx* ctx, const ss4k_frvsr_desc* desc, int generator, int degradation, int route_flags, const float* host_weights,
+                         size_t n_floats, ss4k_frvsr** out);
+int ss4k_frvsr_degradation(const ss4k_frvsr* m);
 /* Replaces `self.model(lr_curr, self.lr_prev, self.hr_prev)` (egvsr_upscaler.py:204) = FRNet.forward (egvsr.py:180-212): lr_curr, lr_prev
  * (n, 3, h, w), hr_prev (n, 3, 4 h, 4 w) -> hr_out (n, 3, 4 h, 4 w), contiguous fp32 NCHW on the device; the n items are independent streams.
  * Stateless.  h, w >= 8 (the reference's reflect pad fails below that): SS4K_EINVAL otherwise. */

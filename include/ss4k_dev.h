@@ -103,6 +103,21 @@ int ss4k_dev_op_frvsr_pack_lr_items(ss4k_ctx* ctx, const float* const* lr_curr, 
 int ss4k_dev_op_frvsr_frames_out_items(ss4k_ctx* ctx, const float* const* hr, uint8_t* const* out, int n, int H, int W, int oh, int ow,
                                        void* hip_stream);
 
+/* ---- launchers of degradation 'BI' (csrc/frvsr_bi.hip): the twins of ss4k_op_bicubic_upsample4, ss4k_dev_op_frvsr_warp_s2d_planes[_items]
+ * and of the bicubic skip of a TecoGAN tail, with F.interpolate(scale_factor=4, mode='bilinear', align_corners=False) as the up-sampling
+ * function.  Same conventions; their routes are reported as "frvsr_bi::...".  What tests/test_gpu_frvsr_bi_glue_budget.py bounds.  (Their
+ * prefix is ss4k_dev_op_frvsrbi_: the ss4k_dev_op_frvsr_ set is the twelve launchers of csrc/frvsr.hip, and a test counts them.) */
+/* (planes, h, w) -> (planes, 4 h, 4 w), fp32 */
+int ss4k_dev_op_frvsrbi_bilinear_upsample4(ss4k_ctx* ctx, const float* in, float* out, int planes, int h, int w, void* hip_stream);
+int ss4k_dev_op_frvsrbi_warp_s2d_planes(ss4k_ctx* ctx, const float* lr_flow, const float* hr_prev, void* out, int half, int n, int h, int w,
+                                         void* hip_stream);
+int ss4k_dev_op_frvsrbi_warp_s2d_planes_items(ss4k_ctx* ctx, const float* lr_flow, const float* const* hr_prev, void* out, int half, int n,
+                                               int h, int w, void* hip_stream);
+/* conv (n, 3, 4 h, 4 w) + bilinear x4 of lr (n, 3, h, w) [items: lr[i] (3, h, w)] -> out (n, 3, 4 h, 4 w) [items: out[i]], fp32 */
+int ss4k_dev_op_frvsrbi_bilinear4_add(ss4k_ctx* ctx, const float* conv, const float* lr, float* out, int n, int h, int w, void* hip_stream);
+int ss4k_dev_op_frvsrbi_bilinear4_add_items(ss4k_ctx* ctx, const float* conv, const float* const* lr, float* const* out, int n, int h, int w,
+                                          void* hip_stream);
+
 /* ss4k_frvsr_step (include/ss4k.h) on a contiguous batch of n items, with the two tensors between FNet, the warp and SRNet copied out for
  * EVERY item: flow_out (n, 2, h, w) = the padded LR flow, s2d_out (n, 48, h, w) = the warped, space-to-depth hr_prev as SRNet's first conv read
  * it (an fp16 model: exactly the fp16 values), both fp32 device memory of the caller.  The public taps describe only the last item of a round.

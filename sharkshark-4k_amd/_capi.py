@@ -36,6 +36,7 @@ SYMBOLS = [
     "ss4k_frvsr_upscaler_create_streams", "ss4k_frvsr_upscale_streams", "ss4k_frvsr_upscaler_reset_stream", "ss4k_frvsr_upscaler_state_bytes",
     "ss4k_frvsr_upscale_streams_at",
     "ss4k_frvsr_param_count_as", "ss4k_frvsr_create_as", "ss4k_frvsr_generator",
+    "ss4k_frvsr_param_count_ex", "ss4k_frvsr_create_ex", "ss4k_frvsr_degradation",
 ]
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
@@ -52,6 +53,9 @@ DEV_SYMBOLS = [
     "ss4k_dev_op_frvsr_warp_s2d_planes", "ss4k_dev_op_frvsr_warp_s2d_planes_items", "ss4k_dev_op_frvsr_ps4_conv_tail",
     "ss4k_dev_op_frvsr_ps4_conv_tail_items", "ss4k_dev_op_frvsr_planes_to_nchw", "ss4k_dev_op_frvsr_clamp01_to",
     "ss4k_dev_op_frvsr_frames_in_items", "ss4k_dev_op_frvsr_pack_lr_items", "ss4k_dev_op_frvsr_frames_out_items",
+    # the launchers of csrc/frvsr_bi.hip, degradation 'BI' (tests/test_gpu_frvsr_bi_glue_budget.py)
+    "ss4k_dev_op_frvsrbi_bilinear_upsample4", "ss4k_dev_op_frvsrbi_warp_s2d_planes", "ss4k_dev_op_frvsrbi_warp_s2d_planes_items",
+    "ss4k_dev_op_frvsrbi_bilinear4_add", "ss4k_dev_op_frvsrbi_bilinear4_add_items",
     # a whole step with every item's flow and warped space-to-depth tensor copied out (tests/test_gpu_frvsr_budget.py)
     "ss4k_dev_frvsr_step_taps",
     # the tail of a TecoGAN generator alone, and the host-side embedding of its transposed layers (tests/test_gpu_tecogan_tail.py)
@@ -176,6 +180,12 @@ def load(path: str) -> C.CDLL:
         L.ss4k_dev_op_frvsr_pack_lr_items.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
         L.ss4k_dev_op_frvsr_frames_out_items.argtypes = [vp, vp, vp, i, i, i, i, i, vp]
         L.ss4k_dev_glue_routes_read.argtypes = [i, C.c_char_p, sz, C.POINTER(C.c_int64)]
+    if hasattr(L, "ss4k_dev_op_frvsrbi_bilinear_upsample4"):   # csrc/frvsr_bi.hip
+        L.ss4k_dev_op_frvsrbi_bilinear_upsample4.argtypes = [vp, vp, vp, i, i, i, vp]
+        L.ss4k_dev_op_frvsrbi_warp_s2d_planes.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
+        L.ss4k_dev_op_frvsrbi_warp_s2d_planes_items.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
+        L.ss4k_dev_op_frvsrbi_bilinear4_add.argtypes = [vp, vp, vp, vp, i, i, i, vp]
+        L.ss4k_dev_op_frvsrbi_bilinear4_add_items.argtypes = [vp, vp, vp, vp, i, i, i, vp]
     if hasattr(L, "ss4k_dev_frvsr_step_taps"):  # dev library only
         L.ss4k_dev_frvsr_step_taps.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
     if hasattr(L, "ss4k_dev_guard_check"):  # dev library only: guard mode
@@ -224,6 +234,10 @@ def load(path: str) -> C.CDLL:
         L.ss4k_frvsr_param_count_as.argtypes = [C.POINTER(FrvsrDesc), i]; L.ss4k_frvsr_param_count_as.restype = sz
         L.ss4k_frvsr_create_as.argtypes = [vp, C.POINTER(FrvsrDesc), i, i, vp, sz, C.POINTER(vp)]
         L.ss4k_frvsr_generator.argtypes = [vp]
+    if hasattr(L, "ss4k_frvsr_create_ex"):   # (absent from builds before degradation 'BI')
+        L.ss4k_frvsr_param_count_ex.argtypes = [C.POINTER(FrvsrDesc), i, i]; L.ss4k_frvsr_param_count_ex.restype = sz
+        L.ss4k_frvsr_create_ex.argtypes = [vp, C.POINTER(FrvsrDesc), i, i, i, vp, sz, C.POINTER(vp)]
+        L.ss4k_frvsr_degradation.argtypes = [vp]
     if hasattr(L, "ss4k_dev_frvsr_tail_taps"):
         L.ss4k_dev_frvsr_tail_taps.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.ss4k_dev_frvsr_embed_convt.argtypes = [vp, i, vp, sz]
@@ -616,6 +630,7 @@ FRVSR_MAX_STREAMS = 64   # SS4K_FRVSR_MAX_STREAMS (include/ss4k.h)
 FRV_STAGES = ("fnet_conv", "srnet_conv", "pool_up", "flow_finish", "warp", "tail", "glue")
 FRV_STAGES_TECOGAN = FRV_STAGES + ("convt", "conv_out", "skip")   # stages 7..9: a TecoGAN generator's tail ("tail" stays 0 there)
 FRVSR_EGVSR, FRVSR_TECOGAN = 0, 1   # SS4K_FRVSR_EGVSR / SS4K_FRVSR_TECOGAN
+FRVSR_BD, FRVSR_BI = 0, 1   # SS4K_FRVSR_BD / SS4K_FRVSR_BI: FRNet's `degradation`, the up-sampling function (bicubic | bilinear x4)
 FRVSR_CONVT_EMBEDDED, FRVSR_CONVT_PHASE = 1, 4   # route_flags: SS4K_FRVSR_CONVT_* (0: the library's choice, today the embedded route)
 
 
@@ -625,7 +640,15 @@ def make_frvsr_desc(dtype: int = F32, num_feat: int = 64, num_block: int = 10, f
     return d
 
 
-def frvsr_param_count(desc: FrvsrDesc, generator: int = FRVSR_EGVSR) -> int:
+def frvsr_degradation(degradation) -> int:
+    """'BD' | 'BI' | 0 | 1 -> SS4K_FRVSR_BD | SS4K_FRVSR_BI; anything else raises ValueError (weights.frvsr_degradation)."""
+    from . import weights as W
+    return W.FRVSR_DEGRADATIONS[W.frvsr_degradation(degradation)]
+
+
+def frvsr_param_count(desc: FrvsrDesc, generator: int = FRVSR_EGVSR, degradation: int = FRVSR_BD) -> int:
+    if degradation != FRVSR_BD:
+        return int(lib().ss4k_frvsr_param_count_ex(C.byref(desc), int(generator), int(degradation)))
     if generator == FRVSR_EGVSR:
         return int(lib().ss4k_frvsr_param_count(C.byref(desc)))
     return int(lib().ss4k_frvsr_param_count_as(C.byref(desc), int(generator)))
@@ -633,14 +656,19 @@ def frvsr_param_count(desc: FrvsrDesc, generator: int = FRVSR_EGVSR) -> int:
 
 class Frvsr:
     """ss4k_frvsr: EGVSR's FRNet x4 (``generator=0``) or TecoGAN's (``generator=1``, tecogan_nets.py:101-202) resident on one GPU; callable like
-    the reference's ``self.model(lr_curr, lr_prev, hr_prev)`` (egvsr_upscaler.py:204)."""
+    the reference's ``self.model(lr_curr, lr_prev, hr_prev)`` (egvsr_upscaler.py:204).  ``degradation``: FRVSR_BD (the entry points from before
+    there was a choice) or FRVSR_BI (``ss4k_frvsr_create_ex``)."""
 
-    def __init__(self, ctx: Context, desc: FrvsrDesc, flat_weights: np.ndarray, generator: int = FRVSR_EGVSR, route_flags: int = 0):
-        self.ctx, self.desc, self.generator = ctx, desc, int(generator)
+    def __init__(self, ctx: Context, desc: FrvsrDesc, flat_weights: np.ndarray, generator: int = FRVSR_EGVSR, route_flags: int = 0,
+                 degradation: int = FRVSR_BD):
+        self.ctx, self.desc, self.generator, self.degradation = ctx, desc, int(generator), int(degradation)
         w = np.ascontiguousarray(flat_weights, dtype=np.float32)
         h = C.c_void_p()
         with torch.cuda.device(ctx.device):
-            if self.generator == FRVSR_EGVSR and not route_flags:
+            if self.degradation != FRVSR_BD:
+                _check(lib().ss4k_frvsr_create_ex(ctx._h, C.byref(desc), self.generator, self.degradation, int(route_flags),
+                                                  w.ctypes.data_as(C.c_void_p), w.size, C.byref(h)))
+            elif self.generator == FRVSR_EGVSR and not route_flags:
                 _check(lib().ss4k_frvsr_create(ctx._h, C.byref(desc), w.ctypes.data_as(C.c_void_p), w.size, C.byref(h)))
             else:
                 _check(lib().ss4k_frvsr_create_as(ctx._h, C.byref(desc), self.generator, int(route_flags), w.ctypes.data_as(C.c_void_p), w.size,

@@ -81,15 +81,33 @@ def bsvd_from_checkpoint(ckpt: Mapping, **kw):
     return _ordered(out, W.bsvd_keys(**kw), "BSVD")
 
 
-def egvsr_from_checkpoint(ckpt: Mapping, nb: int = 10):
+def frvsr_check_degradation(sd: Mapping, what: str, degradation) -> str:
+    """The refusal ``load_state_dict(strict=True)`` gives a state_dict of the other degradation: BicubicUpsample's two ``kernels`` buffers
+    are in a 'BD' state_dict and in no 'BI' one (utils/net_utils.py:96-108).  Returns the degradation's name."""
+    deg = W.frvsr_degradation(degradation)
+    kernels = [k for k in W.FRVSR_KERNELS if k in sd]
+    if deg == "BI" and kernels:
+        raise KeyError(f"{what}(degradation='BI'): unexpected {kernels} in the state_dict - it holds a generator trained with degradation='BD'")
+    if deg == "BD" and len(kernels) < len(W.FRVSR_KERNELS):
+        missing = [k for k in W.FRVSR_KERNELS if k not in sd]
+        raise KeyError(f"{what}(degradation='BD'): the state_dict lacks {missing} - it holds a generator trained with degradation='BI'")
+    return deg
+
+
+def _frvsr_ordered(sd: Mapping, keys, what: str, degradation):
+    frvsr_check_degradation(sd, what, degradation)
+    return _ordered(sd, keys, what)
+
+
+def egvsr_from_checkpoint(ckpt: Mapping, nb: int = 10, degradation="BD"):
     """``torch.load('EGVSR_iter420000.pth')`` is FRNet's bare state_dict (``egvsr_upscaler.py:25-27``); the entries ``forward`` never
-    reads (``srnet.conv_up.*``, the two ``upsample_func.kernels`` buffers) stay in the table: the blob is the whole state_dict."""
+    reads (``srnet.conv_up.*``, with 'BD' the two ``upsample_func.kernels`` buffers) stay in the table: the blob is the whole state_dict."""
     sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
-    return _ordered(sd, W.frnet_keys(nb), "FRNet")
+    return _frvsr_ordered(sd, W.frnet_keys(nb, degradation), "FRNet", degradation)
 
 
-def tecogan_from_checkpoint(ckpt: Mapping, nb: int = W.TECOGAN_NB):
+def tecogan_from_checkpoint(ckpt: Mapping, nb: int = W.TECOGAN_NB, degradation="BD"):
     """A TecoGAN generator checkpoint is ``FRNet``'s bare state_dict too (tecogan_nets.py:101-202, ``define_generator``'s ``name: frnet``); the
     blob is the whole state_dict in key order."""
     sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
-    return _ordered(sd, W.tecogan_keys(nb), "TecoGAN FRNet")
+    return _frvsr_ordered(sd, W.tecogan_keys(nb, degradation), "TecoGAN FRNet", degradation)

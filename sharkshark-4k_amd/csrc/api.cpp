@@ -245,17 +245,25 @@ size_t ss4k_frvsr_param_count_as(const ss4k_frvsr_desc* d, int generator) { retu
 int ss4k_frvsr_create(ss4k_ctx* ctx, const ss4k_frvsr_desc* d, const float* w, size_t n, ss4k_frvsr** out) {
   return ss4k_frvsr_create_as(ctx, d, SS4K_FRVSR_EGVSR, 0, w, n, out);
 }
+size_t ss4k_frvsr_param_count_ex(const ss4k_frvsr_desc* d, int generator, int degradation) { return d ? frvsr_param_count(*d, generator, degradation) : 0; }
 int ss4k_frvsr_generator(const ss4k_frvsr* m) { return m ? m->f.generator : -1; }
+int ss4k_frvsr_degradation(const ss4k_frvsr* m) { return m ? m->f.degradation : -1; }
 int ss4k_frvsr_create_as(ss4k_ctx* ctx, const ss4k_frvsr_desc* d, int generator, int route_flags, const float* w, size_t n, ss4k_frvsr** out) {
+  return ss4k_frvsr_create_ex(ctx, d, generator, SS4K_FRVSR_BD, route_flags, w, n, out);
+}
+int ss4k_frvsr_create_ex(ss4k_ctx* ctx, const ss4k_frvsr_desc* d, int generator, int degradation, int route_flags, const float* w, size_t n,
+                         ss4k_frvsr** out) {
   return guard([&] {
     SS4K_REQUIRE(ctx && d && w && out, "ss4k_frvsr_create: NULL argument");
     SS4K_REQUIRE(generator == SS4K_FRVSR_EGVSR || generator == SS4K_FRVSR_TECOGAN, "ss4k_frvsr_create_as: generator must be SS4K_FRVSR_EGVSR or SS4K_FRVSR_TECOGAN");
+    SS4K_REQUIRE(degradation == SS4K_FRVSR_BD || degradation == SS4K_FRVSR_BI, "ss4k_frvsr_create_ex: degradation must be SS4K_FRVSR_BD or SS4K_FRVSR_BI");
     SS4K_REQUIRE((route_flags & ~(SS4K_FRVSR_CONVT_EMBEDDED | SS4K_FRVSR_CONVT_PHASE)) == 0, "ss4k_frvsr_create_as: unknown route flags");
     SS4K_REQUIRE(generator == SS4K_FRVSR_TECOGAN || route_flags == 0, "ss4k_frvsr_create_as: the route flags belong to the TecoGAN generator");
     SS4K_HIP(hipSetDevice(ctx->device));
     auto m = std::make_unique<ss4k_frvsr>();
-    m->f.ctx = ctx; m->f.desc = *d; m->f.generator = generator;
-    if (generator == SS4K_FRVSR_TECOGAN) m->f.tail = make_tecogan_tail(route_flags);
+    m->f.ctx = ctx; m->f.desc = *d; m->f.generator = generator; m->f.degradation = degradation;
+    if (generator == SS4K_FRVSR_TECOGAN) m->f.tail = make_tecogan_tail(route_flags, degradation);
+    if (degradation == SS4K_FRVSR_BI) m->f.warp = make_bilinear_warp();
     m->f.build(w, n);
 #ifdef SS4K_DEV
     for (DevBuf* b : {&m->f.flow_raw, &m->f.flow, &m->f.tap_s2d}) b->transient = true;   // guard mode: every step rewrites what it reads from these

@@ -216,6 +216,26 @@ int ss4k_dev_op_frvsr_frames_out_items(ss4k_ctx* c, const float* const* hr, uint
   SS4K_DEV_OP(c && hr && out && SS4K_DEV_ITEMS(n),
               op_frames_out_items(dev_items<FrvsrPtrs>(hr, n), dev_items<FrvsrFramesOut>(out, n), n, H, W, oh, ow, (hipStream_t)s));
 }
+// ---- the launchers of csrc/frvsr_bi.hip (degradation 'BI'; tests/test_gpu_frvsr_bi_glue_budget.py)
+int ss4k_dev_op_frvsrbi_bilinear_upsample4(ss4k_ctx* c, const float* in, float* out, int p, int h, int w, void* s) {
+  SS4K_DEV_OP(c && in && out, op_bilinear_upsample4(in, out, p, h, w, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsrbi_warp_s2d_planes(ss4k_ctx* c, const float* lr_flow, const float* hr_prev, void* out, int half, int n, int h, int w, void* s) {
+  SS4K_DEV_OP(c && lr_flow && hr_prev && out, SS4K_DEV_HALF(half, op_warp_s2d_bi_planes(lr_flow, hr_prev, (T*)out, n, h, w, (hipStream_t)s)));
+}
+int ss4k_dev_op_frvsrbi_warp_s2d_planes_items(ss4k_ctx* c, const float* lr_flow, const float* const* hr_prev, void* out, int half, int n, int h, int w,
+                                               void* s) {
+  SS4K_DEV_OP(c && lr_flow && hr_prev && out && SS4K_DEV_ITEMS(n),
+              const FrvsrPtrs t = dev_items<FrvsrPtrs>(hr_prev, n);
+              SS4K_DEV_HALF(half, op_warp_s2d_bi_planes_items(lr_flow, t, (T*)out, n, h, w, (hipStream_t)s)));
+}
+int ss4k_dev_op_frvsrbi_bilinear4_add(ss4k_ctx* c, const float* conv, const float* lr, float* out, int n, int h, int w, void* s) {
+  SS4K_DEV_OP(c && conv && lr && out, op_bilinear4_add(conv, lr, out, n, h, w, (hipStream_t)s));
+}
+int ss4k_dev_op_frvsrbi_bilinear4_add_items(ss4k_ctx* c, const float* conv, const float* const* lr, float* const* out, int n, int h, int w, void* s) {
+  SS4K_DEV_OP(c && conv && lr && out && SS4K_DEV_ITEMS(n),
+              op_bilinear4_add_items(conv, dev_items<FrvsrPtrs>(lr, n), dev_items<FrvsrPtrs>(out, n), n, h, w, (hipStream_t)s));
+}
 #undef SS4K_DEV_ITEMS
 #undef SS4K_DEV_HALF
 #undef SS4K_DEV_OP

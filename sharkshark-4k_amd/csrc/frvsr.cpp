@@ -19,17 +19,19 @@ static void validate_frvsr_desc(const ss4k_frvsr_desc& d) {
   for (int r : d.reserved) SS4K_REQUIRE(r == 0, "frvsr desc.reserved must be 0");
 }
 
-size_t frvsr_param_count(const ss4k_frvsr_desc& d, int generator) {
+size_t frvsr_param_count(const ss4k_frvsr_desc& d, int generator, int degradation) {
   try { validate_frvsr_desc(d); } catch (const Error&) { return 0; }
   if (generator != SS4K_FRVSR_EGVSR && generator != SS4K_FRVSR_TECOGAN) return 0;
+  if (degradation != SS4K_FRVSR_BD && degradation != SS4K_FRVSR_BI) return 0;
   const size_t nf = (size_t)d.num_feat;
-  size_t n = 16;                                                    // upsample_func.kernels
+  const size_t kernels = degradation == SS4K_FRVSR_BD ? 16 : 0;     // 'BI': the function is a functools.partial, not a module with a buffer
+  size_t n = kernels;                                               // upsample_func.kernels
   for (auto& c : FNET_CONVS) n += (size_t)c[0] * c[1] * 9 + c[0];
   n += nf * 51 * 9 + nf;                                            // srnet.conv_in.0
   n += (size_t)d.num_block * 2 * (nf * nf * 9 + nf);                // srnet.resblocks.*.conv.{0,2}
   n += 2 * (nf * nf * 9 + nf);                                      // srnet.conv_up.{0,2}: in the state_dict; EGVSR's forward does not use them
   n += generator == SS4K_FRVSR_TECOGAN ? 3 * nf * 9 + 3 : 3 * 4 * 9 + 3;   // srnet.conv_out: Conv2d(nf, 3) at (4 h, 4 w) (tecogan_nets.py:128) | Conv2d(4, 3)
-  n += 16;                                                          // srnet.upsample_func.kernels
+  n += kernels;                                                     // srnet.upsample_func.kernels
   return n;
 }
 
@@ -37,12 +39,15 @@ void Frvsr::build(const float* w, size_t n) {
   validate_frvsr_desc(desc);
   SS4K_REQUIRE(generator == SS4K_FRVSR_EGVSR || generator == SS4K_FRVSR_TECOGAN, "frvsr: generator must be SS4K_FRVSR_EGVSR or SS4K_FRVSR_TECOGAN");
   SS4K_REQUIRE((generator == SS4K_FRVSR_EGVSR) == (tail == nullptr), "internal: a generator other than EGVSR brings its tail (ss4k_frvsr_create_as)");
-  SS4K_REQUIRE(n == frvsr_param_count(desc, generator), "weight blob size does not match the frvsr description");
+  SS4K_REQUIRE(degradation == SS4K_FRVSR_BD || degradation == SS4K_FRVSR_BI, "frvsr: degradation must be SS4K_FRVSR_BD or SS4K_FRVSR_BI");
+  SS4K_REQUIRE((degradation == SS4K_FRVSR_BD) == (warp == nullptr), "internal: a degradation other than 'BD' brings its warp stage (ss4k_frvsr_create_ex)");
+  SS4K_REQUIRE(n == frvsr_param_count(desc, generator, degradation), "weight blob size does not match the frvsr description");
+  const size_t kernels = degradation == SS4K_FRVSR_BD ? 16 : 0;
   net.ctx = ctx;
   net.desc = ss4k_model_desc{}; net.desc.kind = SS4K_SRVGG; net.desc.dtype = desc.dtype; net.desc.scale = 4; net.desc.num_feat = desc.num_feat;
   const int nf = desc.num_feat;
   ParamCursor pc{w, n};
-  (void)pc.take(16);
+  (void)pc.take(kernels);
   fnet0 = 0;
   for (int i = 0; i < 14; ++i)   // torch.cat([x1, x2], 1) (egvsr.py:67): two input segments of one plane each
     net.add_conv(pc, FNET_CONVS[i][0], FNET_CONVS[i][1], i == 0 ? net.spec_concat(3, 3) : net.spec_plain(FNET_CONVS[i][1]), false);
@@ -62,7 +67,7 @@ void Frvsr::build(const float* w, size_t n) {
     tail_wb.ensure(wb.size() * 4);
     SS4K_HIP(hipMemcpy(tail_wb.ptr, wb.data(), wb.size() * 4, hipMemcpyHostToDevice));
   }
-  (void)pc.take(16);
+  (void)pc.take(kernels);
   SS4K_REQUIRE(pc.pos == n, "internal: weight cursor did not consume the blob");
 }
 
@@ -186,6 +191,7 @@ void Frvsr::run(const float* lr_curr, const float* lr_prev, const float* hr_prev
   Tens Wp = net.act_planes(slot++, px, 3);
   stage(FRV_WARP, [&] {
     if (plan) return;
+    if (warp) { warp->run(*this, FrvsrWarp::Call{flow.as<float>(), hr_prev, items ? items->hr_prev : nullptr, Wp.p, n, h, w}, st); return; }
     if (items) {
       if (f16) op_warp_s2d_planes_items<__half>(flow.as<float>(), *items->hr_prev, reinterpret_cast<__half*>(Wp.p), n, h, w, st);
       else op_warp_s2d_planes_items<float>(flow.as<float>(), *items->hr_prev, reinterpret_cast<float*>(Wp.p), n, h, w, st);

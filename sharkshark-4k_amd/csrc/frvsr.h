@@ -40,6 +40,16 @@ template <typename T> void op_ps4_conv_tail_items(const T* in, const float* wb, 
 void op_bicubic4_add(const float* conv, const float* lr, float* out, int n, int h, int w, hipStream_t st);
 // ... item i reading lr.p[i] (3, h, w) and writing out.p[i] (3, 4 h, 4 w); conv stays one contiguous batch: bit-identical; n <= 64
 void op_bicubic4_add_items(const float* conv, const FrvsrPtrs& lr, const FrvsrPtrs& out, int n, int h, int w, hipStream_t st);
+// ---- kernels of degradation 'BI' (frvsr_bi.hip): get_upsampling_func's F.interpolate(scale_factor=4, 'bilinear', align_corners=False)
+// (utils/net_utils.py:96-108) in the places of BicubicUpsample(4).  No file of tests/hostcheck/PRODUCT_SOURCES names them
+// (planes, h, w) -> (planes, 4 h, 4 w), fp32
+void op_bilinear_upsample4(const float* in, float* out, int planes, int h, int w, hipStream_t st);
+// op_warp_s2d_planes[_items] with 4 * bilinear x4 of the flow: the same warp, the same records, the same requirements and grid
+template <typename T> void op_warp_s2d_bi_planes(const float* lr_flow, const float* hr_prev, T* out, int n, int h, int w, hipStream_t st);
+template <typename T> void op_warp_s2d_bi_planes_items(const float* lr_flow, const FrvsrPtrs& hr_prev, T* out, int n, int h, int w, hipStream_t st);
+// op_bicubic4_add[_items] with the bilinear skip: op_bilinear_upsample4's value bit for bit, then one rounded add
+void op_bilinear4_add(const float* conv, const float* lr, float* out, int n, int h, int w, hipStream_t st);
+void op_bilinear4_add_items(const float* conv, const FrvsrPtrs& lr, const FrvsrPtrs& out, int n, int h, int w, hipStream_t st);
 // planes of T -> fp32 NCHW (n, channels, h, w) (the parity taps)
 template <typename T> void op_planes_to_nchw(const T* in, float* out, int n, int channels, int h, int w, hipStream_t st);
 // clamp(x, 0, 1) into another tensor (egvsr_upscaler.py:209: the recurrent state keeps the unclamped one)
@@ -55,8 +65,9 @@ template <typename T> void op_pack_lr_items(const FrvsrPtrs& lr_curr, const Frvs
 // uint8 HWC (oh, ow, 3) at out.p[i] (op_clamp01_to + op_area + op_f32nchw_to_u8nhwc, or the last alone); no fp32 intermediate in memory
 void op_frames_out_items(const FrvsrPtrs& hr, const FrvsrFramesOut& out, int n, int H, int W, int oh, int ow, hipStream_t st);
 
-// 0 for a description or a generator that is refused.  generator: SS4K_FRVSR_EGVSR | SS4K_FRVSR_TECOGAN (include/ss4k.h)
-size_t frvsr_param_count(const ss4k_frvsr_desc& d, int generator = SS4K_FRVSR_EGVSR);
+// 0 for a description, a generator or a degradation that is refused.  generator: SS4K_FRVSR_EGVSR | SS4K_FRVSR_TECOGAN, degradation:
+// SS4K_FRVSR_BD | SS4K_FRVSR_BI (include/ss4k.h).  'BI': the two 16-scalar `kernels` buffers are not in the state_dict
+size_t frvsr_param_count(const ss4k_frvsr_desc& d, int generator = SS4K_FRVSR_EGVSR, int degradation = SS4K_FRVSR_BD);
 
 // stages of a step, for the per-stage event timing (ss4k_frvsr_prof_read)
 // (7..9 are TecoGAN's tail: its two transposed convolutions, conv_out, the bicubic skip; FRV_TAIL is EGVSR's tail alone)
@@ -76,6 +87,18 @@ struct FrvsrTail {
   virtual void run(Frvsr& f, const Call& c, hipStream_t st) = 0;
 };
 
+// The FRV_WARP stage when it is not 'BD''s (which Frvsr::run holds itself): flow x4 + warp + space-to-depth with another up-sampling function.
+// Like a tail, it lives in a file of its own with the launchers it calls (frvsr_bi.cpp), and ss4k_frvsr_create_ex installs it
+struct FrvsrWarp {
+  virtual ~FrvsrWarp() = default;
+  // flow: the padded LR flow (n, 2, h, w) fp32.  hr_prev: the contiguous batch, or (items != null) the per-item table.  out: three planes of
+  // the model's dtype at (n, h, w).  Never called while the step only plans
+  struct Call { const float* flow; const float* hr_prev; const FrvsrPtrs* items; char* out; int n, h, w; };
+  virtual void run(Frvsr& f, const Call& c, hipStream_t st) = 0;
+};
+// degradation 'BI' (frvsr_bi.cpp)
+std::unique_ptr<FrvsrWarp> make_bilinear_warp();
+
 // ---- conv_up2.hip: ConvTranspose2d(64, 64, 3, 2, 1, output_padding=1) + bias + ReLU on planes, (N, H, W) -> (N, 2 H, 2 W), by output phase
 constexpr int CONVT_TH = 8, CONVT_TW = 32;   // input pixels per workgroup tile
 struct ConvtArgs {
@@ -90,8 +113,9 @@ std::vector<uint8_t> pack_convt3x3s2(const float* wt, int dtype);
 // max_workgroups > 0 caps the persistent grid (dev: a walk of more tiles than workgroups at small shapes)
 void launch_convt3x3s2(ss4k_ctx* ctx, const ConvtArgs& a, int dtype, int max_workgroups, hipStream_t st);
 
-// TecoGAN's tail (frvsr_teco.cpp).  route_flags: SS4K_FRVSR_CONVT_* (include/ss4k.h); unknown bits are refused
-std::unique_ptr<FrvsrTail> make_tecogan_tail(int route_flags);
+// TecoGAN's tail (frvsr_teco.cpp).  route_flags: SS4K_FRVSR_CONVT_* (include/ss4k.h); unknown bits are refused.  degradation: which
+// up-sampling of lr_curr the skip adds; either goes with either route
+std::unique_ptr<FrvsrTail> make_tecogan_tail(int route_flags, int degradation = SS4K_FRVSR_BD);
 // W_eq (4 nf, nf, 3, 3) OIHW + 4 nf biases: the transposed layer (Wt (nf, nf, 3, 3) + nf biases) as a pad-1 3x3 convolution + PixelShuffle(2)
 std::vector<float> embed_convt(const float* wt_and_bias, int nf);
 // dev library: the tail alone on a chosen body tensor (n, nf, h, w) fp32 NCHW, with both transposed layers' outputs copied out as fp32 NCHW
@@ -105,7 +129,9 @@ struct Frvsr {
   ss4k_ctx* ctx = nullptr;
   ss4k_frvsr_desc desc{};
   int generator = SS4K_FRVSR_EGVSR;
+  int degradation = SS4K_FRVSR_BD;
   std::unique_ptr<FrvsrTail> tail;   // null: EGVSR's built-in tail
+  std::unique_ptr<FrvsrWarp> warp;   // null: 'BD''s warp stage, the launchers Frvsr::run names itself
   Model net;                 // container of the conv layers and the activation workspaces (Model::conv / Model::act)
   DevBuf tail_wb;            // srnet.conv_out: 108 weights + 3 biases, fp32
   DevBuf flow_raw, flow;     // fp32 in both dtypes

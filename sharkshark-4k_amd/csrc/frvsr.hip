@@ -7,17 +7,9 @@
 // warp + space-to-depth kernel - and both go through the SAME device functions below, written with explicit __fmaf_rn / __fmul_rn /
 // __fadd_rn so that the compiler contracts nothing differently in the two places: the fused kernel's tensor is bit-identical to the chain
 // of the granular ops (tests/test_gpu_frvsr.py).
-#include "frvsr.h"
+#include "frvsr_warp.h"   // grid_for, warp_pos / warp_taps / warp_sample, the record store: shared with frvsr_bi.hip
 
 namespace ss4k {
-
-#define SS4K_LAUNCH_OK() SS4K_HIP(hipGetLastError())
-
-static inline dim3 grid_for(size_t n, int block = 256) {
-  size_t g = (n + block - 1) / block;
-  if (g > 256 * 8 * 4) g = 256 * 8 * 4;   // grid-stride beyond a few waves per CU
-  return dim3((unsigned)std::max<size_t>(g, 1));
-}
 
 // one 16-byte slot of a record as E values of T
 template <typename T> struct Slot {
@@ -153,31 +145,7 @@ __device__ __forceinline__ float bic4_at(const Bic4& t, const float f[4][4], int
   for (int j = 0; j < 4; ++j) col[j] = bic4_dot(t.k[sy], f[0][j], f[1][j], f[2][j], f[3][j]);
   return bic4_dot(t.k[sx], col[0], col[1], col[2], col[3]);
 }
-// sampling position of backward_warp in pixels, in the reference's order of operations: torch.linspace(-1, 1, size)[i] (ATen's
-// symmetric form) + flow / ((size - 1) / 2) (net_utils.py:62-72), then grid_sample's un-normalisation for align_corners=True,
-// ((g + 1) / 2) * (size - 1), and its border clip.  fminf / fmaxf drop a NaN flow: the position is always inside [0, size - 1]
-__device__ __forceinline__ float warp_pos(int i, int size, float flow) {
-  const float step = 2.f / (float)(size - 1);
-  const float lin = i < size / 2 ? __fmaf_rn(step, (float)i, -1.f) : __fmaf_rn(-step, (float)(size - i - 1), 1.f);   // (ATen's linspace fuses the multiply-add)
-  const float g = __fadd_rn(lin, __fdiv_rn(flow, (float)(((double)size - 1.0) / 2.0)));
-  const float p = __fmul_rn(__fdiv_rn(__fadd_rn(g, 1.f), 2.f), (float)(size - 1));
-  return fminf((float)(size - 1), fmaxf(p, 0.f));
-}
-struct WarpTaps { int x0, x1, y0, y1; float nw, ne, sw, se; };
-__device__ __forceinline__ WarpTaps warp_taps(int X, int Y, int W, int H, float fx, float fy) {
-  const float px = warp_pos(X, W, fx), py = warp_pos(Y, H, fy);
-  const float x0 = floorf(px), y0 = floorf(py);
-  const float ex = __fadd_rn(__fadd_rn(x0, 1.f), -px), ey = __fadd_rn(__fadd_rn(y0, 1.f), -py);   // ix_se - ix, iy_se - iy
-  const float dx = __fadd_rn(px, -x0), dy = __fadd_rn(py, -y0);
-  WarpTaps t;
-  t.x0 = (int)x0; t.y0 = (int)y0; t.x1 = min(t.x0 + 1, W - 1); t.y1 = min(t.y0 + 1, H - 1);   // (a tap past the border has weight 0)
-  t.nw = __fmul_rn(ex, ey); t.ne = __fmul_rn(dx, ey); t.sw = __fmul_rn(ex, dy); t.se = __fmul_rn(dx, dy);
-  return t;
-}
-__device__ __forceinline__ float warp_sample(const float* __restrict__ pl, int W, const WarpTaps& t) {
-  const float a = pl[(size_t)t.y0 * W + t.x0], b = pl[(size_t)t.y0 * W + t.x1], c = pl[(size_t)t.y1 * W + t.x0], d = pl[(size_t)t.y1 * W + t.x1];
-  return __fmaf_rn(d, t.se, __fmaf_rn(c, t.sw, __fmaf_rn(b, t.ne, __fmul_rn(a, t.nw))));
-}
+// backward_warp: warp_pos, warp_taps, warp_sample (frvsr_warp.h)
 
 __global__ void k_bicubic_upsample4(const float* __restrict__ in, float* __restrict__ out, int planes, int h, int w, Bic4 taps) {
   const int OW = 4 * w, OH = 4 * h;
@@ -220,11 +188,10 @@ void op_backward_warp(const float* x, const float* flow, float* out, int n, int 
 template <typename T>
 __device__ __forceinline__ void warp_s2d_pixel(const float* __restrict__ lr_flow, const float* __restrict__ src, uint4* __restrict__ out, size_t i, size_t img,
                                                size_t npix, int h, int w, const Bic4& taps) {
-  constexpr int RV = sizeof(T);
   const int H = 4 * h, W = 4 * w;
   const size_t hw = (size_t)h * w, HW = (size_t)H * W;
   const int x = (int)(i % w), y = (int)((i / w) % h);
-  union { T v[48]; uint4 u[3 * RV]; } rec;
+  S2dRecord<T> rec;
   float fu[4][4], fv[4][4];
   bic4_load(lr_flow + (img * 2) * hw, y, x, h, w, fu);
   bic4_load(lr_flow + (img * 2 + 1) * hw, y, x, h, w, fv);
@@ -237,10 +204,7 @@ __device__ __forceinline__ void warp_s2d_pixel(const float* __restrict__ lr_flow
 #pragma unroll
       for (int c = 0; c < 3; ++c) rec.v[(sy * 4 + sx) * 3 + c] = (T)warp_sample(src + c * HW, W, t);
     }
-#pragma unroll
-  for (int p = 0; p < 3; ++p)
-#pragma unroll
-    for (int q = 0; q < RV; ++q) out[((size_t)p * npix + i) * RV + q] = rec.u[p * RV + q];
+  s2d_store<T>(rec, out, i, npix);
 }
 template <typename T>
 __global__ __launch_bounds__(256) void k_warp_s2d_planes(const float* __restrict__ lr_flow, const float* __restrict__ hr_prev, uint4* __restrict__ out, int n, int h,

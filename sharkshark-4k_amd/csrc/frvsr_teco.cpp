@@ -3,6 +3,7 @@
 //   conv_up  = ConvTranspose2d(64, 64, 3, 2, 1, output_padding=1), ReLU, the same again        (h, w) -> (2 h, 2 w) -> (4 h, 4 w)
 //   conv_out = Conv2d(64, 3, 3, 1, 1)                                                           at (4 h, 4 w)
 //   out     += BicubicUpsample(4)(lr_curr)                                                      degradation 'BD'
+//   out     += F.interpolate(lr_curr, scale_factor=4, 'bilinear', align_corners=False)          degradation 'BI' (frvsr_bi.hip)
 // Everything before it is Frvsr::run (frvsr.cpp), which calls this through FrvsrTail.  The file holds the tail together with every launcher
 // it names beyond Model::conv, so that frvsr.cpp links wherever it linked before.
 //
@@ -45,6 +46,7 @@ namespace {
 
 struct TecoTail final : FrvsrTail {
   bool embedded = false;
+  bool bilinear = false;                        // degradation 'BI': the skip is op_bilinear4_add[_items]
   int up_layer[2] = {-1, -1}, out_layer = -1;   // embedded route: the W_eq layers of f.net
   DevBuf up_w[2], up_b[2];                      // phase route: pack_convt3x3s2's blob and the 64 biases
   TecoTailDev dev{};
@@ -125,7 +127,10 @@ struct TecoTail final : FrvsrTail {
         if (c.items_lr) {
           FrvsrPtrs lr{}, out{};
           for (int i = 0; i < g; ++i) { lr.p[i] = const_cast<float*>(c.items_lr[i0 + i]); out.p[i] = c.items_out->p[i0 + i]; }
-          op_bicubic4_add_items(co, lr, out, g, h, w, st);
+          if (bilinear) op_bilinear4_add_items(co, lr, out, g, h, w, st);
+          else op_bicubic4_add_items(co, lr, out, g, h, w, st);
+        } else if (bilinear) {
+          op_bilinear4_add(co, c.lr_curr + (size_t)i0 * 3 * lr_px, c.hr_out + (size_t)i0 * 48 * lr_px, g, h, w, st);
         } else {
           op_bicubic4_add(co, c.lr_curr + (size_t)i0 * 3 * lr_px, c.hr_out + (size_t)i0 * 48 * lr_px, g, h, w, st);
         }
@@ -136,10 +141,12 @@ struct TecoTail final : FrvsrTail {
 
 }  // namespace
 
-std::unique_ptr<FrvsrTail> make_tecogan_tail(int route_flags) {
+std::unique_ptr<FrvsrTail> make_tecogan_tail(int route_flags, int degradation) {
+  SS4K_REQUIRE(degradation == SS4K_FRVSR_BD || degradation == SS4K_FRVSR_BI, "frvsr: degradation must be SS4K_FRVSR_BD or SS4K_FRVSR_BI");
   SS4K_REQUIRE((route_flags & ~(SS4K_FRVSR_CONVT_EMBEDDED | SS4K_FRVSR_CONVT_PHASE)) == 0, "frvsr: unknown route flags");
   SS4K_REQUIRE(route_flags != (SS4K_FRVSR_CONVT_EMBEDDED | SS4K_FRVSR_CONVT_PHASE), "frvsr: the transposed layers take one route");
   auto t = std::make_unique<TecoTail>();
+  t->bilinear = degradation == SS4K_FRVSR_BI;
   t->embedded = !(route_flags & SS4K_FRVSR_CONVT_PHASE);   // unpinned: the embedded route, the faster one as measured
   return t;
 }

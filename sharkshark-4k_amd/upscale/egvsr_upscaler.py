@@ -102,7 +102,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
     HOST_STAGE_DEPTH = 3
 
     def __init__(self, lr_level=1, device=0, on_queue=None, *, weights=None, checkpoint_dir: Optional[str] = None, dtype="f16", nb=None,
-                 lr_shape=None, seed=0, max_streams=1, generator="egvsr"):
+                 lr_shape=None, seed=0, max_streams=1, generator="egvsr", degradation="BD"):
         self.lr_shape = tuple(lr_shape) if lr_shape is not None else LR_SHAPES[lr_level]
         self.scale = 4
         self.hr_shape = tuple([i * self.scale for i in self.lr_shape])
@@ -112,6 +112,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self.checkpoint_dir = checkpoint_dir
         self.dtype = dtype
         self.generator = generator   # 'egvsr' (the reference service's FRNet) | 'tecogan' (the FRNet it was cut down from, tecogan_nets.py:101-202)
+        self.degradation = degradation   # 'BD' | 'BI': the degradation the generator was trained with (FRNet's argument)
         self.nb = int(nb) if nb is not None else (16 if generator in ("tecogan", 1) else 10)
         self.seed = seed
         self.max_streams = int(max_streams)
@@ -130,7 +131,8 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
             log("WARNING: weights='synthetic' - the network runs on generated weights, output frames are noise")
         self.ctx = _capi.Context(self.device)
         self.torch_device = self.ctx.device
-        self.model = factory.build_model_frvsr(self.ctx, self.weights, self.seed, self.checkpoint_dir, self.dtype, self.nb, self.generator)
+        self.model = factory.build_model_frvsr(self.ctx, self.weights, self.seed, self.checkpoint_dir, self.dtype, self.nb, self.generator,
+                                               degradation=self.degradation)
         self._up = None
         self._up_key = None
         self._slots = StreamSlots(self.max_streams)

@@ -207,13 +207,23 @@ def egvsr_desc(dtype="f16", nb: int = 10):
     return _capi.make_frvsr_desc(_dtype(dtype), 64, nb)
 
 
-def egvsr_flat(weights: WeightSpec = None, seed: int = 0, checkpoint_dir: Optional[str] = None, nb: int = 10) -> np.ndarray:
+def _no_default_bi(weights, what: str, degradation: str):
+    """The reference names a checkpoint file for 'BD' generators only."""
+    if degradation == "BI" and weights is None:
+        raise FileNotFoundError(f"{what}: the reference names no checkpoint file for degradation='BI' - a 'BI' checkpoint must be passed explicitly "
+                                f"(weights=<path to the .pth | torch.load(...) dict | state-dict table>, or weights='synthetic' for tests / bench)")
+
+
+def egvsr_flat(weights: WeightSpec = None, seed: int = 0, checkpoint_dir: Optional[str] = None, nb: int = 10, degradation="BD") -> np.ndarray:
+    degradation = W.frvsr_degradation(degradation)
+    _no_default_bi(weights, "EGVSR", degradation)
     if isinstance(weights, str) and weights == SYNTHETIC:
-        table = W.frnet_table(seed, nb=nb)
+        table = W.frnet_table(seed, nb=nb, degradation=degradation)
     else:
         kind, obj = _load_checkpoint(weights, "EGVSR", EGVSR_CHECKPOINT, checkpoint_dir)
-        table = CK.egvsr_from_checkpoint(obj, nb) if kind == "ckpt" else obj
-    return W.flatten(table, W.frnet_keys(nb))
+        table = CK.egvsr_from_checkpoint(obj, nb, degradation) if kind == "ckpt" else obj
+        CK.frvsr_check_degradation(table, "FRNet", degradation)   # (a bare state_dict handed over in memory arrives as a table)
+    return W.flatten(table, W.frnet_keys(nb, degradation))
 
 
 def build_model_egvsr(ctx: _capi.Context, weights: WeightSpec = None, seed: int = 0, checkpoint_dir: Optional[str] = None,
@@ -238,21 +248,28 @@ def frvsr_generator(generator) -> int:
     return int(generator)
 
 
-def tecogan_flat(weights: WeightSpec = None, seed: int = 0, checkpoint_dir: Optional[str] = None, nb: int = W.TECOGAN_NB) -> np.ndarray:
+def tecogan_flat(weights: WeightSpec = None, seed: int = 0, checkpoint_dir: Optional[str] = None, nb: int = W.TECOGAN_NB,
+                 degradation="BD") -> np.ndarray:
+    degradation = W.frvsr_degradation(degradation)
+    _no_default_bi(weights, "TecoGAN", degradation)
     if isinstance(weights, str) and weights == SYNTHETIC:
-        table = W.tecogan_table(seed, nb=nb)
+        table = W.tecogan_table(seed, nb=nb, degradation=degradation)
     else:
         kind, obj = _load_checkpoint(weights, "TecoGAN", TECOGAN_CHECKPOINT, checkpoint_dir)
-        table = CK.tecogan_from_checkpoint(obj, nb) if kind == "ckpt" else obj
-    return W.flatten(table, W.tecogan_keys(nb))
+        table = CK.tecogan_from_checkpoint(obj, nb, degradation) if kind == "ckpt" else obj
+        CK.frvsr_check_degradation(table, "TecoGAN FRNet", degradation)
+    return W.flatten(table, W.tecogan_keys(nb, degradation))
 
 
 def build_model_frvsr(ctx: _capi.Context, weights: WeightSpec = None, seed: int = 0, checkpoint_dir: Optional[str] = None,
-                      dtype="f16", nb: Optional[int] = None, generator="egvsr", route_flags: int = 0):
-    """``build_model_egvsr`` for either generator; ``nb`` defaults to the generator's own (10 | 16)."""
+                      dtype="f16", nb: Optional[int] = None, generator="egvsr", route_flags: int = 0, degradation="BD"):
+    """``build_model_egvsr`` for either generator; ``nb`` defaults to the generator's own (10 | 16).  ``degradation``: 'BD' | 'BI' | 0 | 1, the
+    ``degradation`` the generator was trained with (FRNet's argument: bicubic | bilinear x4 as the up-sampling function); anything else raises
+    ValueError, and 'BI' without explicit weights FileNotFoundError (the reference names no 'BI' checkpoint file)."""
     g = frvsr_generator(generator)
+    deg = _capi.frvsr_degradation(degradation)
     if g == _capi.FRVSR_EGVSR:
         nb = 10 if nb is None else nb
-        return _capi.Frvsr(ctx, egvsr_desc(dtype, nb), egvsr_flat(weights, seed, checkpoint_dir, nb), g, route_flags)
+        return _capi.Frvsr(ctx, egvsr_desc(dtype, nb), egvsr_flat(weights, seed, checkpoint_dir, nb, deg), g, route_flags, deg)
     nb = W.TECOGAN_NB if nb is None else nb
-    return _capi.Frvsr(ctx, egvsr_desc(dtype, nb), tecogan_flat(weights, seed, checkpoint_dir, nb), g, route_flags)
+    return _capi.Frvsr(ctx, egvsr_desc(dtype, nb), tecogan_flat(weights, seed, checkpoint_dir, nb, deg), g, route_flags, deg)

@@ -188,20 +188,20 @@ def bsvd_table(seed: int = 0, **kw) -> Table:
 TECOGAN_NB = 16   # tecogan_nets.py:153 (FRNet's default nb; EGVSR's service builds its cut-down FRNet with 10)
 
 
-def tecogan_keys(nb: int = TECOGAN_NB) -> List[str]:
-    """TecoGAN's FRNet(degradation='BD').state_dict() order (tecogan_nets.py:101-202): key for key EGVSR's - the two differ in what ``forward`` does
+def tecogan_keys(nb: int = TECOGAN_NB, degradation="BD") -> List[str]:
+    """TecoGAN's FRNet(degradation=...).state_dict() order (tecogan_nets.py:101-202): key for key EGVSR's - the two differ in what ``forward`` does
     with ``srnet.conv_up.*`` and in the shape of ``srnet.conv_out.weight`` ((3, nf, 3, 3) here)."""
-    return frnet_keys(nb)
+    return frnet_keys(nb, degradation)
 
 
-def tecogan_table(seed: int = 0, nf: int = 64, nb: int = TECOGAN_NB, flow_gain: float = 1.0) -> Table:
+def tecogan_table(seed: int = 0, nf: int = 64, nb: int = TECOGAN_NB, flow_gain: float = 1.0, degradation="BD") -> Table:
     """``frnet_table`` with the tail TecoGAN's forward runs: every output pixel of ConvTranspose2d(3, 2, 1, output_padding=1) sums 1, 2 or 4
     of the nine taps (9 / 4 on average), so the transposed layers' weights are kaiming scale times 2 and activations keep their magnitude."""
     t: Table = OrderedDict(frnet_table(seed, nf, nb, flow_gain))
     for c in (0, 2):   # ConvTranspose2d weights are (C_in, C_out, kH, kW)
         _conv(t, seed, f"srnet.conv_up.{c}", nf, nf, 3, gain=2.0)
     _conv(t, seed, "srnet.conv_out", 3, nf, 3)
-    return OrderedDict((k, t[k]) for k in tecogan_keys(nb))
+    return OrderedDict((k, t[k]) for k in tecogan_keys(nb, degradation))
 
 
 # --------------------------------------------------------------------------------------
@@ -213,9 +213,27 @@ _FNET_CONVS = [("encoder1.0", 32, 6), ("encoder1.2", 32, 32), ("encoder2.0", 64,
                ("flow.0", 32, 64), ("flow.2", 2, 32)]
 
 
-def frnet_keys(nb: int = 10) -> List[str]:
+FRVSR_KERNELS = ("upsample_func.kernels", "srnet.upsample_func.kernels")   # BicubicUpsample's buffers: in a 'BD' state_dict only
+
+
+FRVSR_DEGRADATIONS = {"BD": 0, "BI": 1}    # FRNet's `degradation` -> SS4K_FRVSR_BD / SS4K_FRVSR_BI (include/ss4k.h)
+
+
+def frvsr_degradation(degradation) -> str:
+    """'BD' | 'BI' | 0 | 1 -> 'BD' | 'BI'; anything else raises ValueError."""
+    for name, v in FRVSR_DEGRADATIONS.items():
+        if (isinstance(degradation, str) and degradation == name) or (isinstance(degradation, (int, np.integer)) and not isinstance(degradation, bool)
+                                                                       and int(degradation) == v):
+            return name
+    raise ValueError(f"degradation must be 'BD', 'BI', 0 or 1, not {degradation!r}")
+
+
+def frnet_keys(nb: int = 10, degradation="BD") -> List[str]:
     """FRNet(degradation='BD').state_dict() order: the two ``upsample_func.kernels`` buffers and ``srnet.conv_up.*`` are in the
-    state_dict although ``forward`` never reads them (egvsr.py:116-120,141)."""
+    state_dict although ``forward`` never reads them (egvsr.py:116-120,141).  With 'BI' the up-sampling function is a ``functools.partial``
+    of ``F.interpolate``, not a module (utils/net_utils.py:96-108): the two buffers do not exist, everything else keeps its place."""
+    if frvsr_degradation(degradation) == "BI":
+        return [k for k in frnet_keys(nb) if k not in FRVSR_KERNELS]
     keys = ["upsample_func.kernels"]
     for name, _, _ in _FNET_CONVS:
         keys += [f"fnet.{name}.weight", f"fnet.{name}.bias"]
@@ -235,9 +253,9 @@ def bicubic_upsample_kernels(scale: int = 4, a: float = -0.75) -> np.ndarray:
     return np.stack([cubic @ np.array([1, s, s ** 2, s ** 3], dtype=np.float32) for s in [1.0 * d / scale for d in range(scale)]]).astype(np.float32)
 
 
-def frnet_table(seed: int = 0, nf: int = 64, nb: int = 10, flow_gain: float = 1.0) -> Table:
+def frnet_table(seed: int = 0, nf: int = 64, nb: int = 10, flow_gain: float = 1.0, degradation="BD") -> Table:
     """``flow_gain`` scales ``fnet.flow.2.weight`` (tests want flows of several pixels: tests/golden/egvsr/MANIFEST.json records what
-    each fixture's flow measures)."""
+    each fixture's flow measures).  The 'BI' table is the 'BD' table of the same seed without the two ``kernels`` entries."""
     t: Table = OrderedDict()
     t["upsample_func.kernels"] = bicubic_upsample_kernels()
     for name, cout, cin in _FNET_CONVS:
@@ -253,7 +271,7 @@ def frnet_table(seed: int = 0, nf: int = 64, nb: int = 10, flow_gain: float = 1.
         _conv(t, seed, f"srnet.conv_up.{c}", nf, nf, 3)
     _conv(t, seed, "srnet.conv_out", 3, nf // 16, 3)
     t["srnet.upsample_func.kernels"] = bicubic_upsample_kernels()
-    return OrderedDict((k, t[k]) for k in frnet_keys(nb))
+    return OrderedDict((k, t[k]) for k in frnet_keys(nb, degradation))
 
 
 # --------------------------------------------------------------------------------------

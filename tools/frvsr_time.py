@@ -22,8 +22,13 @@ useful FLOPs (2 x 9 x 64 x 64 per input pixel, at (h, w) and at (2 h, 2 w)).  ``
 pad-1 3x3 convolution 64 -> 256 on the conv kernels (``SS4K_FRVSR_CONVT_EMBEDDED``), ``--phase`` to the kernel of their own
 (``SS4K_FRVSR_CONVT_PHASE``); neither: the library's choice.
 
+``--degradation BI``: the generator built with degradation 'BI' (``ss4k_frvsr_create_ex``): stage ``warp`` then is the bilinear x4 of the flow
++ warp + space-to-depth and TecoGAN's ``skip`` the bilinear one.  ``BD`` (the default) uses the entry points from before there was a choice, so
+it also runs on an older build (``SS4K_LIB``) for an A/B.
+
 usage: python tools/frvsr_time.py [--frames 64] [--nb 10] [--streams 1] [--scattered] [--lr 540x960,720x1280]
-                                  [--output-shapes 1440x2560,none] [--generator egvsr|tecogan] [--embedded | --phase] [--out frvsr_time.json]"""
+                                  [--output-shapes 1440x2560,none] [--generator egvsr|tecogan] [--embedded | --phase] [--degradation BD|BI]
+                                  [--out frvsr_time.json]"""
 import argparse
 import json
 import os
@@ -68,6 +73,7 @@ def main():
     ap.add_argument("--generator", default="egvsr", choices=["egvsr", "tecogan"])
     ap.add_argument("--embedded", action="store_true", help="tecogan: the transposed layers on the embedded route (SS4K_FRVSR_CONVT_EMBEDDED)")
     ap.add_argument("--phase", action="store_true", help="tecogan: the transposed layers on the phase kernel (SS4K_FRVSR_CONVT_PHASE)")
+    ap.add_argument("--degradation", default="BD", choices=["BD", "BI"], help="FRNet's degradation: bicubic | bilinear x4 as the up-sampling function")
     ap.add_argument("--streams", type=int, default=1, help="streams stepped in lockstep, one batched step per round")
     ap.add_argument("--scattered", action="store_true", help="rounds through ss4k_frvsr_upscale_streams_at, frames and results as separate allocations")
     ap.add_argument("--lr", default=",".join(f"{h}x{w}" for h, w in REFERENCE_MS), help="lr shapes, HxW[,HxW...]")
@@ -87,11 +93,15 @@ def main():
     from sharkshark4k_amd import _capi, weights as W
     assert torch.cuda.is_available(), "needs the GPU: no timing without one"
     ctx = _capi.Context(0)
-    if teco:
-        model = _capi.Frvsr(ctx, _capi.make_frvsr_desc(_capi.F16, 64, a.nb), W.flatten(W.tecogan_table(0, nb=a.nb), W.tecogan_keys(a.nb)),
-                            _capi.FRVSR_TECOGAN, _capi.FRVSR_CONVT_EMBEDDED if a.embedded else _capi.FRVSR_CONVT_PHASE if a.phase else 0)
+    flags = _capi.FRVSR_CONVT_EMBEDDED if a.embedded else _capi.FRVSR_CONVT_PHASE if a.phase else 0
+    table, keys = (W.tecogan_table, W.tecogan_keys) if teco else (W.frnet_table, W.frnet_keys)
+    if a.degradation == "BI":
+        model = _capi.Frvsr(ctx, _capi.make_frvsr_desc(_capi.F16, 64, a.nb), W.flatten(table(0, nb=a.nb, degradation="BI"), keys(a.nb, "BI")),
+                            _capi.FRVSR_TECOGAN if teco else _capi.FRVSR_EGVSR, flags, _capi.FRVSR_BI)
+    elif teco:
+        model = _capi.Frvsr(ctx, _capi.make_frvsr_desc(_capi.F16, 64, a.nb), W.flatten(table(0, nb=a.nb), keys(a.nb)), _capi.FRVSR_TECOGAN, flags)
     else:
-        model = _capi.Frvsr(ctx, _capi.make_frvsr_desc(_capi.F16, 64, a.nb), W.flatten(W.frnet_table(0, nb=a.nb), W.frnet_keys(a.nb)))
+        model = _capi.Frvsr(ctx, _capi.make_frvsr_desc(_capi.F16, 64, a.nb), W.flatten(table(0, nb=a.nb), keys(a.nb)))
     rows = []
     for lr in lrs:
         frames = stream_frames(a.frames, lr[0], lr[1], ctx.device)
@@ -137,6 +147,7 @@ def main():
             model.prof_enable(False)
             ff, fs = conv_flops(lr[0], lr[1], a.nb)
             row = dict(lr_shape=list(lr), output_shape=None if out_shape is None else list(out_shape), nb=a.nb, streams=S, scattered=bool(a.scattered), frames_timed=half * S,
+                       degradation=a.degradation,
                        library=os.path.basename(os.path.dirname(_capi.LIB_PATH)) + "/" + os.path.basename(_capi.LIB_PATH),
                        state_bytes=up.state_bytes() if hasattr(_capi.lib(), "ss4k_frvsr_upscaler_state_bytes") else None,
                        ms_per_frame=ms, frames_per_s=1000.0 / ms, reference_ms_tensorrt_unknown_hw=REFERENCE_MS.get(lr), realtime_24fps_ms=1000.0 / 24,
