@@ -255,16 +255,10 @@ int ss4k_frvsr_create_ex(ss4k_ctx* ctx, const ss4k_frvsr_desc* d, int generator,
                          ss4k_frvsr** out) {
   return guard([&] {
     SS4K_REQUIRE(ctx && d && w && out, "ss4k_frvsr_create: NULL argument");
-    SS4K_REQUIRE(generator == SS4K_FRVSR_EGVSR || generator == SS4K_FRVSR_TECOGAN, "ss4k_frvsr_create_as: generator must be SS4K_FRVSR_EGVSR or SS4K_FRVSR_TECOGAN");
-    SS4K_REQUIRE(degradation == SS4K_FRVSR_BD || degradation == SS4K_FRVSR_BI, "ss4k_frvsr_create_ex: degradation must be SS4K_FRVSR_BD or SS4K_FRVSR_BI");
-    SS4K_REQUIRE((route_flags & ~(SS4K_FRVSR_CONVT_EMBEDDED | SS4K_FRVSR_CONVT_PHASE)) == 0, "ss4k_frvsr_create_as: unknown route flags");
-    SS4K_REQUIRE(generator == SS4K_FRVSR_TECOGAN || route_flags == 0, "ss4k_frvsr_create_as: the route flags belong to the TecoGAN generator");
     SS4K_HIP(hipSetDevice(ctx->device));
     auto m = std::make_unique<ss4k_frvsr>();
-    m->f.ctx = ctx; m->f.desc = *d; m->f.generator = generator; m->f.degradation = degradation;
-    if (generator == SS4K_FRVSR_TECOGAN) m->f.tail = make_tecogan_tail(route_flags, degradation);
-    if (degradation == SS4K_FRVSR_BI) m->f.warp = make_bilinear_warp();
-    m->f.build(w, n);
+    m->f.ctx = ctx; m->f.desc = *d; m->f.generator = generator; m->f.degradation = degradation; m->f.route_flags = route_flags;
+    m->f.build(w, n);   // (validates the three together with the description and the blob size)
 #ifdef SS4K_DEV
     for (DevBuf* b : {&m->f.flow_raw, &m->f.flow, &m->f.tap_s2d}) b->transient = true;   // guard mode: every step rewrites what it reads from these
 #endif

@@ -261,7 +261,7 @@ int ss4k_dev_frvsr_tail_taps(ss4k_frvsr* m, const float* body_nchw, const float*
   return guard([&] {
     SS4K_REQUIRE(m && body_nchw && lr_curr && up1_out && up2_out && hr_out, "ss4k_dev_frvsr_tail_taps: NULL argument");
     TecoTailDev o; o.max_workgroups = max_workgroups; o.group_items = group_items;
-    tecogan_tail_taps(m->f, body_nchw, lr_curr, up1_out, up2_out, hr_out, n, h, w, o, (hipStream_t)stream);
+    m->f.tecogan_tail_taps(body_nchw, lr_curr, up1_out, up2_out, hr_out, n, h, w, o, (hipStream_t)stream);
   });
 }
 // host only: W_eq + biases of embed_convt for one transposed layer (nf * nf * 9 + nf floats in, 4 nf * nf * 9 + 4 nf out)

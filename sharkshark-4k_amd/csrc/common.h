@@ -345,6 +345,8 @@ PackedConv pack_conv3x3(const PackSpec& s, const float* w_oihw, const float* bia
 // conv_w16.hip weight order (fp16, 64-cout groups, an even number of K-chunks); same virtual cout order / bias as pack_conv3x3
 std::vector<uint8_t> pack_conv3x3_w16(const PackSpec& s, const float* w_oihw, int cout_pad);
 std::vector<uint8_t> pack_conv3x3_w16n(const PackSpec& s, const float* w_oihw);   // one 16-cout block (conv_w16n.hip)
+// conv_up2.hip weight order: Wt (64, 64, 3, 3) (C_in, C_out, kH, kW) -> the kernel's fragments in `dtype` (the head of conv_up2.hip states the map)
+std::vector<uint8_t> pack_convt3x3s2(const float* wt, int dtype);
 int virt_to_real_cout(const PackSpec& s, int v);
 
 }  // namespace ss4k

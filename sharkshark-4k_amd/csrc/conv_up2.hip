@@ -24,7 +24,7 @@
 // The tile is stored slot-major - [16-byte slot of the pixel's four records][pixel] - so that the 16 lanes of a B read (one pixel each,
 // the same slot) touch 16 consecutive 16-byte slots.
 //
-// Packed weights (pack_convt3x3s2, host side, once per model), PASSES = 4 / CBL, KS = k-steps per tap (2 | 16), E = K per lane (8 | 1):
+// Packed weights (pack_convt3x3s2 in pack.cpp, host side, once per model), PASSES = 4 / CBL, KS = k-steps per tap (2 | 16), E = K per lane (8 | 1):
 //   blob[pass][tap = ky * 3 + kx][ks][cb < CBL][lane][e] = Wt[cin = ks * 4 E + E (lane >> 4) + e][cout = 16 (pass * CBL + cb) + (lane & 15)][ky][kx]
 // Every (cin, cout, ky, kx) appears exactly once: lane & 15 and (pass, cb) enumerate cout, (ks, lane >> 4, e) enumerate cin.
 #include "frvsr.h"
@@ -171,26 +171,6 @@ __global__ __launch_bounds__(64 * NW) void convt3x3s2_kernel(const ConvtArgs a) 
 }
 
 }  // namespace up2
-
-// blob[pass][tap][ks][cb][lane][e] (the head of this file) from Wt (64, 64, 3, 3) as the state_dict holds it
-std::vector<uint8_t> pack_convt3x3s2(const float* wt, int dtype) {
-  const bool half = dtype == SS4K_F16;
-  const int KS = half ? 2 : 16, E = half ? 8 : 1, CBL = half ? 4 : 1, PASSES = 4 / CBL;
-  std::vector<uint8_t> out((size_t)64 * 64 * 9 * (half ? 2 : 4));
-  size_t idx = 0;
-  for (int pass = 0; pass < PASSES; ++pass)
-    for (int tap = 0; tap < 9; ++tap)
-      for (int ks = 0; ks < KS; ++ks)
-        for (int cb = 0; cb < CBL; ++cb)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int e = 0; e < E; ++e, ++idx) {
-              const int cin = ks * 4 * E + E * (lane >> 4) + e, cout = 16 * (pass * CBL + cb) + (lane & 15);
-              const float v = wt[((size_t)cin * 64 + cout) * 9 + tap];
-              if (half) reinterpret_cast<__half*>(out.data())[idx] = __float2half_rn(v);
-              else reinterpret_cast<float*>(out.data())[idx] = v;
-            }
-  return out;
-}
 
 void launch_convt3x3s2(ss4k_ctx* ctx, const ConvtArgs& a0, int dtype, int max_workgroups, hipStream_t st) {
   using namespace up2;

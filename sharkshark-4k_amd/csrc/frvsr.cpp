@@ -38,9 +38,10 @@ size_t frvsr_param_count(const ss4k_frvsr_desc& d, int generator, int degradatio
 void Frvsr::build(const float* w, size_t n) {
   validate_frvsr_desc(desc);
   SS4K_REQUIRE(generator == SS4K_FRVSR_EGVSR || generator == SS4K_FRVSR_TECOGAN, "frvsr: generator must be SS4K_FRVSR_EGVSR or SS4K_FRVSR_TECOGAN");
-  SS4K_REQUIRE((generator == SS4K_FRVSR_EGVSR) == (tail == nullptr), "internal: a generator other than EGVSR brings its tail (ss4k_frvsr_create_as)");
   SS4K_REQUIRE(degradation == SS4K_FRVSR_BD || degradation == SS4K_FRVSR_BI, "frvsr: degradation must be SS4K_FRVSR_BD or SS4K_FRVSR_BI");
-  SS4K_REQUIRE((degradation == SS4K_FRVSR_BD) == (warp == nullptr), "internal: a degradation other than 'BD' brings its warp stage (ss4k_frvsr_create_ex)");
+  SS4K_REQUIRE((route_flags & ~(SS4K_FRVSR_CONVT_EMBEDDED | SS4K_FRVSR_CONVT_PHASE)) == 0, "frvsr: unknown route flags");
+  SS4K_REQUIRE(route_flags != (SS4K_FRVSR_CONVT_EMBEDDED | SS4K_FRVSR_CONVT_PHASE), "frvsr: the route flags pin one route of the transposed layers, not both");
+  SS4K_REQUIRE(generator == SS4K_FRVSR_TECOGAN || route_flags == 0, "frvsr: the route flags belong to the TecoGAN generator");
   SS4K_REQUIRE(n == frvsr_param_count(desc, generator, degradation), "weight blob size does not match the frvsr description");
   const size_t kernels = degradation == SS4K_FRVSR_BD ? 16 : 0;
   net.ctx = ctx;
@@ -54,10 +55,10 @@ void Frvsr::build(const float* w, size_t n) {
   srnet0 = (int)net.layers.size();
   net.add_conv(pc, nf, 51, net.spec_concat(3, 48), false);   // torch.cat([lr_curr, hr_prev_tran], 1) (egvsr.py:137)
   for (int i = 0; i < 2 * desc.num_block; ++i) net.add_conv(pc, nf, nf, net.spec_plain(nf), false);
-  if (tail) {
+  if (generator == SS4K_FRVSR_TECOGAN) {
     const float* up0 = pc.take((size_t)nf * nf * 9 + nf);
     const float* up2 = pc.take((size_t)nf * nf * 9 + nf);
-    tail->build(*this, up0, up2, pc.take((size_t)3 * nf * 9 + 3));
+    build_teco_tail(up0, up2, pc.take((size_t)3 * nf * 9 + 3));
   } else {
     (void)pc.take(2 * ((size_t)nf * nf * 9 + nf));
     const float* tw = pc.take(108);
@@ -110,20 +111,17 @@ void Frvsr::run(const float* lr_curr, const float* lr_prev, const float* hr_prev
   SS4K_REQUIRE(n > 0, "frvsr step: empty batch");
   SS4K_REQUIRE(h >= 8 && w >= 8, "frvsr step: h and w must be at least 8 (the flow is computed at (h // 8 * 8, w // 8 * 8) and reflect-padded, egvsr.py:191-194)");
   SS4K_REQUIRE((double)n * 16.0 * h * w < 2147483648.0, "frvsr step: the output of a call holds at most 2^31 pixels per plane");
-  const bool plan = net.plan_only, f16 = desc.dtype == SS4K_F16;
+  const bool plan = net.plan_only, bi = degradation == SS4K_FRVSR_BI;
+  const int dt = desc.dtype;
   const int h1 = h / 2, w1 = w / 2, h2 = h1 / 2, w2 = w1 / 2, h3 = h2 / 2, w3 = w2 / 2, h8 = 8 * h3, w8 = 8 * w3;
   const size_t px = (size_t)n * h * w, px1 = (size_t)n * h1 * w1, px2 = (size_t)n * h2 * w2, px3 = (size_t)n * h3 * w3;
   auto stage = [&](int s, auto&& body) { timed(s, st, body); };
   auto lrelu = [](const Tens& out, float slope) { ConvOpts o; o.act = ACT_LRELU; o.slope = slope; o.out = out; return o; };
   auto pool = [&](const Tens& in, const Tens& out, int channels, int H, int W) {
-    if (plan) return;
-    if (f16) op_maxpool2_planes<__half>(reinterpret_cast<const __half*>(in.p), reinterpret_cast<__half*>(out.p), channels / 16, n, H, W, st);
-    else op_maxpool2_planes<float>(reinterpret_cast<const float*>(in.p), reinterpret_cast<float*>(out.p), channels / 16, n, H, W, st);
+    if (!plan) SS4K_PLANES_T(dt, op_maxpool2_planes((const T*)in.p, (T*)out.p, channels / 16, n, H, W, st));
   };
   auto up2 = [&](const Tens& in, const Tens& out, int channels, int H, int W) {
-    if (plan) return;
-    if (f16) op_bilinear2_planes<__half>(reinterpret_cast<const __half*>(in.p), reinterpret_cast<__half*>(out.p), channels / 16, n, H, W, st);
-    else op_bilinear2_planes<float>(reinterpret_cast<const float*>(in.p), reinterpret_cast<float*>(out.p), channels / 16, n, H, W, st);
+    if (!plan) SS4K_PLANES_T(dt, op_bilinear2_planes((const T*)in.p, (T*)out.p, channels / 16, n, H, W, st));
   };
   int slot = 0;
   auto act = [&](size_t pixels, int channels) { return net.act(slot++, pixels, channels); };
@@ -139,10 +137,9 @@ void Frvsr::run(const float* lr_curr, const float* lr_prev, const float* hr_prev
     } else if (items->pack_batched) {
       FrvsrPtrs c{}, p{};
       for (int i = 0; i < n; ++i) { c.p[i] = const_cast<float*>(items->lr_curr[i]); p.p[i] = const_cast<float*>(items->lr_prev[i]); }
-      if (f16) op_pack_lr_items<__half>(c, p, reinterpret_cast<__half*>(A.p), reinterpret_cast<__half*>(B.p), n, h, w, st);
-      else op_pack_lr_items<float>(c, p, reinterpret_cast<float*>(A.p), reinterpret_cast<float*>(B.p), n, h, w, st);
+      SS4K_PLANES_T(dt, op_pack_lr_items(c, p, (T*)A.p, (T*)B.p, n, h, w, st));
     } else {   // item i's pixels are one contiguous run of the single plane
-      const size_t item_b = (size_t)h * w * conv_rec_bytes(desc.dtype);
+      const size_t item_b = (size_t)h * w * conv_rec_bytes(dt);
       for (int i = 0; i < n; ++i) {
         net.pack_in(items->lr_curr[i], Tens{A.p + i * item_b, A.plane_bytes, 0}, 1, 1, 3, h, w, 1, st);
         net.pack_in(items->lr_prev[i], Tens{B.p + i * item_b, B.plane_bytes, 0}, 1, 1, 3, h, w, 1, st);
@@ -187,21 +184,20 @@ void Frvsr::run(const float* lr_curr, const float* lr_prev, const float* hr_prev
   // tanh * 24 (egvsr.py:76), reflect pad to (h, w) (:191-194)
   stage(FRV_FLOW, [&] { if (!plan) op_flow_finish(flow_raw.as<float>(), flow.as<float>(), n, h8, w8, h, w, st); });
 
-  // ---- hr_flow = 4 * BicubicUpsample(4)(lr_flow), backward_warp(hr_prev, hr_flow), space-to-depth (egvsr.py:196-208): one launch, three planes
+  // ---- hr_flow = 4 * BicubicUpsample(4)(lr_flow), backward_warp(hr_prev, hr_flow), space-to-depth (egvsr.py:196-208): one launch, three planes.
+  // Degradation 'BI': the same stage with F.interpolate(scale_factor=4, 'bilinear') of the flow (utils/net_utils.py:96-108; frvsr_bi.hip)
   Tens Wp = net.act_planes(slot++, px, 3);
   stage(FRV_WARP, [&] {
     if (plan) return;
-    if (warp) { warp->run(*this, FrvsrWarp::Call{flow.as<float>(), hr_prev, items ? items->hr_prev : nullptr, Wp.p, n, h, w}, st); return; }
-    if (items) {
-      if (f16) op_warp_s2d_planes_items<__half>(flow.as<float>(), *items->hr_prev, reinterpret_cast<__half*>(Wp.p), n, h, w, st);
-      else op_warp_s2d_planes_items<float>(flow.as<float>(), *items->hr_prev, reinterpret_cast<float*>(Wp.p), n, h, w, st);
-    } else if (f16) op_warp_s2d_planes<__half>(flow.as<float>(), hr_prev, reinterpret_cast<__half*>(Wp.p), n, h, w, st);
-    else op_warp_s2d_planes<float>(flow.as<float>(), hr_prev, reinterpret_cast<float*>(Wp.p), n, h, w, st);
+    const float* fl = flow.as<float>();
+    if (items && bi) SS4K_PLANES_T(dt, op_warp_s2d_bi_planes_items(fl, *items->hr_prev, (T*)Wp.p, n, h, w, st));
+    else if (items) SS4K_PLANES_T(dt, op_warp_s2d_planes_items(fl, *items->hr_prev, (T*)Wp.p, n, h, w, st));
+    else if (bi) SS4K_PLANES_T(dt, op_warp_s2d_bi_planes(fl, hr_prev, (T*)Wp.p, n, h, w, st));
+    else SS4K_PLANES_T(dt, op_warp_s2d_planes(fl, hr_prev, (T*)Wp.p, n, h, w, st));
   });
   if (keep_taps && !plan) {
     tap_s2d.ensure(px * 48 * 4);
-    if (f16) op_planes_to_nchw<__half>(reinterpret_cast<const __half*>(Wp.p), tap_s2d.as<float>(), n, 48, h, w, st);
-    else op_planes_to_nchw<float>(reinterpret_cast<const float*>(Wp.p), tap_s2d.as<float>(), n, 48, h, w, st);
+    SS4K_PLANES_T(dt, op_planes_to_nchw((const T*)Wp.p, tap_s2d.as<float>(), n, 48, h, w, st));
   }
 
   // ---- SRNet (egvsr.py:132-143): ReLU is LeakyReLU with slope 0; a residual block's skip is res1 with alpha = 1
@@ -219,18 +215,12 @@ void Frvsr::run(const float* lr_curr, const float* lr_prev, const float* hr_prev
     }
     net.lanes_join(st, true);   // (closes the context's conv profiling section if one is open; a step never forks)
   });
-  if (tail) {   // another generator's tail, with stages of its own
-    tail->run(*this, FrvsrTail::Call{cur, slot, lr_curr, hr_out, items ? items->lr_curr : nullptr, items ? items->hr_out : nullptr, n, h, w}, st);
-    return;
-  }
+  if (generator == SS4K_FRVSR_TECOGAN) { run_teco_tail(cur, slot, lr_curr, hr_out, items, n, h, w, st); return; }   // (stages of its own: frvsr_teco.cpp)
   // PixelShuffle(4), ReLU, conv_out (egvsr.py:139-140)
   stage(FRV_TAIL, [&] {
     if (plan) return;
-    if (items) {
-      if (f16) op_ps4_conv_tail_items<__half>(reinterpret_cast<const __half*>(cur.p), tail_wb.as<float>(), *items->hr_out, n, h, w, st);
-      else op_ps4_conv_tail_items<float>(reinterpret_cast<const float*>(cur.p), tail_wb.as<float>(), *items->hr_out, n, h, w, st);
-    } else if (f16) op_ps4_conv_tail<__half>(reinterpret_cast<const __half*>(cur.p), tail_wb.as<float>(), hr_out, n, h, w, st);
-    else op_ps4_conv_tail<float>(reinterpret_cast<const float*>(cur.p), tail_wb.as<float>(), hr_out, n, h, w, st);
+    if (items) SS4K_PLANES_T(dt, op_ps4_conv_tail_items((const T*)cur.p, tail_wb.as<float>(), *items->hr_out, n, h, w, st));
+    else SS4K_PLANES_T(dt, op_ps4_conv_tail((const T*)cur.p, tail_wb.as<float>(), hr_out, n, h, w, st));
   });
 }
 

@@ -1,5 +1,7 @@
 // EGVSR's frame-recurrent upscaler (FRNet x4, reference src/upscale/model/egvsr/egvsr.py:146-212): the executor behind ss4k_frvsr and
-// the service path behind ss4k_frvsr_upscaler (include/ss4k.h), and the launchers of the glue kernels they need (frvsr.hip).
+// the service path behind ss4k_frvsr_upscaler (include/ss4k.h), and the launchers of the glue kernels they need (frvsr.hip).  One Frvsr holds
+// all four (generator, degradation) variants: Frvsr::run branches on `degradation` for the warp stage (frvsr_bi.hip) and on `generator` for the
+// tail (TecoGAN's: frvsr_teco.cpp, conv_up2.hip).
 #pragma once
 #include "models.h"
 #include <memory>
@@ -41,7 +43,7 @@ void op_bicubic4_add(const float* conv, const float* lr, float* out, int n, int 
 // ... item i reading lr.p[i] (3, h, w) and writing out.p[i] (3, 4 h, 4 w); conv stays one contiguous batch: bit-identical; n <= 64
 void op_bicubic4_add_items(const float* conv, const FrvsrPtrs& lr, const FrvsrPtrs& out, int n, int h, int w, hipStream_t st);
 // ---- kernels of degradation 'BI' (frvsr_bi.hip): get_upsampling_func's F.interpolate(scale_factor=4, 'bilinear', align_corners=False)
-// (utils/net_utils.py:96-108) in the places of BicubicUpsample(4).  No file of tests/hostcheck/PRODUCT_SOURCES names them
+// (utils/net_utils.py:96-108) in the places of BicubicUpsample(4)
 // (planes, h, w) -> (planes, 4 h, 4 w), fp32
 void op_bilinear_upsample4(const float* in, float* out, int planes, int h, int w, hipStream_t st);
 // op_warp_s2d_planes[_items] with 4 * bilinear x4 of the flow: the same warp, the same records, the same requirements and grid
@@ -74,66 +76,44 @@ size_t frvsr_param_count(const ss4k_frvsr_desc& d, int generator = SS4K_FRVSR_EG
 enum { FRV_FNET_CONV = 0, FRV_SRNET_CONV = 1, FRV_POOL_UP = 2, FRV_FLOW = 3, FRV_WARP = 4, FRV_TAIL = 5, FRV_GLUE = 6, FRV_CONVT = 7, FRV_CONV_OUT = 8,
        FRV_SKIP = 9, FRV_STAGES = 10 };
 
-struct Frvsr;
-// What follows SRNet's last residual block when it is not EGVSR's tail (which Frvsr::run holds itself).  A tail lives in a file of its own
-// together with the launchers it calls (frvsr_teco.cpp), and ss4k_frvsr_create_as installs it: frvsr.cpp names no launcher but its own.
-struct FrvsrTail {
-  virtual ~FrvsrTail() = default;
-  // srnet.conv_up.{0,2} as the state_dict holds them ((C_in, C_out, 3, 3) + bias each) and srnet.conv_out (OIHW + bias): adds its layers to f.net
-  virtual void build(Frvsr& f, const float* up0, const float* up2, const float* out_w) = 0;
-  // body: the last residual block's output, nf channels at (n, h, w).  lr_curr / hr_out: the contiguous batches, or (items != null) the
-  // per-item tables.  slot: the first free activation slot of f.net.  Plans (f.net.plan_only) like every other part of a step
-  struct Call { Tens body; int slot; const float* lr_curr; float* hr_out; const float* const* items_lr; const FrvsrPtrs* items_out; int n, h, w; };
-  virtual void run(Frvsr& f, const Call& c, hipStream_t st) = 0;
-};
-
-// The FRV_WARP stage when it is not 'BD''s (which Frvsr::run holds itself): flow x4 + warp + space-to-depth with another up-sampling function.
-// Like a tail, it lives in a file of its own with the launchers it calls (frvsr_bi.cpp), and ss4k_frvsr_create_ex installs it
-struct FrvsrWarp {
-  virtual ~FrvsrWarp() = default;
-  // flow: the padded LR flow (n, 2, h, w) fp32.  hr_prev: the contiguous batch, or (items != null) the per-item table.  out: three planes of
-  // the model's dtype at (n, h, w).  Never called while the step only plans
-  struct Call { const float* flow; const float* hr_prev; const FrvsrPtrs* items; char* out; int n, h, w; };
-  virtual void run(Frvsr& f, const Call& c, hipStream_t st) = 0;
-};
-// degradation 'BI' (frvsr_bi.cpp)
-std::unique_ptr<FrvsrWarp> make_bilinear_warp();
-
 // ---- conv_up2.hip: ConvTranspose2d(64, 64, 3, 2, 1, output_padding=1) + bias + ReLU on planes, (N, H, W) -> (N, 2 H, 2 W), by output phase
 constexpr int CONVT_TH = 8, CONVT_TW = 32;   // input pixels per workgroup tile
 struct ConvtArgs {
   const char* in; size_t in_plane_bytes;     // four planes (64 channels) at (N, H, W)
   char* out; size_t out_plane_bytes;         // four planes at (N, 2 H, 2 W)
-  const char* w;                             // pack_convt3x3s2's blob
+  const char* w;                             // pack_convt3x3s2's blob (pack.cpp)
   const float* bias;                         // 64
   int N, H, W, tiles_x, tiles_y;             // (the launcher fills the tile counts)
 };
-// Wt (64, 64, 3, 3) (C_in, C_out, kH, kW) -> the kernel's fragment order in the model's dtype (the head of conv_up2.hip states the map); host only
-std::vector<uint8_t> pack_convt3x3s2(const float* wt, int dtype);
 // max_workgroups > 0 caps the persistent grid (dev: a walk of more tiles than workgroups at small shapes)
 void launch_convt3x3s2(ss4k_ctx* ctx, const ConvtArgs& a, int dtype, int max_workgroups, hipStream_t st);
 
-// TecoGAN's tail (frvsr_teco.cpp).  route_flags: SS4K_FRVSR_CONVT_* (include/ss4k.h); unknown bits are refused.  degradation: which
-// up-sampling of lr_curr the skip adds; either goes with either route
-std::unique_ptr<FrvsrTail> make_tecogan_tail(int route_flags, int degradation = SS4K_FRVSR_BD);
 // W_eq (4 nf, nf, 3, 3) OIHW + 4 nf biases: the transposed layer (Wt (nf, nf, 3, 3) + nf biases) as a pad-1 3x3 convolution + PixelShuffle(2)
 std::vector<float> embed_convt(const float* wt_and_bias, int nf);
 // dev library: the tail alone on a chosen body tensor (n, nf, h, w) fp32 NCHW, with both transposed layers' outputs copied out as fp32 NCHW
 // (up1 (n, nf, 2 h, 2 w), up2 (n, nf, 4 h, 4 w)).  group_items: items per group of the tail's walk (0 = default); max_workgroups: a cap
 // on the phase kernel's grid (launch_convt3x3s2; the embedded route has no grid of its own: accepted and unused)
 struct TecoTailDev { float* up1 = nullptr; float* up2 = nullptr; int group_items = 0, max_workgroups = 0; };
-void tecogan_tail_taps(Frvsr& f, const float* body_nchw, const float* lr_curr, float* up1, float* up2, float* hr_out, int n, int h, int w,
-                       const TecoTailDev& opts, hipStream_t st);
+// TecoGAN's tail (frvsr_teco.cpp: Frvsr::build_teco_tail / run_teco_tail); unused by EGVSR
+struct TecoTail {
+  bool embedded = true;                         // the transposed layers' route (route_flags; unpinned: embedded, the faster one as measured)
+  int up_layer[2] = {-1, -1}, out_layer = -1;   // embedded route: the W_eq layers of net; conv_out
+  DevBuf up_w[2], up_b[2];                      // phase route: pack_convt3x3s2's blob and the 64 biases
+  TecoTailDev dev{};
+};
+
+// `body` with T = __half or float by a model's dtype, so that a planes launcher is named once per call site
+#define SS4K_PLANES_T(dtype, ...) do { if ((dtype) == SS4K_F16) { using T = __half; __VA_ARGS__; } else { using T = float; __VA_ARGS__; } } while (0)
 
 struct Frvsr {
   ss4k_ctx* ctx = nullptr;
   ss4k_frvsr_desc desc{};
-  int generator = SS4K_FRVSR_EGVSR;
-  int degradation = SS4K_FRVSR_BD;
-  std::unique_ptr<FrvsrTail> tail;   // null: EGVSR's built-in tail
-  std::unique_ptr<FrvsrWarp> warp;   // null: 'BD''s warp stage, the launchers Frvsr::run names itself
+  int generator = SS4K_FRVSR_EGVSR;     // | SS4K_FRVSR_TECOGAN: which tail follows SRNet's last residual block
+  int degradation = SS4K_FRVSR_BD;      // | SS4K_FRVSR_BI: which x4 up-sampling the warp stage (and TecoGAN's skip) uses
+  int route_flags = 0;                  // SS4K_FRVSR_CONVT_* (include/ss4k.h): TecoGAN only, at most one pin
+  TecoTail teco;
   Model net;                 // container of the conv layers and the activation workspaces (Model::conv / Model::act)
-  DevBuf tail_wb;            // srnet.conv_out: 108 weights + 3 biases, fp32
+  DevBuf tail_wb;            // EGVSR's srnet.conv_out: 108 weights + 3 biases, fp32
   DevBuf flow_raw, flow;     // fp32 in both dtypes
   int fnet0 = 0, srnet0 = 0; // first layer of each network in net.layers
   bool keep_taps = false;    // step() leaves copies for the service's parity taps
@@ -157,6 +137,7 @@ struct Frvsr {
   }
   ~Frvsr();
 
+  // validates (desc, generator, degradation, route_flags) and the blob size - the one place - then packs the weights
   void build(const float* w, size_t n);
   // FRNet.forward (egvsr.py:180-212)
   void step(const float* lr_curr, const float* lr_prev, const float* hr_prev, float* hr_out, int n, int h, int w, hipStream_t st);
@@ -167,8 +148,15 @@ struct Frvsr {
   struct Items { const float* const* lr_curr; const float* const* lr_prev; const FrvsrPtrs* hr_prev; const FrvsrPtrs* hr_out; bool pack_batched = false; };
   void step_items(const Items& items, int n, int h, int w, hipStream_t st);
   size_t workspace_bytes(int n, int h, int w);
+  // dev library: TecoGAN's tail alone (TecoTailDev above); refused on an EGVSR object
+  void tecogan_tail_taps(const float* body_nchw, const float* lr_curr, float* up1, float* up2, float* hr_out, int n, int h, int w, const TecoTailDev& opts, hipStream_t st);
  private:
   void run(const float* lr_curr, const float* lr_prev, const float* hr_prev, float* hr_out, const Items* items, int n, int h, int w, hipStream_t st);
+  // frvsr_teco.cpp.  build: srnet.conv_up.{0,2} as the state_dict holds them ((C_in, C_out, 3, 3) + bias each) and srnet.conv_out (OIHW + bias).
+  // run: body is the last residual block's output, nf channels at (n, h, w); lr_curr / hr_out are the contiguous batches, or (items != null)
+  // unused; slot is the first free activation slot of net.  Plans (net.plan_only) like every other part of a step
+  void build_teco_tail(const float* up0, const float* up2, const float* out_w);
+  void run_teco_tail(const Tens& body, int slot, const float* lr_curr, float* hr_out, const Items* items, int n, int h, int w, hipStream_t st);
 };
 
 struct FrvsrUpscaler {

@@ -149,4 +149,24 @@ std::vector<uint8_t> pack_conv3x3_w16n(const PackSpec& s, const float* w) {
   return out;
 }
 
+// conv_up2.hip: blob[pass][tap][ks][cb][lane][e] (the head of that file) from Wt (64, 64, 3, 3) as the state_dict holds it
+std::vector<uint8_t> pack_convt3x3s2(const float* wt, int dtype) {
+  const bool half = dtype == SS4K_F16;
+  const int KS = half ? 2 : 16, E = half ? 8 : 1, CBL = half ? 4 : 1, PASSES = 4 / CBL;
+  std::vector<uint8_t> out((size_t)64 * 64 * 9 * (half ? 2 : 4));
+  size_t idx = 0;
+  for (int pass = 0; pass < PASSES; ++pass)
+    for (int tap = 0; tap < 9; ++tap)
+      for (int ks = 0; ks < KS; ++ks)
+        for (int cb = 0; cb < CBL; ++cb)
+          for (int lane = 0; lane < 64; ++lane)
+            for (int e = 0; e < E; ++e, ++idx) {
+              const int cin = ks * 4 * E + E * (lane >> 4) + e, cout = 16 * (pass * CBL + cb) + (lane & 15);
+              const float v = wt[((size_t)cin * 64 + cout) * 9 + tap];
+              if (half) { const uint16_t h = f32_to_f16_bits(v); std::memcpy(&out[idx * 2], &h, 2); }
+              else std::memcpy(&out[idx * 4], &v, 4);
+            }
+  return out;
+}
+
 }  // namespace ss4k

@@ -96,10 +96,11 @@ def frnet_step(lr_curr, lr_prev, hr_prev, w: Mapping, nb: int, taps: Optional[di
 
 
 class OracleEgvsrUpscaler:
-    """EgvsrUpscalerService.upscale / upscale_single (egvsr_upscaler.py:172-212) on the CPU."""
+    """EgvsrUpscalerService.upscale / upscale_single (egvsr_upscaler.py:172-212) on the CPU.  ``step``: the generator's step function, called
+    as ``frnet_step`` is (tests/tecogan_oracle.py and tests/frvsr_bi_oracle.py pass theirs)."""
 
-    def __init__(self, w: Mapping, nb: int, lr_shape, output_shape=None):
-        self.w, self.nb, self.lr_shape, self.output_shape = w, nb, tuple(lr_shape), output_shape
+    def __init__(self, w: Mapping, nb: int, lr_shape, output_shape=None, step=frnet_step):
+        self.w, self.nb, self.lr_shape, self.output_shape, self.step = w, nb, tuple(lr_shape), output_shape, step
         self.hr_shape = tuple(4 * i for i in self.lr_shape)
         self.lr_prev = self.hr_prev = None
         self.taps: dict = {}
@@ -116,7 +117,7 @@ class OracleEgvsrUpscaler:
                 self.lr_prev = torch.zeros_like(lr_curr)
             if self.hr_prev is None:
                 self.hr_prev = torch.zeros((1, 3, self.hr_shape[0], self.hr_shape[1]), dtype=lr_curr.dtype)
-            hr_curr = frnet_step(lr_curr, self.lr_prev, self.hr_prev, self.w, self.nb, self.taps)
+            hr_curr = self.step(lr_curr, self.lr_prev, self.hr_prev, self.w, self.nb, self.taps)
             self.taps["lr_curr"], self.taps["hr_curr"] = lr_curr, hr_curr
             self.hr_prev = hr_curr
             self.lr_prev = lr_curr

@@ -9,10 +9,8 @@ align_corners=False)``: it up-samples the padded LR flow before the warp in both
 against the reference's own modules on every fixture of tests/golden/egvsr_bi and tests/golden/tecogan_bi
 (tests/test_frvsr_bi_oracle_cpu.py).
 
-What is imported and what is restated: ``fnet``, ``backward_warp``, ``space_to_depth4``, EGVSR's ``srnet``, ``_conv`` and ``_convt`` are the
-existing modules' own.  ``tecogan_srnet`` and ``OracleBiUpscaler.upscale_single`` RESTATE ``tecogan_oracle.srnet`` and
-``OracleEgvsrUpscaler.upscale_single`` with one line changed each (the skip; the step function): those two bodies name the bicubic function
-and the 'BD' step inline, and the existing oracle files stay exactly as they are, so there is no seam to import them through.
+Nothing is restated: ``fnet``, ``backward_warp``, ``space_to_depth4``, EGVSR's ``srnet``, TecoGAN's ``srnet`` (which takes the skip's up-sampling
+function) and ``OracleEgvsrUpscaler`` (which takes the step function) are the existing modules' own.
 """
 from __future__ import annotations
 
@@ -22,8 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import egvsr_oracle as EO
-from tests.egvsr_oracle import _conv
-from tests.tecogan_oracle import _convt
+from tests import tecogan_oracle as TO
 
 
 def bilinear_upsample4(x) -> torch.Tensor:
@@ -50,16 +47,7 @@ def frnet_step(lr_curr, lr_prev, hr_prev, w: Mapping, nb: int, taps: Optional[di
 
 def tecogan_srnet(lr_curr, hr_prev_tran, w: Mapping, nb: int, taps: Optional[dict] = None) -> torch.Tensor:
     """TecoGAN's SRNet.forward (tecogan_nets.py:130-141) with the bilinear skip."""
-    out = F.relu(_conv(torch.cat([lr_curr, hr_prev_tran], dim=1), w, "srnet.conv_in.0"))
-    for b in range(nb):
-        out = _conv(F.relu(_conv(out, w, f"srnet.resblocks.{b}.conv.0")), w, f"srnet.resblocks.{b}.conv.2") + out
-    up1 = F.relu(_convt(out, w, "srnet.conv_up.0"))
-    up2 = F.relu(_convt(up1, w, "srnet.conv_up.2"))
-    if taps is not None:
-        taps["body"], taps["up1"], taps["up2"] = out, up1, up2
-    out = _conv(up2, w, "srnet.conv_out")
-    out += bilinear_upsample4(lr_curr)
-    return out
+    return TO.srnet(lr_curr, hr_prev_tran, w, nb, taps, upsample=bilinear_upsample4)
 
 
 def tecogan_step(lr_curr, lr_prev, hr_prev, w: Mapping, nb: int, taps: Optional[dict] = None) -> torch.Tensor:
@@ -75,23 +63,4 @@ class OracleBiUpscaler(EO.OracleEgvsrUpscaler):
     """EgvsrUpscalerService.upscale / upscale_single (egvsr_upscaler.py:172-212) around either 'BI' generator, on the CPU."""
 
     def __init__(self, generator: str, w: Mapping, nb: int, lr_shape, output_shape=None):
-        super().__init__(w, nb, lr_shape, output_shape)
-        self.step = STEP[generator]
-
-    def upscale_single(self, img: torch.Tensor) -> torch.Tensor:
-        with torch.no_grad():
-            img = img.permute(2, 0, 1).unsqueeze(0)
-            img = img / 255.0
-            lr_curr = F.interpolate(img, size=self.lr_shape, mode="area")
-            if self.lr_prev is None:
-                self.lr_prev = torch.zeros_like(lr_curr)
-            if self.hr_prev is None:
-                self.hr_prev = torch.zeros((1, 3, self.hr_shape[0], self.hr_shape[1]), dtype=lr_curr.dtype)
-            hr_curr = self.step(lr_curr, self.lr_prev, self.hr_prev, self.w, self.nb, self.taps)
-            self.taps["lr_curr"], self.taps["hr_curr"] = lr_curr, hr_curr
-            self.hr_prev = hr_curr
-            self.lr_prev = lr_curr
-            _hr_curr = torch.clamp(hr_curr, 0, 1)
-            if self.output_shape is not None:
-                _hr_curr = F.interpolate(_hr_curr, size=self.output_shape, mode="area")
-            return (_hr_curr * 255)[0].permute(1, 2, 0).to(torch.uint8)
+        super().__init__(w, nb, lr_shape, output_shape, step=STEP[generator])

@@ -253,10 +253,11 @@ void op_flow_finish(const float* raw, float* flow, int n, int h8, int w8, int h,
   end_launch();
 }
 
+// degradation 'BD' (frvsr.hip) and 'BI' (frvsr_bi.hip:110-121): the two launchers differ in the flow's up-sampling function alone, which reads the
+// same (n, 2, h, w) flow; the warp, the records, the requirements and the grid are the same
 template <typename T>
-void op_warp_s2d_planes(const float* lr_flow, const float* hr_prev, T* out, int n, int h, int w, hipStream_t) {
-  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull, "warp: sizes");   // frvsr.hip:266
-  const char* K = "warp_s2d_planes";
+void warp_s2d(const char* K, const float* lr_flow, const float* hr_prev, T* out, int n, int h, int w) {
+  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull, "warp: sizes");   // frvsr.hip:266, frvsr_bi.hip:111
   begin_launch(K);
   const size_t hw = (size_t)h * w;
   need(K, -1, "lr_flow", "frvsr.hip:146,229-230", lr_flow, (size_t)n * 2 * hw * 4);
@@ -265,14 +266,10 @@ void op_warp_s2d_planes(const float* lr_flow, const float* hr_prev, T* out, int 
   need(K, -1, "out", "frvsr.hip:243", out, (size_t)3 * n * hw * 16 * sizeof(T), true);
   end_launch();
 }
-template void op_warp_s2d_planes<float>(const float*, const float*, float*, int, int, int, hipStream_t);
-template void op_warp_s2d_planes<__half>(const float*, const float*, __half*, int, int, int, hipStream_t);
-
 template <typename T>
-void op_warp_s2d_planes_items(const float* lr_flow, const FrvsrPtrs& hr_prev, T* out, int n, int h, int w, hipStream_t) {
-  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull, "warp (items): sizes");   // frvsr.hip:275
-  for (int i = 0; i < n; ++i) SS4K_REQUIRE(hr_prev.p[i], "warp (items): NULL item");                                               // frvsr.hip:276
-  const char* K = "warp_s2d_planes(items)";
+void warp_s2d_items(const char* K, const float* lr_flow, const FrvsrPtrs& hr_prev, T* out, int n, int h, int w) {
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull, "warp (items): sizes");   // frvsr.hip:275, frvsr_bi.hip:120
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(hr_prev.p[i], "warp (items): NULL item");                                               // frvsr.hip:276, frvsr_bi.hip:121
   begin_launch(K);
   const size_t hw = (size_t)h * w;
   need(K, -1, "lr_flow", "frvsr.hip:146,229-230", lr_flow, (size_t)n * 2 * hw * 4);
@@ -280,8 +277,18 @@ void op_warp_s2d_planes_items(const float* lr_flow, const FrvsrPtrs& hr_prev, T*
   need(K, -1, "out", "frvsr.hip:243", out, (size_t)3 * n * hw * 16 * sizeof(T), true);
   end_launch();
 }
+template <typename T> void op_warp_s2d_planes(const float* f, const float* hp, T* out, int n, int h, int w, hipStream_t) { warp_s2d("warp_s2d_planes", f, hp, out, n, h, w); }
+template <typename T> void op_warp_s2d_bi_planes(const float* f, const float* hp, T* out, int n, int h, int w, hipStream_t) { warp_s2d("warp_s2d_bi_planes", f, hp, out, n, h, w); }
+template <typename T> void op_warp_s2d_planes_items(const float* f, const FrvsrPtrs& hp, T* out, int n, int h, int w, hipStream_t) { warp_s2d_items("warp_s2d_planes(items)", f, hp, out, n, h, w); }
+template <typename T> void op_warp_s2d_bi_planes_items(const float* f, const FrvsrPtrs& hp, T* out, int n, int h, int w, hipStream_t) { warp_s2d_items("warp_s2d_bi_planes(items)", f, hp, out, n, h, w); }
+template void op_warp_s2d_planes<float>(const float*, const float*, float*, int, int, int, hipStream_t);
+template void op_warp_s2d_planes<__half>(const float*, const float*, __half*, int, int, int, hipStream_t);
+template void op_warp_s2d_bi_planes<float>(const float*, const float*, float*, int, int, int, hipStream_t);
+template void op_warp_s2d_bi_planes<__half>(const float*, const float*, __half*, int, int, int, hipStream_t);
 template void op_warp_s2d_planes_items<float>(const float*, const FrvsrPtrs&, float*, int, int, int, hipStream_t);
 template void op_warp_s2d_planes_items<__half>(const float*, const FrvsrPtrs&, __half*, int, int, int, hipStream_t);
+template void op_warp_s2d_bi_planes_items<float>(const float*, const FrvsrPtrs&, float*, int, int, int, hipStream_t);
+template void op_warp_s2d_bi_planes_items<__half>(const float*, const FrvsrPtrs&, __half*, int, int, int, hipStream_t);
 
 template <typename T>
 void op_ps4_conv_tail(const T* in, const float* wb, float* out, int n, int h, int w, hipStream_t) {
@@ -311,6 +318,48 @@ void op_ps4_conv_tail_items(const T* in, const float* wb, const FrvsrPtrs& out, 
 }
 template void op_ps4_conv_tail_items<float>(const float*, const float*, const FrvsrPtrs&, int, int, int, hipStream_t);
 template void op_ps4_conv_tail_items<__half>(const __half*, const float*, const FrvsrPtrs&, int, int, int, hipStream_t);
+
+// TecoGAN's skip: out = conv + x4 up-sampling of lr, bicubic (frvsr.hip:338-370) or bilinear (frvsr_bi.hip:157-168): every tap is clamped into the
+// item's (3, h, w) planes, conv and out are read and written element by element
+void x4_add(const char* K, const float* conv, const float* lr, float* out, int n, int h, int w) {
+  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "x4_add: sizes");   // frvsr.hip:359, frvsr_bi.hip:158
+  begin_launch(K);
+  const size_t hw = (size_t)h * w;
+  need(K, -1, "conv", "frvsr.hip:345", conv, (size_t)n * 48 * hw * 4);
+  need(K, -1, "lr", "frvsr.hip:345", lr, (size_t)n * 3 * hw * 4, false, n == 1 ? 0 : -1);
+  need(K, -1, "out", "frvsr.hip:345", out, (size_t)n * 48 * hw * 4, true, n == 1 ? 0 : -1);
+  end_launch();
+}
+void x4_add_items(const char* K, const float* conv, const FrvsrPtrs& lr, const FrvsrPtrs& out, int n, int h, int w) {
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "x4_add (items): sizes");   // frvsr.hip:365, frvsr_bi.hip:164
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(lr.p[i] && out.p[i], "x4_add (items): NULL item");                                            // frvsr.hip:366, frvsr_bi.hip:165
+  begin_launch(K);
+  const size_t hw = (size_t)h * w;
+  need(K, -1, "conv", "frvsr.hip:355", conv, (size_t)n * 48 * hw * 4);
+  for (int i = 0; i < n; ++i) {
+    need(K, -1, "lr[i]", "frvsr.hip:355", lr.p[i], 3 * hw * 4, false, i);
+    need(K, -1, "out[i]", "frvsr.hip:355", out.p[i], 48 * hw * 4, true, i);
+  }
+  end_launch();
+}
+void op_bicubic4_add(const float* conv, const float* lr, float* out, int n, int h, int w, hipStream_t) { x4_add("bicubic4_add", conv, lr, out, n, h, w); }
+void op_bilinear4_add(const float* conv, const float* lr, float* out, int n, int h, int w, hipStream_t) { x4_add("bilinear4_add", conv, lr, out, n, h, w); }
+void op_bicubic4_add_items(const float* conv, const FrvsrPtrs& lr, const FrvsrPtrs& out, int n, int h, int w, hipStream_t) { x4_add_items("bicubic4_add(items)", conv, lr, out, n, h, w); }
+void op_bilinear4_add_items(const float* conv, const FrvsrPtrs& lr, const FrvsrPtrs& out, int n, int h, int w, hipStream_t) { x4_add_items("bilinear4_add(items)", conv, lr, out, n, h, w); }
+
+// ConvTranspose2d(64, 64, 3, 2, 1, output_padding=1) + bias + ReLU by output phase (conv_up2.hip): four planes at (N, H, W) -> four at (N, 2 H, 2 W)
+void launch_convt3x3s2(ss4k_ctx*, const ConvtArgs& a, int dtype, int, hipStream_t) {
+  SS4K_REQUIRE(a.N > 0 && a.H > 0 && a.W > 0 && (double)a.N * 4.0 * a.H * a.W < 2147483648.0, "convt3x3s2: sizes");   // conv_up2.hip: conv_up2.hip:178
+  const char* K = "convt3x3s2";
+  begin_launch(K);
+  const size_t rec = conv_rec_bytes(dtype), px = (size_t)a.N * a.H * a.W;
+  // the halo tile reads pixels (y, x), y < H, x < W of every item (row H and column W are zero-filled, not read)
+  planes(K, -1, "in", "conv_up2.hip:87-88", a.in, a.in_plane_bytes, 0, 4, px * rec, 0, 1);
+  need(K, -1, "w", "conv_up2.hip:72-73 (pack.cpp: pack_convt3x3s2)", a.w, (size_t)64 * 64 * 9 * (dtype == SS4K_F16 ? 2 : 4));
+  need(K, -1, "bias", "conv_up2.hip:147", a.bias, 64 * 4);
+  planes(K, -1, "out", "conv_up2.hip:157-163", a.out, a.out_plane_bytes, 0, 4, 4 * px * rec, 0, 1, true);
+  end_launch();
+}
 
 template <typename T>
 void op_planes_to_nchw(const T* in, float* out, int n, int channels, int h, int w, hipStream_t) {

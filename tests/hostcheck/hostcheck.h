@@ -1,4 +1,4 @@
-// Host check (tests/test_hostcheck_cpu.py): models.cpp, pack.cpp and frvsr.cpp of the product, linked against HIP stand-ins backed by host
+// Host check (tests/test_hostcheck_cpu.py): models.cpp, pack.cpp, frvsr.cpp, frvsr_teco.cpp and upscaler.cpp of the product, linked against HIP stand-ins backed by host
 // memory and launch auditors instead of the kernels.  No HIP runtime, no Python: the program cannot open a GPU.
 #pragma once
 #include <cstddef>

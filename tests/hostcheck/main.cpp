@@ -6,16 +6,17 @@
 //
 //   hostcheck                      the whole walk; prints one HOSTCHECK line with the counts, exit status 1 on any finding
 //   hostcheck --shard I N          every N-th point of every walk from the I-th (shard 0 also takes the invalid descriptions and the tables)
-//   hostcheck --only PART          rrdbnet | srvgg | bsvd | bounds | fsrcnn | invalid | tables | frvsr-descs | frvsr-steps | frvsr-rounds | upscaler (for measuring)
+//   hostcheck --only PART          rrdbnet | srvgg | bsvd | bounds | fsrcnn | invalid | tables | frvsr-descs | frvsr-steps | frvsr-rounds | upscaler | variants (for measuring)
 //   hostcheck --trace kind dtype scale num_feat num_block num_grow_ch c0 c1 c2 mid_ch interm_ch stream flags frames H W
 //                                  one line per launch of that description at that layer-resolution shape (which route a width takes)
 //   hostcheck --control-shrink I   positive control: one RRDBNet forward with activation buffer I registered one plane short
 //   hostcheck --control-short-blob positive control: a blob one float short must be refused with SS4K_EINVAL
-//   hostcheck --trace-frvsr dtype num_block n h w
-//                                  one line per launch of one FRNet step through each of its three input-packing routes
-//   hostcheck --control-frvsr hr-short | out-short | cur
-//                                  positive controls of the round walk: a slot's hr buffer registered 4 bytes short, a caller's output frame one
-//                                  byte short, a slot's `cur` not flipped after a round (a hook of this program, not of the product)
+//   hostcheck --trace-frvsr dtype num_block n h w [generator degradation route_flags]
+//                                  one line per launch of one step through each of its three input-packing routes (default: EGVSR, 'BD', 0)
+//   hostcheck --control-frvsr hr-short | out-short | cur | teco-hr-short
+//                                  positive controls of the round walk: a slot's hr buffer registered 4 bytes short (teco-: on a TecoGAN / 'BI'
+//                                  upscaler), a caller's output frame one byte short, a slot's `cur` not flipped after a round (a hook of this
+//                                  program, not of the product)
 #include "hostcheck.h"
 #include "../../sharkshark-4k_amd/csrc/frvsr.h"
 #include "../../sharkshark-4k_amd/csrc/upscaler.h"
@@ -401,6 +402,18 @@ int trace(char** v) {
 
 // =================================================================== the frame-recurrent upscaler (frvsr.cpp; DESIGN.md, "Host check")
 long g_fr_accepted = 0, g_fr_refused = 0, g_steps = 0, g_refused_steps = 0, g_rounds = 0, g_refused_rounds = 0;
+// ... and of the walk of the other five (generator, degradation, route) variants (walk_variants), which counts apart: the totals above stay what they were
+long g_var_accepted = 0, g_var_refused = 0, g_var_steps = 0, g_var_rounds = 0, g_var_refused_rounds = 0;
+long *g_step_count = &g_steps, *g_round_count = &g_rounds, *g_refused_round_count = &g_refused_rounds;
+
+// which of the executor's variants an object is: generator, degradation, TecoGAN's transposed-conv route (include/ss4k.h)
+struct Variant { const char* name; int gen, deg, route; };
+const Variant EGVSR_BD{"EGVSR 'BD'", SS4K_FRVSR_EGVSR, SS4K_FRVSR_BD, 0};
+const Variant VARIANTS[] = {{"EGVSR 'BI'", SS4K_FRVSR_EGVSR, SS4K_FRVSR_BI, 0},
+                            {"TecoGAN 'BD' embedded", SS4K_FRVSR_TECOGAN, SS4K_FRVSR_BD, SS4K_FRVSR_CONVT_EMBEDDED},
+                            {"TecoGAN 'BD' phase", SS4K_FRVSR_TECOGAN, SS4K_FRVSR_BD, SS4K_FRVSR_CONVT_PHASE},
+                            {"TecoGAN 'BI' embedded", SS4K_FRVSR_TECOGAN, SS4K_FRVSR_BI, SS4K_FRVSR_CONVT_EMBEDDED},
+                            {"TecoGAN 'BI' phase", SS4K_FRVSR_TECOGAN, SS4K_FRVSR_BI, SS4K_FRVSR_CONVT_PHASE}};
 
 ss4k_frvsr_desc frdesc(int dtype, int nb) { ss4k_frvsr_desc d{}; d.dtype = dtype; d.num_feat = 64; d.num_block = nb; return d; }
 std::string frdesc_str(const ss4k_frvsr_desc& d) {
@@ -409,25 +422,29 @@ std::string frdesc_str(const ss4k_frvsr_desc& d) {
   return b;
 }
 
-// FRNet's convolutions in state_dict order, restated from the reference's module list (egvsr.py:19-61 FNet, :104-127 SRNet), and where each one's
-// weights start in the blob: 16 floats of upsample_func.kernels first; conv_up.{0,2}, conv_out and another 16 kernels after the residual blocks
-struct FrLayers { std::vector<LSpec> specs; std::vector<size_t> at; size_t total = 0; };
-FrLayers fr_layers(const ss4k_frvsr_desc& d) {
+// FRNet's convolutions in state_dict order, restated from the reference's module list (egvsr.py:19-61 FNet, :104-127 SRNet; TecoGAN's SRNet:
+// tecogan_nets.py:101-149), and where each one's weights start in the blob: the 16 floats of upsample_func.kernels first ('BD'; a 'BI' state_dict has
+// no such buffer); after the residual blocks conv_up.{0,2} (transposed, (C_in, C_out, 3, 3): `up_at`, in no `specs` entry), conv_out (Conv2d(4, 3)
+// for EGVSR, Conv2d(nf, 3) for TecoGAN) and the kernels again
+struct FrLayers { std::vector<LSpec> specs; std::vector<size_t> at; size_t up_at[2] = {0, 0}, total = 0; };
+FrLayers fr_layers(const ss4k_frvsr_desc& d, const Variant& v = EGVSR_BD) {
   FrLayers L;
   const int nf = d.num_feat;
   const int fnet[14][2] = {{32, 6}, {32, 32}, {64, 32}, {64, 64}, {128, 64}, {128, 128}, {256, 128}, {256, 256}, {128, 256}, {128, 128}, {64, 128}, {64, 64}, {32, 64}, {2, 32}};
-  size_t pos = 16;
+  const size_t kernels = v.deg == SS4K_FRVSR_BD ? 16 : 0;
+  size_t pos = kernels;
   auto add = [&](int cout, int cin) { L.specs.push_back({cout, cin, false, 0}); L.at.push_back(pos); pos += (size_t)cout * cin * 9 + cout; };
   for (auto& c : fnet) add(c[0], c[1]);
   add(nf, 51);
   for (int i = 0; i < 2 * d.num_block; ++i) add(nf, nf);
-  pos += 2 * ((size_t)nf * nf * 9 + nf) + 3 * 4 * 9 + 3 + 16;
+  for (int k = 0; k < 2; ++k) { L.up_at[k] = pos; pos += (size_t)nf * nf * 9 + nf; }
+  pos += (size_t)3 * (v.gen == SS4K_FRVSR_TECOGAN ? nf : 4) * 9 + 3 + kernels;
   L.total = pos;
   return L;
 }
-std::vector<float> fr_blob(const ss4k_frvsr_desc& d, int which) {
-  const size_t n = frvsr_param_count(d);
-  const FrLayers L = fr_layers(d);
+std::vector<float> fr_blob(const ss4k_frvsr_desc& d, int which, const Variant& v = EGVSR_BD) {
+  const size_t n = frvsr_param_count(d, v.gen, v.deg);
+  const FrLayers L = fr_layers(d, v);
   if (L.total != n) throw std::logic_error("fr_layers consumes " + std::to_string(L.total) + " parameters, frvsr_param_count gives " + std::to_string(n));
   std::vector<float> blob(n);
   uint32_t s = 2463534242u;
@@ -436,6 +453,8 @@ std::vector<float> fr_blob(const ss4k_frvsr_desc& d, int which) {
     const size_t nw = (size_t)L.specs[l].cout * L.specs[l].cin * 9;
     for (size_t i = 0; i < nw; ++i) blob[L.at[l] + i] = (float)((which == 0 ? i % BASE : i / BASE) + 1);
   }
+  if (v.gen == SS4K_FRVSR_TECOGAN)   // the transposed layers' weights too (pack_convt3x3s2's blobs go through the bijection check)
+    for (size_t at : L.up_at) for (size_t i = 0; i < (size_t)d.num_feat * d.num_feat * 9; ++i) blob[at + i] = (float)((which == 0 ? i % BASE : i / BASE) + 1);
   return blob;
 }
 
@@ -488,7 +507,7 @@ std::string run_step(Frvsr& f, int n, int h, int w, int route, bool keep_taps) {
     f.step_items(Frvsr::Items{c.data(), p.data(), &hp, &ho, route == ROUTE_ITEMS_BATCHED}, n, h, w, nullptr);
   }
   f.keep_taps = false;
-  ++g_steps;
+  ++*g_step_count;
   const std::string where = hc::g_where.desc + " | " + sb;
   // the activation requests, rounded as the product's DevBuf rounds them, and the two flow buffers are what workspace_bytes promised.  (It counts
   // flow_raw at flow's size, "at most as large": the raw flow is (n, 2, h // 8 * 8, w // 8 * 8) fp32 - egvsr.py:191-194 - and must be exactly that.)
@@ -516,11 +535,13 @@ void refuse_step(Frvsr& f, const char* name, F&& call) {
 
 bool mine() { return g_point++ % g_shards == g_shard; }
 
-std::unique_ptr<Frvsr> fr_build(ss4k_ctx& ctx, const ss4k_frvsr_desc& d, int which = 0) {
-  const std::vector<float> blob = fr_blob(d, which);
+std::string frdesc_str(const ss4k_frvsr_desc& d, const Variant& v) { return &v == &EGVSR_BD ? frdesc_str(d) : frdesc_str(d) + " " + v.name; }
+
+std::unique_ptr<Frvsr> fr_build(ss4k_ctx& ctx, const ss4k_frvsr_desc& d, int which = 0, const Variant& v = EGVSR_BD) {
+  const std::vector<float> blob = fr_blob(d, which, v);
   auto f = std::make_unique<Frvsr>();
-  f->ctx = &ctx; f->desc = d;
-  hc::g_where.desc = frdesc_str(d); hc::g_where.shape = "build"; hc::g_where.model = nullptr;
+  f->ctx = &ctx; f->desc = d; f->generator = v.gen; f->degradation = v.deg; f->route_flags = v.route;   // api.cpp: ss4k_frvsr_create_ex
+  hc::g_where.desc = frdesc_str(d, v); hc::g_where.shape = "build"; hc::g_where.model = nullptr;
   f->build(blob.data(), blob.size());
   g_weights += (double)blob.size();
   return f;
@@ -716,7 +737,7 @@ struct RoundWalk {
     for (int i = 0; i < S; ++i) had[i] = model[(size_t)ids[i]].has;
     try { call(ids, S, g.ih, g.iw); }
     catch (const std::exception& e) { finding(hc::g_where.desc + " | " + sb + ": exception " + e.what()); ++round_no; return; }
-    ++g_rounds; ++round_no;
+    ++*g_round_count; ++round_no;
     const size_t lr_b = (size_t)3 * g.lh * g.lw * 4, hr_b = 16 * lr_b;
     // per slot buffer: the launches that read it, the ranges written into it
     struct Use { std::vector<const hc::Launch*> reads; int writes = 0; size_t written = 0; };
@@ -788,7 +809,7 @@ struct RoundWalk {
     try { call(ids, S, h, w, null_frame); }
     catch (const Error& e) { threw = true; if (e.code != SS4K_EINVAL) finding(hc::g_where.desc + " | " + hc::g_where.shape + ": Error code " + std::to_string(e.code)); }
     if (!threw) finding(hc::g_where.desc + " | " + hc::g_where.shape + ": accepted");
-    ++g_refused_rounds;
+    ++*g_refused_round_count;
     if (live0 != hc::reg_live()) finding(hc::g_where.desc + " | " + hc::g_where.shape + ": the refusal came after " + std::to_string((long)hc::reg_live() - (long)live0) + " allocations");
     if (!(snap_slots(u) == before) || st0 != u.state_bytes()) finding(hc::g_where.desc + " | " + hc::g_where.shape + ": the refusal came after a slot had changed");
     if (l0 != hc::g_launches || m0 != hc::g_memsets) finding(hc::g_where.desc + " | " + hc::g_where.shape + ": the refusal came after " + std::to_string(hc::g_launches - l0) + " launches and " + std::to_string(hc::g_memsets - m0) + " memsets");
@@ -997,19 +1018,128 @@ void walk_upscaler(ss4k_ctx& ctx) {
   hc::g_log = false;
 }
 
+// =================================================================== the other five (generator, degradation, route) variants of the executor
+// Descriptions, steps and rounds as above, thinned, with counters of their own (g_var_*): the walk above and its totals stay what they were.
+void walk_variants(ss4k_ctx& ctx) {
+  hc::g_log = true;
+  g_step_count = &g_var_steps; g_round_count = &g_var_rounds; g_refused_round_count = &g_var_refused_rounds;
+  const int thin[] = {8, 9, 15, 16, 17, 23, 31, 33};
+  for (const Variant& v : VARIANTS) {
+    const bool teco = v.gen == SS4K_FRVSR_TECOGAN, phase = v.route == SS4K_FRVSR_CONVT_PHASE;
+    // ---- descriptions: num_block 0, 2 x both dtypes, one step each; on the phase route at num_block 2 both pack_convt3x3s2 blobs are bijections
+    for (int nb : {0, 2})
+      for (int dt : {SS4K_F16, SS4K_F32}) {
+        if (!mine()) continue;
+        const ss4k_frvsr_desc d = frdesc(dt, nb);
+        try {
+          std::unique_ptr<Frvsr> a = fr_build(ctx, d, 0, v);
+          ++g_var_accepted;
+          // FNet's 14, conv_in, the blocks' two each; TecoGAN: conv_out, and on the embedded route the two W_eq layers
+          if ((int)a->net.layers.size() != 15 + 2 * nb + (teco ? (phase ? 1 : 3) : 0)) finding(hc::g_where.desc + ": layer count");
+          run_step(*a, 1, 9, 15, ROUTE_CONTIG, false);
+          if (nb == 2 && phase) {
+            std::unique_ptr<Frvsr> b = fr_build(ctx, d, 1, v);
+            for (int k = 0; k < 2; ++k) {
+              bijection_blob(frdesc_str(d, v) + " conv_up." + std::to_string(2 * k) + " (pack_convt3x3s2)", LSpec{64, 64, false, 0}, a->teco.up_w[k].ptr, b->teco.up_w[k].ptr, dt == SS4K_F16);
+              ++g_bij_layers;
+            }
+          }
+        } catch (const std::exception& e) { finding(frdesc_str(d, v) + " | " + hc::g_where.shape + ": exception " + e.what()); }
+        hc::g_where.model = nullptr;
+      }
+    for (int dt : {SS4K_F16, SS4K_F32}) {
+      std::unique_ptr<Frvsr> fp;
+      auto model = [&]() -> Frvsr& { if (!fp) fp = fr_build(ctx, frdesc(dt, 1), 0, v); hc::g_where.desc = frdesc_str(fp->desc, v); return *fp; };
+      // ---- steps: the thinned (h, w) set at n = 1 (taps off and on), 2, 3 (taps on); n = 64 at {8, 9}^2 alone (a 64-channel (4 h, 4 w) tensor for
+      // 64 items of 33 x 33 is 285 MB under the sanitizers); the three packing routes, run_step's checks as they are
+      auto point = [&](int n, int h, int w, std::initializer_list<bool> taps) {
+        if (!mine()) return;
+        Frvsr& f = model();
+        try {
+          for (bool kt : taps) {
+            std::string seq[3];
+            for (int route = 0; route < 3; ++route) seq[route] = run_step(f, n, h, w, route, kt);
+            if (seq[0] != seq[1] || seq[0] != seq[2]) finding(hc::g_where.desc + " | n " + std::to_string(n) + " " + std::to_string(h) + " x " + std::to_string(w) + ": the three routes differ in their launch sequence");
+          }
+        } catch (const std::exception& e) { finding(hc::g_where.desc + " | " + hc::g_where.shape + ": exception " + e.what()); }
+      };
+      for (int h : thin) for (int w : thin) point(1, h, w, {false, true});
+      for (int n : {2, 3}) for (int h : thin) for (int w : thin) point(n, h, w, {true});
+      for (int h : {8, 9}) for (int w : {8, 9}) point(64, h, w, {true});
+      // ---- TecoGAN's group walk: groups of 1 and 2 items at n = 3, 5 - a group offset i0 > 0 and a short last group.  run_step holds that every
+      // item's hr_out is covered and that the activations are what workspace_bytes planned; here: the tail's three workspaces are ONE group's
+      if (teco)
+        for (int gi : {1, 2}) for (int n : {3, 5}) for (auto hw : {std::pair<int, int>{9, 15}, {17, 8}}) for (int route : {ROUTE_CONTIG, ROUTE_ITEMS}) {
+          if (!mine()) continue;
+          Frvsr& f = model();
+          f.teco.dev.group_items = gi;
+          try {
+            run_step(f, n, hw.first, hw.second, route, true);
+            // slots 0..24 are the step's (2 inputs, FNet's 19, the warp's planes, SRNet's 3); 25..27 the tail's U1, U2 (four planes each) and conv_out's
+            const size_t px = (size_t)gi * hw.first * hw.second, rec = (size_t)f.net.rec();
+            const size_t want[3] = {4 * px * rec * 4, 16 * px * rec * 4, 16 * px * rec};
+            bool ok = f.net.acts.size() == 28;
+            for (int k = 0; ok && k < 3; ++k) ok = f.net.acts[25 + (size_t)k].bytes == want[k];
+            if (!ok) finding(hc::g_where.desc + " | " + hc::g_where.shape + ", group_items " + std::to_string(gi) + ": the tail's workspaces are not one group's");
+          } catch (const std::exception& e) { finding(hc::g_where.desc + " | " + hc::g_where.shape + ": exception " + e.what()); }
+          f.teco.dev.group_items = 0;
+        }
+      // ---- rounds: a geometry without resize, one with an input resize, one with an output_shape; max_streams 4; the ragged schedule with its refusals
+      for (const Geo* g : {&GEOS[0], &GEOS[1], &GEOS[2]})
+        for (bool at : {false, true}) {
+          if (!mine()) continue;
+          Frvsr& f = model();
+          std::unique_ptr<FrvsrUpscaler> u = make_upscaler(ctx, f, g->lh, g->lw, g->oh, g->ow, 4);
+          RoundWalk rw(ctx, f, *u, *g, at);
+          schedule(rw, 4);
+        }
+      hc::g_where.model = nullptr;
+    }
+  }
+  g_step_count = &g_steps; g_round_count = &g_rounds; g_refused_round_count = &g_refused_rounds;
+  hc::g_log = false;
+  if (g_shard != 0) return;
+  // ---- refused, with SS4K_EINVAL (and 0 from frvsr_param_count where the generator or the degradation is none): the triple is validated in Frvsr::build
+  const ss4k_frvsr_desc d = frdesc(SS4K_F16, 1);
+  auto refuse_variant = [&](const char* name, const Variant& obj, const Variant& blob_of, bool no_count) {
+    hc::g_where.desc = std::string("invalid frvsr variant: ") + name; hc::g_where.shape = "build";
+    try {
+      if (no_count && frvsr_param_count(d, obj.gen, obj.deg) != 0) finding(std::string(name) + ": frvsr_param_count answers " + std::to_string(frvsr_param_count(d, obj.gen, obj.deg)));
+      const std::vector<float> blob = fr_blob(d, 0, blob_of);
+      Frvsr f; f.ctx = &ctx; f.desc = d; f.generator = obj.gen; f.degradation = obj.deg; f.route_flags = obj.route;
+      f.build(blob.data(), blob.size());
+      finding(std::string(name) + ": built");
+    } catch (const Error& e) {
+      if (e.code == SS4K_EINVAL) ++g_var_refused; else finding(std::string(name) + ": Error code " + std::to_string(e.code));
+    } catch (const std::exception& e) { finding(std::string(name) + ": exception " + e.what()); }
+  };
+  const Variant &EGVSR_BI = VARIANTS[0], &TECO_BD = VARIANTS[1];
+  for (int g : {-1, 2}) refuse_variant("generator", Variant{"", g, SS4K_FRVSR_BD, 0}, EGVSR_BD, true);
+  for (int g : {-1, 2}) refuse_variant("degradation", Variant{"", SS4K_FRVSR_EGVSR, g, 0}, EGVSR_BD, true);
+  refuse_variant("route flags 2 (unknown bit)", Variant{"", SS4K_FRVSR_TECOGAN, SS4K_FRVSR_BD, 2}, TECO_BD, false);
+  refuse_variant("route flags 5 (both pins)", Variant{"", SS4K_FRVSR_TECOGAN, SS4K_FRVSR_BD, 5}, TECO_BD, false);
+  refuse_variant("route flags 1 on EGVSR", Variant{"", SS4K_FRVSR_EGVSR, SS4K_FRVSR_BD, 1}, EGVSR_BD, false);
+  refuse_variant("a 'BD' blob on a 'BI' object", EGVSR_BI, EGVSR_BD, false);
+  refuse_variant("a 'BI' blob on a 'BD' object", EGVSR_BD, EGVSR_BI, false);
+  refuse_variant("EGVSR's blob on TecoGAN", TECO_BD, EGVSR_BD, false);
+}
+
 // ---- positive controls of the round walk: each must be reported at exactly the launches that touch the object named (the test reads the launch
-// kinds from the trace).  One fp32 upscaler of 4 slots at lr 8 x 8, round_at, launches numbered through all rounds.
+// kinds from the trace).  One fp32 upscaler of 4 slots at lr 8 x 8, round_at, launches numbered through all rounds.  teco-hr-short: hr-short on a
+// TecoGAN / 'BI' generator, whose warp and skip are the launchers of frvsr_bi.hip.
 int control_frvsr(const char* what) {
   ss4k_ctx ctx;
   hc::g_log = true; hc::g_trace = true;
-  std::unique_ptr<Frvsr> f = fr_build(ctx, frdesc(SS4K_F32, 1));
-  hc::g_where.desc = frdesc_str(f->desc);
+  const bool teco = !std::strncmp(what, "teco-", 5);
+  const Variant& v = teco ? VARIANTS[3] : EGVSR_BD;
+  std::unique_ptr<Frvsr> f = fr_build(ctx, frdesc(SS4K_F32, 1), 0, v);
+  hc::g_where.desc = frdesc_str(f->desc, v);
   std::unique_ptr<FrvsrUpscaler> u = make_upscaler(ctx, *f, 8, 8, 0, 0, 4);
   RoundWalk rw(ctx, *f, *u, GEOS[0], true);
   rw.keep_launch_index = true; hc::g_where.launch = 0;
   rw.good({2, 0});
   if (hc::g_violations || g_findings) { std::printf("CONTROL setup failed\n"); return 2; }
-  if (!std::strcmp(what, "hr-short")) {          // slot 2's previous HR frame registered 4 bytes short: read by round 1's warp, written by round 2's tail, read by its output glue
+  if (!std::strcmp(what, "hr-short") || !std::strcmp(what, "teco-hr-short")) {   // slot 2's previous HR frame registered 4 bytes short: read by round 1's warp, written by round 2's tail, read by its output glue
     hc::reg_shrink(u->slots[2].hr[u->slots[2].cur].ptr, 4);
     rw.good({2}); rw.good({3, 2, 0});
   } else if (!std::strcmp(what, "out-short")) {  // item 1's output frame one byte short: the round's output glue
@@ -1024,13 +1154,14 @@ int control_frvsr(const char* what) {
   return 0;
 }
 
-// --trace-frvsr dtype num_block n h w: the launches of one step through each of the three routes
-int trace_frvsr(char** v) {
+// --trace-frvsr dtype num_block n h w [generator degradation route_flags]: the launches of one step through each of the three routes
+int trace_frvsr(char** v, bool with_variant) {
   ss4k_ctx ctx;
   hc::g_log = true;
   try {
-    std::unique_ptr<Frvsr> f = fr_build(ctx, frdesc(std::atoi(v[0]), std::atoi(v[1])));
-    hc::g_where.desc = frdesc_str(f->desc); hc::g_trace = true;
+    const Variant var = with_variant ? Variant{"(--trace-frvsr)", std::atoi(v[5]), std::atoi(v[6]), std::atoi(v[7])} : EGVSR_BD;
+    std::unique_ptr<Frvsr> f = fr_build(ctx, frdesc(std::atoi(v[0]), std::atoi(v[1])), 0, with_variant ? var : EGVSR_BD);
+    hc::g_where.desc = frdesc_str(f->desc, with_variant ? var : EGVSR_BD); hc::g_trace = true;
     for (int route = 0; route < 3; ++route) {
       std::printf("ROUTE %s\n", ROUTE_NAMES[route]);
       run_step(*f, std::atoi(v[2]), std::atoi(v[3]), std::atoi(v[4]), route, true);
@@ -1048,10 +1179,10 @@ int main(int argc, char** argv) {
   if (argc >= 3 && !std::strcmp(argv[1], "--control-shrink")) return control_shrink(std::atoi(argv[2]));
   if (argc >= 2 && !std::strcmp(argv[1], "--control-short-blob")) return control_short_blob();
   if (argc >= 3 && !std::strcmp(argv[1], "--control-frvsr")) return control_frvsr(argv[2]);
-  if (argc == 7 && !std::strcmp(argv[1], "--trace-frvsr")) return trace_frvsr(argv + 2);
+  if ((argc == 7 || argc == 10) && !std::strcmp(argv[1], "--trace-frvsr")) return trace_frvsr(argv + 2, argc == 10);
   const char* only = (argc >= 3 && !std::strcmp(argv[1], "--only")) ? argv[2] : nullptr;   // one part of the walk (measurement)
   if (argc >= 4 && !std::strcmp(argv[1], "--shard")) { g_shard = std::atoi(argv[2]); g_shards = std::max(1, std::atoi(argv[3])); }
-  if (g_shard < 0 || g_shard >= g_shards) { std::printf("usage: hostcheck [--shard I N | --only PART | --control-shrink BUFFER | --control-short-blob | --control-frvsr WHAT | --trace-frvsr DTYPE NB N H W]\n"); return 2; }
+  if (g_shard < 0 || g_shard >= g_shards) { std::printf("usage: hostcheck [--shard I N | --only PART | --control-shrink BUFFER | --control-short-blob | --control-frvsr WHAT | --trace-frvsr DTYPE NB N H W [GENERATOR DEGRADATION ROUTE]]\n"); return 2; }
   const auto t0 = std::chrono::steady_clock::now();
   {
     ss4k_ctx ctx;
@@ -1061,13 +1192,15 @@ int main(int argc, char** argv) {
     if (!only || !std::strcmp(only, "frvsr-steps")) walk_frvsr_steps(ctx);
     if (!only || !std::strcmp(only, "frvsr-rounds")) walk_frvsr_rounds(ctx);
     if (!only || !std::strcmp(only, "upscaler")) walk_upscaler(ctx);
+    if (!only || !std::strcmp(only, "variants")) walk_variants(ctx);
     if ((!only && g_shard == 0) || (only && !std::strcmp(only, "tables"))) walk_tables();
   }
   if (hc::reg_live()) finding(std::to_string(hc::reg_live()) + " allocations still live at the end");
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::printf("HOSTCHECK accepted=%ld refused=%ld shapes=%ld launches=%ld bijection_layers=%ld frvsr_accepted=%ld frvsr_refused=%ld steps=%ld refused_steps=%ld rounds=%ld refused_rounds=%ld jobs=%ld refused_jobs=%ld "
-              "violations=%ld findings=%ld\n", g_accepted, g_refused, g_shapes, hc::g_launches, g_bij_layers, g_fr_accepted, g_fr_refused, g_steps, g_refused_steps, g_rounds, g_refused_rounds, g_jobs, g_refused_jobs,
-              hc::g_violations, g_findings);
+              "variant_accepted=%ld variant_refused=%ld variant_steps=%ld variant_rounds=%ld variant_refused_rounds=%ld violations=%ld findings=%ld\n",
+              g_accepted, g_refused, g_shapes, hc::g_launches, g_bij_layers, g_fr_accepted, g_fr_refused, g_steps, g_refused_steps, g_rounds, g_refused_rounds, g_jobs, g_refused_jobs,
+              g_var_accepted, g_var_refused, g_var_steps, g_var_rounds, g_var_refused_rounds, hc::g_violations, g_findings);
   std::printf("TIME %.1f s for %.0f M parameters packed\n", sec, g_weights / 1e6);
   return (hc::g_violations || g_findings) ? 1 : 0;
 }

@@ -23,8 +23,9 @@ def _convt(x, w, name):
     return F.conv_transpose2d(x, _t(w[name + ".weight"]), _t(w[name + ".bias"]), stride=2, padding=1, output_padding=1)
 
 
-def srnet(lr_curr, hr_prev_tran, w: Mapping, nb: int, taps: Optional[dict] = None) -> torch.Tensor:
-    """SRNet.forward (tecogan_nets.py:130-141); layers :109-128."""
+def srnet(lr_curr, hr_prev_tran, w: Mapping, nb: int, taps: Optional[dict] = None, upsample=None) -> torch.Tensor:
+    """SRNet.forward (tecogan_nets.py:130-141); layers :109-128.  ``upsample``: the skip's x4 up-sampling function of ``lr_curr`` (default: the
+    bicubic one of degradation='BD')."""
     out = F.relu(_conv(torch.cat([lr_curr, hr_prev_tran], dim=1), w, "srnet.conv_in.0"))
     for b in range(nb):
         out = _conv(F.relu(_conv(out, w, f"srnet.resblocks.{b}.conv.0")), w, f"srnet.resblocks.{b}.conv.2") + out
@@ -33,7 +34,7 @@ def srnet(lr_curr, hr_prev_tran, w: Mapping, nb: int, taps: Optional[dict] = Non
     if taps is not None:
         taps["body"], taps["up1"], taps["up2"] = out, up1, up2
     out = _conv(up2, w, "srnet.conv_out")
-    out += EO.bicubic_upsample4(lr_curr, w.get("srnet.upsample_func.kernels"))
+    out += upsample(lr_curr) if upsample else EO.bicubic_upsample4(lr_curr, w.get("srnet.upsample_func.kernels"))
     return out
 
 
@@ -54,20 +55,5 @@ def frnet_step(lr_curr, lr_prev, hr_prev, w: Mapping, nb: int, taps: Optional[di
 class OracleTecoganUpscaler(EO.OracleEgvsrUpscaler):
     """EgvsrUpscalerService.upscale / upscale_single (egvsr_upscaler.py:172-212) around this generator, on the CPU."""
 
-    def upscale_single(self, img: torch.Tensor) -> torch.Tensor:
-        with torch.no_grad():
-            img = img.permute(2, 0, 1).unsqueeze(0)
-            img = img / 255.0
-            lr_curr = F.interpolate(img, size=self.lr_shape, mode="area")
-            if self.lr_prev is None:
-                self.lr_prev = torch.zeros_like(lr_curr)
-            if self.hr_prev is None:
-                self.hr_prev = torch.zeros((1, 3, self.hr_shape[0], self.hr_shape[1]), dtype=lr_curr.dtype)
-            hr_curr = frnet_step(lr_curr, self.lr_prev, self.hr_prev, self.w, self.nb, self.taps)
-            self.taps["lr_curr"], self.taps["hr_curr"] = lr_curr, hr_curr
-            self.hr_prev = hr_curr
-            self.lr_prev = lr_curr
-            _hr_curr = torch.clamp(hr_curr, 0, 1)
-            if self.output_shape is not None:
-                _hr_curr = F.interpolate(_hr_curr, size=self.output_shape, mode="area")
-            return (_hr_curr * 255)[0].permute(1, 2, 0).to(torch.uint8)
+    def __init__(self, w: Mapping, nb: int, lr_shape, output_shape=None):
+        super().__init__(w, nb, lr_shape, output_shape, step=frnet_step)

@@ -1,5 +1,5 @@
-"""GPU: both frame-recurrent generators built with degradation 'BI' (``ss4k_frvsr_create_ex(..., SS4K_FRVSR_BI, ...)``; csrc/frvsr_bi.hip,
-csrc/frvsr_bi.cpp) end to end.
+"""GPU: both frame-recurrent generators built with degradation 'BI' (``ss4k_frvsr_create_ex(..., SS4K_FRVSR_BI, ...)``; csrc/frvsr_bi.hip;
+the branches on ``degradation`` in csrc/frvsr.cpp and csrc/frvsr_teco.cpp) end to end.
 
 * fp32 models against every step and sequence fixture the reference produced with ``degradation='BI'`` (tests/golden/egvsr_bi,
   tests/golden/tecogan_bi) at the project's parity bar, rtol 1e-3 / atol 1e-4; TecoGAN on both routes of the transposed layers.

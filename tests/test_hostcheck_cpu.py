@@ -1,4 +1,4 @@
-"""CPU: the host check - the product's models.cpp, pack.cpp and frvsr.cpp, host side only, under ASan + UBSan (tests/hostcheck, DESIGN.md "Host check").
+"""CPU: the host check - the product's models.cpp, pack.cpp, frvsr.cpp, frvsr_teco.cpp and upscaler.cpp, host side only, under ASan + UBSan (tests/hostcheck, DESIGN.md "Host check").
 
 The program links HIP stand-ins backed by host memory and launch auditors in place of the kernels - no HIP runtime, no Python, so it
 cannot open a GPU - and runs as a plain child process (nothing is preloaded).  It walks the lattice of model descriptions: every
@@ -46,9 +46,24 @@ single_mode x SR model x denoising x lr_hr_resize x output_shape x taps x frame 
 checks, ``st_acc2`` zero-filled whenever ``acc2_clean`` is set, and every job refused or accepted as its sizes say, a refusal before the job's
 first launch and allocation.
 
+The other five (generator, degradation, route) variants of the executor - (EGVSR, 'BI'), (TecoGAN, 'BD' | 'BI') x (embedded | phase) - walked
+after all of the above with counters of their own, so that the totals above stay what they were:
+
+* descriptions: 5 variants x num_block 0, 2 x both dtypes = 20 accepted (layer count, one step at 1 x 9 x 15); on the phase route at num_block 2 both
+  ``pack_convt3x3s2`` blobs go through the bijection check in both dtypes (2 variants x 2 dtypes x 2 blobs = 8 more layers); 10 refused
+  (generator -1, 2; degradation -1, 2; route flags 2, 5 and 1 on EGVSR; a 'BD' blob on a 'BI' object and the reverse; EGVSR's blob on TecoGAN).
+* steps, per variant and dtype at num_block 1: h, w in {8, 9, 15, 16, 17, 23, 31, 33} at n = 1 with taps off and on (64 x 2), n = 2, 3 with taps on
+  (2 x 64), n = 64 at {8, 9}^2 (4), each through the three packing routes: 3 x 260 = 780, x 10 = 7800.  TecoGAN's group walk: ``group_items`` 1, 2 x
+  n = 3, 5 x (9, 15), (17, 8) x contiguous, items = 16 per variant and dtype, x 8 = 128 (a group offset > 0, a short last group; the tail's three
+  workspaces are one group's).  With the 20 of the descriptions: 7948.
+* rounds: 5 variants x both dtypes x 3 geometries (identity, area in, area out) x ``round`` / ``round_at`` at max_streams 4 = 60 schedules of 7 rounds:
+  420; each with 6 refused rounds, 7 under ``round_at`` (the NULL frame): 30 x 6 + 30 x 7 = 390.
+
 14 230 steps, 720 rounds, 724 refused rounds, 2903 upscaler jobs, 989 refused jobs.  Measured on 8 CPUs: 8 shards side by side, 62 s wall (52 s
 before the frame-recurrent and frame upscaler parts; 7.6 G parameters packed at 65 ns each; the slowest shard 62 s, the fastest 55 s).  The walk
-has ONE deadline (DEADLINE), not one per shard.
+has ONE deadline (DEADLINE), not one per shard.  With the variant walk (7948 more steps, 420 more rounds): 62 s wall on 8 CPUs, beside 72 s for the walk
+without it measured right after it on the same machine - the variant walk alone takes 30 s in ONE process, some 4 s of each shard, inside the
+run-to-run spread of the whole walk; nothing had to be thinned.
 """
 import os
 import re
@@ -61,9 +76,10 @@ import sharkshark4k_amd  # noqa: F401
 from sharkshark4k_amd import build as B
 
 SHARDS = 8        # side by side; a command on a GPU machine may use 16 CPUs
-DEADLINE = 600    # seconds for the whole walk (measured: 62 s on 8 CPUs, 7.8 CPU-minutes - a machine with one free core still fits)
+DEADLINE = 600    # seconds for the whole walk (measured: 62 s on 8 CPUs, 7.8 CPU-minutes before the variant walk, which adds 0.5 - a machine with one free core still fits)
 ACCEPTED, REFUSED, SHAPES = 1184, 104, 9472
 FR_ACCEPTED, FR_REFUSED, STEPS, REFUSED_STEPS, ROUNDS, REFUSED_ROUNDS, JOBS, REFUSED_JOBS = 10, 16, 14230, 24, 720, 724, 2903, 989
+VAR_ACCEPTED, VAR_REFUSED, VAR_STEPS, VAR_ROUNDS, VAR_REFUSED_ROUNDS = 20, 10, 7948, 420, 390   # the module docstring derives them
 
 
 @pytest.fixture(scope="module")
@@ -90,7 +106,7 @@ def test_program_links_no_gpu_runtime(prog):
 def test_lattice_walk_is_clean(prog):
     procs = [subprocess.Popen([prog, "--shard", str(i), str(SHARDS)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=_env()) for i in range(SHARDS)]
     total = dict(accepted=0, refused=0, shapes=0, launches=0, bijection_layers=0, frvsr_accepted=0, frvsr_refused=0, steps=0, refused_steps=0, rounds=0, refused_rounds=0, jobs=0, refused_jobs=0,
-                 violations=0, findings=0)
+                 variant_accepted=0, variant_refused=0, variant_steps=0, variant_rounds=0, variant_refused_rounds=0, violations=0, findings=0)
     deadline = time.monotonic() + DEADLINE   # one limit for the whole walk, not one per shard
     try:
         for i, p in enumerate(procs):
@@ -110,9 +126,11 @@ def test_lattice_walk_is_clean(prog):
                 p.kill()
     assert (total["accepted"], total["refused"], total["shapes"]) == (ACCEPTED, REFUSED, SHAPES), total
     assert total["violations"] == 0 and total["findings"] == 0, total
-    assert total["launches"] > 800000 and total["bijection_layers"] == 13904 + 38, total
+    assert total["launches"] > 800000 and total["bijection_layers"] == 13904 + 38 + 8, total
     got = tuple(total[k] for k in ("frvsr_accepted", "frvsr_refused", "steps", "refused_steps", "rounds", "refused_rounds", "jobs", "refused_jobs"))
     assert got == (FR_ACCEPTED, FR_REFUSED, STEPS, REFUSED_STEPS, ROUNDS, REFUSED_ROUNDS, JOBS, REFUSED_JOBS), total
+    got = tuple(total[k] for k in ("variant_accepted", "variant_refused", "variant_steps", "variant_rounds", "variant_refused_rounds"))
+    assert got == (VAR_ACCEPTED, VAR_REFUSED, VAR_STEPS, VAR_ROUNDS, VAR_REFUSED_ROUNDS), total
 
 
 # One RRDBNet forward (num_feat 64, num_grow_ch 32, x4, NO_DENSE, one frame of 7 x 9): launch 0 packs the input, launch 1 is conv_first,
@@ -188,15 +206,32 @@ def test_frvsr_step_launch_sequence_of_the_three_routes(prog):
     }, got
 
 
+# route flags 1 = SS4K_FRVSR_CONVT_EMBEDDED: both transposed layers as conv3x3 layers 17, 18 (W_eq + PixelShuffle(2)), conv_out is layer 19;
+# 4 = SS4K_FRVSR_CONVT_PHASE: two launches of the phase kernel, conv_out is layer 17
+@pytest.mark.parametrize("route,tail", [(1, ["conv3x3:17", "conv3x3:18", "conv3x3:19"]), (4, ["convt3x3s2", "convt3x3s2", "conv3x3:17"])], ids=["embedded", "phase"])
+def test_tecogan_bi_step_launch_sequence_of_the_three_routes(prog, route, tail):
+    """One fp16 TecoGAN / 'BI' step, num_block 1, two items of 9 x 15 (one group), taps on: the warp and the skip are frvsr_bi.hip's launchers."""
+    r = _run(prog, "--trace-frvsr", "1", "1", "2", "9", "15", "1", "1", str(route))
+    assert r.returncode == 0 and r.stderr == "", r.stdout[-2000:] + r.stderr[-2000:]
+    got = {k: [kind for _, kind in v] for k, v in _launches(r.stdout).items()}
+    assert got == {
+        "contiguous": ["pack_input"] * 2 + FNET + ["warp_s2d_bi_planes"] + SRNET + tail + ["bilinear4_add"],
+        "items": ["pack_input"] * 4 + FNET + ["warp_s2d_bi_planes(items)"] + SRNET + tail + ["bilinear4_add(items)"],
+        "items, pack_batched": ["pack_lr(items)"] + FNET + ["warp_s2d_bi_planes(items)"] + SRNET + tail + ["bilinear4_add(items)"],
+    }, got
+
+
 # Each control of the round walk must be reported at exactly the launches that touch the object named, which the test finds in the trace by
 # kind: round 0 opens slots 2 and 0; the fault is injected after it.
 #   hr-short   the HR frame slot 2 wrote in round 0, registered 4 bytes short: round 1 warps it, round 2 writes it again (tail) and converts it (output glue)
 #   out-short  the output frame of item 1 of round 1, one byte short: that round's output glue
 #   cur        slot 2's `cur` flipped back after round 0 (a hook of the program, not of the product): round 1 packs and warps the wrong previous frames
+#   teco-hr-short  hr-short on a TecoGAN / 'BI' fp32 upscaler: the warp and the skip that touch the frame are the launchers of frvsr_bi.hip
 @pytest.mark.parametrize("control,touching", [
     ("hr-short", [("1", "warp_s2d_planes(items)"), ("2", "ps4_conv_tail(items)"), ("2", "frames_out(items)")]),
     ("out-short", [("1", "frames_out(items)")]),
     ("cur", [("1", "pack_lr(items)"), ("1", "warp_s2d_planes(items)")]),
+    ("teco-hr-short", [("1", "warp_s2d_bi_planes(items)"), ("2", "bilinear4_add(items)"), ("2", "frames_out(items)")]),
 ])
 def test_control_of_the_round_walk_is_reported_where_it_touches(prog, control, touching):
     r = _run(prog, "--control-frvsr", control)
