@@ -3,8 +3,8 @@
  * same sources as libss4k_hip.so; a superset of include/ss4k.h).  Not part of the product library:
  * the instrumented / alternative-tile-shape instantiations of the conv kernel live only here.
  * Used by tools/stamp4.py, tools/traffic_ablate.py, tools/conv5_routes.py, tests/test_gpu_glue_budget.py,
- * tests/test_gpu_frvsr_glue_budget.py (the ss4k_dev_op_frvsr_* launchers), tests/test_gpu_frvsr_budget.py (ss4k_dev_frvsr_step_taps) and tests/test_gpu_memory_hygiene.py (guard mode,
- * through tests/drive_guarded.py).
+ * tests/test_gpu_frvsr_glue_budget.py (the ss4k_dev_op_frvsr_* launchers), tests/test_gpu_frvsr_budget.py (ss4k_dev_frvsr_step_taps), tests/test_gpu_memory_hygiene.py (guard mode,
+ * through tests/drive_guarded.py), tests/test_gpu_lane_order.py and tests/test_gpu_host_io_order.py (ss4k_dev_op_spin, ss4k_dev_lane_*).
  */
 #ifndef SS4K_DEV_H
 #define SS4K_DEV_H
@@ -138,6 +138,29 @@ int ss4k_dev_frvsr_embed_convt(const float* wt_and_bias, int nf, float* out, siz
 /* Host only: Wt (64, 64, 3, 3) in the fragment order of the phase kernel (csrc/conv_up2.hip states the map), in `dtype`: 36 864 values of
  * fp16 (73 728 bytes) or fp32 (147 456 bytes) */
 int ss4k_dev_frvsr_pack_convt(const float* wt, int dtype, void* out, size_t capacity_bytes);
+
+/* ---- stream ordering: what tests/test_gpu_lane_order.py and tests/test_gpu_host_io_order.py delay streams with, and the frame lanes'
+ * (csrc/models.cpp: launch_lanes, lanes_begin, lanes_join, abort_forward) handicap, counters and positive control.  The state belongs
+ * to the context; none of it exists in the product library. */
+/* One idle wave that occupies hip_stream for `ticks` of the 100 MHz clock (op_lane_spin, csrc/glue.h); the kernel itself caps a launch at
+ * 50 000 ticks = 0.5 ms: a longer delay is several launches. */
+int ss4k_dev_op_spin(ss4k_ctx* ctx, unsigned ticks, void* hip_stream);
+/* While ticks != 0, and only on the two-chain branch of launch_lanes, every launch pair is preceded by one spin of `ticks`: on the context's
+ * lane stream (lane = 1: the second chain trails at every join) or on the caller's stream (lane = 0: the caller's chain trails at every
+ * re-fork, i.e. after a join + op_temporal_shift).  ticks = 0 switches it off.  SS4K_EINVAL for another lane. */
+int ss4k_dev_lane_handicap(ss4k_ctx* ctx, int lane, unsigned ticks);
+/* forks: fork events recorded; joins: joins that made the caller's stream wait - lanes_join with a fork open, and abort_forward's join of a
+ * forward that failed; spins: handicap spins launched.  Since the context was made or the last _reset. */
+int ss4k_dev_lane_counts(ss4k_ctx* ctx, int64_t* forks, int64_t* joins, int64_t* spins);
+int ss4k_dev_lane_counts_reset(ss4k_ctx* ctx);
+/* Positive control: in the NEXT forward of a model of this context that may fork, the k-th (1-based) join that is not the end-of-forward
+ * join records the lane's event but leaves the caller's hipStreamWaitEvent out (and is not counted in `joins`); the next launch re-forks as
+ * usual.  k = 0 disarms.  The end-of-forward join and abort_forward are never skipped: when the call returns, the caller's stream is
+ * ordered after every launch of both chains.  Honoured only when the forward repeats the (n, h, w) of the model's last completed forward -
+ * every activation request then fits the buffer it finds, so nothing is allocated, re-grown or released between the dropped join and the
+ * final one, and every access stays inside the buffers: the skipped wait only lets op_temporal_shift and the caller's chain read
+ * activations before the second chain wrote them (wrong VALUES, never a fault).  Ignored (and disarmed) on any other shape. */
+int ss4k_dev_lane_drop_join(ss4k_ctx* ctx, int k);
 
 /* Route report: every glue launcher counts the kernel route it chose under a static name ("glue::area_whole<NORM,8,half>", ...).
  * _read returns the index-th route in name order (SS4K_EINVAL past the last), _reset clears the table.  Process-wide. */

@@ -62,6 +62,8 @@ DEV_SYMBOLS = [
     "ss4k_dev_frvsr_tail_taps", "ss4k_dev_frvsr_embed_convt", "ss4k_dev_frvsr_pack_convt",
     # guard mode: red zones and 0xFF poison for every device buffer of the library (tests/test_gpu_memory_hygiene.py)
     "ss4k_dev_guard_enable", "ss4k_dev_guard_check", "ss4k_dev_guard_poison", "ss4k_dev_guard_selftest", "ss4k_dev_guard_poison_frvsr",
+    # stream ordering: a bounded delay on any stream; the frame lanes' handicap, counters and dropped-join control (tests/test_gpu_lane_order.py)
+    "ss4k_dev_op_spin", "ss4k_dev_lane_handicap", "ss4k_dev_lane_counts", "ss4k_dev_lane_counts_reset", "ss4k_dev_lane_drop_join",
 ]
 
 
@@ -195,6 +197,13 @@ def load(path: str) -> C.CDLL:
         L.ss4k_dev_guard_selftest.argtypes = [vp]
         if hasattr(L, "ss4k_dev_guard_poison_frvsr"):
             L.ss4k_dev_guard_poison_frvsr.argtypes = [vp, vp, C.POINTER(i), C.POINTER(sz), C.POINTER(sz)]
+    if hasattr(L, "ss4k_dev_lane_counts"):  # dev library only: stream ordering
+        i64p = C.POINTER(C.c_int64)
+        L.ss4k_dev_op_spin.argtypes = [vp, C.c_uint, vp]
+        L.ss4k_dev_lane_handicap.argtypes = [vp, i, C.c_uint]
+        L.ss4k_dev_lane_counts.argtypes = [vp, i64p, i64p, i64p]
+        L.ss4k_dev_lane_counts_reset.argtypes = [vp]
+        L.ss4k_dev_lane_drop_join.argtypes = [vp, i]
     L.ss4k_prof_enable.argtypes = [vp, i]
     L.ss4k_prof_reset.argtypes = [vp]
     L.ss4k_prof_read.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]

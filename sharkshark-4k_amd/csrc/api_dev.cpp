@@ -282,6 +282,30 @@ int ss4k_dev_frvsr_pack_convt(const float* wt, int dtype, void* out, size_t capa
     std::copy(pk.begin(), pk.end(), static_cast<uint8_t*>(out));
   });
 }
+// ---- stream ordering (tests/test_gpu_lane_order.py, tests/test_gpu_host_io_order.py): a bounded delay on any stream, and the frame lanes'
+// handicap, counters and positive control (the state lives in ss4k_ctx and Model; Model::launch_lanes / lanes_begin / lanes_join read it)
+int ss4k_dev_op_spin(ss4k_ctx* c, unsigned ticks, void* s) {
+  return guard([&] { SS4K_REQUIRE(c, "ss4k_dev_op_spin: NULL ctx"); op_lane_spin(ticks, (hipStream_t)s); SS4K_HIP(hipGetLastError()); });
+}
+int ss4k_dev_lane_handicap(ss4k_ctx* c, int lane, unsigned ticks) {
+  return guard([&] {
+    SS4K_REQUIRE(c && (lane == 0 || lane == 1), "ss4k_dev_lane_handicap: lane is 0 (the caller's stream) or 1 (the lane stream)");
+    c->dev_handicap_lane = lane; c->dev_handicap_ticks = ticks;
+  });
+}
+int ss4k_dev_lane_counts(ss4k_ctx* c, int64_t* forks, int64_t* joins, int64_t* spins) {
+  return guard([&] {
+    SS4K_REQUIRE(c && forks && joins && spins, "ss4k_dev_lane_counts: NULL argument");
+    *forks = c->dev_lane_forks; *joins = c->dev_lane_joins; *spins = c->dev_lane_spins;
+  });
+}
+int ss4k_dev_lane_counts_reset(ss4k_ctx* c) {
+  return guard([&] { SS4K_REQUIRE(c, "ss4k_dev_lane_counts_reset: NULL ctx"); c->dev_lane_forks = c->dev_lane_joins = c->dev_lane_spins = 0; });
+}
+int ss4k_dev_lane_drop_join(ss4k_ctx* c, int k) {
+  return guard([&] { SS4K_REQUIRE(c && k >= 0, "ss4k_dev_lane_drop_join: bad argument"); c->dev_drop_join = k; });
+}
+
 int ss4k_dev_glue_routes_reset(void) { return guard([&] { glue_routes_reset(); }); }
 int ss4k_dev_glue_routes_read(int index, char* name, size_t name_capacity, int64_t* launches) {
   return guard([&] {

@@ -166,6 +166,14 @@ struct ss4k_ctx {
   std::vector<hipStream_t> lane_parked;
   int lane_replaced = 0;
   void lane_check(hipStream_t caller);
+#ifdef SS4K_DEV
+  // stream-ordering tests (include/ss4k_dev.h, ss4k_dev_lane_*; tests/test_gpu_lane_order.py): a spin in front of every launch pair of the
+  // two-chain branch of Model::launch_lanes, counters of the fork / join protocol, and the positive control - one mid-forward join whose
+  // wait on the caller's stream is left out
+  int dev_handicap_lane = 0; unsigned dev_handicap_ticks = 0;
+  int64_t dev_lane_forks = 0, dev_lane_joins = 0, dev_lane_spins = 0;
+  int dev_drop_join = 0;   // armed for the next forward that may fork (Model::lanes_begin takes it)
+#endif
   // conv sections (bench): wall time on the caller's stream from a forward's first conv launch to the end of its last
   std::vector<ss4k::ProfEvent> prof_sections;
   double prof_section_ms = 0;

@@ -338,7 +338,16 @@ void Model::launch_lanes(Args& a, double flops_per_frame, int N, hipStream_t st,
     SS4K_HIP(hipEventRecord(ctx->lane_fork(), st));
     SS4K_HIP(hipStreamWaitEvent(ctx->lane_stream(), ctx->lane_fork(), 0));
     forked = true;
+#ifdef SS4K_DEV
+    ++ctx->dev_lane_forks;
+#endif
   }
+#ifdef SS4K_DEV
+  if (ctx->dev_handicap_ticks) {   // ss4k_dev_lane_handicap: the chosen chain trails the other one by a spin at every launch pair
+    op_lane_spin(ctx->dev_handicap_ticks, ctx->dev_handicap_lane ? ctx->lane_stream() : st);
+    ++ctx->dev_lane_spins;
+  }
+#endif
   for (int l = 0; l < 2; ++l) {
     a.n0 = N * l / 2; a.N = N * (l + 1) / 2 - a.n0;
     a.grid_share = lane_grid_share;
@@ -588,6 +597,13 @@ void Model::lanes_begin(int n, int h, int w, hipStream_t st) {
   cur_lanes = 1; cur_n = n; forked = false; tune_timed = nullptr;
   if (plan_only || lanes_mode == 1 || n < 2 || desc.dtype != SS4K_F16 || dbg) return;   // (an odd job splits 1 : 2, 2 : 3, ...)
   ctx->lane_check(st);   // (first job from this stream only)
+#ifdef SS4K_DEV
+  // ss4k_dev_lane_drop_join: armed for this forward; honoured only on the shape of the last completed forward (every act() request then
+  // fits the buffer it finds: nothing is allocated or released before the end-of-forward join)
+  dev_mid_joins = 0;
+  dev_drop_at = (n == dev_done_n && h == dev_done_h && w == dev_done_w) ? ctx->dev_drop_join : 0;
+  ctx->dev_drop_join = 0;
+#endif
   if (lanes_mode == 2) { cur_lanes = 2; return; }
   cur_lanes = tune_step(lane_tune, n, h, w, st);
 }
@@ -596,6 +612,12 @@ void Model::lanes_begin(int n, int h, int w, hipStream_t st) {
 void Model::lanes_join(hipStream_t st, bool end_of_forward) {
   if (forked) {
     SS4K_HIP(hipEventRecord(ctx->lane_done(), ctx->lane_stream()));
+#ifdef SS4K_DEV
+    // the positive control of the ordering tests: ONE mid-forward join leaves the caller's wait out (never the end-of-forward join)
+    const bool dropped = !end_of_forward && dev_drop_at > 0 && ++dev_mid_joins == dev_drop_at;
+    if (!dropped) ++ctx->dev_lane_joins;
+    if (!dropped)
+#endif
     SS4K_HIP(hipStreamWaitEvent(st, ctx->lane_done(), 0));
     forked = false;
   }
@@ -668,13 +690,24 @@ void Model::abort_forward(hipStream_t st) noexcept {
       if (ctx->lane_stream_) (void)hipStreamSynchronize(ctx->lane_stream_);   // last resort: block the host
     }
     forked = false;
+#ifdef SS4K_DEV
+    ++ctx->dev_lane_joins;   // (the join of a forward that failed)
+#endif
   }
   if (section_open) { ctx->prof_pool.push_back(section); section_open = false; }
   tune_timed = nullptr; cur_lanes = 1;
 }
 
 bool Model::forward(const float* in, float* out, int n, int h, int w, hipStream_t st, const ForwardOpts& o) {
+#ifdef SS4K_DEV
+  try {
+    const bool rode = forward_impl(in, out, n, h, w, st, o);
+    if (!plan_only) { dev_done_n = n; dev_done_h = h; dev_done_w = w; }
+    return rode;
+  }
+#else
   try { return forward_impl(in, out, n, h, w, st, o); }
+#endif
   catch (...) { if (!plan_only) abort_forward(st); throw; }
 }
 

@@ -102,6 +102,13 @@ struct Model {
   int dense_mask = 3;          // ... which pairs: bit 0 = (conv1, conv2), bit 1 = (conv3, conv4)
   bool use_pair = true;        // BSVD: inc / outc layer pairs as one fused launch each (conv_pair.hip); SS4K_MODEL_NO_PAIR: two launches
   int fail_at_conv = 0, conv_calls = 0, forward_calls = 0;   // dev library only: fault injection (SS4K_FAIL_AT_CONV)
+#ifdef SS4K_DEV
+  // ss4k_dev_lane_drop_join (include/ss4k_dev.h): this forward's mid-forward joins so far, the one whose wait is left out (0: none), and
+  // the (n, h, w) of the last forward that completed - a drop is honoured only when the shape repeats, so that no activation buffer is
+  // allocated, re-grown or released between the dropped join and the end-of-forward one
+  int dev_mid_joins = 0, dev_drop_at = 0;
+  int dev_done_n = 0, dev_done_h = 0, dev_done_w = 0;
+#endif
   int dbg = 0;  // ablation build selector forwarded to the conv kernel (bench only)
   unsigned long long* dbg_buf = nullptr;
 
