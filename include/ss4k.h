@@ -347,6 +347,54 @@ int ss4k_op_backward_warp(ss4k_ctx* ctx, const float* x_dev, const float* flow_d
  * pass then width pass - NOT F.interpolate's bicubic.  (planes, h, w) -> (planes, 4 h, 4 w) */
 int ss4k_op_bicubic_upsample4(ss4k_ctx* ctx, const float* in_dev, float* out_dev, int planes, int h, int w, void* hip_stream);
 
+/* ---- BSVD as an online machine: temporal denoising whose state crosses job boundaries (reference bsvd/model.py:510-513
+ * feedin_one_element).  The object holds a BSVD model created with bsvd_stream = 1 (not owned: it must outlive the object, and a clip forward
+ * of the same model may run between pushes) plus the per-stream history of its 16 BiBufferConvs and skip queues, allocated on the first
+ * push.  The frames a stream emits are bit for bit those of ONE ss4k_model_forward over all its frames, however the pushes cut it.
+ * max_push: 1..64 frames per push; the workspace of a push never exceeds ss4k_model_workspace_bytes(model, max_push, h, w). */
+typedef struct ss4k_bsvd_online ss4k_bsvd_online;
+int ss4k_bsvd_online_create(ss4k_ctx* ctx, ss4k_model* bsvd_stream_model, int max_push, ss4k_bsvd_online** out);
+void ss4k_bsvd_online_destroy(ss4k_bsvd_online* o);
+/* number of BiBufferConvs = frames a stream holds back: 16 */
+int ss4k_bsvd_online_lag(const ss4k_bsvd_online* o);
+/* feedin_one_element for n frames: in (n, 4, h, w) fp32 NCHW; out receives the *n_out frames that became ready, (3, h, w) fp32 each, oldest
+ * first.  *n_out is known on the host without a synchronisation: emitted so far = max(0, pushed - lag).  SS4K_EINVAL - before the first launch
+ * and before any state changes - for n outside 1..max_push, h or w not a multiple of 4, a size other than the stream's first push, an output
+ * capacity below the frames that become ready, or a NULL pointer. */
+int ss4k_bsvd_online_push(ss4k_bsvd_online* o, const float* in_dev, int n, int h, int w, float* out_dev, size_t out_capacity_frames, int* n_out,
+                          void* hip_stream);
+/* feedin_one_element(None) until drained, then reset: the remaining min(lag, pushed) frames, in rounds of at most max_push feed calls */
+int ss4k_bsvd_online_flush(ss4k_bsvd_online* o, float* out_dev, size_t out_capacity_frames, int* n_out, void* hip_stream);
+/* drops the stream: the next push starts a new one (of any size).  The state buffers stay allocated */
+int ss4k_bsvd_online_reset(ss4k_bsvd_online* o);
+/* frames pushed and not yet emitted */
+int ss4k_bsvd_online_pending(const ss4k_bsvd_online* o, int* frames);
+/* device bytes of the per-stream state (0 before the first push) */
+int ss4k_bsvd_online_state_bytes(const ss4k_bsvd_online* o, size_t* bytes);
+
+/* ---- the per-frame service chain (ss4k_upscale_frames with single_mode and denoising) with the ONLINE denoiser in the place of the per-frame
+ * one: every frame is denoised with its 16 neighbours on either side, across job boundaries, and meets its own undenoised LR planes - for the
+ * 0.8 / 0.2 blend and the mean / std match - when it comes out, 16 frames later.  cfg must have single_mode and denoising set and an lr_shape
+ * divisible by 4; sr and bsvd_stream_model (created with bsvd_stream = 1) are held, not owned.  Noise map: 0.05 for the stream's first frame,
+ * 0.1 * denoise_rate after, as ss4k_upscale_frames. */
+typedef struct ss4k_upscaler_temporal ss4k_upscaler_temporal;
+int ss4k_upscaler_temporal_create(ss4k_ctx* ctx, const ss4k_upscale_cfg* cfg, ss4k_model* sr, ss4k_model* bsvd_stream_model, int max_push,
+                                  ss4k_upscaler_temporal** out);
+void ss4k_upscaler_temporal_destroy(ss4k_upscaler_temporal* up);
+/* n (1..max_push) uint8 NHWC frames in; out receives the *n_out frames that became ready, (out_h, out_w, 3) uint8 each, oldest first: 0 during
+ * the first 16 frames of a stream, n after.  The bytes of a frame do not depend on how the jobs cut the stream.  Refusals (SS4K_EINVAL) come
+ * before the first launch and change nothing. */
+int ss4k_upscale_frames_temporal(ss4k_upscaler_temporal* up, const uint8_t* in_nhwc_dev, int n, int h, int w, uint8_t* out_nhwc_dev,
+                                 size_t out_capacity_bytes, int* n_out, void* hip_stream);
+/* the frames still inside (min(16, pushed)), then the stream ends: the next frame is a first frame again */
+int ss4k_upscaler_temporal_flush(ss4k_upscaler_temporal* up, uint8_t* out_nhwc_dev, size_t out_capacity_bytes, int* n_out, void* hip_stream);
+/* drops the stream without emitting what is inside */
+int ss4k_upscaler_temporal_reset(ss4k_upscaler_temporal* up);
+int ss4k_upscaler_temporal_out_shape(const ss4k_upscaler_temporal* up, int h, int w, int* out_h, int* out_w);
+int ss4k_upscaler_temporal_pending(const ss4k_upscaler_temporal* up, int* frames);
+/* the denoiser's state plus the ring of waiting LR planes */
+int ss4k_upscaler_temporal_state_bytes(const ss4k_upscaler_temporal* up, size_t* bytes);
+
 /* ---- measurement hooks (bench.py: live per-kernel timing with HIP events on the launch stream) */
 /* When enabled, every launch of the dominant conv kernel is bracketed with hipEvents on the
  * stream it is launched on; ss4k_prof_read returns (#launches, total ms, algorithmic FLOPs). */

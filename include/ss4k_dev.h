@@ -74,6 +74,19 @@ int ss4k_dev_op_pack_input(ss4k_ctx* ctx, const float* in, void* out, int out_ha
 int ss4k_dev_op_temporal_shift(ss4k_ctx* ctx, const void* in, void* out, int nplanes, int frames, size_t frame_px,
                                int slots_per_record, int ch_per_plane, int fold, void* hip_stream);
 
+/* ---- the two kernels of the online BSVD executor (csrc/bsvd_online.hip) on caller buffers; routes "bsvdo::...".  Both only select and copy
+ * 16-byte slots of the planes layout.
+ * shift: the ShiftConv input of `frames` output frames whose centres sit in slots slot0 .. slot0 + frames - 1 of `in` (in_frames frames per
+ * plane): channels [0, fold) from the next slot, zeros for output frames i >= n_next; [fold, 2 fold) from the previous slot, zeros for i = 0
+ * unless first_has_prev; the rest from the centre.  out: nplanes planes of `frames` frames.  SS4K_EINVAL where a read would leave `in`. */
+int ss4k_dev_op_bsvd_online_shift(ss4k_ctx* ctx, const void* in, void* out, int nplanes, int in_frames, int slot0, int frames, size_t frame_px,
+                                  int slots_per_record, int ch_per_plane, int fold, int first_has_prev, int n_next, void* hip_stream);
+/* carry: ONE launch for `entries` (1..22) tensors, HOST arrays of one value per entry: in each of nplanes[i] planes, count[i] frames from frame
+ * src_first[i] of src[i] (src_frames[i] frames per plane) to the front of dst[i] (dst_frames[i] frames per plane); frame_slots[i]: 16-byte
+ * slots per frame.  SS4K_EINVAL where src[i] and dst[i] overlap or the move leaves either buffer. */
+int ss4k_dev_op_bsvd_online_carry(ss4k_ctx* ctx, int entries, const void* const* src, void* const* dst, const int* nplanes, const int* src_frames,
+                                  const int* dst_frames, const int* src_first, const int* count, const size_t* frame_slots, void* hip_stream);
+
 /* ---- launchers of the frame-recurrent upscaler's glue (csrc/frvsr.hip, csrc/frvsr.h) that the public API reaches only inside a whole
  * step or round: what tests/test_gpu_frvsr_glue_budget.py bounds against float64.  Same conventions as above; their routes are reported
  * as "frvsr::...", and so are those of ss4k_op_bicubic_upsample4 / ss4k_op_backward_warp (include/ss4k.h) when called through this library.

@@ -37,6 +37,10 @@ SYMBOLS = [
     "ss4k_frvsr_upscale_streams_at",
     "ss4k_frvsr_param_count_as", "ss4k_frvsr_create_as", "ss4k_frvsr_generator",
     "ss4k_frvsr_param_count_ex", "ss4k_frvsr_create_ex", "ss4k_frvsr_degradation",
+    "ss4k_bsvd_online_create", "ss4k_bsvd_online_destroy", "ss4k_bsvd_online_lag", "ss4k_bsvd_online_push", "ss4k_bsvd_online_flush",
+    "ss4k_bsvd_online_reset", "ss4k_bsvd_online_pending", "ss4k_bsvd_online_state_bytes",
+    "ss4k_upscaler_temporal_create", "ss4k_upscaler_temporal_destroy", "ss4k_upscale_frames_temporal", "ss4k_upscaler_temporal_flush",
+    "ss4k_upscaler_temporal_reset", "ss4k_upscaler_temporal_out_shape", "ss4k_upscaler_temporal_pending", "ss4k_upscaler_temporal_state_bytes",
 ]
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
@@ -64,6 +68,8 @@ DEV_SYMBOLS = [
     "ss4k_dev_guard_enable", "ss4k_dev_guard_check", "ss4k_dev_guard_poison", "ss4k_dev_guard_selftest", "ss4k_dev_guard_poison_frvsr",
     # stream ordering: a bounded delay on any stream; the frame lanes' handicap, counters and dropped-join control (tests/test_gpu_lane_order.py)
     "ss4k_dev_op_spin", "ss4k_dev_lane_handicap", "ss4k_dev_lane_counts", "ss4k_dev_lane_counts_reset", "ss4k_dev_lane_drop_join",
+    # the kernels of csrc/bsvd_online.hip on caller buffers (tests/test_gpu_bsvd_online.py)
+    "ss4k_dev_op_bsvd_online_shift", "ss4k_dev_op_bsvd_online_carry",
 ]
 
 
@@ -247,6 +253,28 @@ def load(path: str) -> C.CDLL:
         L.ss4k_frvsr_param_count_ex.argtypes = [C.POINTER(FrvsrDesc), i, i]; L.ss4k_frvsr_param_count_ex.restype = sz
         L.ss4k_frvsr_create_ex.argtypes = [vp, C.POINTER(FrvsrDesc), i, i, i, vp, sz, C.POINTER(vp)]
         L.ss4k_frvsr_degradation.argtypes = [vp]
+    if hasattr(L, "ss4k_bsvd_online_create"):   # (absent from builds before the online denoiser)
+        L.ss4k_bsvd_online_create.argtypes = [vp, vp, i, C.POINTER(vp)]
+        L.ss4k_bsvd_online_destroy.argtypes = [vp]; L.ss4k_bsvd_online_destroy.restype = None
+        L.ss4k_bsvd_online_lag.argtypes = [vp]
+        L.ss4k_bsvd_online_push.argtypes = [vp, vp, i, i, i, vp, sz, C.POINTER(i), vp]
+        L.ss4k_bsvd_online_flush.argtypes = [vp, vp, sz, C.POINTER(i), vp]
+        L.ss4k_bsvd_online_reset.argtypes = [vp]
+        L.ss4k_bsvd_online_pending.argtypes = [vp, C.POINTER(i)]
+        L.ss4k_bsvd_online_state_bytes.argtypes = [vp, C.POINTER(sz)]
+    if hasattr(L, "ss4k_upscaler_temporal_create"):
+        L.ss4k_upscaler_temporal_create.argtypes = [vp, C.POINTER(UpscaleCfg), vp, vp, i, C.POINTER(vp)]
+        L.ss4k_upscaler_temporal_destroy.argtypes = [vp]; L.ss4k_upscaler_temporal_destroy.restype = None
+        L.ss4k_upscale_frames_temporal.argtypes = [vp, vp, i, i, i, vp, sz, C.POINTER(i), vp]
+        L.ss4k_upscaler_temporal_flush.argtypes = [vp, vp, sz, C.POINTER(i), vp]
+        L.ss4k_upscaler_temporal_reset.argtypes = [vp]
+        L.ss4k_upscaler_temporal_out_shape.argtypes = [vp, i, i, C.POINTER(i), C.POINTER(i)]
+        L.ss4k_upscaler_temporal_pending.argtypes = [vp, C.POINTER(i)]
+        L.ss4k_upscaler_temporal_state_bytes.argtypes = [vp, C.POINTER(sz)]
+    if hasattr(L, "ss4k_dev_op_bsvd_online_shift"):   # dev library only
+        ip, szp = C.POINTER(i), C.POINTER(sz)
+        L.ss4k_dev_op_bsvd_online_shift.argtypes = [vp, vp, vp, i, i, i, i, sz, i, i, i, i, i, vp]
+        L.ss4k_dev_op_bsvd_online_carry.argtypes = [vp, i, C.POINTER(vp), C.POINTER(vp), ip, ip, ip, ip, ip, szp, vp]
     if hasattr(L, "ss4k_dev_frvsr_tail_taps"):
         L.ss4k_dev_frvsr_tail_taps.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.ss4k_dev_frvsr_embed_convt.argtypes = [vp, i, vp, sz]
@@ -633,6 +661,144 @@ class Upscaler:
         with torch.cuda.device(self.ctx.device):
             _check(lib().ss4k_upscale_frames(self._h, frames.data_ptr(), n, h, w, out.data_ptr(), out.numel(), _stream()))
         return out
+
+
+class BsvdOnline:
+    """ss4k_bsvd_online: BSVD as the reference's online machine (``BSVD.feedin_one_element``, bsvd/model.py:510-513).  ``model`` is a BSVD
+    ``Model`` built with ``bsvd_stream=True``; it is held, not owned.  The frames of a stream, however the pushes cut it, are bit for bit
+    those of ``model`` on the whole stream as one clip."""
+
+    def __init__(self, model: Model, max_push: int = 4, L: Optional[C.CDLL] = None):
+        self.model, self.ctx, self.max_push, self._L = model, model.ctx, int(max_push), L or lib()
+        self._shape = None
+        h = C.c_void_p()
+        self._rc(self._L.ss4k_bsvd_online_create(self.ctx._h, model._h, self.max_push, C.byref(h)))
+        self._h = h
+        self.lag = int(self._L.ss4k_bsvd_online_lag(h))
+
+    def _rc(self, rc: int) -> None:   # (the error text lives in the library that made it: the product's, or a dev build given as L)
+        if rc != 0:
+            raise Ss4kError(f"libss4k_hip error {rc}: {self._L.ss4k_last_error().decode()}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ss4k_bsvd_online_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def pending(self) -> int:
+        """Frames pushed and not yet returned."""
+        k = C.c_int()
+        self._rc(self._L.ss4k_bsvd_online_pending(self._h, C.byref(k)))
+        return k.value
+
+    def state_bytes(self) -> int:
+        b = C.c_size_t()
+        self._rc(self._L.ss4k_bsvd_online_state_bytes(self._h, C.byref(b)))
+        return int(b.value)
+
+    def push(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``x`` (n, 4, h, w), 1 <= n <= max_push -> the (k, 3, h, w) frames that became ready, oldest first (k = 0 while the lag fills).
+        ``out``: a caller-owned contiguous float32 device tensor to write into (its leading dimension is the capacity in frames)."""
+        assert x.ndim == 4 and x.shape[1] == 4, f"expected (n, 4, h, w), got {tuple(x.shape)}"
+        x = x.to(device=self.ctx.device, dtype=torch.float32).contiguous()
+        n, _, h, w = x.shape
+        if out is None:
+            out = torch.empty((n, 3, h, w), dtype=torch.float32, device=x.device)
+        k = C.c_int()
+        with torch.cuda.device(self.ctx.device):
+            self._rc(self._L.ss4k_bsvd_online_push(self._h, x.data_ptr(), n, h, w, out.data_ptr(), out.shape[0], C.byref(k), _stream()))
+        self._shape = (h, w)
+        return out[:k.value]
+
+    def flush(self) -> torch.Tensor:
+        """The frames still inside, oldest first; ends the stream (the next push starts a new one)."""
+        left = self.pending
+        h, w = self._shape if self._shape else (0, 0)
+        out = torch.empty((left, 3, h, w), dtype=torch.float32, device=self.ctx.device)
+        k = C.c_int()
+        with torch.cuda.device(self.ctx.device):
+            self._rc(self._L.ss4k_bsvd_online_flush(self._h, out.data_ptr() if left else None, left, C.byref(k), _stream()))
+        self._shape = None
+        return out[:k.value]
+
+    def reset(self) -> None:
+        self._rc(self._L.ss4k_bsvd_online_reset(self._h))
+        self._shape = None
+
+
+class TemporalUpscaler:
+    """ss4k_upscaler_temporal: the per-frame service chain (uint8 NHWC -> uint8 NHWC) with the online BSVD denoiser.  ``denoise`` is a BSVD
+    ``Model`` built with ``bsvd_stream=True`` (or a ``BsvdOnline``'s ``.model``).  A call returns the frames that became ready: none during
+    the first 16 frames of a stream, as many as went in after."""
+
+    def __init__(self, ctx: Context, sr: Model, denoise: Model, lr_shape, output_shape=None, denoise_rate: float = 1.0, max_push: int = 4):
+        self.ctx, self.sr, self.denoise, self.max_push = ctx, sr, denoise, int(max_push)
+        cfg = UpscaleCfg()
+        cfg.lr_h, cfg.lr_w = int(lr_shape[0]), int(lr_shape[1])
+        cfg.out_h, cfg.out_w = (0, 0) if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
+        cfg.lr_hr_resize, cfg.single_mode = 1, 1
+        cfg.sr_is_realesrgan = int(sr.in_channels == 3)
+        cfg.denoising, cfg.denoise_rate = 1, float(denoise_rate)
+        h = C.c_void_p()
+        _check(lib().ss4k_upscaler_temporal_create(ctx._h, C.byref(cfg), sr._h, denoise._h, self.max_push, C.byref(h)))
+        self._h, self.cfg, self.lag = h, cfg, 16
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().ss4k_upscaler_temporal_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def out_shape(self, h=None, w=None):
+        oh, ow = C.c_int(), C.c_int()
+        _check(lib().ss4k_upscaler_temporal_out_shape(self._h, h or self.cfg.lr_h, w or self.cfg.lr_w, C.byref(oh), C.byref(ow)))
+        return oh.value, ow.value
+
+    @property
+    def pending(self) -> int:
+        k = C.c_int()
+        _check(lib().ss4k_upscaler_temporal_pending(self._h, C.byref(k)))
+        return k.value
+
+    def state_bytes(self) -> int:
+        b = C.c_size_t()
+        _check(lib().ss4k_upscaler_temporal_state_bytes(self._h, C.byref(b)))
+        return int(b.value)
+
+    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.ndim == 4 and frames.shape[-1] == 3
+        frames = frames.contiguous()
+        n, h, w, _ = frames.shape
+        oh, ow = self.out_shape(h, w)
+        out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
+        k = C.c_int()
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_upscale_frames_temporal(self._h, frames.data_ptr(), n, h, w, out.data_ptr(), out.numel(), C.byref(k), _stream()))
+        return out[:k.value]
+
+    def flush(self) -> torch.Tensor:
+        left = self.pending
+        oh, ow = self.out_shape()
+        out = torch.empty((left, oh, ow, 3), dtype=torch.uint8, device=self.ctx.device)
+        k = C.c_int()
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_upscaler_temporal_flush(self._h, out.data_ptr() if left else None, out.numel(), C.byref(k), _stream()))
+        return out[:k.value]
+
+    def reset(self) -> None:
+        _check(lib().ss4k_upscaler_temporal_reset(self._h))
 
 
 FRVSR_MAX_STREAMS = 64   # SS4K_FRVSR_MAX_STREAMS (include/ss4k.h)

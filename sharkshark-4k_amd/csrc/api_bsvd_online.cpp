@@ -1,0 +1,113 @@
+// C ABI of the online BSVD machine and of the service chain around it (include/ss4k.h: ss4k_bsvd_online_*, ss4k_upscaler_temporal_*),
+// and - dev library only - the machine's two kernels on caller buffers
+// (include/ss4k_dev.h: ss4k_dev_op_bsvd_online_*).
+#include "api_guard.h"
+#include "bsvd_online.h"
+#include "upscaler_temporal.h"
+#include <memory>
+
+using namespace ss4k;
+
+extern "C" {
+
+int ss4k_bsvd_online_create(ss4k_ctx* ctx, ss4k_model* model, int max_push, ss4k_bsvd_online** out) {
+  return guard([&] {
+    SS4K_REQUIRE(ctx && model && out, "ss4k_bsvd_online_create: NULL argument");
+    auto o = std::make_unique<ss4k_bsvd_online>();
+    o->o.create(ctx, &model->m, max_push);
+    *out = o.release();
+  });
+}
+void ss4k_bsvd_online_destroy(ss4k_bsvd_online* o) { delete o; }
+int ss4k_bsvd_online_lag(const ss4k_bsvd_online* o) { return o ? o->o.lag() : SS4K_EINVAL; }
+int ss4k_bsvd_online_push(ss4k_bsvd_online* o, const float* in, int n, int h, int w, float* out, size_t cap, int* n_out, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(o && n_out, "ss4k_bsvd_online_push: NULL argument");
+    SS4K_HIP(hipSetDevice(o->o.ctx->device));
+    *n_out = o->o.push(in, n, h, w, out, cap, (hipStream_t)stream);
+  });
+}
+int ss4k_bsvd_online_flush(ss4k_bsvd_online* o, float* out, size_t cap, int* n_out, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(o && n_out, "ss4k_bsvd_online_flush: NULL argument");
+    SS4K_HIP(hipSetDevice(o->o.ctx->device));
+    *n_out = o->o.flush(out, cap, (hipStream_t)stream);
+  });
+}
+int ss4k_bsvd_online_reset(ss4k_bsvd_online* o) { if (!o) return SS4K_EINVAL; o->o.reset(); return SS4K_OK; }
+int ss4k_bsvd_online_pending(const ss4k_bsvd_online* o, int* frames) {
+  if (!o || !frames) return SS4K_EINVAL;
+  *frames = o->o.pending();
+  return SS4K_OK;
+}
+int ss4k_bsvd_online_state_bytes(const ss4k_bsvd_online* o, size_t* bytes) {
+  if (!o || !bytes) return SS4K_EINVAL;
+  *bytes = o->o.state_bytes();
+  return SS4K_OK;
+}
+
+int ss4k_upscaler_temporal_create(ss4k_ctx* ctx, const ss4k_upscale_cfg* cfg, ss4k_model* sr, ss4k_model* bsvd_stream_model, int max_push,
+                                  ss4k_upscaler_temporal** out) {
+  return guard([&] {
+    SS4K_REQUIRE(ctx && cfg && sr && bsvd_stream_model && out, "ss4k_upscaler_temporal_create: NULL argument");
+    SS4K_HIP(hipSetDevice(ctx->device));
+    auto u = std::make_unique<ss4k_upscaler_temporal>();
+    u->t.create(ctx, *cfg, &sr->m, &bsvd_stream_model->m, max_push);
+    *out = u.release();
+  });
+}
+void ss4k_upscaler_temporal_destroy(ss4k_upscaler_temporal* up) { delete up; }
+int ss4k_upscale_frames_temporal(ss4k_upscaler_temporal* up, const uint8_t* in, int n, int h, int w, uint8_t* out, size_t cap, int* n_out, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(up && n_out, "ss4k_upscale_frames_temporal: NULL argument");
+    SS4K_HIP(hipSetDevice(up->t.up.ctx->device));
+    *n_out = up->t.frames(in, n, h, w, out, cap, (hipStream_t)stream);
+  });
+}
+int ss4k_upscaler_temporal_flush(ss4k_upscaler_temporal* up, uint8_t* out, size_t cap, int* n_out, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(up && n_out, "ss4k_upscaler_temporal_flush: NULL argument");
+    SS4K_HIP(hipSetDevice(up->t.up.ctx->device));
+    *n_out = up->t.flush(out, cap, (hipStream_t)stream);
+  });
+}
+int ss4k_upscaler_temporal_reset(ss4k_upscaler_temporal* up) { if (!up) return SS4K_EINVAL; up->t.reset(); return SS4K_OK; }
+int ss4k_upscaler_temporal_out_shape(const ss4k_upscaler_temporal* up, int h, int w, int* oh, int* ow) {
+  return guard([&] { SS4K_REQUIRE(up && oh && ow, "NULL argument"); up->t.up.out_shape(h, w, oh, ow); });
+}
+int ss4k_upscaler_temporal_pending(const ss4k_upscaler_temporal* up, int* frames) {
+  if (!up || !frames) return SS4K_EINVAL;
+  *frames = up->t.on.pending();
+  return SS4K_OK;
+}
+int ss4k_upscaler_temporal_state_bytes(const ss4k_upscaler_temporal* up, size_t* bytes) {
+  if (!up || !bytes) return SS4K_EINVAL;
+  *bytes = up->t.state_bytes();
+  return SS4K_OK;
+}
+
+#ifdef SS4K_DEV
+int ss4k_dev_op_bsvd_online_shift(ss4k_ctx* c, const void* in, void* out, int nplanes, int in_frames, int slot0, int frames, size_t frame_px,
+                                  int slots_per_record, int ch_per_plane, int fold, int first_has_prev, int n_next, void* s) {
+  return guard([&] {
+    SS4K_REQUIRE(c, "ss4k_dev_op_bsvd_online_shift: NULL context");
+    op_bsvd_online_shift(in, out, nplanes, in_frames, slot0, frames, frame_px, slots_per_record, ch_per_plane, fold, first_has_prev, n_next,
+                         (hipStream_t)s);
+  });
+}
+int ss4k_dev_op_bsvd_online_carry(ss4k_ctx* c, int entries, const void* const* src, void* const* dst, const int* nplanes, const int* src_frames,
+                                  const int* dst_frames, const int* src_first, const int* count, const size_t* frame_slots, void* s) {
+  return guard([&] {
+    SS4K_REQUIRE(c && src && dst && nplanes && src_frames && dst_frames && src_first && count && frame_slots, "ss4k_dev_op_bsvd_online_carry: NULL argument");
+    SS4K_REQUIRE(entries > 0 && entries <= BSVD_ONLINE_MAX_CARRIES, "ss4k_dev_op_bsvd_online_carry: 1..22 entries");
+    BsvdCarryTable tab{};
+    for (int i = 0; i < entries; ++i) {
+      SS4K_REQUIRE(frame_slots[i] > 0 && frame_slots[i] < 4294967296ull, "ss4k_dev_op_bsvd_online_carry: frame_slots outside 32 bits");
+      tab.e[i] = BsvdCarry{src[i], dst[i], nplanes[i], src_frames[i], dst_frames[i], src_first[i], count[i], (unsigned)frame_slots[i]};
+    }
+    op_bsvd_online_carry(tab, entries, (hipStream_t)s);
+  });
+}
+#endif
+
+}  // extern "C"

@@ -225,7 +225,6 @@ void Upscaler::single(const uint8_t* in, int n, int h, int w, uint8_t* out, hipS
     return;
   }
   const float* lr_before = planes_in(in, n, h, w, lh, lw, st);
-  const float* lr_cur = lr_before;
   if (cfg.denoising) {
     lr4.ensure(plane * 4 * n * 4); den.ensure(plane * P * 4 * 2);
     for (int i = 0; i < n; ++i) {
@@ -235,13 +234,27 @@ void Upscaler::single(const uint8_t* in, int n, int h, int w, uint8_t* out, hipS
       SS4K_HIP(hipMemcpyAsync(dst, lr_before + plane * 3 * i, plane * 3 * 4, hipMemcpyDeviceToDevice, st));
       fill_plane(dst + plane * 3, plane, noise, st);  // constant noise-map plane
     }
-    float* den0 = den.as<float>(); float* den1 = den0 + plane * P;
+    float* den0 = den.as<float>();
     const double t0 = now_ms();
     dn->forward(lr4.as<float>(), den0, n, lh, lw, st);
     enq_denoise_ms = now_ms() - t0;
+    single_tail(lr_before, den0, den0 + plane * P, n, out, st);
+    return;
+  }
+  single_tail(lr_before, nullptr, nullptr, n, out, st);
+}
+
+// What single() does after the denoiser, for n frames at lr_shape: lr_before = the undenoised LR planes of the SAME frames; denoised (null:
+// no denoiser) = the denoiser's output for them, blend = n frames of scratch for the sharpened blend.  The temporal upscaler
+// (upscaler_temporal.cpp) calls it with frames whose denoised planes arrive jobs later than their LR planes.
+void Upscaler::single_tail(const float* lr_before, const float* denoised, float* blend, int n, uint8_t* out, hipStream_t st) {
+  const int lh = cfg.lr_h, lw = cfg.lr_w, P = 3 * n;
+  int oc, H, W; sr->out_shape(1, lh, lw, &oc, &H, &W);
+  const float* lr_cur = lr_before;
+  if (denoised) {
     // clamp(sharpen(den)) * 0.8 + 0.2 * lr   (:279-281)
-    op_depthwise_reflect(den0, den1, k_sharp.as<float>(), P, lh, lw, 3, 1, lr_before, 0.8f, (float)(1 - 0.8), st);
-    lr_cur = den1;
+    op_depthwise_reflect(denoised, blend, k_sharp.as<float>(), P, lh, lw, 3, 1, lr_before, 0.8f, (float)(1 - 0.8), st);
+    lr_cur = blend;
   }
   save_tap(0, lr_cur, n, 3, lh, lw, st);
   hr.ensure((size_t)P * H * W * 4 * 2);

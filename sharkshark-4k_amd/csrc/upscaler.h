@@ -33,12 +33,15 @@ struct Upscaler {
   // n frames (n, h, w, 3) -> (n, oh, ow, 3), enqueued on st: multi() without cfg.single_mode, single() with it
   void multi(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st);    // fsrcnn_upscaler.py:168-233
   void single(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st);   // fsrcnn_upscaler.py:235-326
+  // the two halves of single() that the temporal upscaler (upscaler_temporal.cpp) runs jobs apart:
+  // uint8 NHWC frames -> / 255 -> fp32 planes (img), through area to (lh, lw) where that is another size (lr): the planes' address
+  const float* planes_in(const uint8_t* in, int n, int h, int w, int lh, int lw, hipStream_t st);
+  // ... and everything after the denoiser (:279-326): sharpen + blend with lr_before, the SR forward, the HR sharpen, the statistics, the finish
+  void single_tail(const float* lr_before, const float* denoised, float* blend, int n, uint8_t* out, hipStream_t st);
 
  private:
   void lr_size(int h, int w, int* lh, int* lw) const;         // the size the network sees for (h, w) frames
   bool resized(int H, int W) const;                           // the finished (H, W) tensor is resized to cfg.out_h x cfg.out_w
-  // uint8 NHWC frames -> / 255 -> fp32 planes (img), through area to (lh, lw) where that is another size (lr): the planes' address
-  const float* planes_in(const uint8_t* in, int n, int h, int w, int lh, int lw, hipStream_t st);
   void save_tap(int which, const float* src, int n, int c, int h, int w, hipStream_t st);   // a copy for the parity taps; nothing unless taps_on
   void ensure_stats(int P);                                   // st_hr, st_lr and st_acc for P planes
   // mean / std of the HR planes into st_hr and of the LR planes into st_lr, both through st_acc; hr_rode_along: the network already summed

@@ -56,6 +56,9 @@ class UpscalerNode(WorkerPool):
                  fps: int = 24, frame_skips: bool = True, on_result=None, lost_after_s: float = 5.0, force_group: bool = False,
                  output_shape="unset", host_frames=True, host_slots: int = 6, auto_replace: bool = False, **service_kwargs):
         super().__init__(devices)
+        if service_kwargs.get("denoise_temporal") and len(self.devices) > 1:
+            raise ValueError("denoise_temporal=True on a node of several workers: frames are sharded round-robin there, a temporal stream needs "
+                             "all of its frames on one worker")
         if backend is None and len(set(self.devices)) < len(self.devices):
             backend = "gloo"   # RCCL refuses two ranks on one GPU: workers that share a device exchange the weights through host memory
         self.service_cls, self.service_kwargs, self.backend, self.force_group = service_cls, dict(service_kwargs), backend, force_group

@@ -100,7 +100,8 @@ class HipUpscalerService(BaseUpscalerService):
                  # knobs the reference hard-codes
                  scale=4, model_name=None, dtype="f16", weights=None, checkpoint_dir: Optional[str] = None,
                  lr_shape=None, single_mode=None, seed=0, model_flags=0, fsrcnn_dtype="f32",
-                 group: Optional[sharding.GroupSpec] = None, overlap_jobs=True, overlap_sets=3, overlap_max_frames=1):
+                 group: Optional[sharding.GroupSpec] = None, overlap_jobs=True, overlap_sets=3, overlap_max_frames=1,
+                 denoise_temporal=False, temporal_max_push=None):
         # None (the stream pipeline's default: "the compiled backend", pipeline.py:23,41-44) and False (the image server: "eager",
         # image_pipeline.py:58-61) both mean "whatever this build runs the network with" to a caller that cannot know about 'hip';
         # so does a backend of the REFERENCE asked for by name ('trt', 't2trt', 'jit', 'ds': realesrgan/factory.py:175-230, fsrcnn/factory.py:17-69 -
@@ -139,7 +140,25 @@ class HipUpscalerService(BaseUpscalerService):
         self.overlap_jobs = bool(overlap_jobs)
         self.overlap_sets = max(2, int(overlap_sets))            # job sets that consecutive small jobs alternate over
         self.overlap_max_frames = int(overlap_max_frames)        # jobs of up to this many frames alternate (bigger ones overlap with themselves: frame lanes)
+        # denoise_temporal: BSVD as the online machine (_capi.TemporalUpscaler): every frame is denoised with its neighbours across job
+        # boundaries and comes back TEMPORAL_LAG frames after it went in.  The state is ordered: one stream, job set 0, submit order
+        self.denoise_temporal = bool(denoise_temporal)
+        if self.denoise_temporal:
+            if not denoising:
+                raise ValueError("denoise_temporal=True needs denoising=True")
+            if not self.single_mode:
+                raise ValueError(f"denoise_temporal=True needs the per-frame path: upscaler_model={upscaler_model!r} runs batched jobs, which never "
+                                 f"denoise (fsrcnn_upscaler.py:109,168-233); pass single_mode=True")
+            if group is not None and getattr(group, "world", 1) > 1:
+                raise ValueError("denoise_temporal=True on a node of several workers: frames are sharded round-robin there, a temporal stream "
+                                 "needs all of its frames on one worker")
+        self.temporal_max_push = int(temporal_max_push) if temporal_max_push else max(4, int(batch_size))
+        self._t_emitted = 0          # frames of the running stream returned so far = the stream index of the next frame to come back
+        self._t_first = 0            # ... of the first frame the LAST upscale() / flush() returned
         super().__init__()
+
+    #: frames a temporal stream holds back (the number of BiBufferConvs: ss4k_bsvd_online_lag)
+    TEMPORAL_LAG = 16
 
     def net_scale(self) -> int:
         """The SR network's own factor (no GPU needed: from the model name / ``scale``)."""
@@ -244,7 +263,7 @@ class HipUpscalerService(BaseUpscalerService):
         # quirk kept from the reference: with 'realesrgan' the batched path never denoises even when
         # denoising=True (fsrcnn_upscaler.py:109,168-233); the BSVD model is only used per-frame.
         if self.denoising and self.single_mode:
-            ddesc = factory.denoise_desc(self.dtype)
+            ddesc = factory.denoise_desc(self.dtype, stream=True) if self.denoise_temporal else factory.denoise_desc(self.dtype)
             dflat = self._shared_flat("denoise", ddesc, lambda: factory.denoise_flat(spec("denoise"), self.seed, checkpoint_dir=self.checkpoint_dir))
             self.denoise_model = _capi.Model(self.ctx, ddesc, dflat)
 
@@ -281,8 +300,39 @@ class HipUpscalerService(BaseUpscalerService):
         """``HostFrameIO.run`` around ``upscale``; the end of a job that ran on a job set's stream is that set's event, held under its result."""
         return self._io.run(hf, self.upscale, self._held.pop_event)
 
+    def flush(self) -> torch.Tensor:
+        """denoise_temporal: the frames still inside the denoiser, ``(k, H, W, 3)`` uint8, oldest first; the stream ends (the next frame is a
+        first frame again)."""
+        if not self.denoise_temporal:
+            raise RuntimeError("flush() belongs to denoise_temporal=True: every other job returns its own frames")
+        out = self._get_upscaler(0).flush()
+        self._t_first, self._t_emitted = self._t_emitted, 0
+        return out
+
+    def reset(self) -> None:
+        """denoise_temporal: drop the running stream without returning what is inside."""
+        if self.denoise_temporal:
+            self._get_upscaler(0).reset()
+            self._t_first = self._t_emitted = 0
+
+    def _tag_temporal(self, entry):
+        """A result entry of a temporal stream carries the frames that became ready (possibly none) plus where they belong: the stream index
+        of its first frame and the lag.  Plain ints: the entry stays picklable.  An entry type without room for them goes untagged."""
+        try:
+            entry.first_frame_index, entry.lag_frames = int(self._t_first), self.TEMPORAL_LAG
+        except AttributeError:
+            pass
+        f = getattr(entry, "frames", None)
+        if getattr(self, "_in_worker", False) and isinstance(f, torch.Tensor) and f.is_cuda and f.shape[0] == 0:
+            entry.frames = torch.empty(tuple(f.shape), dtype=f.dtype)   # nothing became ready: an empty host tensor (no device block to share)
+        return entry
+
     def proc_job_recieved(self, job):
         hf = getattr(job, "frames", None)
+        if self.denoise_temporal:
+            if isinstance(hf, HostFrames):
+                raise RuntimeError("denoise_temporal=True takes device or host TENSOR jobs: a host-ring job's result slot is sized for the job's own frames")
+            return self._tag_temporal(super().proc_job_recieved(job))
         if not isinstance(hf, HostFrames):
             entry = super().proc_job_recieved(job)
             return self._to_host_result(entry) if self.host_results and getattr(self, "_in_worker", False) else entry
@@ -453,6 +503,12 @@ class HipUpscalerService(BaseUpscalerService):
         js = self._job_set(k)
         key = (tuple(self.lr_shape), None if self.output_shape is None else tuple(self.output_shape),
                bool(self.lr_hr_resize), bool(self.single_mode), float(self.denoise_rate))
+        if getattr(self, "denoise_temporal", False) and (js["up"] is None or key != js["key"]):
+            # (a new geometry starts a new stream: what the old object still held is dropped with it)
+            js["up"] = _capi.TemporalUpscaler(js["ctx"], js["model"], js["denoise"], self.lr_shape, self.output_shape, self.denoise_rate,
+                                              self.temporal_max_push)
+            js["key"] = key
+            self._t_emitted = self._t_first = 0
         if js["up"] is None or key != js["key"]:
             js["up"] = _capi.Upscaler(js["ctx"], js["model"], self.lr_shape, self.output_shape, self.lr_hr_resize,
                                       self.single_mode, js["denoise"], self.denoise_rate)
@@ -485,6 +541,13 @@ class HipUpscalerService(BaseUpscalerService):
 
     def _run(self, k: int, frames: torch.Tensor) -> torch.Tensor:
         up = self._get_upscaler(k)
+        if getattr(self, "denoise_temporal", False):
+            # jobs of any size go in as pushes of at most temporal_max_push frames; what became ready comes back in stream order
+            m = self.temporal_max_push
+            parts = [up(frames[i:i + m]) for i in range(0, frames.shape[0], m)]
+            out = parts[0] if len(parts) == 1 else torch.cat(parts)
+            self._t_first, self._t_emitted = self._t_emitted, self._t_emitted + int(out.shape[0])
+            return out
         out = up(frames)
         prof = getattr(self, "profiler", None)
         if prof is not None:

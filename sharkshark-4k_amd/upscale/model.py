@@ -192,10 +192,17 @@ def denoise_flat(weights: WeightSpec = None, seed: int = 0, variant: str = "bsvd
 
 
 def build_denoise_model(ctx: _capi.Context, weights: WeightSpec = None, dtype="f16", seed: int = 0,
-                        stream: bool = False, variant: str = "bsvd-32", checkpoint_dir: Optional[str] = None, flags: int = 0):
+                        stream: bool = False, variant: str = "bsvd-32", checkpoint_dir: Optional[str] = None, flags: int = 0,
+                        online: bool = False, max_push: int = 4):
     """``stream=False``: the model the service calls, one independent frame per call (F = 1,
     ``fsrcnn_upscaler.py:277``).  ``stream=True``: ``BSVD.forward`` on ``(N,F,4,H,W)`` clips, all N*F
-    frames run through the bidirectional buffers as one stream (``bsvd/model.py:515-580``)."""
+    frames run through the bidirectional buffers as one stream (``bsvd/model.py:515-580``).
+    ``online=True``: the same stream model as the reference's online machine (``feedin_one_element``, ``:510-513``): a
+    ``_capi.BsvdOnline`` taking up to ``max_push`` frames per ``push`` and returning each frame 16 frames later; its ``.model`` is the
+    clip model it holds."""
+    if online:
+        m = _capi.Model(ctx, denoise_desc(dtype, True, variant, flags), denoise_flat(weights, seed, variant, checkpoint_dir))
+        return _capi.BsvdOnline(m, max_push)
     return _capi.Model(ctx, denoise_desc(dtype, stream, variant, flags), denoise_flat(weights, seed, variant, checkpoint_dir))
 
 

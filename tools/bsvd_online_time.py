@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""Time the online BSVD denoiser (``_capi.BsvdOnline``) against the two forms it sits between, on one GPU:
+
+  online    four-frame pushes in steady state (the lag is full: every push emits four frames)
+  clip      the clip forward (``bsvd_stream = 1``) of four frames: the same conv work without history
+  per_frame the per-frame model (``bsvd_stream = 0``) on four frames: a quarter fewer MACs in 16 of its 32 convs
+
+Each form is timed with events around ``--iters`` calls after ``--warmup``, the three forms interleaved, ``--runs`` times; the JSON line
+holds every run's ms per frame, the spread between runs, the online state's bytes and the launches per push of the two online kernels
+(dev library only: run with ``SS4K_LIB=.../libss4k_hip_dev.so``).  ``--service``: instead, frames/s of
+``HipUpscalerService`` (FSRCNN x2 behind the denoiser, jobs of ``--push`` frames) with ``denoise_temporal`` on and off.
+
+Usage:  python tools/bsvd_online_time.py [--h 720 --w 1280 --dtype f16 --variant bsvd-32 --push 4 --iters 20 --runs 2] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+import sharkshark4k_amd  # noqa: E402,F401
+from sharkshark4k_amd import _capi  # noqa: E402
+from sharkshark4k_amd.upscale import model as factory  # noqa: E402
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def service(a):
+    """Frames/s through ``HipUpscalerService.upscale`` (in-process worker body, resident frames, FSRCNN x2 behind the denoiser)."""
+    from sharkshark4k_amd.upscale.hip_upscaler import HipUpscalerService
+    frames = torch.randint(0, 256, (a.push, a.h, a.w, 3), dtype=torch.uint8, device="cuda")
+    res = {}
+    svcs = {k: HipUpscalerService(denoising=True, denoise_temporal=k == "temporal", temporal_max_push=a.push, upscaler_model="fsrcnn", scale=2,
+                                  lr_shape=(a.h, a.w), dtype=a.dtype, fsrcnn_dtype="f16", weights="synthetic") for k in ("per_frame", "temporal")}
+    for s in svcs.values():
+        s.output_shape = None
+        s.proc_init()
+        for _ in range(max(a.warmup, 16 // a.push + 2)):
+            s.upscale(frames)
+    torch.cuda.synchronize()
+    for _ in range(a.runs):
+        for k, s in svcs.items():
+            res.setdefault(k, []).append(1000.0 * a.push / timed(lambda: s.upscale(frames), a.iters))
+    line = {"tool": "bsvd_online_time --service", "h": a.h, "w": a.w, "dtype": a.dtype, "job_frames": a.push, "sr": "fsrcnn x2 (fp16 mode)",
+            "frames_per_s": {k: [round(v, 1) for v in vs] for k, vs in res.items()},
+            "temporal_over_per_frame": round(max(res["temporal"]) / max(res["per_frame"]), 4)}
+    print(json.dumps(line), flush=True)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    for s in svcs.values():
+        s.proc_cleanup()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--h", type=int, default=720); ap.add_argument("--w", type=int, default=1280)
+    ap.add_argument("--dtype", default="f16"); ap.add_argument("--variant", default="bsvd-32")
+    ap.add_argument("--push", type=int, default=4); ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=8); ap.add_argument("--runs", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--service", action="store_true", help="instead: frames/s of HipUpscalerService (FSRCNN x2, 4-frame jobs) with denoise_temporal on and off")
+    a = ap.parse_args()
+    if a.service:
+        return service(a)
+    ctx = _capi.Context(0)
+    n = a.push
+    on = factory.build_denoise_model(ctx, weights="synthetic", dtype=a.dtype, variant=a.variant, online=True, max_push=n)
+    per = factory.build_denoise_model(ctx, weights="synthetic", dtype=a.dtype, variant=a.variant, stream=False)
+    x = torch.rand(n, 4, a.h, a.w, device="cuda")
+    x[:, 3] = 0.05
+    out = torch.empty(n, 3, a.h, a.w, device="cuda")
+    forms = {"online": lambda: on.push(x, out=out), "clip": lambda: on.model(x, out=out), "per_frame": lambda: per(x, out=out)}
+    for _ in range(max(a.warmup, 16 // n + 2)):   # past the lag (and past the frame lanes' tuning calls of the two forwards)
+        for f in forms.values():
+            f()
+    torch.cuda.synchronize()
+    assert on.pending == 16
+    res = {k: [] for k in forms}
+    for _ in range(a.runs):
+        for k, f in forms.items():
+            res[k].append(timed(f, a.iters) / n)
+    line = {"tool": "bsvd_online_time", "h": a.h, "w": a.w, "dtype": a.dtype, "variant": a.variant, "push": n, "iters": a.iters,
+            "ms_per_frame": {k: [round(v, 4) for v in vs] for k, vs in res.items()},
+            "spread_pct": {k: round(100 * (max(vs) - min(vs)) / min(vs), 2) for k, vs in res.items()},
+            "online_over_clip": round(min(res["online"]) / min(res["clip"]), 4),
+            "online_over_per_frame": round(min(res["online"]) / min(res["per_frame"]), 4),
+            "state_bytes": on.state_bytes(), "workspace_bytes_clip": on.model.workspace_bytes(n, a.h, a.w)}
+    if hasattr(_capi.lib(), "ss4k_dev_glue_routes_read"):   # dev library: launches of the two online kernels in one steady-state push
+        _capi.lib().ss4k_dev_glue_routes_reset()
+        on.push(x, out=out)
+        torch.cuda.synchronize()
+        line["routes_per_push"] = {k: v for k, v in _capi.glue_routes(_capi.lib()).items() if k.startswith("bsvdo::")}
+    print(json.dumps(line), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
