@@ -252,19 +252,6 @@ void FrvsrUpscaler::check_round(const int32_t* slot_ids, int S, int h, int w, bo
   }
 }
 
-// a span of the service glue in the per-stage timing (stage 6), on the caller's stream
-template <typename F>
-void FrvsrUpscaler::glue_span(hipStream_t st, F&& body) {
-  if (!m->prof) { body(); return; }
-  Frvsr::Span sp{nullptr, nullptr, FRV_GLUE};
-  SS4K_HIP(hipEventCreate(&sp.a));
-  if (hipEventCreate(&sp.b) != hipSuccess) { (void)hipEventDestroy(sp.a); throw Error(SS4K_EHIP, "hipEventCreate failed"); }
-  m->spans.push_back(sp);
-  SS4K_HIP(hipEventRecord(sp.a, st));
-  body();
-  SS4K_HIP(hipEventRecord(sp.b, st));
-}
-
 // the first change of any slot in a round: every item's state buffers exist, a stream's first frame sees zeros, and the round's tables point at them
 void FrvsrUpscaler::open_slots(const int32_t* slot_ids, int S, hipStream_t st, RoundPtrs& r) {
   const size_t lr_b = (size_t)3 * lr_h * lr_w * 4, hr_b = (size_t)3 * 16 * lr_h * lr_w * 4;
@@ -301,7 +288,7 @@ void FrvsrUpscaler::round(const uint8_t* in, const int32_t* slot_ids, int S, int
   const bool resize_in = h != lr_h || w != lr_w, resize_out = oh != H || ow != W;
   RoundPtrs r{};
   open_slots(slot_ids, S, st, r);
-  glue_span(st, [&] {
+  m->timed(FRV_GLUE, st, [&] {
     for (int i = 0; i < S; ++i) {
       const uint8_t* frame = in + (size_t)i * h * w * 3;
       float* dst = r.lr_dst.p[i];
@@ -318,7 +305,7 @@ void FrvsrUpscaler::round(const uint8_t* in, const int32_t* slot_ids, int S, int
   if (S == 1) m->step(r.lr_curr[0], r.lr_prev[0], r.hr_prev.p[0], r.hr_curr.p[0], 1, lr_h, lr_w, st);
   else m->step_items(Frvsr::Items{r.lr_curr, r.lr_prev, &r.hr_prev, &r.hr_curr}, S, lr_h, lr_w, st);
   close_slots(slot_ids, S);
-  glue_span(st, [&] {
+  m->timed(FRV_GLUE, st, [&] {
     for (int i = 0; i < S; ++i) {
       uint8_t* dst = out + (size_t)i * oh * ow * 3;
       if (resize_out) {   // clamp(hr_curr, 0, 1), F.interpolate(size=self.output_shape, mode='area') (:209-211)
@@ -347,11 +334,11 @@ void FrvsrUpscaler::round_at(const uint8_t* const* in, const int32_t* slot_ids, 
   }
   RoundPtrs r{};
   open_slots(slot_ids, S, st, r);
-  glue_span(st, [&] { op_frames_in_items(fin, r.lr_dst, S, h, w, lr_h, lr_w, st); });
+  m->timed(FRV_GLUE, st, [&] { op_frames_in_items(fin, r.lr_dst, S, h, w, lr_h, lr_w, st); });
   // always the item launchers, S = 1 included: they are bit-identical to the contiguous ones, and the packing is one launch for the round
   m->step_items(Frvsr::Items{r.lr_curr, r.lr_prev, &r.hr_prev, &r.hr_curr, true}, S, lr_h, lr_w, st);
   close_slots(slot_ids, S);
-  glue_span(st, [&] { op_frames_out_items(r.hr_curr, fout, S, H, W, oh, ow, st); });
+  m->timed(FRV_GLUE, st, [&] { op_frames_out_items(r.hr_curr, fout, S, H, W, oh, ow, st); });
 }
 
 void FrvsrUpscaler::frames(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st) {

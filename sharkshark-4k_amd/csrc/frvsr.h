@@ -1,7 +1,8 @@
 // EGVSR's frame-recurrent upscaler (FRNet x4, reference src/upscale/model/egvsr/egvsr.py:146-212): the executor behind ss4k_frvsr and
-// the service path behind ss4k_frvsr_upscaler (include/ss4k.h), and the launchers of the glue kernels they need (frvsr.hip).  One Frvsr holds
-// all four (generator, degradation) variants: Frvsr::run branches on `degradation` for the warp stage (frvsr_bi.hip) and on `generator` for the
-// tail (TecoGAN's: frvsr_teco.cpp, conv_up2.hip).
+// the service path behind ss4k_frvsr_upscaler (include/ss4k.h), and the launchers of the glue kernels they need (frvsr.hip, frvsr_bi.hip).  One
+// Frvsr holds all four (generator, degradation) variants: Frvsr::run branches on `degradation` for the warp stage's launcher and on `generator`
+// for the tail (TecoGAN's: frvsr_teco.cpp, conv_up2.hip).  The stages that differ by degradation or addressing alone are one kernel template each
+// (frvsr_stages.h); the launchers declared here name its instantiations.
 #pragma once
 #include "models.h"
 #include <memory>
@@ -16,7 +17,7 @@ struct FrvsrPtrs { float* p[SS4K_FRVSR_MAX_STREAMS]; };
 struct FrvsrFramesIn { const uint8_t* p[SS4K_FRVSR_MAX_STREAMS]; };
 struct FrvsrFramesOut { uint8_t* p[SS4K_FRVSR_MAX_STREAMS]; };
 
-// ---- kernels (frvsr.hip).  "planes" tensors are the conv kernels' layout: [plane][pixel][16 channels of T] -----------------------------
+// ---- launchers (frvsr.hip).  "planes" tensors are the conv kernels' layout: [plane][pixel][16 channels of T] -----------------------------
 // nn.MaxPool2d(2, 2) (egvsr.py:24,31,38): (n, h, w) -> (n, h / 2, w / 2), odd sizes floored
 template <typename T> void op_maxpool2_planes(const T* in, T* out, int nplanes, int n, int h, int w, hipStream_t st);
 // F.interpolate(scale_factor=2, mode='bilinear', align_corners=False) (egvsr.py:70-75): (n, h, w) -> (n, 2 h, 2 w)
@@ -30,7 +31,7 @@ void op_backward_warp(const float* x, const float* flow, float* out, int n, int 
 // 4 * BicubicUpsample(4)(lr_flow), backward_warp(hr_prev, .) and the space-to-depth of egvsr.py:196-208 as one launch: lr_flow (n, 2, h, w),
 // hr_prev (n, 3, 4 h, 4 w), both fp32 -> three planes of T (channel (sy * 4 + sx) * 3 + c)
 template <typename T> void op_warp_s2d_planes(const float* lr_flow, const float* hr_prev, T* out, int n, int h, int w, hipStream_t st);
-// ... item i reading hr_prev.p[i] instead of hr_prev + i * 3 * 16 h w: the same device functions in the same order, bit-identical; n <= 64
+// ... item i reading hr_prev.p[i] instead of hr_prev + i * 3 * 16 h w: the same kernel template on the other addressing, bit-identical; n <= 64
 template <typename T> void op_warp_s2d_planes_items(const float* lr_flow, const FrvsrPtrs& hr_prev, T* out, int n, int h, int w, hipStream_t st);
 // PixelShuffle(4), ReLU, Conv2d(4, 3, 3, 1, 1) (egvsr.py:122-127,139-140): four planes of T (64 channels) at (n, h, w) -> fp32 NCHW
 // (n, 3, 4 h, 4 w); wb: 108 weights (OIHW) + 3 biases on the device
@@ -42,8 +43,8 @@ template <typename T> void op_ps4_conv_tail_items(const T* in, const float* wb, 
 void op_bicubic4_add(const float* conv, const float* lr, float* out, int n, int h, int w, hipStream_t st);
 // ... item i reading lr.p[i] (3, h, w) and writing out.p[i] (3, 4 h, 4 w); conv stays one contiguous batch: bit-identical; n <= 64
 void op_bicubic4_add_items(const float* conv, const FrvsrPtrs& lr, const FrvsrPtrs& out, int n, int h, int w, hipStream_t st);
-// ---- kernels of degradation 'BI' (frvsr_bi.hip): get_upsampling_func's F.interpolate(scale_factor=4, 'bilinear', align_corners=False)
-// (utils/net_utils.py:96-108) in the places of BicubicUpsample(4)
+// ---- launchers of degradation 'BI' (frvsr_bi.hip): the same kernel templates with get_upsampling_func's F.interpolate(scale_factor=4, 'bilinear',
+// align_corners=False) (utils/net_utils.py:96-108) in the places of BicubicUpsample(4)
 // (planes, h, w) -> (planes, 4 h, 4 w), fp32
 void op_bilinear_upsample4(const float* in, float* out, int planes, int h, int w, hipStream_t st);
 // op_warp_s2d_planes[_items] with 4 * bilinear x4 of the flow: the same warp, the same records, the same requirements and grid
@@ -188,7 +189,6 @@ struct FrvsrUpscaler {
   void check_round(const int32_t* slot_ids, int S, int h, int w, bool area_chain) const;
   void open_slots(const int32_t* slot_ids, int S, hipStream_t st, RoundPtrs& r);
   void close_slots(const int32_t* slot_ids, int S);
-  template <typename F> void glue_span(hipStream_t st, F&& body);
 };
 
 }  // namespace ss4k

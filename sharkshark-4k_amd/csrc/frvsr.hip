@@ -3,11 +3,12 @@
 // "planes" tensors: [plane][pixel (n, y, x)][16 channels of T], T = __half (32-byte records) or float (64-byte records).
 // The flow, hr_prev and hr_curr are fp32 in both dtypes.
 //
-// The bicubic x4 and the warp exist twice - as granular ops (ss4k_op_bicubic_upsample4, ss4k_op_backward_warp) and inside the fused
-// warp + space-to-depth kernel - and both go through the SAME device functions below, written with explicit __fmaf_rn / __fmul_rn /
-// __fadd_rn so that the compiler contracts nothing differently in the two places: the fused kernel's tensor is bit-identical to the chain
-// of the granular ops (tests/test_gpu_frvsr.py).
-#include "frvsr_warp.h"   // grid_for, warp_pos / warp_taps / warp_sample, the record store: shared with frvsr_bi.hip
+// The four stages that exist per (degradation, addressing) - the x4, flow x4 + warp + space-to-depth, conv_out + x4 skip, EGVSR's tail - are
+// one kernel template and one launch helper each (frvsr_stages.h); this file holds the bicubic up-sampler (degradation 'BD') and the
+// launchers that instantiate them with it, frvsr_bi.hip the bilinear one.  The x4 and the warp exist as granular ops
+// (ss4k_op_bicubic_upsample4, ss4k_op_backward_warp) and inside the fused kernels, and every one goes through the SAME device functions, so
+// the fused kernel's tensor is bit-identical to the chain of the granular ops (tests/test_gpu_frvsr.py).
+#include "frvsr_stages.h"
 
 namespace ss4k {
 
@@ -109,7 +110,7 @@ void op_flow_finish(const float* raw, float* flow, int n, int h8, int w8, int h,
   SS4K_LAUNCH_OK();
 }
 
-// ------------------------------------------------------------------ BicubicUpsample(4) and backward_warp: shared arithmetic
+// ------------------------------------------------------------------ BicubicUpsample(4)
 // kernels[d] = cubic . (1, s, s^2, s^3), s = d / 4, a = -0.75 (net_utils.py:126-140): tap i of phase d weighs input clamp(base - 1 + i)
 struct Bic4 { float k[4][4]; };
 static Bic4 bic4_taps() {
@@ -145,26 +146,18 @@ __device__ __forceinline__ float bic4_at(const Bic4& t, const float f[4][4], int
   for (int j = 0; j < 4; ++j) col[j] = bic4_dot(t.k[sy], f[0][j], f[1][j], f[2][j], f[3][j]);
   return bic4_dot(t.k[sx], col[0], col[1], col[2], col[3]);
 }
-// backward_warp: warp_pos, warp_taps, warp_sample (frvsr_warp.h)
-
-__global__ void k_bicubic_upsample4(const float* __restrict__ in, float* __restrict__ out, int planes, int h, int w, Bic4 taps) {
-  const int OW = 4 * w, OH = 4 * h;
-  const size_t total = (size_t)planes * OH * OW;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int X = (int)(i % OW), Y = (int)((i / OW) % OH);
-    const size_t pl = i / ((size_t)OW * OH);
-    float f[4][4];
-    bic4_load(in + pl * h * w, Y >> 2, X >> 2, h, w, f);
-    out[i] = bic4_at(taps, f, Y & 3, X & 3);
-  }
-}
+// the up-sampler of frvsr_stages.h's kernels: the taps travel by value in the kernel arguments
+struct UpBicubic4 {
+  static constexpr int N = 4;
+  Bic4 taps;
+  __device__ __forceinline__ void load(const float* __restrict__ pl, int y, int x, int h, int w, float f[4][4]) const { bic4_load(pl, y, x, h, w, f); }
+  __device__ __forceinline__ float at(const float f[4][4], int sy, int sx, int, int, int, int) const { return bic4_at(taps, f, sy, sx); }
+};
 void op_bicubic_upsample4(const float* in, float* out, int planes, int h, int w, hipStream_t st) {
-  SS4K_REQUIRE(planes > 0 && h > 0 && w > 0 && h <= (1 << 28) && w <= (1 << 28), "bicubic x4: sizes");
-  SS4K_GLUE_ROUTE("frvsr::bicubic_upsample4");
-  hipLaunchKernelGGL(k_bicubic_upsample4, grid_for((size_t)planes * 16 * h * w), dim3(256), 0, st, in, out, planes, h, w, bic4_taps());
-  SS4K_LAUNCH_OK();
+  launch_up4("frvsr::bicubic_upsample4", "bicubic x4", in, out, planes, h, w, UpBicubic4{bic4_taps()}, st);
 }
 
+// ------------------------------------------------------------------ backward_warp, the granular op (warp_pos, warp_taps, warp_sample: frvsr_stages.h)
 __global__ void k_backward_warp(const float* __restrict__ x, const float* __restrict__ flow, float* __restrict__ out, int n, int c, int h, int w) {
   const size_t hw = (size_t)h * w, total = (size_t)n * hw;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -181,192 +174,43 @@ void op_backward_warp(const float* x, const float* flow, float* out, int n, int 
   SS4K_LAUNCH_OK();
 }
 
-// ------------------------------------------------------------------ flow x4 + warp + space-to-depth -> three planes
-// One thread per LR pixel: its 4 x 4 flow neighbourhood serves all 16 sub-pixels (the four phases of each pass read the same inputs), and
-// the 48 channels (sy * 4 + sx) * 3 + c it produces are exactly the three records it stores, with 16-byte stores.
-// pixel i of item img: `src` is that item's hr_prev (3, 4 h, 4 w)
-template <typename T>
-__device__ __forceinline__ void warp_s2d_pixel(const float* __restrict__ lr_flow, const float* __restrict__ src, uint4* __restrict__ out, size_t i, size_t img,
-                                               size_t npix, int h, int w, const Bic4& taps) {
-  const int H = 4 * h, W = 4 * w;
-  const size_t hw = (size_t)h * w, HW = (size_t)H * W;
-  const int x = (int)(i % w), y = (int)((i / w) % h);
-  S2dRecord<T> rec;
-  float fu[4][4], fv[4][4];
-  bic4_load(lr_flow + (img * 2) * hw, y, x, h, w, fu);
-  bic4_load(lr_flow + (img * 2 + 1) * hw, y, x, h, w, fv);
-#pragma unroll
-  for (int sy = 0; sy < 4; ++sy)
-#pragma unroll
-    for (int sx = 0; sx < 4; ++sx) {
-      const float u = __fmul_rn(4.f, bic4_at(taps, fu, sy, sx)), v = __fmul_rn(4.f, bic4_at(taps, fv, sy, sx));
-      const WarpTaps t = warp_taps(4 * x + sx, 4 * y + sy, W, H, u, v);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) rec.v[(sy * 4 + sx) * 3 + c] = (T)warp_sample(src + c * HW, W, t);
-    }
-  s2d_store<T>(rec, out, i, npix);
-}
-template <typename T>
-__global__ __launch_bounds__(256) void k_warp_s2d_planes(const float* __restrict__ lr_flow, const float* __restrict__ hr_prev, uint4* __restrict__ out, int n, int h,
-                                                         int w, Bic4 taps) {
-  const size_t hw = (size_t)h * w, npix = (size_t)n * hw;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t img = i / hw;
-    warp_s2d_pixel<T>(lr_flow, hr_prev + img * 3 * (16 * hw), out, i, img, npix, h, w, taps);
-  }
-}
-// ... with every item's hr_prev where its stream keeps it: the base pointers arrive by value in the kernel arguments (FrvsrPtrs, frvsr.h)
-template <typename T>
-__global__ __launch_bounds__(256) void k_warp_s2d_planes_items(const float* __restrict__ lr_flow, FrvsrPtrs hr_prev, uint4* __restrict__ out, int n, int h, int w,
-                                                               Bic4 taps) {
-  const size_t hw = (size_t)h * w, npix = (size_t)n * hw;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t img = i / hw;
-    warp_s2d_pixel<T>(lr_flow, hr_prev.p[img], out, i, img, npix, h, w, taps);
-  }
-}
+// ------------------------------------------------------------------ the stage kernels of frvsr_stages.h with the bicubic x4
 template <typename T>
 void op_warp_s2d_planes(const float* lr_flow, const float* hr_prev, T* out, int n, int h, int w, hipStream_t st) {
-  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull, "warp: sizes");
-  SS4K_GLUE_ROUTE(sizeof(T) == 2 ? "frvsr::warp_s2d_planes<half>" : "frvsr::warp_s2d_planes<float>");
-  hipLaunchKernelGGL((k_warp_s2d_planes<T>), grid_for((size_t)n * h * w), dim3(256), 0, st, lr_flow, hr_prev, reinterpret_cast<uint4*>(out), n, h, w, bic4_taps());
-  SS4K_LAUNCH_OK();
+  launch_warp_s2d(sizeof(T) == 2 ? "frvsr::warp_s2d_planes<half>" : "frvsr::warp_s2d_planes<float>", "warp", lr_flow, Strided<const float>{hr_prev, (size_t)48 * h * w},
+                  out, n, h, w, UpBicubic4{bic4_taps()}, st);
 }
 template void op_warp_s2d_planes<float>(const float*, const float*, float*, int, int, int, hipStream_t);
 template void op_warp_s2d_planes<__half>(const float*, const float*, __half*, int, int, int, hipStream_t);
 template <typename T>
 void op_warp_s2d_planes_items(const float* lr_flow, const FrvsrPtrs& hr_prev, T* out, int n, int h, int w, hipStream_t st) {
-  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull, "warp (items): sizes");
-  for (int i = 0; i < n; ++i) SS4K_REQUIRE(hr_prev.p[i], "warp (items): NULL item");
-  SS4K_GLUE_ROUTE(sizeof(T) == 2 ? "frvsr::warp_s2d_planes_items<half>" : "frvsr::warp_s2d_planes_items<float>");
-  hipLaunchKernelGGL((k_warp_s2d_planes_items<T>), grid_for((size_t)n * h * w), dim3(256), 0, st, lr_flow, hr_prev, reinterpret_cast<uint4*>(out), n, h, w,
-                     bic4_taps());
-  SS4K_LAUNCH_OK();
+  launch_warp_s2d(sizeof(T) == 2 ? "frvsr::warp_s2d_planes_items<half>" : "frvsr::warp_s2d_planes_items<float>", "warp (items)", lr_flow, Table{hr_prev}, out, n, h, w,
+                  UpBicubic4{bic4_taps()}, st);
 }
 template void op_warp_s2d_planes_items<float>(const float*, const FrvsrPtrs&, float*, int, int, int, hipStream_t);
 template void op_warp_s2d_planes_items<__half>(const float*, const FrvsrPtrs&, __half*, int, int, int, hipStream_t);
 
-// ------------------------------------------------------------------ PixelShuffle(4) + ReLU + Conv2d(4, 3, 3, 1, 1) -> fp32 NCHW
-// One thread per HR pixel.  Shuffled channel c of HR pixel (Y, X) is LR channel c * 16 + (Y % 4) * 4 + X % 4 of pixel (Y / 4, X / 4): element
-// (Y % 4) * 4 + X % 4 of plane c's record.  3 x 3 x 4 rectified values, 108 MACs in fp32, weights and biases in LDS; zero padding at the HR border.
-// HR pixel (Y, X) of item img: the three output values, bias first, taps in (ky, kx, c) order
-template <typename T>
-__device__ __forceinline__ void ps4_tail_pixel(const T* __restrict__ in, const float* s_w, size_t img, size_t npix, int X, int Y, int h, int w, float acc[3]) {
-  const int H = 4 * h, W = 4 * w;
-  acc[0] = s_w[108]; acc[1] = s_w[109]; acc[2] = s_w[110];
-#pragma unroll
-  for (int ky = 0; ky < 3; ++ky) {
-    const int yy = Y + ky - 1;
-    if (yy < 0 || yy >= H) continue;
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      const int xx = X + kx - 1;
-      if (xx < 0 || xx >= W) continue;
-      const size_t pix = (img * h + (yy >> 2)) * w + (xx >> 2);
-      const int sub = (yy & 3) * 4 + (xx & 3);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float v = fmaxf((float)in[((size_t)c * npix + pix) * 16 + sub], 0.f);
-#pragma unroll
-        for (int o = 0; o < 3; ++o) acc[o] = fmaf(s_w[((o * 4 + c) * 3 + ky) * 3 + kx], v, acc[o]);
-      }
-    }
-  }
-}
-template <typename T>
-__global__ __launch_bounds__(256) void k_ps4_conv_tail(const T* __restrict__ in, const float* __restrict__ wb, float* __restrict__ out, int n, int h, int w) {
-  __shared__ float s_w[112];
-  if (threadIdx.x < 111) s_w[threadIdx.x] = wb[threadIdx.x];
-  __syncthreads();
-  const int H = 4 * h, W = 4 * w;
-  const size_t HW = (size_t)H * W, total = (size_t)n * HW, npix = (size_t)n * h * w;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int X = (int)(i % W), Y = (int)((i / W) % H);
-    const size_t img = i / HW;
-    float acc[3];
-    ps4_tail_pixel<T>(in, s_w, img, npix, X, Y, h, w, acc);
-    const size_t p = i - img * HW;
-#pragma unroll
-    for (int o = 0; o < 3; ++o) out[(img * 3 + o) * HW + p] = acc[o];
-  }
-}
-// ... writing every item's (3, 4 h, 4 w) where its stream keeps it (FrvsrPtrs by value, as k_warp_s2d_planes_items)
-template <typename T>
-__global__ __launch_bounds__(256) void k_ps4_conv_tail_items(const T* __restrict__ in, const float* __restrict__ wb, FrvsrPtrs out, int n, int h, int w) {
-  __shared__ float s_w[112];
-  if (threadIdx.x < 111) s_w[threadIdx.x] = wb[threadIdx.x];
-  __syncthreads();
-  const int H = 4 * h, W = 4 * w;
-  const size_t HW = (size_t)H * W, total = (size_t)n * HW, npix = (size_t)n * h * w;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int X = (int)(i % W), Y = (int)((i / W) % H);
-    const size_t img = i / HW;
-    float acc[3];
-    ps4_tail_pixel<T>(in, s_w, img, npix, X, Y, h, w, acc);
-    float* dst = out.p[img] + (i - img * HW);
-#pragma unroll
-    for (int o = 0; o < 3; ++o) dst[o * HW] = acc[o];
-  }
-}
 template <typename T>
 void op_ps4_conv_tail(const T* in, const float* wb, float* out, int n, int h, int w, hipStream_t st) {
-  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "tail: sizes");
-  SS4K_GLUE_ROUTE(sizeof(T) == 2 ? "frvsr::ps4_conv_tail<half>" : "frvsr::ps4_conv_tail<float>");
-  hipLaunchKernelGGL((k_ps4_conv_tail<T>), grid_for((size_t)n * 16 * h * w), dim3(256), 0, st, in, wb, out, n, h, w);
-  SS4K_LAUNCH_OK();
+  launch_ps4_conv_tail(sizeof(T) == 2 ? "frvsr::ps4_conv_tail<half>" : "frvsr::ps4_conv_tail<float>", "tail",
+                       in, wb, Strided<float>{out, (size_t)48 * h * w}, n, h, w, st);
 }
 template void op_ps4_conv_tail<float>(const float*, const float*, float*, int, int, int, hipStream_t);
 template void op_ps4_conv_tail<__half>(const __half*, const float*, float*, int, int, int, hipStream_t);
 template <typename T>
 void op_ps4_conv_tail_items(const T* in, const float* wb, const FrvsrPtrs& out, int n, int h, int w, hipStream_t st) {
-  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "tail (items): sizes");
-  for (int i = 0; i < n; ++i) SS4K_REQUIRE(out.p[i], "tail (items): NULL item");
-  SS4K_GLUE_ROUTE(sizeof(T) == 2 ? "frvsr::ps4_conv_tail_items<half>" : "frvsr::ps4_conv_tail_items<float>");
-  hipLaunchKernelGGL((k_ps4_conv_tail_items<T>), grid_for((size_t)n * 16 * h * w), dim3(256), 0, st, in, wb, out, n, h, w);
-  SS4K_LAUNCH_OK();
+  launch_ps4_conv_tail(sizeof(T) == 2 ? "frvsr::ps4_conv_tail_items<half>" : "frvsr::ps4_conv_tail_items<float>", "tail (items)", in, wb, Table{out}, n, h, w, st);
 }
 template void op_ps4_conv_tail_items<float>(const float*, const float*, const FrvsrPtrs&, int, int, int, hipStream_t);
 template void op_ps4_conv_tail_items<__half>(const __half*, const float*, const FrvsrPtrs&, int, int, int, hipStream_t);
 
-// ------------------------------------------------------------------ conv_out + BicubicUpsample(4)(lr_curr) -> fp32 NCHW (TecoGAN's tail)
-// One thread per HR value.  The skip is bic4_load / bic4_at, as k_bicubic_upsample4 calls them: that op's value bit for bit, then ONE rounded add
-__device__ __forceinline__ float bic4_add_value(const Bic4& t, const float* __restrict__ lr_plane, float conv, int X, int Y, int h, int w) {
-  float f[4][4];
-  bic4_load(lr_plane, Y >> 2, X >> 2, h, w, f);
-  return __fadd_rn(conv, bic4_at(t, f, Y & 3, X & 3));
-}
-__global__ __launch_bounds__(256) void k_bicubic4_add(const float* __restrict__ conv, const float* __restrict__ lr, float* __restrict__ out, int planes, int h,
-                                                      int w, Bic4 taps) {
-  const int OW = 4 * w, OH = 4 * h;
-  const size_t total = (size_t)planes * OH * OW;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int X = (int)(i % OW), Y = (int)((i / OW) % OH);
-    const size_t pl = i / ((size_t)OW * OH);
-    out[i] = bic4_add_value(taps, lr + pl * h * w, conv[i], X, Y, h, w);
-  }
-}
-// ... item (pl / 3) reading lr.p[item] and writing out.p[item] (FrvsrPtrs by value, as k_ps4_conv_tail_items); conv stays one batch
-__global__ __launch_bounds__(256) void k_bicubic4_add_items(const float* __restrict__ conv, FrvsrPtrs lr, FrvsrPtrs out, int planes, int h, int w, Bic4 taps) {
-  const int OW = 4 * w, OH = 4 * h;
-  const size_t HW = (size_t)OW * OH, total = (size_t)planes * HW;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int X = (int)(i % OW), Y = (int)((i / OW) % OH);
-    const size_t pl = i / HW, item = pl / 3, c = pl - item * 3;
-    out.p[item][c * HW + (i - pl * HW)] = bic4_add_value(taps, lr.p[item] + c * h * w, conv[i], X, Y, h, w);
-  }
-}
+// (the tail of the second generator: bounded by tests/test_gpu_tecogan*.py)
 void op_bicubic4_add(const float* conv, const float* lr, float* out, int n, int h, int w, hipStream_t st) {
-  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "bicubic4_add: sizes");
-  SS4K_GLUE_ROUTE("frvsr_teco::bicubic4_add");   // (the tail of the second generator: bounded by tests/test_gpu_tecogan*.py)
-  hipLaunchKernelGGL(k_bicubic4_add, grid_for((size_t)n * 3 * 16 * h * w), dim3(256), 0, st, conv, lr, out, 3 * n, h, w, bic4_taps());
-  SS4K_LAUNCH_OK();
+  launch_x4_add("frvsr_teco::bicubic4_add", "bicubic4_add", conv, Strided<const float>{lr, (size_t)3 * h * w}, Strided<float>{out, (size_t)48 * h * w}, n, h, w,
+                UpBicubic4{bic4_taps()}, st);
 }
 void op_bicubic4_add_items(const float* conv, const FrvsrPtrs& lr, const FrvsrPtrs& out, int n, int h, int w, hipStream_t st) {
-  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "bicubic4_add (items): sizes");
-  for (int i = 0; i < n; ++i) SS4K_REQUIRE(lr.p[i] && out.p[i], "bicubic4_add (items): NULL item");
-  SS4K_GLUE_ROUTE("frvsr_teco::bicubic4_add_items");
-  hipLaunchKernelGGL(k_bicubic4_add_items, grid_for((size_t)n * 3 * 16 * h * w), dim3(256), 0, st, conv, lr, out, 3 * n, h, w, bic4_taps());
-  SS4K_LAUNCH_OK();
+  launch_x4_add("frvsr_teco::bicubic4_add_items", "bicubic4_add (items)", conv, Table{lr}, Table{out}, n, h, w, UpBicubic4{bic4_taps()}, st);
 }
 
 // ------------------------------------------------------------------ planes -> fp32 NCHW (parity taps), clamp into another tensor

@@ -20,7 +20,7 @@ import torch.nn.functional as F
 from oracle import frvsr_ref as R
 from tests import egvsr_oracle as EO
 from tests import frvsr_glue_cases as FC
-from tests.frvsr_glue_cases import F32, F64, FLOWS, budget, depth_to_space4, exact, lr_flow  # noqa: F401
+from tests.frvsr_glue_cases import F32, F64, FLOWS, NO_ITEMS, budget, depth_to_space4, exact, lr_flow  # noqa: F401
 from tests.glue_cases import KINDS, Case, _ht, _seed, plane  # noqa: F401
 
 t = R.t
@@ -135,6 +135,9 @@ def _s2d_cases():
     for half in (False, True):
         out.append(Case(f"warp_s2d_bi_8x8_smooth_n64_{_ht(half)}", "warp_s2d_bi", dict(nhw=(64, 8, 8), flow="smooth", half=half, order=None),
                         routes("warp_s2d_bi_planes", half) | routes("warp_s2d_bi_planes_items", half)))
+        # one item more than a pointer table holds: the contiguous form alone (frvsr_glue_cases.NO_ITEMS), every item with its own hr_prev and flow
+        out.append(Case(f"warp_s2d_bi_8x8_smooth_n65_{_ht(half)}", "warp_s2d_bi", dict(nhw=(65, 8, 8), flow="smooth", half=half, order=NO_ITEMS),
+                        routes("warp_s2d_bi_planes", half)))
     return out
 
 
@@ -154,7 +157,8 @@ def s2d_check(c, d, got, what):      # the form of frvsr_glue_cases.s2d_check
 
 def _add_cases():
     return [Case(f"bilinear4_add_{h}x{w}", "bilinear4_add", dict(nhw=(3, h, w), order=(1, 2, 0)), routes("bilinear4_add") | routes("bilinear4_add_items"))
-            for h, w in ((1, 1), (2, 3), (9, 15))]
+            for h, w in ((1, 1), (2, 3), (9, 15))] + \
+           [Case("bilinear4_add_2x3_n65", "bilinear4_add", dict(nhw=(65, 2, 3), order=NO_ITEMS), routes("bilinear4_add"))]
 
 
 def add_inputs(c, kind):

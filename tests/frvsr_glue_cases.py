@@ -132,6 +132,7 @@ def bic_check(c, d, got, what):
 
 # ------------------------------------------------------------------------------ the flow sets of the warps
 FLOWS = ("zero", "shift", "pm96", "smooth", "edge")
+NO_ITEMS = "no items"        # a case's ``order``: more items than SS4K_FRVSR_MAX_STREAMS = 64, so the runner calls the contiguous launcher alone
 
 
 def hr_flow(name, n, H, W, step=1):
@@ -202,6 +203,9 @@ def _s2d_cases():
     for half in (False, True):
         out.append(Case(f"warp_s2d_8x8_smooth_n64_{_ht(half)}", "warp_s2d", dict(nhw=(64, 8, 8), flow="smooth", half=half, order=None),
                         routes("warp_s2d_planes", half) | routes("warp_s2d_planes_items", half)))
+        # one item more than a pointer table holds (order: NO_ITEMS): the contiguous form alone, every item with its own hr_prev and flow
+        out.append(Case(f"warp_s2d_8x8_smooth_n65_{_ht(half)}", "warp_s2d", dict(nhw=(65, 8, 8), flow="smooth", half=half, order=NO_ITEMS),
+                        routes("warp_s2d_planes", half)))
     return out
 
 
@@ -239,7 +243,9 @@ def tail_wb(which):
 def _tail_cases():
     return [Case(f"ps4_tail_{h}x{w}_{wb}_{_ht(half)}", "ps4_tail", dict(nhw=(3, h, w), wb=wb, half=half, order=(1, 2, 0)),
                  routes("ps4_conv_tail", half) | routes("ps4_conv_tail_items", half))
-            for h, w in ((1, 1), (2, 3), (9, 15)) for wb in ("frnet", "bias") for half in (False, True)]
+            for h, w in ((1, 1), (2, 3), (9, 15)) for wb in ("frnet", "bias") for half in (False, True)] + \
+           [Case(f"ps4_tail_2x3_frnet_n65_{_ht(half)}", "ps4_tail", dict(nhw=(65, 2, 3), wb="frnet", half=half, order=NO_ITEMS), routes("ps4_conv_tail", half))
+            for half in (False, True)]
 
 
 def tail_inputs(c, kind):

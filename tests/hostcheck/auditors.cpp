@@ -218,14 +218,14 @@ void op_temporal_shift(const void* in, void* out, int nplanes, int frames, size_
 // SS4K_REQUIRE lines first: the executor meets the refusals the product meets, at the same place.
 template <typename T>
 void op_maxpool2_planes(const T* in, T* out, int nplanes, int n, int h, int w, hipStream_t) {
-  SS4K_REQUIRE(nplanes > 0 && n > 0 && h >= 2 && w >= 2, "maxpool2: needs at least 2 x 2 pixels");   // frvsr.hip:52
+  SS4K_REQUIRE(nplanes > 0 && n > 0 && h >= 2 && w >= 2, "maxpool2: needs at least 2 x 2 pixels");   // op_maxpool2_planes (frvsr.hip)
   const char* K = "maxpool2_planes";
   begin_launch(K);
   const size_t rec = 16 * sizeof(T), ipx = (size_t)n * h * w, opx = (size_t)n * (h / 2) * (w / 2);
   // plane p reads pixels 2 oy, 2 oy + 1 x 2 ox, 2 ox + 1 of every image: up to ((n - 1) h + 2 (h / 2) - 1) w + 2 (w / 2) - 1 of its n h w
   const size_t last = ((size_t)(n - 1) * h + 2 * (size_t)(h / 2) - 1) * w + 2 * (size_t)(w / 2) - 1;
-  for (int p = 0; p < nplanes; ++p) need(K, -1, "in", "frvsr.hip:40-43", reinterpret_cast<const char*>(in) + (size_t)p * ipx * rec, (last + 1) * rec);
-  need(K, -1, "out", "frvsr.hip:34,47", out, (size_t)nplanes * opx * rec, true);
+  for (int p = 0; p < nplanes; ++p) need(K, -1, "in", "frvsr.hip: k_maxpool2_planes", reinterpret_cast<const char*>(in) + (size_t)p * ipx * rec, (last + 1) * rec);
+  need(K, -1, "out", "frvsr.hip: k_maxpool2_planes", out, (size_t)nplanes * opx * rec, true);
   end_launch();
 }
 template void op_maxpool2_planes<float>(const float*, float*, int, int, int, int, hipStream_t);
@@ -233,48 +233,48 @@ template void op_maxpool2_planes<__half>(const __half*, __half*, int, int, int, 
 
 template <typename T>
 void op_bilinear2_planes(const T* in, T* out, int nplanes, int n, int h, int w, hipStream_t) {
-  SS4K_REQUIRE(nplanes > 0 && n > 0 && h > 0 && w > 0, "bilinear x2: empty tensor");   // frvsr.hip:93
+  SS4K_REQUIRE(nplanes > 0 && n > 0 && h > 0 && w > 0, "bilinear x2: empty tensor");   // op_bilinear2_planes (frvsr.hip)
   const char* K = "bilinear2_planes";
   begin_launch(K);
   const size_t rec = 16 * sizeof(T), ipx = (size_t)n * h * w;
-  need(K, -1, "in", "frvsr.hip:66,81-84", in, (size_t)nplanes * ipx * rec);           // rows and columns 0 .. size - 1 of every image
-  need(K, -1, "out", "frvsr.hip:73,88", out, (size_t)nplanes * ipx * 4 * rec, true);
+  need(K, -1, "in", "frvsr.hip: k_bilinear2_planes", in, (size_t)nplanes * ipx * rec);           // rows and columns 0 .. size - 1 of every image
+  need(K, -1, "out", "frvsr.hip: k_bilinear2_planes", out, (size_t)nplanes * ipx * 4 * rec, true);
   end_launch();
 }
 template void op_bilinear2_planes<float>(const float*, float*, int, int, int, int, hipStream_t);
 template void op_bilinear2_planes<__half>(const __half*, __half*, int, int, int, int, hipStream_t);
 
 void op_flow_finish(const float* raw, float* flow, int n, int h8, int w8, int h, int w, hipStream_t) {
-  SS4K_REQUIRE(n > 0 && h8 >= 8 && w8 >= 8 && h >= h8 && w >= w8 && h - h8 < 8 && w - w8 < 8, "flow pad: sizes");   // frvsr.hip:114
+  SS4K_REQUIRE(n > 0 && h8 >= 8 && w8 >= 8 && h >= h8 && w >= w8 && h - h8 < 8 && w - w8 < 8, "flow pad: sizes");   // op_flow_finish (frvsr.hip)
   const char* K = "flow_finish";
   begin_launch(K);
-  need(K, -1, "raw", "frvsr.hip:109-110", raw, (size_t)n * 2 * h8 * w8 * 4);   // sy in [2 (h8 - 1) - (h - 1), h8): inside as h - h8 < 8 <= h8
-  need(K, -1, "flow", "frvsr.hip:105,110", flow, (size_t)n * 2 * h * w * 4, true);
+  need(K, -1, "raw", "frvsr.hip: k_flow_finish", raw, (size_t)n * 2 * h8 * w8 * 4);   // sy in [2 (h8 - 1) - (h - 1), h8): inside as h - h8 < 8 <= h8
+  need(K, -1, "flow", "frvsr.hip: k_flow_finish", flow, (size_t)n * 2 * h * w * 4, true);
   end_launch();
 }
 
-// degradation 'BD' (frvsr.hip) and 'BI' (frvsr_bi.hip:110-121): the two launchers differ in the flow's up-sampling function alone, which reads the
-// same (n, 2, h, w) flow; the warp, the records, the requirements and the grid are the same
+// degradation 'BD' (frvsr.hip) and 'BI' (frvsr_bi.hip): the launchers are one launch helper and one kernel template (frvsr_stages.h) and differ in the
+// flow's up-sampler alone, which reads the same (n, 2, h, w) flow; the warp, the records, the requirements and the grid are the same
 template <typename T>
 void warp_s2d(const char* K, const float* lr_flow, const float* hr_prev, T* out, int n, int h, int w) {
-  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull, "warp: sizes");   // frvsr.hip:266, frvsr_bi.hip:111
+  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull, "warp: sizes");   // launch_warp_s2d (frvsr_stages.h), "<what>: sizes"
   begin_launch(K);
   const size_t hw = (size_t)h * w;
-  need(K, -1, "lr_flow", "frvsr.hip:146,229-230", lr_flow, (size_t)n * 2 * hw * 4);
-  // a tap lies anywhere in [0, 4 h - 1] x [0, 4 w - 1] of the item's three colour planes (warp_pos clips: frvsr.hip:164,173)
-  need(K, -1, "hr_prev", "frvsr.hip:178,238,251", hr_prev, (size_t)n * 3 * 16 * hw * 4, false, n == 1 ? 0 : -1);
-  need(K, -1, "out", "frvsr.hip:243", out, (size_t)3 * n * hw * 16 * sizeof(T), true);
+  need(K, -1, "lr_flow", "frvsr_stages.h: k_warp_s2d", lr_flow, (size_t)n * 2 * hw * 4);
+  // a tap lies anywhere in [0, 4 h - 1] x [0, 4 w - 1] of the item's three colour planes (warp_pos clips)
+  need(K, -1, "hr_prev", "frvsr_stages.h: k_warp_s2d", hr_prev, (size_t)n * 3 * 16 * hw * 4, false, n == 1 ? 0 : -1);
+  need(K, -1, "out", "frvsr_stages.h: k_warp_s2d", out, (size_t)3 * n * hw * 16 * sizeof(T), true);
   end_launch();
 }
 template <typename T>
 void warp_s2d_items(const char* K, const float* lr_flow, const FrvsrPtrs& hr_prev, T* out, int n, int h, int w) {
-  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull, "warp (items): sizes");   // frvsr.hip:275, frvsr_bi.hip:120
-  for (int i = 0; i < n; ++i) SS4K_REQUIRE(hr_prev.p[i], "warp (items): NULL item");                                               // frvsr.hip:276, frvsr_bi.hip:121
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull, "warp (items): sizes");   // launch_warp_s2d (frvsr_stages.h), "<what>: sizes"
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(hr_prev.p[i], "warp (items): NULL item");   // launch_warp_s2d (frvsr_stages.h), "<what>: NULL item"
   begin_launch(K);
   const size_t hw = (size_t)h * w;
-  need(K, -1, "lr_flow", "frvsr.hip:146,229-230", lr_flow, (size_t)n * 2 * hw * 4);
-  for (int i = 0; i < n; ++i) need(K, -1, "hr_prev[i]", "frvsr.hip:178,238,261", hr_prev.p[i], (size_t)3 * 16 * hw * 4, false, i);
-  need(K, -1, "out", "frvsr.hip:243", out, (size_t)3 * n * hw * 16 * sizeof(T), true);
+  need(K, -1, "lr_flow", "frvsr_stages.h: k_warp_s2d", lr_flow, (size_t)n * 2 * hw * 4);
+  for (int i = 0; i < n; ++i) need(K, -1, "hr_prev[i]", "frvsr_stages.h: k_warp_s2d", hr_prev.p[i], (size_t)3 * 16 * hw * 4, false, i);
+  need(K, -1, "out", "frvsr_stages.h: k_warp_s2d", out, (size_t)3 * n * hw * 16 * sizeof(T), true);
   end_launch();
 }
 template <typename T> void op_warp_s2d_planes(const float* f, const float* hp, T* out, int n, int h, int w, hipStream_t) { warp_s2d("warp_s2d_planes", f, hp, out, n, h, w); }
@@ -292,13 +292,13 @@ template void op_warp_s2d_bi_planes_items<__half>(const float*, const FrvsrPtrs&
 
 template <typename T>
 void op_ps4_conv_tail(const T* in, const float* wb, float* out, int n, int h, int w, hipStream_t) {
-  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "tail: sizes");   // frvsr.hip:349
+  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "tail: sizes");   // launch_ps4_conv_tail (frvsr_stages.h), "<what>: sizes"
   const char* K = "ps4_conv_tail";
   begin_launch(K);
   const size_t hw = (size_t)h * w;
-  need(K, -1, "in", "frvsr.hip:301-305", in, (size_t)4 * n * hw * 16 * sizeof(T));   // planes 0..3, every pixel's 16 sub-pixel elements
-  need(K, -1, "wb", "frvsr.hip:315", wb, 111 * 4);
-  need(K, -1, "out", "frvsr.hip:326", out, (size_t)n * 3 * 16 * hw * 4, true, n == 1 ? 0 : -1);
+  need(K, -1, "in", "frvsr_stages.h: k_ps4_conv_tail", in, (size_t)4 * n * hw * 16 * sizeof(T));   // planes 0..3, every pixel's 16 sub-pixel elements
+  need(K, -1, "wb", "frvsr_stages.h: k_ps4_conv_tail", wb, 111 * 4);
+  need(K, -1, "out", "frvsr_stages.h: k_ps4_conv_tail", out, (size_t)n * 3 * 16 * hw * 4, true, n == 1 ? 0 : -1);
   end_launch();
 }
 template void op_ps4_conv_tail<float>(const float*, const float*, float*, int, int, int, hipStream_t);
@@ -306,39 +306,39 @@ template void op_ps4_conv_tail<__half>(const __half*, const float*, float*, int,
 
 template <typename T>
 void op_ps4_conv_tail_items(const T* in, const float* wb, const FrvsrPtrs& out, int n, int h, int w, hipStream_t) {
-  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "tail (items): sizes");   // frvsr.hip:358
-  for (int i = 0; i < n; ++i) SS4K_REQUIRE(out.p[i], "tail (items): NULL item");                                                       // frvsr.hip:359
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "tail (items): sizes");   // launch_ps4_conv_tail (frvsr_stages.h), "<what>: sizes"
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(out.p[i], "tail (items): NULL item");   // launch_ps4_conv_tail (frvsr_stages.h), "<what>: NULL item"
   const char* K = "ps4_conv_tail(items)";
   begin_launch(K);
   const size_t hw = (size_t)h * w;
-  need(K, -1, "in", "frvsr.hip:301-305", in, (size_t)4 * n * hw * 16 * sizeof(T));
-  need(K, -1, "wb", "frvsr.hip:333", wb, 111 * 4);
-  for (int i = 0; i < n; ++i) need(K, -1, "out[i]", "frvsr.hip:342-344", out.p[i], (size_t)3 * 16 * hw * 4, true, i);
+  need(K, -1, "in", "frvsr_stages.h: k_ps4_conv_tail", in, (size_t)4 * n * hw * 16 * sizeof(T));
+  need(K, -1, "wb", "frvsr_stages.h: k_ps4_conv_tail", wb, 111 * 4);
+  for (int i = 0; i < n; ++i) need(K, -1, "out[i]", "frvsr_stages.h: k_ps4_conv_tail", out.p[i], (size_t)3 * 16 * hw * 4, true, i);
   end_launch();
 }
 template void op_ps4_conv_tail_items<float>(const float*, const float*, const FrvsrPtrs&, int, int, int, hipStream_t);
 template void op_ps4_conv_tail_items<__half>(const __half*, const float*, const FrvsrPtrs&, int, int, int, hipStream_t);
 
-// TecoGAN's skip: out = conv + x4 up-sampling of lr, bicubic (frvsr.hip:338-370) or bilinear (frvsr_bi.hip:157-168): every tap is clamped into the
+// TecoGAN's skip: out = conv + x4 up-sampling of lr, bicubic (frvsr.hip) or bilinear (frvsr_bi.hip) through launch_x4_add: every tap is clamped into the
 // item's (3, h, w) planes, conv and out are read and written element by element
 void x4_add(const char* K, const float* conv, const float* lr, float* out, int n, int h, int w) {
-  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "x4_add: sizes");   // frvsr.hip:359, frvsr_bi.hip:158
+  SS4K_REQUIRE(n > 0 && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "x4_add: sizes");   // launch_x4_add (frvsr_stages.h), "<what>: sizes"
   begin_launch(K);
   const size_t hw = (size_t)h * w;
-  need(K, -1, "conv", "frvsr.hip:345", conv, (size_t)n * 48 * hw * 4);
-  need(K, -1, "lr", "frvsr.hip:345", lr, (size_t)n * 3 * hw * 4, false, n == 1 ? 0 : -1);
-  need(K, -1, "out", "frvsr.hip:345", out, (size_t)n * 48 * hw * 4, true, n == 1 ? 0 : -1);
+  need(K, -1, "conv", "frvsr_stages.h: k_x4_add", conv, (size_t)n * 48 * hw * 4);
+  need(K, -1, "lr", "frvsr_stages.h: k_x4_add", lr, (size_t)n * 3 * hw * 4, false, n == 1 ? 0 : -1);
+  need(K, -1, "out", "frvsr_stages.h: k_x4_add", out, (size_t)n * 48 * hw * 4, true, n == 1 ? 0 : -1);
   end_launch();
 }
 void x4_add_items(const char* K, const float* conv, const FrvsrPtrs& lr, const FrvsrPtrs& out, int n, int h, int w) {
-  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "x4_add (items): sizes");   // frvsr.hip:365, frvsr_bi.hip:164
-  for (int i = 0; i < n; ++i) SS4K_REQUIRE(lr.p[i] && out.p[i], "x4_add (items): NULL item");                                            // frvsr.hip:366, frvsr_bi.hip:165
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && (size_t)n * h * w < 2147483648ull / 16, "x4_add (items): sizes");   // launch_x4_add (frvsr_stages.h), "<what>: sizes"
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(lr.p[i] && out.p[i], "x4_add (items): NULL item");   // launch_x4_add (frvsr_stages.h), "<what>: NULL item"
   begin_launch(K);
   const size_t hw = (size_t)h * w;
-  need(K, -1, "conv", "frvsr.hip:355", conv, (size_t)n * 48 * hw * 4);
+  need(K, -1, "conv", "frvsr_stages.h: k_x4_add", conv, (size_t)n * 48 * hw * 4);
   for (int i = 0; i < n; ++i) {
-    need(K, -1, "lr[i]", "frvsr.hip:355", lr.p[i], 3 * hw * 4, false, i);
-    need(K, -1, "out[i]", "frvsr.hip:355", out.p[i], 48 * hw * 4, true, i);
+    need(K, -1, "lr[i]", "frvsr_stages.h: k_x4_add", lr.p[i], 3 * hw * 4, false, i);
+    need(K, -1, "out[i]", "frvsr_stages.h: k_x4_add", out.p[i], 48 * hw * 4, true, i);
   }
   end_launch();
 }
@@ -366,8 +366,8 @@ void op_planes_to_nchw(const T* in, float* out, int n, int channels, int h, int 
   const char* K = "planes_to_nchw";
   begin_launch(K);
   const size_t npix = (size_t)n * h * w;
-  need(K, -1, "in", "frvsr.hip:373", in, (size_t)((channels + 15) / 16) * npix * 16 * sizeof(T));
-  need(K, -1, "out", "frvsr.hip:370,373", out, npix * channels * 4, true);
+  need(K, -1, "in", "frvsr.hip: k_planes_to_nchw", in, (size_t)((channels + 15) / 16) * npix * 16 * sizeof(T));
+  need(K, -1, "out", "frvsr.hip: k_planes_to_nchw", out, npix * channels * 4, true);
   end_launch();
 }
 template void op_planes_to_nchw<float>(const float*, float*, int, int, int, int, hipStream_t);
@@ -376,53 +376,53 @@ template void op_planes_to_nchw<__half>(const __half*, float*, int, int, int, in
 void op_clamp01_to(const float* in, float* out, size_t n, hipStream_t) {
   const char* K = "clamp01_to";
   begin_launch(K);
-  need(K, -1, "in", "frvsr.hip:386", in, n * 4);
-  need(K, -1, "out", "frvsr.hip:386", out, n * 4, true);
+  need(K, -1, "in", "frvsr.hip: k_clamp01_to", in, n * 4);
+  need(K, -1, "out", "frvsr.hip: k_clamp01_to", out, n * 4, true);
   end_launch();
 }
 
 void op_frames_in_items(const FrvsrFramesIn& in, const FrvsrPtrs& lr_curr, int n, int h, int w, int lh, int lw, hipStream_t) {
-  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && lh > 0 && lw > 0, "frames in (items): sizes");                  // frvsr.hip:431
-  SS4K_REQUIRE((double)h * lh < 2147483648.0 && (double)w * lw < 2147483648.0, "frames in (items): a window bound would overflow");   // frvsr.hip:432
-  for (int i = 0; i < n; ++i) SS4K_REQUIRE(in.p[i] && lr_curr.p[i], "frames in (items): NULL item");                                   // frvsr.hip:433
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && lh > 0 && lw > 0, "frames in (items): sizes");   // op_frames_in_items (frvsr.hip)
+  SS4K_REQUIRE((double)h * lh < 2147483648.0 && (double)w * lw < 2147483648.0, "frames in (items): a window bound would overflow");   // op_frames_in_items (frvsr.hip)
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(in.p[i] && lr_curr.p[i], "frames in (items): NULL item");   // op_frames_in_items (frvsr.hip)
   const char* K = "frames_in(items)";
   begin_launch(K);
   for (int i = 0; i < n; ++i) {
-    // the windows [floor(i h / lh), ceil((i + 1) h / lh)) cover rows 0 .. h - 1 whichever of h, lh is larger (frvsr.hip:401-402,417-423)
-    need(K, -1, "in[i]", "frvsr.hip:413,420-423", in.p[i], (size_t)h * w * 3, false, i);
-    need(K, -1, "lr_curr[i]", "frvsr.hip:410,413,427", lr_curr.p[i], (size_t)3 * lh * lw * 4, true, i);
+    // the windows [floor(i h / lh), ceil((i + 1) h / lh)) cover rows 0 .. h - 1 whichever of h, lh is larger (area_lo / area_hi)
+    need(K, -1, "in[i]", "frvsr.hip: k_frames_in_items", in.p[i], (size_t)h * w * 3, false, i);
+    need(K, -1, "lr_curr[i]", "frvsr.hip: k_frames_in_items", lr_curr.p[i], (size_t)3 * lh * lw * 4, true, i);
   }
   end_launch();
 }
 
 template <typename T>
 void op_pack_lr_items(const FrvsrPtrs& lr_curr, const FrvsrPtrs& lr_prev, T* a, T* b, int n, int h, int w, hipStream_t) {
-  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && a && b, "pack (items): sizes");   // frvsr.hip:456
-  for (int i = 0; i < n; ++i) SS4K_REQUIRE(lr_curr.p[i] && lr_prev.p[i], "pack (items): NULL item");      // frvsr.hip:457
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && h > 0 && w > 0 && a && b, "pack (items): sizes");   // op_pack_lr_items (frvsr.hip)
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(lr_curr.p[i] && lr_prev.p[i], "pack (items): NULL item");   // op_pack_lr_items (frvsr.hip)
   const char* K = "pack_lr(items)";
   begin_launch(K);
   const size_t hw = (size_t)h * w;
   for (int i = 0; i < n; ++i) {
-    need(K, -1, "lr_curr[i]", "frvsr.hip:445,449", lr_curr.p[i], 3 * hw * 4, false, i);
-    need(K, -1, "lr_prev[i]", "frvsr.hip:446,449", lr_prev.p[i], 3 * hw * 4, false, i);
+    need(K, -1, "lr_curr[i]", "frvsr.hip: k_pack_lr_items", lr_curr.p[i], 3 * hw * 4, false, i);
+    need(K, -1, "lr_prev[i]", "frvsr.hip: k_pack_lr_items", lr_prev.p[i], 3 * hw * 4, false, i);
   }
-  need(K, -1, "a", "frvsr.hip:451", a, (size_t)n * hw * 16 * sizeof(T), true);
-  need(K, -1, "b", "frvsr.hip:451", b, (size_t)n * hw * 16 * sizeof(T), true);
+  need(K, -1, "a", "frvsr.hip: k_pack_lr_items", a, (size_t)n * hw * 16 * sizeof(T), true);
+  need(K, -1, "b", "frvsr.hip: k_pack_lr_items", b, (size_t)n * hw * 16 * sizeof(T), true);
   end_launch();
 }
 template void op_pack_lr_items<float>(const FrvsrPtrs&, const FrvsrPtrs&, float*, float*, int, int, int, hipStream_t);
 template void op_pack_lr_items<__half>(const FrvsrPtrs&, const FrvsrPtrs&, __half*, __half*, int, int, int, hipStream_t);
 
 void op_frames_out_items(const FrvsrPtrs& hr, const FrvsrFramesOut& out, int n, int H, int W, int oh, int ow, hipStream_t) {
-  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && H > 0 && W > 0 && oh > 0 && ow > 0, "frames out (items): sizes");                  // frvsr.hip:522
-  SS4K_REQUIRE((double)H * oh < 2147483648.0 && (double)W * ow < 2147483648.0, "frames out (items): a window bound would overflow");   // frvsr.hip:523
-  for (int i = 0; i < n; ++i) SS4K_REQUIRE(hr.p[i] && out.p[i], "frames out (items): NULL item");                                      // frvsr.hip:524
+  SS4K_REQUIRE(n > 0 && n <= SS4K_FRVSR_MAX_STREAMS && H > 0 && W > 0 && oh > 0 && ow > 0, "frames out (items): sizes");   // op_frames_out_items (frvsr.hip)
+  SS4K_REQUIRE((double)H * oh < 2147483648.0 && (double)W * ow < 2147483648.0, "frames out (items): a window bound would overflow");   // op_frames_out_items (frvsr.hip)
+  for (int i = 0; i < n; ++i) SS4K_REQUIRE(hr.p[i] && out.p[i], "frames out (items): NULL item");   // op_frames_out_items (frvsr.hip)
   const char* K = "frames_out(items)";
   begin_launch(K);
   for (int i = 0; i < n; ++i) {
-    need(K, -1, "hr[i]", "frvsr.hip:483,489,501", hr.p[i], (size_t)3 * H * W * 4, false, i);
-    // groups of four pixels, twelve bytes each, the last group cut at oh * ow pixels: 4-byte stores only in whole groups (frvsr.hip:506-517)
-    need(K, -1, "out[i]", "frvsr.hip:476,513,517", out.p[i], (size_t)oh * ow * 3, true, i);
+    need(K, -1, "hr[i]", "frvsr.hip: k_frames_out_items", hr.p[i], (size_t)3 * H * W * 4, false, i);
+    // groups of four pixels, twelve bytes each, the last group cut at oh * ow pixels: 4-byte stores only in whole groups
+    need(K, -1, "out[i]", "frvsr.hip: k_frames_out_items", out.p[i], (size_t)oh * ow * 3, true, i);
   }
   end_launch();
 }

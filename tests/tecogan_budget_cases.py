@@ -178,7 +178,9 @@ TAIL_CASES = [
     TailCase("2x9x15", (2, 9, 15), 0),
     TailCase("1x9x33_straddles_the_tile", (1, TH + 1, TW + 1), 0),   # 2 x 2 tiles; the second layer runs at 18 x 66: 3 x 3 tiles
     TailCase("1x9x33_two_workgroups", (1, TH + 1, TW + 1), 2),       # ... walked by two workgroups: 2 and 4 or 5 tiles each
+    TailCase("65x2x3", (65, 2, 3), 0),                               # one contiguous batch of more items than a pointer table (and a group) holds
 ]
+GROUP_MAX = 64   # items per group of the tail's walk at most (SS4K_FRVSR_MAX_STREAMS; csrc/frvsr_teco.cpp: run_teco_tail)
 TAIL_SLICES = dict(tiles=(1, 2))    # up2 and hr are at the second layer's output; (8 | 16 | 20 rows, 32 columns) x 2 per layer-2 input pixel
 TAIL_SEED = 91
 

@@ -4,8 +4,9 @@ tests/test_gpu_glue_budget.py, as tests/test_gpu_frvsr_glue_budget.py does for c
 
 * ``bilinear_upsample4`` at (2, 2, h, w) for 1 x 1, 1 x 9, 2 x 3 and 15 x 17;
 * ``warp_s2d_bi_planes[_items]`` at n = 3 for 8 x 8, 9 x 15 and 16 x 24 with every flow set, both dtypes, the items in arenas allocated in
-  the order (2, 0, 1) and bit-identical to the contiguous route; n = 64 at 8 x 8;
-* ``bilinear4_add[_items]`` at 1 x 1, 2 x 3 and 9 x 15; its skip equals conv + ``bilinear_upsample4`` bit for bit;
+  the order (2, 0, 1) and bit-identical to the contiguous route; n = 64 at 8 x 8; n = 65 at 8 x 8 on the contiguous route alone;
+* ``bilinear4_add[_items]`` at 1 x 1, 2 x 3 and 9 x 15, n = 65 at 2 x 3 on the contiguous route alone; its skip equals conv +
+  ``bilinear_upsample4`` bit for bit;
 * one case per kernel beyond one pass of the 8192 x 256-thread grid (the fused warps on sampled pixels);
 * the refusals, and the census of the route names of the source.
 """
@@ -43,6 +44,8 @@ def run_s2d(dev, c, d):
     flow = dev.put(d["lr_flow"])
     out, out_items = dev.new((3, n, h, w, 16), _dt(half)), dev.new((3, n, h, w, 16), _dt(half))
     dev.call("ss4k_dev_op_frvsrbi_warp_s2d_planes", flow, dev.put(d["hr_prev"]), out, int(half), n, h, w)
+    if c.a["order"] == BR.NO_ITEMS:
+        return R.from_planes(out.cpu().float(), 48)
     items = scattered(dev, list(d["hr_prev"]), c.a["order"])
     dev.call("ss4k_dev_op_frvsrbi_warp_s2d_planes_items", flow, ptrs(items), out_items, int(half), n, h, w)
     assert torch.equal(bits(out), bits(out_items)), f"{c.id}: the items route differs from the contiguous one"
@@ -54,12 +57,13 @@ def run_add(dev, c, d):
     conv, lr = dev.put(d["conv"]), dev.put(d["lr"])
     out = dev.new((n, 3, 4 * h, 4 * w))
     dev.call("ss4k_dev_op_frvsrbi_bilinear4_add", conv, lr, out, n, h, w)
-    lrs = scattered(dev, list(d["lr"]), c.a["order"])
-    items = [None] * n
-    for i in c.a["order"]:
-        items[i] = dev.new((3, 4 * h, 4 * w))
-    dev.call("ss4k_dev_op_frvsrbi_bilinear4_add_items", conv, ptrs(lrs), ptrs(items), n, h, w)
-    assert torch.equal(bits(out), bits(torch.stack(items))), f"{c.id}: the items route differs from the contiguous one"
+    if c.a["order"] != BR.NO_ITEMS:
+        lrs = scattered(dev, list(d["lr"]), c.a["order"])
+        items = [None] * n
+        for i in c.a["order"]:
+            items[i] = dev.new((3, 4 * h, 4 * w))
+        dev.call("ss4k_dev_op_frvsrbi_bilinear4_add_items", conv, ptrs(lrs), ptrs(items), n, h, w)
+        assert torch.equal(bits(out), bits(torch.stack(items))), f"{c.id}: the items route differs from the contiguous one"
     # the skip is the granular op's value bit for bit, then one rounded add (torch's fp32 add is that add)
     up = dev.new((n, 3, 4 * h, 4 * w))
     dev.call("ss4k_dev_op_frvsrbi_bilinear_upsample4", lr, up, 3 * n, h, w)

@@ -1,6 +1,6 @@
 """GPU: the recurrent streams of both frame-recurrent generators built with degradation 'BI' - LR 16 x 24, one residual block, both dtypes.
-A round's warp reads every stream's hr_prev where it lives (``k_warp_s2d_bi_planes_items``) and TecoGAN's skip writes every item's result
-into that stream's own state buffer (``k_bilinear4_add_items``); all of the following hold bit for bit (``torch.equal``), as they do for
+A round's warp reads every stream's hr_prev where it lives (``op_warp_s2d_bi_planes_items``) and TecoGAN's skip writes every item's result
+into that stream's own state buffer (``op_bilinear4_add_items``); all of the following hold bit for bit (``torch.equal``), as they do for
 'BD' (tests/test_gpu_frvsr_streams.py, tests/test_gpu_frvsr_scattered.py, tests/test_gpu_tecogan_streams.py):
 
 * four streams in ragged rounds on one upscaler equal four single-stream objects;

@@ -98,6 +98,8 @@ def run_s2d(dev, c, d):
     flow = dev.put(d["lr_flow"])
     out, out_items = dev.new((3, n, h, w, 16), _dt(half)), dev.new((3, n, h, w, 16), _dt(half))
     dev.call("ss4k_dev_op_frvsr_warp_s2d_planes", flow, dev.put(d["hr_prev"]), out, int(half), n, h, w)
+    if c.a["order"] == FC.NO_ITEMS:
+        return R.from_planes(out.cpu().float(), 48)
     items = scattered(dev, list(d["hr_prev"]), c.a["order"])
     dev.call("ss4k_dev_op_frvsr_warp_s2d_planes_items", flow, ptrs(items), out_items, int(half), n, h, w)
     assert torch.equal(bits(out), bits(out_items)), f"{c.id}: the items route differs from the contiguous one"
@@ -110,6 +112,8 @@ def run_tail(dev, c, d):
     x, wb = put_planes(dev, d["x"], half), dev.put(d["wb"])
     out = dev.new((n, 3, 4 * h, 4 * w))
     dev.call("ss4k_dev_op_frvsr_ps4_conv_tail", x, int(half), wb, out, n, h, w)
+    if c.a["order"] == FC.NO_ITEMS:
+        return out.cpu()
     items = [None] * n
     for i in c.a["order"]:
         items[i] = dev.new((3, 4 * h, 4 * w))
@@ -183,6 +187,23 @@ def test_frvsr_route_error_budget(dev, case):
     record_measured(f"frvsr_budget_{c.id}", routes=sorted(seen), **{f"{k}_{kk}": v for k, mm in measured.items() for kk, v in mm.items()})
     assert c.must <= seen, f"{c.id}: routes {sorted(c.must - seen)} not launched (launched: {sorted(seen)})"
     assert seen <= FC.FRVSR_ROUTES, sorted(seen - FC.FRVSR_ROUTES)
+
+
+@pytest.mark.parametrize("wrapper", ["ss4k_dev_op_frvsr_warp_s2d_planes", "ss4k_dev_op_frvsrbi_warp_s2d_planes"], ids=["BD", "BI"])
+def test_warp_s2d_half_planes_are_the_float_planes_rounded(dev, wrapper):
+    """The warp's value is rounded to fp32 as backward_warp rounds it and THEN to fp16, so the __half planes are the float planes rounded,
+    bit for bit.  A build whose compiler fuses warp_sample's last multiply-add with the conversion (one rounding) differs in a few values of
+    these inputs."""
+    c = FC.by_id("warp_s2d_8x8_smooth_n64_half")
+    n, h, w = c.a["nhw"]
+    for kind in FC.KINDS:
+        d = FC.s2d_inputs(c, kind)
+        flow, hp = dev.put(d["lr_flow"]), dev.put(d["hr_prev"])
+        out32, out16 = dev.new((3, n, h, w, 16)), dev.new((3, n, h, w, 16), torch.float16)
+        dev.call(wrapper, flow, hp, out32, 0, n, h, w)
+        dev.call(wrapper, flow, hp, out16, 1, n, h, w)
+        dev.check_arenas(f"{wrapper} [{kind}]")
+        assert torch.equal(bits(out16), bits(out32.to(torch.float16))), f"{wrapper} [{kind}]: the __half planes are not the float planes rounded to fp16"
 
 
 # ------------------------------------------------------------------------------ exact converters

@@ -8,7 +8,7 @@
 * The service vectors (the reference's own ``upscale_single``) within 1 LSB.  The fp32 model shows 0.034 % (no resize) and 0.048 % (area
   resize to 50 x 70) of the bytes at 1 LSB on MI355X; asserted: no more than 0.05 % (the project's general bound for a float within 1e-4 of
   the reference is 0.2 %, tests/helpers.py: assert_u8_close).
-* The skip of ``k_bicubic4_add`` and of its pointer-table build equals ``ss4k_op_bicubic_upsample4`` bit for bit on a zeroed conv_out.
+* The skip of ``op_bicubic4_add`` and of its pointer-table form equals ``ss4k_op_bicubic_upsample4`` bit for bit on a zeroed conv_out.
 """
 import ctypes as C
 import json
@@ -205,11 +205,11 @@ def test_skip_is_the_granular_bicubic_bit_for_bit(ctx, dtype):
     m = _capi.Frvsr(ctx, _capi.make_frvsr_desc(dtype, 64, 1), W.flatten(t, W.tecogan_keys(1)), _capi.FRVSR_TECOGAN)
     g = torch.Generator().manual_seed(9)
     lr = (torch.rand(3, 3, 9, 15, generator=g) * 2 - 0.5).cuda()
-    # the contiguous launch (k_bicubic4_add)
+    # the contiguous launch (op_bicubic4_add)
     got = m(lr, torch.rand(3, 3, 9, 15, generator=g).cuda(), torch.rand(3, 3, 36, 60, generator=g).cuda())
     want = _bicubic4(ctx, lr)
-    assert float(want.abs().max()) > 0.5 and torch.equal(got, want), "k_bicubic4_add on a zeroed conv_out is not ss4k_op_bicubic_upsample4"
-    # the pointer-table launch (k_bicubic4_add_items): a scattered round of three streams, the last item's taps
+    assert float(want.abs().max()) > 0.5 and torch.equal(got, want), "op_bicubic4_add on a zeroed conv_out is not ss4k_op_bicubic_upsample4"
+    # the pointer-table launch (op_bicubic4_add_items): a scattered round of three streams, the last item's taps
     up = _capi.FrvsrUpscaler(ctx, m, (9, 15), None, max_streams=3)
     up.enable_taps(True)
     frames = torch.randint(0, 256, (3, 9, 15, 3), dtype=torch.uint8, generator=g).cuda()
@@ -217,5 +217,5 @@ def test_skip_is_the_granular_bicubic_bit_for_bit(ctx, dtype):
     up.upscale_streams_at([frames[i] for i in range(3)], [2, 0, 1], [outs[i] for i in range(3)])
     lr_tap, hr_tap = up.read_tap(0), up.read_tap(3)
     assert tuple(lr_tap.shape) == (1, 3, 9, 15) and float((lr_tap[0] - frames[2].permute(2, 0, 1).float() / 255.0).abs().max()) < 1e-6   # the round's last item
-    assert torch.equal(hr_tap, _bicubic4(ctx, lr_tap)), "k_bicubic4_add_items on a zeroed conv_out is not ss4k_op_bicubic_upsample4"
+    assert torch.equal(hr_tap, _bicubic4(ctx, lr_tap)), "op_bicubic4_add_items on a zeroed conv_out is not ss4k_op_bicubic_upsample4"
     up.close(); m.close()

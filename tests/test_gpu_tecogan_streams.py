@@ -1,5 +1,5 @@
 """GPU: the recurrent streams of the frame-recurrent upscaler on the TecoGAN generator - LR 16 x 24, one residual block, both dtypes.  The
-tail walks a round in groups of items and writes every item's result into that stream's own state buffer (``k_bicubic4_add_items``); all of
+tail walks a round in groups of items and writes every item's result into that stream's own state buffer (``op_bicubic4_add_items``); all of
 the following hold bit for bit (``torch.equal``), as they do for EGVSR (tests/test_gpu_frvsr_streams.py, tests/test_gpu_frvsr_scattered.py):
 
 * frames ``[a, b]`` then ``[c]`` equal ``[a, b, c]``;

@@ -8,7 +8,8 @@ conv_mfma.hip (``SS4K_FRVSR_CONVT_EMBEDDED``; also what route flags 0 choose tod
   so that the ReLU hides nothing: a flipped or transposed tap, or a phase that reads the wrong neighbour, fails here.
 * Random inputs against ``ref64``: ``up1``, ``up2`` and ``hr_out`` each, slices on the kernels' tile grids, at the shapes of
   ``BC.TAIL_CASES`` - 1 x 1, 2 x 3, two items of 9 x 15, a shape that straddles the phase kernel's tile (TH x TW = 8 x 32 input pixels) in both
-  dimensions at both levels, and the same shape walked by two workgroups (``max_workgroups``).
+  dimensions at both levels, the same shape walked by two workgroups (``max_workgroups``), and 65 items of 2 x 3 in one contiguous batch
+  (two groups of the walk: the skip's launcher sees 64 items, then the 65th at its offset in the batch).
 * Three items with ``group_items`` 1 and 2 equal the default grouping bit for bit.
 
 Bars: tests/test_gpu_error_budget.py's, imported.  fp16: ``emu16`` with the body as packed, the conv weights (conv_out's included: an fp16
@@ -160,7 +161,7 @@ def test_tail_error_budget(tails, case, half, route):
         assert min(tiles) > c.max_workgroups, f"{tiles} tiles on {c.max_workgroups} workgroups: no workgroup walks a second tile"
     for k in ("up1", "up2", "hr"):
         assert_error_budget(got[k], ref[k], yard[k], what=f"{tag} {k}", **bars(half), **BC.TAIL_SLICES)
-    tail.assert_route(fams)
+    tail.assert_route(fams, -(-c.nhw[0] // BC.GROUP_MAX))
 
 
 @pytest.mark.parametrize("route", ["embedded", "phase"])
