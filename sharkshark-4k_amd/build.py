@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libss4k_hip.so")
 LIB_DEV = os.path.join(HERE, "libss4k_hip_dev.so")
-SOURCES = ["conv_mfma.hip", "conv_pair.hip", "conv_dense.hip", "conv_w16.hip", "conv_w16n.hip", "conv_up2.hip", "glue.hip", "fsrcnn.hip", "frvsr.hip", "frvsr_bi.hip", "pack.cpp", "models.cpp", "frvsr.cpp", "frvsr_teco.cpp", "upscaler.cpp", "api.cpp", "api_dev.cpp",
+SOURCES = ["conv_mfma.hip", "conv_pair.hip", "conv_dense.hip", "conv_w16.hip", "conv_w16n.hip", "conv_up2.hip", "glue.hip", "fsrcnn.hip", "fsrcnn_weights.cpp", "frvsr.hip", "frvsr_bi.hip", "pack.cpp", "models.cpp", "frvsr.cpp", "frvsr_teco.cpp", "upscaler.cpp", "api.cpp", "api_dev.cpp",
            "bsvd_online.hip", "bsvd_online.cpp", "upscaler_temporal.cpp", "api_bsvd_online.cpp"]
 # fsrcnn.hip: no SLP vectorisation - left on, the tail's overlap-add (two adjacent output columns per lane) is packed into v_pk_add_f32,
 # which cannot take a DPP operand: 20 of its 35 wave shifts per row then become separate v_mov_b32_dpp, and packed fp32 adds are slower
@@ -94,6 +94,10 @@ def _hostcheck_product_sources() -> list:
     if os.path.exists(listing):
         with open(listing) as f:
             names = [ln.strip() for ln in f if ln.strip() and not ln.startswith("#")]
+    # fsrcnn_weights.cpp is the part of Model::build that packs FSRCNN's blob: host code that calls no launcher, so it needs no auditor and
+    # goes wherever models.cpp goes - a program directory from before the file existed lists models.cpp alone and still links
+    if "models.cpp" in names and "fsrcnn_weights.cpp" not in names:
+        names.insert(names.index("models.cpp") + 1, "fsrcnn_weights.cpp")
     return [os.path.join(CSRC, n) for n in names]
 
 

@@ -9,10 +9,9 @@
 //   map   = conv3x3(12->12)+PReLU                                 (x4)
 //   tail  = conv1x1(12->56)+PReLU -> ConvTranspose 9x9 stride s   (fused, exact-fp32 MFMA: k_fs_tail)
 #include "common.h"
-#include "glue.h"
+#include "fsrcnn.h"
+#include "fsrcnn_bands.h"
 #include "conv_tile.h"
-#include <cstdio>
-#include <vector>
 
 namespace ss4k {
 
@@ -356,20 +355,15 @@ __global__ __launch_bounds__(256, 3) void k_fs_tail_r(const float* __restrict__ 
   // bands of tall_rpb rows, so that the wave count can be what fills the chip's slots: 720p x2, 12 planes, are 46 wave strips - classic
   // 12 workgroup strips (two idle waves each) x 5 bands x 12 planes = 720 workgroups of 768 slots and 148 row steps each, tall 66 bands of
   // 131 rows.  A band that straddles a plane boundary is marched as two segments (4 more halo rows).
-  int ws, plane, ylo, yhi, tall0 = 0, tall1 = 0;
+  int ws, band;
   if (tall_rpb > 0) {
     const int wid = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(wave);
-    ws = wid % wstrips;
-    tall0 = (wid / wstrips) * tall_rpb; tall1 = min(planes * h, tall0 + tall_rpb);
-    plane = tall0 / h; ylo = tall0 - plane * h; yhi = min(h, ylo + (tall1 - tall0));
+    ws = wid % wstrips; band = wid / wstrips;
   } else {
-    const int strip = blockIdx.x % strips, band = (blockIdx.x / strips) % bands;
-    plane = blockIdx.x / (strips * bands);
-    const int rpb = (h + bands - 1) / bands;
-    ylo = band * rpb; yhi = min(h, ylo + rpb);
-    if (plane >= planes || ylo >= yhi) return;
-    ws = strip * 4 + wave;
+    ws = (blockIdx.x % strips) * 4 + wave; band = blockIdx.x / strips;
   }
+  fs_bands::Walk seg = fs_bands::first(band, planes, h, bands, tall_rpb);
+  if (tall_rpb <= 0 && seg.empty()) return;   // (classic: the whole workgroup; tall: a wave leaves after the tables below are built)
 
   // Tap slot r of block tb sits in half hs = (r>>2)&1 of the accumulator; half 0 carries the 45 taps with even ky,
   // half 1 the 36 with odd ky, each in (ky, kx) order (as k_fs_tail).  k = 8*kq + j of k-step s is channel
@@ -411,7 +405,7 @@ __global__ __launch_bounds__(256, 3) void k_fs_tail_r(const float* __restrict__ 
   if (tid < 64) { bea[tid] = tid < 56 ? be[tid] : 0.f; bea[64 + tid] = tid < 56 ? ae[tid] : 0.f; }   // (PReLU constants c, prelu_mx: 0 = identity)
   __syncthreads();
   // ws: this wave's strip of CI interior columns; nothing below synchronises
-  if (ws >= wstrips || (tall_rpb > 0 && tall0 >= tall1)) return;
+  if (ws >= wstrips || seg.empty()) return;
 
   // fp16 mode: PReLU constants of the expand channels this lane's accumulators hold (registers instead of LDS reads)
   float slp[2][SPLIT ? 1 : 16];
@@ -438,7 +432,7 @@ __global__ __launch_bounds__(256, 3) void k_fs_tail_r(const float* __restrict__ 
   const int pxc = min(max(px, 0), w - 1);
   const int g0i = hh ? 2 : 0, g1i = hh ? 2 : 1;   // half 1 reads group 2 twice (the same line) instead of branching
   auto load_x = [&](int yy, float4& a0, float4& a1) {
-    const size_t at = (size_t)plane * plane_px + (size_t)min(max(yy, 0), h - 1) * w + pxc;
+    const size_t at = (size_t)seg.plane * plane_px + (size_t)min(max(yy, 0), h - 1) * w + pxc;
     if constexpr (SPLIT) {
       const float4* src = reinterpret_cast<const float4*>(in12) + at;
       a0 = src[g0i * total]; a1 = src[g1i * total];
@@ -451,7 +445,8 @@ __global__ __launch_bounds__(256, 3) void k_fs_tail_r(const float* __restrict__ 
   typedef float fvS __attribute__((ext_vector_type(S)));
   constexpr float LO = 1.f / 2048.f;
   const f32x16v zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
- for (;;) {   // one segment = rows [ylo, yhi) of `plane` (classic bands: exactly one)
+ do {   // one segment = rows [ylo, yhi) of `plane` (classic bands: exactly one)
+  const int plane = seg.plane, ylo = seg.ylo, yhi = seg.yhi;
   float* oplane = out + (size_t)plane * OH * OW;
   fvS V[5];   // output rows S*y - 4 + 2j + hh under construction, this lane's S columns of each
 #pragma unroll
@@ -600,11 +595,7 @@ __global__ __launch_bounds__(256, 3) void k_fs_tail_r(const float* __restrict__ 
     }
    }
   }
-  if (tall_rpb <= 0) break;
-  tall0 += yhi - ylo;
-  if (tall0 >= tall1) break;
-  plane = tall0 / h; ylo = 0; yhi = min(h, tall1 - tall0);   // the rest of the band: the first rows of the next plane
- }
+ } while (seg.next(h));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -910,21 +901,9 @@ __global__ __launch_bounds__(256, 4) void k_fs_maps4(const float* __restrict__ i
   const int st = __builtin_amdgcn_readfirstlane(tid >> 6);   // this wave's layer
   const int strips = (w + FM_CI - 1) / FM_CI;
   const int strip = blockIdx.x % strips;
-  // bands: classic (tall_rpb == 0) `bands` equal bands per plane; tall: bands of tall_rpb rows of the stacked planes, a band that straddles
-  // a plane boundary marched as two segments (as k_fs_maps4_h below: the grid is then what fills the chip's workgroup slots)
-  int tall0 = 0, tall1 = 0, plane, ylo, yhi;
-  if (tall_rpb > 0) {
-    const int band = blockIdx.x / strips;
-    tall0 = band * tall_rpb; tall1 = min(planes * h, tall0 + tall_rpb);
-    if (tall0 >= tall1) return;
-    plane = tall0 / h; ylo = tall0 - plane * h; yhi = min(h, ylo + (tall1 - tall0));
-  } else {
-    const int band = (blockIdx.x / strips) % bands;
-    plane = blockIdx.x / (strips * bands);
-    const int rpb = (h + bands - 1) / bands;
-    ylo = band * rpb; yhi = min(h, ylo + rpb);
-    if (plane >= planes || ylo >= yhi) return;
-  }
+  // bands (fsrcnn_bands.h; tall ones as k_fs_maps4_h below: the grid is then what fills the chip's workgroup slots)
+  fs_bands::Walk seg = fs_bands::first(blockIdx.x / strips, planes, h, bands, tall_rpb);
+  if (seg.empty()) return;
   const int x0 = strip * FM_CI;
 
   // A operands of this wave's layer: row m = lane & 15 is the output channel; element j of lane quarter q in K-step ks is element j & 3
@@ -973,8 +952,8 @@ __global__ __launch_bounds__(256, 4) void k_fs_maps4(const float* __restrict__ i
   const f32x4v zero4 = {0.f, 0.f, 0.f, 0.f};
   int lo_delta = FM_LOB;
   asm volatile("" : "+s"(lo_delta));
- for (int seg = 0;; ++seg) {   // one segment = rows [ylo, yhi) of `plane` (classic bands: exactly one)
-  if (seg) __syncthreads();   // (every wave is done with the rings)
+ for (;;) {   // one segment = rows [ylo, yhi) of `plane` (classic bands: exactly one)
+  const int plane = seg.plane, ylo = seg.ylo, yhi = seg.yhi;
   for (int e = tid; e < FM_LDS / 16; e += 256) reinterpret_cast<uint4*>(fm_ring)[e] = make_uint4(0u, 0u, 0u, 0u);
   const float4* in4 = reinterpret_cast<const float4*>(in) + (size_t)plane * plane_px;
   float4* out4 = reinterpret_cast<float4*>(out) + (size_t)plane * plane_px;
@@ -1076,10 +1055,8 @@ __global__ __launch_bounds__(256, 4) void k_fs_maps4(const float* __restrict__ i
     }
     lds_barrier();   // LDS-only (conv_tile.h): the fetched row and layer 3's stores stay in flight across it
   }
-  if (tall_rpb <= 0) break;
-  tall0 += yhi - ylo;
-  if (tall0 >= tall1) break;
-  plane = tall0 / h; ylo = 0; yhi = min(h, tall1 - tall0);   // the rest of the band: the first rows of the next plane
+  if (!seg.next(h)) break;
+  __syncthreads();   // (every wave is done with the rings)
  }
 }
 
@@ -1098,52 +1075,26 @@ __global__ __launch_bounds__(256, 4) void k_fs_maps4(const float* __restrict__ i
 //   * layer s keeps input row R in ring slot (R + 2s) & 3, so at step t EVERY layer reads slots (t-1, t, t+1) & 3 and writes
 //     slot (t+2) & 3 of the next ring: with the step loop unrolled by four all LDS offsets are immediates;
 //   * PReLU on packed fp16.
-// NU units of 64 columns per workgroup strip (a wave computes NU x 32 pixel pairs per row: NU independent accumulators, reads and
-// epilogues between two barriers; 8 halo columns per 64 NU instead of per 64)
-constexpr int MH_HALO = 4, MH_RECB = 24, MH_UNITB = 64 * MH_RECB;
-template <int NU> struct MhGeo {
-  static constexpr int COLS = 64 * NU, CI = COLS - 2 * MH_HALO, REC = COLS + 2, ROWB = REC * MH_RECB, STAGEB = 4 * ROWB, LDS = 4 * STAGEB;
-};
+// One unit of 64 columns per workgroup strip.  Two units per strip (half the barriers and halo columns per pixel, three workgroups per CU)
+// were bit-identical and slower on the stage: 8.7 % in round 5 (profiles/earlier/r05/r05_fs_nu_ab.txt), within 1 % with round 6's packed records.
+// The row march still runs over MH_NU = 1 units (`un` loops of one trip, arrays of one element): hipcc unrolls such a loop late, after it has
+// optimised the body as a loop's, and the march written straight compiles to other code that measures 1.5 - 3.5 % slower on the stage
+// (profiles/NOTES_r15.md 3).
+constexpr int MH_NU = 1, MH_HALO = 4, MH_RECB = 24, MH_UNITB = 64 * MH_RECB;
+constexpr int MH_COLS = 64, MH_CI = MH_COLS - 2 * MH_HALO, MH_REC = MH_COLS + 2, MH_ROWB = MH_REC * MH_RECB, MH_STAGEB = 4 * MH_ROWB, MH_LDS = 4 * MH_STAGEB;
 
-template <bool STAMP, int NU>
-__global__ __launch_bounds__(256, NU == 2 ? 3 : 4) void k_fs_maps4_h(const uint2* __restrict__ in, uint2* __restrict__ out, const FsMapW W,
-                                                            int planes, int h, int w, int bands, unsigned long long* dbg, int tall_rpb = 0) {
-  constexpr int MH_COLS = MhGeo<NU>::COLS, MH_CI = MhGeo<NU>::CI, MH_ROWB = MhGeo<NU>::ROWB, MH_STAGEB = MhGeo<NU>::STAGEB, MH_LDS = MhGeo<NU>::LDS;
+__global__ __launch_bounds__(256, 4) void k_fs_maps4_h(const uint2* __restrict__ in, uint2* __restrict__ out, const FsMapW W,
+                                                       int planes, int h, int w, int bands, int tall_rpb) {
   extern __shared__ __attribute__((aligned(16))) char mh_ring[];
-  // dev build, STAMP: cycles of this wave per phase (s_memtime): [0] loader, [1] operand reads + MFMAs, [2] epilogue + stores, [3] barrier
-  unsigned long long ph[4] = {0, 0, 0, 0}, tlast = 0, rt0 = 0, ct0 = 0;
-  if constexpr (STAMP) { rt0 = __builtin_amdgcn_s_memrealtime(); ct0 = __builtin_amdgcn_s_memtime(); }
-  auto stamp = [&](int k) {
-    if constexpr (STAMP) {
-      unsigned long long t;
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-      __builtin_amdgcn_sched_barrier(0);
-      if (k >= 0) ph[k] += t - tlast;
-      tlast = t;
-    }
-  };
   const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, hh = lane >> 5;
   const int st = __builtin_amdgcn_readfirstlane(tid >> 6);   // this wave's layer
   const int strips = (w + MH_CI - 1) / MH_CI;
   const int strip = blockIdx.x % strips;
-  // Bands.  Classic (tall_rpb == 0): `bands` equal bands per plane.  Tall (round 6): the planes stacked into one image of planes * h rows
-  // cut into bands of tall_rpb rows - so that the workgroup count can be what fills the chip's slots (12 planes x 23 strips x 3 bands are
-  // 828 workgroups for 1024 slots; 44 tall bands x 23 are 1012) - and a band that straddles a plane boundary is marched as two segments
-  // (the four-layer pipeline drains and refills at the boundary: 14 more steps for that workgroup).
-  int tall0 = 0, tall1 = 0, plane, ylo, yhi;
-  if (tall_rpb > 0) {
-    const int band = blockIdx.x / strips;
-    tall0 = band * tall_rpb; tall1 = min(planes * h, tall0 + tall_rpb);
-    if (tall0 >= tall1) return;
-    plane = tall0 / h; ylo = tall0 - plane * h; yhi = min(h, ylo + (tall1 - tall0));
-  } else {
-    const int band = (blockIdx.x / strips) % bands;
-    plane = blockIdx.x / (strips * bands);
-    const int rpb = (h + bands - 1) / bands;
-    ylo = band * rpb; yhi = min(h, ylo + rpb);
-    if (plane >= planes || ylo >= yhi) return;
-  }
+  // Bands (fsrcnn_bands.h).  Tall ones let the workgroup count be what fills the chip's slots (12 planes x 23 strips x 3 bands are 828
+  // workgroups for 1024 slots; 44 tall bands x 23 are 1012); at a plane boundary inside a band the four-layer pipeline drains and refills:
+  // 14 more steps for that workgroup.
+  fs_bands::Walk seg = fs_bands::first(blockIdx.x / strips, planes, h, bands, tall_rpb);
+  if (seg.empty()) return;
   const int x0 = strip * MH_CI;
 
   // weights of this wave's layer: row m = (co & 3) + 8 * (co >> 2) + 4 * g (the accumulator register order, so lane half g holds
@@ -1180,12 +1131,11 @@ __global__ __launch_bounds__(256, NU == 2 ? 3 : 4) void k_fs_maps4_h(const uint2
   const bool edge = x0 - MH_HALO < 0 || x0 - MH_HALO + MH_COLS > w;   // wave-uniform: this strip has columns outside the image
 
   const size_t plane_px = (size_t)h * w, total = (size_t)planes * plane_px;
-  const uint2* src = in + (size_t)plane * plane_px;
-  uint2* dst = out + (size_t)plane * plane_px;
-  unsigned long long pre = 0;
-  int steps_done = 0;
- for (int seg = 0;; ++seg) {   // one segment = rows [ylo, yhi) of `plane` (classic bands: exactly one)
-  if (seg) { src = in + (size_t)plane * plane_px; dst = out + (size_t)plane * plane_px; __syncthreads(); }   // (every wave is done with the rings)
+  const uint2* src = in + (size_t)seg.plane * plane_px;
+  uint2* dst = out + (size_t)seg.plane * plane_px;
+ for (int sg = 0;; ++sg) {   // one segment = rows [ylo, yhi) of `plane` (classic bands: exactly one)
+  const int ylo = seg.ylo, yhi = seg.yhi;
+  if (sg) { src = in + (size_t)seg.plane * plane_px; dst = out + (size_t)seg.plane * plane_px; __syncthreads(); }   // (every wave is done with the rings)
   for (int e = tid; e < MH_LDS / 16; e += 256) reinterpret_cast<uint4*>(mh_ring)[e] = make_uint4(0u, 0u, 0u, 0u);
   // input loader: thread tid < 192 moves channel group lg = tid / 64 (8 bytes) of ring column lc = tid % 64 (layer 3's wave has none)
   const int lg = tid >> 6, lc = tid & 63, lx = x0 - MH_HALO + lc;
@@ -1206,64 +1156,59 @@ __global__ __launch_bounds__(256, NU == 2 ? 3 : 4) void k_fs_maps4_h(const uint2
   };
   __syncthreads();   // rings are zero
 #pragma unroll
-  for (int un = 0; un < NU; ++un) { store_row(0, un, load_row(0, un)); store_row(1, un, load_row(1, un)); }
+  for (int un = 0; un < MH_NU; ++un) { store_row(0, un, load_row(0, un)); store_row(1, un, load_row(1, un)); }
   // four input rows in flight: a step is shorter than a trip to HBM, so row t + 2 was requested four steps before it is stored
-  uint2 nxt[NU][4];
+  uint2 nxt[MH_NU][4];
 #pragma unroll
-  for (int un = 0; un < NU; ++un)
+  for (int un = 0; un < MH_NU; ++un)
 #pragma unroll
     for (int i = 0; i < 4; ++i) nxt[un][(i + 2) & 3] = load_row(i + 2, un);
   __syncthreads();
   const f32x16v zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const int nsteps = (yhi - ylo) + 4 + 6;   // layer 3 reaches relative row (yhi - ylo) + 3 at step that + 6
   const int rlast = (yhi - ylo) + 3 + (3 - st);
-  if constexpr (STAMP) { if (!seg) pre = __builtin_amdgcn_s_memtime() - ct0; }
-  steps_done += nsteps;
   for (int t0 = 0; t0 < nsteps; t0 += 4) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int t = t0 + u;
       if (t >= nsteps) break;   // uniform over the workgroup
       // input row t + 2 goes into layer 0's ring (slot (t + 2) & 3) while rows t - 1 .. t + 1 are being read; row t + 6 is requested
-      stamp(-1);
 #pragma unroll
-      for (int un = 0; un < NU; ++un) {
+      for (int un = 0; un < MH_NU; ++un) {
         store_row(t + 2, un, nxt[un][(u + 2) & 3]);
         nxt[un][(u + 2) & 3] = load_row(t + 6, un);
       }
-      stamp(0);
       const int r = t - 2 * st;   // this layer's output row (wave-uniform)
       if (r >= 0 && r <= rlast) {
         const int y = ylo - 4 + r;
         const bool row_in = y >= 0 && y < h;
-        uint32_t E[NU][6];
+        uint32_t E[MH_NU][6];
 #pragma unroll
-        for (int un = 0; un < NU; ++un)
+        for (int un = 0; un < MH_NU; ++un)
 #pragma unroll
           for (int j = 0; j < 6; ++j) E[un][j] = 0u;
         if (row_in) {   // wave-uniform
-          f32x16v acc[NU];
+          f32x16v acc[MH_NU];
           // the three pixel operands of a kernel row (of every unit) are read together, then its MFMAs issue; the next row's reads overlap
           // them (left to itself hipcc re-uses one register quad: read, wait, MFMA, nine times over)
 #pragma unroll
           for (int dy = 0; dy < 3; ++dy) {
-            uint4 b[NU][3];
+            uint4 b[MH_NU][3];
 #pragma unroll
-            for (int un = 0; un < NU; ++un)
+            for (int un = 0; un < MH_NU; ++un)
 #pragma unroll
               for (int s = 0; s < 3; ++s) b[un][s] = *reinterpret_cast<const uint4*>(mh_ring + rd + 32 * s + un * MH_UNITB + ((u + 3 + dy) & 3) * MH_ROWB);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int s = 0; s < 3; ++s)
 #pragma unroll
-              for (int un = 0; un < NU; ++un)
+              for (int un = 0; un < MH_NU; ++un)
                 acc[un] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8v, A[dy][s]), __builtin_bit_cast(f16x8v, b[un][s]),
                                                                  (dy == 0 && s == 0) ? bias16 : acc[un], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
           }
-          stamp(1);
 #pragma unroll
-          for (int un = 0; un < NU; ++un) {
+          for (int un = 0; un < MH_NU; ++un) {
 #pragma unroll
             for (int j = 0; j < 6; ++j) E[un][j] = prelu_h2(acc[un][2 * j], acc[un][2 * j + 1], slp[2 * j], slp[2 * j + 1]);
             const int Xu = X + 64 * un;
@@ -1274,7 +1219,7 @@ __global__ __launch_bounds__(256, NU == 2 ? 3 : 4) void k_fs_maps4_h(const uint2
           }
         }
 #pragma unroll
-        for (int un = 0; un < NU; ++un) {
+        for (int un = 0; un < MH_NU; ++un) {
           const int ocu = oc + 64 * un, Xu = X + 64 * un;
           if (st < 3) {
 #pragma unroll
@@ -1286,199 +1231,129 @@ __global__ __launch_bounds__(256, NU == 2 ? 3 : 4) void k_fs_maps4_h(const uint2
           }
         }
       }
-      stamp(2);
       lds_barrier();   // not __syncthreads(): the prefetched rows stay in flight across it (conv_tile.h)
-      stamp(3);
     }
   }
-  if (tall_rpb <= 0) break;
-  tall0 += yhi - ylo;
-  if (tall0 >= tall1) break;
-  plane = tall0 / h; ylo = 0; yhi = min(h, tall1 - tall0);   // the rest of the band: the first rows of the next plane
+  if (!seg.next(h)) break;
  }
-  if constexpr (STAMP) {
-    if (lane == 0 && dbg && blockIdx.x < 1024) {
-      unsigned long long* o = dbg + ((size_t)blockIdx.x * 4 + st) * 8;
-      for (int k = 0; k < 4; ++k) o[k] = ph[k];
-      o[5] = (unsigned long long)steps_done; o[4] = pre; o[6] = __builtin_amdgcn_s_memtime() - ct0;
-      o[7] = ((__builtin_amdgcn_s_memtime() - ct0) << 20) / (__builtin_amdgcn_s_memrealtime() - rt0 + 1);
-    }
-  }
 }
+
+// ---------------------------------------------------------------------------------------------
+// The three stage launchers.  exact: the exact-fp32 kernels (A/B switch and the reference of the split-precision test); half: fp16 mode;
+// neither: the default fp32-grade mode.
+namespace {
+
+// SS4K_MH_NO_TALL / SS4K_TAIL_NO_TALL: the classic whole-bands-per-plane grids of the mapping kernels / the tails (fsrcnn_bands.h) - the
+// reference that tests/drive_fs_bands.py compares the tall bands against.  Read once per process.
+struct ClassicBands { bool maps, tail; };
+const ClassicBands& classic_bands() {
+  static const ClassicBands c{std::getenv("SS4K_MH_NO_TALL") != nullptr, std::getenv("SS4K_TAIL_NO_TALL") != nullptr};
+  return c;
+}
+
+const dim3 FS_BLOCK(256);
+
+// (an fp16-split MFMA head of the exact mode - 16x16x32, the first product's accumulators feeding the 1x1 shrink - was built and measured:
+// 0.56 ms against k_fs_head's 0.62 per 12 planes of 720p; PReLU + re-splitting the 56-channel map costs ~7 vector instructions per value,
+// as many as the whole exact vector-ALU chain: not kept)
+void fs_head(ss4k_ctx* ctx, const FsrcnnWeights& W, const float* in, float* out12, int planes, int h, int w, bool exact, bool half, bool in_u8,
+             hipStream_t st) {
+  if (exact) {
+    const size_t total = (size_t)planes * h * w;
+    hipLaunchKernelGGL(k_fs_head, dim3((unsigned)((total + 255) / 256)), FS_BLOCK, 0, st, in, out12, W.w_feat, W.b_feat, W.a_feat, W.w_shrink,
+                       W.b_shrink, W.a_shrink, planes, h, w);
+    return;
+  }
+  const int strips = (w + FH_COLS - 1) / FH_COLS;
+  // two waves per SIMD over the chip, bands of at least 8 rows (every band re-reads 4 halo rows)
+  const int b0 = std::max(1, std::min((h + 7) / 8, 4 * 2 * ctx->num_cu / std::max(1, planes * strips)));
+  const int rpb = (h + b0 - 1) / b0, bands = (h + rpb - 1) / rpb;
+  const unsigned waves = (unsigned)(planes * bands * strips);
+  auto kern = half ? (in_u8 ? &k_fs_head_m<false, true> : &k_fs_head_m<false, false>) : (in_u8 ? &k_fs_head_m<true, true> : &k_fs_head_m<true, false>);
+  hipLaunchKernelGGL(kern, dim3((waves + 3) / 4), FS_BLOCK, 0, st, in, static_cast<void*>(out12), W.w_feat, W.b_feat, W.a_feat, W.w_shrink,
+                     W.b_shrink, W.a_shrink, planes, h, w, bands);
+}
+
+// the four mapping layers from `cur` (`nxt`: the other stage buffer); returns the buffer that holds the result
+float* fs_maps(ss4k_ctx* ctx, const FsrcnnWeights& W, float* cur, float* nxt, int planes, int h, int w, bool exact, bool half, hipStream_t st) {
+  if (exact) {
+    constexpr int R = 4;
+    const dim3 grid((unsigned)(((size_t)planes * ((h + R - 1) / R) * w + 255) / 256));
+    for (int l = 0; l < 4; ++l) {
+      hipLaunchKernelGGL(k_fs_map<R>, grid, FS_BLOCK, 0, st, cur, nxt, W.w_map[l], W.b_map[l], W.a_map[l], planes, h, w);
+      std::swap(cur, nxt);
+    }
+    return cur;
+  }
+  FsMapW mw;
+  for (int l = 0; l < 4; ++l) { mw.w[l] = W.w_map[l]; mw.b[l] = W.b_map[l]; mw.a[l] = W.a_map[l]; }
+  // at most one round of workgroups at four per CU (a second, partly filled round costs a whole march); every band re-does 8 halo rows plus
+  // 6 steps of pipeline fill
+  const int strips = (w + (half ? MH_CI : FM_CI) - 1) / (half ? MH_CI : FM_CI), lds = half ? MH_LDS : FM_LDS;
+  const fs_bands::Plan bp = fs_bands::plan(planes, h, strips, fs_bands::MAPS_MIN_ROWS, fs_bands::MAPS_SLOTS_PER_CU * ctx->num_cu, classic_bands().maps);
+  const dim3 grid((unsigned)(bp.band_count(planes) * strips));
+  const void* fn = half ? reinterpret_cast<const void*>(&k_fs_maps4_h) : reinterpret_cast<const void*>(&k_fs_maps4);
+  if (ctx->lds_attr_set.insert(fn).second) SS4K_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  if (half)
+    hipLaunchKernelGGL(k_fs_maps4_h, grid, FS_BLOCK, lds, st, reinterpret_cast<const uint2*>(cur), reinterpret_cast<uint2*>(nxt), mw, planes, h, w,
+                       bp.bands, bp.tall_rpb);
+  else
+    hipLaunchKernelGGL(k_fs_maps4, grid, FS_BLOCK, lds, st, cur, nxt, mw, planes, h, w, bp.bands, bp.tall_rpb);
+  return nxt;
+}
+
+// the matrix-core tail's builds of one factor: fp32-grade, fp16, fp16 with an fp16 HR tensor
+using FsTailR = decltype(&k_fs_tail_r<2, true, false>);
+template <int S> FsTailR fs_tail_r_build(bool half, bool out_half) {
+  return !half ? &k_fs_tail_r<S, true, false> : out_half ? &k_fs_tail_r<S, false, true> : &k_fs_tail_r<S, false, false>;
+}
+
+void fs_tail(ss4k_ctx* ctx, const FsrcnnWeights& W, int factor, const float* in12, float* out, int planes, int h, int w, bool exact, bool half,
+             bool out_half, hipStream_t st) {
+  const int wg_slots = fs_bands::TAIL_SLOTS_PER_CU / 4 * ctx->num_cu;   // workgroups of four waves
+  if (exact) {   // one round of workgroups, classic bands; every band re-does 4 halo rows
+    const int strips = (w + FS_CI - 1) / FS_CI;
+    const int bands = fs_bands::plan(planes, h, strips, fs_bands::TAIL_MIN_ROWS, wg_slots, true).bands;
+    const size_t lds = (size_t)(6144 + 768 + 128 + 16 * (factor * 128 + 8)) * 4;
+    auto kern = factor == 2 ? &k_fs_tail<2> : &k_fs_tail<4>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(planes * bands * strips)), FS_BLOCK, lds, st, in12, out, W.w_expand, W.b_expand, W.a_expand,
+                       W.w_deconv, W.b_deconv, planes, h, w, bands);
+    return;
+  }
+  // The matrix-core tails.  Tall bands: the unit is the wave (see the kernel), twelve per CU (fp16 mode: 4, 5 or 6 workgroups per CU measured,
+  // no gain).  Classic bands: the unit is the workgroup of four neighbouring wave strips, three per CU.
+  const int ci = factor == 2 ? FsTailGeo<2>::CI : FsTailGeo<4>::CI, wstrips = (w + ci - 1) / ci, strips = (wstrips + 3) / 4;
+  const bool classic = classic_bands().tail;
+  const fs_bands::Plan bp = classic ? fs_bands::plan(planes, h, strips, fs_bands::TAIL_MIN_ROWS, wg_slots, true)
+                                    : fs_bands::plan(planes, h, wstrips, fs_bands::TAIL_MIN_ROWS, fs_bands::TAIL_SLOTS_PER_CU * ctx->num_cu, false);
+  const long workgroups = classic ? (long)bp.band_count(planes) * strips : ((long)bp.band_count(planes) * wstrips + 3) / 4;
+  const size_t lds = (size_t)(2 * 768 + 2 * 128) * 16 + 128 * 4;
+  const FsTailR kern = factor == 2 ? fs_tail_r_build<2>(half, out_half) : fs_tail_r_build<4>(half, out_half);
+  hipLaunchKernelGGL(kern, dim3((unsigned)workgroups), FS_BLOCK, lds, st, in12, out, W.w_expand, W.b_expand, W.a_expand, W.w_deconv, W.b_deconv,
+                     planes, h, w, bp.bands, bp.tall_rpb);
+}
+
+}  // namespace
 
 void fsrcnn_forward(ss4k_ctx* ctx, const FsrcnnWeights& W, int factor, const float* in, float* out, int planes, int h,
                     int w, float* ws12a, float* ws12b, int mode, hipStream_t st, bool out_half, bool in_u8) {
   const bool exact = mode == FS_MODE_EXACT, half = mode == FS_MODE_HALF;
+  SS4K_REQUIRE(factor == 2 || factor == 4, "FSRCNN: scale must be 2 or 4");
   SS4K_REQUIRE(!out_half || half, "FSRCNN: an fp16 output tensor is offered in fp16 mode only");
-  SS4K_REQUIRE(exact || W.prelu_abs, "FSRCNN matrix-core modes: the weight blob is not scaled for the one-fma PReLU (models.cpp)");
+  SS4K_REQUIRE(exact || W.prelu_abs, "FSRCNN matrix-core modes: the weight blob is not scaled for the one-fma PReLU (fsrcnn_weights.cpp)");
   SS4K_REQUIRE(!in_u8 || (!exact && planes % 3 == 0), "FSRCNN: uint8 NHWC input is read by the matrix-core head only, three colour planes per frame");
-  const size_t total = (size_t)planes * h * w;
-  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  // exact (SS4K_FS_EXACT=1 when the model was built): the exact-fp32 kernels - vector-ALU mapping layers, fp32-MFMA tail with
-  // the LDS ring - A/B switch and the reference of the split-precision test
-  // (an fp16-split MFMA head - 16x16x32, the first product's accumulators feeding the 1x1 shrink - was built and measured:
-  // 0.56 ms against this kernel's 0.62 per 12 planes of 720p; PReLU + re-splitting the 56-channel map costs ~7 vector
-  // instructions per value, as many as the whole exact vector-ALU chain: not kept)
   // per-stage timing for bench.py's stage rooflines (ss4k_prof_read_kind); algorithmic FLOPs per LR pixel and plane:
   // head 2 * (25 * 56 + 56 * 12), mapping 2 * 4 * 9 * 12 * 12, tail 2 * (12 * 56 + 81 * 56)  (12 464 MAC in all)
+  const double total = (double)((size_t)planes * h * w);
   ProfScope prof_head(ctx, st, PROF_FS_HEAD);
-  // fp16 mode and the default fp32-grade mode run the head on the matrix cores (k_fs_head_m: one | three MFMAs per product); the exact
-  // mode keeps the vector-ALU kernel
-  if (!exact) {
-    const int hstrips = (w + FH_COLS - 1) / FH_COLS;
-    // two waves (fp32-grade: one) per SIMD over the chip, bands of at least 8 rows (every band re-reads 4 halo rows)
-    const int per_simd = 2;
-    const int hb0 = std::max(1, std::min((h + 7) / 8, 4 * per_simd * ctx->num_cu / std::max(1, planes * hstrips)));
-    const int hbands = (h + (h + hb0 - 1) / hb0 - 1) / ((h + hb0 - 1) / hb0);
-    const unsigned hwaves = (unsigned)(planes * hbands * hstrips);
-    if (half) {
-      SS4K_REQUIRE(W.prelu_abs, "FSRCNN fp16 mode: the weight blob is not scaled for the one-fma PReLU (models.cpp)");
-      auto hk = in_u8 ? &k_fs_head_m<false, true> : &k_fs_head_m<false, false>;
-      hipLaunchKernelGGL(hk, dim3((hwaves + 3) / 4), block, 0, st, in, static_cast<void*>(ws12a), W.w_feat, W.b_feat,
-                         W.a_feat, W.w_shrink, W.b_shrink, W.a_shrink, planes, h, w, hbands);
-    }
-    else {
-      auto hk = in_u8 ? &k_fs_head_m<true, true> : &k_fs_head_m<true, false>;
-      hipLaunchKernelGGL(hk, dim3((hwaves + 3) / 4), block, 0, st, in, static_cast<void*>(ws12a), W.w_feat, W.b_feat,
-                         W.a_feat, W.w_shrink, W.b_shrink, W.a_shrink, planes, h, w, hbands);
-    }
-  } else
-  hipLaunchKernelGGL(k_fs_head, grid, block, 0, st, in, ws12a, W.w_feat, W.b_feat, W.a_feat, W.w_shrink, W.b_shrink,
-                     W.a_shrink, planes, h, w);
-  prof_head.done(4144.0 * (double)total);
+  fs_head(ctx, W, in, ws12a, planes, h, w, exact, half, in_u8, st);
+  prof_head.done(4144.0 * total);
   ProfScope prof_map(ctx, st, PROF_FS_MAP);
-  constexpr int FS_MAP_R = 4;
-  const dim3 mgrid((unsigned)(((size_t)planes * ((h + FS_MAP_R - 1) / FS_MAP_R) * w + 255) / 256));
-  float* cur = ws12a; float* nxt = ws12b;
-  if (exact) {
-    for (int l = 0; l < 4; ++l) {
-      hipLaunchKernelGGL(k_fs_map<FS_MAP_R>, mgrid, block, 0, st, cur, nxt, W.w_map[l], W.b_map[l], W.a_map[l], planes, h, w);
-      std::swap(cur, nxt);
-    }
-  } else {
-    FsMapW mw;
-    for (int l = 0; l < 4; ++l) { mw.w[l] = W.w_map[l]; mw.b[l] = W.b_map[l]; mw.a[l] = W.a_map[l]; }
-    const int mstrips = (w + FM_CI - 1) / FM_CI;
-    // at most one round of workgroups at four per CU (a second, partly filled round costs a whole march); every band
-    // re-does 8 halo rows plus 6 steps of pipeline fill
-    const int mbands = std::max(1, std::min((h + 31) / 32, 4 * ctx->num_cu / std::max(1, planes * mstrips)));
-    if (half) {
-      // strips of 64 NU columns (56 / 120 interior).  NU = 2 (round 5, VERDICT r4 item 8: two independent units of work per wave between
-      // barriers, half the barriers and halo columns per pixel - at two workgroups per CU instead of four, 66.5 KB of rings each) is
-      // bit-identical and 8.7 % SLOWER on the stage (0.375 against 0.345 ms per 12 planes of 720p, profiles/earlier/r05/r05_fs_nu_ab.txt): four
-      // resident workgroups per CU interleave better than one wave does with itself.  Kept as a dev-library switch (SS4K_MH_NU=2).
-      // Round 6, packed records (rings of 50 KB, three workgroups per CU, tall bands): 0.235 against 0.238 ms - within a percent; still the switch.
-      int mh_nu = 1;
-#ifdef SS4K_DEV
-      if (const char* e = std::getenv("SS4K_MH_NU")) mh_nu = std::atoi(e);
-#endif
-      const int NUr = (mh_nu != 2 || w <= MhGeo<1>::CI) ? 1 : 2;
-      const int MH_CI = NUr == 2 ? MhGeo<2>::CI : MhGeo<1>::CI, MH_LDS = NUr == 2 ? MhGeo<2>::LDS : MhGeo<1>::LDS;
-      const int hs = (w + MH_CI - 1) / MH_CI;
-      const int per_cu = NUr == 2 ? 3 : 4;   // resident workgroups per CU (rings of 25 | 50 KB)
-      int hb = std::max(1, std::min((h + 31) / 32, per_cu * ctx->num_cu / std::max(1, planes * hs)));   // one round
-#ifdef SS4K_DEV
-      if (const char* e = std::getenv("SS4K_MH_BANDS")) hb = std::max(1, std::atoi(e));
-#endif
-#ifdef SS4K_DEV
-      static const bool stamp_mode = std::getenv("SS4K_FS_STAMP") && std::getenv("SS4K_FS_STAMP")[0] == '1';
-      if (stamp_mode) {   // phase cycle counters of every wave of the first 1024 workgroups, printed per layer
-        static unsigned long long* dbuf = nullptr;
-        if (!dbuf) SS4K_HIP(hipMalloc(reinterpret_cast<void**>(&dbuf), 1024 * 4 * 8 * 8));
-        SS4K_HIP(hipMemsetAsync(dbuf, 0, 1024 * 4 * 8 * 8, st));
-        auto kst = NUr == 2 ? &k_fs_maps4_h<true, 2> : &k_fs_maps4_h<true, 1>;
-        const void* fs = reinterpret_cast<const void*>(kst);
-        if (ctx->lds_attr_set.insert(fs).second) SS4K_HIP(hipFuncSetAttribute(fs, hipFuncAttributeMaxDynamicSharedMemorySize, MH_LDS));
-        hipLaunchKernelGGL(kst, dim3((unsigned)(planes * hb * hs)), block, MH_LDS, st, reinterpret_cast<const uint2*>(cur),
-                           reinterpret_cast<uint2*>(nxt), mw, planes, h, w, hb, dbuf, 0);
-        SS4K_HIP(hipStreamSynchronize(st));
-        std::vector<unsigned long long> hbuf(1024 * 4 * 8);
-        SS4K_HIP(hipMemcpy(hbuf.data(), dbuf, hbuf.size() * 8, hipMemcpyDeviceToHost));
-        for (int l = 0; l < 4; ++l) {
-          double acc[4] = {0, 0, 0, 0}, steps = 0, clk = 0, pre = 0, tot = 0; int nw = 0;
-          for (int wg = 0; wg < 1024; ++wg) {
-            const unsigned long long* o = &hbuf[((size_t)wg * 4 + l) * 8];
-            if (!o[5]) continue;
-            for (int k = 0; k < 4; ++k) acc[k] += (double)o[k];
-            steps += (double)o[5]; clk += (double)o[7] / 1048576.0 * 100.0; pre += (double)o[4]; tot += (double)o[6]; ++nw;
-          }
-          if (nw) std::fprintf(stderr, "[k_fs_maps4_h layer %d] %.0f MHz; wave life %.0f cycles of which before the row loop %.0f; per row: loader %.0f  reads+mfma %.0f  epilogue+stores %.0f  barrier %.0f\n",
-                               l, clk / nw, tot / nw, pre / nw, acc[0] / steps, acc[1] / steps, acc[2] / steps, acc[3] / steps);
-        }
-      } else
-#endif
-      {
-        auto kfn = NUr == 2 ? &k_fs_maps4_h<false, 2> : &k_fs_maps4_h<false, 1>;
-        const void* fn = reinterpret_cast<const void*>(kfn);
-        if (ctx->lds_attr_set.insert(fn).second) SS4K_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, MH_LDS));
-        // tall bands: as many bands over the stacked planes as fill the chip's workgroup slots once (bands of at least 32 rows)
-        int tall_rpb = 0;
-        unsigned nwg = (unsigned)(planes * hb * hs);
-        static const bool tall_off = std::getenv("SS4K_MH_NO_TALL") != nullptr;
-        if (!tall_off) {
-          const long rows = (long)planes * h;
-          const int slots = per_cu * ctx->num_cu;
-          const int nb = (int)std::max(1L, std::min(rows / 32, (long)(slots / std::max(1, hs))));
-          tall_rpb = (int)((rows + nb - 1) / nb);
-          nwg = (unsigned)(((rows + tall_rpb - 1) / tall_rpb) * hs);
-        }
-        hipLaunchKernelGGL(kfn, dim3(nwg), block, MH_LDS, st, reinterpret_cast<const uint2*>(cur),
-                           reinterpret_cast<uint2*>(nxt), mw, planes, h, w, hb, nullptr, tall_rpb);
-      }
-    } else {
-      const void* fn = reinterpret_cast<const void*>(&k_fs_maps4);
-      if (ctx->lds_attr_set.insert(fn).second) SS4K_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, FM_LDS));
-      // tall bands: as many bands over the stacked planes as fill the chip's workgroup slots once (bands of at least 32 rows)
-      static const bool tall_off = std::getenv("SS4K_MH_NO_TALL") != nullptr;
-      int tall_rpb = 0;
-      unsigned nwg = (unsigned)(planes * mbands * mstrips);
-      if (!tall_off) {
-        const long rows = (long)planes * h;
-        const int nb = (int)std::max(1L, std::min(rows / 32, (long)(4 * ctx->num_cu / std::max(1, mstrips))));
-        tall_rpb = (int)((rows + nb - 1) / nb);
-        nwg = (unsigned)(((rows + tall_rpb - 1) / tall_rpb) * mstrips);
-      }
-      hipLaunchKernelGGL(k_fs_maps4, dim3(nwg), block, FM_LDS, st, cur, nxt, mw, planes, h, w, mbands, tall_rpb);
-    }
-    std::swap(cur, nxt);
-  }
-  prof_map.done(10368.0 * (double)total);
-  SS4K_REQUIRE(factor == 2 || factor == 4, "FSRCNN: scale must be 2 or 4");
+  const float* mapped = fs_maps(ctx, W, ws12a, ws12b, planes, h, w, exact, half, st);
+  prof_map.done(10368.0 * total);
   ProfScope prof_tail(ctx, st, PROF_FS_TAIL);
-  const int ci = exact ? FS_CI : 4 * (factor == 2 ? FsTailGeo<2>::CI : FsTailGeo<4>::CI);   // interior LR columns per workgroup
-  const int strips = (w + ci - 1) / ci;
-  // one round of workgroups at three per CU; every band re-does 4 halo rows (fp16 mode: 4, 5 or 6 per CU measured, no gain)
-  const int bands = std::max(1, std::min((h + 15) / 16, 3 * ctx->num_cu / std::max(1, planes * strips)));
-  const dim3 tgrid((unsigned)(planes * bands * strips));
-  auto launch_tail = [&](auto kern, int S) {   // the exact-fp32 tail
-    const size_t lds = (size_t)(6144 + 768 + 128 + 16 * (S * 128 + 8)) * 4;
-    hipLaunchKernelGGL(kern, tgrid, block, lds, st, cur, out, W.w_expand, W.b_expand, W.a_expand, W.w_deconv, W.b_deconv,
-                       planes, h, w, bands);
-  };
-  auto launch_tail_r = [&](auto kern, int S) {   // the matrix-core tails: tall bands of independent waves (see the kernel)
-    const size_t lds = (size_t)(2 * 768 + 2 * 128) * 16 + 128 * 4;
-    static const bool tall_off = std::getenv("SS4K_TAIL_NO_TALL") != nullptr;
-    int tall_rpb = 0;
-    dim3 grid = tgrid;
-    if (!tall_off) {
-      const int wstrips = (w + ci / 4 - 1) / (ci / 4);
-      const long rows = (long)planes * h;
-      const int nb = (int)std::max(1L, std::min(rows / 16, (long)(4 * 3 * ctx->num_cu / wstrips)));
-      tall_rpb = (int)((rows + nb - 1) / nb);
-      const long waves = ((rows + tall_rpb - 1) / tall_rpb) * wstrips;
-      grid = dim3((unsigned)((waves + 3) / 4));
-    }
-    hipLaunchKernelGGL(kern, grid, block, lds, st, cur, out, W.w_expand, W.b_expand, W.a_expand, W.w_deconv, W.b_deconv,
-                       planes, h, w, bands, tall_rpb);
-  };
-  if (factor == 2) {
-    if (exact) launch_tail(k_fs_tail<2>, 2); else if (half && out_half) launch_tail_r(k_fs_tail_r<2, false, true>, 2);
-    else if (half) launch_tail_r(k_fs_tail_r<2, false>, 2); else launch_tail_r(k_fs_tail_r<2, true>, 2);
-  } else {
-    if (exact) launch_tail(k_fs_tail<4>, 4); else if (half && out_half) launch_tail_r(k_fs_tail_r<4, false, true>, 4);
-    else if (half) launch_tail_r(k_fs_tail_r<4, false>, 4); else launch_tail_r(k_fs_tail_r<4, true>, 4);
-  }
-  prof_tail.done(10416.0 * (double)total);
+  fs_tail(ctx, W, factor, mapped, out, planes, h, w, exact, half, out_half, st);
+  prof_tail.done(10416.0 * total);
   SS4K_HIP(hipGetLastError());
 }
 

@@ -217,77 +217,7 @@ void Model::build(const float* w, size_t n) {
   SS4K_REQUIRE(n == model_param_count(desc), "weight blob size does not match the model description");
   ParamCursor pc{w, n};
   if (desc.kind == SS4K_FSRCNN) {
-    // The fp16 hi/lo split (fsrcnn.hip split2) needs every operand inside the fp16 range: |x| < 65504 (below 2^-14 the hi part
-    // is an fp16 subnormal and the lo part makes up the difference, absolute error < 2^-24 |w|).  The values the matrix-core
-    // kernels receive are checked below, after the PReLU scaling (which multiplies a producing weight or bias by up to (1 + s) / 2:
-    // x 5.05 on the T91 x4 checkpoint's s = 9.1) - a checkpoint that does not fit runs the exact-fp32 kernels; activations of an
-    // image-range network are orders of magnitude inside (T91: < 120 for inputs in [0,1],
-    // tests/test_oracle_golden.py::test_fsrcnn_t91_activation_range), and SS4K_MODEL_FS_EXACT is the caller's switch for a network
-    // that is not.
-    // device blob layout: see FsrcnnWeights (glue.h)
-    std::vector<float> blob;
-    auto push = [&](const std::vector<float>& v) { size_t o = blob.size(); blob.insert(blob.end(), v.begin(), v.end()); while (blob.size() % 4) blob.push_back(0.f); return o; };
-    auto conv_tcico = [&](const float* W, int co, int ci, int k2) {  // OIHW -> [tap][ci][co]
-      std::vector<float> o((size_t)k2 * ci * co);
-      for (int a = 0; a < co; ++a) for (int b = 0; b < ci; ++b) for (int t = 0; t < k2; ++t)
-        o[((size_t)t * ci + b) * co + a] = W[((size_t)a * ci + b) * k2 + t];
-      return o;
-    };
-    auto vec = [&](const float* p, int k) { return std::vector<float>(p, p + k); };
-    size_t off[32]; int k = 0;
-    const float* p;
-    p = pc.take(56 * 25); off[k++] = push(conv_tcico(p, 56, 1, 25));
-    off[k++] = push(vec(pc.take(56), 56)); off[k++] = push(vec(pc.take(56), 56));
-    p = pc.take(12 * 56); off[k++] = push(conv_tcico(p, 12, 56, 1));
-    off[k++] = push(vec(pc.take(12), 12)); off[k++] = push(vec(pc.take(12), 12));
-    for (int l = 0; l < 4; ++l) {
-      p = pc.take(12 * 12 * 9); off[k++] = push(conv_tcico(p, 12, 12, 9));
-      off[k++] = push(vec(pc.take(12), 12)); off[k++] = push(vec(pc.take(12), 12));
-    }
-    p = pc.take(56 * 12); off[k++] = push(conv_tcico(p, 56, 12, 1));
-    off[k++] = push(vec(pc.take(56), 56)); off[k++] = push(vec(pc.take(56), 56));
-    p = pc.take(56 * 81);  // ConvTranspose weight (C_in=56, C_out=1, 9, 9) -> [tap][cin]
-    std::vector<float> wd(81 * 56);
-    for (int c = 0; c < 56; ++c) for (int t = 0; t < 81; ++t) wd[(size_t)t * 56 + c] = p[(size_t)c * 81 + t];
-    off[k++] = push(wd);
-    fsw.b_deconv = *pc.take(1);
-    // Matrix-core modes: PReLU(x) = a x + b |x| with a = (1 + s) / 2, b = (1 - s) / 2.  The weights and the bias that PRODUCE a channel are
-    // scaled by its a here, so the kernels' accumulators hold y = a x, and PReLU(x) = y + c |y| with c = b / a = (1 - s) / (1 + s) - one fma
-    // with a free |.| modifier per value (fsrcnn.hip prelu_mx; rounds 3-6: multiply + max on values carried negated where s > 1).  The
-    // slope arrays of the blob hold c.  Needs a > 0, i.e. s > -1, for every channel (real checkpoints: T91 x2 0.0 .. 1.04, x4 up to 9.1);
-    // a slope at or below -1 + 1/8 - where c would exceed 15 and the scaled weights lose their bits - sends the model to the exact kernels.
-    // (offsets into `blob`: 0 w_feat [25][56], 1 b_feat, 2 a_feat, 3 w_shrink [56][12], 4 b, 5 a, 6 + 3l w_map[l] [9][12][12] (tap, cin, cout),
-    //  7 + 3l b, 8 + 3l a, 18 w_expand [12][56], 19 b, 20 a, 21 w_deconv [81][56] (tap, cin))
-    struct Act { int w, b, a, channels, count, stride; };   // producing weights: `count` values per channel, `stride` apart, first at w + channel
-    const Act acts[7] = {{0, 1, 2, 56, 25, 56}, {3, 4, 5, 12, 56, 12}, {6, 7, 8, 12, 108, 12}, {9, 10, 11, 12, 108, 12}, {12, 13, 14, 12, 108, 12},
-                         {15, 16, 17, 12, 108, 12}, {18, 19, 20, 56, 12, 56}};
-    if (!fs_exact)
-      for (const Act& A : acts)
-        for (int c = 0; c < A.channels; ++c) if (!(blob[off[A.a] + c] > -0.875f)) fs_exact = true;
-    if (!fs_exact) {   // (both matrix-core modes: fp16 and fp32-grade)
-      std::vector<float> scaled = blob;
-      float* B = scaled.data();
-      for (const Act& A : acts)
-        for (int c = 0; c < A.channels; ++c) {
-          const float sl = B[off[A.a] + c], sa = 0.5f * (1.f + sl);
-          for (int i = 0; i < A.count; ++i) B[off[A.w] + c + (size_t)i * A.stride] *= sa;
-          B[off[A.b] + c] *= sa;
-          B[off[A.a] + c] = (1.f - sl) / (1.f + sl);
-        }
-      // the range check on what the kernels get: every scaled weight and bias, the slopes' c, the tail's weights and bias
-      bool fits = std::fabs(fsw.b_deconv) < 6.0e4f;
-      for (float v : scaled) fits = fits && std::fabs(v) < 6.0e4f;
-      if (fits) { blob.swap(scaled); fsw.prelu_abs = true; }
-      else fs_exact = true;   // the exact kernels take the unscaled layout
-    }
-    upload(fs_blob, blob.data(), blob.size() * 4);
-    weight_bytes = blob.size() * 4;
-    const float* d = fs_blob.as<float>(); k = 0;
-    fsw.w_feat = d + off[k++]; fsw.b_feat = d + off[k++]; fsw.a_feat = d + off[k++];
-    fsw.w_shrink = d + off[k++]; fsw.b_shrink = d + off[k++]; fsw.a_shrink = d + off[k++];
-    for (int l = 0; l < 4; ++l) { fsw.w_map[l] = d + off[k++]; fsw.b_map[l] = d + off[k++]; fsw.a_map[l] = d + off[k++]; }
-    fsw.w_expand = d + off[k++]; fsw.b_expand = d + off[k++]; fsw.a_expand = d + off[k++];
-    fsw.w_deconv = d + off[k++];
+    weight_bytes = fsrcnn_pack_weights(pc, fs_exact, fs_blob, fsw);   // (fsrcnn_weights.cpp; a checkpoint outside the matrix-core modes' range sets fs_exact)
   } else if (desc.kind == SS4K_RRDBNET) {
     const int nf = desc.num_feat, g = desc.num_grow_ch;
     const int cin0 = 3 * (desc.scale == 2 ? 4 : desc.scale == 1 ? 16 : 1);

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "glue.h"
+#include "fsrcnn.h"
 #include <tuple>
 
 namespace ss4k {

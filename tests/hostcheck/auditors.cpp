@@ -165,19 +165,20 @@ void fsrcnn_forward(ss4k_ctx*, const FsrcnnWeights& W, int factor, const float* 
   begin_launch();
   const char* K = "fsrcnn";
   const size_t px = (size_t)n * h * w;
-  need(K, -1, "in", "fsrcnn.hip:1315,1337", in, px * (in_u8 ? 1 : 4));
-  need(K, -1, "out", "fsrcnn.hip:1309 (HR planes)", out, px * factor * factor * (out_half ? 2 : 4), true);
+  need(K, -1, "in", "fsrcnn.hip fs_head (k_fs_head, k_fs_head_m)", in, px * (in_u8 ? 1 : 4));
+  need(K, -1, "out", "fsrcnn.hip fs_tail (HR planes)", out, px * factor * factor * (out_half ? 2 : 4), true);
   // the two stage buffers: 12 channels per pixel, fp32 at most (the fp16 mode packs them tighter)
-  need(K, -1, "ws12a", "models.cpp:702; fsrcnn.hip:1337,1352", ws12a, px * 12 * 4, true);
-  need(K, -1, "ws12b", "models.cpp:702; fsrcnn.hip:1352-1356", ws12b, px * 12 * 4, true);
+  need(K, -1, "ws12a", "models.cpp Model::forward_impl; fsrcnn.hip fs_head, fs_maps", ws12a, px * 12 * 4, true);
+  need(K, -1, "ws12b", "models.cpp Model::forward_impl; fsrcnn.hip fs_maps", ws12b, px * 12 * 4, true);
   (void)mode;
-  need(K, -1, "w_feat", "glue.h:77", W.w_feat, 25 * 56 * 4); need(K, -1, "b_feat", "glue.h:78", W.b_feat, 56 * 4); need(K, -1, "a_feat", "glue.h:79", W.a_feat, 56 * 4);
-  need(K, -1, "w_shrink", "glue.h:80", W.w_shrink, 56 * 12 * 4); need(K, -1, "b_shrink", "glue.h:81", W.b_shrink, 12 * 4); need(K, -1, "a_shrink", "glue.h:81", W.a_shrink, 12 * 4);
+  const char* L = "fsrcnn.h FsrcnnWeights";   // the layouts fsrcnn_pack_weights (fsrcnn_weights.cpp) produces
+  need(K, -1, "w_feat", L, W.w_feat, 25 * 56 * 4); need(K, -1, "b_feat", L, W.b_feat, 56 * 4); need(K, -1, "a_feat", L, W.a_feat, 56 * 4);
+  need(K, -1, "w_shrink", L, W.w_shrink, 56 * 12 * 4); need(K, -1, "b_shrink", L, W.b_shrink, 12 * 4); need(K, -1, "a_shrink", L, W.a_shrink, 12 * 4);
   for (int l = 0; l < 4; ++l) {
-    need(K, -1, "w_map", "glue.h:82", W.w_map[l], 9 * 12 * 12 * 4); need(K, -1, "b_map", "glue.h:83", W.b_map[l], 12 * 4); need(K, -1, "a_map", "glue.h:83", W.a_map[l], 12 * 4);
+    need(K, -1, "w_map", L, W.w_map[l], 9 * 12 * 12 * 4); need(K, -1, "b_map", L, W.b_map[l], 12 * 4); need(K, -1, "a_map", L, W.a_map[l], 12 * 4);
   }
-  need(K, -1, "w_expand", "glue.h:84", W.w_expand, 12 * 56 * 4); need(K, -1, "b_expand", "glue.h:85", W.b_expand, 56 * 4); need(K, -1, "a_expand", "glue.h:85", W.a_expand, 56 * 4);
-  need(K, -1, "w_deconv", "glue.h:86", W.w_deconv, 81 * 56 * 4);
+  need(K, -1, "w_expand", L, W.w_expand, 12 * 56 * 4); need(K, -1, "b_expand", L, W.b_expand, 56 * 4); need(K, -1, "a_expand", L, W.a_expand, 56 * 4);
+  need(K, -1, "w_deconv", L, W.w_deconv, 81 * 56 * 4);
   end_launch();
 }
 

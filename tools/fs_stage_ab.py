@@ -1,5 +1,5 @@
 """Dev tool (GPU box): FSRCNN x2 on 12 planes of 720p, per-stage ms (ss4k_prof_read_kind) in fp16 mode and fp32-grade mode, for the values of an
-environment switch read per call / per process: python tools/fs_stage_ab.py SS4K_MH_NU 1 2   (one child process per value, interleaved)"""
+environment switch read per call / per process: python tools/fs_stage_ab.py SS4K_FS_EXACT 0 1   (one child process per value, interleaved)"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if sys.argv[1] == "--child":
