@@ -340,6 +340,32 @@ int ss4k_frvsr_upscale_streams_at(ss4k_frvsr_upscaler* up, const int32_t* slots,
 int ss4k_frvsr_upscaler_enable_taps(ss4k_frvsr_upscaler* up, int enable);
 int ss4k_frvsr_upscaler_read_tap(ss4k_frvsr_upscaler* up, int which, float* out_dev, size_t capacity_floats, int dims[4], void* hip_stream);
 
+/* Scene cuts (an addition to the reference, whose service never resets a stream: after a hard cut it warps a 4x image of the old scene into the new
+ * one).  Off by default, and a stream with it off is bit for bit what it is without.  With a threshold set, every round of the three ss4k_frvsr_upscale_*
+ * entry points is preceded by three launches on the round's stream - no host round trip, no synchronisation - that apply this rule per slot, in
+ * exact integer arithmetic on the input frames AS THEY ARRIVE (uint8 HWC, before the area resize):
+ *   1. the slot has no recurrent state (its first frame, after a reset, ...) or the frame's (h, w) differs from the stored frame's: no comparison;
+ *      the frame is stored, S_prev = 0.
+ *   2. otherwise S = sum over the 3 h w bytes of |frame - stored|, score = min(S, |S - S_prev|) - the second term keeps sustained fast motion from
+ *      firing on every frame -, a CUT iff score >= T = max(1, ceil(threshold * 3 h w)); then S_prev = S, the frame is stored, compared += 1.  On a
+ *      cut, cuts += 1 and the slot's lr_prev / hr_prev become zero: the step that follows treats the frame exactly as a new stream's first.
+ * threshold is the mean absolute byte difference in 8-bit levels, in (0, 255]; 0 turns the detector off, which drops the stored frames and the
+ * counters (turning it on again starts every slot at 1.); NaN, negative values and values above 255: SS4K_EINVAL.  A round that is refused
+ * changes nothing of the detector either.  ss4k_frvsr_upscaler_state_bytes includes the stored frames.
+ * _stats synchronises with hip_stream and reads the slot's counters and the last frame's values (all 0 after a frame that was not compared);
+ * _total never synchronises: the cuts of all slots in the rounds that have COMPLETED (a pinned host array that every round refreshes by an
+ * asynchronous copy on its stream). */
+typedef struct ss4k_scene_cut_stats { uint64_t compared, cuts, last_sad, last_score; int32_t last_was_cut, reserved; } ss4k_scene_cut_stats;
+int ss4k_frvsr_upscaler_set_scene_cut(ss4k_frvsr_upscaler* up, double threshold);      /* 0 = off (default) */
+int ss4k_frvsr_upscaler_scene_cut(const ss4k_frvsr_upscaler* up, double* threshold);
+int ss4k_frvsr_upscaler_scene_cut_stats(ss4k_frvsr_upscaler* up, int slot, ss4k_scene_cut_stats* out, void* hip_stream);  /* synchronises */
+int ss4k_frvsr_upscaler_scene_cut_total(const ss4k_frvsr_upscaler* up, uint64_t* cuts); /* never synchronises: cuts of rounds that have completed */
+/* The detector's sum on its own: sad_out_dev[i] = sum over bytes_per_frame bytes of |a_dev[i][k] - b_dev[i][k]|, exact.  a_dev / b_dev: HOST arrays
+ * of n_items (1..64) DEVICE pointers, frames at any byte address; sad_out_dev: n_items uint64 on the device, 8-byte aligned.  Nothing else is
+ * written.  (A caller of the temporal BSVD service can decide about flush() with it.) */
+int ss4k_op_frame_sad_u8(ss4k_ctx* ctx, const uint8_t* const* a_dev, const uint8_t* const* b_dev, int n_items, size_t bytes_per_frame,
+                         uint64_t* sad_out_dev, void* hip_stream);
+
 /* backward_warp(x, flow) (utils/net_utils.py:50-93): grid_sample(bilinear, padding_mode='border', align_corners=True) at linspace(-1, 1) +
  * flow / ((size - 1) / 2).  x (n, c, h, w), flow (n, 2, h, w) (channel 0 = x displacement in pixels), out (n, c, h, w); h, w >= 2 */
 int ss4k_op_backward_warp(ss4k_ctx* ctx, const float* x_dev, const float* flow_dev, float* out_dev, int n, int c, int h, int w, void* hip_stream);

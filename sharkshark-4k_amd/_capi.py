@@ -37,6 +37,8 @@ SYMBOLS = [
     "ss4k_frvsr_upscale_streams_at",
     "ss4k_frvsr_param_count_as", "ss4k_frvsr_create_as", "ss4k_frvsr_generator",
     "ss4k_frvsr_param_count_ex", "ss4k_frvsr_create_ex", "ss4k_frvsr_degradation",
+    "ss4k_frvsr_upscaler_set_scene_cut", "ss4k_frvsr_upscaler_scene_cut", "ss4k_frvsr_upscaler_scene_cut_stats", "ss4k_frvsr_upscaler_scene_cut_total",
+    "ss4k_op_frame_sad_u8",
     "ss4k_bsvd_online_create", "ss4k_bsvd_online_destroy", "ss4k_bsvd_online_lag", "ss4k_bsvd_online_push", "ss4k_bsvd_online_flush",
     "ss4k_bsvd_online_reset", "ss4k_bsvd_online_pending", "ss4k_bsvd_online_state_bytes",
     "ss4k_upscaler_temporal_create", "ss4k_upscaler_temporal_destroy", "ss4k_upscale_frames_temporal", "ss4k_upscaler_temporal_flush",
@@ -96,6 +98,12 @@ class UpscaleCfg(C.Structure):
 class FrvsrDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("num_feat", C.c_int32), ("num_block", C.c_int32), ("flags", C.c_int32),
                 ("reserved", C.c_int32 * 4)]
+
+
+class SceneCutStats(C.Structure):
+    """ss4k_scene_cut_stats: a slot's counters and the values of its last frame (include/ss4k.h)."""
+    _fields_ = [("compared", C.c_uint64), ("cuts", C.c_uint64), ("last_sad", C.c_uint64), ("last_score", C.c_uint64),
+                ("last_was_cut", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Ss4kError(RuntimeError):
@@ -253,6 +261,12 @@ def load(path: str) -> C.CDLL:
         L.ss4k_frvsr_param_count_ex.argtypes = [C.POINTER(FrvsrDesc), i, i]; L.ss4k_frvsr_param_count_ex.restype = sz
         L.ss4k_frvsr_create_ex.argtypes = [vp, C.POINTER(FrvsrDesc), i, i, i, vp, sz, C.POINTER(vp)]
         L.ss4k_frvsr_degradation.argtypes = [vp]
+    if hasattr(L, "ss4k_frvsr_upscaler_set_scene_cut"):   # (absent from builds before the scene-cut detector)
+        L.ss4k_frvsr_upscaler_set_scene_cut.argtypes = [vp, C.c_double]
+        L.ss4k_frvsr_upscaler_scene_cut.argtypes = [vp, C.POINTER(C.c_double)]
+        L.ss4k_frvsr_upscaler_scene_cut_stats.argtypes = [vp, i, C.POINTER(SceneCutStats), vp]
+        L.ss4k_frvsr_upscaler_scene_cut_total.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.ss4k_op_frame_sad_u8.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, sz, vp, vp]
     if hasattr(L, "ss4k_bsvd_online_create"):   # (absent from builds before the online denoiser)
         L.ss4k_bsvd_online_create.argtypes = [vp, vp, i, C.POINTER(vp)]
         L.ss4k_bsvd_online_destroy.argtypes = [vp]; L.ss4k_bsvd_online_destroy.restype = None
@@ -502,6 +516,21 @@ class Context:
         n, c, h, w = x.shape
         out = torch.empty((n, c, 4 * h, 4 * w), dtype=torch.float32, device=x.device)
         _check(lib().ss4k_op_bicubic_upsample4(self._h, x.data_ptr(), out.data_ptr(), n * c, h, w, _stream()))
+        return out
+
+    def frame_sad(self, a_frames, b_frames) -> torch.Tensor:
+        """``sum |a_frames[i] - b_frames[i]|`` over the bytes of each pair of uint8 device frames (1..64 pairs of one size, each contiguous, at
+        any byte address): an int64 tensor of the exact sums on the device (ss4k_op_frame_sad_u8, the scene-cut detector's kernel)."""
+        n = len(a_frames)
+        assert n >= 1 and len(b_frames) == n, "one b frame per a frame"
+        nbytes = int(a_frames[0].numel())
+        for t in list(a_frames) + list(b_frames):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and int(t.numel()) == nbytes, "frames: contiguous uint8 of one size"
+        out = torch.empty((n,), dtype=torch.int64, device=a_frames[0].device)
+        pa = (C.c_void_p * n)(*[t.data_ptr() for t in a_frames])
+        pb = (C.c_void_p * n)(*[t.data_ptr() for t in b_frames])
+        with torch.cuda.device(self.device):
+            _check(lib().ss4k_op_frame_sad_u8(self._h, pa, pb, n, nbytes, out.data_ptr(), _stream()))
         return out
 
     def f32nchw_to_u8nhwc(self, x):
@@ -898,7 +927,7 @@ class FrvsrUpscaler:
     """ss4k_frvsr_upscaler: EgvsrUpscalerService.upscale (egvsr_upscaler.py:172-212), uint8 NHWC frames of ONE stream in order -> uint8 NHWC;
     with ``max_streams`` > 1 also rounds of one frame per stream slot (``upscale_streams``).  Calling the object drives slot 0."""
 
-    def __init__(self, ctx: Context, model: Frvsr, lr_shape, output_shape=None, max_streams: int = 1):
+    def __init__(self, ctx: Context, model: Frvsr, lr_shape, output_shape=None, max_streams: int = 1, scene_cut: Optional[float] = None):
         self.ctx, self.model, self.max_streams = ctx, model, int(max_streams)
         oh, ow = (0, 0) if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
         h = C.c_void_p()
@@ -907,6 +936,12 @@ class FrvsrUpscaler:
         else:
             _check(lib().ss4k_frvsr_upscaler_create_streams(ctx._h, model._h, int(lr_shape[0]), int(lr_shape[1]), oh, ow, self.max_streams, C.byref(h)))
         self._h = h
+        if scene_cut is not None:
+            try:
+                self.set_scene_cut(scene_cut)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None):
@@ -925,6 +960,30 @@ class FrvsrUpscaler:
             _check(lib().ss4k_frvsr_upscaler_reset(self._h))
         else:
             _check(lib().ss4k_frvsr_upscaler_reset_stream(self._h, int(slot)))
+
+    def set_scene_cut(self, threshold: float) -> None:
+        """Scene-cut detection in front of every round (include/ss4k.h): ``threshold`` is the mean absolute byte difference between a
+        stream's consecutive input frames, in (0, 255]; 0 turns it off (the default).  A cut resets that stream's state on the device."""
+        _check(lib().ss4k_frvsr_upscaler_set_scene_cut(self._h, float(threshold)))
+
+    def scene_cut(self) -> float:
+        t = C.c_double()
+        _check(lib().ss4k_frvsr_upscaler_scene_cut(self._h, C.byref(t)))
+        return float(t.value)
+
+    def scene_cut_stats(self, slot: int = 0) -> dict:
+        """The slot's counters and its last frame's values: compared, cuts, last_sad, last_score, last_was_cut.  Synchronises."""
+        s = SceneCutStats()
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_frvsr_upscaler_scene_cut_stats(self._h, int(slot), C.byref(s), _stream()))
+        return {"compared": int(s.compared), "cuts": int(s.cuts), "last_sad": int(s.last_sad), "last_score": int(s.last_score),
+                "last_was_cut": int(s.last_was_cut)}
+
+    def scene_cut_total(self) -> int:
+        """Cuts of all slots in the rounds that have completed on the device; never synchronises."""
+        n = C.c_uint64()
+        _check(lib().ss4k_frvsr_upscaler_scene_cut_total(self._h, C.byref(n)))
+        return int(n.value)
 
     def state_bytes(self) -> int:
         """Device bytes of recurrent state held now (slots that never saw a frame hold none)."""

@@ -2,6 +2,7 @@
 #include "api_guard.h"
 #include "frvsr.h"
 #include "host_tables.h"
+#include "scene_cut.h"
 #include "upscaler.h"
 #include <cmath>
 #include <cstdarg>
@@ -326,7 +327,7 @@ int ss4k_frvsr_upscaler_reset_stream(ss4k_frvsr_upscaler* up, int slot) {
   });
 }
 int ss4k_frvsr_upscaler_state_bytes(const ss4k_frvsr_upscaler* up, size_t* bytes) {
-  return guard([&] { SS4K_REQUIRE(up && bytes, "ss4k_frvsr_upscaler_state_bytes: NULL argument"); *bytes = up->u.state_bytes(); });
+  return guard([&] { SS4K_REQUIRE(up && bytes, "ss4k_frvsr_upscaler_state_bytes: NULL argument"); *bytes = up->u.state_bytes() + (up->cut ? up->cut->bytes() : 0); });
 }
 int ss4k_frvsr_upscaler_out_shape(const ss4k_frvsr_upscaler* up, int* oh, int* ow) {
   return guard([&] { SS4K_REQUIRE(up && oh && ow, "NULL argument"); up->u.out_shape(oh, ow); });
@@ -337,7 +338,8 @@ int ss4k_frvsr_upscale_frames(ss4k_frvsr_upscaler* up, const uint8_t* in, int n,
     SS4K_REQUIRE(n > 0 && h > 0 && w > 0, "ss4k_frvsr_upscale_frames: empty batch");
     int oh, ow; up->u.out_shape(&oh, &ow);
     SS4K_REQUIRE(cap >= (size_t)oh * ow * 3 * n, "ss4k_frvsr_upscale_frames: output buffer too small");
-    up->u.frames(in, n, h, w, out, (hipStream_t)stream);
+    if (up->cut && up->cut->on()) scene_cut_frames(up, in, n, h, w, out, (hipStream_t)stream);   // (the detector's launches in front of every round)
+    else up->u.frames(in, n, h, w, out, (hipStream_t)stream);
   });
 }
 int ss4k_frvsr_upscale_streams(ss4k_frvsr_upscaler* up, const int32_t* slots, int n_streams, const uint8_t* in, int h, int w, uint8_t* out, size_t cap,
@@ -349,7 +351,8 @@ int ss4k_frvsr_upscale_streams(ss4k_frvsr_upscaler* up, const int32_t* slots, in
     SS4K_REQUIRE(h > 0 && w > 0, "ss4k_frvsr_upscale_streams: empty frames");
     int oh, ow; up->u.out_shape(&oh, &ow);
     SS4K_REQUIRE(cap >= (size_t)oh * ow * 3 * n_streams, "ss4k_frvsr_upscale_streams: output buffer too small");
-    up->u.round(in, slots, n_streams, h, w, out, (hipStream_t)stream);
+    if (up->cut && up->cut->on()) scene_cut_round(up, in, slots, n_streams, h, w, out, (hipStream_t)stream);
+    else up->u.round(in, slots, n_streams, h, w, out, (hipStream_t)stream);
   });
 }
 int ss4k_frvsr_upscale_streams_at(ss4k_frvsr_upscaler* up, const int32_t* slots, int n_streams, const uint8_t* const* in, int h, int w, uint8_t* const* out,
@@ -361,7 +364,8 @@ int ss4k_frvsr_upscale_streams_at(ss4k_frvsr_upscaler* up, const int32_t* slots,
     SS4K_REQUIRE(h > 0 && w > 0, "ss4k_frvsr_upscale_streams_at: empty frames");
     int oh, ow; up->u.out_shape(&oh, &ow);
     SS4K_REQUIRE(frame_cap >= (size_t)oh * ow * 3, "ss4k_frvsr_upscale_streams_at: output frames too small");
-    up->u.round_at(in, slots, n_streams, h, w, out, (hipStream_t)stream);
+    if (up->cut && up->cut->on()) scene_cut_round_at(up, in, slots, n_streams, h, w, out, (hipStream_t)stream);
+    else up->u.round_at(in, slots, n_streams, h, w, out, (hipStream_t)stream);
   });
 }
 int ss4k_frvsr_upscaler_enable_taps(ss4k_frvsr_upscaler* up, int en) {

@@ -9,6 +9,8 @@
 
 namespace ss4k {
 
+struct SceneCut;
+
 // Base pointers of the items of a batched launch whose tensors are NOT one contiguous batch: stream i's hr_prev / hr_curr, (3, 4 h, 4 w) fp32,
 // each in its own allocation.  Passed BY VALUE in the kernel arguments (512 B): no device table, no upload, no synchronisation, and the
 // buffers stay separate DevBufs (a red zone around each in the dev library's guard mode).  Entries past the launch's n are not read.
@@ -183,6 +185,7 @@ struct FrvsrUpscaler {
   void frames(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st);   // n consecutive frames of slot 0
   size_t state_bytes() const;
  private:
+  friend struct SceneCut;   // (scene_cut.h: the detector makes a round's refusals - check_round - before its own launches, from outside)
   // a round's per-item pointers into the slots' state: lr_curr (= lr_dst, as a table), lr_prev, hr_prev, hr_curr
   struct RoundPtrs { const float* lr_curr[SS4K_FRVSR_MAX_STREAMS]; const float* lr_prev[SS4K_FRVSR_MAX_STREAMS]; FrvsrPtrs lr_dst, hr_prev, hr_curr; };
   // every refusal of a round, before any slot changes; area_chain: the round resizes with op_area (round), not inside the frame kernels (round_at)
@@ -194,4 +197,5 @@ struct FrvsrUpscaler {
 }  // namespace ss4k
 
 struct ss4k_frvsr { ss4k::Frvsr f; };
-struct ss4k_frvsr_upscaler { ss4k::FrvsrUpscaler u; };
+// the scene-cut detector (scene_cut.h, api_scene_cut.cpp) lives beside the upscaler, not in it: null until ss4k_frvsr_upscaler_set_scene_cut
+struct ss4k_frvsr_upscaler { ss4k::FrvsrUpscaler u; ss4k::SceneCut* cut = nullptr; ~ss4k_frvsr_upscaler(); };

@@ -31,6 +31,9 @@ Semantics (``StreamRouter`` is the table, testable without processes):
   living worker FROM ZERO STATE (``report()['reopened']``).  Nothing is rescued or run again - old frames on fresh state would be a
   wrong picture - and no replacement worker is started.
 
+* SCENE CUTS - ``EgvsrNode(scene_cut=T)`` hands the keyword to every worker's service (its docstring has the rule); ``report()['scene_cuts']``
+  is, per worker, the latest ``egvsr.scene_cuts`` seen in the profiler of one of its answers (frames-less ones included).
+
 The workers' life cycle (device list, rings and ready events before the start, the ready wait, ``alive`` / ``stop`` / ``close``) is
 ``worker_pool.WorkerPool``'s, shared with ``node.UpscalerNode``.
 """
@@ -136,6 +139,7 @@ class EgvsrNode(WorkerPool):
         self.next_step = 0
         self.next_emit = 0
         self.host_jobs = [0] * G
+        self.scene_cuts = [0] * G   # per worker: the latest 'egvsr.scene_cuts' seen in a result's profiler
         self.lost = 0
 
     def _make_service(self, k: int):
@@ -251,6 +255,9 @@ class EgvsrNode(WorkerPool):
             except (queue.Empty, OSError, EOFError):
                 return n
             n += 1
+            cuts = getattr(getattr(e, "profiler", None), "data", {}).get("egvsr.scene_cuts")
+            if cuts is not None:
+                self.scene_cuts[k] = int(cuts)
             part = self._inflight[k].pop(e.step, None)
             if part is None or not part["frames"]:
                 continue                                       # (the answer of a frames-less end_streams entry: swallowed)
@@ -335,6 +342,6 @@ class EgvsrNode(WorkerPool):
 
     def report(self) -> dict:
         self._reap()
-        return {"streams": [self.router.streams(k) for k in range(len(self.services))], "host_jobs": list(self.host_jobs), "lost": self.lost,
+        return {"streams": [self.router.streams(k) for k in range(len(self.services))], "host_jobs": list(self.host_jobs), "scene_cuts": list(self.scene_cuts), "lost": self.lost,
                 "streams_lost": list(self.router.streams_lost), "reopened": self.router.reopened, "alive": list(self.router.alive),
                 "in_flight": [len(d) for d in self._inflight]}

@@ -21,6 +21,12 @@ own, runs the job, copies the result into the named slot of the output ring on a
 ``HostFrames(result=True)``; one more job is enqueued before that result is waited for, so the copies run under the neighbour's kernels (``host_io.py``: ``HostFrameIO`` and ``HeldResults``, shared with ``HipUpscalerService``).  A
 ``StreamQueueEntry`` with ``frames=None`` and ``end_streams`` only frees those slots: no GPU work, answered with ``frames=None``.
 
+``scene_cut=T`` (None / 0: off, the default, and the service is bit for bit what it is without it): a detector on the device in front of
+every round (``ss4k_frvsr_upscaler_set_scene_cut``, include/ss4k.h) compares each stream's input frame with its previous one and, at a
+hard cut, zeroes that stream's ``lr_prev`` / ``hr_prev`` before the step - the reference's service never resets and ghosts the old scene
+into the new one.  T is a mean absolute byte difference in (0, 255]; each job's profiler carries ``egvsr.scene_cuts``, the worker's cuts in
+the rounds that have completed (read without a synchronisation).
+
 ``generator='tecogan'`` runs TecoGAN's FRNet instead (``nb`` then defaults to 16; its checkpoint is that class's bare state_dict).
 
 Weights as for the other services: ``weights=None`` looks ``EGVSR_iter420000.pth`` (``egvsr_upscaler.py:25``) up in
@@ -95,6 +101,19 @@ def plan_rounds(streams: Sequence[Hashable]) -> List[List[int]]:
     return rounds
 
 
+def check_scene_cut(threshold) -> Optional[float]:
+    """``scene_cut`` as the services take it: None (off) or the detector's threshold, a mean absolute byte difference in (0, 255]; 0 is off too
+    (``ss4k_frvsr_upscaler_set_scene_cut``).  Anything the library would refuse raises ``ValueError`` here, before a worker exists."""
+    if threshold is None:
+        return None
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
+        raise ValueError(f"scene_cut is None or a number in [0, 255], not {threshold!r}")
+    t = float(threshold)
+    if not (0.0 <= t <= 255.0):   # (NaN fails both comparisons)
+        raise ValueError(f"scene_cut is None or a number in [0, 255], not {threshold!r}")
+    return t
+
+
 class HipEgvsrUpscalerService(BaseUpscalerService):
     #: (frames-in ring, frames-out ring) of ``hostring.make_rings``, set before ``start()``: the worker then takes ``HostFrames`` jobs
     host_rings = None
@@ -102,7 +121,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
     HOST_STAGE_DEPTH = 3
 
     def __init__(self, lr_level=1, device=0, on_queue=None, *, weights=None, checkpoint_dir: Optional[str] = None, dtype="f16", nb=None,
-                 lr_shape=None, seed=0, max_streams=1, generator="egvsr", degradation="BD"):
+                 lr_shape=None, seed=0, max_streams=1, generator="egvsr", degradation="BD", scene_cut=None):
         self.lr_shape = tuple(lr_shape) if lr_shape is not None else LR_SHAPES[lr_level]
         self.scale = 4
         self.hr_shape = tuple([i * self.scale for i in self.lr_shape])
@@ -116,6 +135,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self.nb = int(nb) if nb is not None else (16 if generator in ("tecogan", 1) else 10)
         self.seed = seed
         self.max_streams = int(max_streams)
+        self.scene_cut = check_scene_cut(scene_cut)
         super().__init__()
 
     def out_hw(self):
@@ -135,6 +155,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
                                                degradation=self.degradation)
         self._up = None
         self._up_key = None
+        self._cuts_before = 0   # cuts counted by upscaler objects that have been replaced (a new shape)
         self._slots = StreamSlots(self.max_streams)
         self._init_host_io()
         log("model loaded")
@@ -166,10 +187,22 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         key = (tuple(self.lr_shape), None if self.output_shape is None else tuple(int(v) for v in self.output_shape))
         if self._up is None or self._up_key != key:   # (the pipelines overwrite lr_shape / output_shape after construction)
             if self._up is not None:
+                if self.scene_cut:
+                    self._cuts_before += self._up.scene_cut_total()
                 self._up.close()
-            self._up, self._up_key = _capi.FrvsrUpscaler(self.ctx, self.model, key[0], key[1], self.max_streams), key
+            self._up, self._up_key = self._make_upscaler(_capi, key), key
             self._slots = StreamSlots(self.max_streams)   # (a new shape: every stream starts over)
         return self._up
+
+    def _make_upscaler(self, _capi, key):
+        if not self.scene_cut:
+            return _capi.FrvsrUpscaler(self.ctx, self.model, key[0], key[1], self.max_streams)
+        return _capi.FrvsrUpscaler(self.ctx, self.model, key[0], key[1], self.max_streams, scene_cut=self.scene_cut)
+
+    def scene_cuts(self) -> int:
+        """Scene cuts seen by this worker in the rounds that have completed on the device (never synchronises); 0 with the detector off."""
+        up = getattr(self, "_up", None)
+        return self._cuts_before + (up.scene_cut_total() if up is not None and self.scene_cut else 0)
 
     def reset(self):
         """Forget ``lr_prev`` / ``hr_prev``: the next frame is a stream's first (egvsr_upscaler.py:165-166)."""
@@ -264,6 +297,8 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
             return answered
 
         upscaled, elapsed, prof = self._run_job(job, run)
+        if self.scene_cut:
+            prof.set("egvsr.scene_cuts", self.scene_cuts())   # (as the device has counted so far: a job still running is not in it)
         if hasattr(job, "streams") or hasattr(job, "end_streams"):
             try:   # the caller's own type, when it takes the eight fields
                 return type(job)(frames=upscaled, audio_segment=getattr(job, "audio_segment", None), step=getattr(job, "step", 0), elapsed=elapsed,

@@ -26,9 +26,15 @@ pad-1 3x3 convolution 64 -> 256 on the conv kernels (``SS4K_FRVSR_CONVT_EMBEDDED
 + warp + space-to-depth and TecoGAN's ``skip`` the bilinear one.  ``BD`` (the default) uses the entry points from before there was a choice, so
 it also runs on an older build (``SS4K_LIB``) for an A/B.
 
+``--scene-cut T``: after the table's own figures (detector off, as ever) the steady-state window is timed again ``--repeats`` times with the
+scene-cut detector off and on in turn, in this process and on the one upscaler (``ss4k_frvsr_upscaler_set_scene_cut``): ``ms_off`` / ``ms_on``
+hold every window, ``glue_off`` / ``glue_on`` the stage split's glue column (the detector's three launches are timed as glue).  T = 255 never
+fires on these frames.  ``--cut-every N`` makes every N-th frame of every stream black - a cut at it and none after it, at a T between the
+scene's motion and that jump (60) - and the row's ``cuts_per_window`` says how many the device counted.  Needs a library with the detector.
+
 usage: python tools/frvsr_time.py [--frames 64] [--nb 10] [--streams 1] [--scattered] [--lr 540x960,720x1280]
                                   [--output-shapes 1440x2560,none] [--generator egvsr|tecogan] [--embedded | --phase] [--degradation BD|BI]
-                                  [--out frvsr_time.json]"""
+                                  [--scene-cut T [--cut-every N] [--repeats 3]] [--out frvsr_time.json]"""
 import argparse
 import json
 import os
@@ -78,6 +84,9 @@ def main():
     ap.add_argument("--scattered", action="store_true", help="rounds through ss4k_frvsr_upscale_streams_at, frames and results as separate allocations")
     ap.add_argument("--lr", default=",".join(f"{h}x{w}" for h, w in REFERENCE_MS), help="lr shapes, HxW[,HxW...]")
     ap.add_argument("--output-shapes", default="1440x2560,none", help="output shapes, HxW or none[,...]")
+    ap.add_argument("--scene-cut", type=float, default=0.0, help="also time the steady state with the scene-cut detector off / on in turn, at this threshold")
+    ap.add_argument("--cut-every", type=int, default=0, help="every N-th frame of every stream is black: a forced scene cut")
+    ap.add_argument("--repeats", type=int, default=3, help="--scene-cut: windows per setting")
     ap.add_argument("--out", default="frvsr_time.json")
     a = ap.parse_args()
     assert a.frames >= 64, "the steady state is read from a stream of at least 64 distinct frames"
@@ -105,6 +114,8 @@ def main():
     rows = []
     for lr in lrs:
         frames = stream_frames(a.frames, lr[0], lr[1], ctx.device)
+        if a.cut_every > 0:
+            frames[a.cut_every - 1::a.cut_every] = 0
         if S > 1:   # (frames, S, h, w, 3): round i holds frame i of every stream
             frames = torch.stack([torch.roll(frames, shifts=-5 * k, dims=0) for k in range(S)], dim=1)
         if a.scattered:   # [round][item]: every frame in an allocation of its own
@@ -154,6 +165,37 @@ def main():
                        stage_ms_per_frame=stages, stage_sum_ms=sum(stages.values()), fnet_conv_tflops=ff / stages["fnet_conv"] / 1e9,
                        srnet_conv_tflops=fs / stages["srnet_conv"] / 1e9, conv_tflop_per_step=(ff + fs) / 1e12,
                        workspace_mb=model.workspace_bytes(S, lr[0], lr[1]) / 2 ** 20)
+            if a.scene_cut > 0:
+                ms_of, glue_of, cuts = {"off": [], "on": []}, {}, []
+                for _ in range(a.repeats):
+                    for mode in ("off", "on"):
+                        up.set_scene_cut(a.scene_cut if mode == "on" else 0)
+                        up.reset()
+                        run(0, 8)                       # (the stored frames exist, the stream has state)
+                        torch.cuda.synchronize()
+                        before = up.scene_cut_total()
+                        t0 = time.perf_counter()
+                        run(half, half)
+                        torch.cuda.synchronize()
+                        ms_of[mode].append(1000.0 * (time.perf_counter() - t0) / (half * S))
+                        if mode == "on":
+                            cuts.append(up.scene_cut_total() - before)
+                for mode in ("off", "on"):
+                    up.set_scene_cut(a.scene_cut if mode == "on" else 0)
+                    up.reset()
+                    run(0, 8)
+                    model.prof_enable(True)
+                    run(8, 16)
+                    glue_of[mode] = model.prof_read()["glue"] / (16 * S)
+                    model.prof_enable(False)
+                up.set_scene_cut(0)
+                med = {k: float(np.median(v)) for k, v in ms_of.items()}
+                row.update(scene_cut=a.scene_cut, cut_every=a.cut_every, ms_off=ms_of["off"], ms_on=ms_of["on"], ms_off_median=med["off"], ms_on_median=med["on"],
+                           detector_ms_per_frame=med["on"] - med["off"], detector_percent=100.0 * (med["on"] - med["off"]) / med["off"],
+                           glue_off=glue_of["off"], glue_on=glue_of["on"], cuts_per_window=cuts)
+                print(f"  scene cut {a.scene_cut:g}" + (f", a black frame every {a.cut_every}" if a.cut_every else "") + ": off " + " ".join(f"{v:.3f}" for v in ms_of["off"])
+                      + " | on " + " ".join(f"{v:.3f}" for v in ms_of["on"]) + f" ms/frame; medians {med['off']:.3f} -> {med['on']:.3f} ({row['detector_percent']:+.2f} %); "
+                      f"glue {glue_of['off']:.3f} -> {glue_of['on']:.3f} ms; cuts per window {cuts}", flush=True)
             if teco:
                 ft, fo = tecogan_tail_flops(lr[0], lr[1])
                 row.update(generator="tecogan", convt_route=route, convt_tflops_useful=ft / stages["convt"] / 1e9,
