@@ -362,7 +362,8 @@ int ss4k_frvsr_upscaler_scene_cut_stats(ss4k_frvsr_upscaler* up, int slot, ss4k_
 int ss4k_frvsr_upscaler_scene_cut_total(const ss4k_frvsr_upscaler* up, uint64_t* cuts); /* never synchronises: cuts of rounds that have completed */
 /* The detector's sum on its own: sad_out_dev[i] = sum over bytes_per_frame bytes of |a_dev[i][k] - b_dev[i][k]|, exact.  a_dev / b_dev: HOST arrays
  * of n_items (1..64) DEVICE pointers, frames at any byte address; sad_out_dev: n_items uint64 on the device, 8-byte aligned.  Nothing else is
- * written.  (A caller of the temporal BSVD service can decide about flush() with it.) */
+ * written.  (The temporal BSVD service needs no caller-side decision any more: ss4k_upscaler_temporal_set_scene_cut runs this sum and the rule on
+ * the device and keeps a cut out of the denoiser without a flush.) */
 int ss4k_op_frame_sad_u8(ss4k_ctx* ctx, const uint8_t* const* a_dev, const uint8_t* const* b_dev, int n_items, size_t bytes_per_frame,
                          uint64_t* sad_out_dev, void* hip_stream);
 
@@ -389,6 +390,16 @@ int ss4k_bsvd_online_lag(const ss4k_bsvd_online* o);
  * capacity below the frames that become ready, or a NULL pointer. */
 int ss4k_bsvd_online_push(ss4k_bsvd_online* o, const float* in_dev, int n, int h, int w, float* out_dev, size_t out_capacity_frames, int* n_out,
                           void* hip_stream);
+/* ss4k_bsvd_online_push with scene cuts: cuts_dev points to n 32-bit DEVICE words, read in stream order on hip_stream (an earlier kernel on that
+ * stream may have produced them); word i != 0: frame i of this push is the FIRST FRAME OF A NEW SCENE.  The only thing that joins two frames in this
+ * network is the temporal shift in front of each BiBufferConv; across a cut it gives zeros, exactly as at either end of a stream.  So a stream
+ * with cuts is, frame for frame and bit for bit, the concatenation of its scenes pushed and flushed as streams of their own - while the lag stays
+ * 16 and every push returns the frames it would return without cuts.  The flags live in a ring of 128 frames on the device (part of
+ * ss4k_bsvd_online_state_bytes from the first push that brings flags).  cuts_dev = NULL: no cut in this push (ss4k_bsvd_online_push); flags of
+ * earlier pushes keep acting until their frames have left, flush rounds included.  A flag on a stream's first frame has no effect.  reset and
+ * the end of a flush clear the flags.  A refused push changes nothing, the flags included. */
+int ss4k_bsvd_online_push_cuts(ss4k_bsvd_online* o, const float* in_dev, const uint32_t* cuts_dev, int n, int h, int w, float* out_dev,
+                               size_t out_capacity_frames, int* n_out, void* hip_stream);
 /* feedin_one_element(None) until drained, then reset: the remaining min(lag, pushed) frames, in rounds of at most max_push feed calls */
 int ss4k_bsvd_online_flush(ss4k_bsvd_online* o, float* out_dev, size_t out_capacity_frames, int* n_out, void* hip_stream);
 /* drops the stream: the next push starts a new one (of any size).  The state buffers stay allocated */
@@ -418,8 +429,22 @@ int ss4k_upscaler_temporal_flush(ss4k_upscaler_temporal* up, uint8_t* out_nhwc_d
 int ss4k_upscaler_temporal_reset(ss4k_upscaler_temporal* up);
 int ss4k_upscaler_temporal_out_shape(const ss4k_upscaler_temporal* up, int h, int w, int* out_h, int* out_w);
 int ss4k_upscaler_temporal_pending(const ss4k_upscaler_temporal* up, int* frames);
-/* the denoiser's state plus the ring of waiting LR planes */
+/* the denoiser's state plus the ring of waiting LR planes (plus the detector's stored frame, below) */
 int ss4k_upscaler_temporal_state_bytes(const ss4k_upscaler_temporal* up, size_t* bytes);
+/* Scene cuts for the temporal stream.  Off by default, and with it off every job runs the launches it ran before there was a detector.  With
+ * a threshold set (validated as ss4k_frvsr_upscaler_set_scene_cut: (0, 255], 0 = off, else SS4K_EINVAL) every job is preceded, after all its
+ * refusals, by the rule above on its input bytes AS THEY ARRIVE - frame i against frame i - 1 of the job, frame 0 against a device copy of the
+ * previous job's last frame; no comparison for a stream's first frame or after a change of (h, w) - and the flags go to the denoiser as in
+ * ss4k_bsvd_online_push_cuts; a scene's first frame also gets the noise map of a stream's first frame (0.05).  The output is, byte for byte,
+ * that of the scenes run as separate streams (frames + flush), a job returns exactly the frames it returns without the detector, and the host
+ * is never asked: no round trip, no synchronisation.  Setting 0 stops detection for later frames (and drops the stored frame and the
+ * counters); flags already inside keep acting until their frames have left.  reset and flush end the detector's stream: the next frame is
+ * not compared.  _stats synchronises with hip_stream; _total never does: the cuts of the jobs that have COMPLETED (a pinned host block that
+ * every job refreshes by an asynchronous copy on its stream). */
+int ss4k_upscaler_temporal_set_scene_cut(ss4k_upscaler_temporal* up, double threshold);   /* 0 = off (default) */
+int ss4k_upscaler_temporal_scene_cut(const ss4k_upscaler_temporal* up, double* threshold);
+int ss4k_upscaler_temporal_scene_cut_stats(ss4k_upscaler_temporal* up, ss4k_scene_cut_stats* out, void* hip_stream);   /* synchronises */
+int ss4k_upscaler_temporal_scene_cut_total(const ss4k_upscaler_temporal* up, uint64_t* cuts);   /* never synchronises */
 
 /* ---- measurement hooks (bench.py: live per-kernel timing with HIP events on the launch stream) */
 /* When enabled, every launch of the dominant conv kernel is bracketed with hipEvents on the

@@ -81,6 +81,16 @@ int ss4k_dev_op_temporal_shift(ss4k_ctx* ctx, const void* in, void* out, int npl
  * unless first_has_prev; the rest from the centre.  out: nplanes planes of `frames` frames.  SS4K_EINVAL where a read would leave `in`. */
 int ss4k_dev_op_bsvd_online_shift(ss4k_ctx* ctx, const void* in, void* out, int nplanes, int in_frames, int slot0, int frames, size_t frame_px,
                                   int slots_per_record, int ch_per_plane, int fold, int first_has_prev, int n_next, void* hip_stream);
+/* shift_cuts: the cut-aware build (include/ss4k.h: ss4k_bsvd_online_push_cuts).  flag_ring: ring_mask + 1 DEVICE words (ring_mask = 2^k - 1),
+ * flag_ring[f & ring_mask] != 0: stream frame f starts a scene; f0: the stream frame of output frame 0.  The next group of output frame t is
+ * also zeros where flag[f0 + t + 1] is set, the previous group where flag[f0 + t] is set.  Routes "bsvdo::shift_window_cuts<half|float>". */
+int ss4k_dev_op_bsvd_online_shift_cuts(ss4k_ctx* ctx, const void* in, void* out, int nplanes, int in_frames, int slot0, int frames, size_t frame_px,
+                                       int slots_per_record, int ch_per_plane, int fold, int first_has_prev, int n_next, const uint32_t* flag_ring,
+                                       unsigned ring_mask, int f0, void* hip_stream);
+/* noise_planes: channel 3 of each of the n (1..64) packed (4, plane_px) fp32 frames becomes level_start where flags[i] != 0 or (i == 0 and
+ * stream_first), else level.  flags: n DEVICE words.  Route "bsvdo::noise_planes". */
+int ss4k_dev_op_bsvd_noise_planes(ss4k_ctx* ctx, float* frames4, int n, size_t plane_px, const uint32_t* flags, int stream_first,
+                                  float level_start, float level, void* hip_stream);
 /* carry: ONE launch for `entries` (1..22) tensors, HOST arrays of one value per entry: in each of nplanes[i] planes, count[i] frames from frame
  * src_first[i] of src[i] (src_frames[i] frames per plane) to the front of dst[i] (dst_frames[i] frames per plane); frame_slots[i]: 16-byte
  * slots per frame.  SS4K_EINVAL where src[i] and dst[i] overlap or the move leaves either buffer. */

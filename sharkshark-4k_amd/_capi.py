@@ -43,6 +43,9 @@ SYMBOLS = [
     "ss4k_bsvd_online_reset", "ss4k_bsvd_online_pending", "ss4k_bsvd_online_state_bytes",
     "ss4k_upscaler_temporal_create", "ss4k_upscaler_temporal_destroy", "ss4k_upscale_frames_temporal", "ss4k_upscaler_temporal_flush",
     "ss4k_upscaler_temporal_reset", "ss4k_upscaler_temporal_out_shape", "ss4k_upscaler_temporal_pending", "ss4k_upscaler_temporal_state_bytes",
+    "ss4k_bsvd_online_push_cuts",
+    "ss4k_upscaler_temporal_set_scene_cut", "ss4k_upscaler_temporal_scene_cut", "ss4k_upscaler_temporal_scene_cut_stats",
+    "ss4k_upscaler_temporal_scene_cut_total",
 ]
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
@@ -72,6 +75,8 @@ DEV_SYMBOLS = [
     "ss4k_dev_op_spin", "ss4k_dev_lane_handicap", "ss4k_dev_lane_counts", "ss4k_dev_lane_counts_reset", "ss4k_dev_lane_drop_join",
     # the kernels of csrc/bsvd_online.hip on caller buffers (tests/test_gpu_bsvd_online.py)
     "ss4k_dev_op_bsvd_online_shift", "ss4k_dev_op_bsvd_online_carry",
+    # ... and the scene-cut builds (tests/test_gpu_bsvd_cuts.py)
+    "ss4k_dev_op_bsvd_online_shift_cuts", "ss4k_dev_op_bsvd_noise_planes",
 ]
 
 
@@ -285,6 +290,15 @@ def load(path: str) -> C.CDLL:
         L.ss4k_upscaler_temporal_out_shape.argtypes = [vp, i, i, C.POINTER(i), C.POINTER(i)]
         L.ss4k_upscaler_temporal_pending.argtypes = [vp, C.POINTER(i)]
         L.ss4k_upscaler_temporal_state_bytes.argtypes = [vp, C.POINTER(sz)]
+    if hasattr(L, "ss4k_bsvd_online_push_cuts"):   # (absent from builds before the temporal stream's scene cuts)
+        L.ss4k_bsvd_online_push_cuts.argtypes = [vp, vp, vp, i, i, i, vp, sz, C.POINTER(i), vp]
+        L.ss4k_upscaler_temporal_set_scene_cut.argtypes = [vp, C.c_double]
+        L.ss4k_upscaler_temporal_scene_cut.argtypes = [vp, C.POINTER(C.c_double)]
+        L.ss4k_upscaler_temporal_scene_cut_stats.argtypes = [vp, C.POINTER(SceneCutStats), vp]
+        L.ss4k_upscaler_temporal_scene_cut_total.argtypes = [vp, C.POINTER(C.c_uint64)]
+    if hasattr(L, "ss4k_dev_op_bsvd_online_shift_cuts"):   # dev library only
+        L.ss4k_dev_op_bsvd_online_shift_cuts.argtypes = [vp, vp, vp, i, i, i, i, sz, i, i, i, i, i, vp, C.c_uint, i, vp]
+        L.ss4k_dev_op_bsvd_noise_planes.argtypes = [vp, vp, i, sz, vp, i, C.c_float, C.c_float, vp]
     if hasattr(L, "ss4k_dev_op_bsvd_online_shift"):   # dev library only
         ip, szp = C.POINTER(i), C.POINTER(sz)
         L.ss4k_dev_op_bsvd_online_shift.argtypes = [vp, vp, vp, i, i, i, i, sz, i, i, i, i, i, vp]
@@ -732,17 +746,26 @@ class BsvdOnline:
         self._rc(self._L.ss4k_bsvd_online_state_bytes(self._h, C.byref(b)))
         return int(b.value)
 
-    def push(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def push(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, cuts: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``x`` (n, 4, h, w), 1 <= n <= max_push -> the (k, 3, h, w) frames that became ready, oldest first (k = 0 while the lag fills).
-        ``out``: a caller-owned contiguous float32 device tensor to write into (its leading dimension is the capacity in frames)."""
+        ``out``: a caller-owned contiguous float32 device tensor to write into (its leading dimension is the capacity in frames).
+        ``cuts``: an (n,) int32 / uint32 device tensor, element i != 0: frame i is the first of a new scene (ss4k_bsvd_online_push_cuts) -
+        the stream is then the concatenation of its scenes run as streams of their own; k is what it is without cuts."""
         assert x.ndim == 4 and x.shape[1] == 4, f"expected (n, 4, h, w), got {tuple(x.shape)}"
         x = x.to(device=self.ctx.device, dtype=torch.float32).contiguous()
         n, _, h, w = x.shape
         if out is None:
             out = torch.empty((n, 3, h, w), dtype=torch.float32, device=x.device)
         k = C.c_int()
+        if cuts is not None:
+            if not (cuts.is_cuda and cuts.ndim == 1 and cuts.shape[0] == n and cuts.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+                raise ValueError(f"cuts must be an ({n},) int32 / uint32 device tensor")
+            cuts = cuts.contiguous()
         with torch.cuda.device(self.ctx.device):
-            self._rc(self._L.ss4k_bsvd_online_push(self._h, x.data_ptr(), n, h, w, out.data_ptr(), out.shape[0], C.byref(k), _stream()))
+            if cuts is not None:
+                self._rc(self._L.ss4k_bsvd_online_push_cuts(self._h, x.data_ptr(), cuts.data_ptr(), n, h, w, out.data_ptr(), out.shape[0], C.byref(k), _stream()))
+            else:
+                self._rc(self._L.ss4k_bsvd_online_push(self._h, x.data_ptr(), n, h, w, out.data_ptr(), out.shape[0], C.byref(k), _stream()))
         self._shape = (h, w)
         return out[:k.value]
 
@@ -767,7 +790,8 @@ class TemporalUpscaler:
     ``Model`` built with ``bsvd_stream=True`` (or a ``BsvdOnline``'s ``.model``).  A call returns the frames that became ready: none during
     the first 16 frames of a stream, as many as went in after."""
 
-    def __init__(self, ctx: Context, sr: Model, denoise: Model, lr_shape, output_shape=None, denoise_rate: float = 1.0, max_push: int = 4):
+    def __init__(self, ctx: Context, sr: Model, denoise: Model, lr_shape, output_shape=None, denoise_rate: float = 1.0, max_push: int = 4,
+                 scene_cut: Optional[float] = None):
         self.ctx, self.sr, self.denoise, self.max_push = ctx, sr, denoise, int(max_push)
         cfg = UpscaleCfg()
         cfg.lr_h, cfg.lr_w = int(lr_shape[0]), int(lr_shape[1])
@@ -778,11 +802,43 @@ class TemporalUpscaler:
         h = C.c_void_p()
         _check(lib().ss4k_upscaler_temporal_create(ctx._h, C.byref(cfg), sr._h, denoise._h, self.max_push, C.byref(h)))
         self._h, self.cfg, self.lag = h, cfg, 16
+        if scene_cut is not None:
+            try:
+                self.set_scene_cut(scene_cut)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None):
             lib().ss4k_upscaler_temporal_destroy(self._h)
             self._h = None
+
+    def set_scene_cut(self, threshold: float) -> None:
+        """Scene-cut detection in front of every job (include/ss4k.h): ``threshold`` is the mean absolute byte difference between consecutive
+        input frames, in (0, 255]; 0 turns it off (the default).  A cut keeps the two scenes apart inside the denoiser, on the device: the
+        output is that of the scenes run as separate streams, and every job still returns the frames it returns without the detector."""
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_upscaler_temporal_set_scene_cut(self._h, float(threshold)))
+
+    def scene_cut(self) -> float:
+        t = C.c_double()
+        _check(lib().ss4k_upscaler_temporal_scene_cut(self._h, C.byref(t)))
+        return float(t.value)
+
+    def scene_cut_stats(self) -> dict:
+        """The stream's counters and its last frame's values: compared, cuts, last_sad, last_score, last_was_cut.  Synchronises."""
+        s = SceneCutStats()
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_upscaler_temporal_scene_cut_stats(self._h, C.byref(s), _stream()))
+        return {"compared": int(s.compared), "cuts": int(s.cuts), "last_sad": int(s.last_sad), "last_score": int(s.last_score),
+                "last_was_cut": int(s.last_was_cut)}
+
+    def scene_cut_total(self) -> int:
+        """Cuts in the jobs that have completed on the device; never synchronises."""
+        n = C.c_uint64()
+        _check(lib().ss4k_upscaler_temporal_scene_cut_total(self._h, C.byref(n)))
+        return int(n.value)
 
     def __del__(self):
         try:

@@ -1,5 +1,5 @@
 // C ABI of the online BSVD machine and of the service chain around it (include/ss4k.h: ss4k_bsvd_online_*, ss4k_upscaler_temporal_*),
-// and - dev library only - the machine's two kernels on caller buffers
+// scene cuts included, and - dev library only - the machine's kernels on caller buffers
 // (include/ss4k_dev.h: ss4k_dev_op_bsvd_online_*).
 #include "api_guard.h"
 #include "bsvd_online.h"
@@ -25,6 +25,14 @@ int ss4k_bsvd_online_push(ss4k_bsvd_online* o, const float* in, int n, int h, in
     SS4K_REQUIRE(o && n_out, "ss4k_bsvd_online_push: NULL argument");
     SS4K_HIP(hipSetDevice(o->o.ctx->device));
     *n_out = o->o.push(in, n, h, w, out, cap, (hipStream_t)stream);
+  });
+}
+int ss4k_bsvd_online_push_cuts(ss4k_bsvd_online* o, const float* in, const uint32_t* cuts, int n, int h, int w, float* out, size_t cap, int* n_out,
+                               void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(o && n_out, "ss4k_bsvd_online_push_cuts: NULL argument");
+    SS4K_HIP(hipSetDevice(o->o.ctx->device));
+    *n_out = o->o.push(in, n, h, w, out, cap, (hipStream_t)stream, cuts);
   });
 }
 int ss4k_bsvd_online_flush(ss4k_bsvd_online* o, float* out, size_t cap, int* n_out, void* stream) {
@@ -86,7 +94,65 @@ int ss4k_upscaler_temporal_state_bytes(const ss4k_upscaler_temporal* up, size_t*
   return SS4K_OK;
 }
 
+int ss4k_upscaler_temporal_set_scene_cut(ss4k_upscaler_temporal* up, double threshold) {
+  return guard([&] {
+    SS4K_REQUIRE(up, "ss4k_upscaler_temporal_set_scene_cut: NULL argument");
+    SS4K_HIP(hipSetDevice(up->t.up.ctx->device));
+    up->t.set_scene_cut(threshold);
+  });
+}
+int ss4k_upscaler_temporal_scene_cut(const ss4k_upscaler_temporal* up, double* threshold) {
+  return guard([&] {
+    SS4K_REQUIRE(up && threshold, "ss4k_upscaler_temporal_scene_cut: NULL argument");
+    *threshold = up->t.cut ? up->t.cut->threshold : 0.0;
+  });
+}
+int ss4k_upscaler_temporal_scene_cut_stats(ss4k_upscaler_temporal* up, ss4k_scene_cut_stats* out, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(up && out, "ss4k_upscaler_temporal_scene_cut_stats: NULL argument");
+    cut::SlotState s{};
+    const TemporalCut* c = up->t.cut.get();
+    if (c && c->on() && !c->fresh) {
+      SS4K_HIP(hipSetDevice(up->t.up.ctx->device));
+      SS4K_HIP(hipMemcpyAsync(&s, c->state.ptr, sizeof(s), hipMemcpyDeviceToHost, (hipStream_t)stream));
+      SS4K_HIP(hipStreamSynchronize((hipStream_t)stream));
+    }
 #ifdef SS4K_DEV
+    SS4K_REQUIRE(!c || c->zones_intact(), "ss4k_upscaler_temporal_scene_cut_stats: a red zone around the pinned stats block was written");
+#endif
+    out->compared = s.compared; out->cuts = s.cuts; out->last_sad = s.last_sad; out->last_score = s.last_score;
+    out->last_was_cut = s.last_was_cut; out->reserved = 0;
+  });
+}
+int ss4k_upscaler_temporal_scene_cut_total(const ss4k_upscaler_temporal* up, uint64_t* cuts) {
+  return guard([&] {
+    SS4K_REQUIRE(up && cuts, "ss4k_upscaler_temporal_scene_cut_total: NULL argument");
+    uint64_t n = 0;
+    if (up->t.cut && up->t.cut->host) {
+      const volatile cut::SlotState* h = up->t.cut->host;   // (written by the device's copies: read once, no synchronisation)
+      n = h->cuts;
+    }
+    *cuts = n;
+  });
+}
+
+#ifdef SS4K_DEV
+int ss4k_dev_op_bsvd_online_shift_cuts(ss4k_ctx* c, const void* in, void* out, int nplanes, int in_frames, int slot0, int frames, size_t frame_px,
+                                       int slots_per_record, int ch_per_plane, int fold, int first_has_prev, int n_next, const uint32_t* flag_ring,
+                                       unsigned ring_mask, int f0, void* s) {
+  return guard([&] {
+    SS4K_REQUIRE(c, "ss4k_dev_op_bsvd_online_shift_cuts: NULL context");
+    op_bsvd_online_shift_cuts(in, out, nplanes, in_frames, slot0, frames, frame_px, slots_per_record, ch_per_plane, fold, first_has_prev, n_next,
+                              flag_ring, ring_mask, f0, (hipStream_t)s);
+  });
+}
+int ss4k_dev_op_bsvd_noise_planes(ss4k_ctx* c, float* frames4, int n, size_t plane_px, const uint32_t* flags, int stream_first, float level_start,
+                                  float level, void* s) {
+  return guard([&] {
+    SS4K_REQUIRE(c, "ss4k_dev_op_bsvd_noise_planes: NULL context");
+    op_bsvd_noise_planes(frames4, n, plane_px, flags, stream_first, level_start, level, (hipStream_t)s);
+  });
+}
 int ss4k_dev_op_bsvd_online_shift(ss4k_ctx* c, const void* in, void* out, int nplanes, int in_frames, int slot0, int frames, size_t frame_px,
                                   int slots_per_record, int ch_per_plane, int fold, int first_has_prev, int n_next, void* s) {
   return guard([&] {

@@ -9,7 +9,7 @@ using namespace bsvd_online;
 void BsvdOnline::create(ss4k_ctx* c, Model* m, int max_push_) {
   SS4K_REQUIRE(c && m, "bsvd online: NULL argument");
   SS4K_REQUIRE(m->desc.kind == SS4K_BSVD && m->desc.bsvd_stream == 1, "bsvd online: the model must be BSVD built with bsvd_stream = 1");
-  SS4K_REQUIRE(max_push_ >= 1 && max_push_ <= 64, "bsvd online: max_push must be in 1..64");
+  SS4K_REQUIRE(max_push_ >= 1 && max_push_ <= BSVD_ONLINE_MAX_PUSH, "bsvd online: max_push must be in 1..64");
   ctx = c; net = m; max_push = max_push_;
 }
 
@@ -34,7 +34,7 @@ size_t BsvdOnline::frame_bytes(int c) const {
 size_t BsvdOnline::state_bytes() const {
   size_t t = 0;
   for (auto& blk : carried) for (auto& pr : blk) for (auto& b : pr) t += b.bytes;
-  return t;
+  return t + flag_ring.bytes;
 }
 size_t BsvdOnline::state_bytes_for(int hh, int ww) const {
   size_t t = 0;
@@ -53,7 +53,18 @@ void BsvdOnline::ensure_state() {
       for (int k = 0; k < 2; ++k) carried[b][c][k].ensure((size_t)planes_of(b, c) * cap_frames(c) * frame_bytes(c));
 }
 
-int BsvdOnline::push(const float* in, int n, int hh, int ww, float* out, size_t out_capacity_frames, hipStream_t st) {
+// the flags of stream frames first .. first + n - 1 into the ring (NULL: zeros), in at most two pieces where the run wraps
+void BsvdOnline::ring_write(const uint32_t* cuts_dev, int first, int n, hipStream_t st) {
+  uint32_t* ring = flag_ring.as<uint32_t>();
+  for (int done = 0; done < n;) {
+    const int at = (first + done) & (BSVD_ONLINE_CUT_RING - 1), k = std::min(n - done, BSVD_ONLINE_CUT_RING - at);
+    if (cuts_dev) SS4K_HIP(hipMemcpyAsync(ring + at, cuts_dev + done, (size_t)k * 4, hipMemcpyDeviceToDevice, st));
+    else SS4K_HIP(hipMemsetAsync(ring + at, 0, (size_t)k * 4, st));
+    done += k;
+  }
+}
+
+int BsvdOnline::push(const float* in, int n, int hh, int ww, float* out, size_t out_capacity_frames, hipStream_t st, const uint32_t* cuts_dev) {
   // every refusal before the first launch and before any state or counter changes
   SS4K_REQUIRE(net, "bsvd online: not created");
   SS4K_REQUIRE(in && out, "bsvd online push: NULL argument");
@@ -63,13 +74,21 @@ int BsvdOnline::push(const float* in, int n, int hh, int ww, float* out, size_t 
   SS4K_REQUIRE((double)(LAG / 2 + max_push) * hh * ww < 2147483648.0, "bsvd online push: a carried plane holds at most 2^31 pixels");
   const Plan p = make_plan(state, n, false);
   SS4K_REQUIRE(out_capacity_frames >= (size_t)p.emitted, "bsvd online push: output capacity below the frames that become ready");
-  const bool first = h == 0;
+  SS4K_REQUIRE(!cuts_dev || ((uintptr_t)cuts_dev & 3) == 0, "bsvd online push: the cut flags are 32-bit words");
+  const bool first = h == 0, cuts_before = cuts_live;
   h = hh; w = ww;
   try {
     ensure_state();
+    if (cuts_dev && !cuts_live) {   // the stream's first flags: from here on it runs the cut-aware shift
+      flag_ring.ensure((size_t)BSVD_ONLINE_CUT_RING * 4);
+      SS4K_HIP(hipMemsetAsync(flag_ring.ptr, 0, (size_t)BSVD_ONLINE_CUT_RING * 4, st));
+      cuts_live = true;
+    }
+    if (cuts_live) ring_write(cuts_dev, state.pushed, n, st);   // (a push without flags still retires the slots of frames 128 back)
     run(p, in, out, st);
   } catch (...) {
     if (first) { h = w = 0; }
+    cuts_live = cuts_before;
     throw;
   }
   state = p.after;
@@ -130,8 +149,12 @@ void BsvdOnline::run(const Plan& p, const float* in, float* out, hipStream_t st)
       const Tens centre = at(b, src, wo.lo);
       const int n_next = std::max(0, std::min(N, wi.hi - 1 - wo.lo));   // output frames whose t + 1 the input holds
       SS4K_REQUIRE(n_next == N || p.flushing, "internal: a BiBufferConv would run ahead of its input");
-      op_bsvd_online_shift(carried[b][src][cur[b][src]].ptr, S.p, lead, cap_frames(src), p.slot_of(b, src, wo.lo), N, (size_t)H * W, rec / 16,
-                           m.cw(), c / 8, wo.lo > 0 ? 1 : 0, n_next, st);
+      if (cuts_live)
+        op_bsvd_online_shift_cuts(carried[b][src][cur[b][src]].ptr, S.p, lead, cap_frames(src), p.slot_of(b, src, wo.lo), N, (size_t)H * W, rec / 16,
+                                  m.cw(), c / 8, wo.lo > 0 ? 1 : 0, n_next, flag_ring.as<uint32_t>(), BSVD_ONLINE_CUT_RING - 1, wo.lo, st);
+      else
+        op_bsvd_online_shift(carried[b][src][cur[b][src]].ptr, S.p, lead, cap_frames(src), p.slot_of(b, src, wo.lo), N, (size_t)H * W, rec / 16,
+                             m.cw(), c / 8, wo.lo > 0 ? 1 : 0, n_next, st);
       const Tens rest{centre.p, centre.plane_bytes, lead};
       m.conv(l0 + MEM_LAYER[k - 1], S, m.planes_for(c) > lead ? &rest : nullptr, N, H, W, relu6(outT), st);
     };

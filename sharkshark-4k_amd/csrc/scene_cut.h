@@ -32,6 +32,12 @@ struct ClearItems { void* lr[MAX_ITEMS]; void* hr[MAX_ITEMS]; };
 void sad_items(const SadItems& it, unsigned long long* acc, int n, size_t bytes, bool store, hipStream_t st);
 // one thread per item: the rule on acc[i] and state[slot[i]] -> flags[i] (1 = cut), the slot's S_prev / counters / last values, acc[i] = 0
 void decide(const DecideItems& it, unsigned long long* acc, SlotState* state, uint32_t* flags, int n, hipStream_t st);
+// The rule over a RUN of n consecutive frames of one stream (the temporal BSVD service: a job's frames), one thread walking them in order
+// because frame i's score needs frame i - 1's sum: acc[i] = sum |frame i - frame i - 1| (acc[0]: against the previous job's last frame;
+// not read unless compare_first).  Writes ring[(pos + i) & mask] = 1 where frame i starts a scene, else 0; updates state[0] (S_prev, the
+// counters, the last values); acc[0..n) = 0.  mask = 2^k - 1 >= n - 1.
+void decide_run(unsigned long long* acc, SlotState* state, uint32_t* ring, unsigned pos, unsigned mask, int n, bool compare_first,
+                unsigned long long T, hipStream_t st);
 // lr[i] (lr_bytes) and hr[i] (hr_bytes) become zero for every item with flags[i] != 0; an item that was not compared may hold NULLs (its flag is 0).
 // Sizes are multiples of 4, pointers of compared items 16-byte aligned
 void clear_items(const ClearItems& it, unsigned long long compare, const uint32_t* flags, int n, size_t lr_bytes, size_t hr_bytes, hipStream_t st);

@@ -1,7 +1,9 @@
 // Scene-cut detection kernels (scene_cut.h), gfx950.  Three launches per round whatever its size, in stream order: cut::sad_items sums
 // |frame - prev| per item into a u64 and writes the frame over prev in the same pass, cut::decide applies the rule per item, cut::clear_items
 // zero-fills the recurrent state of the items it flagged.  Integer sums: exact, and independent of the order the workgroups arrive in.
+// cut::decide_run is the rule for the temporal BSVD service (upscaler_temporal.cpp): the n frames of a job are ONE stream's consecutive frames.
 #include "scene_cut.h"
+#include "glue.h"
 
 #define SS4K_LAUNCH_OK() SS4K_HIP(hipGetLastError())
 
@@ -107,6 +109,39 @@ void decide(const DecideItems& it, unsigned long long* acc, SlotState* state, ui
   SS4K_REQUIRE(acc && state && flags && it.T >= 1, "scene cut (decide): NULL argument or a threshold of 0");
   for (int i = 0; i < n; ++i) SS4K_REQUIRE(it.slot[i] >= 0 && it.slot[i] < MAX_ITEMS, "scene cut (decide): slot");
   hipLaunchKernelGGL(k_decide, dim3(1), dim3(64), 0, st, it, acc, state, flags, n);
+  SS4K_LAUNCH_OK();
+}
+
+// ONE thread: the n sums of a run of consecutive frames of one stream depend on each other through S_prev, so they are walked in order
+__global__ __launch_bounds__(64) void k_decide_run(unsigned long long* __restrict__ acc, SlotState* __restrict__ state, uint32_t* __restrict__ ring,
+                                                   unsigned pos, unsigned mask, int n, int compare_first, unsigned long long T) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  SlotState s = state[0];
+  for (int i = 0; i < n; ++i) {
+    uint32_t is_cut = 0;
+    if (i > 0 || compare_first) {
+      const unsigned long long S = acc[i], d = S > s.s_prev ? S - s.s_prev : s.s_prev - S, score = S < d ? S : d;
+      is_cut = score >= T ? 1u : 0u;
+      s.s_prev = S; s.compared += 1; s.cuts += is_cut;
+      s.last_sad = S; s.last_score = score;
+    } else {   // no comparison: the next one starts from S_prev = 0
+      s.s_prev = 0; s.last_sad = 0; s.last_score = 0;
+    }
+    s.last_was_cut = (int32_t)is_cut;
+    ring[(pos + (unsigned)i) & mask] = is_cut;
+    acc[i] = 0;
+  }
+  s.reserved = 0;
+  state[0] = s;
+}
+
+void decide_run(unsigned long long* acc, SlotState* state, uint32_t* ring, unsigned pos, unsigned mask, int n, bool compare_first,
+                unsigned long long T, hipStream_t st) {
+  SS4K_REQUIRE(n >= 1 && n <= MAX_ITEMS, "scene cut (decide_run): 1..64 frames");
+  SS4K_REQUIRE(acc && state && ring && T >= 1, "scene cut (decide_run): NULL argument or a threshold of 0");
+  SS4K_REQUIRE((mask & (mask + 1u)) == 0 && mask != 0xffffffffu && (unsigned)n <= mask + 1u, "scene cut (decide_run): the ring mask must be 2^k - 1 and hold the run");
+  SS4K_GLUE_ROUTE("cut::decide_run");
+  hipLaunchKernelGGL(k_decide_run, dim3(1), dim3(64), 0, st, acc, state, ring, pos, mask, n, compare_first ? 1 : 0, T);
   SS4K_LAUNCH_OK();
 }
 

@@ -61,6 +61,15 @@ from .upscaler_base import BaseUpscalerService, UpscalerQueueEntry, answer, reco
 LR_LEVELS = [(360, 640), (540, 960), (630, 1120), (720, 1280), (900, 1600), (1080, 1920)]
 
 
+def validate_scene_cut(scene_cut, denoise_temporal: bool) -> Optional[float]:
+    """The ``scene_cut`` keyword of ``HipUpscalerService``: None stays None; a number needs ``denoise_temporal`` and lies in [0, 255]."""
+    from .egvsr_upscaler import check_scene_cut
+    t = check_scene_cut(scene_cut)
+    if t is not None and not denoise_temporal:
+        raise ValueError("scene_cut belongs to denoise_temporal=True: the per-frame denoiser joins no frames, a cut has nothing to keep apart")
+    return t
+
+
 def under_profiler() -> bool:
     """A profiler has loaded itself into this process (rocprofv3 sets ROCP_TOOL_LIBRARIES and preloads librocprofiler-sdk): counter
     collection serialises kernels, so every "do these two streams run side by side?" measurement fails - the library skips its lane check
@@ -101,7 +110,7 @@ class HipUpscalerService(BaseUpscalerService):
                  scale=4, model_name=None, dtype="f16", weights=None, checkpoint_dir: Optional[str] = None,
                  lr_shape=None, single_mode=None, seed=0, model_flags=0, fsrcnn_dtype="f32",
                  group: Optional[sharding.GroupSpec] = None, overlap_jobs=True, overlap_sets=3, overlap_max_frames=1,
-                 denoise_temporal=False, temporal_max_push=None):
+                 denoise_temporal=False, temporal_max_push=None, scene_cut=None):
         # None (the stream pipeline's default: "the compiled backend", pipeline.py:23,41-44) and False (the image server: "eager",
         # image_pipeline.py:58-61) both mean "whatever this build runs the network with" to a caller that cannot know about 'hip';
         # so does a backend of the REFERENCE asked for by name ('trt', 't2trt', 'jit', 'ds': realesrgan/factory.py:175-230, fsrcnn/factory.py:17-69 -
@@ -153,6 +162,9 @@ class HipUpscalerService(BaseUpscalerService):
                 raise ValueError("denoise_temporal=True on a node of several workers: frames are sharded round-robin there, a temporal stream "
                                  "needs all of its frames on one worker")
         self.temporal_max_push = int(temporal_max_push) if temporal_max_push else max(4, int(batch_size))
+        # scene_cut: the temporal stream's scene-cut threshold (_capi.TemporalUpscaler.set_scene_cut), the mean absolute byte difference
+        # between consecutive input frames in (0, 255]; None or 0: off.  Cuts are found and acted on on the device; jobs return what they return without
+        self.scene_cut = validate_scene_cut(scene_cut, self.denoise_temporal)
         self._t_emitted = 0          # frames of the running stream returned so far = the stream index of the next frame to come back
         self._t_first = 0            # ... of the first frame the LAST upscale() / flush() returned
         super().__init__()
@@ -506,7 +518,7 @@ class HipUpscalerService(BaseUpscalerService):
         if getattr(self, "denoise_temporal", False) and (js["up"] is None or key != js["key"]):
             # (a new geometry starts a new stream: what the old object still held is dropped with it)
             js["up"] = _capi.TemporalUpscaler(js["ctx"], js["model"], js["denoise"], self.lr_shape, self.output_shape, self.denoise_rate,
-                                              self.temporal_max_push)
+                                              self.temporal_max_push, scene_cut=getattr(self, "scene_cut", None))
             js["key"] = key
             self._t_emitted = self._t_first = 0
         if js["up"] is None or key != js["key"]:
@@ -547,6 +559,9 @@ class HipUpscalerService(BaseUpscalerService):
             parts = [up(frames[i:i + m]) for i in range(0, frames.shape[0], m)]
             out = parts[0] if len(parts) == 1 else torch.cat(parts)
             self._t_first, self._t_emitted = self._t_emitted, self._t_emitted + int(out.shape[0])
+            prof = getattr(self, "profiler", None)
+            if prof is not None and getattr(self, "scene_cut", None):
+                prof.set("fsrcnn.scene_cuts", up.scene_cut_total())   # (the cuts of the jobs that have completed: never synchronises)
             return out
         out = up(frames)
         prof = getattr(self, "profiler", None)

@@ -9,8 +9,10 @@ Each form is timed with events around ``--iters`` calls after ``--warmup``, the 
 holds every run's ms per frame, the spread between runs, the online state's bytes and the launches per push of the two online kernels
 (dev library only: run with ``SS4K_LIB=.../libss4k_hip_dev.so``).  ``--service``: instead, frames/s of
 ``HipUpscalerService`` (FSRCNN x2 behind the denoiser, jobs of ``--push`` frames) with ``denoise_temporal`` on and off.
+``--scene-cut T``: a fourth form, ``online_cuts`` - the same pushes with a flag word per frame (all zero: the cut-aware shift and the ring
+copy, no cut) - and with ``--service`` a third service, ``temporal_cuts``, whose detector (threshold T) reads every input byte once.
 
-Usage:  python tools/bsvd_online_time.py [--h 720 --w 1280 --dtype f16 --variant bsvd-32 --push 4 --iters 20 --runs 2] [--out FILE]
+Usage:  python tools/bsvd_online_time.py [--h 720 --w 1280 --dtype f16 --variant bsvd-32 --push 4 --iters 20 --runs 2] [--scene-cut T] [--out FILE]
 """
 import argparse
 import json
@@ -42,9 +44,14 @@ def service(a):
     """Frames/s through ``HipUpscalerService.upscale`` (in-process worker body, resident frames, FSRCNN x2 behind the denoiser)."""
     from sharkshark4k_amd.upscale.hip_upscaler import HipUpscalerService
     frames = torch.randint(0, 256, (a.push, a.h, a.w, 3), dtype=torch.uint8, device="cuda")
+    if a.scene_cut:   # one scene: a base image plus +-2 levels of noise per frame, so that the detector reads every byte and fires nowhere
+        base = torch.randint(2, 254, (1, a.h, a.w, 3), dtype=torch.int16, device="cuda")
+        frames = (base + torch.randint(-2, 3, (a.push, a.h, a.w, 3), dtype=torch.int16, device="cuda")).to(torch.uint8)
     res = {}
-    svcs = {k: HipUpscalerService(denoising=True, denoise_temporal=k == "temporal", temporal_max_push=a.push, upscaler_model="fsrcnn", scale=2,
-                                  lr_shape=(a.h, a.w), dtype=a.dtype, fsrcnn_dtype="f16", weights="synthetic") for k in ("per_frame", "temporal")}
+    kinds = ("per_frame", "temporal") + (("temporal_cuts",) if a.scene_cut else ())
+    svcs = {k: HipUpscalerService(denoising=True, denoise_temporal=k != "per_frame", temporal_max_push=a.push, upscaler_model="fsrcnn", scale=2,
+                                  lr_shape=(a.h, a.w), dtype=a.dtype, fsrcnn_dtype="f16", weights="synthetic",
+                                  scene_cut=a.scene_cut if k == "temporal_cuts" else None) for k in kinds}
     for s in svcs.values():
         s.output_shape = None
         s.proc_init()
@@ -57,6 +64,10 @@ def service(a):
     line = {"tool": "bsvd_online_time --service", "h": a.h, "w": a.w, "dtype": a.dtype, "job_frames": a.push, "sr": "fsrcnn x2 (fp16 mode)",
             "frames_per_s": {k: [round(v, 1) for v in vs] for k, vs in res.items()},
             "temporal_over_per_frame": round(max(res["temporal"]) / max(res["per_frame"]), 4)}
+    if a.scene_cut:
+        line["scene_cut"] = a.scene_cut
+        line["temporal_cuts_over_temporal"] = round(max(res["temporal_cuts"]) / max(res["temporal"]), 4)
+        line["detector_bytes_read_per_frame"] = 2 * 3 * a.h * a.w   # the frame and its predecessor, once each
     print(json.dumps(line), flush=True)
     if a.out:
         with open(a.out, "a") as f:
@@ -72,6 +83,7 @@ def main():
     ap.add_argument("--push", type=int, default=4); ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=8); ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--scene-cut", type=float, default=0.0, help="also time the cut-aware path (with --service: the detector at this threshold)")
     ap.add_argument("--service", action="store_true", help="instead: frames/s of HipUpscalerService (FSRCNN x2, 4-frame jobs) with denoise_temporal on and off")
     a = ap.parse_args()
     if a.service:
@@ -84,6 +96,10 @@ def main():
     x[:, 3] = 0.05
     out = torch.empty(n, 3, a.h, a.w, device="cuda")
     forms = {"online": lambda: on.push(x, out=out), "clip": lambda: on.model(x, out=out), "per_frame": lambda: per(x, out=out)}
+    if a.scene_cut:   # a second executor on the same model: its stream carries flags (all zero), so it runs the cut-aware shift
+        on_cuts = _capi.BsvdOnline(on.model, n)
+        zeros = torch.zeros(n, dtype=torch.int32, device="cuda")
+        forms["online_cuts"] = lambda: on_cuts.push(x, out=out, cuts=zeros)
     for _ in range(max(a.warmup, 16 // n + 2)):   # past the lag (and past the frame lanes' tuning calls of the two forwards)
         for f in forms.values():
             f()
@@ -99,11 +115,18 @@ def main():
             "online_over_clip": round(min(res["online"]) / min(res["clip"]), 4),
             "online_over_per_frame": round(min(res["online"]) / min(res["per_frame"]), 4),
             "state_bytes": on.state_bytes(), "workspace_bytes_clip": on.model.workspace_bytes(n, a.h, a.w)}
+    if a.scene_cut:
+        line["online_cuts_over_online"] = round(min(res["online_cuts"]) / min(res["online"]), 4)
     if hasattr(_capi.lib(), "ss4k_dev_glue_routes_read"):   # dev library: launches of the two online kernels in one steady-state push
         _capi.lib().ss4k_dev_glue_routes_reset()
         on.push(x, out=out)
         torch.cuda.synchronize()
         line["routes_per_push"] = {k: v for k, v in _capi.glue_routes(_capi.lib()).items() if k.startswith("bsvdo::")}
+        if a.scene_cut:
+            _capi.lib().ss4k_dev_glue_routes_reset()
+            forms["online_cuts"]()
+            torch.cuda.synchronize()
+            line["routes_per_push_cuts"] = {k: v for k, v in _capi.glue_routes(_capi.lib()).items() if k.startswith("bsvdo::")}
     print(json.dumps(line), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
