@@ -445,6 +445,37 @@ int ss4k_upscaler_temporal_set_scene_cut(ss4k_upscaler_temporal* up, double thre
 int ss4k_upscaler_temporal_scene_cut(const ss4k_upscaler_temporal* up, double* threshold);
 int ss4k_upscaler_temporal_scene_cut_stats(ss4k_upscaler_temporal* up, ss4k_scene_cut_stats* out, void* hip_stream);   /* synchronises */
 int ss4k_upscaler_temporal_scene_cut_total(const ss4k_upscaler_temporal* up, uint64_t* cuts);   /* never synchronises */
+/* Several streams on one object.  _create_streams makes max_streams (1..64) SLOTS; a slot owns one stream's denoiser state, its ring of waiting LR
+ * planes, its counters and its scene-cut detector, and allocates them with its first push.  The SR model, the glue and the job buffers are
+ * shared.  _create means max_streams = 1, and every call above is slot 0 and launches what it launched before there were slots;
+ * _set_scene_cut applies to every slot, _scene_cut_total sums over them, _state_bytes sums the slots in use.
+ * A ROUND takes k_frames (1..64) frames of one (h, w), frame i of slot slots[i] at frames_dev[i] - HOST arrays; each frame is uint8 HWC at any
+ * byte address, read where it lies.  Frames of one slot enter in the order they appear, at most max_push per slot.  The slots of the round become
+ * ITEMS in order of first appearance: *n_items of them, item t being slot item_slots[t] with n_out_per_item[t] frames ready (both arrays hold
+ * k_frames entries; the counts are known on the host without a synchronisation).  out receives the ready frames contiguously, item after item,
+ * oldest first within an item.  Every stream's bytes are those of the same frames through a one-stream object.  The round's frames that became
+ * ready share the SR forward, in chunks of at most max_push frames.  Refusals (SS4K_EINVAL: k_frames outside 1..64, a slot outside
+ * 0..max_streams-1, more than max_push frames of one slot, a NULL frame, an output capacity below the ready frames) are decided for the whole
+ * round before the first launch and change nothing, and so does a failed allocation of the round's buffers, the slots' rings or detectors (all
+ * made before the first launch).  A round that fails after its first launch - a HIP error, or the allocation of a denoiser's state inside a
+ * slot's first push - resets every slot it named. */
+int ss4k_upscaler_temporal_create_streams(ss4k_ctx* ctx, const ss4k_upscale_cfg* cfg, ss4k_model* sr, ss4k_model* bsvd_stream_model, int max_push,
+                                          int max_streams, ss4k_upscaler_temporal** out);
+int ss4k_upscale_round_temporal(ss4k_upscaler_temporal* up, const uint8_t* const* frames_dev, const int* slots, int k_frames, int h, int w,
+                                uint8_t* out_dev, size_t out_capacity_bytes, int* n_out_per_item, int* item_slots, int* n_items, void* hip_stream);
+int ss4k_upscaler_temporal_flush_stream(ss4k_upscaler_temporal* up, int slot, uint8_t* out_nhwc_dev, size_t out_capacity_bytes, int* n_out,
+                                        void* hip_stream);
+int ss4k_upscaler_temporal_reset_stream(ss4k_upscaler_temporal* up, int slot);
+int ss4k_upscaler_temporal_pending_stream(const ss4k_upscaler_temporal* up, int slot, int* frames);
+int ss4k_upscaler_temporal_scene_cut_stats_stream(ss4k_upscaler_temporal* up, int slot, ss4k_scene_cut_stats* out, void* hip_stream);
+/* what ONE slot will hold once its stream runs: the denoiser's state plus the ring, before any push.  Not counted: what scene cuts add to a slot
+ * (the 512-byte flag ring, which _state_bytes counts once a stream carries flags, the stored frame of 3 h w bytes, which it counts too, and the
+ * detector's sums, flags and counters - under 1 KiB and a pinned host block of 176 bytes -, which it does not) */
+int ss4k_upscaler_temporal_stream_state_bytes_for(const ss4k_upscaler_temporal* up, size_t* bytes);
+/* frees the device memory of every slot with no running stream (never pushed, flushed or reset): the denoiser's state, the flag ring, the LR ring
+ * and the detector's device buffers - that slot's cut counters start over, as after _set_scene_cut(0), and _scene_cut_total no longer holds
+ * them; the threshold stays.  Such a slot allocates again with its next push. */
+int ss4k_upscaler_temporal_release_idle(ss4k_upscaler_temporal* up);
 
 /* ---- measurement hooks (bench.py: live per-kernel timing with HIP events on the launch stream) */
 /* When enabled, every launch of the dominant conv kernel is bracketed with hipEvents on the

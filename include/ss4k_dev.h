@@ -96,6 +96,12 @@ int ss4k_dev_op_bsvd_noise_planes(ss4k_ctx* ctx, float* frames4, int n, size_t p
  * slots per frame.  SS4K_EINVAL where src[i] and dst[i] overlap or the move leaves either buffer. */
 int ss4k_dev_op_bsvd_online_carry(ss4k_ctx* ctx, int entries, const void* const* src, void* const* dst, const int* nplanes, const int* src_frames,
                                   const int* dst_frames, const int* src_first, const int* count, const size_t* frame_slots, void* hip_stream);
+/* ---- the kernel of a temporal round (csrc/temporal_round.hip) on caller buffers; routes "tround::gather_planes<3>" / "<4>".  src: k (1..64) HOST
+ * entries, frame j's three fp32 planes (3 * plane_px floats, 16-byte aligned) -> dst (k, planes, plane_px) fp32, 16-byte aligned.  planes == 4:
+ * plane 3 of frame j is level_start where bit j of start_bits is set or *flags[j] != 0 (flags: NULL, or k HOST entries of DEVICE words, each
+ * may be NULL), level otherwise.  SS4K_EINVAL: k outside 1..64, planes not 3 or 4, a NULL or misaligned pointer, a source inside dst. */
+int ss4k_dev_op_temporal_gather(ss4k_ctx* ctx, const float* const* src, const uint32_t* const* flags, int k, size_t plane_px, int planes,
+                                uint64_t start_bits, float level_start, float level, float* dst, void* hip_stream);
 
 /* ---- launchers of the frame-recurrent upscaler's glue (csrc/frvsr.hip, csrc/frvsr.h) that the public API reaches only inside a whole
  * step or round: what tests/test_gpu_frvsr_glue_budget.py bounds against float64.  Same conventions as above; their routes are reported
@@ -207,6 +213,9 @@ int ss4k_dev_guard_poison(ss4k_ctx* ctx, ss4k_model* model, ss4k_upscaler* upsca
 /* ... the same for the frame-recurrent upscaler (include/ss4k.h, ss4k_frvsr_*; each may be NULL): the executor's activations, flow buffers
  * and tap, the service path's staging buffers.  The recurrent state (lr_prev / hr_prev) is NOT transient: the next frame is entitled to it. */
 int ss4k_dev_guard_poison_frvsr(ss4k_frvsr* m, ss4k_frvsr_upscaler* up, int* buffers, size_t* bytes, size_t* bytes_256);
+/* ... and for a temporal upscaler (ss4k_upscaler_temporal_*): the chain's intermediates and the job buffers its slots share (the packed denoiser
+ * input, the denoised frames, the gathered LR planes, the blend).  What a slot owns - the denoiser's state, the ring, the detector - is state. */
+int ss4k_dev_guard_poison_temporal(ss4k_upscaler_temporal* up, int* buffers, size_t* bytes, size_t* bytes_256);
 /* Positive control without a fault: allocates a guarded buffer, writes one byte at payload - 1 and one at payload + need with hipMemset
  * (both inside the allocation), requires the check to report exactly those two zones with those offsets, releases the buffer and clears
  * the sticky list.  SS4K_EINVAL with a text if the guard does not see them (or if damage was already on record: run it first). */

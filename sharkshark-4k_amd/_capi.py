@@ -46,6 +46,10 @@ SYMBOLS = [
     "ss4k_bsvd_online_push_cuts",
     "ss4k_upscaler_temporal_set_scene_cut", "ss4k_upscaler_temporal_scene_cut", "ss4k_upscaler_temporal_scene_cut_stats",
     "ss4k_upscaler_temporal_scene_cut_total",
+    # several streams on one temporal upscaler: slots and rounds
+    "ss4k_upscaler_temporal_create_streams", "ss4k_upscale_round_temporal", "ss4k_upscaler_temporal_flush_stream",
+    "ss4k_upscaler_temporal_reset_stream", "ss4k_upscaler_temporal_pending_stream", "ss4k_upscaler_temporal_scene_cut_stats_stream",
+    "ss4k_upscaler_temporal_stream_state_bytes_for", "ss4k_upscaler_temporal_release_idle",
 ]
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
@@ -70,13 +74,15 @@ DEV_SYMBOLS = [
     # the tail of a TecoGAN generator alone, and the host-side embedding of its transposed layers (tests/test_gpu_tecogan_tail.py)
     "ss4k_dev_frvsr_tail_taps", "ss4k_dev_frvsr_embed_convt", "ss4k_dev_frvsr_pack_convt",
     # guard mode: red zones and 0xFF poison for every device buffer of the library (tests/test_gpu_memory_hygiene.py)
-    "ss4k_dev_guard_enable", "ss4k_dev_guard_check", "ss4k_dev_guard_poison", "ss4k_dev_guard_selftest", "ss4k_dev_guard_poison_frvsr",
+    "ss4k_dev_guard_enable", "ss4k_dev_guard_check", "ss4k_dev_guard_poison", "ss4k_dev_guard_selftest", "ss4k_dev_guard_poison_frvsr", "ss4k_dev_guard_poison_temporal",
     # stream ordering: a bounded delay on any stream; the frame lanes' handicap, counters and dropped-join control (tests/test_gpu_lane_order.py)
     "ss4k_dev_op_spin", "ss4k_dev_lane_handicap", "ss4k_dev_lane_counts", "ss4k_dev_lane_counts_reset", "ss4k_dev_lane_drop_join",
     # the kernels of csrc/bsvd_online.hip on caller buffers (tests/test_gpu_bsvd_online.py)
     "ss4k_dev_op_bsvd_online_shift", "ss4k_dev_op_bsvd_online_carry",
     # ... and the scene-cut builds (tests/test_gpu_bsvd_cuts.py)
     "ss4k_dev_op_bsvd_online_shift_cuts", "ss4k_dev_op_bsvd_noise_planes",
+    # the kernel of a temporal round (tests/test_gpu_temporal_streams_kernel.py)
+    "ss4k_dev_op_temporal_gather",
 ]
 
 
@@ -216,6 +222,8 @@ def load(path: str) -> C.CDLL:
         L.ss4k_dev_guard_selftest.argtypes = [vp]
         if hasattr(L, "ss4k_dev_guard_poison_frvsr"):
             L.ss4k_dev_guard_poison_frvsr.argtypes = [vp, vp, C.POINTER(i), C.POINTER(sz), C.POINTER(sz)]
+        if hasattr(L, "ss4k_dev_guard_poison_temporal"):
+            L.ss4k_dev_guard_poison_temporal.argtypes = [vp, C.POINTER(i), C.POINTER(sz), C.POINTER(sz)]
     if hasattr(L, "ss4k_dev_lane_counts"):  # dev library only: stream ordering
         i64p = C.POINTER(C.c_int64)
         L.ss4k_dev_op_spin.argtypes = [vp, C.c_uint, vp]
@@ -296,6 +304,18 @@ def load(path: str) -> C.CDLL:
         L.ss4k_upscaler_temporal_scene_cut.argtypes = [vp, C.POINTER(C.c_double)]
         L.ss4k_upscaler_temporal_scene_cut_stats.argtypes = [vp, C.POINTER(SceneCutStats), vp]
         L.ss4k_upscaler_temporal_scene_cut_total.argtypes = [vp, C.POINTER(C.c_uint64)]
+    if hasattr(L, "ss4k_upscale_round_temporal"):
+        ip = C.POINTER(i)
+        L.ss4k_upscaler_temporal_create_streams.argtypes = [vp, C.POINTER(UpscaleCfg), vp, vp, i, i, C.POINTER(vp)]
+        L.ss4k_upscale_round_temporal.argtypes = [vp, C.POINTER(vp), ip, i, i, i, vp, sz, ip, ip, ip, vp]
+        L.ss4k_upscaler_temporal_flush_stream.argtypes = [vp, i, vp, sz, ip, vp]
+        L.ss4k_upscaler_temporal_reset_stream.argtypes = [vp, i]
+        L.ss4k_upscaler_temporal_pending_stream.argtypes = [vp, i, ip]
+        L.ss4k_upscaler_temporal_scene_cut_stats_stream.argtypes = [vp, i, C.POINTER(SceneCutStats), vp]
+        L.ss4k_upscaler_temporal_stream_state_bytes_for.argtypes = [vp, C.POINTER(sz)]
+        L.ss4k_upscaler_temporal_release_idle.argtypes = [vp]
+    if hasattr(L, "ss4k_dev_op_temporal_gather"):   # dev library only
+        L.ss4k_dev_op_temporal_gather.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, sz, i, C.c_uint64, C.c_float, C.c_float, vp, vp]
     if hasattr(L, "ss4k_dev_op_bsvd_online_shift_cuts"):   # dev library only
         L.ss4k_dev_op_bsvd_online_shift_cuts.argtypes = [vp, vp, vp, i, i, i, i, sz, i, i, i, i, i, vp, C.c_uint, i, vp]
         L.ss4k_dev_op_bsvd_noise_planes.argtypes = [vp, vp, i, sz, vp, i, C.c_float, C.c_float, vp]
@@ -363,6 +383,14 @@ def guard_poison_frvsr(model=None, upscaler=None, L: Optional[C.CDLL] = None) ->
     h = [getattr(o, "_h", o) for o in (model, upscaler)]
     n, b, b256 = C.c_int(), C.c_size_t(), C.c_size_t()
     _guard_rc(L, L.ss4k_dev_guard_poison_frvsr(*h, C.byref(n), C.byref(b), C.byref(b256)))
+    return n.value, int(b.value), int(b256.value)
+
+
+def guard_poison_temporal(upscaler, L: Optional[C.CDLL] = None) -> Tuple[int, int, int]:
+    """``guard_poison`` for a ``TemporalUpscaler``: the chain's intermediates and the job buffers its slots share; every slot's state is left alone."""
+    L = _guard_lib(L)
+    n, b, b256 = C.c_int(), C.c_size_t(), C.c_size_t()
+    _guard_rc(L, L.ss4k_dev_guard_poison_temporal(getattr(upscaler, "_h", upscaler), C.byref(n), C.byref(b), C.byref(b256)))
     return n.value, int(b.value), int(b256.value)
 
 
@@ -791,8 +819,8 @@ class TemporalUpscaler:
     the first 16 frames of a stream, as many as went in after."""
 
     def __init__(self, ctx: Context, sr: Model, denoise: Model, lr_shape, output_shape=None, denoise_rate: float = 1.0, max_push: int = 4,
-                 scene_cut: Optional[float] = None):
-        self.ctx, self.sr, self.denoise, self.max_push = ctx, sr, denoise, int(max_push)
+                 scene_cut: Optional[float] = None, max_streams: int = 1):
+        self.ctx, self.sr, self.denoise, self.max_push, self.max_streams = ctx, sr, denoise, int(max_push), int(max_streams)
         cfg = UpscaleCfg()
         cfg.lr_h, cfg.lr_w = int(lr_shape[0]), int(lr_shape[1])
         cfg.out_h, cfg.out_w = (0, 0) if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
@@ -800,7 +828,10 @@ class TemporalUpscaler:
         cfg.sr_is_realesrgan = int(sr.in_channels == 3)
         cfg.denoising, cfg.denoise_rate = 1, float(denoise_rate)
         h = C.c_void_p()
-        _check(lib().ss4k_upscaler_temporal_create(ctx._h, C.byref(cfg), sr._h, denoise._h, self.max_push, C.byref(h)))
+        if self.max_streams == 1:
+            _check(lib().ss4k_upscaler_temporal_create(ctx._h, C.byref(cfg), sr._h, denoise._h, self.max_push, C.byref(h)))
+        else:   # several streams on this object: slots, served in rounds (``round``)
+            _check(lib().ss4k_upscaler_temporal_create_streams(ctx._h, C.byref(cfg), sr._h, denoise._h, self.max_push, self.max_streams, C.byref(h)))
         self._h, self.cfg, self.lag = h, cfg, 16
         if scene_cut is not None:
             try:
@@ -826,11 +857,14 @@ class TemporalUpscaler:
         _check(lib().ss4k_upscaler_temporal_scene_cut(self._h, C.byref(t)))
         return float(t.value)
 
-    def scene_cut_stats(self) -> dict:
-        """The stream's counters and its last frame's values: compared, cuts, last_sad, last_score, last_was_cut.  Synchronises."""
+    def scene_cut_stats(self, slot: int = 0) -> dict:
+        """The counters of a slot's stream and its last frame's values: compared, cuts, last_sad, last_score, last_was_cut.  Synchronises."""
         s = SceneCutStats()
         with torch.cuda.device(self.ctx.device):
-            _check(lib().ss4k_upscaler_temporal_scene_cut_stats(self._h, C.byref(s), _stream()))
+            if slot == 0:
+                _check(lib().ss4k_upscaler_temporal_scene_cut_stats(self._h, C.byref(s), _stream()))
+            else:
+                _check(lib().ss4k_upscaler_temporal_scene_cut_stats_stream(self._h, int(slot), C.byref(s), _stream()))
         return {"compared": int(s.compared), "cuts": int(s.cuts), "last_sad": int(s.last_sad), "last_score": int(s.last_score),
                 "last_was_cut": int(s.last_was_cut)}
 
@@ -873,17 +907,65 @@ class TemporalUpscaler:
             _check(lib().ss4k_upscale_frames_temporal(self._h, frames.data_ptr(), n, h, w, out.data_ptr(), out.numel(), C.byref(k), _stream()))
         return out[:k.value]
 
-    def flush(self) -> torch.Tensor:
-        left = self.pending
+    def flush(self, slot: int = 0) -> torch.Tensor:
+        """The frames still inside a slot's stream, oldest first; the stream ends and the slot is free for another."""
+        left = self.pending if slot == 0 else self.pending_of(slot)
         oh, ow = self.out_shape()
         out = torch.empty((left, oh, ow, 3), dtype=torch.uint8, device=self.ctx.device)
         k = C.c_int()
         with torch.cuda.device(self.ctx.device):
-            _check(lib().ss4k_upscaler_temporal_flush(self._h, out.data_ptr() if left else None, out.numel(), C.byref(k), _stream()))
+            if slot == 0:
+                _check(lib().ss4k_upscaler_temporal_flush(self._h, out.data_ptr() if left else None, out.numel(), C.byref(k), _stream()))
+            else:
+                _check(lib().ss4k_upscaler_temporal_flush_stream(self._h, int(slot), out.data_ptr() if left else None, out.numel(), C.byref(k), _stream()))
         return out[:k.value]
 
-    def reset(self) -> None:
-        _check(lib().ss4k_upscaler_temporal_reset(self._h))
+    def reset(self, slot: int = 0) -> None:
+        if slot == 0:
+            _check(lib().ss4k_upscaler_temporal_reset(self._h))
+        else:
+            _check(lib().ss4k_upscaler_temporal_reset_stream(self._h, int(slot)))
+
+    def pending_of(self, slot: int) -> int:
+        """Frames of a slot's stream that went in and have not come back."""
+        k = C.c_int()
+        _check(lib().ss4k_upscaler_temporal_pending_stream(self._h, int(slot), C.byref(k)))
+        return k.value
+
+    def stream_state_bytes_for(self) -> int:
+        """Device bytes one slot holds while its stream runs (the denoiser's state and the ring of waiting LR planes): known before any push."""
+        b = C.c_size_t()
+        _check(lib().ss4k_upscaler_temporal_stream_state_bytes_for(self._h, C.byref(b)))
+        return int(b.value)
+
+    def release_idle(self) -> None:
+        """Frees the state of every slot without a running stream; ``state_bytes`` drops by their share."""
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_upscaler_temporal_release_idle(self._h))
+
+    def round(self, frames, slots):
+        """One round (ss4k_upscale_round_temporal): ``frames`` is a list of (h, w, 3) uint8 device tensors or views, each with contiguous bytes at
+        any byte address; frame i belongs to slot ``slots[i]``.  Frames of a slot enter in list order, at most ``max_push`` per slot and 64 in all.
+        Returns ``(out, [(slot, count), ...])``: the frames that became ready, contiguous, slot after slot in order of first appearance and oldest
+        first within a slot.  The counts are known without a synchronisation."""
+        k = len(frames)
+        if k != len(slots):
+            raise ValueError(f"{k} frames and {len(slots)} slots")
+        for f in frames:
+            if not (isinstance(f, torch.Tensor) and f.is_cuda and f.dtype == torch.uint8 and f.ndim == 3 and f.shape[-1] == 3 and f.is_contiguous()):
+                raise ValueError("a round takes (h, w, 3) uint8 device tensors whose bytes are contiguous")
+        h, w = (int(frames[0].shape[0]), int(frames[0].shape[1])) if k else (1, 1)
+        if any(tuple(f.shape) != (h, w, 3) for f in frames):
+            raise ValueError("the frames of a round have one size")
+        oh, ow = self.out_shape(h, w)
+        out = torch.empty((max(k, 1), oh, ow, 3), dtype=torch.uint8, device=self.ctx.device)
+        ptrs = (C.c_void_p * max(k, 1))(*[f.data_ptr() for f in frames])
+        ids = (C.c_int * max(k, 1))(*[int(s) for s in slots])
+        counts, item_slots, n_items = (C.c_int * max(k, 1))(), (C.c_int * max(k, 1))(), C.c_int()
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_upscale_round_temporal(self._h, ptrs, ids, k, h, w, out.data_ptr(), out.numel(), counts, item_slots, C.byref(n_items), _stream()))
+        items = [(int(item_slots[t]), int(counts[t])) for t in range(n_items.value)]
+        return out[:sum(c for _, c in items)], items
 
 
 FRVSR_MAX_STREAMS = 64   # SS4K_FRVSR_MAX_STREAMS (include/ss4k.h)

@@ -76,16 +76,16 @@ int ss4k_upscaler_temporal_flush(ss4k_upscaler_temporal* up, uint8_t* out, size_
   return guard([&] {
     SS4K_REQUIRE(up && n_out, "ss4k_upscaler_temporal_flush: NULL argument");
     SS4K_HIP(hipSetDevice(up->t.up.ctx->device));
-    *n_out = up->t.flush(out, cap, (hipStream_t)stream);
+    *n_out = up->t.flush(0, out, cap, (hipStream_t)stream);
   });
 }
-int ss4k_upscaler_temporal_reset(ss4k_upscaler_temporal* up) { if (!up) return SS4K_EINVAL; up->t.reset(); return SS4K_OK; }
+int ss4k_upscaler_temporal_reset(ss4k_upscaler_temporal* up) { if (!up) return SS4K_EINVAL; up->t.reset(0); return SS4K_OK; }
 int ss4k_upscaler_temporal_out_shape(const ss4k_upscaler_temporal* up, int h, int w, int* oh, int* ow) {
   return guard([&] { SS4K_REQUIRE(up && oh && ow, "NULL argument"); up->t.up.out_shape(h, w, oh, ow); });
 }
 int ss4k_upscaler_temporal_pending(const ss4k_upscaler_temporal* up, int* frames) {
   if (!up || !frames) return SS4K_EINVAL;
-  *frames = up->t.on.pending();
+  *frames = up->t.slot(0).on.pending();
   return SS4K_OK;
 }
 int ss4k_upscaler_temporal_state_bytes(const ss4k_upscaler_temporal* up, size_t* bytes) {
@@ -104,37 +104,110 @@ int ss4k_upscaler_temporal_set_scene_cut(ss4k_upscaler_temporal* up, double thre
 int ss4k_upscaler_temporal_scene_cut(const ss4k_upscaler_temporal* up, double* threshold) {
   return guard([&] {
     SS4K_REQUIRE(up && threshold, "ss4k_upscaler_temporal_scene_cut: NULL argument");
-    *threshold = up->t.cut ? up->t.cut->threshold : 0.0;
+    *threshold = up->t.cut_threshold;
   });
+}
+static void cut_stats_of(ss4k_upscaler_temporal* up, int slot, ss4k_scene_cut_stats* out, void* stream) {
+  cut::SlotState s{};
+  const TemporalCut* c = up->t.slot(slot).cut.get();
+  if (c && c->on() && !c->fresh) {
+    SS4K_HIP(hipSetDevice(up->t.up.ctx->device));
+    SS4K_HIP(hipMemcpyAsync(&s, c->state.ptr, sizeof(s), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    SS4K_HIP(hipStreamSynchronize((hipStream_t)stream));
+  }
+#ifdef SS4K_DEV
+  SS4K_REQUIRE(!c || c->zones_intact(), "ss4k_upscaler_temporal_scene_cut_stats: a red zone around the pinned stats block was written");
+#endif
+  out->compared = s.compared; out->cuts = s.cuts; out->last_sad = s.last_sad; out->last_score = s.last_score;
+  out->last_was_cut = s.last_was_cut; out->reserved = 0;
 }
 int ss4k_upscaler_temporal_scene_cut_stats(ss4k_upscaler_temporal* up, ss4k_scene_cut_stats* out, void* stream) {
   return guard([&] {
     SS4K_REQUIRE(up && out, "ss4k_upscaler_temporal_scene_cut_stats: NULL argument");
-    cut::SlotState s{};
-    const TemporalCut* c = up->t.cut.get();
-    if (c && c->on() && !c->fresh) {
-      SS4K_HIP(hipSetDevice(up->t.up.ctx->device));
-      SS4K_HIP(hipMemcpyAsync(&s, c->state.ptr, sizeof(s), hipMemcpyDeviceToHost, (hipStream_t)stream));
-      SS4K_HIP(hipStreamSynchronize((hipStream_t)stream));
-    }
-#ifdef SS4K_DEV
-    SS4K_REQUIRE(!c || c->zones_intact(), "ss4k_upscaler_temporal_scene_cut_stats: a red zone around the pinned stats block was written");
-#endif
-    out->compared = s.compared; out->cuts = s.cuts; out->last_sad = s.last_sad; out->last_score = s.last_score;
-    out->last_was_cut = s.last_was_cut; out->reserved = 0;
+    cut_stats_of(up, 0, out, stream);
+  });
+}
+int ss4k_upscaler_temporal_scene_cut_stats_stream(ss4k_upscaler_temporal* up, int slot, ss4k_scene_cut_stats* out, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(up && out, "ss4k_upscaler_temporal_scene_cut_stats_stream: NULL argument");
+    cut_stats_of(up, slot, out, stream);
   });
 }
 int ss4k_upscaler_temporal_scene_cut_total(const ss4k_upscaler_temporal* up, uint64_t* cuts) {
   return guard([&] {
     SS4K_REQUIRE(up && cuts, "ss4k_upscaler_temporal_scene_cut_total: NULL argument");
     uint64_t n = 0;
-    if (up->t.cut && up->t.cut->host) {
-      const volatile cut::SlotState* h = up->t.cut->host;   // (written by the device's copies: read once, no synchronisation)
-      n = h->cuts;
+    for (const auto& s : up->t.slots) {
+      if (!(s->cut && s->cut->host)) continue;
+      const volatile cut::SlotState* h = s->cut->host;   // (written by the device's copies: read once, no synchronisation)
+      n += h->cuts;
     }
     *cuts = n;
   });
 }
+
+// ---- several streams on one object: slots and rounds (upscaler_temporal.h, temporal_round_plan.h)
+int ss4k_upscaler_temporal_create_streams(ss4k_ctx* ctx, const ss4k_upscale_cfg* cfg, ss4k_model* sr, ss4k_model* bsvd_stream_model, int max_push,
+                                          int max_streams, ss4k_upscaler_temporal** out) {
+  return guard([&] {
+    SS4K_REQUIRE(ctx && cfg && sr && bsvd_stream_model && out, "ss4k_upscaler_temporal_create_streams: NULL argument");
+    SS4K_HIP(hipSetDevice(ctx->device));
+    auto u = std::make_unique<ss4k_upscaler_temporal>();
+    u->t.create(ctx, *cfg, &sr->m, &bsvd_stream_model->m, max_push, max_streams);
+    *out = u.release();
+  });
+}
+int ss4k_upscale_round_temporal(ss4k_upscaler_temporal* up, const uint8_t* const* frames_dev, const int* slots, int k_frames, int h, int w,
+                                uint8_t* out_dev, size_t out_capacity_bytes, int* n_out_per_item, int* item_slots, int* n_items, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(up, "ss4k_upscale_round_temporal: NULL argument");
+    SS4K_HIP(hipSetDevice(up->t.up.ctx->device));
+    (void)up->t.round(frames_dev, slots, k_frames, h, w, out_dev, out_capacity_bytes, n_out_per_item, item_slots, n_items, (hipStream_t)stream);
+  });
+}
+int ss4k_upscaler_temporal_flush_stream(ss4k_upscaler_temporal* up, int slot, uint8_t* out, size_t cap, int* n_out, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(up && n_out, "ss4k_upscaler_temporal_flush_stream: NULL argument");
+    SS4K_HIP(hipSetDevice(up->t.up.ctx->device));
+    (void)up->t.slot(slot);   // (a slot outside the object: refused before anything else)
+    *n_out = up->t.flush(slot, out, cap, (hipStream_t)stream);
+  });
+}
+int ss4k_upscaler_temporal_reset_stream(ss4k_upscaler_temporal* up, int slot) {
+  return guard([&] { SS4K_REQUIRE(up, "ss4k_upscaler_temporal_reset_stream: NULL argument"); up->t.reset(slot); });
+}
+int ss4k_upscaler_temporal_pending_stream(const ss4k_upscaler_temporal* up, int slot, int* frames) {
+  return guard([&] {
+    SS4K_REQUIRE(up && frames, "ss4k_upscaler_temporal_pending_stream: NULL argument");
+    *frames = up->t.slot(slot).on.pending();
+  });
+}
+int ss4k_upscaler_temporal_stream_state_bytes_for(const ss4k_upscaler_temporal* up, size_t* bytes) {
+  return guard([&] {
+    SS4K_REQUIRE(up && bytes, "ss4k_upscaler_temporal_stream_state_bytes_for: NULL argument");
+    *bytes = up->t.stream_state_bytes_for();
+  });
+}
+int ss4k_upscaler_temporal_release_idle(ss4k_upscaler_temporal* up) {
+  return guard([&] {
+    SS4K_REQUIRE(up, "ss4k_upscaler_temporal_release_idle: NULL argument");
+    SS4K_HIP(hipSetDevice(up->t.up.ctx->device));
+    up->t.release_idle();
+  });
+}
+
+#ifdef SS4K_DEV
+int ss4k_dev_op_temporal_gather(ss4k_ctx* c, const float* const* src, const uint32_t* const* flags, int k, size_t plane_px, int planes,
+                                uint64_t start_bits, float level_start, float level, float* dst, void* s) {
+  return guard([&] {
+    SS4K_REQUIRE(c && src, "ss4k_dev_op_temporal_gather: NULL argument");
+    SS4K_REQUIRE(k >= 1 && k <= TROUND_MAX_FRAMES, "ss4k_dev_op_temporal_gather: 1..64 frames");
+    TroundTable tab{};
+    for (int j = 0; j < k; ++j) { tab.src[j] = src[j]; tab.flag[j] = flags ? flags[j] : nullptr; }
+    op_tround_gather(tab, dst, k, plane_px, planes, (unsigned long long)start_bits, level_start, level, (hipStream_t)s);
+  });
+}
+#endif
 
 #ifdef SS4K_DEV
 int ss4k_dev_op_bsvd_online_shift_cuts(ss4k_ctx* c, const void* in, void* out, int nplanes, int in_frames, int slot0, int frames, size_t frame_px,

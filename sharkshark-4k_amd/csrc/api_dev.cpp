@@ -5,6 +5,7 @@
 #include "frvsr.h"
 #include "host_tables.h"
 #include "upscaler.h"
+#include "upscaler_temporal.h"
 #include <mutex>
 #include <type_traits>
 
@@ -355,6 +356,16 @@ int ss4k_dev_guard_poison_frvsr(ss4k_frvsr* m, ss4k_frvsr_upscaler* up, int* buf
       for (DevBuf* b : {&m->f.flow_raw, &m->f.flow, &m->f.tap_s2d}) poison_one(*b, buffers, bytes, bytes_256);
     }
     if (up) for (DevBuf* b : {&up->u.img, &up->u.hrc, &up->u.outf}) poison_one(*b, buffers, bytes, bytes_256);
+    SS4K_HIP(hipDeviceSynchronize());
+  });
+}
+int ss4k_dev_guard_poison_temporal(ss4k_upscaler_temporal* up, int* buffers, size_t* bytes, size_t* bytes_256) {
+  return guard([&] {
+    SS4K_REQUIRE(up && buffers && bytes && bytes_256, "ss4k_dev_guard_poison_temporal: NULL argument");
+    *buffers = 0; *bytes = 0; *bytes_256 = 0;
+    SS4K_HIP(hipDeviceSynchronize());
+    up->t.up.for_each_job_buf([&](DevBuf& b) { poison_one(b, buffers, bytes, bytes_256); });
+    for (DevBuf* b : {&up->t.lr4, &up->t.den, &up->t.den_flush, &up->t.lrk, &up->t.blend}) poison_one(*b, buffers, bytes, bytes_256);
     SS4K_HIP(hipDeviceSynchronize());
   });
 }

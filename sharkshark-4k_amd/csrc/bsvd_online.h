@@ -71,6 +71,12 @@ struct BsvdOnline {
   size_t state_bytes_for(int hh, int ww) const;
   // (the ring counts as zero again: the next stream's first push with flags zero-fills it on its stream before it writes into it)
   void reset() { state = bsvd_online::State{}; h = w = 0; cuts_live = false; }
+  // reset() and the memory back: the next stream's first push allocates again (a temporal upscaler's idle slot)
+  void release_state() {
+    reset();
+    for (auto& blk : carried) for (auto& pr : blk) for (auto& b : pr) b.release();
+    flag_ring.release();
+  }
   // in (n, 4, h, w) fp32 NCHW -> the frames that became ready, oldest first, (k, 3, h, w) fp32 NCHW; returns k.
   // cuts_dev: n device words read in stream order (an earlier kernel on st may have produced them), word i != 0: frame i of the push is the
   // first of a new scene; NULL: no cut in this push.  A flag on the stream's first frame has no effect.

@@ -2,15 +2,17 @@
 #pragma once
 #include "bsvd_online.h"
 #include "scene_cut.h"
+#include "temporal_round_plan.h"
 #include "upscaler.h"
 #include <memory>
+#include <vector>
 
 namespace ss4k {
 
-// Scene cuts for the temporal stream (include/ss4k.h: ss4k_upscaler_temporal_set_scene_cut): the rule of scene_cut.h on the job's input bytes,
+// Scene cuts for a temporal stream (include/ss4k.h: ss4k_upscaler_temporal_set_scene_cut): the rule of scene_cut.h on the job's input bytes,
 // frame i against frame i - 1 of the job and frame 0 against a device copy of the previous job's last frame.  The flags never leave the
 // device: BsvdOnline::push copies them into its ring, and the host learns about cuts only when it asks.  Created by the first
-// set_scene_cut(threshold > 0); every device buffer is a DevBuf, so guard mode sees it.
+// set_scene_cut(threshold > 0); every device buffer is a DevBuf, so guard mode sees it.  One per stream slot, nothing shared.
 struct TemporalCut {
   double threshold = 0;        // mean absolute byte difference in 8-bit levels, (0, 255]; 0 = off
   DevBuf prev;                 // the previous job's last frame, uint8 HWC as it arrived: 3hw bytes
@@ -28,31 +30,63 @@ struct TemporalCut {
   bool on() const { return threshold > 0; }
   void set(double t);
   void forget() { have = false; }   // reset / flush: the next frame is a stream's first
+  void reserve(size_t frame_bytes);   // the device buffers a job of such frames needs; detect / detect_at start with it
+  void release_device();              // every device buffer goes and the counters start over (set(0), an idle slot's release); the threshold stays
   // the sums, cut::decide_run, the refresh of prev and of the pinned block; returns the job's n flag words (device)
   const uint32_t* detect(const uint8_t* in, int n, int hh, int ww, hipStream_t st);
+  // ... the job's frames named one by one (a round's item: each frame lies where the caller has it, at any byte address)
+  const uint32_t* detect_at(const uint8_t* const* fr, int n, int hh, int ww, hipStream_t st);
+};
+
+// ---- the kernel of a round (temporal_round.hip) -----------------------------------------------------------------------------------------------
+// Frame j of a launch: its three LR planes at src[j] (3 * plane_px fp32, contiguous, 16-byte aligned - a slot of its stream's ring), and the device
+// word that says whether it starts a scene (NULL: it does not).  BY VALUE in the kernel arguments, as FrvsrPtrs (1 KiB): no device table.
+constexpr int TROUND_MAX_FRAMES = temporal_round::MAX_FRAMES;
+struct TroundTable { const float* src[TROUND_MAX_FRAMES]; const uint32_t* flag[TROUND_MAX_FRAMES]; };
+// dst (k, planes, plane_px) fp32: planes 0..2 of frame j from src[j]; with planes == 4, plane 3 is level_start where bit j of start_bits is set or
+// *flag[j] != 0, and level otherwise - the bits of bsvdo::noise_planes / the one-stream path's fill.  One launch, one thread per 16-byte slot.
+void op_tround_gather(const TroundTable& tab, float* dst, int k, size_t plane_px, int planes, unsigned long long start_bits, float level_start,
+                      float level, hipStream_t st);
+
+// what one stream owns; allocated by its first push
+struct TemporalSlot {
+  BsvdOnline on;
+  DevBuf ring;          // lr_before of the frames inside the denoiser: (lag + max_push) frames of (3, lr_h, lr_w) fp32, frame i in slot i % frames
+  bool first_frame = true;
+  std::unique_ptr<TemporalCut> cut;   // null until a threshold > 0 reaches the slot
+  long long pushed = 0, emitted = 0;   // frames of the running stream
+  bool running() const { return on.state.pushed > 0; }
 };
 
 struct TemporalUpscaler {
   Upscaler up;          // the chain's glue, taps and SR model; its per-frame denoiser path is not used
-  BsvdOnline on;
-  DevBuf ring;          // lr_before of the frames inside the denoiser: (lag + max_push) frames of (3, lr_h, lr_w) fp32, frame i in slot i % frames
-  DevBuf lr4, den, den_flush, lrk, blend;
-  bool first_frame = true;
-  std::unique_ptr<TemporalCut> cut;   // null until the first set_scene_cut(threshold > 0)
-  long long pushed = 0, emitted = 0;   // frames of the running stream
+  std::vector<std::unique_ptr<TemporalSlot>> slots;   // max_streams of them; the one-stream entry points are slot 0
+  DevBuf lr4, den, den_flush, lrk, blend;             // job buffers, shared: the pushes of a round run one after the other
+  double cut_threshold = 0;                           // what set_scene_cut last said; a slot's detector is made when the slot first needs it
+  int max_push = 0;
 
-  void create(ss4k_ctx* c, const ss4k_upscale_cfg& cfg, Model* sr, Model* bsvd_stream_model, int max_push);
-  int ring_frames() const { return on.lag() + on.max_push; }
-  // n frames (n, h, w, 3) in -> the k frames that became ready, (k, oh, ow, 3), oldest first; returns k
+  void create(ss4k_ctx* c, const ss4k_upscale_cfg& cfg, Model* sr, Model* bsvd_stream_model, int max_push, int max_streams = 1);
+  int max_streams() const { return (int)slots.size(); }
+  int ring_frames() const { return bsvd_online::LAG + max_push; }
+  TemporalSlot& slot(int s);
+  const TemporalSlot& slot(int s) const;
+  // n frames (n, h, w, 3) in -> the k frames that became ready, (k, oh, ow, 3), oldest first; returns k.  Slot 0.
   int frames(const uint8_t* in, int n, int h, int w, uint8_t* out, size_t out_capacity_bytes, hipStream_t st);
-  // the frames still inside; ends the stream
-  int flush(uint8_t* out, size_t out_capacity_bytes, hipStream_t st);
-  void reset();
-  size_t state_bytes() const;
-  void set_scene_cut(double threshold);
+  // A round (temporal_round_plan.h): k frames, frame i of slot slot_ids[i], each read where it lies.  The ready frames leave contiguously, item
+  // after item; n_out_per_item / item_slots (k entries each) and *n_items describe them.  Returns their number.
+  int round(const uint8_t* const* frames, const int* slot_ids, int k, int h, int w, uint8_t* out, size_t out_capacity_bytes, int* n_out_per_item,
+            int* item_slots, int* n_items, hipStream_t st);
+  // the frames still inside a slot; ends its stream
+  int flush(int s, uint8_t* out, size_t out_capacity_bytes, hipStream_t st);
+  void reset(int s);
+  size_t state_bytes() const;              // the slots in use
+  size_t stream_state_bytes_for() const;   // what one slot will hold, before any push
+  void release_idle();                     // frees the state of slots with no running stream
+  void set_scene_cut(double threshold);    // every slot
 
  private:
-  void emit(int k, const float* denoised, uint8_t* out, hipStream_t st);
+  void emit(TemporalSlot& s, int k, const float* denoised, uint8_t* out, hipStream_t st);
+  void want_cut(TemporalSlot& s);
 };
 
 }  // namespace ss4k

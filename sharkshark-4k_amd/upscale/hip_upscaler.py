@@ -110,7 +110,7 @@ class HipUpscalerService(BaseUpscalerService):
                  scale=4, model_name=None, dtype="f16", weights=None, checkpoint_dir: Optional[str] = None,
                  lr_shape=None, single_mode=None, seed=0, model_flags=0, fsrcnn_dtype="f32",
                  group: Optional[sharding.GroupSpec] = None, overlap_jobs=True, overlap_sets=3, overlap_max_frames=1,
-                 denoise_temporal=False, temporal_max_push=None, scene_cut=None):
+                 denoise_temporal=False, temporal_max_push=None, scene_cut=None, max_streams=1):
         # None (the stream pipeline's default: "the compiled backend", pipeline.py:23,41-44) and False (the image server: "eager",
         # image_pipeline.py:58-61) both mean "whatever this build runs the network with" to a caller that cannot know about 'hip';
         # so does a backend of the REFERENCE asked for by name ('trt', 't2trt', 'jit', 'ds': realesrgan/factory.py:175-230, fsrcnn/factory.py:17-69 -
@@ -167,7 +167,22 @@ class HipUpscalerService(BaseUpscalerService):
         self.scene_cut = validate_scene_cut(scene_cut, self.denoise_temporal)
         self._t_emitted = 0          # frames of the running stream returned so far = the stream index of the next frame to come back
         self._t_first = 0            # ... of the first frame the LAST upscale() / flush() returned
+        # max_streams: stream slots of the temporal upscaler (_capi.TemporalUpscaler(max_streams=S)): ``upscale(frames, streams=ids)`` names the
+        # stream of every frame, the job runs in ROUNDS over the streams present, and what became ready comes back grouped (``last_ready``)
+        self.max_streams = int(max_streams)
+        if not 1 <= self.max_streams <= 64:
+            raise ValueError(f"max_streams={max_streams!r}: a temporal upscaler has 1..64 stream slots")
+        if self.max_streams > 1 and not self.denoise_temporal:
+            raise ValueError("max_streams belongs to denoise_temporal=True: every other job returns its own frames, whatever stream they belong to")
+        self._init_streams()
         super().__init__()
+
+    def _init_streams(self):
+        from .egvsr_upscaler import StreamSlots
+        self._tslots = StreamSlots(self.max_streams)   # which stream id sits in which slot
+        self._t_index = {}                             # stream id -> frames of it returned so far (named streams; the unnamed one: _t_emitted)
+        #: ``(stream_id, first_frame_index, count)`` per group of the frames the last ``upscale`` / ``flush`` returned, in the tensor's order
+        self.last_ready = []
 
     #: frames a temporal stream holds back (the number of BiBufferConvs: ss4k_bsvd_online_lag)
     TEMPORAL_LAG = 16
@@ -317,21 +332,31 @@ class HipUpscalerService(BaseUpscalerService):
         first frame again)."""
         if not self.denoise_temporal:
             raise RuntimeError("flush() belongs to denoise_temporal=True: every other job returns its own frames")
-        out = self._get_upscaler(0).flush()
+        up = self._get_upscaler(0)   # (first: building the object starts the slot table over)
+        if self._tslots.slot_of and self._tslots.slot_of.get(None) != 0:   # named streams came first: slot 0 is not the unnamed stream's
+            return self._temporal_job(None, [], (None,))
+        out = up.flush()
         self._t_first, self._t_emitted = self._t_emitted, 0
+        self._tslots.end(None)
+        self.last_ready = [(None, int(self._t_first), int(out.shape[0]))] if out.shape[0] else []
         return out
 
     def reset(self) -> None:
         """denoise_temporal: drop the running stream without returning what is inside."""
         if self.denoise_temporal:
-            self._get_upscaler(0).reset()
+            up = self._get_upscaler(0)
+            for slot in sorted(set(self._tslots.slot_of.values()) - {0}):   # every stream of a service with slots
+                up.reset(slot)
+            up.reset()
             self._t_first = self._t_emitted = 0
+            self._init_streams()
 
     def _tag_temporal(self, entry):
         """A result entry of a temporal stream carries the frames that became ready (possibly none) plus where they belong: the stream index
         of its first frame and the lag.  Plain ints: the entry stays picklable.  An entry type without room for them goes untagged."""
         try:
             entry.first_frame_index, entry.lag_frames = int(self._t_first), self.TEMPORAL_LAG
+            entry.ready = list(self.last_ready)   # (stream_id, first_frame_index, count) per group of entry.frames
         except AttributeError:
             pass
         f = getattr(entry, "frames", None)
@@ -344,7 +369,11 @@ class HipUpscalerService(BaseUpscalerService):
         if self.denoise_temporal:
             if isinstance(hf, HostFrames):
                 raise RuntimeError("denoise_temporal=True takes device or host TENSOR jobs: a host-ring job's result slot is sized for the job's own frames")
-            return self._tag_temporal(super().proc_job_recieved(job))
+            streams, end_streams = getattr(job, "streams", None), tuple(getattr(job, "end_streams", None) or ())
+            if streams is None and not end_streams:
+                return self._tag_temporal(super().proc_job_recieved(job))
+            entry = answer(job, *self._run_job(job, lambda: self.upscale(job.frames, streams=streams, end_streams=end_streams)))
+            return self._tag_temporal(entry)
         if not isinstance(hf, HostFrames):
             entry = super().proc_job_recieved(job)
             return self._to_host_result(entry) if self.host_results and getattr(self, "_in_worker", False) else entry
@@ -517,15 +546,117 @@ class HipUpscalerService(BaseUpscalerService):
                bool(self.lr_hr_resize), bool(self.single_mode), float(self.denoise_rate))
         if getattr(self, "denoise_temporal", False) and (js["up"] is None or key != js["key"]):
             # (a new geometry starts a new stream: what the old object still held is dropped with it)
+            more = {"max_streams": self.max_streams} if getattr(self, "max_streams", 1) > 1 else {}
             js["up"] = _capi.TemporalUpscaler(js["ctx"], js["model"], js["denoise"], self.lr_shape, self.output_shape, self.denoise_rate,
-                                              self.temporal_max_push, scene_cut=getattr(self, "scene_cut", None))
+                                              self.temporal_max_push, scene_cut=getattr(self, "scene_cut", None), **more)
             js["key"] = key
             self._t_emitted = self._t_first = 0
+            self._init_streams()
+            log(f"temporal upscaler: {getattr(self, 'max_streams', 1)} stream slot(s), {js['up'].stream_state_bytes_for() / 2**20:.1f} MiB of state per "
+                f"running stream (max_push {self.temporal_max_push})")
         if js["up"] is None or key != js["key"]:
             js["up"] = _capi.Upscaler(js["ctx"], js["model"], self.lr_shape, self.output_shape, self.lr_hr_resize,
                                       self.single_mode, js["denoise"], self.denoise_rate)
             js["key"] = key
         return js["up"]
+
+    def _temporal_rounds(self, streams):
+        """The rounds of a job: ``streams[i]`` is the stream of frame i.  Round r takes the next up-to-``temporal_max_push`` frames of every stream
+        that still has some, streams in order of first appearance, at most 64 frames in all (a stream that does not fit waits for the next
+        round).  Returns lists of frame indices."""
+        queues = {}
+        for i, sid in enumerate(streams):
+            queues.setdefault(sid, []).append(i)
+        rounds, m = [], self.temporal_max_push
+        while any(queues.values()):
+            idx = []
+            for sid, q in queues.items():
+                n = min(m, len(q), 64 - len(idx))
+                idx += q[:n]
+                del q[:n]
+            rounds.append(idx)
+        return rounds
+
+    def _temporal_job(self, frames, streams, end_streams):
+        """A job of a temporal service with stream slots: its rounds, then the flushes of ``end_streams``.  Every stream id gets its slot BEFORE the
+        first frame runs: a job that does not fit raises, has run nothing and has taken no slot."""
+        n = 0 if frames is None else int(frames.shape[0])
+        if len(streams) != n:
+            raise ValueError(f"one stream id per frame: {len(streams)} ids for {n} frames")
+        up = self._get_upscaler(0)
+        slots, taken = [], []
+        try:
+            for sid in streams:
+                slot, new = self._tslots.slot(sid)
+                if new:
+                    taken.append(sid)
+                slots.append(slot)
+        except RuntimeError:
+            for sid in taken:
+                self._tslots.end(sid)
+            raise
+        parts, ready = [], []
+
+        def came_back(sid, out):
+            k = int(out.shape[0])
+            if not k:
+                return
+            first = self._t_emitted if sid is None else self._t_index.get(sid, 0)
+            if sid is None:
+                self._t_emitted += k
+            else:
+                self._t_index[sid] = first + k
+            parts.append(out)
+            ready.append((sid, int(first), k))
+
+        try:
+            if n:
+                frames = frames.contiguous()
+                for idx in self._temporal_rounds(streams):
+                    out, items = up.round([frames[i] for i in idx], [slots[i] for i in idx])
+                    sid_of, o = {slots[i]: streams[i] for i in idx}, 0
+                    for slot, k in items:
+                        came_back(sid_of[slot], out[o:o + k])
+                        o += k
+            for sid in end_streams:
+                slot = self._tslots.slot_of.get(sid)
+                if slot is None:
+                    continue   # (an id that holds no slot: nothing inside, nothing to free)
+                came_back(sid, up.flush(slot))
+                self._tslots.end(sid)
+                if sid is None:
+                    self._t_emitted = 0
+                else:
+                    self._t_index.pop(sid, None)
+        except Exception:
+            # The library has reset the slots of the round that failed; frames of the job's other streams that came back are lost with the
+            # exception.  So every stream the job named ends here: its slot is reset and freed, its index starts over.
+            for sid in dict.fromkeys(list(streams) + list(end_streams)):
+                slot = self._tslots.end(sid)
+                if slot is None:
+                    continue
+                try:
+                    up.reset(slot)
+                except Exception:   # noqa: BLE001 - the first failure is the one to report
+                    pass
+                if sid is None:
+                    self._t_emitted = self._t_first = 0
+                else:
+                    self._t_index.pop(sid, None)
+            self.last_ready = []
+            raise
+        self.last_ready = ready
+        self._t_first = ready[0][1] if ready else 0
+        if frames is not None and frames.is_cuda and hasattr(self, "_inflight"):   # (the hold on the input: see _retire)
+            self._retire()
+            self._inflight.append((torch.cuda.current_stream(self.torch_device).record_event(), frames))
+        prof = getattr(self, "profiler", None)
+        if prof is not None and getattr(self, "scene_cut", None):
+            prof.set("fsrcnn.scene_cuts", up.scene_cut_total())
+        if parts:
+            return parts[0] if len(parts) == 1 else torch.cat(parts)
+        oh, ow = up.out_shape()
+        return torch.empty((0, oh, ow, 3), dtype=torch.uint8, device=self.torch_device)
 
     def _retire(self) -> None:
         """Let go of the input frames of jobs whose device work has finished.  A job's input is usually a tensor received over CUDA IPC; when
@@ -559,6 +690,7 @@ class HipUpscalerService(BaseUpscalerService):
             parts = [up(frames[i:i + m]) for i in range(0, frames.shape[0], m)]
             out = parts[0] if len(parts) == 1 else torch.cat(parts)
             self._t_first, self._t_emitted = self._t_emitted, self._t_emitted + int(out.shape[0])
+            self.last_ready = [(None, int(self._t_first), int(out.shape[0]))] if out.shape[0] else []
             prof = getattr(self, "profiler", None)
             if prof is not None and getattr(self, "scene_cut", None):
                 prof.set("fsrcnn.scene_cuts", up.scene_cut_total())   # (the cuts of the jobs that have completed: never synchronises)
@@ -574,10 +706,15 @@ class HipUpscalerService(BaseUpscalerService):
             record_span(prof, "fsrcnn.model", model_ms / 1000.0)
         return out
 
-    def upscale(self, frames: torch.Tensor, wait: bool = True):
+    def upscale(self, frames: torch.Tensor, wait: bool = True, streams=None, end_streams=()):
         """``wait=False`` (direct callers only): with the one-frame overlap active the result is ordered on its job set's stream, not
         on the current one - synchronise (``torch.cuda.synchronize()``) before reading it.  The default orders it on the current
-        stream like any torch op."""
+        stream like any torch op.
+        ``denoise_temporal`` with stream slots: ``streams[i]`` is the stream id of ``frames[i]`` (any hashable; None: the unnamed stream) and
+        ``end_streams`` are flushed after the job, in the order given, and give their slots back.  The result is every frame that became ready, as
+        one tensor, and ``last_ready`` says which group of it belongs where.  ``streams=None`` without ``end_streams`` is the service of one
+        stream as it was: the same calls, the same tags.  A job with ids that raises after its slots were taken ends every stream it named:
+        their slots are reset and freed and their indices start over (frames that had come back are lost with the exception)."""
         assert isinstance(frames, torch.Tensor)
         if frames.device != self.torch_device:
             if frames.is_cuda:   # a device tensor from ANOTHER GPU (the caller put job s somewhere else than on GPU s % G): one peer copy, counted
@@ -590,6 +727,15 @@ class HipUpscalerService(BaseUpscalerService):
             raise Exception(frames.shape)
         assert frames.shape[-1] == 3
         self._lag_now = 0
+        if getattr(self, "denoise_temporal", False):
+            self._get_upscaler(0)   # before any slot is taken: building the object (the first job, a new geometry) starts the slot table over
+            named = streams is not None or tuple(end_streams) != ()
+            # the unnamed stream takes a slot with its first frame, like any other; in slot 0 - always, unless named streams came first - it is
+            # served by the one-stream calls
+            if named or self._tslots.slot(None)[0] != 0:
+                return self._temporal_job(frames, [None] * frames.shape[0] if streams is None else list(streams), tuple(end_streams))
+        elif streams is not None or tuple(end_streams) != ():
+            raise ValueError("streams / end_streams belong to denoise_temporal=True")
         if not self._overlap_active():
             out = self._run(0, frames)
             if frames.is_cuda and hasattr(self, "_inflight"):   # (same hold on the input as below: see _retire)

@@ -12,7 +12,13 @@ holds every run's ms per frame, the spread between runs, the online state's byte
 ``--scene-cut T``: a fourth form, ``online_cuts`` - the same pushes with a flag word per frame (all zero: the cut-aware shift and the ring
 copy, no cut) - and with ``--service`` a third service, ``temporal_cuts``, whose detector (threshold T) reads every input byte once.
 
+``--streams S``: instead, S live streams that each bring ONE frame per round, behind ``--sr rrdbnet`` (RRDBNet x2) or ``fsrcnn`` (x2):
+(a) ``objects`` - S one-stream ``_capi.TemporalUpscaler`` served in turn, one call each (the only way before there were slots) against
+(b) ``rounds`` - one S-slot object, one ``round`` call for all S frames.  ``max_push`` is ``--push`` (1 for a live stream), 16 settle rounds,
+then ``--iters`` timed rounds per run, the two forms interleaved; frames/s, ``state_bytes`` and (dev library) the launches per round.
+
 Usage:  python tools/bsvd_online_time.py [--h 720 --w 1280 --dtype f16 --variant bsvd-32 --push 4 --iters 20 --runs 2] [--scene-cut T] [--out FILE]
+        python tools/bsvd_online_time.py --streams 4 --push 1 --sr rrdbnet --iters 64 [--out FILE]
 """
 import argparse
 import json
@@ -76,6 +82,58 @@ def service(a):
         s.proc_cleanup()
 
 
+def streams(a):
+    """S live streams, one frame per stream per round: S one-stream objects in turn against one S-slot object in rounds."""
+    ctx, S = _capi.Context(0), a.streams
+    if a.sr == "rrdbnet":
+        sr = factory.build_model_esrgan(ctx, "RealESRGAN_x2plus", weights="synthetic", dtype=a.dtype)
+    else:
+        sr = factory.build_model_fsrcnn(ctx, factor=2, weights="synthetic", dtype=a.dtype)
+    dn = factory.build_denoise_model(ctx, weights="synthetic", dtype=a.dtype, variant=a.variant, stream=True)
+    lr = (a.h, a.w)
+    objects = [_capi.TemporalUpscaler(ctx, sr, dn, lr, None, denoise_rate=1.0, max_push=a.push) for _ in range(S)]
+    slots = _capi.TemporalUpscaler(ctx, sr, dn, lr, None, denoise_rate=1.0, max_push=a.push, max_streams=S)
+    frames = torch.randint(0, 256, (S, a.h, a.w, 3), dtype=torch.uint8, device="cuda")
+    one = [frames[i:i + 1] for i in range(S)]
+    each, ids = [frames[i] for i in range(S)], list(range(S))
+    forms = {"objects": lambda: [objects[i](one[i]) for i in range(S)], "rounds": lambda: slots.round(each, ids)}
+    for _ in range(max(a.warmup, 16)):   # the settle rounds: past the lag, every round returns S frames
+        for f in forms.values():
+            f()
+    torch.cuda.synchronize()
+    assert all(o.pending == 16 for o in objects) and all(slots.pending_of(i) == 16 for i in range(S))
+    res = {k: [] for k in forms}
+    for _ in range(a.runs):
+        for k, f in forms.items():
+            res[k].append(1000.0 * S / timed(f, a.iters))
+    line = {"tool": "bsvd_online_time --streams", "h": a.h, "w": a.w, "dtype": a.dtype, "variant": a.variant, "sr": a.sr + " x2", "streams": S,
+            "max_push": a.push, "settle_rounds": max(a.warmup, 16), "timed_rounds": a.iters,
+            "frames_per_s": {k: [round(v, 2) for v in vs] for k, vs in res.items()},
+            "spread_pct": {k: round(100 * (max(vs) - min(vs)) / min(vs), 2) for k, vs in res.items()},
+            "rounds_over_objects": round(max(res["rounds"]) / max(res["objects"]), 4),
+            "state_bytes": {"objects": sum(o.state_bytes() for o in objects), "rounds": slots.state_bytes(), "per_slot": slots.stream_state_bytes_for()}}
+    # both forms have seen the same frames the same number of times: one more round of each must return the same bytes, at the size timed
+    alone, (together, items) = torch.cat(forms["objects"]()), forms["rounds"]()
+    line["outputs_equal"] = bool(items == [(i, 1) for i in range(S)] and torch.equal(alone, together))
+    if hasattr(_capi.lib(), "ss4k_dev_glue_routes_read"):   # dev library: glue launches of one steady-state round, either way
+        per_round = {}
+        for k, f in forms.items():
+            _capi.lib().ss4k_dev_glue_routes_reset()
+            f()
+            torch.cuda.synchronize()
+            routes = _capi.glue_routes(_capi.lib())
+            per_round[k] = {"glue_launches": sum(routes.values()), "tround": {r: v for r, v in routes.items() if r.startswith("tround::")},
+                            "frames_in_items": sum(v for r, v in routes.items() if r.startswith("frvsr::frames_in_items"))}
+        line["routes_per_round"] = per_round
+    print(json.dumps(line), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    for o in objects + [slots]:
+        o.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--h", type=int, default=720); ap.add_argument("--w", type=int, default=1280)
@@ -85,7 +143,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--scene-cut", type=float, default=0.0, help="also time the cut-aware path (with --service: the detector at this threshold)")
     ap.add_argument("--service", action="store_true", help="instead: frames/s of HipUpscalerService (FSRCNN x2, 4-frame jobs) with denoise_temporal on and off")
+    ap.add_argument("--streams", type=int, default=0, help="instead: S live streams, one frame each per round - S one-stream objects in turn against one S-slot object")
+    ap.add_argument("--sr", default="rrdbnet", choices=("rrdbnet", "fsrcnn"), help="the SR model behind the denoiser in --streams mode (x2)")
     a = ap.parse_args()
+    if a.streams:
+        return streams(a)
     if a.service:
         return service(a)
     ctx = _capi.Context(0)
