@@ -476,6 +476,12 @@ int ss4k_upscaler_temporal_stream_state_bytes_for(const ss4k_upscaler_temporal* 
  * and the detector's device buffers - that slot's cut counters start over, as after _set_scene_cut(0), and _scene_cut_total no longer holds
  * them; the threshold stays.  Such a slot allocates again with its next push. */
 int ss4k_upscaler_temporal_release_idle(ss4k_upscaler_temporal* up);
+/* The denoise rate of ONE slot's stream: the noise level of every frame of that slot that enters from the next push or round on is 0.1 * rate
+ * (a stream's or a scene's first frame keeps 0.05).  A slot that was never set uses cfg.denoise_rate.  The rate belongs to the stream: _reset,
+ * _reset_stream, _flush, _flush_stream and - for a slot with no running stream - _release_idle put the slot back to cfg.denoise_rate, so the next
+ * stream in it starts with the default.  Slot 0 is also the stream of the one-stream calls.  SS4K_EINVAL, changing nothing: a slot outside
+ * 0..max_streams-1, a rate that is not finite or is negative.  A stream at rate r gives the bytes of an object created with denoise_rate = r. */
+int ss4k_upscaler_temporal_set_denoise_rate_stream(ss4k_upscaler_temporal* up, int slot, float rate);
 
 /* ---- measurement hooks (bench.py: live per-kernel timing with HIP events on the launch stream) */
 /* When enabled, every launch of the dominant conv kernel is bracketed with hipEvents on the

@@ -102,6 +102,10 @@ int ss4k_dev_op_bsvd_online_carry(ss4k_ctx* ctx, int entries, const void* const*
  * may be NULL), level otherwise.  SS4K_EINVAL: k outside 1..64, planes not 3 or 4, a NULL or misaligned pointer, a source inside dst. */
 int ss4k_dev_op_temporal_gather(ss4k_ctx* ctx, const float* const* src, const uint32_t* const* flags, int k, size_t plane_px, int planes,
                                 uint64_t start_bits, float level_start, float level, float* dst, void* hip_stream);
+/* ... with a level per frame, as a round of slots at different denoise rates launches it: levels holds k HOST floats, frame j's plane 3 is
+ * levels[j] where the one above writes level.  Same routes, same refusals, and SS4K_EINVAL for NULL levels. */
+int ss4k_dev_op_temporal_gather_levels(ss4k_ctx* ctx, const float* const* src, const uint32_t* const* flags, int k, size_t plane_px, int planes,
+                                       uint64_t start_bits, float level_start, const float* levels, float* dst, void* hip_stream);
 
 /* ---- launchers of the frame-recurrent upscaler's glue (csrc/frvsr.hip, csrc/frvsr.h) that the public API reaches only inside a whole
  * step or round: what tests/test_gpu_frvsr_glue_budget.py bounds against float64.  Same conventions as above; their routes are reported

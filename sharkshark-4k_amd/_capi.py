@@ -50,6 +50,8 @@ SYMBOLS = [
     "ss4k_upscaler_temporal_create_streams", "ss4k_upscale_round_temporal", "ss4k_upscaler_temporal_flush_stream",
     "ss4k_upscaler_temporal_reset_stream", "ss4k_upscaler_temporal_pending_stream", "ss4k_upscaler_temporal_scene_cut_stats_stream",
     "ss4k_upscaler_temporal_stream_state_bytes_for", "ss4k_upscaler_temporal_release_idle",
+    # a denoise rate per slot
+    "ss4k_upscaler_temporal_set_denoise_rate_stream",
 ]
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
@@ -82,7 +84,7 @@ DEV_SYMBOLS = [
     # ... and the scene-cut builds (tests/test_gpu_bsvd_cuts.py)
     "ss4k_dev_op_bsvd_online_shift_cuts", "ss4k_dev_op_bsvd_noise_planes",
     # the kernel of a temporal round (tests/test_gpu_temporal_streams_kernel.py)
-    "ss4k_dev_op_temporal_gather",
+    "ss4k_dev_op_temporal_gather", "ss4k_dev_op_temporal_gather_levels",
 ]
 
 
@@ -314,8 +316,12 @@ def load(path: str) -> C.CDLL:
         L.ss4k_upscaler_temporal_scene_cut_stats_stream.argtypes = [vp, i, C.POINTER(SceneCutStats), vp]
         L.ss4k_upscaler_temporal_stream_state_bytes_for.argtypes = [vp, C.POINTER(sz)]
         L.ss4k_upscaler_temporal_release_idle.argtypes = [vp]
+    if hasattr(L, "ss4k_upscaler_temporal_set_denoise_rate_stream"):   # (absent from builds before the per-slot rate)
+        L.ss4k_upscaler_temporal_set_denoise_rate_stream.argtypes = [vp, i, C.c_float]
     if hasattr(L, "ss4k_dev_op_temporal_gather"):   # dev library only
         L.ss4k_dev_op_temporal_gather.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, sz, i, C.c_uint64, C.c_float, C.c_float, vp, vp]
+    if hasattr(L, "ss4k_dev_op_temporal_gather_levels"):   # dev library only
+        L.ss4k_dev_op_temporal_gather_levels.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, sz, i, C.c_uint64, C.c_float, C.POINTER(C.c_float), vp, vp]
     if hasattr(L, "ss4k_dev_op_bsvd_online_shift_cuts"):   # dev library only
         L.ss4k_dev_op_bsvd_online_shift_cuts.argtypes = [vp, vp, vp, i, i, i, i, sz, i, i, i, i, i, vp, C.c_uint, i, vp]
         L.ss4k_dev_op_bsvd_noise_planes.argtypes = [vp, vp, i, sz, vp, i, C.c_float, C.c_float, vp]
@@ -907,18 +913,37 @@ class TemporalUpscaler:
             _check(lib().ss4k_upscale_frames_temporal(self._h, frames.data_ptr(), n, h, w, out.data_ptr(), out.numel(), C.byref(k), _stream()))
         return out[:k.value]
 
-    def flush(self, slot: int = 0) -> torch.Tensor:
-        """The frames still inside a slot's stream, oldest first; the stream ends and the slot is free for another."""
+    def _out_view(self, out: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
+        """A caller-owned result buffer as (capacity, oh, ow, 3): any contiguous uint8 view on this device; bytes beyond whole frames are not used."""
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+                and out.device.index == torch.device(self.ctx.device).index):
+            raise ValueError("out= is a contiguous uint8 tensor or view on the upscaler's device")
+        frame = oh * ow * 3
+        cap = out.numel() // frame
+        return out.reshape(-1)[:cap * frame].view(cap, oh, ow, 3)
+
+    def flush(self, slot: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The frames still inside a slot's stream, oldest first; the stream ends and the slot is free for another.  ``out``: a caller-owned
+        contiguous uint8 device view to write them into (the result is a view of its first frames); one too small for the pending frames is the
+        library's refusal, and the stream stays as it was."""
         left = self.pending if slot == 0 else self.pending_of(slot)
         oh, ow = self.out_shape()
-        out = torch.empty((left, oh, ow, 3), dtype=torch.uint8, device=self.ctx.device)
+        if out is None:
+            out = torch.empty((left, oh, ow, 3), dtype=torch.uint8, device=self.ctx.device)
+        else:
+            out = self._out_view(out, oh, ow)
         k = C.c_int()
         with torch.cuda.device(self.ctx.device):
             if slot == 0:
-                _check(lib().ss4k_upscaler_temporal_flush(self._h, out.data_ptr() if left else None, out.numel(), C.byref(k), _stream()))
+                _check(lib().ss4k_upscaler_temporal_flush(self._h, out.data_ptr() if out.numel() else None, out.numel(), C.byref(k), _stream()))
             else:
-                _check(lib().ss4k_upscaler_temporal_flush_stream(self._h, int(slot), out.data_ptr() if left else None, out.numel(), C.byref(k), _stream()))
+                _check(lib().ss4k_upscaler_temporal_flush_stream(self._h, int(slot), out.data_ptr() if out.numel() else None, out.numel(), C.byref(k), _stream()))
         return out[:k.value]
+
+    def set_denoise_rate(self, slot: int, rate: float) -> None:
+        """The denoise rate of one slot's stream (ss4k_upscaler_temporal_set_denoise_rate_stream): its frames enter at the level 0.1 * rate from
+        the next call or round on.  It ends with the stream: after ``flush`` / ``reset`` the slot is back at the object's ``denoise_rate``."""
+        _check(lib().ss4k_upscaler_temporal_set_denoise_rate_stream(self._h, int(slot), float(rate)))
 
     def reset(self, slot: int = 0) -> None:
         if slot == 0:
@@ -943,11 +968,12 @@ class TemporalUpscaler:
         with torch.cuda.device(self.ctx.device):
             _check(lib().ss4k_upscaler_temporal_release_idle(self._h))
 
-    def round(self, frames, slots):
+    def round(self, frames, slots, out: Optional[torch.Tensor] = None):
         """One round (ss4k_upscale_round_temporal): ``frames`` is a list of (h, w, 3) uint8 device tensors or views, each with contiguous bytes at
         any byte address; frame i belongs to slot ``slots[i]``.  Frames of a slot enter in list order, at most ``max_push`` per slot and 64 in all.
         Returns ``(out, [(slot, count), ...])``: the frames that became ready, contiguous, slot after slot in order of first appearance and oldest
-        first within a slot.  The counts are known without a synchronisation."""
+        first within a slot.  The counts are known without a synchronisation.  ``out``: a caller-owned contiguous uint8 device view that the ready
+        frames are written into (the result is a view of it); one too small for them is the library's refusal, and nothing changes."""
         k = len(frames)
         if k != len(slots):
             raise ValueError(f"{k} frames and {len(slots)} slots")
@@ -958,12 +984,16 @@ class TemporalUpscaler:
         if any(tuple(f.shape) != (h, w, 3) for f in frames):
             raise ValueError("the frames of a round have one size")
         oh, ow = self.out_shape(h, w)
-        out = torch.empty((max(k, 1), oh, ow, 3), dtype=torch.uint8, device=self.ctx.device)
+        if out is None:
+            out = torch.empty((max(k, 1), oh, ow, 3), dtype=torch.uint8, device=self.ctx.device)
+        else:
+            out = self._out_view(out, oh, ow)
         ptrs = (C.c_void_p * max(k, 1))(*[f.data_ptr() for f in frames])
         ids = (C.c_int * max(k, 1))(*[int(s) for s in slots])
         counts, item_slots, n_items = (C.c_int * max(k, 1))(), (C.c_int * max(k, 1))(), C.c_int()
         with torch.cuda.device(self.ctx.device):
-            _check(lib().ss4k_upscale_round_temporal(self._h, ptrs, ids, k, h, w, out.data_ptr(), out.numel(), counts, item_slots, C.byref(n_items), _stream()))
+            _check(lib().ss4k_upscale_round_temporal(self._h, ptrs, ids, k, h, w, out.data_ptr() if out.numel() else None, out.numel(), counts, item_slots,
+                                                     C.byref(n_items), _stream()))
         items = [(int(item_slots[t]), int(counts[t])) for t in range(n_items.value)]
         return out[:sum(c for _, c in items)], items
 

@@ -195,16 +195,34 @@ int ss4k_upscaler_temporal_release_idle(ss4k_upscaler_temporal* up) {
     up->t.release_idle();
   });
 }
+int ss4k_upscaler_temporal_set_denoise_rate_stream(ss4k_upscaler_temporal* up, int slot, float rate) {
+  return guard([&] {
+    SS4K_REQUIRE(up, "ss4k_upscaler_temporal_set_denoise_rate_stream: NULL argument");
+    up->t.set_denoise_rate(slot, rate);
+  });
+}
 
 #ifdef SS4K_DEV
+// one launcher call behind both dev entries: levels[j] per frame, or one level for all of them
+static void dev_temporal_gather(const float* const* src, const uint32_t* const* flags, int k, size_t plane_px, int planes, uint64_t start_bits,
+                                float level_start, const float* levels, float level, float* dst, void* s) {
+  SS4K_REQUIRE(k >= 1 && k <= TROUND_MAX_FRAMES, "ss4k_dev_op_temporal_gather: 1..64 frames");
+  TroundTable tab{};
+  for (int j = 0; j < k; ++j) { tab.src[j] = src[j]; tab.flag[j] = flags ? flags[j] : nullptr; tab.level[j] = levels ? levels[j] : level; }
+  op_tround_gather(tab, dst, k, plane_px, planes, (unsigned long long)start_bits, level_start, (hipStream_t)s);
+}
+int ss4k_dev_op_temporal_gather_levels(ss4k_ctx* c, const float* const* src, const uint32_t* const* flags, int k, size_t plane_px, int planes,
+                                       uint64_t start_bits, float level_start, const float* levels, float* dst, void* s) {
+  return guard([&] {
+    SS4K_REQUIRE(c && src && levels, "ss4k_dev_op_temporal_gather_levels: NULL argument");
+    dev_temporal_gather(src, flags, k, plane_px, planes, start_bits, level_start, levels, 0.f, dst, s);
+  });
+}
 int ss4k_dev_op_temporal_gather(ss4k_ctx* c, const float* const* src, const uint32_t* const* flags, int k, size_t plane_px, int planes,
                                 uint64_t start_bits, float level_start, float level, float* dst, void* s) {
   return guard([&] {
     SS4K_REQUIRE(c && src, "ss4k_dev_op_temporal_gather: NULL argument");
-    SS4K_REQUIRE(k >= 1 && k <= TROUND_MAX_FRAMES, "ss4k_dev_op_temporal_gather: 1..64 frames");
-    TroundTable tab{};
-    for (int j = 0; j < k; ++j) { tab.src[j] = src[j]; tab.flag[j] = flags ? flags[j] : nullptr; }
-    op_tround_gather(tab, dst, k, plane_px, planes, (unsigned long long)start_bits, level_start, level, (hipStream_t)s);
+    dev_temporal_gather(src, flags, k, plane_px, planes, start_bits, level_start, nullptr, level, dst, s);
   });
 }
 #endif

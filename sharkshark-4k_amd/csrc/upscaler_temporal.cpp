@@ -141,6 +141,7 @@ size_t TemporalUpscaler::stream_state_bytes_for() const {
 void TemporalUpscaler::release_idle() {
   for (auto& s : slots) {
     if (s->running()) continue;
+    s->rate = -1;
     s->on.release_state(); s->ring.release();
     if (s->cut) s->cut->release_device();   // (its counters start over, as after set_scene_cut(0): they lived in the buffers that go)
   }
@@ -148,8 +149,14 @@ void TemporalUpscaler::release_idle() {
 
 void TemporalUpscaler::reset(int si) {
   TemporalSlot& s = slot(si);
-  s.on.reset(); s.first_frame = true; s.pushed = s.emitted = 0;
+  s.on.reset(); s.first_frame = true; s.pushed = s.emitted = 0; s.rate = -1;
   if (s.cut) s.cut->forget();
+}
+
+void TemporalUpscaler::set_denoise_rate(int si, float rate) {
+  TemporalSlot& s = slot(si);
+  SS4K_REQUIRE(std::isfinite(rate) && rate >= 0.f, "temporal upscaler: a denoise rate is finite and not negative");
+  s.rate = (double)rate;
 }
 
 // the detector of a slot that has none yet, once a threshold is set
@@ -219,6 +226,7 @@ int TemporalUpscaler::round(const uint8_t* const* fr, const int* slot_ids, int k
         fin.p[q] = fr[p.order[q]];
         dst.p[q] = s.ring.as<float>() + frame * p.ring_in[q];
         tab.src[q] = dst.p[q];
+        tab.level[q] = level(s);
       }
       if (s.first_frame) start_bits |= 1ull << it.first;
     }
@@ -233,7 +241,7 @@ int TemporalUpscaler::round(const uint8_t* const* fr, const int* slot_ids, int k
       for (int j = 0; j < it.n; ++j) tab.flag[it.first + j] = item_cuts[t] + j;
     }
     // ---- 3. the packed (k, 4, lh, lw) denoiser input, noise planes included: one launch
-    op_tround_gather(tab, lr4.as<float>(), k, plane, 4, start_bits, 0.05f, (float)(0.1 * up.cfg.denoise_rate), st);
+    op_tround_gather(tab, lr4.as<float>(), k, plane, 4, start_bits, 0.05f, st);
     // ---- 4. one push per item, one after the other: they share the model's activation slots
     for (int t = 0; t < p.n_items; ++t) {
       const temporal_round::Item& it = p.items[t];
@@ -252,7 +260,7 @@ int TemporalUpscaler::round(const uint8_t* const* fr, const int* slot_ids, int k
         for (int q = 0; q < it.emitted; ++q) leave.src[it.den_off + q] = slots[it.slot]->ring.as<float>() + frame * p.ring_out[it.den_off + q];
         slots[it.slot]->emitted += it.emitted;
       }
-      op_tround_gather(leave, lrk.as<float>(), p.total, plane, 3, 0ull, 0.f, 0.f, st);
+      op_tround_gather(leave, lrk.as<float>(), p.total, plane, 3, 0ull, 0.f, st);
       // ---- 6. the tail over the round's frames, whatever stream they belong to
       for (int c = 0; c < p.n_chunks; ++c) {
         const size_t off = (size_t)p.chunk_off[c];
@@ -288,13 +296,13 @@ int TemporalUpscaler::frames(const uint8_t* in, int n, int h, int w, uint8_t* ou
     SS4K_REQUIRE((double)(bsvd_online::LAG / 2 + on.max_push) * lh * lw < 2147483648.0, "bsvd online push: a carried plane holds at most 2^31 pixels");
     lr4.ensure(plane * 4 * n * 4);
     cuts = cut->detect(in, n, h, w, st);
-    op_bsvd_noise_planes(lr4.as<float>(), n, plane, cuts, first_frame ? 1 : 0, 0.05f, (float)(0.1 * up.cfg.denoise_rate), st);
+    op_bsvd_noise_planes(lr4.as<float>(), n, plane, cuts, first_frame ? 1 : 0, 0.05f, level(s0), st);
     first_frame = false;
   }
   const float* lr_before = up.planes_in(in, n, h, w, lh, lw, st);
   ring.ensure(frame * ring_frames() * 4); lr4.ensure(plane * 4 * n * 4); den.ensure(frame * on.max_push * 4);
   for (int i = 0; i < n; ++i) {
-    const float noise = first_frame ? 0.05f : (float)(0.1 * up.cfg.denoise_rate);  // fsrcnn_upscaler.py:262, :269-271
+    const float noise = first_frame ? 0.05f : level(s0);  // fsrcnn_upscaler.py:262, :269-271
     first_frame = false;
     float* dst = lr4.as<float>() + plane * 4 * i;
     SS4K_HIP(hipMemcpyAsync(dst, lr_before + frame * i, frame * 4, hipMemcpyDeviceToDevice, st));
@@ -325,7 +333,7 @@ int TemporalUpscaler::flush(int si, uint8_t* out, size_t out_capacity_bytes, hip
     const int k = std::min(on.max_push, left - done);
     emit(s, k, den_flush.as<float>() + frame * done, out + (size_t)done * oh * ow * 3, st);
   }
-  s.first_frame = true; s.pushed = s.emitted = 0;
+  s.first_frame = true; s.pushed = s.emitted = 0; s.rate = -1;
   if (s.cut) s.cut->forget();
   return left;
 }

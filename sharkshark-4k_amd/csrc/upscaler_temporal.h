@@ -40,13 +40,15 @@ struct TemporalCut {
 
 // ---- the kernel of a round (temporal_round.hip) -----------------------------------------------------------------------------------------------
 // Frame j of a launch: its three LR planes at src[j] (3 * plane_px fp32, contiguous, 16-byte aligned - a slot of its stream's ring), and the device
-// word that says whether it starts a scene (NULL: it does not).  BY VALUE in the kernel arguments, as FrvsrPtrs (1 KiB): no device table.
+// word that says whether it starts a scene (NULL: it does not), and the noise level of its stream's slot (read with four planes only).  BY VALUE
+// in the kernel arguments, as FrvsrPtrs: 1280 bytes, no device table.
 constexpr int TROUND_MAX_FRAMES = temporal_round::MAX_FRAMES;
-struct TroundTable { const float* src[TROUND_MAX_FRAMES]; const uint32_t* flag[TROUND_MAX_FRAMES]; };
+struct TroundTable { const float* src[TROUND_MAX_FRAMES]; const uint32_t* flag[TROUND_MAX_FRAMES]; float level[TROUND_MAX_FRAMES]; };
+static_assert(sizeof(TroundTable) == 1280, "the round's table travels in the kernel arguments: keep it far below 4 KiB");
 // dst (k, planes, plane_px) fp32: planes 0..2 of frame j from src[j]; with planes == 4, plane 3 is level_start where bit j of start_bits is set or
-// *flag[j] != 0, and level otherwise - the bits of bsvdo::noise_planes / the one-stream path's fill.  One launch, one thread per 16-byte slot.
+// *flag[j] != 0, and level[j] otherwise - the bits of bsvdo::noise_planes / the one-stream path's fill.  One launch, one thread per 16-byte slot.
 void op_tround_gather(const TroundTable& tab, float* dst, int k, size_t plane_px, int planes, unsigned long long start_bits, float level_start,
-                      float level, hipStream_t st);
+                      hipStream_t st);
 
 // what one stream owns; allocated by its first push
 struct TemporalSlot {
@@ -55,6 +57,7 @@ struct TemporalSlot {
   bool first_frame = true;
   std::unique_ptr<TemporalCut> cut;   // null until a threshold > 0 reaches the slot
   long long pushed = 0, emitted = 0;   // frames of the running stream
+  double rate = -1;     // the stream's denoise rate (set_denoise_rate); negative: the object's cfg.denoise_rate.  Ends with the stream
   bool running() const { return on.state.pushed > 0; }
 };
 
@@ -83,6 +86,8 @@ struct TemporalUpscaler {
   size_t stream_state_bytes_for() const;   // what one slot will hold, before any push
   void release_idle();                     // frees the state of slots with no running stream
   void set_scene_cut(double threshold);    // every slot
+  void set_denoise_rate(int s, float rate);   // the slot's frames from the next push or round on, until its stream ends
+  float level(const TemporalSlot& s) const { return (float)(0.1 * (s.rate < 0 ? up.cfg.denoise_rate : s.rate)); }   // fsrcnn_upscaler.py:269-271
 
  private:
   void emit(TemporalSlot& s, int k, const float* denoised, uint8_t* out, hipStream_t st);

@@ -121,6 +121,9 @@ class NodeResult:
 
 
 class EgvsrNode(WorkerPool):
+    #: the key under which a worker's answers carry its scene-cut counter
+    CUTS_KEY = "egvsr.scene_cuts"
+
     def __init__(self, devices: Union[int, Sequence[int], None] = None, max_streams: int = 1, job_frames: int = 4, host_frames=True,
                  host_slots: int = 6, output_shape="unset", service_cls=HipEgvsrUpscalerService, push_timeout: float = 10.0, **service_kwargs):
         super().__init__(devices)
@@ -146,6 +149,32 @@ class EgvsrNode(WorkerPool):
         svc = self.service_cls(device=self.devices[k], max_streams=self.max_streams, **self.service_kwargs)
         return self._prepare(svc, svc.lr_shape if self.host_frames is True else self.host_frames, svc.out_hw)
 
+    # ---- what a node of another stream service (temporal_node.TemporalNode) answers differently; the rules around them are this class's
+    def _answered(self, idx, ends) -> bool:
+        """Does this part of a submit own ring slots and come back as a result?  Here: a part with frames (a frames-less ``end_streams`` entry
+        only frees slots in the worker; its answer is swallowed)."""
+        return bool(idx)
+
+    def _check_parts(self, parts, ends, streams, extra) -> None:
+        """More refusals, before anything is queued or the table changes."""
+
+    def _payload(self, k, idx, frames, slot, out_slot):
+        shape = self.services[k].host_rings[0].write(slot, frames[idx])
+        return HostFrames(slot=slot, out_slot=out_slot, shape=shape)
+
+    def _entry(self, k, payload, ids, ends, step, audio_segment, profiler, extra):
+        return StreamQueueEntry(frames=payload, audio_segment=audio_segment, step=step, profiler=profiler, streams=list(ids), end_streams=tuple(ends))
+
+    def _queued(self, k, step, part) -> None:
+        """The part has reached its worker's job queue."""
+
+    def _result(self, k, e, part, view):
+        return NodeResult(step=e.step, worker=k, streams=part["streams"], frames=view, audio_segment=e.audio_segment, elapsed=e.elapsed,
+                          profiler=e.profiler)
+
+    def _streams_gone(self, k, gone) -> None:
+        """Worker k was found dead; ``gone`` are the ids it held."""
+
     # ------------------------------------------------------------------------------------------ in
     def submit(self, frames, streams: Sequence[Hashable], end_streams: Sequence[Hashable] = (), audio_segment=None, profiler=None) -> int:
         """``frames``: (N, H, W, 3) uint8 on the host (numpy array or CPU tensor), ``streams[i]`` the stream of ``frames[i]``.  Returns the
@@ -154,6 +183,10 @@ class EgvsrNode(WorkerPool):
         frames bigger than a ring slot, ``TimeoutError`` when a ring stays full for ``push_timeout``.  A part that cannot be put into
         its worker's job queue after all that is written off (``report()['lost']``) and reported by a ``RuntimeError`` that carries
         ``.step``; the other parts of the step are queued."""
+        return self._submit(frames, streams, end_streams, audio_segment, profiler)
+
+    def _submit(self, frames, streams, end_streams, audio_segment, profiler, extra=None) -> int:
+        """``submit``; ``extra`` is what a subclass hands on to its own ``_check_parts`` / ``_entry``."""
         import torch
         if isinstance(frames, torch.Tensor):
             assert not frames.is_cuda and frames.dtype == torch.uint8, "EgvsrNode.submit takes HOST uint8 frames"
@@ -178,10 +211,12 @@ class EgvsrNode(WorkerPool):
                 raise ValueError(f"the part of worker {k} holds {len(idx)} frames, job_frames is {self.job_frames}: submit fewer frames per stream")
             if idx and not self.services[k].host_rings[0].fits((len(idx),) + frames.shape[1:]):
                 raise ValueError(f"{len(idx)} frames of {frames.shape[1:3]} do not fit a slot of worker {k}'s input ring (host_frames)")
+        self._check_parts(parts, ends, streams, extra)
+        has = [self._answered(parts[k], ends[k]) for k in range(G)]
         taken: Dict[int, Tuple[int, int]] = {}
         deadline = time.monotonic() + self.push_timeout
         for k, idx in enumerate(parts):
-            while idx and k not in taken:
+            while has[k] and k not in taken:
                 pair = self._pools[k].take()
                 if pair is not None:
                     taken[k] = pair
@@ -206,25 +241,25 @@ class EgvsrNode(WorkerPool):
             if not parts[k] and not ends[k]:
                 continue
             ids = tuple(streams[i] for i in parts[k])
-            if parts[k]:
+            if has[k]:
                 slot, out_slot = taken[k]
-                shape = self.services[k].host_rings[0].write(slot, frames[parts[k]])
-                payload = HostFrames(slot=slot, out_slot=out_slot, shape=shape)
+                payload = self._payload(k, parts[k], frames, slot, out_slot)
             else:
                 slot = out_slot = payload = None
             try:
-                self.services[k].push_job(StreamQueueEntry(frames=payload, audio_segment=audio_segment if parts[k] else None, step=step, profiler=profiler,
-                                                           streams=list(ids), end_streams=tuple(ends[k])), timeout=self.push_timeout)
+                self.services[k].push_job(self._entry(k, payload, ids, ends[k], step, audio_segment if parts[k] else None, profiler, extra),
+                                          timeout=self.push_timeout)
             except Exception as ex:  # noqa: BLE001 - a full job queue, a worker that just died: this part never left
-                if parts[k]:         # written off like a part inside a dead worker: the slots come back, the step does not wait for it
+                if has[k]:           # written off like a part inside a dead worker: the slots come back, the step does not wait for it
                     self._pools[k].give_in(slot); self._pools[k].give_out(out_slot)
                     self.lost += 1
                 failed.append((k, ex))
                 continue
-            if parts[k]:
+            if has[k]:
                 rec["waiting"].add(k)
                 self.host_jobs[k] += 1
-            self._inflight[k][step] = {"slot": slot, "out_slot": out_slot, "streams": ids, "frames": bool(parts[k])}
+            self._inflight[k][step] = {"slot": slot, "out_slot": out_slot, "streams": ids, "frames": has[k], "ends": tuple(ends[k])}
+            self._queued(k, step, self._inflight[k][step])
         for sid in end_streams:
             self.router.end(sid)
         if failed:
@@ -240,7 +275,7 @@ class EgvsrNode(WorkerPool):
         for k, svc in enumerate(self.services):
             if self.router.alive[k] and self.started and not svc.proc.is_alive():
                 self._collect_worker(k)
-                self.router.worker_died(k)
+                self._streams_gone(k, self.router.worker_died(k))
                 for step, part in self._inflight[k].items():
                     if part["frames"]:
                         self.lost += 1
@@ -255,7 +290,7 @@ class EgvsrNode(WorkerPool):
             except (queue.Empty, OSError, EOFError):
                 return n
             n += 1
-            cuts = getattr(getattr(e, "profiler", None), "data", {}).get("egvsr.scene_cuts")
+            cuts = getattr(getattr(e, "profiler", None), "data", {}).get(self.CUTS_KEY)
             if cuts is not None:
                 self.scene_cuts[k] = int(cuts)
             part = self._inflight[k].pop(e.step, None)
@@ -265,8 +300,7 @@ class EgvsrNode(WorkerPool):
             rec = self._steps[e.step]
             rec["waiting"].discard(k)
             view = self.services[k].host_rings[1].view(e.frames.out_slot, e.frames.shape)
-            rec["parts"][k] = (NodeResult(step=e.step, worker=k, streams=part["streams"], frames=view, audio_segment=e.audio_segment,
-                                          elapsed=e.elapsed, profiler=e.profiler), part["out_slot"])
+            rec["parts"][k] = (self._result(k, e, part, view), part["out_slot"])
 
     def _make_room(self, k: int) -> None:
         """A submit waits for a slot of worker k: results of k that are back but not handed out yet are copied out of its output ring."""

@@ -87,6 +87,9 @@ class BaseService(abc.ABC):
     deliver_lag = 0
     #: set by the worker once proc_init() has returned (None: nobody waits for it)
     ready_event = None
+    #: how a worker that was asked to leave ends: None - by SIGTERM to itself, exit code -15, as ever; a number - ``os._exit`` with that code, for
+    #: a launcher whose callers tell a clean leave (0) from a worker that was killed (``temporal_node.TemporalNode``)
+    leave_exit_code = None
 
     def __init__(self) -> None:
         mpctx = mp.get_context("spawn")   # (named semaphores: usable from a forked and from a spawned worker)
@@ -171,6 +174,9 @@ class BaseService(abc.ABC):
             _interrupt_process_group(ex)
             return
         print(f"{type(self).__name__}: worker leaves on request", file=sys.stderr)
+        if self.leave_exit_code is not None:   # (like the signal below: at once, daemon threads of the runtime or not)
+            sys.stderr.flush()
+            os._exit(int(self.leave_exit_code))
         os.kill(os.getpid(), signal.SIGTERM)  # daemon threads of the runtime must not keep it alive
 
     # ---------------------------------------------------------------- client side

@@ -42,11 +42,20 @@ named slot of the pinned output ring on a second copy stream and answers with a 
 waited for (two jobs in flight), so both copies run under the neighbouring jobs' kernels (``pipeline.py:84-93`` / ``streamer.py:92-98`` are the
 reference's host <-> device hops).  The copies, their ordering and the held results are ``host_io.py``'s (``HostFrameIO``, ``HeldResults``), shared with
 the EGVSR service; this service adds its staging depth, the job sets' end events and its lag policy.  A device tensor that lives on ANOTHER GPU is copied over once, counted in ``'upscaler.input.peer_copies'``.
+
+Host frames on the temporal service (``denoise_temporal=True``): a ``HostFrames`` job's answer is not the job's own frames but the frames that
+became ready - ``shape = (ready, oH, oW, 3)``, ``ready`` possibly 0, the entry tagged with ``ready`` / ``first_frame_index`` / ``lag_frames`` as
+every temporal answer.  A job of K frames that ends E streams returns at most ``K + 16 E`` frames (``temporal_result_bound``); one whose bound
+does not fit the out slot raises before a frame runs and takes no stream slot.  An entry with ``end_streams`` and a ``HostFrames`` of 0 frames is
+a flush: its input slot is not read, what was inside lands in its out slot.  ``stream_rates={id: rate}`` - the keyword of ``upscale`` and an
+optional field of a queue entry - sets the denoise rate of those streams' slots before the job's first round (``temporal_node.TemporalNode`` is
+the caller that runs all this on several workers).
 """
 from __future__ import annotations
 
 import collections
 import contextlib
+import dataclasses
 import sys
 from typing import Mapping, Optional
 
@@ -56,6 +65,7 @@ from .. import sharding
 from ..hostring import HostFrames
 from ..util.profiler import Profiler
 from .host_io import DEVICE, HOST, HeldResults, HostFrameIO
+from .egvsr_upscaler import StreamQueueEntry
 from .upscaler_base import BaseUpscalerService, UpscalerQueueEntry, answer, record_span  # noqa: F401
 
 LR_LEVELS = [(360, 640), (540, 960), (630, 1120), (720, 1280), (900, 1600), (1080, 1920)]
@@ -68,6 +78,31 @@ def validate_scene_cut(scene_cut, denoise_temporal: bool) -> Optional[float]:
     if t is not None and not denoise_temporal:
         raise ValueError("scene_cut belongs to denoise_temporal=True: the per-frame denoiser joins no frames, a cut has nothing to keep apart")
     return t
+
+
+@dataclasses.dataclass
+class TemporalQueueEntry(StreamQueueEntry):
+    """The job record of a temporal worker with stream slots: ``StreamQueueEntry`` plus ``stream_rates`` (``{stream id: denoise rate}`` for
+    streams of this job, or None).  Any entry type works - the service reads the three optional fields with ``getattr``."""
+    stream_rates: Optional[Mapping] = None
+
+
+def validate_stream_rates(stream_rates, streams) -> dict:
+    """The ``stream_rates`` of a temporal job, ``{stream id: denoise rate}``: every id is one of the job's ``streams`` and every rate is a
+    finite number >= 0 (what ``ss4k_upscaler_temporal_set_denoise_rate_stream`` takes).  Anything else raises ``ValueError`` here, before a
+    frame runs or a slot is taken.  None and {} mean: no stream's rate changes."""
+    if not stream_rates:
+        return {}
+    if not isinstance(stream_rates, Mapping):
+        raise ValueError(f"stream_rates is a mapping {{stream id: rate}}, not {type(stream_rates).__name__}")
+    present, rates = set(streams), {}
+    for sid, rate in stream_rates.items():
+        if sid not in present:
+            raise ValueError(f"stream_rates names {sid!r}, which has no frame in this job: a rate is set with frames of its stream")
+        if isinstance(rate, bool) or not isinstance(rate, (int, float)) or rate != rate or rate < 0 or rate == float("inf"):
+            raise ValueError(f"stream_rates[{sid!r}] = {rate!r}: a denoise rate is a finite number >= 0")
+        rates[sid] = float(rate)
+    return rates
 
 
 def under_profiler() -> bool:
@@ -367,12 +402,16 @@ class HipUpscalerService(BaseUpscalerService):
     def proc_job_recieved(self, job):
         hf = getattr(job, "frames", None)
         if self.denoise_temporal:
-            if isinstance(hf, HostFrames):
-                raise RuntimeError("denoise_temporal=True takes device or host TENSOR jobs: a host-ring job's result slot is sized for the job's own frames")
             streams, end_streams = getattr(job, "streams", None), tuple(getattr(job, "end_streams", None) or ())
-            if streams is None and not end_streams:
+            rates = getattr(job, "stream_rates", None) or None
+            if isinstance(hf, HostFrames):
+                frames, elapsed, prof = self._run_job(job, lambda: self._temporal_host_job(hf, streams, end_streams, rates))
+                prof.set("upscaler.input.peer_copies", self._peer_copies)
+                return self._tag_temporal(answer(job, frames, elapsed, prof))
+            if streams is None and not end_streams and not rates:
                 return self._tag_temporal(super().proc_job_recieved(job))
-            entry = answer(job, *self._run_job(job, lambda: self.upscale(job.frames, streams=streams, end_streams=end_streams)))
+            more = {"stream_rates": rates} if rates else {}
+            entry = answer(job, *self._run_job(job, lambda: self.upscale(job.frames, streams=streams, end_streams=end_streams, **more)))
             return self._tag_temporal(entry)
         if not isinstance(hf, HostFrames):
             entry = super().proc_job_recieved(job)
@@ -391,6 +430,54 @@ class HipUpscalerService(BaseUpscalerService):
         frames, elapsed, prof = self._run_job(job, host_job)
         prof.set("upscaler.input.peer_copies", self._peer_copies)
         return answer(job, frames, elapsed, prof)
+
+    def temporal_result_bound(self, n_frames: int, ended: int = 0) -> int:
+        """The most frames a temporal job of ``n_frames`` frames that ends ``ended`` streams can return: its own number (every frame that goes in
+        pushes at most one out) plus ``TEMPORAL_LAG`` per ended stream (what a flush can hold)."""
+        return int(n_frames) + self.TEMPORAL_LAG * int(ended)
+
+    def _ending(self, streams, end_streams) -> set:
+        """The ids of ``end_streams`` that have something to flush: they hold a slot or have a frame in this job (the others are ignored)."""
+        return {sid for sid in end_streams if sid in self._tslots.slot_of or sid in streams}
+
+    def _temporal_host_job(self, hf: HostFrames, streams, end_streams, rates):
+        """A ``HostFrames`` job of the temporal service.  Its result is not the job's own frames but what became ready, so the out slot must hold
+        the job's bound (``temporal_result_bound``): a job whose bound does not fit is refused here, before a frame runs, a slot is taken or the
+        device is touched.  A job of 0 frames is a flush: its input slot is not read.  The rounds and the flushes write into ONE device buffer
+        of the bound's size (``out=``), which ``HostFrameIO.run`` copies to the out slot.  An entry without ids is a job of the unnamed stream:
+        it runs as rounds too - on slot 0 they give the bytes of the one-stream calls (tests/test_gpu_temporal_streams.py)."""
+        if self.host_rings is None:
+            raise RuntimeError("a HostFrames job reached a worker that was started without host rings")
+        n = int(hf.shape[0])
+        ids = [None] * n if streams is None else list(streams)
+        if len(ids) != n:
+            raise ValueError(f"one stream id per frame: {len(ids)} ids for {n} frames")
+        rates = validate_stream_rates(rates, ids)
+        ended = len(self._ending(ids, end_streams))
+        bound = self.temporal_result_bound(n, ended)
+        oh, ow = self.out_hw(int(hf.shape[1]), int(hf.shape[2]))
+        if not self.host_rings[1].fits((bound, oh, ow, 3)):
+            raise ValueError(f"a temporal job of {n} frames that ends {ended} stream(s) can return {bound} frames of {oh} x {ow}: more "
+                             f"than a {self.host_rings[1].slot_bytes}-byte slot of the output ring holds (end fewer streams per job)")
+
+        def job(stage):
+            self._lag_now = 0
+            self._get_upscaler(0)   # (first: building the object starts the slot table over)
+            return self._temporal_job(stage if n else None, ids, end_streams, rates, into=bound)
+
+        if n:
+            shape, landed = self._io.run(hf, job)
+        else:   # a flush: no H2D, no staging tensor - only the way out
+            with torch.cuda.device(self.torch_device):
+                out = job(None)
+                shape = tuple(out.shape)
+                done = torch.cuda.current_stream(self.torch_device).record_event()
+                landed = self._io.copy_out(out, self.host_rings[1].view(hf.out_slot, shape), done)
+        self._host_jobs += 1
+        frames = HostFrames(slot=hf.slot, out_slot=hf.out_slot, shape=shape, result=True)
+        if landed is not None:
+            self._hold_host(frames, landed)
+        return frames
 
     def _hold_host(self, frames, landed) -> None:
         self._held.hold(frames, landed, HOST)
@@ -577,13 +664,19 @@ class HipUpscalerService(BaseUpscalerService):
             rounds.append(idx)
         return rounds
 
-    def _temporal_job(self, frames, streams, end_streams):
+    def _temporal_job(self, frames, streams, end_streams, stream_rates=None, into=None):
         """A job of a temporal service with stream slots: its rounds, then the flushes of ``end_streams``.  Every stream id gets its slot BEFORE the
-        first frame runs: a job that does not fit raises, has run nothing and has taken no slot."""
+        first frame runs: a job that does not fit raises, has run nothing and has taken no slot.  ``stream_rates`` (validated) reach their slots
+        before the first round.  ``into``: a frame count - every round and flush then writes behind the last one into ONE device buffer of that
+        many frames and the result is a view of it (a host-ring job: nothing is concatenated)."""
         n = 0 if frames is None else int(frames.shape[0])
         if len(streams) != n:
             raise ValueError(f"one stream id per frame: {len(streams)} ids for {n} frames")
         up = self._get_upscaler(0)
+        result, filled = None, 0
+        if into is not None:
+            oh, ow = up.out_shape(*((int(frames.shape[1]), int(frames.shape[2])) if n else (None, None)))
+            result = torch.empty((int(into), oh, ow, 3), dtype=torch.uint8, device=self.torch_device)
         slots, taken = [], []
         try:
             for sid in streams:
@@ -610,10 +703,16 @@ class HipUpscalerService(BaseUpscalerService):
             ready.append((sid, int(first), k))
 
         try:
+            for sid, rate in (stream_rates or {}).items():
+                up.set_denoise_rate(slots[streams.index(sid)], rate)
             if n:
                 frames = frames.contiguous()
                 for idx in self._temporal_rounds(streams):
-                    out, items = up.round([frames[i] for i in idx], [slots[i] for i in idx])
+                    if result is None:
+                        out, items = up.round([frames[i] for i in idx], [slots[i] for i in idx])
+                    else:
+                        out, items = up.round([frames[i] for i in idx], [slots[i] for i in idx], out=result[filled:])
+                        filled += int(out.shape[0])
                     sid_of, o = {slots[i]: streams[i] for i in idx}, 0
                     for slot, k in items:
                         came_back(sid_of[slot], out[o:o + k])
@@ -622,7 +721,12 @@ class HipUpscalerService(BaseUpscalerService):
                 slot = self._tslots.slot_of.get(sid)
                 if slot is None:
                     continue   # (an id that holds no slot: nothing inside, nothing to free)
-                came_back(sid, up.flush(slot))
+                if result is None:
+                    came_back(sid, up.flush(slot))
+                else:
+                    out = up.flush(slot, out=result[filled:])
+                    filled += int(out.shape[0])
+                    came_back(sid, out)
                 self._tslots.end(sid)
                 if sid is None:
                     self._t_emitted = 0
@@ -653,6 +757,8 @@ class HipUpscalerService(BaseUpscalerService):
         prof = getattr(self, "profiler", None)
         if prof is not None and getattr(self, "scene_cut", None):
             prof.set("fsrcnn.scene_cuts", up.scene_cut_total())
+        if result is not None:
+            return result[:filled]   # (the parts are consecutive views of it)
         if parts:
             return parts[0] if len(parts) == 1 else torch.cat(parts)
         oh, ow = up.out_shape()
@@ -706,7 +812,7 @@ class HipUpscalerService(BaseUpscalerService):
             record_span(prof, "fsrcnn.model", model_ms / 1000.0)
         return out
 
-    def upscale(self, frames: torch.Tensor, wait: bool = True, streams=None, end_streams=()):
+    def upscale(self, frames: torch.Tensor, wait: bool = True, streams=None, end_streams=(), stream_rates=None):
         """``wait=False`` (direct callers only): with the one-frame overlap active the result is ordered on its job set's stream, not
         on the current one - synchronise (``torch.cuda.synchronize()``) before reading it.  The default orders it on the current
         stream like any torch op.
@@ -714,8 +820,15 @@ class HipUpscalerService(BaseUpscalerService):
         ``end_streams`` are flushed after the job, in the order given, and give their slots back.  The result is every frame that became ready, as
         one tensor, and ``last_ready`` says which group of it belongs where.  ``streams=None`` without ``end_streams`` is the service of one
         stream as it was: the same calls, the same tags.  A job with ids that raises after its slots were taken ends every stream it named:
-        their slots are reset and freed and their indices start over (frames that had come back are lost with the exception)."""
+        their slots are reset and freed and their indices start over (frames that had come back are lost with the exception).
+        ``stream_rates={id: rate}`` sets the denoise rate of those streams' slots before the job's first round (the level of their frames is
+        0.1 * rate from then on, until the stream ends; a stream never named runs at the service's ``denoise_rate``).  Every id must be one of
+        the job's ``streams`` (``ValueError``, before anything runs)."""
         assert isinstance(frames, torch.Tensor)
+        if stream_rates:
+            if not getattr(self, "denoise_temporal", False):
+                raise ValueError("stream_rates belongs to denoise_temporal=True")
+            stream_rates = validate_stream_rates(stream_rates, [None] * frames.shape[0] if streams is None else list(streams))
         if frames.device != self.torch_device:
             if frames.is_cuda:   # a device tensor from ANOTHER GPU (the caller put job s somewhere else than on GPU s % G): one peer copy, counted
                 self._peer_copies = getattr(self, "_peer_copies", 0) + 1
@@ -729,11 +842,12 @@ class HipUpscalerService(BaseUpscalerService):
         self._lag_now = 0
         if getattr(self, "denoise_temporal", False):
             self._get_upscaler(0)   # before any slot is taken: building the object (the first job, a new geometry) starts the slot table over
-            named = streams is not None or tuple(end_streams) != ()
+            named = streams is not None or tuple(end_streams) != () or bool(stream_rates)
             # the unnamed stream takes a slot with its first frame, like any other; in slot 0 - always, unless named streams came first - it is
             # served by the one-stream calls
             if named or self._tslots.slot(None)[0] != 0:
-                return self._temporal_job(frames, [None] * frames.shape[0] if streams is None else list(streams), tuple(end_streams))
+                return self._temporal_job(frames, [None] * frames.shape[0] if streams is None else list(streams), tuple(end_streams),
+                                          stream_rates or None)
         elif streams is not None or tuple(end_streams) != ():
             raise ValueError("streams / end_streams belong to denoise_temporal=True")
         if not self._overlap_active():

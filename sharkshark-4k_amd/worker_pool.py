@@ -21,16 +21,17 @@ class WorkerPool:
         if not self.devices:
             raise ValueError(f"{type(self).__name__} needs at least one device")
 
-    def _prepare(self, svc, frame_hw=None, out_hw=None):
+    def _prepare(self, svc, frame_hw=None, out_hw=None, out_frames=None):
         """``svc`` as the node starts it: ``self.output_shape`` unless "unset" (the pipelines overwrite this attribute on the service
         object, pipeline.py:46-50); with ``frame_hw`` = (H, W), host rings of ``self.host_slots`` slots for jobs of ``self.job_frames``
-        such frames in and ``out_hw()`` frames out; a spawned child; a ready event."""
+        such frames in and ``out_hw()`` frames out (``out_frames`` of them where a job can return more than went in); a spawned child; a
+        ready event."""
         import torch.multiprocessing as mp
         if self.output_shape != "unset":
             svc.output_shape = self.output_shape
         if frame_hw is not None:
             (h, w), (oh, ow) = frame_hw, out_hw()   # (after the override: the services' out_hw read output_shape)
-            svc.host_rings = hostring.make_rings(self.host_slots, self.job_frames * h * w * 3, self.job_frames * oh * ow * 3)
+            svc.host_rings = hostring.make_rings(self.host_slots, self.job_frames * h * w * 3, (out_frames or self.job_frames) * oh * ow * 3)
         svc.mp_start_method = "spawn"   # the launcher may have touched the GPU (warm-up, device queries); workers are fresh interpreters
         svc.ready_event = mp.get_context("spawn").Event()
         return svc

@@ -17,13 +17,23 @@ copy, no cut) - and with ``--service`` a third service, ``temporal_cuts``, whose
 (b) ``rounds`` - one S-slot object, one ``round`` call for all S frames.  ``max_push`` is ``--push`` (1 for a live stream), 16 settle rounds,
 then ``--iters`` timed rounds per run, the two forms interleaved; frames/s, ``state_bytes`` and (dev library) the launches per round.
 
+``--streams S --host-rings``: the same rounds twice, interleaved in one session on one box - ``rounds`` as above (resident frames, device events)
+and ``host_rings``: a STARTED ``HipUpscalerService(denoise_temporal=True, max_streams=S)`` with pinned rings, every round a ``HostFrames`` job of
+the S frames (written into the in-ring slot by this process, up to ``--depth`` jobs in flight, wall clock from the first push to the last
+answer).  ``host_over_resident`` is the ratio of the best samples.  The S one-stream objects are left out of this mode.
+``--gather-kernel`` (dev library): microseconds per launch of ``tround::gather_planes<4>`` alone, 4 and 16 frames of ``--h`` x ``--w``, through
+``ss4k_dev_op_temporal_gather`` - the entry a parent build has too, for an A/B of the kernel across builds (``SS4K_LIB``).
+
 Usage:  python tools/bsvd_online_time.py [--h 720 --w 1280 --dtype f16 --variant bsvd-32 --push 4 --iters 20 --runs 2] [--scene-cut T] [--out FILE]
         python tools/bsvd_online_time.py --streams 4 --push 1 --sr rrdbnet --iters 64 [--out FILE]
+        python tools/bsvd_online_time.py --streams 4 --push 1 --sr fsrcnn --iters 64 --host-rings [--depth 3] [--out FILE]
+        SS4K_LIB=.../libss4k_hip_dev.so python tools/bsvd_online_time.py --gather-kernel [--out FILE]
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -82,6 +92,78 @@ def service(a):
         s.proc_cleanup()
 
 
+def emit(a, line):
+    print(json.dumps(line), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(json.dumps(line) + "\n")
+
+
+class HostRingLeg:
+    """A started temporal service with pinned rings; ``run(n)`` sends n rounds of S host frames through it and returns the seconds they took."""
+
+    def __init__(self, a, frames_host):
+        from sharkshark4k_amd import hostring
+        from sharkshark4k_amd.upscale.hip_upscaler import HipUpscalerService
+        S = a.streams
+        if a.sr == "rrdbnet":
+            kw = dict(upscaler_model="realesrgan", model_name="RealESRGAN_x2plus", single_mode=True)
+        else:
+            kw = dict(upscaler_model="fsrcnn", scale=2, fsrcnn_dtype=a.dtype)
+        self.svc = HipUpscalerService(denoising=True, denoise_temporal=True, temporal_max_push=a.push, max_streams=S, lr_shape=(a.h, a.w), dtype=a.dtype,
+                                      weights="synthetic", **kw)
+        self.svc.output_shape = None
+        oh, ow = self.svc.out_hw(a.h, a.w)
+        self.slots, self.depth, self.frames, self.ids, self.step = a.depth + 2, a.depth, frames_host, list(range(S)), 0
+        self.svc.host_rings = hostring.make_rings(self.slots, S * a.h * a.w * 3, S * oh * ow * 3)   # (no stream ends here: a round returns at most S frames)
+        self.svc.start()
+
+    def run(self, n):
+        from sharkshark4k_amd.hostring import HostFrames
+        from sharkshark4k_amd.upscale.hip_upscaler import TemporalQueueEntry
+        sent = got = ready = 0
+        t0 = time.perf_counter()
+        while got < n:
+            while sent < n and sent - got < self.depth:
+                slot = self.step % self.slots
+                shape = self.svc.host_rings[0].write(slot, self.frames)
+                self.svc.push_job(TemporalQueueEntry(frames=HostFrames(slot=slot, out_slot=slot, shape=shape), step=self.step, streams=self.ids), timeout=600)
+                self.step += 1
+                sent += 1
+            ready += int(self.svc.get_result(timeout=600).frames.shape[0])
+            got += 1
+        return time.perf_counter() - t0, ready
+
+    def close(self):
+        self.svc.stop()
+        for ring in self.svc.host_rings:
+            ring.close()
+
+
+def gather_kernel(a):
+    """tround::gather_planes<4> alone through the dev entry that every build since the rounds has: microseconds per launch."""
+    import ctypes as C
+    L, ctx = _capi.lib(), _capi.Context(0)
+    assert hasattr(L, "ss4k_dev_op_temporal_gather"), "--gather-kernel needs the dev library (SS4K_LIB)"
+    plane, res = a.h * a.w, {}
+    for k in (4, 16):
+        ring = torch.rand(k, 3, plane, device="cuda")
+        dst = torch.empty(k, 4, plane, device="cuda")
+        src = (C.c_void_p * k)(*[ring[(j * 5) % k].data_ptr() for j in range(k)])
+
+        def launch():
+            rc = L.ss4k_dev_op_temporal_gather(ctx._h, src, None, k, plane, 4, 1, 0.05, 0.1, dst.data_ptr(), _capi._stream())
+            assert rc == 0, L.ss4k_last_error()
+        for _ in range(20):
+            launch()
+        torch.cuda.synchronize()
+        res[str(k)] = [round(1000.0 * timed(launch, 200), 2) for _ in range(max(a.runs, 3))]
+    emit(a, {"tool": "bsvd_online_time --gather-kernel", "lib": os.path.basename(os.path.dirname(_capi.LIB_PATH)) + "/" + os.path.basename(_capi.LIB_PATH),
+             "h": a.h, "w": a.w, "per_frame_levels": bool(hasattr(L, "ss4k_dev_op_temporal_gather_levels")),
+             "us_per_launch_by_frames": res, "bytes_moved_per_frame": 7 * plane * 4})
+
+
 def streams(a):
     """S live streams, one frame per stream per round: S one-stream objects in turn against one S-slot object in rounds."""
     ctx, S = _capi.Context(0), a.streams
@@ -91,12 +173,14 @@ def streams(a):
         sr = factory.build_model_fsrcnn(ctx, factor=2, weights="synthetic", dtype=a.dtype)
     dn = factory.build_denoise_model(ctx, weights="synthetic", dtype=a.dtype, variant=a.variant, stream=True)
     lr = (a.h, a.w)
-    objects = [_capi.TemporalUpscaler(ctx, sr, dn, lr, None, denoise_rate=1.0, max_push=a.push) for _ in range(S)]
+    objects = [] if a.host_rings else [_capi.TemporalUpscaler(ctx, sr, dn, lr, None, denoise_rate=1.0, max_push=a.push) for _ in range(S)]
     slots = _capi.TemporalUpscaler(ctx, sr, dn, lr, None, denoise_rate=1.0, max_push=a.push, max_streams=S)
     frames = torch.randint(0, 256, (S, a.h, a.w, 3), dtype=torch.uint8, device="cuda")
     one = [frames[i:i + 1] for i in range(S)]
     each, ids = [frames[i] for i in range(S)], list(range(S))
     forms = {"objects": lambda: [objects[i](one[i]) for i in range(S)], "rounds": lambda: slots.round(each, ids)}
+    if a.host_rings:
+        return streams_host_rings(a, slots, forms["rounds"], frames)
     for _ in range(max(a.warmup, 16)):   # the settle rounds: past the lag, every round returns S frames
         for f in forms.values():
             f()
@@ -134,6 +218,35 @@ def streams(a):
         o.close()
 
 
+def streams_host_rings(a, slots, resident_round, frames):
+    """The resident rounds against the same rounds through a started service with host rings, interleaved."""
+    S = a.streams
+    leg = HostRingLeg(a, frames.cpu())
+    try:
+        settle = max(a.warmup, 16)
+        for _ in range(settle):
+            resident_round()
+        _, ready = leg.run(settle + a.depth)
+        torch.cuda.synchronize()
+        assert all(slots.pending_of(i) == 16 for i in range(S)) and ready == S * (settle + a.depth - 16), f"the service is not past its lag ({ready} frames ready)"
+        res = {"rounds": [], "host_rings": []}
+        for _ in range(a.runs):
+            res["rounds"].append(1000.0 * S / timed(resident_round, a.iters))
+            sec, ready = leg.run(a.iters)
+            assert ready == S * a.iters
+            res["host_rings"].append(S * a.iters / sec)
+        emit(a, {"tool": "bsvd_online_time --streams --host-rings", "h": a.h, "w": a.w, "dtype": a.dtype, "variant": a.variant, "sr": a.sr + " x2",
+                 "streams": S, "max_push": a.push, "settle_rounds": settle, "timed_rounds": a.iters, "jobs_in_flight": a.depth,
+                 "frames_per_s": {k: [round(v, 2) for v in vs] for k, vs in res.items()},
+                 "spread_pct": {k: round(100 * (max(vs) - min(vs)) / min(vs), 2) for k, vs in res.items()},
+                 "ms_per_round_resident": round(1000.0 * S / max(res["rounds"]), 3),
+                 "host_over_resident": round(max(res["host_rings"]) / max(res["rounds"]), 4),
+                 "host_bytes_per_round": {"in": int(frames.numel()), "out": int(S * 3 * (2 * a.h) * (2 * a.w))}})
+    finally:
+        leg.close()
+        slots.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--h", type=int, default=720); ap.add_argument("--w", type=int, default=1280)
@@ -145,7 +258,12 @@ def main():
     ap.add_argument("--service", action="store_true", help="instead: frames/s of HipUpscalerService (FSRCNN x2, 4-frame jobs) with denoise_temporal on and off")
     ap.add_argument("--streams", type=int, default=0, help="instead: S live streams, one frame each per round - S one-stream objects in turn against one S-slot object")
     ap.add_argument("--sr", default="rrdbnet", choices=("rrdbnet", "fsrcnn"), help="the SR model behind the denoiser in --streams mode (x2)")
+    ap.add_argument("--host-rings", action="store_true", help="with --streams: the same rounds through a started service with pinned host rings, against the resident rounds")
+    ap.add_argument("--depth", type=int, default=3, help="--host-rings: jobs in flight")
+    ap.add_argument("--gather-kernel", action="store_true", help="instead (dev library): microseconds per launch of tround::gather_planes<4>")
     a = ap.parse_args()
+    if a.gather_kernel:
+        return gather_kernel(a)
     if a.streams:
         return streams(a)
     if a.service:
