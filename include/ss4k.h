@@ -483,6 +483,50 @@ int ss4k_upscaler_temporal_release_idle(ss4k_upscaler_temporal* up);
  * 0..max_streams-1, a rate that is not finite or is negative.  A stream at rate r gives the bytes of an object created with denoise_rate = r. */
 int ss4k_upscaler_temporal_set_denoise_rate_stream(ss4k_upscaler_temporal* up, int slot, float rate);
 
+/* ---- the frame-recurrent service chain (ss4k_frvsr_upscaler) with the ONLINE denoiser in front, per stream.  A recurrent generator warps hr_prev
+ * forward frame after frame, so the noise of a block-compressed stream accumulates where a per-frame network forgets it; the reference's main
+ * service always denoises before it upscales (fsrcnn_upscaler.py:245-284), its EGVSR service never got that step.  For one stream, frame t
+ * (uint8 HWC, any size):
+ *   1. lr_before_t = area(img / 255, lr_shape)
+ *   2. den_t = the online BSVD output for frame t of the stream whose 4-plane inputs are (lr_before, noise); noise is 0.05 for a stream's first
+ *      frame and 0.1 * rate after it.  den_t exists once frame t + 16 has entered, or at a flush.
+ *   3. lr_curr_t = 0.8 * clamp01(sharpen3x3_reflect(den_t)) + 0.2 * lr_before_t   (sharpen_ker(strength = 0.00002), fsrcnn_upscaler.py:279-281)
+ *   4. hr_t = FRNet(lr_curr_t, lr_curr_{t-1}, hr_{t-1}), zeros for a stream's first frame; then clamp, area to (out_h, out_w) if set, * 255
+ *      truncated to uint8 (egvsr_upscaler.py:197-212).  lr_prev is the denoised, blended previous frame.
+ *   5. nothing of the per-frame tail follows (no HR sharpening, no mean / std match): hr_prev stays the generator's own output.
+ * A stream returns nothing for its first 16 frames and one frame per frame after; a flush returns the up to 16 frames still inside, through the
+ * generator in order, and ends the stream - denoiser state, LR ring and recurrent state count as gone and the slot is free.
+ * frvsr (either generator, either degradation) and bsvd_stream_model (created with bsvd_stream = 1) are held, not owned.  lr_h and lr_w are at
+ * least 8 and divisible by 4; (out_h, out_w) = (0, 0) is None; max_push 1..64 frames of one slot per round; max_streams 1..64 SLOTS.  A slot owns
+ * one stream's denoiser state, its ring of 16 + max_push waiting LR frames and its recurrent state (2 x (lr + hr) fp32), all allocated with the
+ * stream's first frame; the models and the job buffers are shared.
+ * A ROUND is ss4k_upscale_round_temporal's: k_frames (1..64) frames of one (h, w), frame i of slot slots[i] at frames_dev[i] - HOST arrays, each
+ * frame uint8 HWC at any byte address.  The slots become ITEMS in order of first appearance (*n_items, item_slots[t], n_out_per_item[t]; both
+ * arrays hold k_frames entries, the counts are known without a synchronisation); out receives the ready frames contiguously, item after item,
+ * oldest first within an item.  Behind the denoiser the ready frames pass the generator in waves - wave r is frame r of every item that has
+ * one, as ONE batched step - so a wave costs a fixed number of launches whatever its size.  Every stream's bytes are those of the same frames
+ * through an object of its own, however the rounds cut them.  Refusals (SS4K_EINVAL: what ss4k_upscale_round_temporal refuses) are decided for
+ * the whole round before the first launch and change nothing, and so does a failed allocation of the round's buffers or a slot's ring and
+ * recurrent state.  A round that fails after its first launch resets every slot it named.
+ * _set_denoise_rate_stream, _stream_state_bytes_for, _state_bytes and _release_idle are their ss4k_upscaler_temporal_* counterparts (a slot's
+ * share includes its recurrent state).  Scene cuts are not available on this object. */
+typedef struct ss4k_frvsr_temporal ss4k_frvsr_temporal;
+int ss4k_frvsr_temporal_create(ss4k_ctx* ctx, ss4k_frvsr* frvsr, ss4k_model* bsvd_stream_model, int lr_h, int lr_w, int out_h, int out_w,
+                               double denoise_rate, int max_push, int max_streams, ss4k_frvsr_temporal** out);
+void ss4k_frvsr_temporal_destroy(ss4k_frvsr_temporal* up);
+int ss4k_frvsr_temporal_round(ss4k_frvsr_temporal* up, const uint8_t* const* frames_dev, const int* slots, int k_frames, int h, int w,
+                              uint8_t* out_dev, size_t out_capacity_bytes, int* n_out_per_item, int* item_slots, int* n_items, void* hip_stream);
+int ss4k_frvsr_temporal_flush_stream(ss4k_frvsr_temporal* up, int slot, uint8_t* out_nhwc_dev, size_t out_capacity_bytes, int* n_out,
+                                     void* hip_stream);
+/* drops the slot's stream without emitting what is inside */
+int ss4k_frvsr_temporal_reset_stream(ss4k_frvsr_temporal* up, int slot);
+int ss4k_frvsr_temporal_pending_stream(const ss4k_frvsr_temporal* up, int slot, int* frames);
+int ss4k_frvsr_temporal_set_denoise_rate_stream(ss4k_frvsr_temporal* up, int slot, float rate);
+int ss4k_frvsr_temporal_out_shape(const ss4k_frvsr_temporal* up, int* out_h, int* out_w);
+int ss4k_frvsr_temporal_state_bytes(const ss4k_frvsr_temporal* up, size_t* bytes);
+int ss4k_frvsr_temporal_stream_state_bytes_for(const ss4k_frvsr_temporal* up, size_t* bytes);
+int ss4k_frvsr_temporal_release_idle(ss4k_frvsr_temporal* up);
+
 /* ---- measurement hooks (bench.py: live per-kernel timing with HIP events on the launch stream) */
 /* When enabled, every launch of the dominant conv kernel is bracketed with hipEvents on the
  * stream it is launched on; ss4k_prof_read returns (#launches, total ms, algorithmic FLOPs). */

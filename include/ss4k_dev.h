@@ -151,6 +151,15 @@ int ss4k_dev_op_frvsrbi_bilinear4_add(ss4k_ctx* ctx, const float* conv, const fl
 int ss4k_dev_op_frvsrbi_bilinear4_add_items(ss4k_ctx* ctx, const float* conv, const float* const* lr, float* const* out, int n, int h, int w,
                                           void* hip_stream);
 
+/* ---- the glue kernel of the frame-recurrent chain with the online denoiser in front (csrc/frvsr_temporal.hip); route "frvt::denoised_in_items".
+ * den / lr / dst: HOST arrays of n_items (1..64) device pointers, 3 planes of (h, w) fp32 each; taps_dev: nine DEVICE floats.  One launch:
+ * dst[i] = 0.8 * clamp01(depthwise3x3_reflect(den[i], taps)) + 0.2 * lr[i], bit for bit ss4k_dev_op_depthwise_reflect (k = 3, clamp01,
+ * blend 0.8f / (float)(1 - 0.8)) per item.  SS4K_EINVAL before any launch: n_items outside 1..64, h < 2 or w < 2, 3 h w >= 2^31, a NULL or
+ * misaligned pointer, a destination inside its item's sources.  (Its prefix is ss4k_dev_op_frvsrt_, for the reason given at
+ * ss4k_dev_op_frvsrbi_ below.) */
+int ss4k_dev_op_frvsrt_denoised_in(ss4k_ctx* ctx, const float* const* den, const float* const* lr, float* const* dst, int n_items, int h, int w,
+                                   const float* taps_dev, void* hip_stream);
+
 /* ss4k_frvsr_step (include/ss4k.h) on a contiguous batch of n items, with the two tensors between FNet, the warp and SRNet copied out for
  * EVERY item: flow_out (n, 2, h, w) = the padded LR flow, s2d_out (n, 48, h, w) = the warped, space-to-depth hr_prev as SRNet's first conv read
  * it (an fp16 model: exactly the fp16 values), both fp32 device memory of the caller.  The public taps describe only the last item of a round.
@@ -220,6 +229,9 @@ int ss4k_dev_guard_poison_frvsr(ss4k_frvsr* m, ss4k_frvsr_upscaler* up, int* buf
 /* ... and for a temporal upscaler (ss4k_upscaler_temporal_*): the chain's intermediates and the job buffers its slots share (the packed denoiser
  * input, the denoised frames, the gathered LR planes, the blend).  What a slot owns - the denoiser's state, the ring, the detector - is state. */
 int ss4k_dev_guard_poison_temporal(ss4k_upscaler_temporal* up, int* buffers, size_t* bytes, size_t* bytes_256);
+/* ... and for the frame-recurrent chain with the denoiser in front (ss4k_frvsr_temporal_*): the packed denoiser input and the denoised frames.
+ * What a slot owns - the denoiser's state, the ring, lr_prev / hr_prev - is state; the two models' activations are theirs (_poison, _poison_frvsr). */
+int ss4k_dev_guard_poison_frvsr_temporal(ss4k_frvsr_temporal* up, int* buffers, size_t* bytes, size_t* bytes_256);
 /* Positive control without a fault: allocates a guarded buffer, writes one byte at payload - 1 and one at payload + need with hipMemset
  * (both inside the allocation), requires the check to report exactly those two zones with those offsets, releases the buffer and clears
  * the sticky list.  SS4K_EINVAL with a text if the guard does not see them (or if damage was already on record: run it first). */

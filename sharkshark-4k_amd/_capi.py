@@ -52,6 +52,11 @@ SYMBOLS = [
     "ss4k_upscaler_temporal_stream_state_bytes_for", "ss4k_upscaler_temporal_release_idle",
     # a denoise rate per slot
     "ss4k_upscaler_temporal_set_denoise_rate_stream",
+    # the frame-recurrent chain with the online denoiser in front
+    "ss4k_frvsr_temporal_create", "ss4k_frvsr_temporal_destroy", "ss4k_frvsr_temporal_round", "ss4k_frvsr_temporal_flush_stream",
+    "ss4k_frvsr_temporal_reset_stream", "ss4k_frvsr_temporal_pending_stream", "ss4k_frvsr_temporal_set_denoise_rate_stream",
+    "ss4k_frvsr_temporal_out_shape", "ss4k_frvsr_temporal_state_bytes", "ss4k_frvsr_temporal_stream_state_bytes_for",
+    "ss4k_frvsr_temporal_release_idle",
 ]
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
@@ -85,6 +90,9 @@ DEV_SYMBOLS = [
     "ss4k_dev_op_bsvd_online_shift_cuts", "ss4k_dev_op_bsvd_noise_planes",
     # the kernel of a temporal round (tests/test_gpu_temporal_streams_kernel.py)
     "ss4k_dev_op_temporal_gather", "ss4k_dev_op_temporal_gather_levels",
+    # the glue kernel of the frame-recurrent chain with the denoiser in front, and the poison of its job buffers
+    # (tests/test_gpu_frvsr_temporal_kernel.py, tests/test_gpu_frvsr_temporal_hygiene.py)
+    "ss4k_dev_op_frvsrt_denoised_in", "ss4k_dev_guard_poison_frvsr_temporal",
 ]
 
 
@@ -318,6 +326,22 @@ def load(path: str) -> C.CDLL:
         L.ss4k_upscaler_temporal_release_idle.argtypes = [vp]
     if hasattr(L, "ss4k_upscaler_temporal_set_denoise_rate_stream"):   # (absent from builds before the per-slot rate)
         L.ss4k_upscaler_temporal_set_denoise_rate_stream.argtypes = [vp, i, C.c_float]
+    if hasattr(L, "ss4k_frvsr_temporal_create"):   # (absent from builds before the denoiser in front of the frame-recurrent chain)
+        ip = C.POINTER(i)
+        L.ss4k_frvsr_temporal_create.argtypes = [vp, vp, vp, i, i, i, i, C.c_double, i, i, C.POINTER(vp)]
+        L.ss4k_frvsr_temporal_destroy.argtypes = [vp]; L.ss4k_frvsr_temporal_destroy.restype = None
+        L.ss4k_frvsr_temporal_round.argtypes = [vp, C.POINTER(vp), ip, i, i, i, vp, sz, ip, ip, ip, vp]
+        L.ss4k_frvsr_temporal_flush_stream.argtypes = [vp, i, vp, sz, ip, vp]
+        L.ss4k_frvsr_temporal_reset_stream.argtypes = [vp, i]
+        L.ss4k_frvsr_temporal_pending_stream.argtypes = [vp, i, ip]
+        L.ss4k_frvsr_temporal_set_denoise_rate_stream.argtypes = [vp, i, C.c_float]
+        L.ss4k_frvsr_temporal_out_shape.argtypes = [vp, ip, ip]
+        L.ss4k_frvsr_temporal_state_bytes.argtypes = [vp, C.POINTER(sz)]
+        L.ss4k_frvsr_temporal_stream_state_bytes_for.argtypes = [vp, C.POINTER(sz)]
+        L.ss4k_frvsr_temporal_release_idle.argtypes = [vp]
+    if hasattr(L, "ss4k_dev_op_frvsrt_denoised_in"):   # dev library only
+        L.ss4k_dev_op_frvsrt_denoised_in.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, i, vp, vp]
+        L.ss4k_dev_guard_poison_frvsr_temporal.argtypes = [vp, C.POINTER(i), C.POINTER(sz), C.POINTER(sz)]
     if hasattr(L, "ss4k_dev_op_temporal_gather"):   # dev library only
         L.ss4k_dev_op_temporal_gather.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, sz, i, C.c_uint64, C.c_float, C.c_float, vp, vp]
     if hasattr(L, "ss4k_dev_op_temporal_gather_levels"):   # dev library only
@@ -397,6 +421,14 @@ def guard_poison_temporal(upscaler, L: Optional[C.CDLL] = None) -> Tuple[int, in
     L = _guard_lib(L)
     n, b, b256 = C.c_int(), C.c_size_t(), C.c_size_t()
     _guard_rc(L, L.ss4k_dev_guard_poison_temporal(getattr(upscaler, "_h", upscaler), C.byref(n), C.byref(b), C.byref(b256)))
+    return n.value, int(b.value), int(b256.value)
+
+
+def guard_poison_frvsr_temporal(upscaler, L: Optional[C.CDLL] = None) -> Tuple[int, int, int]:
+    """``guard_poison`` for a ``TemporalFrvsrUpscaler``: the job buffers its slots share; every slot's state is left alone."""
+    L = _guard_lib(L)
+    n, b, b256 = C.c_int(), C.c_size_t(), C.c_size_t()
+    _guard_rc(L, L.ss4k_dev_guard_poison_frvsr_temporal(getattr(upscaler, "_h", upscaler), C.byref(n), C.byref(b), C.byref(b256)))
     return n.value, int(b.value), int(b256.value)
 
 
@@ -1225,3 +1257,113 @@ class FrvsrUpscaler:
         fout = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
         with torch.cuda.device(self.ctx.device):
             _check(lib().ss4k_frvsr_upscale_streams_at(self._h, ids, n, fin, h, w, fout, oh * ow * 3, _stream()))
+
+
+class TemporalFrvsrUpscaler:
+    """ss4k_frvsr_temporal: the frame-recurrent service chain (uint8 HWC frames -> uint8 NHWC) with the online BSVD denoiser in front of the
+    generator, per stream.  ``model`` is a ``Frvsr`` (either generator, either degradation), ``denoise`` a BSVD ``Model`` built with
+    ``bsvd_stream=True``; both are held, not owned.  A stream returns nothing for its first 16 frames and one frame per frame after; ``flush``
+    returns the up to 16 frames still inside and ends it.  The methods mirror ``TemporalUpscaler``'s."""
+
+    def __init__(self, ctx: Context, model: Frvsr, denoise: Model, lr_shape, output_shape=None, denoise_rate: float = 1.0, max_push: int = 4,
+                 max_streams: int = 1):
+        self.ctx, self.model, self.denoise, self.max_push, self.max_streams = ctx, model, denoise, int(max_push), int(max_streams)
+        self.lr_shape = (int(lr_shape[0]), int(lr_shape[1]))
+        oh, ow = (0, 0) if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
+        h = C.c_void_p()
+        with torch.cuda.device(ctx.device):
+            _check(lib().ss4k_frvsr_temporal_create(ctx._h, model._h, denoise._h, self.lr_shape[0], self.lr_shape[1], oh, ow, float(denoise_rate),
+                                                    self.max_push, self.max_streams, C.byref(h)))
+        self._h, self.lag = h, 16
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().ss4k_frvsr_temporal_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def out_shape(self):
+        oh, ow = C.c_int(), C.c_int()
+        _check(lib().ss4k_frvsr_temporal_out_shape(self._h, C.byref(oh), C.byref(ow)))
+        return oh.value, ow.value
+
+    def pending_of(self, slot: int) -> int:
+        """Frames of a slot's stream that went in and have not come back."""
+        k = C.c_int()
+        _check(lib().ss4k_frvsr_temporal_pending_stream(self._h, int(slot), C.byref(k)))
+        return k.value
+
+    @property
+    def pending(self) -> int:
+        return self.pending_of(0)
+
+    def state_bytes(self) -> int:
+        b = C.c_size_t()
+        _check(lib().ss4k_frvsr_temporal_state_bytes(self._h, C.byref(b)))
+        return int(b.value)
+
+    def stream_state_bytes_for(self) -> int:
+        """Device bytes one slot holds while its stream runs (the denoiser's state, the ring of waiting LR planes, lr / hr twice): known before
+        any push."""
+        b = C.c_size_t()
+        _check(lib().ss4k_frvsr_temporal_stream_state_bytes_for(self._h, C.byref(b)))
+        return int(b.value)
+
+    def release_idle(self) -> None:
+        """Frees the state of every slot without a running stream; ``state_bytes`` drops by their share."""
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_frvsr_temporal_release_idle(self._h))
+
+    def set_denoise_rate(self, slot: int, rate: float) -> None:
+        """The denoise rate of one slot's stream: its frames enter at the level 0.1 * rate from the next round on.  It ends with the stream."""
+        _check(lib().ss4k_frvsr_temporal_set_denoise_rate_stream(self._h, int(slot), float(rate)))
+
+    def reset(self, slot: int = 0) -> None:
+        _check(lib().ss4k_frvsr_temporal_reset_stream(self._h, int(slot)))
+
+    _out_view = TemporalUpscaler._out_view
+
+    def flush(self, slot: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The frames still inside a slot's stream, through the generator in order, oldest first; the stream ends and the slot is free."""
+        left = self.pending_of(slot)
+        oh, ow = self.out_shape()
+        out = torch.empty((left, oh, ow, 3), dtype=torch.uint8, device=self.ctx.device) if out is None else self._out_view(out, oh, ow)
+        k = C.c_int()
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_frvsr_temporal_flush_stream(self._h, int(slot), out.data_ptr() if out.numel() else None, out.numel(), C.byref(k), _stream()))
+        return out[:k.value]
+
+    def round(self, frames, slots, out: Optional[torch.Tensor] = None):
+        """One round (ss4k_frvsr_temporal_round), as ``TemporalUpscaler.round``: ``frames`` is a list of (h, w, 3) uint8 device tensors or views
+        with contiguous bytes at any byte address, frame i of slot ``slots[i]``; returns ``(out, [(slot, count), ...])``, the ready frames slot
+        after slot in order of first appearance and oldest first within a slot."""
+        k = len(frames)
+        if k != len(slots):
+            raise ValueError(f"{k} frames and {len(slots)} slots")
+        for f in frames:
+            if not (isinstance(f, torch.Tensor) and f.is_cuda and f.dtype == torch.uint8 and f.ndim == 3 and f.shape[-1] == 3 and f.is_contiguous()):
+                raise ValueError("a round takes (h, w, 3) uint8 device tensors whose bytes are contiguous")
+        h, w = (int(frames[0].shape[0]), int(frames[0].shape[1])) if k else (1, 1)
+        if any(tuple(f.shape) != (h, w, 3) for f in frames):
+            raise ValueError("the frames of a round have one size")
+        oh, ow = self.out_shape()
+        out = torch.empty((max(k, 1), oh, ow, 3), dtype=torch.uint8, device=self.ctx.device) if out is None else self._out_view(out, oh, ow)
+        ptrs = (C.c_void_p * max(k, 1))(*[f.data_ptr() for f in frames])
+        ids = (C.c_int * max(k, 1))(*[int(s) for s in slots])
+        counts, item_slots, n_items = (C.c_int * max(k, 1))(), (C.c_int * max(k, 1))(), C.c_int()
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_frvsr_temporal_round(self._h, ptrs, ids, k, h, w, out.data_ptr() if out.numel() else None, out.numel(), counts, item_slots,
+                                                   C.byref(n_items), _stream()))
+        items = [(int(item_slots[t]), int(counts[t])) for t in range(n_items.value)]
+        return out[:sum(c for _, c in items)], items
+
+    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
+        """A round of slot 0: (n, h, w, 3) uint8, 1 <= n <= max_push -> the frames that became ready."""
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.ndim == 4 and frames.shape[-1] == 3
+        frames = frames.contiguous()
+        return self.round([frames[i] for i in range(frames.shape[0])], [0] * frames.shape[0])[0]

@@ -16,7 +16,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libss4k_hip.so")
 LIB_DEV = os.path.join(HERE, "libss4k_hip_dev.so")
 SOURCES = ["conv_mfma.hip", "conv_pair.hip", "conv_dense.hip", "conv_w16.hip", "conv_w16n.hip", "conv_up2.hip", "glue.hip", "fsrcnn.hip", "fsrcnn_weights.cpp", "frvsr.hip", "frvsr_bi.hip", "pack.cpp", "models.cpp", "frvsr.cpp", "frvsr_teco.cpp", "upscaler.cpp", "api.cpp", "api_dev.cpp",
-           "bsvd_online.hip", "bsvd_online.cpp", "upscaler_temporal.cpp", "temporal_round.hip", "api_bsvd_online.cpp", "scene_cut.hip", "api_scene_cut.cpp"]
+           "bsvd_online.hip", "bsvd_online.cpp", "upscaler_temporal.cpp", "temporal_round.hip", "api_bsvd_online.cpp", "scene_cut.hip", "api_scene_cut.cpp",
+           "frvsr_temporal.hip", "frvsr_temporal.cpp", "api_frvsr_temporal.cpp"]
 # fsrcnn.hip: no SLP vectorisation - left on, the tail's overlap-add (two adjacent output columns per lane) is packed into v_pk_add_f32,
 # which cannot take a DPP operand: 20 of its 35 wave shifts per row then become separate v_mov_b32_dpp, and packed fp32 adds are slower
 # than two plain ones beside MFMAs (MI355X_MICROARCH.md, cycle constants).  Without it every shift is folded into its add (v_add_f32_dpp)

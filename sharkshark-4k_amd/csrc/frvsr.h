@@ -186,6 +186,7 @@ struct FrvsrUpscaler {
   size_t state_bytes() const;
  private:
   friend struct SceneCut;   // (scene_cut.h: the detector makes a round's refusals - check_round - before its own launches, from outside)
+  friend struct FrvsrTemporal;   // (frvsr_temporal.h: the chain with the online denoiser in front runs its waves as rounds, from outside)
   // a round's per-item pointers into the slots' state: lr_curr (= lr_dst, as a table), lr_prev, hr_prev, hr_curr
   struct RoundPtrs { const float* lr_curr[SS4K_FRVSR_MAX_STREAMS]; const float* lr_prev[SS4K_FRVSR_MAX_STREAMS]; FrvsrPtrs lr_dst, hr_prev, hr_curr; };
   // every refusal of a round, before any slot changes; area_chain: the round resizes with op_area (round), not inside the frame kernels (round_at)

@@ -1,0 +1,241 @@
+// The frame-recurrent chain with a LAGGED denoiser in front (frvsr_temporal.h): TemporalUpscaler::round's steps up to the denoiser's pushes -
+// frames into each stream's LR ring, one gather of the packed denoiser input, one push per item - and then, instead of one tail over the ready
+// frames, the recurrent generator in waves (frvsr_temporal_plan.h): per wave one open_slots, ONE glue launch that writes every item's
+// 0.8 * clamp01(sharpen(den)) + 0.2 * lr_before into its stream's lr buffer (frvsr_temporal.hip), one batched step, close_slots and one launch
+// that writes the wave's frames where they go in the output.  The generator's files are not touched: the waves are FrvsrUpscaler rounds made
+// from outside, as the scene-cut detector makes its refusals.
+#include "frvsr_temporal.h"
+#include "upscaler_temporal.h"   // op_tround_gather, TroundTable
+#include <cmath>
+
+namespace ss4k {
+
+// sharpen_ker(strength), fsrcnn_upscaler.py:54-84: the taps Upscaler::upload_taps uploads as k_sharp (upscaler.cpp), the same expressions
+static std::vector<float> frvt_sharpen_taps(double strength) {
+  std::vector<float> t(9);
+  const float s = (float)strength, one_m = (float)(1.0 - strength);
+  float sum = 0.f;
+  for (int i = 0; i < 9; ++i) {
+    const float sharp = i == 4 ? 9.f : -1.f, ident = i == 4 ? 1.f : 0.f;
+    t[i] = sharp * s + one_m * ident; sum += t[i];
+  }
+  for (auto& v : t) v /= sum;
+  return t;
+}
+
+void FrvsrTemporal::create(ss4k_ctx* c, Frvsr* m, Model* bsvd_stream_model, int lr_h, int lr_w, int out_h, int out_w, double rate, int max_push_,
+                           int max_streams_) {
+  SS4K_REQUIRE(c && m && bsvd_stream_model, "frvsr temporal: NULL argument");
+  SS4K_REQUIRE(max_streams_ >= 1 && max_streams_ <= temporal_round::MAX_STREAMS, "frvsr temporal: max_streams must be in 1..64");
+  SS4K_REQUIRE(lr_h >= 8 && lr_w >= 8, "lr_shape must be at least 8 x 8");
+  SS4K_REQUIRE(lr_h % 4 == 0 && lr_w % 4 == 0, "frvsr temporal: lr_shape must be divisible by 4 (BSVD)");
+  SS4K_REQUIRE((out_h == 0 && out_w == 0) || (out_h > 0 && out_w > 0), "output_shape is (0, 0) or positive");
+  SS4K_REQUIRE((double)lr_h * lr_w * 16.0 < 2147483648.0, "lr_shape: the output frame must hold fewer than 2^31 pixels");
+  SS4K_REQUIRE(std::isfinite(rate) && rate >= 0.0, "frvsr temporal: a denoise rate is finite and not negative");
+  std::vector<std::unique_ptr<FrvtSlot>> made;
+  for (int s = 0; s < max_streams_; ++s) {
+    made.push_back(std::make_unique<FrvtSlot>());
+    made.back()->on.create(c, bsvd_stream_model, max_push_);   // (refuses max_push outside 1..64 and a model that is not a streaming BSVD)
+  }
+  const std::vector<float> taps = frvt_sharpen_taps(0.00002);
+  k_sharp.ensure(taps.size() * 4);
+  SS4K_HIP(hipMemcpy(k_sharp.ptr, taps.data(), taps.size() * 4, hipMemcpyHostToDevice));
+  slots = std::move(made);
+  ctx = c; denoise_rate = rate; max_push = max_push_;
+  up.ctx = c; up.m = m; up.lr_h = lr_h; up.lr_w = lr_w; up.out_h = out_h; up.out_w = out_w;
+  up.slots.resize((size_t)max_streams_);
+#ifdef SS4K_DEV
+  // guard mode (upscaler.h): a round reads nothing of these that it has not written.  The rings, the denoisers' state and lr / hr are state
+  for (DevBuf* b : {&lr4, &den}) b->transient = true;
+#endif
+}
+
+FrvtSlot& FrvsrTemporal::slot(int s) {
+  SS4K_REQUIRE(s >= 0 && s < max_streams(), "frvsr temporal: a slot outside 0..max_streams-1");
+  return *slots[s];
+}
+const FrvtSlot& FrvsrTemporal::slot(int s) const {
+  SS4K_REQUIRE(s >= 0 && s < max_streams(), "frvsr temporal: a slot outside 0..max_streams-1");
+  return *slots[s];
+}
+
+static size_t recurrent_bytes(const FrvsrUpscaler::Slot& r) { return r.lr[0].bytes + r.lr[1].bytes + r.hr[0].bytes + r.hr[1].bytes; }
+
+size_t FrvsrTemporal::state_bytes() const {
+  size_t t = 0;
+  for (int s = 0; s < max_streams(); ++s) t += slots[s]->on.state_bytes() + slots[s]->ring.bytes + recurrent_bytes(up.slots[s]);
+  return t;
+}
+
+size_t FrvsrTemporal::stream_state_bytes_for() const {
+  const auto r256 = [](size_t b) { return (b + 255) & ~size_t(255); };
+  const size_t lr_b = (size_t)3 * up.lr_h * up.lr_w * 4;
+  return slots[0]->on.state_bytes_for(up.lr_h, up.lr_w) + r256(lr_b * ring_frames()) + 2 * r256(lr_b) + 2 * r256(16 * lr_b);
+}
+
+void FrvsrTemporal::release_idle() {
+  for (int s = 0; s < max_streams(); ++s) {
+    FrvtSlot& t = *slots[s];
+    if (t.running()) continue;
+    t.rate = -1;
+    t.on.release_state(); t.ring.release();
+    FrvsrUpscaler::Slot& r = up.slots[s];
+    r.have_state = false;
+    for (int k = 0; k < 2; ++k) { r.lr[k].release(); r.hr[k].release(); }
+  }
+}
+
+void FrvsrTemporal::reset(int si) {
+  FrvtSlot& s = slot(si);
+  s.on.reset(); s.first_frame = true; s.pushed = s.emitted = 0; s.rate = -1;
+  up.slots[si].have_state = false;   // the next frame through the generator sees zero lr_prev / hr_prev
+}
+
+void FrvsrTemporal::set_denoise_rate(int si, float rate) {
+  FrvtSlot& s = slot(si);
+  SS4K_REQUIRE(std::isfinite(rate) && rate >= 0.f, "frvsr temporal: a denoise rate is finite and not negative");
+  s.rate = (double)rate;
+}
+
+// what the launchers of a round or a flush would refuse, restated: none of them may stop either half way
+void FrvsrTemporal::check_sizes(int h, int w) const {
+  const int lh = up.lr_h, lw = up.lr_w, H = 4 * lh, W = 4 * lw;
+  int oh, ow; up.out_shape(&oh, &ow);
+  SS4K_REQUIRE((double)(bsvd_online::LAG / 2 + max_push) * lh * lw < 2147483648.0, "bsvd online push: a carried plane holds at most 2^31 pixels");
+  SS4K_REQUIRE((double)h * lh < 2147483648.0 && (double)w * lw < 2147483648.0 && (double)H * oh < 2147483648.0 && (double)W * ow < 2147483648.0,
+               "frvsr temporal: frame sizes whose area window bounds overflow");
+  SS4K_REQUIRE(lh >= 2 && lw >= 2 && (double)lh * lw * 3.0 < 2147483648.0, "frvsr denoised in: a frame of at least 2 x 2 and fewer than 2^31 values");
+}
+
+void FrvsrTemporal::run_wave(const frvsr_temporal::Wave& wv, const float* const* den_of, const float* const* ring_of, uint8_t* const* out_of,
+                             hipStream_t st) {
+  const int lh = up.lr_h, lw = up.lr_w;
+  int oh, ow; up.out_shape(&oh, &ow);
+  int32_t ids[FRVT_MAX_ITEMS];
+  for (int i = 0; i < wv.n; ++i) ids[i] = wv.slot[i];
+  FrvsrUpscaler::RoundPtrs r{};
+  up.open_slots(ids, wv.n, st, r);
+  FrvtTable tab{}; FrvsrFramesOut fout{};
+  for (int i = 0; i < wv.n; ++i) { tab.den[i] = den_of[i]; tab.lr[i] = ring_of[i]; tab.dst[i] = r.lr_dst.p[i]; fout.p[i] = out_of[i]; }
+  // clamp(sharpen(den)) * 0.8 + 0.2 * lr   (fsrcnn_upscaler.py:279-281; Upscaler::single_tail's constants)
+  up.m->timed(FRV_GLUE, st, [&] { op_frvt_denoised_in_items(tab, wv.n, lh, lw, k_sharp.as<float>(), 0.8f, (float)(1 - 0.8), st); });
+  up.m->step_items(Frvsr::Items{r.lr_curr, r.lr_prev, &r.hr_prev, &r.hr_curr, true}, wv.n, lh, lw, st);
+  up.close_slots(ids, wv.n);
+  up.m->timed(FRV_GLUE, st, [&] { op_frames_out_items(r.hr_curr, fout, wv.n, 4 * lh, 4 * lw, oh, ow, st); });
+}
+
+int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, int h, int w, uint8_t* out, size_t out_capacity_bytes,
+                         int* n_out_per_item, int* item_slots, int* n_items, hipStream_t st) {
+  const int lh = up.lr_h, lw = up.lr_w;
+  const size_t plane = (size_t)lh * lw, frame = 3 * plane;
+  // ---- every refusal for the whole round, before the first launch and before any state changes
+  SS4K_REQUIRE(fr && slot_ids && n_out_per_item && item_slots && n_items, "frvsr temporal round: NULL argument");
+  SS4K_REQUIRE(h > 0 && w > 0, "frvsr temporal round: empty frames");
+  int oh, ow; up.out_shape(&oh, &ow);
+  const size_t out_frame = (size_t)oh * ow * 3;
+  bsvd_online::State states[temporal_round::MAX_STREAMS];
+  for (int s = 0; s < max_streams(); ++s) states[s] = slots[s]->on.state;
+  const temporal_round::Plan p = temporal_round::make_round(slot_ids, k, states, max_push, max_streams(), (long long)(out_capacity_bytes / out_frame));
+  SS4K_REQUIRE(!p.refusal, p.refusal ? p.refusal : "");
+  for (int i = 0; i < k; ++i) SS4K_REQUIRE(fr[i], "frvsr temporal round: NULL frame");
+  SS4K_REQUIRE(out || p.total == 0, "frvsr temporal round: NULL output for a round that returns frames");
+  const frvsr_temporal::Waves waves = frvsr_temporal::make_waves(p);
+  for (int r = 0; r < waves.n_waves; ++r) {
+    int32_t ids[FRVT_MAX_ITEMS];
+    for (int i = 0; i < waves.w[r].n; ++i) ids[i] = waves.w[r].slot[i];
+    up.check_round(ids, waves.w[r].n, h, w, false);
+  }
+  check_sizes(h, w);
+  // ---- allocations, still before the first launch: one that fails leaves every stream as it was (a slot that gained buffers keeps them).  A
+  // slot's recurrent state is made here, with the stream's first frame, not 16 frames later: what a running slot holds does not depend on
+  // how far its stream has come.  What a slot's denoiser allocates with its first push is BsvdOnline's own and happens inside step 3.
+  lr4.ensure(plane * 4 * k * 4);
+  den.ensure(frame * std::max(p.total, max_push) * 4);
+  for (int t = 0; t < p.n_items; ++t) {
+    slots[p.items[t].slot]->ring.ensure(frame * ring_frames() * 4);
+    FrvsrUpscaler::Slot& rs = up.slots[p.items[t].slot];
+    for (int b = 0; b < 2; ++b) { rs.lr[b].ensure(frame * 4); rs.hr[b].ensure(frame * 16 * 4); }
+  }
+  try {
+    // ---- 1. frames in: one launch, every frame from where it lies into its stream's ring slot
+    FrvsrFramesIn fin{}; FrvsrPtrs dst{}; TroundTable tab{};
+    unsigned long long start_bits = 0;
+    for (int t = 0; t < p.n_items; ++t) {
+      const temporal_round::Item& it = p.items[t];
+      FrvtSlot& s = *slots[it.slot];
+      for (int j = 0; j < it.n; ++j) {
+        const int q = it.first + j;
+        fin.p[q] = fr[p.order[q]];
+        dst.p[q] = s.ring.as<float>() + frame * p.ring_in[q];
+        tab.src[q] = dst.p[q];
+        tab.level[q] = level(s);
+      }
+      if (s.first_frame) start_bits |= 1ull << it.first;
+    }
+    up.m->timed(FRV_GLUE, st, [&] { op_frames_in_items(fin, dst, k, h, w, lh, lw, st); });
+    // ---- 2. the packed (k, 4, lh, lw) denoiser input, noise planes included: one launch
+    op_tround_gather(tab, lr4.as<float>(), k, plane, 4, start_bits, 0.05f, st);
+    // ---- 3. one push per item, one after the other: they share the model's activation slots
+    for (int t = 0; t < p.n_items; ++t) {
+      const temporal_round::Item& it = p.items[t];
+      FrvtSlot& s = *slots[it.slot];
+      s.first_frame = false;
+      const int got = s.on.push(lr4.as<float>() + plane * 4 * it.first, it.n, lh, lw, den.as<float>() + frame * it.den_off, (size_t)std::max(it.emitted, 1), st);
+      s.pushed += it.n;
+      SS4K_REQUIRE(got == it.emitted, "internal: the online denoiser emitted another number of frames than its plan");
+    }
+    // ---- 4. the generator, wave after wave: frame den_off + r of every item that has one
+    for (int r = 0; r < waves.n_waves; ++r) {
+      const frvsr_temporal::Wave& wv = waves.w[r];
+      const float* den_of[FRVT_MAX_ITEMS]; const float* ring_of[FRVT_MAX_ITEMS]; uint8_t* out_of[FRVT_MAX_ITEMS];
+      for (int i = 0; i < wv.n; ++i) {
+        den_of[i] = den.as<float>() + frame * wv.out[i];
+        ring_of[i] = slots[wv.slot[i]]->ring.as<float>() + frame * p.ring_out[wv.out[i]];
+        out_of[i] = out + out_frame * wv.out[i];
+      }
+      run_wave(wv, den_of, ring_of, out_of, st);
+      for (int i = 0; i < wv.n; ++i) slots[wv.slot[i]]->emitted += 1;
+    }
+  } catch (...) {   // a round that failed half way: none of its streams can go on, neither half of them
+    for (int t = 0; t < p.n_items; ++t) reset(p.items[t].slot);
+    throw;
+  }
+  for (int t = 0; t < p.n_items; ++t) { n_out_per_item[t] = p.items[t].emitted; item_slots[t] = p.items[t].slot; }
+  *n_items = p.n_items;
+  return p.total;
+}
+
+int FrvsrTemporal::flush(int si, uint8_t* out, size_t out_capacity_bytes, hipStream_t st) {
+  FrvtSlot& s = slot(si);
+  const int left = s.on.pending();
+  if (left == 0) { reset(si); return 0; }
+  // ---- every refusal before the first launch
+  SS4K_REQUIRE(out, "frvsr temporal flush: NULL argument");
+  const int lh = up.lr_h, lw = up.lr_w;
+  int oh, ow; up.out_shape(&oh, &ow);
+  const size_t out_frame = (size_t)oh * ow * 3, frame = (size_t)3 * lh * lw;
+  SS4K_REQUIRE(out_capacity_bytes >= (size_t)left * out_frame, "frvsr temporal flush: output buffer too small for the pending frames");
+  const frvsr_temporal::Waves waves = frvsr_temporal::make_flush(si, left);
+  SS4K_REQUIRE(waves.n_waves == left, "internal: a flush of more frames than a slot can hold");
+  const int32_t id = si;
+  up.check_round(&id, 1, lh, lw, false);
+  check_sizes(lh, lw);
+  den.ensure(frame * left * 4);
+  try {
+    const int got = s.on.flush(den.as<float>(), (size_t)left, st);
+    SS4K_REQUIRE(got == left, "internal: the online denoiser drained another number of frames than were pending");
+    for (int r = 0; r < left; ++r) {   // the generator takes a stream's frames one at a time
+      const float* den_of = den.as<float>() + frame * r;
+      const float* ring_of = s.ring.as<float>() + frame * ((s.emitted + r) % ring_frames());
+      uint8_t* out_of = out + out_frame * r;
+      run_wave(waves.w[r], &den_of, &ring_of, &out_of, st);
+    }
+  } catch (...) {
+    reset(si);
+    throw;
+  }
+  reset(si);   // the stream has ended: the slot is free
+  return left;
+}
+
+}  // namespace ss4k

@@ -1,0 +1,73 @@
+// The one glue kernel of the frame-recurrent chain with the online denoiser in front (frvsr_temporal.cpp, FrvsrTemporal::round / flush):
+// frvt::denoised_in_items turns a wave's denoised frames into the generator's input, each written into its own stream's lr buffer,
+//   lr_curr = 0.8 * clamp01(sharpen3x3_reflect(den)) + 0.2 * lr_before            (fsrcnn_upscaler.py:279-281)
+// in ONE launch whatever the wave's size.  The value is bit for bit what glue::depthwise_reflect<3> (glue.hip) gives with clamp and blend: the
+// loops below are that kernel's - the same tap order, the row loop kept rolled, the same `acc += tap * px` and `acc * a + b * src` expressions,
+// the taps read from the same device table and the two blend factors passed as kernel arguments - so the compiler contracts them the same way.
+// Do not "improve" the arithmetic: tests/test_gpu_frvsr_temporal_kernel.py compares the bits.
+#include "frvsr_temporal.h"
+
+#ifndef SS4K_LAUNCH_OK
+#define SS4K_LAUNCH_OK() SS4K_HIP(hipGetLastError())
+#endif
+
+namespace ss4k {
+
+// torch's 'reflect': -1 -> 1, n -> n - 2 (glue.hip's reflect)
+__device__ __forceinline__ int frvt_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
+
+// blockIdx.z = 3 * item + plane, blockIdx.y strides over the rows, blockIdx.x over a row's pixels.  The item is uniform over the workgroup, so
+// its three table entries are scalar loads from the kernel arguments: no scratch, no device table.  Every output pixel is written by exactly one
+// thread, and no workgroup waits for another.
+__global__ __launch_bounds__(256) void k_frvt_denoised_in(FrvtTable tab, const float* __restrict__ taps, int n_items, int h, int w,
+                                                          float blend_a, float blend_b) {
+  constexpr int K = 3, r = 1;
+  const int item = blockIdx.z / 3, pl = blockIdx.z % 3;
+  if (item >= n_items) return;
+  const float* __restrict__ src = tab.den[item] + (size_t)pl * h * w;
+  const float* __restrict__ blend_src = tab.lr[item];
+  float* __restrict__ out = tab.dst[item];
+  for (int y = blockIdx.y; y < h; y += gridDim.y) {
+    const size_t row = ((size_t)pl * h + y) * w;
+    for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < w; x += gridDim.x * blockDim.x) {
+      int xi[K];
+#pragma unroll
+      for (int kx = 0; kx < K; ++kx) xi[kx] = frvt_reflect(x + kx - r, w);
+      float acc = 0.f;
+#pragma unroll 1
+      for (int ky = 0; ky < K; ++ky) {
+        const float* sr = src + (size_t)frvt_reflect(y + ky - r, h) * w;
+#pragma unroll
+        for (int kx = 0; kx < K; ++kx) acc += taps[ky * K + kx] * sr[xi[kx]];
+      }
+      acc = fminf(fmaxf(acc, 0.f), 1.f);
+      acc = acc * blend_a + blend_b * blend_src[row + x];
+      out[row + x] = acc;
+    }
+  }
+}
+
+void op_frvt_denoised_in_items(const FrvtTable& tab, int n_items, int h, int w, const float* taps_dev, float blend_a, float blend_b, hipStream_t st) {
+  // every refusal before the launch
+  SS4K_REQUIRE(n_items >= 1 && n_items <= FRVT_MAX_ITEMS, "frvsr denoised in: 1..64 items");
+  SS4K_REQUIRE(h >= 2 && w >= 2, "frvsr denoised in: reflect padding of 1 needs a plane of at least 2 x 2, as torch requires");
+  SS4K_REQUIRE((double)h * (double)w * 3.0 < 2147483648.0, "frvsr denoised in: a frame holds fewer than 2^31 values");
+  SS4K_REQUIRE(taps_dev, "frvsr denoised in: NULL taps");
+  const size_t frame_bytes = (size_t)3 * h * w * 4;
+  for (int i = 0; i < n_items; ++i) {
+    SS4K_REQUIRE(tab.den[i] && tab.lr[i] && tab.dst[i], "frvsr denoised in: NULL item pointer");
+    SS4K_REQUIRE((((uintptr_t)tab.den[i] | (uintptr_t)tab.lr[i] | (uintptr_t)tab.dst[i]) & 3) == 0, "frvsr denoised in: misaligned item pointer");
+    // a pixel's neighbours are read while other pixels are written: the destination may not lie inside the item's sources
+    const char* d = reinterpret_cast<const char*>(tab.dst[i]);
+    for (const float* src : {tab.den[i], tab.lr[i]}) {
+      const char* s = reinterpret_cast<const char*>(src);
+      SS4K_REQUIRE(s + frame_bytes <= d || d + frame_bytes <= s, "frvsr denoised in: a destination overlaps its item's sources");
+    }
+  }
+  SS4K_GLUE_ROUTE("frvt::denoised_in_items");
+  const dim3 grid((unsigned)std::min((w + 255) / 256, 64), (unsigned)std::min(h, 65535), (unsigned)(3 * n_items));
+  hipLaunchKernelGGL(k_frvt_denoised_in, grid, dim3(256), 0, st, tab, taps_dev, n_items, h, w, blend_a, blend_b);
+  SS4K_LAUNCH_OK();
+}
+
+}  // namespace ss4k

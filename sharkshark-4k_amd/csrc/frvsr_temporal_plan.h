@@ -1,0 +1,57 @@
+// The tail of one round of the frame-recurrent chain with the online denoiser in front (frvsr_temporal.cpp, FrvsrTemporal::round).  The round
+// itself - items, ring slots, den_off, refusals - is temporal_round::make_round, unchanged.  What differs is what follows the denoiser: the
+// per-frame chain runs ONE tail over everything that became ready, the recurrent generator cannot - frame t of a stream needs frame t - 1's
+// output.  So the ready frames leave in WAVES: wave r holds, for every item that emitted more than r frames, that item's r-th ready frame.  A wave
+// is one FrvsrUpscaler round: its slots are distinct because the items of a round are (one item per slot), and a stream's frames pass in order
+// because wave r comes before wave r + 1.  The number of waves is the largest `emitted` of the round.
+// A pure function of the plan: no GPU call, no allocation and no #include - bsvd_online_plan.h and temporal_round_plan.h go in front of it.
+// tests/test_frvsr_temporal_plan_cpu.py replays random rounds and flushes against a naive per-stream simulation.
+#pragma once
+
+namespace ss4k {
+namespace frvsr_temporal {
+
+constexpr int MAX_WAVES = temporal_round::MAX_FRAMES;   // an item emits at most max_push <= 64 frames
+constexpr int MAX_WAVE_ITEMS = temporal_round::MAX_STREAMS;
+
+struct Wave {
+  int n = 0;                       // entries: 1..max_streams
+  int slot[MAX_WAVE_ITEMS] = {};   // the stream slot of entry i (distinct within the wave)
+  int item[MAX_WAVE_ITEMS] = {};   // the round's item it belongs to (flush: 0)
+  int out[MAX_WAVE_ITEMS] = {};    // its index in the denoised buffer and in the output, in frames: den_off + r
+};
+
+struct Waves {
+  int n_waves = 0;                 // max(emitted) over the items
+  Wave w[MAX_WAVES];
+};
+
+// the waves of a round that make_round accepted (a refused plan has none)
+inline Waves make_waves(const temporal_round::Plan& p) {
+  Waves v;
+  if (p.refusal) return v;
+  for (int t = 0; t < p.n_items; ++t)
+    if (p.items[t].emitted > v.n_waves) v.n_waves = p.items[t].emitted;
+  for (int r = 0; r < v.n_waves; ++r) {
+    Wave& wv = v.w[r];
+    for (int t = 0; t < p.n_items; ++t) {
+      const temporal_round::Item& it = p.items[t];
+      if (it.emitted <= r) continue;
+      wv.slot[wv.n] = it.slot; wv.item[wv.n] = t; wv.out[wv.n] = it.den_off + r;
+      ++wv.n;
+    }
+  }
+  return v;
+}
+
+// a flush of the n frames still inside one slot (0..LAG): n waves of one, output frame r in wave r
+inline Waves make_flush(int slot, int n) {
+  Waves v;
+  if (n < 0 || n > MAX_WAVES) return v;
+  v.n_waves = n;
+  for (int r = 0; r < n; ++r) { v.w[r].n = 1; v.w[r].slot[0] = slot; v.w[r].item[0] = 0; v.w[r].out[0] = r; }
+  return v;
+}
+
+}  // namespace frvsr_temporal
+}  // namespace ss4k

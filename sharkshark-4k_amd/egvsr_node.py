@@ -126,6 +126,9 @@ class EgvsrNode(WorkerPool):
 
     def __init__(self, devices: Union[int, Sequence[int], None] = None, max_streams: int = 1, job_frames: int = 4, host_frames=True,
                  host_slots: int = 6, output_shape="unset", service_cls=HipEgvsrUpscalerService, push_timeout: float = 10.0, **service_kwargs):
+        if service_kwargs.get("denoise_temporal") and isinstance(service_cls, type) and issubclass(service_cls, HipEgvsrUpscalerService):
+            raise ValueError("EgvsrNode(denoise_temporal=True) is not supported: the node feeds its workers host-ring jobs, which a denoised "
+                             "frame-recurrent worker refuses (run HipEgvsrUpscalerService(denoise_temporal=True) as one worker)")
         super().__init__(devices)
         if not host_frames:
             raise ValueError("EgvsrNode takes host frames: host_frames is True (frames of the service's lr_shape) or (H, W)")

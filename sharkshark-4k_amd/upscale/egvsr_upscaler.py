@@ -27,6 +27,18 @@ hard cut, zeroes that stream's ``lr_prev`` / ``hr_prev`` before the step - the r
 into the new one.  T is a mean absolute byte difference in (0, 255]; each job's profiler carries ``egvsr.scene_cuts``, the worker's cuts in
 the rounds that have completed (read without a synchronisation).
 
+``denoise_temporal=True`` (default False, and the service is then exactly what it is without the keyword: no new object, the same path): BSVD
+as the online machine in front of the generator, per stream (``_capi.TemporalFrvsrUpscaler``, ``ss4k_frvsr_temporal_*`` in include/ss4k.h,
+which states the semantics).  ``upscale(frames, streams=None, end_streams=(), stream_rates=None)`` then returns the frames that BECAME READY -
+none for a stream's first 16 frames, one per frame after - and ``last_ready = [(stream_id, first_frame_index, count), ...]`` says which group
+belongs where (``HipUpscalerService``'s convention); ids in ``end_streams`` are flushed after the job and their up to 16 frames appended, so a
+job of K frames that ends E streams returns at most ``temporal_result_bound(K, E) = K + 16 E`` frames.  ``flush()`` / ``reset()`` act on the
+unnamed stream.  ``denoise_rate`` is the service's rate, ``stream_rates`` a stream's own; ``denoise_weights`` is the BSVD checkpoint, resolved
+like the per-frame service's ``'denoise'`` entry (None: ``bsvd-32.pth`` in the checkpoint directory or ``FileNotFoundError``; ``'synthetic'``,
+or ``weights='synthetic'`` with nothing else said, is the opt-in); ``temporal_max_push`` (4) frames of one stream enter per round.  ``lr_shape``
+must be divisible by 4: of the reference's three, (630, 1120) is refused.  Refused with it, before any GPU work: ``scene_cut`` (a cut seen
+when a frame goes in would have to reset the recurrent state 16 frames later), ``HostFrames`` jobs, and ``EgvsrNode(denoise_temporal=True)``.
+
 ``generator='tecogan'`` runs TecoGAN's FRNet instead (``nb`` then defaults to 16; its checkpoint is that class's bare state_dict).
 
 Weights as for the other services: ``weights=None`` looks ``EGVSR_iter420000.pth`` (``egvsr_upscaler.py:25``) up in
@@ -114,14 +126,44 @@ def check_scene_cut(threshold) -> Optional[float]:
     return t
 
 
+def check_temporal_lr_shape(lr_shape) -> None:
+    """``denoise_temporal=True`` needs an ``lr_shape`` divisible by 4 (BSVD's two 2x poolings; ``ss4k_frvsr_temporal_create``): of the reference's
+    three shapes (630, 1120) is refused.  Raises ``ValueError``."""
+    lh, lw = int(lr_shape[0]), int(lr_shape[1])
+    if lh % 4 or lw % 4:
+        raise ValueError(f"denoise_temporal=True needs an lr_shape divisible by 4 (BSVD), not {(lh, lw)}")
+
+
+def temporal_rounds(streams: Sequence[Hashable], max_push: int) -> List[List[int]]:
+    """The rounds of a denoised job: ``streams[i]`` is the stream of frame i.  Round r takes the next up-to-``max_push`` frames of every stream
+    that still has some, streams in order of first appearance, at most 64 frames in all (a stream that does not fit waits for the next round).
+    Returns lists of frame indices (``HipUpscalerService._temporal_rounds``'s rule)."""
+    queues = {}
+    for i, sid in enumerate(streams):
+        queues.setdefault(sid, []).append(i)
+    rounds = []
+    while any(queues.values()):
+        idx = []
+        for q in queues.values():
+            n = min(max_push, len(q), 64 - len(idx))
+            idx += q[:n]
+            del q[:n]
+        rounds.append(idx)
+    return rounds
+
+
 class HipEgvsrUpscalerService(BaseUpscalerService):
     #: (frames-in ring, frames-out ring) of ``hostring.make_rings``, set before ``start()``: the worker then takes ``HostFrames`` jobs
     host_rings = None
     #: staging tensors per input shape: one more than the jobs that can be in flight (the job running, the one held back, the next one's copy)
     HOST_STAGE_DEPTH = 3
 
+    #: frames a denoised stream holds back (the number of BiBufferConvs: ss4k_bsvd_online_lag)
+    TEMPORAL_LAG = 16
+
     def __init__(self, lr_level=1, device=0, on_queue=None, *, weights=None, checkpoint_dir: Optional[str] = None, dtype="f16", nb=None,
-                 lr_shape=None, seed=0, max_streams=1, generator="egvsr", degradation="BD", scene_cut=None):
+                 lr_shape=None, seed=0, max_streams=1, generator="egvsr", degradation="BD", scene_cut=None, denoise_temporal=False,
+                 denoise_rate=1.0, denoise_weights=None, temporal_max_push=None):
         self.lr_shape = tuple(lr_shape) if lr_shape is not None else LR_SHAPES[lr_level]
         self.scale = 4
         self.hr_shape = tuple([i * self.scale for i in self.lr_shape])
@@ -136,6 +178,22 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self.seed = seed
         self.max_streams = int(max_streams)
         self.scene_cut = check_scene_cut(scene_cut)
+        # denoise_temporal: BSVD as the online machine in front of the generator (_capi.TemporalFrvsrUpscaler): upscale() then returns the
+        # frames that BECAME READY, 16 frames after they went in (the module docstring)
+        self.denoise_temporal = bool(denoise_temporal)
+        self.denoise_rate = denoise_rate
+        self.denoise_weights = denoise_weights
+        self.temporal_max_push = int(temporal_max_push) if temporal_max_push else 4
+        self.last_ready = []
+        if self.denoise_temporal:
+            if self.scene_cut:
+                raise ValueError("denoise_temporal=True together with scene_cut is not supported: a cut seen when a frame goes in has to reset "
+                                 "the recurrent state 16 frames later, when the frame comes out of the denoiser")
+            check_temporal_lr_shape(self.lr_shape)
+            if isinstance(denoise_rate, bool) or not isinstance(denoise_rate, (int, float)) or not (0.0 <= float(denoise_rate) < float("inf")):
+                raise ValueError(f"denoise_rate={denoise_rate!r}: a denoise rate is a finite number >= 0")
+            if not 1 <= self.temporal_max_push <= 64:
+                raise ValueError(f"temporal_max_push={temporal_max_push!r}: a round takes 1..64 frames of one stream")
         super().__init__()
 
     def out_hw(self):
@@ -143,6 +201,10 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         return tuple(int(v) for v in self.output_shape) if self.output_shape is not None else self.hr_shape
 
     # worker side -----------------------------------------------------------------------------
+    def proc_main(self):
+        self._in_worker = True   # (read by the denoised path alone: a job that returns no frame answers with an empty HOST tensor)
+        super().proc_main()
+
     def proc_init(self):
         from .. import _capi
         from . import model as factory
@@ -153,6 +215,11 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self.torch_device = self.ctx.device
         self.model = factory.build_model_frvsr(self.ctx, self.weights, self.seed, self.checkpoint_dir, self.dtype, self.nb, self.generator,
                                                degradation=self.degradation)
+        if self.denoise_temporal:   # BSVD as the streaming model the online machine holds; resolved like HipUpscalerService's 'denoise' entry
+            spec = "synthetic" if self.denoise_weights is None and self.weights == "synthetic" else self.denoise_weights
+            self.denoise_model = factory.build_denoise_model(self.ctx, weights=spec, dtype=self.dtype, seed=self.seed, stream=True,
+                                                             checkpoint_dir=self.checkpoint_dir)
+            self._t_index = {}   # frames that have come back, per stream id
         self._up = None
         self._up_key = None
         self._cuts_before = 0   # cuts counted by upscaler objects that have been replaced (a new shape)
@@ -177,7 +244,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self._held.release(entry)   # (the consumer reads the ring slot from another process: the bytes must have landed)
 
     def proc_cleanup(self):
-        for name in ("_up", "model", "ctx"):
+        for name in ("_up", "denoise_model", "model", "ctx"):
             obj = getattr(self, name, None)
             if obj is not None:
                 obj.close()
@@ -195,6 +262,14 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         return self._up
 
     def _make_upscaler(self, _capi, key):
+        if self.denoise_temporal:
+            check_temporal_lr_shape(key[0])   # (the pipelines overwrite lr_shape after construction)
+            self._t_index = {}
+            up = _capi.TemporalFrvsrUpscaler(self.ctx, self.model, self.denoise_model, key[0], key[1], float(self.denoise_rate),
+                                             self.temporal_max_push, self.max_streams)
+            log(f"denoised streams: {self.max_streams} stream slot(s), {up.stream_state_bytes_for() / 2**20:.1f} MiB of state per running "
+                f"stream (max_push {self.temporal_max_push})")
+            return up
         if not self.scene_cut:
             return _capi.FrvsrUpscaler(self.ctx, self.model, key[0], key[1], self.max_streams)
         return _capi.FrvsrUpscaler(self.ctx, self.model, key[0], key[1], self.max_streams, scene_cut=self.scene_cut)
@@ -206,14 +281,118 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
 
     def reset(self):
         """Forget ``lr_prev`` / ``hr_prev``: the next frame is a stream's first (egvsr_upscaler.py:165-166)."""
+        if self.denoise_temporal:   # the unnamed stream is dropped without returning what is inside
+            slot = self._slots.end(None) if getattr(self, "_slots", None) is not None else None
+            if slot is not None and getattr(self, "_up", None) is not None:
+                self._up.reset(slot)
+            self._t_index.pop(None, None)
+            self.last_ready = []
+            return
         if getattr(self, "_up", None) is not None:
             self._up.reset()
 
-    def upscale(self, frames: torch.Tensor, streams: Optional[Sequence[Hashable]] = None, end_streams: Sequence[Hashable] = ()):
+    def flush(self):
+        """denoise_temporal: the frames still inside the unnamed stream, ``(k, H, W, 3)`` uint8, oldest first; the stream ends (the next frame
+        is a first frame again).  ``last_ready`` describes them."""
+        if not self.denoise_temporal:
+            raise RuntimeError("flush() belongs to denoise_temporal=True: every other job returns its own frames")
+        return self._temporal_job(None, [], (None,))
+
+    def temporal_result_bound(self, n_frames: int, ended: int = 0) -> int:
+        """The most frames a denoised job of ``n_frames`` frames that ends ``ended`` streams can return: K + 16 E."""
+        return int(n_frames) + self.TEMPORAL_LAG * int(ended)
+
+    def _temporal_job(self, frames, streams, end_streams, stream_rates=None):
+        """A job of the denoised service: its rounds, then the flushes of ``end_streams``; returns what became ready, possibly nothing, and
+        sets ``last_ready``.  Every stream id gets its slot BEFORE the first frame runs: a job that does not fit raises, has run nothing and
+        has taken no slot (``HipUpscalerService._temporal_job``'s rules)."""
+        n = 0 if frames is None else int(frames.shape[0])
+        if len(streams) != n:
+            raise ValueError(f"one stream id per frame: {len(streams)} ids for {n} frames")
+        rates = {}
+        if stream_rates:
+            from .hip_upscaler import validate_stream_rates   # (that module imports this one)
+            rates = validate_stream_rates(stream_rates, streams)
+        up = self._upscaler()
+        slots, taken = [], []
+        try:
+            for sid in streams:
+                slot, new = self._slots.slot(sid)
+                if new:
+                    taken.append(sid)
+                slots.append(slot)
+        except RuntimeError:
+            for sid in taken:
+                self._slots.end(sid)
+            raise
+        parts, ready = [], []
+
+        def came_back(sid, out):
+            k = int(out.shape[0])
+            if k:
+                first = self._t_index.get(sid, 0)
+                self._t_index[sid] = first + k
+                parts.append(out)
+                ready.append((sid, int(first), k))
+
+        try:
+            for sid, rate in rates.items():
+                up.set_denoise_rate(slots[streams.index(sid)], rate)
+            if n:
+                frames = frames.contiguous()
+                for idx in temporal_rounds(streams, self.temporal_max_push):
+                    out, items = up.round([frames[i] for i in idx], [slots[i] for i in idx])
+                    sid_of, o = {slots[i]: streams[i] for i in idx}, 0
+                    for slot, k in items:
+                        came_back(sid_of[slot], out[o:o + k])
+                        o += k
+            for sid in end_streams:
+                slot = self._slots.slot_of.get(sid)
+                if slot is None:
+                    continue   # (an id that holds no slot: nothing inside, nothing to free)
+                came_back(sid, up.flush(slot))
+                self._slots.end(sid)
+                self._t_index.pop(sid, None)
+        except Exception:
+            # the library has reset the slots of the round that failed, and frames that came back are lost with the exception: every stream
+            # the job named ends here
+            for sid in dict.fromkeys(list(streams) + list(end_streams)):
+                slot = self._slots.end(sid)
+                if slot is None:
+                    continue
+                try:
+                    up.reset(slot)
+                except Exception:   # noqa: BLE001 - the first failure is the one to report
+                    pass
+                self._t_index.pop(sid, None)
+            self.last_ready = []
+            raise
+        self.last_ready = ready
+        if parts:
+            return parts[0] if len(parts) == 1 else torch.cat(parts)
+        return torch.empty((0,) + tuple(up.out_shape()) + (3,), dtype=torch.uint8, device=self.torch_device)
+
+    def upscale(self, frames: torch.Tensor, streams: Optional[Sequence[Hashable]] = None, end_streams: Sequence[Hashable] = (), stream_rates=None):
         """``streams=None``: ``frames`` are the next frames of the unnamed stream (id ``None``), as before there were slots.  Else
         ``streams[i]`` is the stream of ``frames[i]`` (one id for a 3-D frame): the job runs as ``plan_rounds(streams)``, one batched step per
-        round, and the result is in input order.  ``end_streams`` are released after the job."""
+        round, and the result is in input order.  ``end_streams`` are released after the job.
+
+        ``denoise_temporal=True``: the result is the frames that BECAME READY - none during a stream's first 16 frames, one per frame after,
+        grouped per stream in order of first appearance within each round; ``last_ready = [(stream_id, first_frame_index, count), ...]``
+        describes the groups.  Ids in ``end_streams`` are flushed after the job and their frames appended.  ``stream_rates={id: rate}`` sets the
+        denoise rate of those streams before the job's first round."""
         assert isinstance(frames, torch.Tensor)
+        if stream_rates and not self.denoise_temporal:
+            raise ValueError("stream_rates belongs to denoise_temporal=True")
+        if self.denoise_temporal:
+            frames = frames.to(self.torch_device, non_blocking=True)
+            if frames.dtype != torch.uint8:
+                frames = frames.to(torch.uint8)
+            if frames.ndim == 3:
+                frames = frames.unsqueeze(0)
+            if frames.ndim != 4 or frames.shape[-1] != 3:
+                raise ValueError(f"frames are (h, w, 3) or (n, h, w, 3), not {tuple(frames.shape)}")
+            return self._temporal_job(frames, [None] * frames.shape[0] if streams is None else list(streams), tuple(end_streams), stream_rates)
         frames = frames.to(self.torch_device, non_blocking=True)
         if frames.dtype != torch.uint8:   # (the reference's own demo pushes float frames holding byte values, egvsr_upscaler.py:226-230)
             frames = frames.to(torch.uint8)
@@ -270,10 +449,48 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
                 out.index_copy_(0, ix, up.upscale_streams(frames.index_select(0, ix), [slots[i] for i in idx]))
         return out
 
+    def _temporal_job_recieved(self, job, streams, end_streams):
+        """A job of a denoised worker: device-tensor frames (or ``frames=None`` with ``end_streams``: only flushes).  The answer carries the
+        frames that became ready and, as ``HipUpscalerService._tag_temporal`` leaves them, ``ready`` (= ``last_ready``), ``first_frame_index``
+        and ``lag_frames``."""
+        hf = getattr(job, "frames", None)
+        if isinstance(hf, HostFrames):
+            raise RuntimeError("a HostFrames job reached a worker with denoise_temporal=True: host-ring jobs of denoised frame-recurrent "
+                               "streams are not supported (send device tensors)")
+        rates = getattr(job, "stream_rates", None) or None
+
+        def run():
+            if hf is None:
+                return self._temporal_job(None, [], end_streams, None)
+            return self.upscale(hf, streams=streams, end_streams=end_streams, stream_rates=rates)
+
+        upscaled, elapsed, prof = self._run_job(job, run)
+        entry = None
+        if hasattr(job, "streams") or hasattr(job, "end_streams"):
+            try:   # the caller's own type, when it takes the eight fields
+                entry = type(job)(frames=upscaled, audio_segment=getattr(job, "audio_segment", None), step=getattr(job, "step", 0), elapsed=elapsed,
+                                  last_modified=time.time(), profiler=prof, streams=streams, end_streams=end_streams)
+            except TypeError:
+                pass
+        if entry is None:
+            entry = answer(job, upscaled, elapsed, prof)
+        try:   # plain ints and tuples: the entry stays picklable.  An entry type without room for them goes untagged
+            entry.first_frame_index = int(self.last_ready[0][1]) if self.last_ready else 0
+            entry.lag_frames = self.TEMPORAL_LAG
+            entry.ready = list(self.last_ready)   # (stream_id, first_frame_index, count) per group of entry.frames
+        except AttributeError:
+            pass
+        f = getattr(entry, "frames", None)
+        if getattr(self, "_in_worker", False) and isinstance(f, torch.Tensor) and f.is_cuda and f.shape[0] == 0:
+            entry.frames = torch.empty(tuple(f.shape), dtype=f.dtype)   # nothing became ready: an empty host tensor (no device block to share)
+        return entry
+
     def proc_job_recieved(self, job):  # (sic) the reference's spelling
         # as BaseUpscalerService.proc_job_recieved, plus the two optional attributes of a multi-stream job; a record without them is a job of
         # the unnamed stream and is answered by the base class's answer() exactly as before
         streams, end_streams = getattr(job, "streams", None), tuple(getattr(job, "end_streams", None) or ())
+        if self.denoise_temporal:
+            return self._temporal_job_recieved(job, streams, end_streams)
 
         def upscale(frames):
             return self.upscale(frames, streams, end_streams) if streams is not None or end_streams else self.upscale(frames)

@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""Time the frame-recurrent chain with the online BSVD denoiser in front (``_capi.TemporalFrvsrUpscaler``) against its two halves, on one GPU,
+in one process, in alternating runs:
+
+  chain     S lockstep streams, one frame each per round, in steady state (the lag is full: every round returns S frames)
+  frvsr     ``_capi.FrvsrUpscaler`` alone: the same S frames as one scattered round (``upscale_streams_at``)
+  bsvd      ``_capi.BsvdOnline.push`` alone: S one-frame pushes of S denoisers, one after the other, as the chain pushes its items
+
+for S = 1 and S = 4 (``--streams``), at LR ``--h`` x ``--w`` (540 x 960), ``--dtype`` f16.  Each form is timed with events around ``--iters``
+rounds after 16 + ``--warmup`` settle rounds, ``--runs`` times; the JSON line holds every run's ms per frame, the best of each and
+``chain_over_sum`` = best chain / (best frvsr + best bsvd): the expectation is about 1.  With the dev library
+(``SS4K_LIB=.../libss4k_hip_dev.so``) it also times ``frvt::denoised_in_items`` alone, microseconds per launch at 1 and S items.
+No gate: it states what it measures.
+
+Usage:  python tools/frvsr_temporal_time.py [--h 540 --w 960 --dtype f16 --streams 1 4 --iters 24 --runs 3] [--generator egvsr] [--out FILE]
+        SS4K_LIB=.../libss4k_hip_dev.so python tools/frvsr_temporal_time.py --kernel-only [--iters 200] [--out FILE]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+import sharkshark4k_amd  # noqa: E402,F401
+from sharkshark4k_amd import _capi  # noqa: E402
+from sharkshark4k_amd.upscale import model as factory  # noqa: E402
+
+LAG = 16
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def kernel_us(ctx, S, h, w, iters):
+    """Microseconds per launch of frvt::denoised_in_items at 1 and S items (dev library only; None otherwise)."""
+    L = _capi.lib()
+    if not hasattr(L, "ss4k_dev_op_frvsrt_denoised_in"):
+        return None
+    out = {}
+    taps = torch.tensor([0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32, device="cuda")
+    for n in sorted({1, S}):
+        den, lr, dst = (torch.rand((n, 3, h, w), dtype=torch.float32, device="cuda") for _ in range(3))
+        p = [(C.c_void_p * n)(*[t[i].data_ptr() for i in range(n)]) for t in (den, lr, dst)]
+
+        def launch():
+            _capi._check(L.ss4k_dev_op_frvsrt_denoised_in(ctx._h, p[0], p[1], p[2], n, h, w, taps.data_ptr(), _capi._stream()))
+
+        for _ in range(5):
+            launch()
+        out[str(n)] = round(1000.0 * min(timed(launch, iters) for _ in range(3)), 2)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--h", type=int, default=540)
+    ap.add_argument("--w", type=int, default=960)
+    ap.add_argument("--dtype", default="f16")
+    ap.add_argument("--generator", default="egvsr")
+    ap.add_argument("--streams", type=int, nargs="+", default=[1, 4])
+    ap.add_argument("--iters", type=int, default=24)
+    ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--kernel-only", action="store_true", help="dev library: the wave kernel's microseconds per launch alone")
+    a = ap.parse_args()
+    ctx = _capi.Context(0)
+    if a.kernel_only:
+        line = {"tool": "frvsr_temporal_time --kernel-only", "h": a.h, "w": a.w,
+                "denoised_in_us_per_launch": {str(S): kernel_us(ctx, S, a.h, a.w, a.iters) for S in a.streams}}
+        print(json.dumps(line), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write(json.dumps(line) + "\n")
+        ctx.close()
+        return
+    model = factory.build_model_frvsr(ctx, "synthetic", 0, None, a.dtype, None, a.generator)
+    dn = factory.build_denoise_model(ctx, weights="synthetic", dtype=a.dtype, stream=True)
+    for S in a.streams:
+        frames = torch.randint(0, 256, (S, a.h, a.w, 3), dtype=torch.uint8, device="cuda")
+        x4 = torch.rand((S, 1, 4, a.h, a.w), dtype=torch.float32, device="cuda")
+        chain = _capi.TemporalFrvsrUpscaler(ctx, model, dn, (a.h, a.w), None, max_push=1, max_streams=S)
+        bare = _capi.FrvsrUpscaler(ctx, model, (a.h, a.w), None, max_streams=S)
+        ons = [_capi.BsvdOnline(dn, max_push=1) for _ in range(S)]
+        slots = list(range(S))
+        fr = [frames[i] for i in range(S)]
+        out_chain = torch.empty((S, 4 * a.h, 4 * a.w, 3), dtype=torch.uint8, device="cuda")
+        out_bare = [torch.empty((4 * a.h, 4 * a.w, 3), dtype=torch.uint8, device="cuda") for _ in range(S)]
+        out_den = torch.empty((1, 3, a.h, a.w), dtype=torch.float32, device="cuda")
+
+        def run_chain():
+            got, items = chain.round(fr, slots, out=out_chain)
+            return got
+
+        def run_bare():
+            bare.upscale_streams_at(fr, slots, out_bare)
+
+        def run_bsvd():
+            for i, on in enumerate(ons):
+                on.push(x4[i], out=out_den)
+
+        forms = {"chain": run_chain, "frvsr": run_bare, "bsvd": run_bsvd}
+        for fn in forms.values():
+            for _ in range(LAG + a.warmup):
+                fn()
+        torch.cuda.synchronize()
+        assert run_chain().shape[0] == S, "the chain is not in steady state"
+        res = {k: [] for k in forms}
+        for _ in range(a.runs):
+            for k, fn in forms.items():   # alternating: every run times the three forms one after the other
+                res[k].append(timed(fn, a.iters) / S)
+        best = {k: min(v) for k, v in res.items()}
+        line = {"tool": "frvsr_temporal_time", "h": a.h, "w": a.w, "dtype": a.dtype, "generator": a.generator, "streams": S, "iters": a.iters,
+                "ms_per_frame": {k: [round(v, 4) for v in vs] for k, vs in res.items()}, "best_ms_per_frame": {k: round(v, 4) for k, v in best.items()},
+                "spread": {k: round(max(v) / min(v), 4) for k, v in res.items()},
+                "chain_over_sum": round(best["chain"] / (best["frvsr"] + best["bsvd"]), 4),
+                "state_bytes_per_stream": chain.stream_state_bytes_for(), "denoised_in_us_per_launch": kernel_us(ctx, S, a.h, a.w, a.iters)}
+        print(json.dumps(line), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write(json.dumps(line) + "\n")
+        chain.close(); bare.close()
+        for on in ons:
+            on.close()
+    dn.close(); model.close(); ctx.close()
+
+
+if __name__ == "__main__":
+    main()
