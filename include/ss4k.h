@@ -509,7 +509,21 @@ int ss4k_upscaler_temporal_set_denoise_rate_stream(ss4k_upscaler_temporal* up, i
  * the whole round before the first launch and change nothing, and so does a failed allocation of the round's buffers or a slot's ring and
  * recurrent state.  A round that fails after its first launch resets every slot it named.
  * _set_denoise_rate_stream, _stream_state_bytes_for, _state_bytes and _release_idle are their ss4k_upscaler_temporal_* counterparts (a slot's
- * share includes its recurrent state).  Scene cuts are not available on this object. */
+ * share includes its recurrent state).
+ * SCENE CUTS.  Off by default, and with it off a round launches exactly what it launches without a detector.  _set_scene_cut (every slot;
+ * validated as ss4k_frvsr_upscaler_set_scene_cut: (0, 255], 0 = off, NaN / negative / > 255 SS4K_EINVAL) puts the rule above in front of
+ * every round, per slot, on the input bytes AS THEY ARRIVE - frame i of an item against frame i - 1, frame 0 against a device copy of the
+ * slot's previous frame; no comparison for a stream's first frame or after a change of (h, w) - exactly as ss4k_upscaler_temporal_set_scene_cut.
+ * With a threshold set a stream is the concatenation of its scenes, frame for frame and bit for bit, each scene as if it had been pushed into
+ * and flushed out of an object of its own: when stream frame f of a slot is flagged, (1) the denoiser does not reach across f, (2) f's noise
+ * plane is 0.05, and (3) in the wave in which frame f LEAVES the denoiser - 16 frames later, or at the flush - the slot's lr_prev / hr_prev
+ * read as zero, as for a stream's first frame.  The lag stays 16, a round returns the frames it returns without the detector in the same order,
+ * and the flags never leave the device.  Setting 0 stops detection for later frames and drops the stored frames and the counters; flags already
+ * inside keep acting, on the denoiser and on the generator, until their frames have left.  _reset_stream and _flush_stream end the detector's
+ * stream (the next frame is not compared); _release_idle frees an idle slot's detector buffers, and that slot's counters start over.
+ * _state_bytes includes the detectors' device buffers (the stored frame of 3 h w bytes and under 1 KiB of sums, flags and counters per slot);
+ * _stream_state_bytes_for does not.  _scene_cut_stats_stream synchronises with hip_stream; _scene_cut_total never does: the cuts of the rounds
+ * that have COMPLETED, summed over the slots.  A refused round changes nothing, the detectors included. */
 typedef struct ss4k_frvsr_temporal ss4k_frvsr_temporal;
 int ss4k_frvsr_temporal_create(ss4k_ctx* ctx, ss4k_frvsr* frvsr, ss4k_model* bsvd_stream_model, int lr_h, int lr_w, int out_h, int out_w,
                                double denoise_rate, int max_push, int max_streams, ss4k_frvsr_temporal** out);
@@ -526,6 +540,10 @@ int ss4k_frvsr_temporal_out_shape(const ss4k_frvsr_temporal* up, int* out_h, int
 int ss4k_frvsr_temporal_state_bytes(const ss4k_frvsr_temporal* up, size_t* bytes);
 int ss4k_frvsr_temporal_stream_state_bytes_for(const ss4k_frvsr_temporal* up, size_t* bytes);
 int ss4k_frvsr_temporal_release_idle(ss4k_frvsr_temporal* up);
+int ss4k_frvsr_temporal_set_scene_cut(ss4k_frvsr_temporal* up, double threshold);   /* 0 = off (default) */
+int ss4k_frvsr_temporal_scene_cut(const ss4k_frvsr_temporal* up, double* threshold);
+int ss4k_frvsr_temporal_scene_cut_stats_stream(ss4k_frvsr_temporal* up, int slot, ss4k_scene_cut_stats* out, void* hip_stream);   /* synchronises */
+int ss4k_frvsr_temporal_scene_cut_total(const ss4k_frvsr_temporal* up, uint64_t* cuts);   /* never synchronises */
 
 /* ---- measurement hooks (bench.py: live per-kernel timing with HIP events on the launch stream) */
 /* When enabled, every launch of the dominant conv kernel is bracketed with hipEvents on the

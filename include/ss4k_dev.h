@@ -159,6 +159,12 @@ int ss4k_dev_op_frvsrbi_bilinear4_add_items(ss4k_ctx* ctx, const float* conv, co
  * ss4k_dev_op_frvsrbi_ below.) */
 int ss4k_dev_op_frvsrt_denoised_in(ss4k_ctx* ctx, const float* const* den, const float* const* lr, float* const* dst, int n_items, int h, int w,
                                    const float* taps_dev, void* hip_stream);
+/* ... and the late reset of a scene cut; route "frvt::clear_flagged_items".  flag_ptrs / lr_ptrs / hr_ptrs: HOST arrays of n_items (1..64) device
+ * pointers.  One launch: lr_ptrs[i] (lr_bytes) and hr_ptrs[i] (hr_bytes) become zero for every item whose flag pointer is not NULL and whose
+ * 32-bit word is not 0; nothing else is written.  SS4K_EINVAL before any launch: n_items outside 1..64, a size that is 0 or no multiple of 4, a
+ * NULL or not 16-byte aligned lr / hr of ANY item, a flag pointer that is not 4-byte aligned. */
+int ss4k_dev_op_frvsrt_clear_flagged(ss4k_ctx* ctx, const uint32_t* const* flag_ptrs, void* const* lr_ptrs, void* const* hr_ptrs, int n_items,
+                                     size_t lr_bytes, size_t hr_bytes, void* hip_stream);
 
 /* ss4k_frvsr_step (include/ss4k.h) on a contiguous batch of n items, with the two tensors between FNet, the warp and SRNet copied out for
  * EVERY item: flow_out (n, 2, h, w) = the padded LR flow, s2d_out (n, 48, h, w) = the warped, space-to-depth hr_prev as SRNet's first conv read

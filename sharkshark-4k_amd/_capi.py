@@ -57,6 +57,9 @@ SYMBOLS = [
     "ss4k_frvsr_temporal_reset_stream", "ss4k_frvsr_temporal_pending_stream", "ss4k_frvsr_temporal_set_denoise_rate_stream",
     "ss4k_frvsr_temporal_out_shape", "ss4k_frvsr_temporal_state_bytes", "ss4k_frvsr_temporal_stream_state_bytes_for",
     "ss4k_frvsr_temporal_release_idle",
+    # ... and its scene cuts
+    "ss4k_frvsr_temporal_set_scene_cut", "ss4k_frvsr_temporal_scene_cut", "ss4k_frvsr_temporal_scene_cut_stats_stream",
+    "ss4k_frvsr_temporal_scene_cut_total",
 ]
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
@@ -93,6 +96,8 @@ DEV_SYMBOLS = [
     # the glue kernel of the frame-recurrent chain with the denoiser in front, and the poison of its job buffers
     # (tests/test_gpu_frvsr_temporal_kernel.py, tests/test_gpu_frvsr_temporal_hygiene.py)
     "ss4k_dev_op_frvsrt_denoised_in", "ss4k_dev_guard_poison_frvsr_temporal",
+    # the late reset of a scene cut in that chain (tests/test_gpu_frvsr_temporal_cuts_kernel.py)
+    "ss4k_dev_op_frvsrt_clear_flagged",
 ]
 
 
@@ -339,6 +344,13 @@ def load(path: str) -> C.CDLL:
         L.ss4k_frvsr_temporal_state_bytes.argtypes = [vp, C.POINTER(sz)]
         L.ss4k_frvsr_temporal_stream_state_bytes_for.argtypes = [vp, C.POINTER(sz)]
         L.ss4k_frvsr_temporal_release_idle.argtypes = [vp]
+    if hasattr(L, "ss4k_frvsr_temporal_set_scene_cut"):   # (absent from builds before that chain's scene cuts)
+        L.ss4k_frvsr_temporal_set_scene_cut.argtypes = [vp, C.c_double]
+        L.ss4k_frvsr_temporal_scene_cut.argtypes = [vp, C.POINTER(C.c_double)]
+        L.ss4k_frvsr_temporal_scene_cut_stats_stream.argtypes = [vp, i, C.POINTER(SceneCutStats), vp]
+        L.ss4k_frvsr_temporal_scene_cut_total.argtypes = [vp, C.POINTER(C.c_uint64)]
+    if hasattr(L, "ss4k_dev_op_frvsrt_clear_flagged"):   # dev library only
+        L.ss4k_dev_op_frvsrt_clear_flagged.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, sz, sz, vp]
     if hasattr(L, "ss4k_dev_op_frvsrt_denoised_in"):   # dev library only
         L.ss4k_dev_op_frvsrt_denoised_in.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, i, vp, vp]
         L.ss4k_dev_guard_poison_frvsr_temporal.argtypes = [vp, C.POINTER(i), C.POINTER(sz), C.POINTER(sz)]
@@ -1266,7 +1278,7 @@ class TemporalFrvsrUpscaler:
     returns the up to 16 frames still inside and ends it.  The methods mirror ``TemporalUpscaler``'s."""
 
     def __init__(self, ctx: Context, model: Frvsr, denoise: Model, lr_shape, output_shape=None, denoise_rate: float = 1.0, max_push: int = 4,
-                 max_streams: int = 1):
+                 max_streams: int = 1, scene_cut: Optional[float] = None):
         self.ctx, self.model, self.denoise, self.max_push, self.max_streams = ctx, model, denoise, int(max_push), int(max_streams)
         self.lr_shape = (int(lr_shape[0]), int(lr_shape[1]))
         oh, ow = (0, 0) if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
@@ -1275,11 +1287,44 @@ class TemporalFrvsrUpscaler:
             _check(lib().ss4k_frvsr_temporal_create(ctx._h, model._h, denoise._h, self.lr_shape[0], self.lr_shape[1], oh, ow, float(denoise_rate),
                                                     self.max_push, self.max_streams, C.byref(h)))
         self._h, self.lag = h, 16
+        if scene_cut is not None:
+            try:
+                self.set_scene_cut(scene_cut)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None):
             lib().ss4k_frvsr_temporal_destroy(self._h)
             self._h = None
+
+    def set_scene_cut(self, threshold: float) -> None:
+        """Scene-cut detection in front of every round, every slot (include/ss4k.h): ``threshold`` is the mean absolute byte difference between
+        a stream's consecutive input frames, in (0, 255]; 0 turns it off (the default).  A cut keeps the two scenes apart inside the denoiser
+        and, when the scene's first frame leaves it 16 frames later, zeroes the stream's recurrent state: the output is that of the scenes run
+        as separate streams, and every round still returns the frames it returns without the detector."""
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_frvsr_temporal_set_scene_cut(self._h, float(threshold)))
+
+    def scene_cut(self) -> float:
+        t = C.c_double()
+        _check(lib().ss4k_frvsr_temporal_scene_cut(self._h, C.byref(t)))
+        return float(t.value)
+
+    def scene_cut_stats(self, slot: int = 0) -> dict:
+        """The counters of a slot's stream and its last frame's values: compared, cuts, last_sad, last_score, last_was_cut.  Synchronises."""
+        s = SceneCutStats()
+        with torch.cuda.device(self.ctx.device):
+            _check(lib().ss4k_frvsr_temporal_scene_cut_stats_stream(self._h, int(slot), C.byref(s), _stream()))
+        return {"compared": int(s.compared), "cuts": int(s.cuts), "last_sad": int(s.last_sad), "last_score": int(s.last_score),
+                "last_was_cut": int(s.last_was_cut)}
+
+    def scene_cut_total(self) -> int:
+        """Cuts in the rounds that have completed on the device, over all slots; never synchronises."""
+        n = C.c_uint64()
+        _check(lib().ss4k_frvsr_temporal_scene_cut_total(self._h, C.byref(n)))
+        return int(n.value)
 
     def __del__(self):
         try:

@@ -70,7 +70,61 @@ int ss4k_frvsr_temporal_release_idle(ss4k_frvsr_temporal* up) {
   });
 }
 
+int ss4k_frvsr_temporal_set_scene_cut(ss4k_frvsr_temporal* up, double threshold) {
+  return guard([&] {
+    SS4K_REQUIRE(up, "ss4k_frvsr_temporal_set_scene_cut: NULL argument");
+    SS4K_HIP(hipSetDevice(up->t.ctx->device));
+    up->t.set_scene_cut(threshold);
+  });
+}
+int ss4k_frvsr_temporal_scene_cut(const ss4k_frvsr_temporal* up, double* threshold) {
+  return guard([&] {
+    SS4K_REQUIRE(up && threshold, "ss4k_frvsr_temporal_scene_cut: NULL argument");
+    *threshold = up->t.cut_threshold;
+  });
+}
+int ss4k_frvsr_temporal_scene_cut_stats_stream(ss4k_frvsr_temporal* up, int slot, ss4k_scene_cut_stats* out, void* stream) {
+  return guard([&] {
+    SS4K_REQUIRE(up && out, "ss4k_frvsr_temporal_scene_cut_stats_stream: NULL argument");
+    cut::SlotState s{};
+    const TemporalCut* c = up->t.slot(slot).cut.get();
+    if (c && c->on() && !c->fresh) {
+      SS4K_HIP(hipSetDevice(up->t.ctx->device));
+      SS4K_HIP(hipMemcpyAsync(&s, c->state.ptr, sizeof(s), hipMemcpyDeviceToHost, (hipStream_t)stream));
+      SS4K_HIP(hipStreamSynchronize((hipStream_t)stream));
+    }
 #ifdef SS4K_DEV
+    SS4K_REQUIRE(!c || c->zones_intact(), "ss4k_frvsr_temporal_scene_cut_stats_stream: a red zone around the pinned stats block was written");
+#endif
+    out->compared = s.compared; out->cuts = s.cuts; out->last_sad = s.last_sad; out->last_score = s.last_score;
+    out->last_was_cut = s.last_was_cut; out->reserved = 0;
+  });
+}
+int ss4k_frvsr_temporal_scene_cut_total(const ss4k_frvsr_temporal* up, uint64_t* cuts) {
+  return guard([&] {
+    SS4K_REQUIRE(up && cuts, "ss4k_frvsr_temporal_scene_cut_total: NULL argument");
+    uint64_t n = 0;
+    for (const auto& s : up->t.slots) {
+      if (!(s->cut && s->cut->host)) continue;
+      const volatile cut::SlotState* h = s->cut->host;   // (written by the device's copies: read once, no synchronisation)
+      n += h->cuts;
+    }
+    *cuts = n;
+  });
+}
+
+#ifdef SS4K_DEV
+int ss4k_dev_op_frvsrt_clear_flagged(ss4k_ctx* c, const uint32_t* const* flags, void* const* lr, void* const* hr, int n_items, size_t lr_bytes,
+                                     size_t hr_bytes, void* s) {
+  return guard([&] {
+    SS4K_REQUIRE(c && flags && lr && hr, "ss4k_dev_op_frvsrt_clear_flagged: NULL argument");
+    SS4K_REQUIRE(n_items >= 1 && n_items <= FRVT_MAX_ITEMS, "ss4k_dev_op_frvsrt_clear_flagged: 1..64 items");
+    FrvtClearTable tab{};
+    for (int i = 0; i < n_items; ++i) { tab.flag[i] = flags[i]; tab.lr[i] = lr[i]; tab.hr[i] = hr[i]; }
+    op_frvt_clear_flagged_items(tab, n_items, lr_bytes, hr_bytes, (hipStream_t)s);
+    SS4K_HIP(hipGetLastError());
+  });
+}
 int ss4k_dev_op_frvsrt_denoised_in(ss4k_ctx* c, const float* const* den, const float* const* lr, float* const* dst, int n_items, int h, int w,
                                    const float* taps_dev, void* s) {
   return guard([&] {

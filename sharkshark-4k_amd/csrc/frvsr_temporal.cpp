@@ -4,6 +4,9 @@
 // 0.8 * clamp01(sharpen(den)) + 0.2 * lr_before into its stream's lr buffer (frvsr_temporal.hip), one batched step, close_slots and one launch
 // that writes the wave's frames where they go in the output.  The generator's files are not touched: the waves are FrvsrUpscaler rounds made
 // from outside, as the scene-cut detector makes its refusals.
+// Scene cuts (set_scene_cut): a slot's TemporalCut flags the input frames as they arrive, the flags go into the noise planes and the denoiser's
+// ring as in TemporalUpscaler::round, and a wave that holds a stream with a live ring runs one more launch, frvt::clear_flagged_items, between
+// open_slots and the glue: where the leaving frame's word is set, the stream's lr_prev / hr_prev are zeroed - the reset, 16 frames late.
 #include "frvsr_temporal.h"
 #include "upscaler_temporal.h"   // op_tround_gather, TroundTable
 #include <cmath>
@@ -61,9 +64,14 @@ const FrvtSlot& FrvsrTemporal::slot(int s) const {
 
 static size_t recurrent_bytes(const FrvsrUpscaler::Slot& r) { return r.lr[0].bytes + r.lr[1].bytes + r.hr[0].bytes + r.hr[1].bytes; }
 
+static size_t detector_bytes(const FrvtSlot& s) {
+  return s.cut ? s.cut->prev.bytes + s.cut->state.bytes + s.cut->acc.bytes + s.cut->flags.bytes : 0;
+}
+
 size_t FrvsrTemporal::state_bytes() const {
   size_t t = 0;
-  for (int s = 0; s < max_streams(); ++s) t += slots[s]->on.state_bytes() + slots[s]->ring.bytes + recurrent_bytes(up.slots[s]);
+  for (int s = 0; s < max_streams(); ++s)
+    t += slots[s]->on.state_bytes() + slots[s]->ring.bytes + recurrent_bytes(up.slots[s]) + detector_bytes(*slots[s]);
   return t;
 }
 
@@ -79,6 +87,7 @@ void FrvsrTemporal::release_idle() {
     if (t.running()) continue;
     t.rate = -1;
     t.on.release_state(); t.ring.release();
+    if (t.cut) t.cut->release_device();   // (its counters start over, as after set_scene_cut(0): they lived in the buffers that go)
     FrvsrUpscaler::Slot& r = up.slots[s];
     r.have_state = false;
     for (int k = 0; k < 2; ++k) { r.lr[k].release(); r.hr[k].release(); }
@@ -89,6 +98,22 @@ void FrvsrTemporal::reset(int si) {
   FrvtSlot& s = slot(si);
   s.on.reset(); s.first_frame = true; s.pushed = s.emitted = 0; s.rate = -1;
   up.slots[si].have_state = false;   // the next frame through the generator sees zero lr_prev / hr_prev
+  if (s.cut) s.cut->forget();        // ... and is not compared
+}
+
+// the detector of a slot that has none yet, once a threshold is set
+void FrvsrTemporal::want_cut(FrvtSlot& s) {
+  if (s.cut || !(cut_threshold > 0)) return;
+  auto c = std::make_unique<TemporalCut>();
+  c->set(cut_threshold);
+  s.cut = std::move(c);
+}
+
+void FrvsrTemporal::set_scene_cut(double threshold) {
+  SS4K_REQUIRE(threshold == threshold && threshold >= 0.0 && threshold <= 255.0, "scene cut: the threshold is 0 (off) or a mean absolute difference in (0, 255]");
+  cut_threshold = threshold;
+  want_cut(*slots[0]);   // (the other slots make theirs with their first round: a pinned block each)
+  for (auto& s : slots) if (s->cut) s->cut->set(threshold);
 }
 
 void FrvsrTemporal::set_denoise_rate(int si, float rate) {
@@ -108,13 +133,20 @@ void FrvsrTemporal::check_sizes(int h, int w) const {
 }
 
 void FrvsrTemporal::run_wave(const frvsr_temporal::Wave& wv, const float* const* den_of, const float* const* ring_of, uint8_t* const* out_of,
-                             hipStream_t st) {
+                             const uint32_t* const* flag_of, hipStream_t st) {
   const int lh = up.lr_h, lw = up.lr_w;
   int oh, ow; up.out_shape(&oh, &ow);
   int32_t ids[FRVT_MAX_ITEMS];
   for (int i = 0; i < wv.n; ++i) ids[i] = wv.slot[i];
   FrvsrUpscaler::RoundPtrs r{};
   up.open_slots(ids, wv.n, st, r);
+  if (flag_of) {
+    // a frame that was flagged when it went in leaves now: its stream's lr_prev / hr_prev read as zero, as open_slots gives a stream's first
+    // frame.  The flags stay on the device; the launch is the same whether a cut leaves or not
+    FrvtClearTable clr{};
+    for (int i = 0; i < wv.n; ++i) { clr.flag[i] = flag_of[i]; clr.lr[i] = const_cast<float*>(r.lr_prev[i]); clr.hr[i] = r.hr_prev.p[i]; }
+    up.m->timed(FRV_GLUE, st, [&] { op_frvt_clear_flagged_items(clr, wv.n, (size_t)3 * lh * lw * 4, (size_t)3 * 16 * lh * lw * 4, st); });
+  }
   FrvtTable tab{}; FrvsrFramesOut fout{};
   for (int i = 0; i < wv.n; ++i) { tab.den[i] = den_of[i]; tab.lr[i] = ring_of[i]; tab.dst[i] = r.lr_dst.p[i]; fout.p[i] = out_of[i]; }
   // clamp(sharpen(den)) * 0.8 + 0.2 * lr   (fsrcnn_upscaler.py:279-281; Upscaler::single_tail's constants)
@@ -146,6 +178,7 @@ int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, i
     up.check_round(ids, waves.w[r].n, h, w, false);
   }
   check_sizes(h, w);
+  SS4K_REQUIRE(!(cut_threshold > 0) || (size_t)3 * h * w <= cut::MAX_FRAME_BYTES, "scene cut: a frame holds at most 2^36 bytes");
   // ---- allocations, still before the first launch: one that fails leaves every stream as it was (a slot that gained buffers keeps them).  A
   // slot's recurrent state is made here, with the stream's first frame, not 16 frames later: what a running slot holds does not depend on
   // how far its stream has come.  What a slot's denoiser allocates with its first push is BsvdOnline's own and happens inside step 3.
@@ -155,6 +188,9 @@ int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, i
     slots[p.items[t].slot]->ring.ensure(frame * ring_frames() * 4);
     FrvsrUpscaler::Slot& rs = up.slots[p.items[t].slot];
     for (int b = 0; b < 2; ++b) { rs.lr[b].ensure(frame * 4); rs.hr[b].ensure(frame * 16 * 4); }
+    FrvtSlot& s = *slots[p.items[t].slot];
+    want_cut(s);   // (with no threshold set: nothing, and the round launches what it launched before there was a detector)
+    if (s.cut && s.cut->on()) s.cut->reserve((size_t)3 * h * w);
   }
   try {
     // ---- 1. frames in: one launch, every frame from where it lies into its stream's ring slot
@@ -173,6 +209,16 @@ int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, i
       if (s.first_frame) start_bits |= 1ull << it.first;
     }
     up.m->timed(FRV_GLUE, st, [&] { op_frames_in_items(fin, dst, k, h, w, lh, lw, st); });
+    // ---- 1b. scene cuts (TemporalUpscaler::round's step 2): each slot's own detector on its own frames as they arrived, frame 0 of an item
+    // against the slot's stored frame.  The flags stay on the device: the gather, the denoiser's ring and - 16 frames later - the waves read them
+    const uint32_t* item_cuts[temporal_round::MAX_FRAMES] = {};
+    for (int t = 0; t < p.n_items; ++t) {
+      const temporal_round::Item& it = p.items[t];
+      FrvtSlot& s = *slots[it.slot];
+      if (!(s.cut && s.cut->on())) continue;
+      item_cuts[t] = s.cut->detect_at(fin.p + it.first, it.n, h, w, st);
+      for (int j = 0; j < it.n; ++j) tab.flag[it.first + j] = item_cuts[t] + j;
+    }
     // ---- 2. the packed (k, 4, lh, lw) denoiser input, noise planes included: one launch
     op_tround_gather(tab, lr4.as<float>(), k, plane, 4, start_bits, 0.05f, st);
     // ---- 3. one push per item, one after the other: they share the model's activation slots
@@ -180,7 +226,8 @@ int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, i
       const temporal_round::Item& it = p.items[t];
       FrvtSlot& s = *slots[it.slot];
       s.first_frame = false;
-      const int got = s.on.push(lr4.as<float>() + plane * 4 * it.first, it.n, lh, lw, den.as<float>() + frame * it.den_off, (size_t)std::max(it.emitted, 1), st);
+      const int got = s.on.push(lr4.as<float>() + plane * 4 * it.first, it.n, lh, lw, den.as<float>() + frame * it.den_off, (size_t)std::max(it.emitted, 1), st,
+                                item_cuts[t]);
       s.pushed += it.n;
       SS4K_REQUIRE(got == it.emitted, "internal: the online denoiser emitted another number of frames than its plan");
     }
@@ -188,12 +235,19 @@ int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, i
     for (int r = 0; r < waves.n_waves; ++r) {
       const frvsr_temporal::Wave& wv = waves.w[r];
       const float* den_of[FRVT_MAX_ITEMS]; const float* ring_of[FRVT_MAX_ITEMS]; uint8_t* out_of[FRVT_MAX_ITEMS];
+      const uint32_t* flag_of[FRVT_MAX_ITEMS];
+      bool any_ring = false;
       for (int i = 0; i < wv.n; ++i) {
+        FrvtSlot& s = *slots[wv.slot[i]];
         den_of[i] = den.as<float>() + frame * wv.out[i];
-        ring_of[i] = slots[wv.slot[i]]->ring.as<float>() + frame * p.ring_out[wv.out[i]];
+        ring_of[i] = s.ring.as<float>() + frame * p.ring_out[wv.out[i]];
         out_of[i] = out + out_frame * wv.out[i];
+        SS4K_REQUIRE((long long)wv.frame[i] == s.emitted, "internal: a wave carries another frame than the next one of its stream");
+        // the leaving frame's own word: written by the push that brought it, this round's or an earlier one (frvsr_temporal_plan.h)
+        flag_of[i] = s.on.cuts_live ? s.on.flag_ring.as<uint32_t>() + frvsr_temporal::ring_word(wv.frame[i]) : nullptr;
+        any_ring = any_ring || s.on.cuts_live;
       }
-      run_wave(wv, den_of, ring_of, out_of, st);
+      run_wave(wv, den_of, ring_of, out_of, any_ring ? flag_of : nullptr, st);
       for (int i = 0; i < wv.n; ++i) slots[wv.slot[i]]->emitted += 1;
     }
   } catch (...) {   // a round that failed half way: none of its streams can go on, neither half of them
@@ -215,8 +269,11 @@ int FrvsrTemporal::flush(int si, uint8_t* out, size_t out_capacity_bytes, hipStr
   int oh, ow; up.out_shape(&oh, &ow);
   const size_t out_frame = (size_t)oh * ow * 3, frame = (size_t)3 * lh * lw;
   SS4K_REQUIRE(out_capacity_bytes >= (size_t)left * out_frame, "frvsr temporal flush: output buffer too small for the pending frames");
-  const frvsr_temporal::Waves waves = frvsr_temporal::make_flush(si, left);
+  const frvsr_temporal::Waves waves = frvsr_temporal::make_flush(si, left, (int)s.emitted);
   SS4K_REQUIRE(waves.n_waves == left, "internal: a flush of more frames than a slot can hold");
+  // BsvdOnline::flush() ends with reset(), which drops cuts_live - and leaves the ring's words as they are until the NEXT stream's first push
+  // with flags zero-fills them on its stream.  The waves below run before any such push, on the same stream: they read what this stream wrote
+  const uint32_t* const flag_ring = s.on.cuts_live ? s.on.flag_ring.as<uint32_t>() : nullptr;
   const int32_t id = si;
   up.check_round(&id, 1, lh, lw, false);
   check_sizes(lh, lw);
@@ -228,7 +285,8 @@ int FrvsrTemporal::flush(int si, uint8_t* out, size_t out_capacity_bytes, hipStr
       const float* den_of = den.as<float>() + frame * r;
       const float* ring_of = s.ring.as<float>() + frame * ((s.emitted + r) % ring_frames());
       uint8_t* out_of = out + out_frame * r;
-      run_wave(waves.w[r], &den_of, &ring_of, &out_of, st);
+      const uint32_t* flag_of = flag_ring ? flag_ring + frvsr_temporal::ring_word(waves.w[r].frame[0]) : nullptr;
+      run_wave(waves.w[r], &den_of, &ring_of, &out_of, flag_ring ? &flag_of : nullptr, st);
     }
   } catch (...) {
     reset(si);

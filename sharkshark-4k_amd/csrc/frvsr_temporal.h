@@ -13,6 +13,7 @@
 #include "temporal_round_plan.h"
 #include "frvsr_temporal_plan.h"
 #include "glue.h"
+#include "upscaler_temporal.h"   // TemporalCut: a slot's detector, the one TemporalSlot holds
 #include <memory>
 #include <vector>
 
@@ -30,11 +31,25 @@ static_assert(sizeof(FrvtTable) == 1536, "the wave's table travels in the kernel
 // pointers and a destination that overlaps its item's sources.
 void op_frvt_denoised_in_items(const FrvtTable& tab, int n_items, int h, int w, const float* taps_dev, float blend_a, float blend_b, hipStream_t st);
 
-// what one stream owns beside its recurrent state (FrvsrUpscaler::Slot): TemporalSlot without the cut detector
+// ---- the late reset of a scene cut (frvsr_temporal.hip) -------------------------------------------------------------------------------------------
+// Item i: the device word that says whether the frame that leaves the denoiser in this wave starts a scene - its stream's flag ring at the
+// frame's number (frvsr_temporal_plan.h: ring_word), NULL for a stream without a live ring - and the stream's lr_prev / hr_prev as
+// FrvsrUpscaler::open_slots hands them out.  BY VALUE in the kernel arguments, as FrvtTable: 1536 bytes, no device table.
+struct FrvtClearTable { const uint32_t* flag[FRVT_MAX_ITEMS]; void* lr[FRVT_MAX_ITEMS]; void* hr[FRVT_MAX_ITEMS]; };
+static_assert(sizeof(FrvtClearTable) == 1536, "the wave's table travels in the kernel arguments: keep it far below 4 KiB");
+static_assert(frvsr_temporal::CUT_RING == BSVD_ONLINE_CUT_RING, "the wave plan addresses the denoiser's flag ring: one size");
+// lr[i] (lr_bytes) and hr[i] (hr_bytes) become zero for every item whose flag pointer is not NULL and whose word is not 0: what open_slots gives
+// a stream's first frame (cut::clear_items with the flag read where the ring keeps it).  One launch.  Refuses - before the launch - n_items
+// outside 1..64, a size that is 0 or no multiple of 4, and a NULL or not 16-byte aligned lr / hr of ANY item; a flag pointer is NULL or 4-byte
+// aligned.
+void op_frvt_clear_flagged_items(const FrvtClearTable& tab, int n_items, size_t lr_bytes, size_t hr_bytes, hipStream_t st);
+
+// what one stream owns beside its recurrent state (FrvsrUpscaler::Slot): TemporalSlot
 struct FrvtSlot {
   BsvdOnline on;
   DevBuf ring;          // lr_before of the frames inside the denoiser: (lag + max_push) frames of (3, lr_h, lr_w) fp32, frame i in slot i % frames
   bool first_frame = true;
+  std::unique_ptr<TemporalCut> cut;   // null until a threshold > 0 reaches the slot
   long long pushed = 0, emitted = 0;   // frames of the running stream
   double rate = -1;     // the stream's denoise rate (set_denoise_rate); negative: the object's.  Ends with the stream
   bool running() const { return on.state.pushed > 0; }
@@ -47,6 +62,7 @@ struct FrvsrTemporal {
   DevBuf lr4, den;      // job buffers, shared: the packed denoiser input of a round, the denoised frames of a round or a flush
   DevBuf k_sharp;       // the nine taps of sharpen_ker(strength = 0.00002), uploaded once
   double denoise_rate = 1.0;
+  double cut_threshold = 0;   // what set_scene_cut last said; a slot's detector is made when the slot first needs it
   int max_push = 0;
 
   void create(ss4k_ctx* c, Frvsr* m, Model* bsvd_stream_model, int lr_h, int lr_w, int out_h, int out_w, double denoise_rate, int max_push, int max_streams);
@@ -63,6 +79,9 @@ struct FrvsrTemporal {
   void reset(int s);                       // drops the stream: denoiser state, LR ring and recurrent state count as gone
   int pending(int s) const { return slot(s).on.pending(); }
   void set_denoise_rate(int s, float rate);
+  // Scene cuts, every slot (include/ss4k.h: ss4k_frvsr_temporal_set_scene_cut).  0: detection stops, the stored frames and the counters go; flags
+  // already in a ring keep acting - on the denoiser and, when their frames leave, on the generator
+  void set_scene_cut(double threshold);
   void out_shape(int* oh, int* ow) const { up.out_shape(oh, ow); }
   size_t state_bytes() const;              // the slots in use
   size_t stream_state_bytes_for() const;   // what one slot will hold, before any push
@@ -70,10 +89,13 @@ struct FrvsrTemporal {
   float level(const FrvtSlot& s) const { return (float)(0.1 * (s.rate < 0 ? denoise_rate : s.rate)); }   // fsrcnn_upscaler.py:269-271
 
  private:
-  // one wave: open_slots, denoised_in_items, the step, close_slots, frames out.  den_of / ring_of / out_of: entry i's denoised frame, ring slot
-  // and output frame
-  void run_wave(const frvsr_temporal::Wave& wv, const float* const* den_of, const float* const* ring_of, uint8_t* const* out_of, hipStream_t st);
+  // one wave: open_slots, the late reset if a stream of the wave carries cut flags, denoised_in_items, the step, close_slots, frames out.
+  // den_of / ring_of / out_of: entry i's denoised frame, ring slot and output frame; flag_of: NULL (no entry has a live flag ring) or entry i's
+  // word in its stream's flag ring, NULL for an entry without one
+  void run_wave(const frvsr_temporal::Wave& wv, const float* const* den_of, const float* const* ring_of, uint8_t* const* out_of,
+                const uint32_t* const* flag_of, hipStream_t st);
   void check_sizes(int h, int w) const;    // the launchers' size limits, restated
+  void want_cut(FrvtSlot& s);              // the detector of a slot that has none yet, once a threshold is set
 };
 
 }  // namespace ss4k

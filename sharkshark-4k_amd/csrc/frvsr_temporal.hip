@@ -1,4 +1,5 @@
-// The one glue kernel of the frame-recurrent chain with the online denoiser in front (frvsr_temporal.cpp, FrvsrTemporal::round / flush):
+// The glue kernels of the frame-recurrent chain with the online denoiser in front (frvsr_temporal.cpp, FrvsrTemporal::round / flush): the one
+// every wave runs, and frvt::clear_flagged_items (below), which only the waves of streams that carry scene-cut flags run in front of it.
 // frvt::denoised_in_items turns a wave's denoised frames into the generator's input, each written into its own stream's lr buffer,
 //   lr_curr = 0.8 * clamp01(sharpen3x3_reflect(den)) + 0.2 * lr_before            (fsrcnn_upscaler.py:279-281)
 // in ONE launch whatever the wave's size.  The value is bit for bit what glue::depthwise_reflect<3> (glue.hip) gives with clamp and blend: the
@@ -67,6 +68,50 @@ void op_frvt_denoised_in_items(const FrvtTable& tab, int n_items, int h, int w, 
   SS4K_GLUE_ROUTE("frvt::denoised_in_items");
   const dim3 grid((unsigned)std::min((w + 255) / 256, 64), (unsigned)std::min(h, 65535), (unsigned)(3 * n_items));
   hipLaunchKernelGGL(k_frvt_denoised_in, grid, dim3(256), 0, st, tab, taps_dev, n_items, h, w, blend_a, blend_b);
+  SS4K_LAUNCH_OK();
+}
+
+// ---- frvt::clear_flagged_items: the late reset of a scene cut -----------------------------------------------------------------------------------
+// A frame that the detector flagged when it went in leaves the denoiser 16 frames later; in that wave its stream's lr_prev / hr_prev must read
+// as zero, as for a stream's first frame.  blockIdx.y is the item: its flag pointer and the flag word are uniform over the workgroup (loads from
+// the kernel arguments and one load through a uniform pointer), so a workgroup whose item has no live ring or no cut returns at once, whole.
+// Otherwise it zero-fills both buffers grid-stride over blockIdx.x with 16-byte stores, plus a tail of up to three dwords - cut::clear_items'
+// fill (scene_cut.hip) with the flag read where the ring keeps it.  No LDS, no atomics, no workgroup waits for another, no scratch.
+typedef uint32_t frvt_u32x4 __attribute__((ext_vector_type(4)));
+constexpr int FRVT_CLEAR_BLOCK = 256;
+
+__device__ __forceinline__ void frvt_zero_fill(void* p, size_t bytes) {
+  const size_t chunks = bytes >> 4;
+  frvt_u32x4* q = reinterpret_cast<frvt_u32x4*>(p);
+  const frvt_u32x4 z = {0u, 0u, 0u, 0u};
+  for (size_t c = blockIdx.x * (size_t)FRVT_CLEAR_BLOCK + threadIdx.x; c < chunks; c += (size_t)gridDim.x * FRVT_CLEAR_BLOCK) q[c] = z;
+  if (blockIdx.x == 0 && threadIdx.x < ((bytes & 15) >> 2)) reinterpret_cast<uint32_t*>(p)[(chunks << 2) + threadIdx.x] = 0u;
+}
+
+__global__ __launch_bounds__(FRVT_CLEAR_BLOCK) void k_frvt_clear_flagged(FrvtClearTable tab, int n_items, size_t lr_bytes, size_t hr_bytes) {
+  const int item = blockIdx.y;
+  if (item >= n_items) return;
+  const uint32_t* flag = tab.flag[item];
+  if (!flag) return;      // a stream without a live flag ring
+  if (!*flag) return;     // the leaving frame starts no scene
+  frvt_zero_fill(tab.lr[item], lr_bytes);
+  frvt_zero_fill(tab.hr[item], hr_bytes);
+}
+
+void op_frvt_clear_flagged_items(const FrvtClearTable& tab, int n_items, size_t lr_bytes, size_t hr_bytes, hipStream_t st) {
+  // every refusal before the launch
+  SS4K_REQUIRE(n_items >= 1 && n_items <= FRVT_MAX_ITEMS, "frvsr clear flagged: 1..64 items");
+  SS4K_REQUIRE(lr_bytes > 0 && hr_bytes > 0 && lr_bytes % 4 == 0 && hr_bytes % 4 == 0, "frvsr clear flagged: sizes are multiples of 4");
+  for (int i = 0; i < n_items; ++i) {
+    SS4K_REQUIRE(tab.lr[i] && tab.hr[i], "frvsr clear flagged: NULL state pointer");
+    SS4K_REQUIRE((((uintptr_t)tab.lr[i] | (uintptr_t)tab.hr[i]) & 15) == 0, "frvsr clear flagged: state pointers are 16-byte aligned");
+    SS4K_REQUIRE(((uintptr_t)tab.flag[i] & 3) == 0, "frvsr clear flagged: a flag is a 32-bit word");
+  }
+  SS4K_GLUE_ROUTE("frvt::clear_flagged_items");
+  // cut::clear_items' shape: at most max(32, 2048 / n) workgroups per item, enough to stream the larger buffer
+  const size_t want = ((std::max(lr_bytes, hr_bytes) >> 4) + FRVT_CLEAR_BLOCK - 1) / FRVT_CLEAR_BLOCK, cap = (size_t)std::max(32, 2048 / n_items);
+  const unsigned gx = (unsigned)std::max<size_t>(1, std::min(want, cap));
+  hipLaunchKernelGGL(k_frvt_clear_flagged, dim3(gx, (unsigned)n_items), dim3(FRVT_CLEAR_BLOCK), 0, st, tab, n_items, lr_bytes, hr_bytes);
   SS4K_LAUNCH_OK();
 }
 

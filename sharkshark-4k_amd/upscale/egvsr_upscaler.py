@@ -36,8 +36,15 @@ job of K frames that ends E streams returns at most ``temporal_result_bound(K, E
 unnamed stream.  ``denoise_rate`` is the service's rate, ``stream_rates`` a stream's own; ``denoise_weights`` is the BSVD checkpoint, resolved
 like the per-frame service's ``'denoise'`` entry (None: ``bsvd-32.pth`` in the checkpoint directory or ``FileNotFoundError``; ``'synthetic'``,
 or ``weights='synthetic'`` with nothing else said, is the opt-in); ``temporal_max_push`` (4) frames of one stream enter per round.  ``lr_shape``
-must be divisible by 4: of the reference's three, (630, 1120) is refused.  Refused with it, before any GPU work: ``scene_cut`` (a cut seen
-when a frame goes in would have to reset the recurrent state 16 frames later), ``HostFrames`` jobs, and ``EgvsrNode(denoise_temporal=True)``.
+must be divisible by 4: of the reference's three, (630, 1120) is refused.  Refused with it, before any GPU work: ``scene_cut`` (that keyword
+names the detector that resets at input time; the denoised chain's is ``denoise_scene_cut``), ``HostFrames`` jobs, and
+``EgvsrNode(denoise_temporal=True)``.
+
+``denoise_scene_cut=T`` (None / 0: off, the default; needs ``denoise_temporal=True``): scene cuts for the denoised streams
+(``ss4k_frvsr_temporal_set_scene_cut``, include/ss4k.h).  Every stream's input frames are compared as they arrive, on the device; at a hard cut
+the denoiser does not reach across the scene's first frame, and when that frame leaves the denoiser 16 frames later the stream's ``lr_prev`` /
+``hr_prev`` are zeroed before the step: a stream is the concatenation of its scenes, each as if it had been a stream of its own.  A job still
+returns the frames it returns without the keyword.  T is validated as ``scene_cut``; each job's profiler carries ``egvsr.scene_cuts``.
 
 ``generator='tecogan'`` runs TecoGAN's FRNet instead (``nb`` then defaults to 16; its checkpoint is that class's bare state_dict).
 
@@ -163,7 +170,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
 
     def __init__(self, lr_level=1, device=0, on_queue=None, *, weights=None, checkpoint_dir: Optional[str] = None, dtype="f16", nb=None,
                  lr_shape=None, seed=0, max_streams=1, generator="egvsr", degradation="BD", scene_cut=None, denoise_temporal=False,
-                 denoise_rate=1.0, denoise_weights=None, temporal_max_push=None):
+                 denoise_rate=1.0, denoise_weights=None, temporal_max_push=None, denoise_scene_cut=None):
         self.lr_shape = tuple(lr_shape) if lr_shape is not None else LR_SHAPES[lr_level]
         self.scale = 4
         self.hr_shape = tuple([i * self.scale for i in self.lr_shape])
@@ -185,10 +192,17 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self.denoise_weights = denoise_weights
         self.temporal_max_push = int(temporal_max_push) if temporal_max_push else 4
         self.last_ready = []
+        # denoise_scene_cut: the denoised streams' scene-cut threshold (_capi.TemporalFrvsrUpscaler.set_scene_cut); None / 0: off
+        try:
+            self.denoise_scene_cut = check_scene_cut(denoise_scene_cut)
+        except ValueError as e:
+            raise ValueError(str(e).replace("scene_cut", "denoise_scene_cut", 1)) from None
+        if self.denoise_scene_cut is not None and not self.denoise_temporal:
+            raise ValueError("denoise_scene_cut belongs to denoise_temporal=True: without the denoiser in front, scene_cut is the keyword")
         if self.denoise_temporal:
             if self.scene_cut:
-                raise ValueError("denoise_temporal=True together with scene_cut is not supported: a cut seen when a frame goes in has to reset "
-                                 "the recurrent state 16 frames later, when the frame comes out of the denoiser")
+                raise ValueError("denoise_temporal=True together with scene_cut is not supported: scene_cut resets the recurrent state when a "
+                                 "frame goes in, and here the frame comes out of the denoiser 16 frames later (use denoise_scene_cut)")
             check_temporal_lr_shape(self.lr_shape)
             if isinstance(denoise_rate, bool) or not isinstance(denoise_rate, (int, float)) or not (0.0 <= float(denoise_rate) < float("inf")):
                 raise ValueError(f"denoise_rate={denoise_rate!r}: a denoise rate is a finite number >= 0")
@@ -254,7 +268,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         key = (tuple(self.lr_shape), None if self.output_shape is None else tuple(int(v) for v in self.output_shape))
         if self._up is None or self._up_key != key:   # (the pipelines overwrite lr_shape / output_shape after construction)
             if self._up is not None:
-                if self.scene_cut:
+                if self.scene_cut or self.denoise_scene_cut:
                     self._cuts_before += self._up.scene_cut_total()
                 self._up.close()
             self._up, self._up_key = self._make_upscaler(_capi, key), key
@@ -265,8 +279,9 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         if self.denoise_temporal:
             check_temporal_lr_shape(key[0])   # (the pipelines overwrite lr_shape after construction)
             self._t_index = {}
+            more = {"scene_cut": self.denoise_scene_cut} if self.denoise_scene_cut else {}   # (off: the object is built as before the keyword)
             up = _capi.TemporalFrvsrUpscaler(self.ctx, self.model, self.denoise_model, key[0], key[1], float(self.denoise_rate),
-                                             self.temporal_max_push, self.max_streams)
+                                             self.temporal_max_push, self.max_streams, **more)
             log(f"denoised streams: {self.max_streams} stream slot(s), {up.stream_state_bytes_for() / 2**20:.1f} MiB of state per running "
                 f"stream (max_push {self.temporal_max_push})")
             return up
@@ -277,7 +292,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
     def scene_cuts(self) -> int:
         """Scene cuts seen by this worker in the rounds that have completed on the device (never synchronises); 0 with the detector off."""
         up = getattr(self, "_up", None)
-        return self._cuts_before + (up.scene_cut_total() if up is not None and self.scene_cut else 0)
+        return self._cuts_before + (up.scene_cut_total() if up is not None and (self.scene_cut or self.denoise_scene_cut) else 0)
 
     def reset(self):
         """Forget ``lr_prev`` / ``hr_prev``: the next frame is a stream's first (egvsr_upscaler.py:165-166)."""
@@ -465,6 +480,8 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
             return self.upscale(hf, streams=streams, end_streams=end_streams, stream_rates=rates)
 
         upscaled, elapsed, prof = self._run_job(job, run)
+        if self.denoise_scene_cut:
+            prof.set("egvsr.scene_cuts", self.scene_cuts())   # (the cuts of the rounds that have completed: never synchronises)
         entry = None
         if hasattr(job, "streams") or hasattr(job, "end_streams"):
             try:   # the caller's own type, when it takes the eight fields

@@ -12,7 +12,16 @@ rounds after 16 + ``--warmup`` settle rounds, ``--runs`` times; the JSON line ho
 (``SS4K_LIB=.../libss4k_hip_dev.so``) it also times ``frvt::denoised_in_items`` alone, microseconds per launch at 1 and S items.
 No gate: it states what it measures.
 
+``--scene-cut T``: after the figures above (detector off, as ever) the chain's steady-state window is timed again ``--repeats`` times with the
+scene-cut detector off and on in turn, in this process and on the one object (``ss4k_frvsr_temporal_set_scene_cut``): ``ms_off`` / ``ms_on``
+hold every window's ms per frame, with their medians and spreads, and ``launches_per_round`` says what a round gains (the detector's three
+launches per item and one ``frvt::clear_flagged_items`` per wave).  The rounds of these windows walk a clip of frames that differ a little, so
+T = 255 never fires; ``--cut-every N`` makes every N-th frame of every stream black - a cut at it and none after it, at a T between the
+clip's motion and that jump (60) - and ``cuts_per_window`` says how many the device counted.  Needs a library with the detector; without
+``--scene-cut`` the tool runs on an older build too (``SS4K_LIB``) for an A/B.
+
 Usage:  python tools/frvsr_temporal_time.py [--h 540 --w 960 --dtype f16 --streams 1 4 --iters 24 --runs 3] [--generator egvsr] [--out FILE]
+                                            [--scene-cut T [--cut-every N] [--repeats 3]]
         SS4K_LIB=.../libss4k_hip_dev.so python tools/frvsr_temporal_time.py --kernel-only [--iters 200] [--out FILE]
 """
 import argparse
@@ -64,6 +73,47 @@ def kernel_us(ctx, S, h, w, iters):
     return out
 
 
+def scene_cut_windows(a, chain, frames, slots, out_chain):
+    """--scene-cut: the chain's steady-state window with the detector off and on in turn, ``--repeats`` times each; the JSON keys it adds."""
+    S = len(slots)
+    g = torch.Generator(device="cuda").manual_seed(5)
+    # a clip per stream: the frames differ by +-2 levels (far below any threshold); --cut-every swaps in a black frame
+    clip = [(frames.to(torch.int16) + torch.randint(-2, 3, frames.shape, device="cuda", generator=g, dtype=torch.int16)).clamp_(0, 255).to(torch.uint8)
+            for _ in range(8)]
+    black = torch.zeros_like(frames)
+    count = [0]
+
+    def one_round():
+        count[0] += 1
+        src = black if a.cut_every > 0 and count[0] % a.cut_every == 0 else clip[count[0] % len(clip)]
+        chain.round([src[i] for i in range(S)], slots, out=out_chain)
+
+    ms, cuts = {"off": [], "on": []}, []
+    for _ in range(a.repeats):
+        for mode in ("off", "on"):
+            chain.set_scene_cut(a.scene_cut if mode == "on" else 0)
+            for s in slots:
+                chain.reset(s)
+            count[0] = 0
+            for _ in range(LAG + a.warmup):
+                one_round()
+            torch.cuda.synchronize()
+            before = chain.scene_cut_total()
+            ms[mode].append(timed(one_round, a.iters) / S)
+            torch.cuda.synchronize()
+            if mode == "on":
+                cuts.append(chain.scene_cut_total() - before)
+    chain.set_scene_cut(0)
+    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    return {"scene_cut": a.scene_cut, "cut_every": a.cut_every, "ms_off": [round(v, 4) for v in ms["off"]], "ms_on": [round(v, 4) for v in ms["on"]],
+            "ms_off_median": round(med["off"], 4), "ms_on_median": round(med["on"], 4), "on_over_off": round(med["on"] / med["off"], 4),
+            "spread_off": round(max(ms["off"]) / min(ms["off"]), 4), "spread_on": round(max(ms["on"]) / min(ms["on"]), 4), "cuts_per_window": cuts,
+            # what a round of S one-frame items (one wave) gains with the detector on, read from the executor: per item the sums, the rule, the
+            # copy of the stored frame, the copy of the counters to the pinned block and the copy of the flags into the denoiser's ring; per
+            # wave frvt::clear_flagged_items
+            "launches_per_round": {"detector_kernels": 2 * S, "detector_copies": 3 * S, "clear_flagged_items": 1}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--h", type=int, default=540)
@@ -75,6 +125,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--scene-cut", type=float, default=0.0, help="also time the chain with the scene-cut detector off / on in turn, at this threshold")
+    ap.add_argument("--cut-every", type=int, default=0, help="--scene-cut: every N-th frame of every stream is black: a forced scene cut")
+    ap.add_argument("--repeats", type=int, default=3, help="--scene-cut: windows per setting")
     ap.add_argument("--kernel-only", action="store_true", help="dev library: the wave kernel's microseconds per launch alone")
     a = ap.parse_args()
     ctx = _capi.Context(0)
@@ -129,6 +182,8 @@ def main():
                 "spread": {k: round(max(v) / min(v), 4) for k, v in res.items()},
                 "chain_over_sum": round(best["chain"] / (best["frvsr"] + best["bsvd"]), 4),
                 "state_bytes_per_stream": chain.stream_state_bytes_for(), "denoised_in_us_per_launch": kernel_us(ctx, S, a.h, a.w, a.iters)}
+        if a.scene_cut > 0:
+            line.update(scene_cut_windows(a, chain, frames, slots, out_chain))
         print(json.dumps(line), flush=True)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
