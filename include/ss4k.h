@@ -523,10 +523,21 @@ int ss4k_upscaler_temporal_set_denoise_rate_stream(ss4k_upscaler_temporal* up, i
  * stream (the next frame is not compared); _release_idle frees an idle slot's detector buffers, and that slot's counters start over.
  * _state_bytes includes the detectors' device buffers (the stored frame of 3 h w bytes and under 1 KiB of sums, flags and counters per slot);
  * _stream_state_bytes_for does not.  _scene_cut_stats_stream synchronises with hip_stream; _scene_cut_total never does: the cuts of the rounds
- * that have COMPLETED, summed over the slots.  A refused round changes nothing, the detectors included. */
+ * that have COMPLETED, summed over the slots.  A refused round changes nothing, the detectors included.
+ * ANY LR SHAPE (_create_padded).  BSVD's two 2x poolings need planes divisible by 4, and the reference never runs the denoiser at another
+ * shape, so this library defines it.  For (lr_h, lr_w), both at least 8, let (ph, pw) be (lr_h, lr_w) rounded up to multiples of 4.  Step 1 and
+ * the slot's LR ring stay at (lr_h, lr_w).  The denoiser sees each colour plane padded at the bottom and on the right by reflection without
+ * repeating the edge (torch's and numpy's 'reflect': padded row y >= lr_h is row 2 (lr_h - 1) - y, columns likewise; at most 3 rows or columns,
+ * fewer than the 8 a plane has), the noise plane is its constant over the whole (ph, pw), and the denoiser runs - and keeps its state - at
+ * (ph, pw).  den_t is cropped to its top-left (lr_h, lr_w); step 3 acts on the crop, and the sharpening kernel's own reflection is at the
+ * crop's borders and never reads the padding.  The generator, lr_prev / hr_prev, the output, scene cuts, rates, flush and reset are at
+ * (lr_h, lr_w), exactly as above.  _create_padded takes _create's arguments; a shape divisible by 4 builds the very object _create builds (the
+ * same launches), any other shape of at least 8 x 8 the padded form.  _create itself keeps refusing such a shape. */
 typedef struct ss4k_frvsr_temporal ss4k_frvsr_temporal;
 int ss4k_frvsr_temporal_create(ss4k_ctx* ctx, ss4k_frvsr* frvsr, ss4k_model* bsvd_stream_model, int lr_h, int lr_w, int out_h, int out_w,
                                double denoise_rate, int max_push, int max_streams, ss4k_frvsr_temporal** out);
+int ss4k_frvsr_temporal_create_padded(ss4k_ctx* ctx, ss4k_frvsr* frvsr, ss4k_model* bsvd_stream_model, int lr_h, int lr_w, int out_h, int out_w,
+                                      double denoise_rate, int max_push, int max_streams, ss4k_frvsr_temporal** out);
 void ss4k_frvsr_temporal_destroy(ss4k_frvsr_temporal* up);
 int ss4k_frvsr_temporal_round(ss4k_frvsr_temporal* up, const uint8_t* const* frames_dev, const int* slots, int k_frames, int h, int w,
                               uint8_t* out_dev, size_t out_capacity_bytes, int* n_out_per_item, int* item_slots, int* n_items, void* hip_stream);

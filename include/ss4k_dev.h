@@ -106,6 +106,12 @@ int ss4k_dev_op_temporal_gather(ss4k_ctx* ctx, const float* const* src, const ui
  * levels[j] where the one above writes level.  Same routes, same refusals, and SS4K_EINVAL for NULL levels. */
 int ss4k_dev_op_temporal_gather_levels(ss4k_ctx* ctx, const float* const* src, const uint32_t* const* flags, int k, size_t plane_px, int planes,
                                        uint64_t start_bits, float level_start, const float* levels, float* dst, void* hip_stream);
+/* ... and the padded four-plane form of the frame-recurrent chain at an lr_shape that 4 does not divide; route "tround::gather_planes_pad".
+ * src[j]: (3, lh, lw) fp32 at any 4-byte address -> dst (k, 4, ph, pw) fp32, 16-byte aligned, (ph, pw) = (lh, lw) rounded up to multiples of
+ * 4: planes 0..2 padded at the bottom and on the right by 'reflect' (row y >= lh is row 2 (lh - 1) - y, columns likewise), plane 3 by the
+ * rule above, over the whole (ph, pw).  SS4K_EINVAL before any launch: what the one above refuses, lh < 4 or lw < 4, 4 ph pw >= 2^31. */
+int ss4k_dev_op_temporal_gather_pad(ss4k_ctx* ctx, const float* const* src, const uint32_t* const* flags, int k, int lh, int lw,
+                                    uint64_t start_bits, float level_start, const float* levels, float* dst, void* hip_stream);
 
 /* ---- launchers of the frame-recurrent upscaler's glue (csrc/frvsr.hip, csrc/frvsr.h) that the public API reaches only inside a whole
  * step or round: what tests/test_gpu_frvsr_glue_budget.py bounds against float64.  Same conventions as above; their routes are reported
@@ -159,6 +165,11 @@ int ss4k_dev_op_frvsrbi_bilinear4_add_items(ss4k_ctx* ctx, const float* conv, co
  * ss4k_dev_op_frvsrbi_ below.) */
 int ss4k_dev_op_frvsrt_denoised_in(ss4k_ctx* ctx, const float* const* den, const float* const* lr, float* const* dst, int n_items, int h, int w,
                                    const float* taps_dev, void* hip_stream);
+/* ... on the top-left (h, w) of denoised planes of (ph, pw) >= (h, w); route "frvt::denoised_in_crop_items".  den[i]: 3 planes of (ph, pw),
+ * lr[i] and dst[i]: 3 planes of (h, w).  Bit for bit the one above on a contiguous copy of the crop; nothing of den outside the crop is read.
+ * SS4K_EINVAL before any launch: what the one above refuses, ph < h or pw < w, 3 ph pw >= 2^31; the overlap check takes den at (ph, pw). */
+int ss4k_dev_op_frvsrt_denoised_in_crop(ss4k_ctx* ctx, const float* const* den, const float* const* lr, float* const* dst, int n_items, int h,
+                                        int w, int ph, int pw, const float* taps_dev, void* hip_stream);
 /* ... and the late reset of a scene cut; route "frvt::clear_flagged_items".  flag_ptrs / lr_ptrs / hr_ptrs: HOST arrays of n_items (1..64) device
  * pointers.  One launch: lr_ptrs[i] (lr_bytes) and hr_ptrs[i] (hr_bytes) become zero for every item whose flag pointer is not NULL and whose
  * 32-bit word is not 0; nothing else is written.  SS4K_EINVAL before any launch: n_items outside 1..64, a size that is 0 or no multiple of 4, a

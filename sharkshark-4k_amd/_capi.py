@@ -60,6 +60,8 @@ SYMBOLS = [
     # ... and its scene cuts
     "ss4k_frvsr_temporal_set_scene_cut", "ss4k_frvsr_temporal_scene_cut", "ss4k_frvsr_temporal_scene_cut_stats_stream",
     "ss4k_frvsr_temporal_scene_cut_total",
+    # ... and an lr_shape that 4 does not divide: reflect-pad in front of the denoiser, crop behind it
+    "ss4k_frvsr_temporal_create_padded",
 ]
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
@@ -98,6 +100,8 @@ DEV_SYMBOLS = [
     "ss4k_dev_op_frvsrt_denoised_in", "ss4k_dev_guard_poison_frvsr_temporal",
     # the late reset of a scene cut in that chain (tests/test_gpu_frvsr_temporal_cuts_kernel.py)
     "ss4k_dev_op_frvsrt_clear_flagged",
+    # the two kernels of the padded form of that chain (tests/test_gpu_frvsr_temporal_pad_kernel.py)
+    "ss4k_dev_op_temporal_gather_pad", "ss4k_dev_op_frvsrt_denoised_in_crop",
 ]
 
 
@@ -349,6 +353,11 @@ def load(path: str) -> C.CDLL:
         L.ss4k_frvsr_temporal_scene_cut.argtypes = [vp, C.POINTER(C.c_double)]
         L.ss4k_frvsr_temporal_scene_cut_stats_stream.argtypes = [vp, i, C.POINTER(SceneCutStats), vp]
         L.ss4k_frvsr_temporal_scene_cut_total.argtypes = [vp, C.POINTER(C.c_uint64)]
+    if hasattr(L, "ss4k_frvsr_temporal_create_padded"):   # (absent from builds before the padded form)
+        L.ss4k_frvsr_temporal_create_padded.argtypes = [vp, vp, vp, i, i, i, i, C.c_double, i, i, C.POINTER(vp)]
+    if hasattr(L, "ss4k_dev_op_temporal_gather_pad"):   # dev library only
+        L.ss4k_dev_op_temporal_gather_pad.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, i, C.c_uint64, C.c_float, C.POINTER(C.c_float), vp, vp]
+        L.ss4k_dev_op_frvsrt_denoised_in_crop.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, i, i, i, vp, vp]
     if hasattr(L, "ss4k_dev_op_frvsrt_clear_flagged"):   # dev library only
         L.ss4k_dev_op_frvsrt_clear_flagged.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, sz, sz, vp]
     if hasattr(L, "ss4k_dev_op_frvsrt_denoised_in"):   # dev library only
@@ -1275,17 +1284,23 @@ class TemporalFrvsrUpscaler:
     """ss4k_frvsr_temporal: the frame-recurrent service chain (uint8 HWC frames -> uint8 NHWC) with the online BSVD denoiser in front of the
     generator, per stream.  ``model`` is a ``Frvsr`` (either generator, either degradation), ``denoise`` a BSVD ``Model`` built with
     ``bsvd_stream=True``; both are held, not owned.  A stream returns nothing for its first 16 frames and one frame per frame after; ``flush``
-    returns the up to 16 frames still inside and ends it.  The methods mirror ``TemporalUpscaler``'s."""
+    returns the up to 16 frames still inside and ends it.  The methods mirror ``TemporalUpscaler``'s.  ``pad=True``
+    (ss4k_frvsr_temporal_create_padded) accepts an ``lr_shape`` that 4 does not divide: the denoiser alone runs at the shape rounded up to
+    multiples of 4, on reflect-padded planes, and its output is cropped (include/ss4k.h); at a divisible shape it changes nothing."""
 
     def __init__(self, ctx: Context, model: Frvsr, denoise: Model, lr_shape, output_shape=None, denoise_rate: float = 1.0, max_push: int = 4,
-                 max_streams: int = 1, scene_cut: Optional[float] = None):
+                 max_streams: int = 1, scene_cut: Optional[float] = None, pad: bool = False):
         self.ctx, self.model, self.denoise, self.max_push, self.max_streams = ctx, model, denoise, int(max_push), int(max_streams)
         self.lr_shape = (int(lr_shape[0]), int(lr_shape[1]))
         oh, ow = (0, 0) if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
         h = C.c_void_p()
+        if pad and not self.has_padded():
+            raise RuntimeError("pad=True needs a library with ss4k_frvsr_temporal_create_padded")
+        create = lib().ss4k_frvsr_temporal_create_padded if pad else lib().ss4k_frvsr_temporal_create
+        self.padded_shape = tuple((v + 3) // 4 * 4 for v in self.lr_shape) if pad else self.lr_shape
         with torch.cuda.device(ctx.device):
-            _check(lib().ss4k_frvsr_temporal_create(ctx._h, model._h, denoise._h, self.lr_shape[0], self.lr_shape[1], oh, ow, float(denoise_rate),
-                                                    self.max_push, self.max_streams, C.byref(h)))
+            _check(create(ctx._h, model._h, denoise._h, self.lr_shape[0], self.lr_shape[1], oh, ow, float(denoise_rate),
+                          self.max_push, self.max_streams, C.byref(h)))
         self._h, self.lag = h, 16
         if scene_cut is not None:
             try:
@@ -1293,6 +1308,11 @@ class TemporalFrvsrUpscaler:
             except Exception:
                 self.close()
                 raise
+
+    @staticmethod
+    def has_padded() -> bool:
+        """Whether the loaded library has ``pad=True`` (an older build loaded through SS4K_LIB has not)."""
+        return hasattr(lib(), "ss4k_frvsr_temporal_create_padded")
 
     def close(self):
         if getattr(self, "_h", None):

@@ -218,6 +218,16 @@ int ss4k_dev_op_temporal_gather_levels(ss4k_ctx* c, const float* const* src, con
     dev_temporal_gather(src, flags, k, plane_px, planes, start_bits, level_start, levels, 0.f, dst, s);
   });
 }
+int ss4k_dev_op_temporal_gather_pad(ss4k_ctx* c, const float* const* src, const uint32_t* const* flags, int k, int lh, int lw, uint64_t start_bits,
+                                    float level_start, const float* levels, float* dst, void* s) {
+  return guard([&] {
+    SS4K_REQUIRE(c && src && levels, "ss4k_dev_op_temporal_gather_pad: NULL argument");
+    SS4K_REQUIRE(k >= 1 && k <= TROUND_MAX_FRAMES, "ss4k_dev_op_temporal_gather_pad: 1..64 frames");
+    TroundTable tab{};
+    for (int j = 0; j < k; ++j) { tab.src[j] = src[j]; tab.flag[j] = flags ? flags[j] : nullptr; tab.level[j] = levels[j]; }
+    op_tround_gather_pad(tab, dst, k, lh, lw, (unsigned long long)start_bits, level_start, (hipStream_t)s);
+  });
+}
 int ss4k_dev_op_temporal_gather(ss4k_ctx* c, const float* const* src, const uint32_t* const* flags, int k, size_t plane_px, int planes,
                                 uint64_t start_bits, float level_start, float level, float* dst, void* s) {
   return guard([&] {

@@ -18,6 +18,16 @@ int ss4k_frvsr_temporal_create(ss4k_ctx* ctx, ss4k_frvsr* frvsr, ss4k_model* bsv
     *out = u.release();
   });
 }
+int ss4k_frvsr_temporal_create_padded(ss4k_ctx* ctx, ss4k_frvsr* frvsr, ss4k_model* bsvd_stream_model, int lr_h, int lr_w, int out_h, int out_w,
+                                      double denoise_rate, int max_push, int max_streams, ss4k_frvsr_temporal** out) {
+  return guard([&] {
+    SS4K_REQUIRE(ctx && frvsr && bsvd_stream_model && out, "ss4k_frvsr_temporal_create_padded: NULL argument");
+    SS4K_HIP(hipSetDevice(ctx->device));
+    auto u = std::make_unique<ss4k_frvsr_temporal>();
+    u->t.create(ctx, &frvsr->f, &bsvd_stream_model->m, lr_h, lr_w, out_h, out_w, denoise_rate, max_push, max_streams, true);
+    *out = u.release();
+  });
+}
 void ss4k_frvsr_temporal_destroy(ss4k_frvsr_temporal* up) { delete up; }
 int ss4k_frvsr_temporal_round(ss4k_frvsr_temporal* up, const uint8_t* const* frames_dev, const int* slots, int k_frames, int h, int w,
                               uint8_t* out_dev, size_t out_capacity_bytes, int* n_out_per_item, int* item_slots, int* n_items, void* stream) {
@@ -136,12 +146,23 @@ int ss4k_dev_op_frvsrt_denoised_in(ss4k_ctx* c, const float* const* den, const f
     SS4K_HIP(hipGetLastError());
   });
 }
+int ss4k_dev_op_frvsrt_denoised_in_crop(ss4k_ctx* c, const float* const* den, const float* const* lr, float* const* dst, int n_items, int h, int w,
+                                        int ph, int pw, const float* taps_dev, void* s) {
+  return guard([&] {
+    SS4K_REQUIRE(c && den && lr && dst, "ss4k_dev_op_frvsrt_denoised_in_crop: NULL argument");
+    SS4K_REQUIRE(n_items >= 1 && n_items <= FRVT_MAX_ITEMS, "ss4k_dev_op_frvsrt_denoised_in_crop: 1..64 items");
+    FrvtTable tab{};
+    for (int i = 0; i < n_items; ++i) { tab.den[i] = den[i]; tab.lr[i] = lr[i]; tab.dst[i] = dst[i]; }
+    op_frvt_denoised_in_crop_items(tab, n_items, h, w, ph, pw, taps_dev, 0.8f, (float)(1 - 0.8), (hipStream_t)s);
+    SS4K_HIP(hipGetLastError());
+  });
+}
 int ss4k_dev_guard_poison_frvsr_temporal(ss4k_frvsr_temporal* up, int* buffers, size_t* bytes, size_t* bytes_256) {
   return guard([&] {
     SS4K_REQUIRE(up && buffers && bytes && bytes_256, "ss4k_dev_guard_poison_frvsr_temporal: NULL argument");
     *buffers = 0; *bytes = 0; *bytes_256 = 0;
     SS4K_HIP(hipDeviceSynchronize());
-    for (DevBuf* b : {&up->t.lr4, &up->t.den}) {
+    for (DevBuf* b : {&up->t.lr4, &up->t.den}) {   // (a padded object's are these two as well, at the denoiser's larger shape)
       if (!b->ptr || !b->transient) continue;
       SS4K_HIP(hipMemset(b->ptr, 0xFF, b->bytes));
       *buffers += 1; *bytes += b->bytes; *bytes_256 += (b->bytes + 255) & ~size_t(255);

@@ -27,11 +27,11 @@ static std::vector<float> frvt_sharpen_taps(double strength) {
 }
 
 void FrvsrTemporal::create(ss4k_ctx* c, Frvsr* m, Model* bsvd_stream_model, int lr_h, int lr_w, int out_h, int out_w, double rate, int max_push_,
-                           int max_streams_) {
+                           int max_streams_, bool allow_pad) {
   SS4K_REQUIRE(c && m && bsvd_stream_model, "frvsr temporal: NULL argument");
   SS4K_REQUIRE(max_streams_ >= 1 && max_streams_ <= temporal_round::MAX_STREAMS, "frvsr temporal: max_streams must be in 1..64");
   SS4K_REQUIRE(lr_h >= 8 && lr_w >= 8, "lr_shape must be at least 8 x 8");
-  SS4K_REQUIRE(lr_h % 4 == 0 && lr_w % 4 == 0, "frvsr temporal: lr_shape must be divisible by 4 (BSVD)");
+  SS4K_REQUIRE(allow_pad || (lr_h % 4 == 0 && lr_w % 4 == 0), "frvsr temporal: lr_shape must be divisible by 4 (BSVD)");
   SS4K_REQUIRE((out_h == 0 && out_w == 0) || (out_h > 0 && out_w > 0), "output_shape is (0, 0) or positive");
   SS4K_REQUIRE((double)lr_h * lr_w * 16.0 < 2147483648.0, "lr_shape: the output frame must hold fewer than 2^31 pixels");
   SS4K_REQUIRE(std::isfinite(rate) && rate >= 0.0, "frvsr temporal: a denoise rate is finite and not negative");
@@ -47,6 +47,7 @@ void FrvsrTemporal::create(ss4k_ctx* c, Frvsr* m, Model* bsvd_stream_model, int 
   ctx = c; denoise_rate = rate; max_push = max_push_;
   up.ctx = c; up.m = m; up.lr_h = lr_h; up.lr_w = lr_w; up.out_h = out_h; up.out_w = out_w;
   up.slots.resize((size_t)max_streams_);
+  pad_h = (lr_h + 3) & ~3; pad_w = (lr_w + 3) & ~3;   // (a divisible shape: itself, and every launch below is the unpadded one)
 #ifdef SS4K_DEV
   // guard mode (upscaler.h): a round reads nothing of these that it has not written.  The rings, the denoisers' state and lr / hr are state
   for (DevBuf* b : {&lr4, &den}) b->transient = true;
@@ -78,7 +79,7 @@ size_t FrvsrTemporal::state_bytes() const {
 size_t FrvsrTemporal::stream_state_bytes_for() const {
   const auto r256 = [](size_t b) { return (b + 255) & ~size_t(255); };
   const size_t lr_b = (size_t)3 * up.lr_h * up.lr_w * 4;
-  return slots[0]->on.state_bytes_for(up.lr_h, up.lr_w) + r256(lr_b * ring_frames()) + 2 * r256(lr_b) + 2 * r256(16 * lr_b);
+  return slots[0]->on.state_bytes_for(pad_h, pad_w) + r256(lr_b * ring_frames()) + 2 * r256(lr_b) + 2 * r256(16 * lr_b);
 }
 
 void FrvsrTemporal::release_idle() {
@@ -126,7 +127,8 @@ void FrvsrTemporal::set_denoise_rate(int si, float rate) {
 void FrvsrTemporal::check_sizes(int h, int w) const {
   const int lh = up.lr_h, lw = up.lr_w, H = 4 * lh, W = 4 * lw;
   int oh, ow; up.out_shape(&oh, &ow);
-  SS4K_REQUIRE((double)(bsvd_online::LAG / 2 + max_push) * lh * lw < 2147483648.0, "bsvd online push: a carried plane holds at most 2^31 pixels");
+  SS4K_REQUIRE((double)(bsvd_online::LAG / 2 + max_push) * pad_h * pad_w < 2147483648.0, "bsvd online push: a carried plane holds at most 2^31 pixels");
+  SS4K_REQUIRE((double)pad_h * pad_w * 4.0 < 2147483648.0, "frvsr temporal: a padded denoiser frame holds fewer than 2^31 values");
   SS4K_REQUIRE((double)h * lh < 2147483648.0 && (double)w * lw < 2147483648.0 && (double)H * oh < 2147483648.0 && (double)W * ow < 2147483648.0,
                "frvsr temporal: frame sizes whose area window bounds overflow");
   SS4K_REQUIRE(lh >= 2 && lw >= 2 && (double)lh * lw * 3.0 < 2147483648.0, "frvsr denoised in: a frame of at least 2 x 2 and fewer than 2^31 values");
@@ -150,7 +152,10 @@ void FrvsrTemporal::run_wave(const frvsr_temporal::Wave& wv, const float* const*
   FrvtTable tab{}; FrvsrFramesOut fout{};
   for (int i = 0; i < wv.n; ++i) { tab.den[i] = den_of[i]; tab.lr[i] = ring_of[i]; tab.dst[i] = r.lr_dst.p[i]; fout.p[i] = out_of[i]; }
   // clamp(sharpen(den)) * 0.8 + 0.2 * lr   (fsrcnn_upscaler.py:279-281; Upscaler::single_tail's constants)
-  up.m->timed(FRV_GLUE, st, [&] { op_frvt_denoised_in_items(tab, wv.n, lh, lw, k_sharp.as<float>(), 0.8f, (float)(1 - 0.8), st); });
+  if (padded())   // den is (3, pad_h, pad_w): the top-left (lh, lw) are the frame
+    up.m->timed(FRV_GLUE, st, [&] { op_frvt_denoised_in_crop_items(tab, wv.n, lh, lw, pad_h, pad_w, k_sharp.as<float>(), 0.8f, (float)(1 - 0.8), st); });
+  else
+    up.m->timed(FRV_GLUE, st, [&] { op_frvt_denoised_in_items(tab, wv.n, lh, lw, k_sharp.as<float>(), 0.8f, (float)(1 - 0.8), st); });
   up.m->step_items(Frvsr::Items{r.lr_curr, r.lr_prev, &r.hr_prev, &r.hr_curr, true}, wv.n, lh, lw, st);
   up.close_slots(ids, wv.n);
   up.m->timed(FRV_GLUE, st, [&] { op_frames_out_items(r.hr_curr, fout, wv.n, 4 * lh, 4 * lw, oh, ow, st); });
@@ -160,6 +165,7 @@ int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, i
                          int* n_out_per_item, int* item_slots, int* n_items, hipStream_t st) {
   const int lh = up.lr_h, lw = up.lr_w;
   const size_t plane = (size_t)lh * lw, frame = 3 * plane;
+  const size_t pplane = (size_t)pad_h * pad_w, pframe = 3 * pplane;   // the denoiser's planes and frames: lr4 and den
   // ---- every refusal for the whole round, before the first launch and before any state changes
   SS4K_REQUIRE(fr && slot_ids && n_out_per_item && item_slots && n_items, "frvsr temporal round: NULL argument");
   SS4K_REQUIRE(h > 0 && w > 0, "frvsr temporal round: empty frames");
@@ -182,8 +188,8 @@ int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, i
   // ---- allocations, still before the first launch: one that fails leaves every stream as it was (a slot that gained buffers keeps them).  A
   // slot's recurrent state is made here, with the stream's first frame, not 16 frames later: what a running slot holds does not depend on
   // how far its stream has come.  What a slot's denoiser allocates with its first push is BsvdOnline's own and happens inside step 3.
-  lr4.ensure(plane * 4 * k * 4);
-  den.ensure(frame * std::max(p.total, max_push) * 4);
+  lr4.ensure(pplane * 4 * k * 4);
+  den.ensure(pframe * std::max(p.total, max_push) * 4);
   for (int t = 0; t < p.n_items; ++t) {
     slots[p.items[t].slot]->ring.ensure(frame * ring_frames() * 4);
     FrvsrUpscaler::Slot& rs = up.slots[p.items[t].slot];
@@ -220,13 +226,14 @@ int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, i
       for (int j = 0; j < it.n; ++j) tab.flag[it.first + j] = item_cuts[t] + j;
     }
     // ---- 2. the packed (k, 4, lh, lw) denoiser input, noise planes included: one launch
-    op_tround_gather(tab, lr4.as<float>(), k, plane, 4, start_bits, 0.05f, st);
+    if (padded()) op_tround_gather_pad(tab, lr4.as<float>(), k, lh, lw, start_bits, 0.05f, st);
+    else op_tround_gather(tab, lr4.as<float>(), k, plane, 4, start_bits, 0.05f, st);
     // ---- 3. one push per item, one after the other: they share the model's activation slots
     for (int t = 0; t < p.n_items; ++t) {
       const temporal_round::Item& it = p.items[t];
       FrvtSlot& s = *slots[it.slot];
       s.first_frame = false;
-      const int got = s.on.push(lr4.as<float>() + plane * 4 * it.first, it.n, lh, lw, den.as<float>() + frame * it.den_off, (size_t)std::max(it.emitted, 1), st,
+      const int got = s.on.push(lr4.as<float>() + pplane * 4 * it.first, it.n, pad_h, pad_w, den.as<float>() + pframe * it.den_off, (size_t)std::max(it.emitted, 1), st,
                                 item_cuts[t]);
       s.pushed += it.n;
       SS4K_REQUIRE(got == it.emitted, "internal: the online denoiser emitted another number of frames than its plan");
@@ -239,7 +246,7 @@ int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, i
       bool any_ring = false;
       for (int i = 0; i < wv.n; ++i) {
         FrvtSlot& s = *slots[wv.slot[i]];
-        den_of[i] = den.as<float>() + frame * wv.out[i];
+        den_of[i] = den.as<float>() + pframe * wv.out[i];
         ring_of[i] = s.ring.as<float>() + frame * p.ring_out[wv.out[i]];
         out_of[i] = out + out_frame * wv.out[i];
         SS4K_REQUIRE((long long)wv.frame[i] == s.emitted, "internal: a wave carries another frame than the next one of its stream");
@@ -267,7 +274,7 @@ int FrvsrTemporal::flush(int si, uint8_t* out, size_t out_capacity_bytes, hipStr
   SS4K_REQUIRE(out, "frvsr temporal flush: NULL argument");
   const int lh = up.lr_h, lw = up.lr_w;
   int oh, ow; up.out_shape(&oh, &ow);
-  const size_t out_frame = (size_t)oh * ow * 3, frame = (size_t)3 * lh * lw;
+  const size_t out_frame = (size_t)oh * ow * 3, frame = (size_t)3 * lh * lw, pframe = (size_t)3 * pad_h * pad_w;
   SS4K_REQUIRE(out_capacity_bytes >= (size_t)left * out_frame, "frvsr temporal flush: output buffer too small for the pending frames");
   const frvsr_temporal::Waves waves = frvsr_temporal::make_flush(si, left, (int)s.emitted);
   SS4K_REQUIRE(waves.n_waves == left, "internal: a flush of more frames than a slot can hold");
@@ -277,12 +284,12 @@ int FrvsrTemporal::flush(int si, uint8_t* out, size_t out_capacity_bytes, hipStr
   const int32_t id = si;
   up.check_round(&id, 1, lh, lw, false);
   check_sizes(lh, lw);
-  den.ensure(frame * left * 4);
+  den.ensure(pframe * left * 4);
   try {
     const int got = s.on.flush(den.as<float>(), (size_t)left, st);
     SS4K_REQUIRE(got == left, "internal: the online denoiser drained another number of frames than were pending");
     for (int r = 0; r < left; ++r) {   // the generator takes a stream's frames one at a time
-      const float* den_of = den.as<float>() + frame * r;
+      const float* den_of = den.as<float>() + pframe * r;
       const float* ring_of = s.ring.as<float>() + frame * ((s.emitted + r) % ring_frames());
       uint8_t* out_of = out + out_frame * r;
       const uint32_t* flag_of = flag_ring ? flag_ring + frvsr_temporal::ring_word(waves.w[r].frame[0]) : nullptr;

@@ -5,6 +5,10 @@
 //                 0.1 * rate after (fsrcnn_upscaler.py:262,269-271); it exists once frame t + 16 has entered, or at a flush
 //   lr_curr_t   = 0.8 * clamp01(sharpen3x3_reflect(den_t)) + 0.2 * lr_before_t           (fsrcnn_upscaler.py:279-281)
 //   hr_t        = FRNet(lr_curr_t, lr_curr_{t-1}, hr_{t-1}), zeros for a stream's first frame; clamp, area to output_shape, * 255 truncated
+// An lr_shape (lh, lw) that 4 does not divide (create with allow_pad; include/ss4k.h: ss4k_frvsr_temporal_create_padded): the denoiser alone runs
+// at (ph, pw), (lh, lw) rounded up to multiples of 4.  Its input is lr_before padded at the bottom and on the right by 'reflect' (row y >= lh is
+// row 2 (lh - 1) - y, columns likewise; the noise plane its constant over (ph, pw)), its output is cropped to the top-left (lh, lw) before the
+// sharpening, whose own reflection is at the crop's borders.  The ring, the generator, its state, the detector and the output stay at (lh, lw).
 // Nothing of the per-frame tail follows (no HR sharpening, no mean / std match): hr_prev stays the generator's own output.
 // The round is temporal_round::make_round's; its ready frames pass the generator in waves (frvsr_temporal_plan.h).
 #pragma once
@@ -30,6 +34,11 @@ static_assert(sizeof(FrvtTable) == 1536, "the wave's table travels in the kernel
 // bit, in one launch.  Refuses - before the launch - n_items outside 1..64, h < 2 or w < 2 (torch's reflect), 3 h w >= 2^31, NULL or misaligned
 // pointers and a destination that overlaps its item's sources.
 void op_frvt_denoised_in_items(const FrvtTable& tab, int n_items, int h, int w, const float* taps_dev, float blend_a, float blend_b, hipStream_t st);
+// The cropped form: den[i] is 3 planes of (ph, pw) >= (h, w), of which the top-left (h, w) are the frame; lr[i] and dst[i] stay (3, h, w).  The
+// reflection is at the crop's borders, the rest of den is never read; bit for bit op_frvt_denoised_in_items on a contiguous copy of the crop.
+// Refuses what that one refuses, ph < h or pw < w, 3 ph pw >= 2^31; the overlap check takes den at its own, larger size.
+void op_frvt_denoised_in_crop_items(const FrvtTable& tab, int n_items, int h, int w, int ph, int pw, const float* taps_dev, float blend_a,
+                                    float blend_b, hipStream_t st);
 
 // ---- the late reset of a scene cut (frvsr_temporal.hip) -------------------------------------------------------------------------------------------
 // Item i: the device word that says whether the frame that leaves the denoiser in this wave starts a scene - its stream's flag ring at the
@@ -59,13 +68,16 @@ struct FrvsrTemporal {
   ss4k_ctx* ctx = nullptr;
   FrvsrUpscaler up;     // the generator's rounds, every stream's lr / hr state where it lives; its own frame entry points are not used
   std::vector<std::unique_ptr<FrvtSlot>> slots;   // max_streams of them, slot s beside up.slots[s]
-  DevBuf lr4, den;      // job buffers, shared: the packed denoiser input of a round, the denoised frames of a round or a flush
+  DevBuf lr4, den;      // job buffers, shared: the packed denoiser input of a round, the denoised frames of a round or a flush - at (pad_h, pad_w)
+  int pad_h = 0, pad_w = 0;   // the denoiser's shape: lr_shape rounded up to multiples of 4 - lr_shape itself unless created with allow_pad
   DevBuf k_sharp;       // the nine taps of sharpen_ker(strength = 0.00002), uploaded once
   double denoise_rate = 1.0;
   double cut_threshold = 0;   // what set_scene_cut last said; a slot's detector is made when the slot first needs it
   int max_push = 0;
 
-  void create(ss4k_ctx* c, Frvsr* m, Model* bsvd_stream_model, int lr_h, int lr_w, int out_h, int out_w, double denoise_rate, int max_push, int max_streams);
+  void create(ss4k_ctx* c, Frvsr* m, Model* bsvd_stream_model, int lr_h, int lr_w, int out_h, int out_w, double denoise_rate, int max_push, int max_streams,
+              bool allow_pad = false);
+  bool padded() const { return pad_h != up.lr_h || pad_w != up.lr_w; }
   int max_streams() const { return (int)slots.size(); }
   int ring_frames() const { return bsvd_online::LAG + max_push; }
   FrvtSlot& slot(int s);

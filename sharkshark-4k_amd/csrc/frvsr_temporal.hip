@@ -71,6 +71,66 @@ void op_frvt_denoised_in_items(const FrvtTable& tab, int n_items, int h, int w, 
   SS4K_LAUNCH_OK();
 }
 
+// ---- frvt::denoised_in_crop_items: the same, with den a frame of LARGER planes of which only the top-left (h, w) count -------------------------
+// The padded chain's denoiser runs at (ph, pw), (h, w) rounded up to multiples of 4; what follows it acts on the crop.  The loops, the
+// expressions and the tap table are k_frvt_denoised_in's, term for term - only den's strides differ: a row is pw values, a plane ph * pw; lr and
+// dst keep w and h * w.  The reflection is at the crop's borders (h, w), so the padding is never read.  The value is bit for bit what
+// k_frvt_denoised_in gives on a contiguous copy of the crop (tests/test_gpu_frvsr_temporal_pad_kernel.py): the strides change addresses, not
+// the order or the form of the floating-point operations.
+__global__ __launch_bounds__(256) void k_frvt_denoised_in_crop(FrvtTable tab, const float* __restrict__ taps, int n_items, int h, int w, int ph,
+                                                               int pw, float blend_a, float blend_b) {
+  constexpr int K = 3, r = 1;
+  const int item = blockIdx.z / 3, pl = blockIdx.z % 3;
+  if (item >= n_items) return;
+  const float* __restrict__ src = tab.den[item] + (size_t)pl * ph * pw;
+  const float* __restrict__ blend_src = tab.lr[item];
+  float* __restrict__ out = tab.dst[item];
+  for (int y = blockIdx.y; y < h; y += gridDim.y) {
+    const size_t row = ((size_t)pl * h + y) * w;
+    for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < w; x += gridDim.x * blockDim.x) {
+      int xi[K];
+#pragma unroll
+      for (int kx = 0; kx < K; ++kx) xi[kx] = frvt_reflect(x + kx - r, w);
+      float acc = 0.f;
+#pragma unroll 1
+      for (int ky = 0; ky < K; ++ky) {
+        const float* sr = src + (size_t)frvt_reflect(y + ky - r, h) * pw;
+#pragma unroll
+        for (int kx = 0; kx < K; ++kx) acc += taps[ky * K + kx] * sr[xi[kx]];
+      }
+      acc = fminf(fmaxf(acc, 0.f), 1.f);
+      acc = acc * blend_a + blend_b * blend_src[row + x];
+      out[row + x] = acc;
+    }
+  }
+}
+
+void op_frvt_denoised_in_crop_items(const FrvtTable& tab, int n_items, int h, int w, int ph, int pw, const float* taps_dev, float blend_a,
+                                    float blend_b, hipStream_t st) {
+  // every refusal before the launch
+  SS4K_REQUIRE(n_items >= 1 && n_items <= FRVT_MAX_ITEMS, "frvsr denoised in crop: 1..64 items");
+  SS4K_REQUIRE(h >= 2 && w >= 2, "frvsr denoised in crop: reflect padding of 1 needs a plane of at least 2 x 2, as torch requires");
+  SS4K_REQUIRE(ph >= h && pw >= w, "frvsr denoised in crop: the denoised planes hold the crop");
+  SS4K_REQUIRE((double)ph * (double)pw * 3.0 < 2147483648.0, "frvsr denoised in crop: a denoised frame holds fewer than 2^31 values");
+  SS4K_REQUIRE(taps_dev, "frvsr denoised in crop: NULL taps");
+  const size_t frame_bytes = (size_t)3 * h * w * 4, den_bytes = (size_t)3 * ph * pw * 4;
+  for (int i = 0; i < n_items; ++i) {
+    SS4K_REQUIRE(tab.den[i] && tab.lr[i] && tab.dst[i], "frvsr denoised in crop: NULL item pointer");
+    SS4K_REQUIRE((((uintptr_t)tab.den[i] | (uintptr_t)tab.lr[i] | (uintptr_t)tab.dst[i]) & 3) == 0, "frvsr denoised in crop: misaligned item pointer");
+    // a pixel's neighbours are read while other pixels are written: the destination may not lie inside the item's sources, of which den is
+    // the larger frame
+    const char* d = reinterpret_cast<const char*>(tab.dst[i]);
+    const char* dn = reinterpret_cast<const char*>(tab.den[i]);
+    const char* l = reinterpret_cast<const char*>(tab.lr[i]);
+    SS4K_REQUIRE(dn + den_bytes <= d || d + frame_bytes <= dn, "frvsr denoised in crop: a destination overlaps its item's sources");
+    SS4K_REQUIRE(l + frame_bytes <= d || d + frame_bytes <= l, "frvsr denoised in crop: a destination overlaps its item's sources");
+  }
+  SS4K_GLUE_ROUTE("frvt::denoised_in_crop_items");
+  const dim3 grid((unsigned)std::min((w + 255) / 256, 64), (unsigned)std::min(h, 65535), (unsigned)(3 * n_items));
+  hipLaunchKernelGGL(k_frvt_denoised_in_crop, grid, dim3(256), 0, st, tab, taps_dev, n_items, h, w, ph, pw, blend_a, blend_b);
+  SS4K_LAUNCH_OK();
+}
+
 // ---- frvt::clear_flagged_items: the late reset of a scene cut -----------------------------------------------------------------------------------
 // A frame that the detector flagged when it went in leaves the denoiser 16 frames later; in that wave its stream's lr_prev / hr_prev must read
 // as zero, as for a stream's first frame.  blockIdx.y is the item: its flag pointer and the flag word are uniform over the workgroup (loads from

@@ -49,6 +49,13 @@ static_assert(sizeof(TroundTable) == 1280, "the round's table travels in the ker
 // *flag[j] != 0, and level[j] otherwise - the bits of bsvdo::noise_planes / the one-stream path's fill.  One launch, one thread per 16-byte slot.
 void op_tround_gather(const TroundTable& tab, float* dst, int k, size_t plane_px, int planes, unsigned long long start_bits, float level_start,
                       hipStream_t st);
+// The padded form of the four-plane gather, for the frame-recurrent chain at an lr_shape that 4 does not divide (frvsr_temporal.h): src[j] is
+// (3, lh, lw) fp32 at any 4-byte address, dst (k, 4, ph, pw) with (ph, pw) = (lh, lw) rounded up to multiples of 4.  Planes 0..2 are padded at
+// the bottom and on the right by 'reflect' (row y >= lh is row 2 (lh - 1) - y, columns likewise), plane 3 is the frame's level by the rule above,
+// over the whole (ph, pw).  One launch.  Refuses - before the launch - what op_tround_gather refuses (a source need only be 4-byte aligned),
+// lh < 4 or lw < 4, and 4 ph pw >= 2^31.
+void op_tround_gather_pad(const TroundTable& tab, float* dst, int k, int lh, int lw, unsigned long long start_bits, float level_start,
+                          hipStream_t st);
 
 // what one stream owns; allocated by its first push
 struct TemporalSlot {

@@ -123,12 +123,16 @@ class NodeResult:
 class EgvsrNode(WorkerPool):
     #: the key under which a worker's answers carry its scene-cut counter
     CUTS_KEY = "egvsr.scene_cuts"
+    #: whether this node's workers may be HipEgvsrUpscalerService(denoise_temporal=True): only a node that knows their answers
+    #: (temporal_node.TemporalEgvsrNode) says so
+    DENOISED_WORKERS = False
 
     def __init__(self, devices: Union[int, Sequence[int], None] = None, max_streams: int = 1, job_frames: int = 4, host_frames=True,
                  host_slots: int = 6, output_shape="unset", service_cls=HipEgvsrUpscalerService, push_timeout: float = 10.0, **service_kwargs):
-        if service_kwargs.get("denoise_temporal") and isinstance(service_cls, type) and issubclass(service_cls, HipEgvsrUpscalerService):
-            raise ValueError("EgvsrNode(denoise_temporal=True) is not supported: the node feeds its workers host-ring jobs, which a denoised "
-                             "frame-recurrent worker refuses (run HipEgvsrUpscalerService(denoise_temporal=True) as one worker)")
+        if (service_kwargs.get("denoise_temporal") and not self.DENOISED_WORKERS and isinstance(service_cls, type)
+                and issubclass(service_cls, HipEgvsrUpscalerService)):
+            raise ValueError("EgvsrNode(denoise_temporal=True) is not supported: a denoised worker answers a job with OTHER frames than the "
+                             "job's own, 16 frames late, and this node hands every job's own frames back (use temporal_node.TemporalEgvsrNode)")
         super().__init__(devices)
         if not host_frames:
             raise ValueError("EgvsrNode takes host frames: host_frames is True (frames of the service's lr_shape) or (H, W)")

@@ -33,6 +33,9 @@ stays where it opened.  This class is ``egvsr_node.EgvsrNode`` - its ``StreamRou
   inside}`` - and ``frames_inside_lost``.
 
 Every worker loads its own weights (no process group: ``node.UpscalerNode`` keeps refusing ``denoise_temporal`` because IT shards by step).
+
+``TemporalEgvsrNode`` (below) is this class with ``HipEgvsrUpscalerService(denoise_temporal=True)`` in the workers: the denoised
+frame-recurrent streams on G GPUs.
 """
 from __future__ import annotations
 
@@ -43,6 +46,7 @@ import numpy as np
 
 from .egvsr_node import EgvsrNode, NodeResult
 from .hostring import HostFrames
+from .upscale.egvsr_upscaler import HipEgvsrUpscalerService
 from .upscale.hip_upscaler import HipUpscalerService, TemporalQueueEntry, validate_stream_rates
 
 
@@ -164,3 +168,39 @@ class TemporalNode(EgvsrNode):
         r["pending"] = pending
         r["frames_inside_lost"] = self.frames_inside_lost
         return r
+
+
+class TemporalEgvsrNode(TemporalNode):
+    """The denoised frame-recurrent service (``HipEgvsrUpscalerService(denoise_temporal=True)``: the online BSVD denoiser in front of either
+    generator, per stream) on G workers, one per GPU.  It is ``TemporalNode`` with that service in the workers: the router, the slot pools,
+    submit / collect / emit / lend, ``ends_per_part``, ``TemporalResult`` with ``ready``, ``stream_rates``, ``report()['pending']`` and
+    ``['frames_inside_lost']``, ``end_all`` and the audio rule are that class's, word for word::
+
+        node = TemporalEgvsrNode(devices=8, max_streams=4, job_frames=4, ends_per_part=1, host_frames=(720, 1280), host_slots=4,
+                                 lr_shape=(540, 960), output_shape=(1080, 1920), checkpoint_dir="/models")
+
+    What differs:
+
+    * SCENE CUTS - ``report()['scene_cuts']`` reads ``egvsr.scene_cuts`` (``denoise_scene_cut=`` sets the threshold).
+    * OUT-RING SLOTS - a slot holds ``job_frames + 16 * ends_per_part`` frames of the service's ``out_hw()``, and without ``output_shape`` that
+      is the generator's x4 output: at ``lr_shape=(540, 960)`` a frame is 2160 x 3840 x 3 = 24.9 MB, so a slot is about 500 MB at the defaults
+      (4 + 16 frames) and a worker pins ``host_slots`` of them.  Set ``output_shape`` (the frames are area-resized on the device) or lower
+      ``host_slots`` / ``job_frames``.
+    * KEYWORDS - ``denoise_scene_cut``, ``denoise_rate``, ``denoise_weights`` and ``denoise_pad`` (any ``lr_shape`` of at least 8 x 8) pass
+      through to the workers, with every other keyword of the service; ``scene_cut`` stays refused with the denoiser (the service's rule).
+    """
+    CUTS_KEY = "egvsr.scene_cuts"
+    LAG = HipEgvsrUpscalerService.TEMPORAL_LAG
+    DENOISED_WORKERS = True
+
+    def __init__(self, devices: Union[int, Sequence[int], None] = None, max_streams: int = 1, job_frames: int = 4, ends_per_part: int = 1,
+                 host_frames=True, host_slots: int = 6, output_shape="unset", service_cls=HipEgvsrUpscalerService, push_timeout: float = 10.0,
+                 temporal_max_push=None, **service_kwargs):
+        super().__init__(devices, max_streams=max_streams, job_frames=job_frames, ends_per_part=ends_per_part, host_frames=host_frames,
+                         host_slots=host_slots, output_shape=output_shape, service_cls=service_cls, push_timeout=push_timeout,
+                         temporal_max_push=temporal_max_push, **service_kwargs)
+
+    def _make_service(self, k: int):
+        svc = self.service_cls(device=self.devices[k], max_streams=self.max_streams, **self.service_kwargs)
+        svc.leave_exit_code = 0   # (as TemporalNode: every worker that left on request returns 0)
+        return self._prepare(svc, self._frame_hw(svc), svc.out_hw, out_frames=self.job_frames + self.LAG * self.ends_per_part)

@@ -36,9 +36,12 @@ job of K frames that ends E streams returns at most ``temporal_result_bound(K, E
 unnamed stream.  ``denoise_rate`` is the service's rate, ``stream_rates`` a stream's own; ``denoise_weights`` is the BSVD checkpoint, resolved
 like the per-frame service's ``'denoise'`` entry (None: ``bsvd-32.pth`` in the checkpoint directory or ``FileNotFoundError``; ``'synthetic'``,
 or ``weights='synthetic'`` with nothing else said, is the opt-in); ``temporal_max_push`` (4) frames of one stream enter per round.  ``lr_shape``
-must be divisible by 4: of the reference's three, (630, 1120) is refused.  Refused with it, before any GPU work: ``scene_cut`` (that keyword
-names the detector that resets at input time; the denoised chain's is ``denoise_scene_cut``), ``HostFrames`` jobs, and
-``EgvsrNode(denoise_temporal=True)``.
+must be divisible by 4 - of the reference's three, (630, 1120) is refused - unless ``denoise_pad=True``: then any shape of at least 8 x 8 is
+taken, the denoiser alone runs at the shape rounded up to multiples of 4 on reflect-padded planes and its output is cropped (include/ss4k.h:
+``ss4k_frvsr_temporal_create_padded``).  A worker with ``host_rings`` takes ``HostFrames`` jobs (``_temporal_host_job``: the out slot must
+hold the job's bound, a job of 0 frames is a flush); on several GPUs ``temporal_node.TemporalEgvsrNode`` runs this service.  Refused with it,
+before any GPU work: ``scene_cut`` (that keyword names the detector that resets at input time; the denoised chain's is
+``denoise_scene_cut``), a ``HostFrames`` job on a worker started without host rings, and ``EgvsrNode(denoise_temporal=True)`` itself.
 
 ``denoise_scene_cut=T`` (None / 0: off, the default; needs ``denoise_temporal=True``): scene cuts for the denoised streams
 (``ss4k_frvsr_temporal_set_scene_cut``, include/ss4k.h).  Every stream's input frames are compared as they arrive, on the device; at a hard cut
@@ -133,12 +136,23 @@ def check_scene_cut(threshold) -> Optional[float]:
     return t
 
 
-def check_temporal_lr_shape(lr_shape) -> None:
+def check_temporal_lr_shape(lr_shape, pad: bool = False) -> None:
     """``denoise_temporal=True`` needs an ``lr_shape`` divisible by 4 (BSVD's two 2x poolings; ``ss4k_frvsr_temporal_create``): of the reference's
-    three shapes (630, 1120) is refused.  Raises ``ValueError``."""
+    three shapes (630, 1120) is refused.  With ``pad`` (``denoise_pad=True``; ``ss4k_frvsr_temporal_create_padded``) any shape of at least
+    8 x 8 passes.  Raises ``ValueError``."""
     lh, lw = int(lr_shape[0]), int(lr_shape[1])
+    if pad:
+        if lh < 8 or lw < 8:
+            raise ValueError(f"denoise_temporal=True needs an lr_shape of at least 8 x 8, not {(lh, lw)}")
+        return
     if lh % 4 or lw % 4:
-        raise ValueError(f"denoise_temporal=True needs an lr_shape divisible by 4 (BSVD), not {(lh, lw)}")
+        raise ValueError(f"denoise_temporal=True needs an lr_shape divisible by 4 (BSVD), not {(lh, lw)} (denoise_pad=True pads the "
+                         "denoiser's input to the next multiple of 4 and crops its output)")
+
+
+def padded_lr_shape(lr_shape) -> tuple:
+    """``lr_shape`` rounded up to multiples of 4: the shape the denoiser of a ``denoise_pad=True`` service runs at."""
+    return tuple((int(v) + 3) // 4 * 4 for v in lr_shape)
 
 
 def temporal_rounds(streams: Sequence[Hashable], max_push: int) -> List[List[int]]:
@@ -170,7 +184,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
 
     def __init__(self, lr_level=1, device=0, on_queue=None, *, weights=None, checkpoint_dir: Optional[str] = None, dtype="f16", nb=None,
                  lr_shape=None, seed=0, max_streams=1, generator="egvsr", degradation="BD", scene_cut=None, denoise_temporal=False,
-                 denoise_rate=1.0, denoise_weights=None, temporal_max_push=None, denoise_scene_cut=None):
+                 denoise_rate=1.0, denoise_weights=None, temporal_max_push=None, denoise_scene_cut=None, denoise_pad=False):
         self.lr_shape = tuple(lr_shape) if lr_shape is not None else LR_SHAPES[lr_level]
         self.scale = 4
         self.hr_shape = tuple([i * self.scale for i in self.lr_shape])
@@ -192,6 +206,11 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self.denoise_weights = denoise_weights
         self.temporal_max_push = int(temporal_max_push) if temporal_max_push else 4
         self.last_ready = []
+        # denoise_pad: any lr_shape of at least 8 x 8 - the denoiser runs at the shape rounded up to multiples of 4, on reflect-padded planes, and
+        # its output is cropped (include/ss4k.h: ss4k_frvsr_temporal_create_padded)
+        self.denoise_pad = bool(denoise_pad)
+        if self.denoise_pad and not self.denoise_temporal:
+            raise ValueError("denoise_pad belongs to denoise_temporal=True: without the denoiser in front there is nothing to pad")
         # denoise_scene_cut: the denoised streams' scene-cut threshold (_capi.TemporalFrvsrUpscaler.set_scene_cut); None / 0: off
         try:
             self.denoise_scene_cut = check_scene_cut(denoise_scene_cut)
@@ -203,7 +222,7 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
             if self.scene_cut:
                 raise ValueError("denoise_temporal=True together with scene_cut is not supported: scene_cut resets the recurrent state when a "
                                  "frame goes in, and here the frame comes out of the denoiser 16 frames later (use denoise_scene_cut)")
-            check_temporal_lr_shape(self.lr_shape)
+            check_temporal_lr_shape(self.lr_shape, self.denoise_pad)
             if isinstance(denoise_rate, bool) or not isinstance(denoise_rate, (int, float)) or not (0.0 <= float(denoise_rate) < float("inf")):
                 raise ValueError(f"denoise_rate={denoise_rate!r}: a denoise rate is a finite number >= 0")
             if not 1 <= self.temporal_max_push <= 64:
@@ -277,13 +296,16 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
 
     def _make_upscaler(self, _capi, key):
         if self.denoise_temporal:
-            check_temporal_lr_shape(key[0])   # (the pipelines overwrite lr_shape after construction)
+            check_temporal_lr_shape(key[0], self.denoise_pad)   # (the pipelines overwrite lr_shape after construction)
             self._t_index = {}
             more = {"scene_cut": self.denoise_scene_cut} if self.denoise_scene_cut else {}   # (off: the object is built as before the keyword)
+            if self.denoise_pad:
+                more["pad"] = True
             up = _capi.TemporalFrvsrUpscaler(self.ctx, self.model, self.denoise_model, key[0], key[1], float(self.denoise_rate),
                                              self.temporal_max_push, self.max_streams, **more)
             log(f"denoised streams: {self.max_streams} stream slot(s), {up.stream_state_bytes_for() / 2**20:.1f} MiB of state per running "
-                f"stream (max_push {self.temporal_max_push})")
+                f"stream (max_push {self.temporal_max_push})"
+                + (f", denoiser at the padded shape {padded_lr_shape(key[0])} for lr_shape {tuple(key[0])}" if self.denoise_pad else ""))
             return up
         if not self.scene_cut:
             return _capi.FrvsrUpscaler(self.ctx, self.model, key[0], key[1], self.max_streams)
@@ -317,10 +339,11 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         """The most frames a denoised job of ``n_frames`` frames that ends ``ended`` streams can return: K + 16 E."""
         return int(n_frames) + self.TEMPORAL_LAG * int(ended)
 
-    def _temporal_job(self, frames, streams, end_streams, stream_rates=None):
+    def _temporal_job(self, frames, streams, end_streams, stream_rates=None, into=None):
         """A job of the denoised service: its rounds, then the flushes of ``end_streams``; returns what became ready, possibly nothing, and
         sets ``last_ready``.  Every stream id gets its slot BEFORE the first frame runs: a job that does not fit raises, has run nothing and
-        has taken no slot (``HipUpscalerService._temporal_job``'s rules)."""
+        has taken no slot (``HipUpscalerService._temporal_job``'s rules).  ``into``: a frame count - every round and flush then writes behind
+        the last one into ONE device buffer of that many frames and the result is a view of it (a host-ring job: nothing is concatenated)."""
         n = 0 if frames is None else int(frames.shape[0])
         if len(streams) != n:
             raise ValueError(f"one stream id per frame: {len(streams)} ids for {n} frames")
@@ -329,6 +352,9 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
             from .hip_upscaler import validate_stream_rates   # (that module imports this one)
             rates = validate_stream_rates(stream_rates, streams)
         up = self._upscaler()
+        result, filled = None, 0
+        if into is not None:
+            result = torch.empty((int(into),) + tuple(up.out_shape()) + (3,), dtype=torch.uint8, device=self.torch_device)
         slots, taken = [], []
         try:
             for sid in streams:
@@ -356,7 +382,11 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
             if n:
                 frames = frames.contiguous()
                 for idx in temporal_rounds(streams, self.temporal_max_push):
-                    out, items = up.round([frames[i] for i in idx], [slots[i] for i in idx])
+                    if result is None:
+                        out, items = up.round([frames[i] for i in idx], [slots[i] for i in idx])
+                    else:
+                        out, items = up.round([frames[i] for i in idx], [slots[i] for i in idx], out=result[filled:])
+                        filled += int(out.shape[0])
                     sid_of, o = {slots[i]: streams[i] for i in idx}, 0
                     for slot, k in items:
                         came_back(sid_of[slot], out[o:o + k])
@@ -365,7 +395,12 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
                 slot = self._slots.slot_of.get(sid)
                 if slot is None:
                     continue   # (an id that holds no slot: nothing inside, nothing to free)
-                came_back(sid, up.flush(slot))
+                if result is None:
+                    came_back(sid, up.flush(slot))
+                else:
+                    out = up.flush(slot, out=result[filled:])
+                    filled += int(out.shape[0])
+                    came_back(sid, out)
                 self._slots.end(sid)
                 self._t_index.pop(sid, None)
         except Exception:
@@ -383,6 +418,8 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
             self.last_ready = []
             raise
         self.last_ready = ready
+        if result is not None:
+            return result[:filled]   # (the parts are consecutive views of it)
         if parts:
             return parts[0] if len(parts) == 1 else torch.cat(parts)
         return torch.empty((0,) + tuple(up.out_shape()) + (3,), dtype=torch.uint8, device=self.torch_device)
@@ -464,17 +501,59 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
                 out.index_copy_(0, ix, up.upscale_streams(frames.index_select(0, ix), [slots[i] for i in idx]))
         return out
 
+    def _temporal_host_job(self, hf: HostFrames, streams, end_streams, rates):
+        """A ``HostFrames`` job of the denoised service (``HipUpscalerService._temporal_host_job``'s rules).  Its result is what became ready,
+        so the out slot must hold the job's bound, ``K + 16 E`` frames of ``out_hw()``: a job whose bound does not fit is refused here, before a
+        frame runs, a slot is taken or the device is touched.  A job of 0 frames is a flush: its input slot is not read, there is no H2D and no
+        staging tensor.  The rounds and the flushes write into ONE device buffer of the bound's size, which goes to the out slot."""
+        if self.host_rings is None:
+            raise RuntimeError("a HostFrames job reached a worker with denoise_temporal=True that was started without host rings")
+        n = int(hf.shape[0])
+        ids = [None] * n if streams is None else list(streams)
+        if len(ids) != n:
+            raise ValueError(f"one stream id per frame: {len(ids)} ids for {n} frames")
+        if rates:
+            from .hip_upscaler import validate_stream_rates   # (that module imports this one)
+            rates = validate_stream_rates(rates, ids)
+        ended = len({sid for sid in end_streams if sid in self._slots.slot_of or sid in ids})   # the ids that have something to flush
+        bound = self.temporal_result_bound(n, ended)
+        oh, ow = self.out_hw()
+        if not self.host_rings[1].fits((bound, oh, ow, 3)):
+            raise ValueError(f"a denoised job of {n} frames that ends {ended} stream(s) can return {bound} frames of {oh} x {ow}: more "
+                             f"than a {self.host_rings[1].slot_bytes}-byte slot of the output ring holds (end fewer streams per job)")
+
+        def job(stage):
+            self._lag_now = 0
+            return self._temporal_job(stage if n else None, ids, end_streams, rates or None, into=bound)
+
+        if n:
+            shape, landed = self._io.run(hf, job)
+        else:   # a flush: no H2D, no staging tensor - only the way out
+            with torch.cuda.device(self.torch_device):
+                out = job(None)
+                shape = tuple(out.shape)
+                done = torch.cuda.current_stream(self.torch_device).record_event()
+                landed = self._io.copy_out(out, self.host_rings[1].view(hf.out_slot, shape), done)
+        self._host_jobs += 1
+        answered = HostFrames(slot=hf.slot, out_slot=hf.out_slot, shape=shape, result=True)
+        if landed is not None:
+            self._held.hold(answered, landed, HOST)
+            self._lag_now = max(self._lag_now, 1)   # one more job is enqueued before this result is waited for: the copies hide under it
+        return answered
+
     def _temporal_job_recieved(self, job, streams, end_streams):
         """A job of a denoised worker: device-tensor frames (or ``frames=None`` with ``end_streams``: only flushes).  The answer carries the
         frames that became ready and, as ``HipUpscalerService._tag_temporal`` leaves them, ``ready`` (= ``last_ready``), ``first_frame_index``
         and ``lag_frames``."""
         hf = getattr(job, "frames", None)
-        if isinstance(hf, HostFrames):
-            raise RuntimeError("a HostFrames job reached a worker with denoise_temporal=True: host-ring jobs of denoised frame-recurrent "
-                               "streams are not supported (send device tensors)")
         rates = getattr(job, "stream_rates", None) or None
+        if isinstance(hf, HostFrames) and self.host_rings is None:   # (before the upscaler object is built and before a slot is taken)
+            raise RuntimeError("a HostFrames job reached a worker with denoise_temporal=True that was started without host rings (set "
+                               "host_rings before start(), or send device tensors)")
 
         def run():
+            if isinstance(hf, HostFrames):
+                return self._temporal_host_job(hf, streams, end_streams, rates)
             if hf is None:
                 return self._temporal_job(None, [], end_streams, None)
             return self.upscale(hf, streams=streams, end_streams=end_streams, stream_rates=rates)
