@@ -482,6 +482,19 @@ int ss4k_upscaler_temporal_release_idle(ss4k_upscaler_temporal* up);
  * stream in it starts with the default.  Slot 0 is also the stream of the one-stream calls.  SS4K_EINVAL, changing nothing: a slot outside
  * 0..max_streams-1, a rate that is not finite or is negative.  A stream at rate r gives the bytes of an object created with denoise_rate = r. */
 int ss4k_upscaler_temporal_set_denoise_rate_stream(ss4k_upscaler_temporal* up, int slot, float rate);
+/* THE NOISE MAP.  BSVD's fourth input plane says, pixel by pixel, how much noise to assume.  SS4K_NOISE_MAP_CONSTANT (the default) is the plane
+ * above: 0.05 for a stream's or a scene's first frame, 0.1 * rate after.  SS4K_NOISE_MAP_MOTION is the rule the reference computes and then
+ * overwrites (fsrcnn_upscaler.py:250-254, :262): first frames keep the constant 0.05; every other frame t of a stream gets
+ *   m_t = min(max(10 B, 0), 0.1f) * (float)(0.35 * rate),   B = gauss3x3(sigma 0.5, 'reflect')(mean over the planes of |lr_t - lr_{t-1}|)
+ * in fp32, with lr_t the frame's LR planes as they enter (step 1) and rate the slot's denoise rate.  ONE DEPARTURE from the reference: its
+ * lr_{t-1} is the previous frame after denoising and blending, which here exists only 16 frames later; ours is the previous frame as it went
+ * in - it is still in the slot's LR ring, so the mode adds no state, no launch and no host round trip.  The mode holds for every slot and both
+ * for rounds and the one-stream calls, which stay bit-identical on slot 0.  _set_noise_map: SS4K_EINVAL, changing nothing, for another mode
+ * and while ANY slot has a running stream (pushed and neither flushed nor reset). */
+#define SS4K_NOISE_MAP_CONSTANT 0
+#define SS4K_NOISE_MAP_MOTION 1
+int ss4k_upscaler_temporal_set_noise_map(ss4k_upscaler_temporal* up, int mode);
+int ss4k_upscaler_temporal_noise_map(const ss4k_upscaler_temporal* up, int* mode);
 
 /* ---- the frame-recurrent service chain (ss4k_frvsr_upscaler) with the ONLINE denoiser in front, per stream.  A recurrent generator warps hr_prev
  * forward frame after frame, so the noise of a block-compressed stream accumulates where a per-frame network forgets it; the reference's main
@@ -555,6 +568,10 @@ int ss4k_frvsr_temporal_set_scene_cut(ss4k_frvsr_temporal* up, double threshold)
 int ss4k_frvsr_temporal_scene_cut(const ss4k_frvsr_temporal* up, double* threshold);
 int ss4k_frvsr_temporal_scene_cut_stats_stream(ss4k_frvsr_temporal* up, int slot, ss4k_scene_cut_stats* out, void* hip_stream);   /* synchronises */
 int ss4k_frvsr_temporal_scene_cut_total(const ss4k_frvsr_temporal* up, uint64_t* cuts);   /* never synchronises */
+/* the noise map of step 2, as ss4k_upscaler_temporal_set_noise_map: SS4K_NOISE_MAP_CONSTANT (default) or SS4K_NOISE_MAP_MOTION.  In the padded
+ * form the map is computed on the (lr_h, lr_w) frame and padded to (ph, pw) by the reflection that pads the colour planes. */
+int ss4k_frvsr_temporal_set_noise_map(ss4k_frvsr_temporal* up, int mode);
+int ss4k_frvsr_temporal_noise_map(const ss4k_frvsr_temporal* up, int* mode);
 
 /* ---- measurement hooks (bench.py: live per-kernel timing with HIP events on the launch stream) */
 /* When enabled, every launch of the dominant conv kernel is bracketed with hipEvents on the

@@ -112,6 +112,21 @@ int ss4k_dev_op_temporal_gather_levels(ss4k_ctx* ctx, const float* const* src, c
  * rule above, over the whole (ph, pw).  SS4K_EINVAL before any launch: what the one above refuses, lh < 4 or lw < 4, 4 ph pw >= 2^31. */
 int ss4k_dev_op_temporal_gather_pad(ss4k_ctx* ctx, const float* const* src, const uint32_t* const* flags, int k, int lh, int lw,
                                     uint64_t start_bits, float level_start, const float* levels, float* dst, void* hip_stream);
+/* ... and the four-plane gathers with the motion-adaptive noise map (include/ss4k.h: SS4K_NOISE_MAP_MOTION); routes
+ * "tround::gather_planes_motion" / "tround::gather_planes_motion_pad".  src, flags, k, start_bits, level_start, dst as above; (lh, lw) is the
+ * frame's shape - the unpadded form needs lw divisible by 4 and 16-byte aligned frames, the padded form takes what _gather_pad takes.  prev: k
+ * HOST entries, the three planes of the frame before frame j in its stream, aligned as src[j]; a NULL entry sets frame j's start bit (it gets
+ * the constant level_start).  scales: k HOST floats, frame j's (float)(0.35 * rate).  Plane 3 of frame j is level_start where its start bit is
+ * set or *flags[j] != 0, else min(max(10 B, 0), 0.1f) * scales[j] per pixel.  SS4K_EINVAL before any launch: what the forms above refuse, NULL
+ * prev or scales, a misaligned previous frame or one that overlaps dst, lh < 2 or lw < 2. */
+int ss4k_dev_op_temporal_gather_motion(ss4k_ctx* ctx, const float* const* src, const float* const* prev, const uint32_t* const* flags, int k,
+                                       int lh, int lw, uint64_t start_bits, float level_start, const float* scales, float* dst, void* hip_stream);
+int ss4k_dev_op_temporal_gather_motion_pad(ss4k_ctx* ctx, const float* const* src, const float* const* prev, const uint32_t* const* flags, int k,
+                                           int lh, int lw, uint64_t start_bits, float level_start, const float* scales, float* dst,
+                                           void* hip_stream);
+/* the pixel tile a workgroup of those kernels takes (rows of the frame, columns of the padded width), and the nine fp32 taps they use, row-major */
+int ss4k_dev_temporal_motion_tile(int* tile_h, int* tile_w);
+int ss4k_dev_temporal_motion_taps(float* taps9);
 
 /* ---- launchers of the frame-recurrent upscaler's glue (csrc/frvsr.hip, csrc/frvsr.h) that the public API reaches only inside a whole
  * step or round: what tests/test_gpu_frvsr_glue_budget.py bounds against float64.  Same conventions as above; their routes are reported

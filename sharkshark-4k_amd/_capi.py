@@ -62,7 +62,20 @@ SYMBOLS = [
     "ss4k_frvsr_temporal_scene_cut_total",
     # ... and an lr_shape that 4 does not divide: reflect-pad in front of the denoiser, crop behind it
     "ss4k_frvsr_temporal_create_padded",
+    # the motion-adaptive noise map of both temporal chains
+    "ss4k_upscaler_temporal_set_noise_map", "ss4k_upscaler_temporal_noise_map", "ss4k_frvsr_temporal_set_noise_map",
+    "ss4k_frvsr_temporal_noise_map",
 ]
+NOISE_MAPS = {"constant": 0, "motion": 1}   # SS4K_NOISE_MAP_*
+
+
+def noise_map_mode(word) -> int:
+    """``'constant'`` / ``'motion'`` -> SS4K_NOISE_MAP_*; anything else raises ``ValueError``."""
+    if not isinstance(word, str) or word not in NOISE_MAPS:
+        raise ValueError(f"noise_map is 'constant' or 'motion', not {word!r}")
+    return NOISE_MAPS[word]
+
+
 # include/ss4k_dev.h: libss4k_hip_dev.so only (SS4K_LIB=.../libss4k_hip_dev.so, or load(build.LIB_DEV))
 DEV_SYMBOLS = [
     "ss4k_bench_conv",
@@ -102,6 +115,9 @@ DEV_SYMBOLS = [
     "ss4k_dev_op_frvsrt_clear_flagged",
     # the two kernels of the padded form of that chain (tests/test_gpu_frvsr_temporal_pad_kernel.py)
     "ss4k_dev_op_temporal_gather_pad", "ss4k_dev_op_frvsrt_denoised_in_crop",
+    # the gathers with the motion-adaptive noise map, their tile and their taps (tests/test_gpu_temporal_motion_kernel.py)
+    "ss4k_dev_op_temporal_gather_motion", "ss4k_dev_op_temporal_gather_motion_pad", "ss4k_dev_temporal_motion_tile",
+    "ss4k_dev_temporal_motion_taps",
 ]
 
 
@@ -355,6 +371,16 @@ def load(path: str) -> C.CDLL:
         L.ss4k_frvsr_temporal_scene_cut_total.argtypes = [vp, C.POINTER(C.c_uint64)]
     if hasattr(L, "ss4k_frvsr_temporal_create_padded"):   # (absent from builds before the padded form)
         L.ss4k_frvsr_temporal_create_padded.argtypes = [vp, vp, vp, i, i, i, i, C.c_double, i, i, C.POINTER(vp)]
+    if hasattr(L, "ss4k_upscaler_temporal_set_noise_map"):   # (absent from builds before the motion map)
+        L.ss4k_upscaler_temporal_set_noise_map.argtypes = [vp, i]
+        L.ss4k_upscaler_temporal_noise_map.argtypes = [vp, C.POINTER(i)]
+        L.ss4k_frvsr_temporal_set_noise_map.argtypes = [vp, i]
+        L.ss4k_frvsr_temporal_noise_map.argtypes = [vp, C.POINTER(i)]
+    if hasattr(L, "ss4k_dev_op_temporal_gather_motion"):   # dev library only
+        for f in (L.ss4k_dev_op_temporal_gather_motion, L.ss4k_dev_op_temporal_gather_motion_pad):
+            f.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, i, C.c_uint64, C.c_float, C.POINTER(C.c_float), vp, vp]
+        L.ss4k_dev_temporal_motion_tile.argtypes = [C.POINTER(i), C.POINTER(i)]
+        L.ss4k_dev_temporal_motion_taps.argtypes = [C.POINTER(C.c_float)]
     if hasattr(L, "ss4k_dev_op_temporal_gather_pad"):   # dev library only
         L.ss4k_dev_op_temporal_gather_pad.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, i, C.c_uint64, C.c_float, C.POINTER(C.c_float), vp, vp]
         L.ss4k_dev_op_frvsrt_denoised_in_crop.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, i, i, i, vp, vp]
@@ -878,8 +904,9 @@ class TemporalUpscaler:
     the first 16 frames of a stream, as many as went in after."""
 
     def __init__(self, ctx: Context, sr: Model, denoise: Model, lr_shape, output_shape=None, denoise_rate: float = 1.0, max_push: int = 4,
-                 scene_cut: Optional[float] = None, max_streams: int = 1):
+                 scene_cut: Optional[float] = None, max_streams: int = 1, noise_map: str = "constant"):
         self.ctx, self.sr, self.denoise, self.max_push, self.max_streams = ctx, sr, denoise, int(max_push), int(max_streams)
+        mode = noise_map_mode(noise_map)
         cfg = UpscaleCfg()
         cfg.lr_h, cfg.lr_w = int(lr_shape[0]), int(lr_shape[1])
         cfg.out_h, cfg.out_w = (0, 0) if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
@@ -892,17 +919,30 @@ class TemporalUpscaler:
         else:   # several streams on this object: slots, served in rounds (``round``)
             _check(lib().ss4k_upscaler_temporal_create_streams(ctx._h, C.byref(cfg), sr._h, denoise._h, self.max_push, self.max_streams, C.byref(h)))
         self._h, self.cfg, self.lag = h, cfg, 16
-        if scene_cut is not None:
-            try:
+        try:
+            if scene_cut is not None:
                 self.set_scene_cut(scene_cut)
-            except Exception:
-                self.close()
-                raise
+            if mode != 0:
+                self.set_noise_map(noise_map)
+        except Exception:
+            self.close()
+            raise
 
     def close(self):
         if getattr(self, "_h", None):
             lib().ss4k_upscaler_temporal_destroy(self._h)
             self._h = None
+
+    def set_noise_map(self, noise_map: str) -> None:
+        """The denoiser's fourth input plane (ss4k_upscaler_temporal_set_noise_map): ``'constant'`` - 0.05 for a stream's or scene's first frame,
+        0.1 * rate after, the default - or ``'motion'``, the reference's motion-adaptive map from each frame and the one before it in its
+        stream.  Refused (``RuntimeError``) while any slot has a running stream; ``ValueError`` for another word."""
+        _check(lib().ss4k_upscaler_temporal_set_noise_map(self._h, noise_map_mode(noise_map)))
+
+    def noise_map(self) -> str:
+        m = C.c_int()
+        _check(lib().ss4k_upscaler_temporal_noise_map(self._h, C.byref(m)))
+        return {v: k for k, v in NOISE_MAPS.items()}[int(m.value)]
 
     def set_scene_cut(self, threshold: float) -> None:
         """Scene-cut detection in front of every job (include/ss4k.h): ``threshold`` is the mean absolute byte difference between consecutive
@@ -1289,8 +1329,9 @@ class TemporalFrvsrUpscaler:
     multiples of 4, on reflect-padded planes, and its output is cropped (include/ss4k.h); at a divisible shape it changes nothing."""
 
     def __init__(self, ctx: Context, model: Frvsr, denoise: Model, lr_shape, output_shape=None, denoise_rate: float = 1.0, max_push: int = 4,
-                 max_streams: int = 1, scene_cut: Optional[float] = None, pad: bool = False):
+                 max_streams: int = 1, scene_cut: Optional[float] = None, pad: bool = False, noise_map: str = "constant"):
         self.ctx, self.model, self.denoise, self.max_push, self.max_streams = ctx, model, denoise, int(max_push), int(max_streams)
+        mode = noise_map_mode(noise_map)
         self.lr_shape = (int(lr_shape[0]), int(lr_shape[1]))
         oh, ow = (0, 0) if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
         h = C.c_void_p()
@@ -1302,12 +1343,14 @@ class TemporalFrvsrUpscaler:
             _check(create(ctx._h, model._h, denoise._h, self.lr_shape[0], self.lr_shape[1], oh, ow, float(denoise_rate),
                           self.max_push, self.max_streams, C.byref(h)))
         self._h, self.lag = h, 16
-        if scene_cut is not None:
-            try:
+        try:
+            if scene_cut is not None:
                 self.set_scene_cut(scene_cut)
-            except Exception:
-                self.close()
-                raise
+            if mode != 0:
+                self.set_noise_map(noise_map)
+        except Exception:
+            self.close()
+            raise
 
     @staticmethod
     def has_padded() -> bool:
@@ -1318,6 +1361,16 @@ class TemporalFrvsrUpscaler:
         if getattr(self, "_h", None):
             lib().ss4k_frvsr_temporal_destroy(self._h)
             self._h = None
+
+    def set_noise_map(self, noise_map: str) -> None:
+        """``'constant'`` (default) or ``'motion'``: ``TemporalUpscaler.set_noise_map`` (ss4k_frvsr_temporal_set_noise_map).  With ``pad=True``
+        the map is computed on the ``lr_shape`` frame and reflect-padded with the colour planes."""
+        _check(lib().ss4k_frvsr_temporal_set_noise_map(self._h, noise_map_mode(noise_map)))
+
+    def noise_map(self) -> str:
+        m = C.c_int()
+        _check(lib().ss4k_frvsr_temporal_noise_map(self._h, C.byref(m)))
+        return {v: k for k, v in NOISE_MAPS.items()}[int(m.value)]
 
     def set_scene_cut(self, threshold: float) -> None:
         """Scene-cut detection in front of every round, every slot (include/ss4k.h): ``threshold`` is the mean absolute byte difference between

@@ -201,6 +201,57 @@ int ss4k_upscaler_temporal_set_denoise_rate_stream(ss4k_upscaler_temporal* up, i
     up->t.set_denoise_rate(slot, rate);
   });
 }
+int ss4k_upscaler_temporal_set_noise_map(ss4k_upscaler_temporal* up, int mode) {
+  return guard([&] {
+    SS4K_REQUIRE(up, "ss4k_upscaler_temporal_set_noise_map: NULL argument");
+    up->t.set_noise_map(mode);
+  });
+}
+int ss4k_upscaler_temporal_noise_map(const ss4k_upscaler_temporal* up, int* mode) {
+  return guard([&] {
+    SS4K_REQUIRE(up && mode, "ss4k_upscaler_temporal_noise_map: NULL argument");
+    *mode = up->t.noise_map;
+  });
+}
+
+#ifdef SS4K_DEV
+static void dev_temporal_gather_motion(const float* const* src, const float* const* prev, const uint32_t* const* flags, int k, int lh, int lw,
+                                       bool pad, uint64_t start_bits, float level_start, const float* scales, float* dst, void* s) {
+  SS4K_REQUIRE(k >= 1 && k <= TROUND_MAX_FRAMES, "ss4k_dev_op_temporal_gather_motion: 1..64 frames");
+  TroundTable tab{};
+  unsigned long long bits = (unsigned long long)start_bits;
+  for (int j = 0; j < k; ++j) {
+    tab.src[j] = src[j]; tab.prev[j] = prev[j]; tab.flag[j] = flags ? flags[j] : nullptr; tab.level[j] = scales[j];
+    if (!prev[j]) bits |= 1ull << j;   // no previous frame: the constant
+  }
+  if (pad) op_tround_gather_motion_pad(tab, dst, k, lh, lw, bits, level_start, (hipStream_t)s);
+  else op_tround_gather_motion(tab, dst, k, lh, lw, bits, level_start, (hipStream_t)s);
+}
+int ss4k_dev_op_temporal_gather_motion(ss4k_ctx* c, const float* const* src, const float* const* prev, const uint32_t* const* flags, int k, int lh,
+                                       int lw, uint64_t start_bits, float level_start, const float* scales, float* dst, void* s) {
+  return guard([&] {
+    SS4K_REQUIRE(c && src && prev && scales, "ss4k_dev_op_temporal_gather_motion: NULL argument");
+    dev_temporal_gather_motion(src, prev, flags, k, lh, lw, false, start_bits, level_start, scales, dst, s);
+  });
+}
+int ss4k_dev_op_temporal_gather_motion_pad(ss4k_ctx* c, const float* const* src, const float* const* prev, const uint32_t* const* flags, int k,
+                                           int lh, int lw, uint64_t start_bits, float level_start, const float* scales, float* dst, void* s) {
+  return guard([&] {
+    SS4K_REQUIRE(c && src && prev && scales, "ss4k_dev_op_temporal_gather_motion_pad: NULL argument");
+    dev_temporal_gather_motion(src, prev, flags, k, lh, lw, true, start_bits, level_start, scales, dst, s);
+  });
+}
+int ss4k_dev_temporal_motion_tile(int* th, int* tw) {
+  if (!th || !tw) return SS4K_EINVAL;
+  *th = TROUND_MOTION_TILE_H; *tw = TROUND_MOTION_TILE_W;
+  return SS4K_OK;
+}
+int ss4k_dev_temporal_motion_taps(float* taps9) {
+  if (!taps9) return SS4K_EINVAL;
+  temporal_round::motion_taps(taps9);
+  return SS4K_OK;
+}
+#endif
 
 #ifdef SS4K_DEV
 // one launcher call behind both dev entries: levels[j] per frame, or one level for all of them

@@ -60,6 +60,18 @@ int ss4k_frvsr_temporal_set_denoise_rate_stream(ss4k_frvsr_temporal* up, int slo
     up->t.set_denoise_rate(slot, rate);
   });
 }
+int ss4k_frvsr_temporal_set_noise_map(ss4k_frvsr_temporal* up, int mode) {
+  return guard([&] {
+    SS4K_REQUIRE(up, "ss4k_frvsr_temporal_set_noise_map: NULL argument");
+    up->t.set_noise_map(mode);
+  });
+}
+int ss4k_frvsr_temporal_noise_map(const ss4k_frvsr_temporal* up, int* mode) {
+  return guard([&] {
+    SS4K_REQUIRE(up && mode, "ss4k_frvsr_temporal_noise_map: NULL argument");
+    *mode = up->t.noise_map;
+  });
+}
 int ss4k_frvsr_temporal_out_shape(const ss4k_frvsr_temporal* up, int* oh, int* ow) {
   return guard([&] { SS4K_REQUIRE(up && oh && ow, "ss4k_frvsr_temporal_out_shape: NULL argument"); up->t.out_shape(oh, ow); });
 }

@@ -117,6 +117,13 @@ void FrvsrTemporal::set_scene_cut(double threshold) {
   for (auto& s : slots) if (s->cut) s->cut->set(threshold);
 }
 
+void FrvsrTemporal::set_noise_map(int mode) {
+  SS4K_REQUIRE(mode == temporal_round::NOISE_MAP_CONSTANT || mode == temporal_round::NOISE_MAP_MOTION, "frvsr temporal: the noise map is constant (0) or motion (1)");
+  // a stream's frames all enter by one rule: what its denoiser carries was made from the planes it was given
+  for (const auto& s : slots) SS4K_REQUIRE(!s->running(), "frvsr temporal: the noise map cannot change while a stream is running");
+  noise_map = mode;
+}
+
 void FrvsrTemporal::set_denoise_rate(int si, float rate) {
   FrvtSlot& s = slot(si);
   SS4K_REQUIRE(std::isfinite(rate) && rate >= 0.f, "frvsr temporal: a denoise rate is finite and not negative");
@@ -178,6 +185,7 @@ int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, i
   for (int i = 0; i < k; ++i) SS4K_REQUIRE(fr[i], "frvsr temporal round: NULL frame");
   SS4K_REQUIRE(out || p.total == 0, "frvsr temporal round: NULL output for a round that returns frames");
   const frvsr_temporal::Waves waves = frvsr_temporal::make_waves(p);
+  const temporal_round::Motion mo = temporal_round::make_motion(p, max_push);   // (read in motion mode alone)
   for (int r = 0; r < waves.n_waves; ++r) {
     int32_t ids[FRVT_MAX_ITEMS];
     for (int i = 0; i < waves.w[r].n; ++i) ids[i] = waves.w[r].slot[i];
@@ -210,9 +218,12 @@ int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, i
         fin.p[q] = fr[p.order[q]];
         dst.p[q] = s.ring.as<float>() + frame * p.ring_in[q];
         tab.src[q] = dst.p[q];
-        tab.level[q] = level(s);
+        tab.level[q] = motion() ? motion_level(s) : level(s);
+        // the frame before it in its stream: a ring slot this round's frames-in launch does not write, or an earlier frame of this item
+        if (motion() && mo.ring_prev[q] >= 0) tab.prev[q] = s.ring.as<float>() + frame * mo.ring_prev[q];
       }
       if (s.first_frame) start_bits |= 1ull << it.first;
+      SS4K_REQUIRE(!motion() || s.first_frame == (((mo.constant_bits >> it.first) & 1ull) != 0), "internal: a slot's first frame is not its denoiser's");
     }
     up.m->timed(FRV_GLUE, st, [&] { op_frames_in_items(fin, dst, k, h, w, lh, lw, st); });
     // ---- 1b. scene cuts (TemporalUpscaler::round's step 2): each slot's own detector on its own frames as they arrived, frame 0 of an item
@@ -226,7 +237,9 @@ int FrvsrTemporal::round(const uint8_t* const* fr, const int* slot_ids, int k, i
       for (int j = 0; j < it.n; ++j) tab.flag[it.first + j] = item_cuts[t] + j;
     }
     // ---- 2. the packed (k, 4, lh, lw) denoiser input, noise planes included: one launch
-    if (padded()) op_tround_gather_pad(tab, lr4.as<float>(), k, lh, lw, start_bits, 0.05f, st);
+    if (motion() && padded()) op_tround_gather_motion_pad(tab, lr4.as<float>(), k, lh, lw, start_bits, 0.05f, st);
+    else if (motion()) op_tround_gather_motion(tab, lr4.as<float>(), k, lh, lw, start_bits, 0.05f, st);
+    else if (padded()) op_tround_gather_pad(tab, lr4.as<float>(), k, lh, lw, start_bits, 0.05f, st);
     else op_tround_gather(tab, lr4.as<float>(), k, plane, 4, start_bits, 0.05f, st);
     // ---- 3. one push per item, one after the other: they share the model's activation slots
     for (int t = 0; t < p.n_items; ++t) {

@@ -74,6 +74,7 @@ struct FrvsrTemporal {
   double denoise_rate = 1.0;
   double cut_threshold = 0;   // what set_scene_cut last said; a slot's detector is made when the slot first needs it
   int max_push = 0;
+  int noise_map = temporal_round::NOISE_MAP_CONSTANT;   // set_noise_map: the denoiser's fourth plane, a constant per frame or the motion map
 
   void create(ss4k_ctx* c, Frvsr* m, Model* bsvd_stream_model, int lr_h, int lr_w, int out_h, int out_w, double denoise_rate, int max_push, int max_streams,
               bool allow_pad = false);
@@ -99,6 +100,10 @@ struct FrvsrTemporal {
   size_t stream_state_bytes_for() const;   // what one slot will hold, before any push
   void release_idle();                     // frees the state of slots with no running stream
   float level(const FrvtSlot& s) const { return (float)(0.1 * (s.rate < 0 ? denoise_rate : s.rate)); }   // fsrcnn_upscaler.py:269-271
+  // the motion map's scale for the slot's frames (temporal_motion_plan.h)
+  float motion_level(const FrvtSlot& s) const { return temporal_round::motion_scale(s.rate < 0 ? denoise_rate : s.rate); }
+  bool motion() const { return noise_map == temporal_round::NOISE_MAP_MOTION; }
+  void set_noise_map(int mode);            // refused while any slot has a running stream
 
  private:
   // one wave: open_slots, the late reset if a stream of the wave carries cut flags, denoised_in_items, the step, close_slots, frames out.

@@ -6,6 +6,8 @@
 // denoiser's shift and the noise planes read them.
 // Several streams share one object: what a stream owns sits in a TemporalSlot, and a round (temporal_round_plan.h) takes frames of several slots,
 // pushes each slot's denoiser in turn and runs ONE tail over everything that became ready.  The one-stream entry points are slot 0.
+// The noise plane is a constant per frame, or - set_noise_map - the motion-adaptive map (temporal_motion_plan.h): the same ring that keeps a
+// frame's LR planes for its tail still holds the frame before it when it arrives, and the round's gather reads both.
 #include "upscaler_temporal.h"
 #include "frvsr.h"
 #include <cmath>
@@ -159,6 +161,13 @@ void TemporalUpscaler::set_denoise_rate(int si, float rate) {
   s.rate = (double)rate;
 }
 
+void TemporalUpscaler::set_noise_map(int mode) {
+  SS4K_REQUIRE(mode == temporal_round::NOISE_MAP_CONSTANT || mode == temporal_round::NOISE_MAP_MOTION, "temporal upscaler: the noise map is constant (0) or motion (1)");
+  // a stream's frames all enter by one rule: what its denoiser carries was made from the planes it was given
+  for (const auto& s : slots) SS4K_REQUIRE(!s->running(), "temporal upscaler: the noise map cannot change while a stream is running");
+  noise_map = mode;
+}
+
 // the detector of a slot that has none yet, once a threshold is set
 void TemporalUpscaler::want_cut(TemporalSlot& s) {
   if (s.cut || !(cut_threshold > 0)) return;
@@ -198,6 +207,7 @@ int TemporalUpscaler::round(const uint8_t* const* fr, const int* slot_ids, int k
   SS4K_REQUIRE(!p.refusal, p.refusal ? p.refusal : "");
   for (int i = 0; i < k; ++i) SS4K_REQUIRE(fr[i], "temporal round: NULL frame");
   SS4K_REQUIRE(out || p.total == 0, "temporal round: NULL output for a round that returns frames");
+  const temporal_round::Motion mo = temporal_round::make_motion(p, max_push);   // (read in motion mode alone)
   // (what the launchers and the push would refuse, restated: none of them may stop a round half way)
   SS4K_REQUIRE((double)(bsvd_online::LAG / 2 + max_push) * lh * lw < 2147483648.0, "bsvd online push: a carried plane holds at most 2^31 pixels");
   SS4K_REQUIRE((double)h * lh < 2147483648.0 && (double)w * lw < 2147483648.0, "temporal round: a window bound of the area resize would overflow");
@@ -226,9 +236,12 @@ int TemporalUpscaler::round(const uint8_t* const* fr, const int* slot_ids, int k
         fin.p[q] = fr[p.order[q]];
         dst.p[q] = s.ring.as<float>() + frame * p.ring_in[q];
         tab.src[q] = dst.p[q];
-        tab.level[q] = level(s);
+        tab.level[q] = motion() ? motion_level(s) : level(s);
+        // the frame before it in its stream: a ring slot this round's frames-in launch does not write, or an earlier frame of this item
+        if (motion() && mo.ring_prev[q] >= 0) tab.prev[q] = s.ring.as<float>() + frame * mo.ring_prev[q];
       }
       if (s.first_frame) start_bits |= 1ull << it.first;
+      SS4K_REQUIRE(!motion() || s.first_frame == (((mo.constant_bits >> it.first) & 1ull) != 0), "internal: a slot's first frame is not its denoiser's");
     }
     op_frames_in_items(fin, dst, k, h, w, lh, lw, st);
     // ---- 2. scene cuts: each slot's own detector on its own frames, frame 0 of an item against the slot's stored frame
@@ -241,7 +254,8 @@ int TemporalUpscaler::round(const uint8_t* const* fr, const int* slot_ids, int k
       for (int j = 0; j < it.n; ++j) tab.flag[it.first + j] = item_cuts[t] + j;
     }
     // ---- 3. the packed (k, 4, lh, lw) denoiser input, noise planes included: one launch
-    op_tround_gather(tab, lr4.as<float>(), k, plane, 4, start_bits, 0.05f, st);
+    if (motion()) op_tround_gather_motion(tab, lr4.as<float>(), k, lh, lw, start_bits, 0.05f, st);
+    else op_tround_gather(tab, lr4.as<float>(), k, plane, 4, start_bits, 0.05f, st);
     // ---- 4. one push per item, one after the other: they share the model's activation slots
     for (int t = 0; t < p.n_items; ++t) {
       const temporal_round::Item& it = p.items[t];
@@ -289,25 +303,43 @@ int TemporalUpscaler::frames(const uint8_t* in, int n, int h, int w, uint8_t* ou
   int oh, ow; up.out_shape(h, w, &oh, &ow);
   SS4K_REQUIRE(out_capacity_bytes >= (size_t)k * oh * ow * 3, "temporal upscaler: output buffer too small for the frames that become ready");
   up.sr->check_input(up.cfg.sr_is_realesrgan ? std::max(k, 1) : 3 * std::max(k, 1), lh, lw);
-  // ---- scene cuts, if on: the job's flags and its noise planes (0.05 for a scene's first frame as for a stream's), all on the device
+  // (the push's own size refusal, restated: a job that BsvdOnline::push would refuse must not move the detector either)
+  const bool with_cuts = cut && cut->on();
+  SS4K_REQUIRE(!(with_cuts || motion()) || (double)(bsvd_online::LAG / 2 + on.max_push) * lh * lw < 2147483648.0,
+               "bsvd online push: a carried plane holds at most 2^31 pixels");
+  SS4K_REQUIRE(!motion() || first_frame == (pushed == 0), "internal: a slot's first frame is not its stream's");
+  // ---- scene cuts, if on: the job's flags, all on the device; with the constant plane also the noise planes (0.05 for a scene's first frame as
+  // for a stream's) - the motion gather below reads the flags itself
   const uint32_t* cuts = nullptr;
-  if (cut && cut->on()) {
-    // (the push's own size refusal, restated: a job that BsvdOnline::push would refuse must not move the detector either)
-    SS4K_REQUIRE((double)(bsvd_online::LAG / 2 + on.max_push) * lh * lw < 2147483648.0, "bsvd online push: a carried plane holds at most 2^31 pixels");
+  if (with_cuts) {
     lr4.ensure(plane * 4 * n * 4);
     cuts = cut->detect(in, n, h, w, st);
-    op_bsvd_noise_planes(lr4.as<float>(), n, plane, cuts, first_frame ? 1 : 0, 0.05f, level(s0), st);
-    first_frame = false;
+    if (!motion()) {
+      op_bsvd_noise_planes(lr4.as<float>(), n, plane, cuts, first_frame ? 1 : 0, 0.05f, level(s0), st);
+      first_frame = false;
+    }
   }
   const float* lr_before = up.planes_in(in, n, h, w, lh, lw, st);
   ring.ensure(frame * ring_frames() * 4); lr4.ensure(plane * 4 * n * 4); den.ensure(frame * on.max_push * 4);
+  // ---- lr4, the packed denoiser input, and the job's planes into the ring.  Constant plane: a copy and a fill per frame.  Motion map: round()'s
+  // gather on the ring slots, every frame against the slot before its own (one launch, behind the loop)
+  TroundTable tab{};
   for (int i = 0; i < n; ++i) {
-    const float noise = first_frame ? 0.05f : level(s0);  // fsrcnn_upscaler.py:262, :269-271
+    float* at = ring.as<float>() + frame * ((pushed + i) % ring_frames());
+    if (!motion()) {
+      const float noise = first_frame ? 0.05f : level(s0);  // fsrcnn_upscaler.py:262, :269-271
+      first_frame = false;
+      float* dst = lr4.as<float>() + plane * 4 * i;
+      SS4K_HIP(hipMemcpyAsync(dst, lr_before + frame * i, frame * 4, hipMemcpyDeviceToDevice, st));
+      if (!cuts) fill_plane(dst + frame, plane, noise, st);
+    }
+    SS4K_HIP(hipMemcpyAsync(at, lr_before + frame * i, frame * 4, hipMemcpyDeviceToDevice, st));
+    tab.src[i] = at; tab.flag[i] = cuts ? cuts + i : nullptr; tab.level[i] = motion_level(s0);
+    if (pushed + i > 0) tab.prev[i] = ring.as<float>() + frame * ((pushed + i - 1) % ring_frames());
+  }
+  if (motion()) {
+    op_tround_gather_motion(tab, lr4.as<float>(), n, lh, lw, first_frame ? 1ull : 0ull, 0.05f, st);
     first_frame = false;
-    float* dst = lr4.as<float>() + plane * 4 * i;
-    SS4K_HIP(hipMemcpyAsync(dst, lr_before + frame * i, frame * 4, hipMemcpyDeviceToDevice, st));
-    if (!cuts) fill_plane(dst + frame, plane, noise, st);
-    SS4K_HIP(hipMemcpyAsync(ring.as<float>() + frame * ((pushed + i) % ring_frames()), lr_before + frame * i, frame * 4, hipMemcpyDeviceToDevice, st));
   }
   const int got = on.push(lr4.as<float>(), n, lh, lw, den.as<float>(), on.max_push, st, cuts);
   pushed += n;

@@ -3,6 +3,7 @@
 #include "bsvd_online.h"
 #include "scene_cut.h"
 #include "temporal_round_plan.h"
+#include "temporal_motion_plan.h"
 #include "upscaler.h"
 #include <memory>
 #include <vector>
@@ -40,11 +41,14 @@ struct TemporalCut {
 
 // ---- the kernel of a round (temporal_round.hip) -----------------------------------------------------------------------------------------------
 // Frame j of a launch: its three LR planes at src[j] (3 * plane_px fp32, contiguous, 16-byte aligned - a slot of its stream's ring), and the device
-// word that says whether it starts a scene (NULL: it does not), and the noise level of its stream's slot (read with four planes only).  BY VALUE
-// in the kernel arguments, as FrvsrPtrs: 1280 bytes, no device table.
+// word that says whether it starts a scene (NULL: it does not), and the noise level of its stream's slot (read with four planes only).  prev[j]
+// is read by the motion gathers alone: the three LR planes of the frame before it in its stream (NULL: it has none).  BY VALUE in the kernel
+// arguments, as FrvsrPtrs: 1792 bytes, no device table.
 constexpr int TROUND_MAX_FRAMES = temporal_round::MAX_FRAMES;
-struct TroundTable { const float* src[TROUND_MAX_FRAMES]; const uint32_t* flag[TROUND_MAX_FRAMES]; float level[TROUND_MAX_FRAMES]; };
-static_assert(sizeof(TroundTable) == 1280, "the round's table travels in the kernel arguments: keep it far below 4 KiB");
+struct TroundTable {
+  const float* src[TROUND_MAX_FRAMES]; const uint32_t* flag[TROUND_MAX_FRAMES]; float level[TROUND_MAX_FRAMES]; const float* prev[TROUND_MAX_FRAMES];
+};
+static_assert(sizeof(TroundTable) == 1792, "the round's table travels in the kernel arguments: keep it far below 4 KiB");
 // dst (k, planes, plane_px) fp32: planes 0..2 of frame j from src[j]; with planes == 4, plane 3 is level_start where bit j of start_bits is set or
 // *flag[j] != 0, and level[j] otherwise - the bits of bsvdo::noise_planes / the one-stream path's fill.  One launch, one thread per 16-byte slot.
 void op_tround_gather(const TroundTable& tab, float* dst, int k, size_t plane_px, int planes, unsigned long long start_bits, float level_start,
@@ -56,6 +60,20 @@ void op_tround_gather(const TroundTable& tab, float* dst, int k, size_t plane_px
 // lh < 4 or lw < 4, and 4 ph pw >= 2^31.
 void op_tround_gather_pad(const TroundTable& tab, float* dst, int k, int lh, int lw, unsigned long long start_bits, float level_start,
                           hipStream_t st);
+
+// ---- the motion-adaptive noise map (temporal_motion_plan.h has the rule) ------------------------------------------------------------------------
+// op_tround_gather with four planes where plane 3 of frame j is a MAP: the constant level_start where bit j of start_bits is set, *flag[j] != 0 or
+// prev[j] is NULL - the bits of op_tround_gather - and otherwise min(max(10 B, 0), 0.1f) * level[j], B the 3 x 3 Gaussian ('reflect' borders) of the
+// mean over the planes of |src[j] - prev[j]|; level[j] carries temporal_round::motion_scale(rate).  fp32 throughout, in one fixed order per pixel:
+// a pixel's bits depend on its own 54 inputs, the taps and level[j] alone.  One launch; a workgroup takes TROUND_MOTION_TILE_H x _W pixel tiles.
+// Refuses - before the launch - what op_tround_gather refuses (with lh * lw for plane_px, and lw a multiple of 4: a row is whole 16-byte slots),
+// lh < 2 or lw < 2, and a prev[j] that a frame needs (no start bit) and that is misaligned or overlaps the destination.
+constexpr int TROUND_MOTION_TILE_H = 16, TROUND_MOTION_TILE_W = 64;
+void op_tround_gather_motion(const TroundTable& tab, float* dst, int k, int lh, int lw, unsigned long long start_bits, float level_start, hipStream_t st);
+// The padded form (op_tround_gather_pad's shapes and alignments): the map is computed on the (lh, lw) frame and padded to (ph, pw) by the same
+// reflection as planes 0..2.  On a shape that 4 divides: the bits of op_tround_gather_motion.
+void op_tround_gather_motion_pad(const TroundTable& tab, float* dst, int k, int lh, int lw, unsigned long long start_bits, float level_start,
+                                 hipStream_t st);
 
 // what one stream owns; allocated by its first push
 struct TemporalSlot {
@@ -74,6 +92,7 @@ struct TemporalUpscaler {
   DevBuf lr4, den, den_flush, lrk, blend;             // job buffers, shared: the pushes of a round run one after the other
   double cut_threshold = 0;                           // what set_scene_cut last said; a slot's detector is made when the slot first needs it
   int max_push = 0;
+  int noise_map = temporal_round::NOISE_MAP_CONSTANT; // set_noise_map: the denoiser's fourth plane, a constant per frame or the motion map
 
   void create(ss4k_ctx* c, const ss4k_upscale_cfg& cfg, Model* sr, Model* bsvd_stream_model, int max_push, int max_streams = 1);
   int max_streams() const { return (int)slots.size(); }
@@ -95,6 +114,10 @@ struct TemporalUpscaler {
   void set_scene_cut(double threshold);    // every slot
   void set_denoise_rate(int s, float rate);   // the slot's frames from the next push or round on, until its stream ends
   float level(const TemporalSlot& s) const { return (float)(0.1 * (s.rate < 0 ? up.cfg.denoise_rate : s.rate)); }   // fsrcnn_upscaler.py:269-271
+  // the motion map's scale for the slot's frames (temporal_motion_plan.h)
+  float motion_level(const TemporalSlot& s) const { return temporal_round::motion_scale(s.rate < 0 ? up.cfg.denoise_rate : s.rate); }
+  bool motion() const { return noise_map == temporal_round::NOISE_MAP_MOTION; }
+  void set_noise_map(int mode);            // refused while any slot has a running stream
 
  private:
   void emit(TemporalSlot& s, int k, const float* denoised, uint8_t* out, hipStream_t st);

@@ -186,8 +186,8 @@ class TemporalEgvsrNode(TemporalNode):
       is the generator's x4 output: at ``lr_shape=(540, 960)`` a frame is 2160 x 3840 x 3 = 24.9 MB, so a slot is about 500 MB at the defaults
       (4 + 16 frames) and a worker pins ``host_slots`` of them.  Set ``output_shape`` (the frames are area-resized on the device) or lower
       ``host_slots`` / ``job_frames``.
-    * KEYWORDS - ``denoise_scene_cut``, ``denoise_rate``, ``denoise_weights`` and ``denoise_pad`` (any ``lr_shape`` of at least 8 x 8) pass
-      through to the workers, with every other keyword of the service; ``scene_cut`` stays refused with the denoiser (the service's rule).
+    * KEYWORDS - ``denoise_scene_cut``, ``denoise_rate``, ``denoise_weights``, ``denoise_pad`` (any ``lr_shape`` of at least 8 x 8) and
+      ``denoise_noise_map`` (``'motion'``: the motion-adaptive noise map; ``TemporalNode`` spells it ``noise_map``) pass through to the workers, with every other keyword of the service; ``scene_cut`` stays refused with the denoiser (the service's rule).
     """
     CUTS_KEY = "egvsr.scene_cuts"
     LAG = HipEgvsrUpscalerService.TEMPORAL_LAG

@@ -49,6 +49,10 @@ the denoiser does not reach across the scene's first frame, and when that frame 
 ``hr_prev`` are zeroed before the step: a stream is the concatenation of its scenes, each as if it had been a stream of its own.  A job still
 returns the frames it returns without the keyword.  T is validated as ``scene_cut``; each job's profiler carries ``egvsr.scene_cuts``.
 
+``denoise_noise_map='motion'`` (default ``'constant'``; needs ``denoise_temporal=True``): the denoiser's noise plane is the motion-adaptive map
+of ``HipUpscalerService(noise_map='motion')`` (``ss4k_frvsr_temporal_set_noise_map``); with ``denoise_pad`` it is computed at ``lr_shape`` and
+reflect-padded with the colour planes.
+
 ``generator='tecogan'`` runs TecoGAN's FRNet instead (``nb`` then defaults to 16; its checkpoint is that class's bare state_dict).
 
 Weights as for the other services: ``weights=None`` looks ``EGVSR_iter420000.pth`` (``egvsr_upscaler.py:25``) up in
@@ -184,7 +188,8 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
 
     def __init__(self, lr_level=1, device=0, on_queue=None, *, weights=None, checkpoint_dir: Optional[str] = None, dtype="f16", nb=None,
                  lr_shape=None, seed=0, max_streams=1, generator="egvsr", degradation="BD", scene_cut=None, denoise_temporal=False,
-                 denoise_rate=1.0, denoise_weights=None, temporal_max_push=None, denoise_scene_cut=None, denoise_pad=False):
+                 denoise_rate=1.0, denoise_weights=None, temporal_max_push=None, denoise_scene_cut=None, denoise_pad=False,
+                 denoise_noise_map="constant"):
         self.lr_shape = tuple(lr_shape) if lr_shape is not None else LR_SHAPES[lr_level]
         self.scale = 4
         self.hr_shape = tuple([i * self.scale for i in self.lr_shape])
@@ -211,6 +216,9 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
         self.denoise_pad = bool(denoise_pad)
         if self.denoise_pad and not self.denoise_temporal:
             raise ValueError("denoise_pad belongs to denoise_temporal=True: without the denoiser in front there is nothing to pad")
+        # denoise_noise_map: the denoiser's fourth input plane, 'constant' (default) or 'motion' (_capi.TemporalFrvsrUpscaler.set_noise_map)
+        from .hip_upscaler import validate_noise_map
+        self.denoise_noise_map = validate_noise_map(denoise_noise_map, self.denoise_temporal, "denoise_noise_map")
         # denoise_scene_cut: the denoised streams' scene-cut threshold (_capi.TemporalFrvsrUpscaler.set_scene_cut); None / 0: off
         try:
             self.denoise_scene_cut = check_scene_cut(denoise_scene_cut)
@@ -301,6 +309,8 @@ class HipEgvsrUpscalerService(BaseUpscalerService):
             more = {"scene_cut": self.denoise_scene_cut} if self.denoise_scene_cut else {}   # (off: the object is built as before the keyword)
             if self.denoise_pad:
                 more["pad"] = True
+            if getattr(self, "denoise_noise_map", "constant") != "constant":
+                more["noise_map"] = self.denoise_noise_map
             up = _capi.TemporalFrvsrUpscaler(self.ctx, self.model, self.denoise_model, key[0], key[1], float(self.denoise_rate),
                                              self.temporal_max_push, self.max_streams, **more)
             log(f"denoised streams: {self.max_streams} stream slot(s), {up.stream_state_bytes_for() / 2**20:.1f} MiB of state per running "

@@ -50,6 +50,11 @@ does not fit the out slot raises before a frame runs and takes no stream slot.  
 a flush: its input slot is not read, what was inside lands in its out slot.  ``stream_rates={id: rate}`` - the keyword of ``upscale`` and an
 optional field of a queue entry - sets the denoise rate of those streams' slots before the job's first round (``temporal_node.TemporalNode`` is
 the caller that runs all this on several workers).
+
+``noise_map='motion'`` (default ``'constant'``; needs ``denoise_temporal=True``): the temporal denoiser's noise plane is the motion-adaptive map
+the reference computes and then overwrites (fsrcnn_upscaler.py:250-254) - from each frame's LR planes and those of the frame before it in its
+stream, on the device (``ss4k_upscaler_temporal_set_noise_map``, include/ss4k.h).  A stream's or scene's first frame keeps the constant 0.05; a
+stream's rate scales its map.  ``ValueError`` without ``denoise_temporal`` or for any other word.
 """
 from __future__ import annotations
 
@@ -69,6 +74,15 @@ from .egvsr_upscaler import StreamQueueEntry
 from .upscaler_base import BaseUpscalerService, UpscalerQueueEntry, answer, record_span  # noqa: F401
 
 LR_LEVELS = [(360, 640), (540, 960), (630, 1120), (720, 1280), (900, 1600), (1080, 1920)]
+
+
+def validate_noise_map(word, denoise_temporal: bool, keyword: str = "noise_map") -> str:
+    """The noise-map keyword of both services: ``'constant'`` (the default) or ``'motion'``; ``'motion'`` needs ``denoise_temporal``."""
+    if not isinstance(word, str) or word not in ("constant", "motion"):
+        raise ValueError(f"{keyword}={word!r}: the denoiser's noise map is 'constant' or 'motion'")
+    if word != "constant" and not denoise_temporal:
+        raise ValueError(f"{keyword}={word!r} belongs to denoise_temporal=True: the per-frame denoiser keeps no previous input frame on the device")
+    return word
 
 
 def validate_scene_cut(scene_cut, denoise_temporal: bool) -> Optional[float]:
@@ -145,7 +159,7 @@ class HipUpscalerService(BaseUpscalerService):
                  scale=4, model_name=None, dtype="f16", weights=None, checkpoint_dir: Optional[str] = None,
                  lr_shape=None, single_mode=None, seed=0, model_flags=0, fsrcnn_dtype="f32",
                  group: Optional[sharding.GroupSpec] = None, overlap_jobs=True, overlap_sets=3, overlap_max_frames=1,
-                 denoise_temporal=False, temporal_max_push=None, scene_cut=None, max_streams=1):
+                 denoise_temporal=False, temporal_max_push=None, scene_cut=None, max_streams=1, noise_map="constant"):
         # None (the stream pipeline's default: "the compiled backend", pipeline.py:23,41-44) and False (the image server: "eager",
         # image_pipeline.py:58-61) both mean "whatever this build runs the network with" to a caller that cannot know about 'hip';
         # so does a backend of the REFERENCE asked for by name ('trt', 't2trt', 'jit', 'ds': realesrgan/factory.py:175-230, fsrcnn/factory.py:17-69 -
@@ -200,6 +214,10 @@ class HipUpscalerService(BaseUpscalerService):
         # scene_cut: the temporal stream's scene-cut threshold (_capi.TemporalUpscaler.set_scene_cut), the mean absolute byte difference
         # between consecutive input frames in (0, 255]; None or 0: off.  Cuts are found and acted on on the device; jobs return what they return without
         self.scene_cut = validate_scene_cut(scene_cut, self.denoise_temporal)
+        # noise_map: the temporal denoiser's fourth input plane (_capi.TemporalUpscaler.set_noise_map): 'constant' (default) or 'motion', the
+        # reference's motion-adaptive map from each frame and the one before it in its stream - the per-frame denoiser has no previous input
+        # frame on the device, so the keyword belongs to denoise_temporal
+        self.noise_map = validate_noise_map(noise_map, self.denoise_temporal, "noise_map")
         self._t_emitted = 0          # frames of the running stream returned so far = the stream index of the next frame to come back
         self._t_first = 0            # ... of the first frame the LAST upscale() / flush() returned
         # max_streams: stream slots of the temporal upscaler (_capi.TemporalUpscaler(max_streams=S)): ``upscale(frames, streams=ids)`` names the
@@ -634,6 +652,8 @@ class HipUpscalerService(BaseUpscalerService):
         if getattr(self, "denoise_temporal", False) and (js["up"] is None or key != js["key"]):
             # (a new geometry starts a new stream: what the old object still held is dropped with it)
             more = {"max_streams": self.max_streams} if getattr(self, "max_streams", 1) > 1 else {}
+            if getattr(self, "noise_map", "constant") != "constant":   # (constant: the object is built as before the keyword)
+                more["noise_map"] = self.noise_map
             js["up"] = _capi.TemporalUpscaler(js["ctx"], js["model"], js["denoise"], self.lr_shape, self.output_shape, self.denoise_rate,
                                               self.temporal_max_push, scene_cut=getattr(self, "scene_cut", None), **more)
             js["key"] = key

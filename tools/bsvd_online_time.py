@@ -23,11 +23,15 @@ the S frames (written into the in-ring slot by this process, up to ``--depth`` j
 answer).  ``host_over_resident`` is the ratio of the best samples.  The S one-stream objects are left out of this mode.
 ``--gather-kernel`` (dev library): microseconds per launch of ``tround::gather_planes<4>`` alone, 4 and 16 frames of ``--h`` x ``--w``, through
 ``ss4k_dev_op_temporal_gather`` - the entry a parent build has too, for an A/B of the kernel across builds (``SS4K_LIB``).
+``--noise-map motion``: the temporal objects and services of ``--streams`` (``--host-rings`` included) and ``--service`` run with the
+motion-adaptive noise map (the per-frame service of ``--service`` has none); with ``--gather-kernel``
+the motion gather (``tround::gather_planes_motion``, six planes read and four written per frame) is timed against the constant one (three read,
+four written) in one session, alternating, with the ratio of the best samples next to the ratio of the planes moved, 10 / 7.
 
 Usage:  python tools/bsvd_online_time.py [--h 720 --w 1280 --dtype f16 --variant bsvd-32 --push 4 --iters 20 --runs 2] [--scene-cut T] [--out FILE]
         python tools/bsvd_online_time.py --streams 4 --push 1 --sr rrdbnet --iters 64 [--out FILE]
         python tools/bsvd_online_time.py --streams 4 --push 1 --sr fsrcnn --iters 64 --host-rings [--depth 3] [--out FILE]
-        SS4K_LIB=.../libss4k_hip_dev.so python tools/bsvd_online_time.py --gather-kernel [--out FILE]
+        SS4K_LIB=.../libss4k_hip_dev.so python tools/bsvd_online_time.py --gather-kernel [--noise-map motion] [--out FILE]
 """
 import argparse
 import json
@@ -67,7 +71,8 @@ def service(a):
     kinds = ("per_frame", "temporal") + (("temporal_cuts",) if a.scene_cut else ())
     svcs = {k: HipUpscalerService(denoising=True, denoise_temporal=k != "per_frame", temporal_max_push=a.push, upscaler_model="fsrcnn", scale=2,
                                   lr_shape=(a.h, a.w), dtype=a.dtype, fsrcnn_dtype="f16", weights="synthetic",
-                                  scene_cut=a.scene_cut if k == "temporal_cuts" else None) for k in kinds}
+                                  scene_cut=a.scene_cut if k == "temporal_cuts" else None,
+                                  noise_map=a.noise_map if k != "per_frame" else "constant") for k in kinds}
     for s in svcs.values():
         s.output_shape = None
         s.proc_init()
@@ -77,7 +82,7 @@ def service(a):
     for _ in range(a.runs):
         for k, s in svcs.items():
             res.setdefault(k, []).append(1000.0 * a.push / timed(lambda: s.upscale(frames), a.iters))
-    line = {"tool": "bsvd_online_time --service", "h": a.h, "w": a.w, "dtype": a.dtype, "job_frames": a.push, "sr": "fsrcnn x2 (fp16 mode)",
+    line = {"tool": "bsvd_online_time --service", "noise_map": a.noise_map, "h": a.h, "w": a.w, "dtype": a.dtype, "job_frames": a.push, "sr": "fsrcnn x2 (fp16 mode)",
             "frames_per_s": {k: [round(v, 1) for v in vs] for k, vs in res.items()},
             "temporal_over_per_frame": round(max(res["temporal"]) / max(res["per_frame"]), 4)}
     if a.scene_cut:
@@ -112,7 +117,7 @@ class HostRingLeg:
         else:
             kw = dict(upscaler_model="fsrcnn", scale=2, fsrcnn_dtype=a.dtype)
         self.svc = HipUpscalerService(denoising=True, denoise_temporal=True, temporal_max_push=a.push, max_streams=S, lr_shape=(a.h, a.w), dtype=a.dtype,
-                                      weights="synthetic", **kw)
+                                      weights="synthetic", noise_map=a.noise_map, **kw)
         self.svc.output_shape = None
         oh, ow = self.svc.out_hw(a.h, a.w)
         self.slots, self.depth, self.frames, self.ids, self.step = a.depth + 2, a.depth, frames_host, list(range(S)), 0
@@ -146,7 +151,9 @@ def gather_kernel(a):
     import ctypes as C
     L, ctx = _capi.lib(), _capi.Context(0)
     assert hasattr(L, "ss4k_dev_op_temporal_gather"), "--gather-kernel needs the dev library (SS4K_LIB)"
-    plane, res = a.h * a.w, {}
+    plane, res, motion = a.h * a.w, {}, {}
+    if a.noise_map == "motion":
+        assert hasattr(L, "ss4k_dev_op_temporal_gather_motion"), "--noise-map motion needs a dev library with the motion gather"
     for k in (4, 16):
         ring = torch.rand(k, 3, plane, device="cuda")
         dst = torch.empty(k, 4, plane, device="cuda")
@@ -158,7 +165,31 @@ def gather_kernel(a):
         for _ in range(20):
             launch()
         torch.cuda.synchronize()
-        res[str(k)] = [round(1000.0 * timed(launch, 200), 2) for _ in range(max(a.runs, 3))]
+        if a.noise_map != "motion":
+            res[str(k)] = [round(1000.0 * timed(launch, 200), 2) for _ in range(max(a.runs, 3))]
+            continue
+        # every frame against a previous frame of its own that differs a little: all but frame 0 (the start bit) get a map
+        before = (ring + 0.01 * torch.rand_like(ring)).clamp_(0, 1)
+        prev = (C.c_void_p * k)(*[before[(j * 5) % k].data_ptr() for j in range(k)])
+        scales = (C.c_float * k)(*[0.35] * k)
+
+        def launch_motion():
+            rc = L.ss4k_dev_op_temporal_gather_motion(ctx._h, src, prev, None, k, a.h, a.w, 1, 0.05, scales, dst.data_ptr(), _capi._stream())
+            assert rc == 0, L.ss4k_last_error()
+        for _ in range(20):
+            launch_motion()
+        torch.cuda.synchronize()
+        res[str(k)], motion[str(k)] = [], []
+        for _ in range(max(a.runs, 3)):   # the two kernels alternate in one session
+            res[str(k)].append(round(1000.0 * timed(launch, 200), 2))
+            motion[str(k)].append(round(1000.0 * timed(launch_motion, 200), 2))
+    if motion:
+        emit(a, {"tool": "bsvd_online_time --gather-kernel --noise-map motion",
+                 "lib": os.path.basename(os.path.dirname(_capi.LIB_PATH)) + "/" + os.path.basename(_capi.LIB_PATH), "h": a.h, "w": a.w,
+                 "us_per_launch_by_frames": {"constant": res, "motion": motion},
+                 "motion_over_constant": {k: round(min(motion[k]) / min(res[k]), 4) for k in res}, "expected_by_planes_moved": round(10 / 7, 4),
+                 "bytes_moved_per_frame": {"constant": 7 * plane * 4, "motion": 10 * plane * 4}})
+        return
     emit(a, {"tool": "bsvd_online_time --gather-kernel", "lib": os.path.basename(os.path.dirname(_capi.LIB_PATH)) + "/" + os.path.basename(_capi.LIB_PATH),
              "h": a.h, "w": a.w, "per_frame_levels": bool(hasattr(L, "ss4k_dev_op_temporal_gather_levels")),
              "us_per_launch_by_frames": res, "bytes_moved_per_frame": 7 * plane * 4})
@@ -173,8 +204,9 @@ def streams(a):
         sr = factory.build_model_fsrcnn(ctx, factor=2, weights="synthetic", dtype=a.dtype)
     dn = factory.build_denoise_model(ctx, weights="synthetic", dtype=a.dtype, variant=a.variant, stream=True)
     lr = (a.h, a.w)
-    objects = [] if a.host_rings else [_capi.TemporalUpscaler(ctx, sr, dn, lr, None, denoise_rate=1.0, max_push=a.push) for _ in range(S)]
-    slots = _capi.TemporalUpscaler(ctx, sr, dn, lr, None, denoise_rate=1.0, max_push=a.push, max_streams=S)
+    more = {"noise_map": a.noise_map} if a.noise_map != "constant" else {}
+    objects = [] if a.host_rings else [_capi.TemporalUpscaler(ctx, sr, dn, lr, None, denoise_rate=1.0, max_push=a.push, **more) for _ in range(S)]
+    slots = _capi.TemporalUpscaler(ctx, sr, dn, lr, None, denoise_rate=1.0, max_push=a.push, max_streams=S, **more)
     frames = torch.randint(0, 256, (S, a.h, a.w, 3), dtype=torch.uint8, device="cuda")
     one = [frames[i:i + 1] for i in range(S)]
     each, ids = [frames[i] for i in range(S)], list(range(S))
@@ -191,7 +223,7 @@ def streams(a):
         for k, f in forms.items():
             res[k].append(1000.0 * S / timed(f, a.iters))
     line = {"tool": "bsvd_online_time --streams", "h": a.h, "w": a.w, "dtype": a.dtype, "variant": a.variant, "sr": a.sr + " x2", "streams": S,
-            "max_push": a.push, "settle_rounds": max(a.warmup, 16), "timed_rounds": a.iters,
+            "noise_map": a.noise_map, "max_push": a.push, "settle_rounds": max(a.warmup, 16), "timed_rounds": a.iters,
             "frames_per_s": {k: [round(v, 2) for v in vs] for k, vs in res.items()},
             "spread_pct": {k: round(100 * (max(vs) - min(vs)) / min(vs), 2) for k, vs in res.items()},
             "rounds_over_objects": round(max(res["rounds"]) / max(res["objects"]), 4),
@@ -235,7 +267,7 @@ def streams_host_rings(a, slots, resident_round, frames):
             sec, ready = leg.run(a.iters)
             assert ready == S * a.iters
             res["host_rings"].append(S * a.iters / sec)
-        emit(a, {"tool": "bsvd_online_time --streams --host-rings", "h": a.h, "w": a.w, "dtype": a.dtype, "variant": a.variant, "sr": a.sr + " x2",
+        emit(a, {"tool": "bsvd_online_time --streams --host-rings", "noise_map": a.noise_map, "h": a.h, "w": a.w, "dtype": a.dtype, "variant": a.variant, "sr": a.sr + " x2",
                  "streams": S, "max_push": a.push, "settle_rounds": settle, "timed_rounds": a.iters, "jobs_in_flight": a.depth,
                  "frames_per_s": {k: [round(v, 2) for v in vs] for k, vs in res.items()},
                  "spread_pct": {k: round(100 * (max(vs) - min(vs)) / min(vs), 2) for k, vs in res.items()},
@@ -261,6 +293,8 @@ def main():
     ap.add_argument("--host-rings", action="store_true", help="with --streams: the same rounds through a started service with pinned host rings, against the resident rounds")
     ap.add_argument("--depth", type=int, default=3, help="--host-rings: jobs in flight")
     ap.add_argument("--gather-kernel", action="store_true", help="instead (dev library): microseconds per launch of tround::gather_planes<4>")
+    ap.add_argument("--noise-map", default="constant", choices=("constant", "motion"),
+                    help="the temporal denoiser's noise map; with --gather-kernel 'motion' times tround::gather_planes_motion against the constant gather")
     a = ap.parse_args()
     if a.gather_kernel:
         return gather_kernel(a)

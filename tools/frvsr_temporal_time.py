@@ -32,6 +32,8 @@ launch moves.  On a library without the padded entry (an A/B through ``SS4K_LIB`
 ``--depth`` jobs in flight, interleaved ``--runs`` times in one session: frames per second either way and ``host_over_resident``.  ``--out-shape
 HxW`` sets the service's and the chain's ``output_shape`` (the x4 frames of 540 x 960 are 24.9 MB each on the way out).
 
+``--noise-map motion`` builds the chain - and ``--host-rings``' service - with the motion-adaptive noise map (``noise_map='motion'``).
+
 Usage:  python tools/frvsr_temporal_time.py [--h 540 --w 960 --dtype f16 --streams 1 4 --iters 24 --runs 3] [--generator egvsr] [--out FILE]
                                             [--scene-cut T [--cut-every N] [--repeats 3]] [--lr-shape 630x1120 --pad]
         python tools/frvsr_temporal_time.py --host-rings --streams 4 [--lr-shape HxW] [--pad] [--out-shape HxW] [--depth 3] [--out FILE]
@@ -136,7 +138,7 @@ class HostRingLeg:
         from sharkshark4k_amd import hostring
         from sharkshark4k_amd.upscale.egvsr_upscaler import HipEgvsrUpscalerService
         self.svc = HipEgvsrUpscalerService(lr_shape=(a.h, a.w), dtype=a.dtype, weights="synthetic", generator=a.generator, denoise_temporal=True,
-                                           temporal_max_push=1, max_streams=S, denoise_pad=a.pad)
+                                           temporal_max_push=1, max_streams=S, denoise_pad=a.pad, denoise_noise_map=a.noise_map)
         self.svc.output_shape = out_shape
         oh, ow = self.svc.out_hw()
         self.slots, self.depth, self.frames, self.ids, self.step = a.depth + 2, a.depth, frames_host, list(range(S)), 0
@@ -170,6 +172,8 @@ def host_rings(a, ctx, model, dn, S, emit):
     out_shape = a.out_shape
     oh, ow = out_shape if out_shape else (4 * a.h, 4 * a.w)
     more = {"pad": True} if a.pad else {}
+    if a.noise_map != "constant":
+        more["noise_map"] = a.noise_map
     chain = _capi.TemporalFrvsrUpscaler(ctx, model, dn, (a.h, a.w), out_shape, max_push=1, max_streams=S, **more)
     frames = torch.randint(0, 256, (S, a.h, a.w, 3), dtype=torch.uint8, device="cuda")
     fr, slots = [frames[i] for i in range(S)], list(range(S))
@@ -263,6 +267,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3, help="--scene-cut: windows per setting")
     ap.add_argument("--kernel-only", action="store_true", help="dev library: the wave kernel's microseconds per launch alone")
     ap.add_argument("--lr-shape", type=hxw, default=None, help="HxW: --h and --w in one word")
+    ap.add_argument("--noise-map", default="constant", choices=("constant", "motion"),
+                    help="the denoiser's noise map: the chain (and --host-rings' service) with the motion-adaptive map")
     ap.add_argument("--pad", action="store_true", help="build the chain with pad=True: any LR shape of at least 8 x 8")
     ap.add_argument("--host-rings", action="store_true", help="the resident rounds against a started service with pinned host rings")
     ap.add_argument("--out-shape", type=hxw, default=None, help="--host-rings: output_shape HxW (default: the generator's x4 frames)")
@@ -301,7 +307,10 @@ def main():
     for S in a.streams:
         frames = torch.randint(0, 256, (S, a.h, a.w, 3), dtype=torch.uint8, device="cuda")
         x4 = torch.rand((S, 1, 4, ph, pw), dtype=torch.float32, device="cuda")   # (the denoiser's shape: the padded one with --pad)
-        chain = _capi.TemporalFrvsrUpscaler(ctx, model, dn, (a.h, a.w), None, max_push=1, max_streams=S, **({"pad": True} if a.pad else {}))
+        more = {"pad": True} if a.pad else {}
+        if a.noise_map != "constant":
+            more["noise_map"] = a.noise_map
+        chain = _capi.TemporalFrvsrUpscaler(ctx, model, dn, (a.h, a.w), None, max_push=1, max_streams=S, **more)
         bare = _capi.FrvsrUpscaler(ctx, model, (a.h, a.w), None, max_streams=S)
         ons = [_capi.BsvdOnline(dn, max_push=1) for _ in range(S)]
         slots = list(range(S))
@@ -333,6 +342,7 @@ def main():
                 res[k].append(timed(fn, a.iters) / S)
         best = {k: min(v) for k, v in res.items()}
         line = {"tool": "frvsr_temporal_time", "h": a.h, "w": a.w, "dtype": a.dtype, "generator": a.generator, "streams": S, "iters": a.iters,
+                "noise_map": a.noise_map,
                 "ms_per_frame": {k: [round(v, 4) for v in vs] for k, vs in res.items()}, "best_ms_per_frame": {k: round(v, 4) for k, v in best.items()},
                 "spread": {k: round(max(v) / min(v), 4) for k, v in res.items()},
                 "chain_over_sum": round(best["chain"] / (best["frvsr"] + best["bsvd"]), 4),
